@@ -11,10 +11,15 @@ is the 1.5 KB query in and the k results out (both included in `value`).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 200 --warmup 20
     python bench.py --gpus 8            # ONE process: the library's own multi-GPU engine (sharded handle)
+    python bench.py --gpus 1 --full     # + checks, roofline, CPU baseline and the secondary configurations
+    python bench.py --gpus 1 --dump-outputs DIR     # + the last timed step's ids / scores as DIR/*.npy
 
-Rank 0 prints ONE JSON line (contract in the task statement):
+Rank 0 prints ONE JSON line. A plain run carries the headline only: it sets up, warms up, times exactly --steps steps
+(`ms_per_step` = the timed region / steps), writes its outputs where --dump-outputs asks, and prints
   `value`        whole-job queries/s of the timed region, run the way the product runs: queries software-pipelined over two
-                 streams, scans free to overlap ("scan_chain" auto: no event chain while kernels are not being timed);
+                 streams, scans free to overlap ("scan_chain" auto: no event chain while kernels are not being timed).
+With --full the run also checks that a stored row retrieves itself (and, in the one-process multi-GPU shape, the first-contact
+preflight), and the line adds
   `roofline`     achieved HBM GB/s of the scan kernel against the 8 TB/s MI355X peak. `frac` is PER LAUNCH: HIP events on
                  every scan-kernel launch, on the stream the kernel runs on, in calibration passes of the SAME run right
                  after the timed region (same engine, same queries, kernels chained so that a launch runs alone): the event
@@ -89,6 +94,14 @@ def parse_args():
     p.add_argument("--traffic-child-batch", default=None, help=argparse.SUPPRESS)   # "nq:corpus:row_base": the batched form of the child
     p.add_argument("--detail-out", default=None, metavar="PATH",
                    help="where the verbose record goes (default bench_detail.json next to bench.py); stdout carries ONE compact line")
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline figure: the untimed self-retrieval and first-contact checks, the per-launch "
+                        "calibration passes and `roofline` (stream-read peak, counter pass), the CPU baseline and the secondary "
+                        "configurations. Without it a run sets up, warms up, times --steps steps, dumps its outputs (--dump-outputs) "
+                        "and prints the line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                        "(ids.npy as float64, scores.npy as float32); the inputs are seeded, so runs with the same arguments compare output for output")
     p.add_argument("--host-merge", action="store_true", help="N>1: merge gathered hits on the host instead of the device")
     p.add_argument("--exchange", choices=["rccl", "host", "tickets"], default=None,
                    help="N>1, one rank per GPU (torchrun): rccl = all-gather device buffers over RCCL (default); host = download + gloo "
@@ -316,6 +329,17 @@ def cpu_baseline_small(torch, dev, rows, dims, topk, queries, seconds=3.0):
 CALIBRATION_STEPS = 60
 
 
+def dump_outputs(out_dir, ids, scores):
+    """--dump-outputs: the last timed step's answer as its caller receives it (the ids and scores of the top-k hits, best first).
+    Ids are uint64 row keys (< 2**53), exact in float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"ids": np.asarray(ids, dtype=np.uint64).astype(np.float64),
+              "scores": np.asarray(scores, dtype=np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def run_pipelined(submit, collect, qs, depth):
     pending = []
     last = None
@@ -328,9 +352,11 @@ def run_pipelined(submit, collect, qs, depth):
     return last
 
 
-def measure_single_query(eng, submit, collect, queries, warmup, steps, depth, barrier, chain_timed_region=False, floor_ms=0.0):
-    """warm-up, then EXACTLY `steps` timed steps bracketed by barrier(); then the per-launch calibration pass.
-    Returns (elapsed_s, last_result, kernel_avg_ms, launches_timed, calibration dict)."""
+def measure_single_query(eng, submit, collect, queries, warmup, steps, depth, barrier, chain_timed_region=False, floor_ms=0.0,
+                         calibrate=True):
+    """warm-up, then EXACTLY `steps` timed steps bracketed by barrier(); then (calibrate) the per-launch calibration pass.
+    Returns (elapsed_s, last_result, kernel_avg_ms, launches_timed, calibration dict); without calibration the last three are
+    (nan, 0, None) unless the timed region itself timed its kernels (chain_timed_region)."""
     eng.setTuning("time_kernels", 1 if chain_timed_region else 0)
     run_pipelined(submit, collect, queries[:warmup], depth)
     eng.setTuning("reset_stats", 1)
@@ -345,6 +371,8 @@ def measure_single_query(eng, submit, collect, queries, warmup, steps, depth, ba
         kern_ms = st.scan_kernel_ms_total / launches if launches else float("nan")
         return elapsed, last, kern_ms, launches, {"steps": steps, "ms_per_step": elapsed / steps * 1e3,
                                                   "mode": "the timed region itself (--chain-timed-region: kernels timed and chained inside it)"}
+    if not calibrate:
+        return elapsed, last, float("nan"), 0, None
     # calibration: the same queries again with HIP events on every scan launch, on the stream the kernel runs on, scans chained
     # through an event so that a launch runs alone. Two passes:
     #   "time_kernels" = 1 (bracketed): hipEventRecord in front of and behind the launch — the interval holds the kernel AND the
@@ -1376,7 +1404,7 @@ def main():
     if in_library:
         same = bool(os.environ.get("WAX_BENCH_SAME_DEVICE"))          # testing only: every shard on GPU 0
         devs = [0 if same else g for g in range(args.gpus)]
-        preflight = handle_preflight(torch, devs)
+        preflight = handle_preflight(torch, devs) if args.full else None
         eng = _load_handle(torch, devs, n, dims)                       # block layout chosen by the library (ceil(n / N) rows per shard at this size)
         shard_rows = [int(eng.shardInfo(g)[2]) for g in range(args.gpus)]
         lo, hi = 0, max(shard_rows)                                     # rows per launch of ONE shard's scan kernel (roofline)
@@ -1392,12 +1420,6 @@ def main():
 
     total = args.warmup + args.steps
     queries = unit_queries(max(total, 8), dims)
-
-    # untimed sanity check: a stored row must retrieve itself
-    probe_row = min(n - 1, 123457)
-    probe = None
-    for r0, x in device_rows(torch, probe_row, probe_row + 1, dims, dev):
-        probe = x[0].cpu().numpy()
 
     apply_tunes(eng)
     if in_library:
@@ -1427,9 +1449,15 @@ def main():
         def collect(_):
             return searcher.collect()
 
-    ids, scores = collect(submit(probe))
-    if not (solo and rank != 0):
-        assert int(ids[0]) == probe_row and abs(float(scores[0]) - 1.0) < 1e-5, (ids[:3], scores[:3])
+    if args.full:
+        # untimed sanity check: a stored row must retrieve itself
+        probe_row = min(n - 1, 123457)
+        probe = None
+        for r0, x in device_rows(torch, probe_row, probe_row + 1, dims, dev):
+            probe = x[0].cpu().numpy()
+        ids, scores = collect(submit(probe))
+        if not (solo and rank != 0):
+            assert int(ids[0]) == probe_row and abs(float(scores[0]) - 1.0) < 1e-5, (ids[:3], scores[:3])
 
     def barrier():
         torch.cuda.synchronize()
@@ -1445,16 +1473,20 @@ def main():
     gc.disable()
     elapsed, last, kern_ms, launches, cal = measure_single_query(eng, submit, collect, queries, args.warmup, args.steps, args.depth,
                                                                  barrier, chain_timed_region=args.chain_timed_region,
-                                                                 floor_ms=max(hi - lo, 0) * dims * 4 / (HBM_PEAK_GBPS * 1e9) * 1e3)
+                                                                 floor_ms=max(hi - lo, 0) * dims * 4 / (HBM_PEAK_GBPS * 1e9) * 1e3,
+                                                                 calibrate=args.full)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if use_rccl else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert len(last[0]) == (min(k, n) if not (solo and rank != 0) else 0)
+    if args.dump_outputs and rank == 0:
+        names = dump_outputs(args.dump_outputs, last[0], last[1])
+        log(f"[bench] last timed step's outputs written to {args.dump_outputs}: {', '.join(names)}")
     # the node's own streaming-read rate over the same slab ("both denominators"): the library's microbenchmark —
     # every float4 of the store summed, no selection — timed with HIP events right behind the timed region, on this engine
     stream_read_gbps = None
-    if not in_library and hi > lo:
+    if args.full and not in_library and hi > lo:
         try:
             ms_sr = eng.timeStreamRead(10)
             if ms_sr and ms_sr > 0:
@@ -1476,13 +1508,13 @@ def main():
         traffic, traffic_source = None, None
         tpath = os.path.join(ROOT, "profiles", "latest_traffic.json")
         live_note = None
-        if args.traffic in ("auto", "live") and world == 1 and not in_library:
+        if args.full and args.traffic in ("auto", "live") and world == 1 and not in_library:
             traffic, live_note = live_traffic(n, dims, k)
             if traffic is not None:
                 traffic_source = live_note
             else:
                 log(f"[bench] live traffic pass unavailable: {live_note}")
-        if traffic is None and args.traffic in ("auto", "replay") and os.path.exists(tpath):
+        if args.full and traffic is None and args.traffic in ("auto", "replay") and os.path.exists(tpath):
             try:
                 tj = json.load(open(tpath))
                 if tj.get("rows_per_launch") == hi - lo and tj.get("dims") == dims:
@@ -1536,20 +1568,21 @@ def main():
                              (("rccl all_gather" if use_rccl else ("host (gloo)" + (f" (rccl failed: {RCCL_FAILURE[0]})" if RCCL_FAILURE[0] else ""))) if world > 1 else "none")),
                 "last_result_checksum": checksum,
             },
-            "roofline": scan_roofline(bytes_per_launch, kern_ms, launches, elapsed, args.steps, cal, traffic, traffic_source),
         }
+        if args.full:
+            out["roofline"] = scan_roofline(bytes_per_launch, kern_ms, launches, elapsed, args.steps, cal, traffic, traffic_source)
         if preflight is not None:
             out["config"]["preflight"] = preflight
-        if stream_read_gbps and out["roofline"].get("achieved"):
+        if stream_read_gbps and out.get("roofline", {}).get("achieved"):
             out["roofline"]["peak_measured"] = stream_read_gbps          # GB/s: the second denominator, measured in this run on this GPU
             out["roofline"]["frac_of_measured"] = out["roofline"]["achieved"] / stream_read_gbps
             out["roofline"]["peak_measured_note"] = ("wax_hip_time_stream_read: 10 passes of a read-only float4 sum over the same slab, HIP events; "
                                                      "`peak` stays the 8 TB/s spec the contract names")
-        if world == 1 and not in_library and not args.no_cpu_baseline:
+        if args.full and world == 1 and not in_library and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(torch, args, dev, queries)
-        elif world == 1:
+        elif args.full and world == 1:
             out["cpu_baseline"] = None
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         # the other BASELINE configurations, timed after the headline (its engine is released first)
         gc.enable()
         eng.close()

@@ -32,6 +32,7 @@ def test_one_rank_per_gpu_shape_falls_back_to_gloo_when_rccl_is_unusable(fake, t
     procs = []
     for rank in range(2):
         env = dict(os.environ, RANK=str(rank), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WAX_OUT=out, OMP_NUM_THREADS="1")
+        env["HIP_VISIBLE_DEVICES"] = "-1"         # no GPU for the ranks, also on a GPU node (there both would land on one device)
         if fake:
             env["WAX_BENCH_FAKE_RCCL_FAILURE"] = "1"
         procs.append(subprocess.Popen([sys.executable, os.path.join(HERE, "_init_worker.py")], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))

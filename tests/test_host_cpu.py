@@ -412,6 +412,25 @@ def test_bench_line_stays_inside_the_drivers_stdout_tail(tmp_path, capsys):
     assert len(out) < 4096 and "secondary_dropped" in j and j["roofline"]["frac"] and j["cpu_baseline"]["cores"] == 16
 
 
+def test_bench_plain_run_is_lean_by_default_and_dumps_float_arrays(tmp_path, monkeypatch):
+    """`--full` (checks, roofline, CPU baseline, secondaries) is off unless asked for; `--dump-outputs DIR` writes the last step's
+    answer as DIR/ids.npy (float64, exact for uint64 row keys below 2**53) and DIR/scores.npy (float32)."""
+    import sys
+    bench = _load_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse_args()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path / "d")])
+    a = bench.parse_args()
+    assert a.full is True and a.dump_outputs == str(tmp_path / "d")
+    ids = np.array([9_999_999, 123_457, 2**52 + 1], dtype=np.uint64)
+    scores = np.array([0.5, 0.25, -0.125], dtype=np.float32)
+    assert bench.dump_outputs(a.dump_outputs, ids, scores) == ["ids", "scores"]
+    got_ids, got_scores = np.load(tmp_path / "d" / "ids.npy"), np.load(tmp_path / "d" / "scores.npy")
+    assert got_ids.dtype == np.float64 and np.array_equal(got_ids.astype(np.uint64), ids)
+    assert got_scores.dtype == np.float32 and np.array_equal(got_scores, scores)
+
+
 def test_bench_line_carries_the_event_mode_and_the_bracketed_figure():
     """Round 5: `frac` is priced with kernel-bound HIP events (hipExtLaunchKernel start / stop pair on the dispatch); the line says
     which events it used and carries the bracketed mean (hipEventRecord around the launch) beside it; the plausibility rule that

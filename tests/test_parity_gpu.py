@@ -951,13 +951,14 @@ def test_batched_full_size_parity_on_one_gpu(wax, n, dims, nq, n_check):
 # global-row keys, pipelined ShardedSearcher, merge, barriers, max-over-ranks timing) is the code the
 # driver runs with --gpus N over RCCL.
 
-def _run_bench(nproc, extra, tmp_path, one_process=False, cpu=False):
+def _run_bench(nproc, extra, tmp_path, one_process=False, cpu=False, full=True):
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--rows", "300000", "--steps", "12", "--warmup", "2", "--c5-rows", "300000"] + ([] if cpu else ["--no-cpu-baseline"]) + extra
+    common = (["--rows", "300000", "--steps", "12", "--warmup", "2", "--c5-rows", "300000"] + (["--full"] if full else [])
+              + ([] if cpu else ["--no-cpu-baseline"]) + extra)
     env = dict(os.environ)
     env.pop("WAX_HIP_SHARD_MIN_MB", None)          # the bench runs with the library's defaults
     if nproc == 1 or one_process:
@@ -980,13 +981,37 @@ def _run_bench(nproc, extra, tmp_path, one_process=False, cpu=False):
     line = json.loads(last)
     full = json.load(open(detail))
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
-                "dtype", "data", "config", "roofline"):
+                "dtype", "data", "config") + (("roofline",) if "--full" in cmd else ()):
         assert key in line, key
     assert abs(line["value"] - full["value"]) <= 1e-5 * full["value"] and line["config"]["checksum"] == full["config"]["last_result_checksum"]
-    assert abs(line["roofline"]["frac"] - full["roofline"]["frac"]) < 1e-5 and line["roofline"]["kernel"] == "wax::scan_kernel"
+    if "--full" in cmd:
+        assert abs(line["roofline"]["frac"] - full["roofline"]["frac"]) < 1e-5 and line["roofline"]["kernel"] == "wax::scan_kernel"
     assert [x["name"] for x in line.get("secondary", [])] == [x["name"] for x in full.get("secondary", [])]
     full["_line"] = line
     return full
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_outputs(wax, tmp_path):
+    """Without --full the run times exactly --steps steps and prints the headline: no roofline, CPU baseline or secondaries.
+    --dump-outputs writes the last timed step's ids / scores, the very answer the line's checksum was taken over, and a second run
+    with the same arguments computes the same arrays."""
+    import os
+    dumps = [str(tmp_path / f"out{i}") for i in range(2)]
+    runs = [_run_bench(1, ["--dump-outputs", d], tmp_path, full=False) for d in dumps]
+    run = runs[0]
+    assert run["steps"] == 12 and run["warmup"] == 2 and run["dtype"] == "f32" and run["higher_is_better"] is True
+    assert abs(run["value"] - 12 / (run["ms_per_step"] * 12e-3)) < 1e-6 * run["value"]
+    for key in ("roofline", "cpu_baseline", "secondary"):
+        assert key not in run and key not in run["_line"], key
+    assert "preflight" not in run["config"]
+    ids, scores = (np.load(os.path.join(dumps[0], n + ".npy")) for n in ("ids", "scores"))
+    assert ids.dtype == np.float64 and scores.dtype == np.float32 and ids.shape == scores.shape == (10,)
+    ck = hashlib.sha256(ids.astype(np.uint64).tobytes() + scores.tobytes()).hexdigest()[:16]
+    assert ck == run["config"]["last_result_checksum"]
+    assert np.all(np.diff(scores) <= 0) and len(set(ids.tolist())) == 10
+    for n in ("ids", "scores"):
+        assert np.array_equal(np.load(os.path.join(dumps[1], n + ".npy")), np.load(os.path.join(dumps[0], n + ".npy"))), n
+    assert runs[1]["config"]["last_result_checksum"] == ck
 
 
 def test_bench_contract_and_shard_invariance(wax, tmp_path):

@@ -3,7 +3,9 @@ christopherkarani/Wax (CosineDistance.metal, TopKReduction.metal) executed on th
 files compile unchanged as C++ against a stand-in for <metal_stdlib>; threads of a threadgroup are fibers).
 
 tests/golden/metal_shader_vectors.json (made by oracle/gen_metal_golden.py where the reference checkout exists) carries inputs and
-outputs, so these checks run everywhere; the live comparisons run only where oracle/_ref can be built (they skip on the GPU box)."""
+outputs, so these checks run everywhere. The checks that compare with the shaders on inputs of their own take the shaders' outputs from
+tests/golden/metal_shader_recorded_runs.json (gen_metal_golden.py --recorded-runs); where oracle/_ref can be built they also run the
+shaders live and require the recording to be what they compute."""
 import base64
 import json
 import os
@@ -42,6 +44,16 @@ def wax(hip_lib):
 @pytest.fixture(scope="module")
 def golden():
     return json.load(open(os.path.join(GOLDEN, "metal_shader_vectors.json")))
+
+
+@pytest.fixture(scope="module")
+def recorded():
+    return json.load(open(os.path.join(GOLDEN, "metal_shader_recorded_runs.json")))
+
+
+def _live():
+    """oracle/_ref where the reference checkout exists (it then also checks the recording), else None."""
+    return oracle.ref_lib()
 
 
 def test_oracle_metal_mode_is_bit_identical_to_the_reference_shaders(golden):
@@ -108,50 +120,68 @@ def test_reference_reduction_loop_has_fixed_points_above_k_128(golden):
     assert got == {(1500, 129): False, (1500, 200): False, (1500, 256): False, (5000, 130): False}
 
 
-def test_live_reference_shaders_against_the_oracle_on_random_shapes():
-    if oracle.ref_lib() is None:
-        pytest.skip("oracle/_ref is only built where the reference checkout exists")
-    rng = np.random.default_rng(5)
-    for dims in (1, 3, 4, 7, 8, 64, 383, 384, 385, 390, 391, 1024):
-        n = 256 * int(rng.integers(0, 3)) + int(rng.integers(max(1, (dims + 3) // 4), 257))   # last threadgroup loads the whole query
-        x = rng.standard_normal((n, dims)).astype(np.float32)
-        q = rng.standard_normal(dims).astype(np.float32)
+def test_live_reference_shaders_against_the_oracle_on_random_shapes(recorded):
+    from oracle.gen_metal_golden import RANDOM_TOPK_KS, random_shape_inputs, sha16
+    live = _live()
+    shapes, d = random_shape_inputs()             # last threadgroups load the whole query
+    assert len(shapes) == len(recorded["random_shapes"])
+    for (dims, x, q), rec in zip(shapes, recorded["random_shapes"]):
+        n = x.shape[0]
+        assert (rec["dims"], rec["rows"], rec["input_sha16"]) == (dims, n, sha16(x, q)), "the random inputs are not the recorded ones"
         for simd8 in (False, True):
-            got = oracle.ref_metal_distances(x, q, simd8=simd8)
+            got = _arr(rec["simd8" if simd8 else "simd4"], np.float32)
+            if live is not None:
+                assert np.array_equal(oracle.ref_metal_distances(x, q, simd8=simd8).view(np.uint32), got.view(np.uint32)), (dims, n, simd8)
             # the oracle picks the kernel by the engine's rule (D >= 384); compare like with like
             if simd8 == (dims >= 384):
                 want = oracle.distances(oracle.METRIC_COSINE, x, q, mode=oracle.MODE_METAL_F32)
                 assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (dims, n, simd8)
-    d = rng.standard_normal(4000).astype(np.float32)
-    for k in (1, 2, 10, 63, 64, 65, 127, 128):
-        idx, dist, passes = oracle.ref_metal_topk(d, k)
+    rt = recorded["random_topk"]
+    assert rt["input_sha16"] == sha16(d) and [r["k"] for r in rt["results"]] == list(RANDOM_TOPK_KS)
+    for r in rt["results"]:
+        k = r["k"]
+        idx, dist = _arr(r["indices"], np.uint32), _arr(r["distances"], np.float32)
+        if live is not None:
+            l_idx, l_dist, l_passes = oracle.ref_metal_topk(d, k)
+            assert np.array_equal(l_idx, idx) and np.array_equal(l_dist, dist) and l_passes == r["passes"], k
         o_idx, o_dist = oracle.topk_heap(d, k, total=True)
         assert np.array_equal(idx, np.asarray(o_idx).astype(np.uint32)) and np.array_equal(dist, np.asarray(o_dist, dtype=np.float32))
-    with pytest.raises(oracle.NonTermination):
-        oracle.ref_metal_topk(d, 200)
+    assert rt["k200_terminates"] is False
+    if live is not None:
+        with pytest.raises(oracle.NonTermination):
+            oracle.ref_metal_topk(d, 200)
 
 
-def test_golden_file_is_what_the_generator_produces_here(golden):
-    """Where the reference checkout exists, regenerate one case and compare with the committed fixture (a stale fixture would
-    otherwise go unnoticed)."""
-    if oracle.ref_lib() is None:
-        pytest.skip("oracle/_ref is only built where the reference checkout exists")
+def test_golden_file_is_what_the_generator_produces_here(golden, recorded):
+    """The committed fixture against the reference's outputs for the same cases, recorded by a separate run (and, where the
+    reference checkout exists, regenerated live): a stale fixture would otherwise go unnoticed."""
+    from oracle.gen_metal_golden import sha16
+    live = _live()
+    rec = {(r["seed"], r["dims"]): r for r in recorded["fixture_distance_cases"]}
+    assert len(rec) == len(golden["distance_cases"])
     for c in golden["distance_cases"]:
         x, q = _inputs(c)
-        assert np.array_equal(oracle.ref_metal_distances(x, q).view(np.uint32), _arr(c["distances"], np.float32).view(np.uint32)), c["dims"]
+        want = _arr(c["distances"], np.float32)
+        r = rec[(c["seed"], c["dims"])]
+        assert r["input_sha16"] == sha16(x, q) and r["distances_sha16"] == sha16(want), c["dims"]
+        if live is not None:
+            assert np.array_equal(oracle.ref_metal_distances(x, q).view(np.uint32), want.view(np.uint32)), c["dims"]
 
 
-def test_reference_kernels_load_the_query_with_live_threads_only():
+def test_reference_kernels_load_the_query_with_live_threads_only(recorded):
     """Recorded while pinning the reference: both SIMD kernels return on `vectorIndex >= vectorCount` BEFORE the cooperative
     load of the query into threadgroup memory (CosineDistance.metal:165-167 / :246-248 ahead of :176-184 / :259-266), so a last
     threadgroup with fewer rows than D / 4 leaves part of the query unloaded and its rows are scored against whatever the
     threadgroup memory held (oracle/_ref poisons it with NaN). 24 rows x 384 dims: 24 live threads load 24 of the 96 float4; a
     store of 256 + 24 rows gets 256 good rows and 24 undefined ones. The oracle (and the HIP engine) score every row against
     the whole query."""
-    if oracle.ref_lib() is None:
-        pytest.skip("oracle/_ref is only built where the reference checkout exists")
+    from oracle.gen_metal_golden import sha16
     x, q = oracle.formula_rows(3, 280, 384), oracle.formula_unit_query(3, 384)
-    shader = oracle.ref_metal_distances(x, q)
+    rec = recorded["query_load_case"]
+    assert (rec["rows"], rec["dims"], rec["input_sha16"]) == (280, 384, sha16(x, q))
+    shader = _arr(rec["distances"], np.float32)
+    if _live() is not None:
+        assert np.array_equal(oracle.ref_metal_distances(x, q).view(np.uint32), shader.view(np.uint32))
     full = oracle.distances(oracle.METRIC_COSINE, x, q, mode=oracle.MODE_METAL_F32)
     assert np.array_equal(shader[:256].view(np.uint32), full[:256].view(np.uint32))     # a full threadgroup: defined
     assert np.all(np.isnan(shader[256:])) and np.all(np.isfinite(full[256:]))           # 24 live threads, 96 float4 to load

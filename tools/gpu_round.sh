@@ -28,7 +28,7 @@ for s in $STAGES; do
       timeout 900 python -m pytest tests -m gpu -q -x -rf --durations=10 -p no:cacheprovider --timeout 400 \
           -k "onepass or batch_mfma or randomised_soak or variants_agree or edge_shapes or special_values or dot_and_l2" > "$OUT/pytest_onepass.log" 2>&1; rc=$? ;;
     benchsec)
-      timeout 600 python bench.py --gpus 1 --no-cpu-baseline --steps 60 --warmup 10 --secondary ${WAX_SEC:-b1m_q256,clustered_k100,dups17} > "$OUT/bench_sec.json" 2> "$OUT/bench_sec.err"; rc=$? ;;
+      timeout 600 python bench.py --full --gpus 1 --no-cpu-baseline --steps 60 --warmup 10 --secondary ${WAX_SEC:-b1m_q256,clustered_k100,dups17} > "$OUT/bench_sec.json" 2> "$OUT/bench_sec.err"; rc=$? ;;
     multiscan)
       timeout 600 python tools/multiscan_bench.py --dims ${WAX_DIMS:-384 768} > "$OUT/multiscan_bench.jsonl" 2> "$OUT/multiscan_bench.err"; rc=$?
       (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_ms" -o ms -- \
@@ -55,23 +55,23 @@ for s in $STAGES; do
     cpusweep)
       timeout 300 python tools/cpu_sweep.py > "$OUT/cpu_sweep.json" 2> "$OUT/cpu_sweep.err"; rc=$? ;;
     bench)
-      timeout 900 python bench.py --gpus 1 > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$? ;;
+      timeout 900 python bench.py --full --gpus 1 > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$? ;;
     prof)
       (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_stats" -o bench -- \
-          python "$R/bench.py" --gpus 1 --steps 100 --warmup 10 --no-cpu-baseline > "$OUT/prof_bench.json" 2> "$OUT/prof.err"); rc=$?
+          python "$R/bench.py" --full --gpus 1 --steps 100 --warmup 10 --no-cpu-baseline > "$OUT/prof_bench.json" 2> "$OUT/prof.err"); rc=$?
       find "$OUT/prof_stats" -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats.csv" \; 2>/dev/null
       find "$OUT/prof_stats" -name "*kernel_trace.csv" -exec sh -c 'head -400 "$1" > "$2"' _ {} "$OUT/kernel_trace_head.csv" \; 2>/dev/null
       find "$OUT/prof_stats" -name "*kernel_trace.csv" -delete 2>/dev/null ;;
     pmc)
       (cd /tmp && timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/prof_pmc" -o pmc -- \
-          python "$R/bench.py" --gpus 1 --steps 20 --warmup 2 --no-cpu-baseline --no-secondary > "$OUT/pmc_bench.json" 2> "$OUT/pmc.err"); rc=$?
+          python "$R/bench.py" --full --gpus 1 --steps 20 --warmup 2 --no-cpu-baseline --no-secondary > "$OUT/pmc_bench.json" 2> "$OUT/pmc.err"); rc=$?
       python tools/pmc_summary.py "$OUT/prof_pmc" > "$OUT/pmc_summary.json" 2>> "$OUT/pmc.err"
       find "$OUT/prof_pmc" -name "*.csv" -size +2M -delete 2>/dev/null ;;
     batch)
       timeout 900 python tools/batch_bench.py --nq 64 256 1024 > "$OUT/batch_bench.log" 2>&1; rc=$? ;;
     trace1m)
       (cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d "$OUT/prof_1m" -o g -- \
-          python "$R/bench.py" --gpus 1 --rows ${WAX_ROWS:-1000000} --steps 60 --warmup 10 --no-cpu-baseline > "$OUT/trace1m_bench.json" 2> "$OUT/trace1m.err"); rc=$?
+          python "$R/bench.py" --full --gpus 1 --rows ${WAX_ROWS:-1000000} --steps 60 --warmup 10 --no-cpu-baseline > "$OUT/trace1m_bench.json" 2> "$OUT/trace1m.err"); rc=$?
       f=$(find "$OUT/prof_1m" -name "*kernel_trace.csv" | head -1)
       [ -n "$f" ] && python "$R/tools/trace_tail.py" "$f" 40 > "$OUT/trace1m_tail.csv" 2>/dev/null
       find "$OUT/prof_1m" -name "*kernel_trace.csv" -delete 2>/dev/null ;;
@@ -81,14 +81,14 @@ for s in $STAGES; do
       WAX_HIP_BATCH_TRACE=1 timeout 300 python tools/batch_bench.py --nq 256 1024 --reps 3 > "$OUT/hosttrace.log" 2>&1; rc=$? ;;
     profdefault)
       (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_default" -o bench -- \
-          python "$R/bench.py" --gpus 1 > "$OUT/profdefault_bench.json" 2> "$OUT/profdefault.err"); rc=$?
+          python "$R/bench.py" --full --gpus 1 > "$OUT/profdefault_bench.json" 2> "$OUT/profdefault.err"); rc=$?
       find "$OUT/prof_default" -name "*kernel_stats.csv" -exec cp {} "$OUT/default_kernel_stats.csv" \; 2>/dev/null
       f=$(find "$OUT/prof_default" -name "*kernel_trace.csv" | head -1)
       [ -n "$f" ] && python "$R/tools/split_kernel_trace.py" "$f" > "$OUT/default_kernel_stats_split.csv" 2>/dev/null
       find "$OUT/prof_default" -name "*kernel_trace.csv" -delete 2>/dev/null
       # the headline alone (no secondary configurations): scan_kernel's --stats row is then one workload
       (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_headline" -o bench -- \
-          python "$R/bench.py" --gpus 1 --no-secondary --no-cpu-baseline > "$OUT/profheadline_bench.json" 2> "$OUT/profheadline.err")
+          python "$R/bench.py" --full --gpus 1 --no-secondary --no-cpu-baseline > "$OUT/profheadline_bench.json" 2> "$OUT/profheadline.err")
       find "$OUT/prof_headline" -name "*kernel_stats.csv" -exec cp {} "$OUT/headline_kernel_stats.csv" \; 2>/dev/null
       find "$OUT/prof_headline" -name "*kernel_trace.csv" -delete 2>/dev/null ;;
     batchprof)
@@ -99,11 +99,11 @@ for s in $STAGES; do
       find "$OUT/prof_batch" -name "*kernel_trace.csv" -delete 2>/dev/null ;;
     multi)
       # N>1 code path on a 1-GPU box: two ranks share GPU 0, exchange over gloo (RCCL refuses duplicate GPUs).
-      timeout 600 python bench.py --gpus 1 --rows 2000000 --steps 50 --warmup 5 --no-cpu-baseline > "$OUT/multi_n1.json" 2> "$OUT/multi_n1.err"
+      timeout 600 python bench.py --full --gpus 1 --rows 2000000 --steps 50 --warmup 5 --no-cpu-baseline > "$OUT/multi_n1.json" 2> "$OUT/multi_n1.err"
       WAX_BENCH_SAME_DEVICE=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 \
-          bench.py --gpus 2 --rows 2000000 --steps 50 --warmup 5 --exchange host > "$OUT/multi_n2_host.json" 2> "$OUT/multi_n2_host.err"; rc=$?
+          bench.py --full --gpus 2 --rows 2000000 --steps 50 --warmup 5 --exchange host > "$OUT/multi_n2_host.json" 2> "$OUT/multi_n2_host.err"; rc=$?
       WAX_BENCH_SAME_DEVICE=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 3 --master-addr 127.0.0.1 --master-port 29512 \
-          bench.py --gpus 3 --rows 2000000 --steps 50 --warmup 5 --exchange host > "$OUT/multi_n3_host.json" 2> "$OUT/multi_n3_host.err"
+          bench.py --full --gpus 3 --rows 2000000 --steps 50 --warmup 5 --exchange host > "$OUT/multi_n3_host.json" 2> "$OUT/multi_n3_host.err"
       timeout 300 python tools/shard_overhead.py > "$OUT/shard_overhead.log" 2>&1
       timeout 300 python tools/batch_bench.py --rows 2000000 --nq 256 --reps 3 > "$OUT/multi_batch_n1.json" 2> "$OUT/multi_batch_n1.err"
       WAX_BENCH_SAME_DEVICE=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29513 \
@@ -137,22 +137,22 @@ PYEOF
     gridsweep)
       # scan grid / pipeline depth under the overlapped product mode (value and pipeline_frac are what moves; frac is per launch)
       for g in 256 384 512 768 1024; do
-        timeout 300 python bench.py --gpus 1 --no-cpu-baseline --no-secondary --steps 150 --warmup 20 --tune grid_blocks=$g >> "$OUT/gridsweep_10m.jsonl" 2>> "$OUT/gridsweep.err"
-        timeout 300 python bench.py --gpus 1 --rows 1000000 --no-cpu-baseline --no-secondary --steps 600 --warmup 50 --tune grid_blocks=$g >> "$OUT/gridsweep_1m.jsonl" 2>> "$OUT/gridsweep.err"
+        timeout 300 python bench.py --full --gpus 1 --no-cpu-baseline --no-secondary --steps 150 --warmup 20 --tune grid_blocks=$g >> "$OUT/gridsweep_10m.jsonl" 2>> "$OUT/gridsweep.err"
+        timeout 300 python bench.py --full --gpus 1 --rows 1000000 --no-cpu-baseline --no-secondary --steps 600 --warmup 50 --tune grid_blocks=$g >> "$OUT/gridsweep_1m.jsonl" 2>> "$OUT/gridsweep.err"
       done
       for d in 2 3 6 8; do
-        timeout 300 python bench.py --gpus 1 --rows 1000000 --no-cpu-baseline --no-secondary --steps 600 --warmup 50 --depth $d >> "$OUT/depthsweep_1m.jsonl" 2>> "$OUT/gridsweep.err"
+        timeout 300 python bench.py --full --gpus 1 --rows 1000000 --no-cpu-baseline --no-secondary --steps 600 --warmup 50 --depth $d >> "$OUT/depthsweep_1m.jsonl" 2>> "$OUT/gridsweep.err"
       done; rc=$? ;;
     profchain)
       # the headline with every scan of the timed region chained and timed (one kernel at a time): the run whose rocprofv3 average
       # the per-launch `roofline.frac` of the default command (calibration pass) is compared with
       (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_chain" -o bench -- \
-          python "$R/bench.py" --gpus 1 --chain-timed-region --no-secondary --no-cpu-baseline > "$OUT/profchain_bench.json" 2> "$OUT/profchain.err"); rc=$?
+          python "$R/bench.py" --full --gpus 1 --chain-timed-region --no-secondary --no-cpu-baseline > "$OUT/profchain_bench.json" 2> "$OUT/profchain.err"); rc=$?
       find "$OUT/prof_chain" -name "*kernel_stats.csv" -exec cp {} "$OUT/chained_kernel_stats.csv" \; 2>/dev/null
       find "$OUT/prof_chain" -name "*kernel_trace.csv" -delete 2>/dev/null ;;
     pmc1m)
       (cd /tmp && timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/prof_pmc1m" -o pmc -- \
-          python "$R/bench.py" --gpus 1 --rows 1000000 --steps 40 --warmup 4 --no-cpu-baseline --no-secondary > "$OUT/pmc1m_bench.json" 2> "$OUT/pmc1m.err"); rc=$?
+          python "$R/bench.py" --full --gpus 1 --rows 1000000 --steps 40 --warmup 4 --no-cpu-baseline --no-secondary > "$OUT/pmc1m_bench.json" 2> "$OUT/pmc1m.err"); rc=$?
       python tools/pmc_summary.py "$OUT/prof_pmc1m" > "$OUT/pmc1m_summary.json" 2>> "$OUT/pmc1m.err"
       find "$OUT/prof_pmc1m" -name "*.csv" -size +2M -delete 2>/dev/null ;;
     onepassprof)

@@ -25,7 +25,7 @@ for rows in ${WAX_SCALE_ROWS:-10000 1000000 10000000}; do
     if [ "$rows" -eq 10000000 ]; then
       if [ "$g" -eq 1 ]; then sec=(--secondary c5_full); else sec=(--secondary c5); fi
     fi
-    common=(--gpus "$g" --rows "$rows" --steps "$steps" --warmup 20 --no-cpu-baseline --detail-out "$OUT.detail_${rows}_${g}.json" "${sec[@]}")
+    common=(--full --gpus "$g" --rows "$rows" --steps "$steps" --warmup 20 --no-cpu-baseline --detail-out "$OUT.detail_${rows}_${g}.json" "${sec[@]}")
     if [ "$g" -eq 1 ]; then
       python "$R/bench.py" "${common[@]}" >> "$OUT" 2>> "$OUT.err"
     else

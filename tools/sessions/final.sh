@@ -27,17 +27,17 @@ timeout 600 python __graft_entry__.py --smoke > "$OUT/smoke.log" 2>&1; echo "smo
 timeout 1500 python -m pytest tests -m gpu -q -rf --durations=10 -p no:cacheprovider --timeout 400 > "$OUT/pytest_gpu.log" 2>&1; echo "pytest rc $?" >> "$OUT/pytest_gpu.log"
 timeout 200 python tools/fuzz_batch.py --seconds 120 --sharded 0.3 --seed 5 > "$OUT/fuzz.txt" 2>&1
 # 1. the driver's command, twice (record)
-timeout 900 python bench.py --gpus 1 --detail-out "$OUT/bench_n1_detail.json" > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
+timeout 900 python bench.py --full --gpus 1 --detail-out "$OUT/bench_n1_detail.json" > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
 echo "bench rc $? bytes $(wc -c < "$OUT/bench_n1.json")" > "$OUT/bench_n1.rc"
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --detail-out "$OUT/bench_driver_style_detail.json" > "$OUT/bench_driver_style.json" 2> /dev/null
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 --detail-out "$OUT/bench_driver_style_detail.json" > "$OUT/bench_driver_style.json" 2> /dev/null
 echo "driver-style rc $? bytes $(wc -c < "$OUT/bench_driver_style.json")" >> "$OUT/bench_n1.rc"
 # 2. rocprofv3 summaries
-stats headline_chained python "$R/bench.py" --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline --no-secondary --chain-timed-region --detail-out "$OUT/headline_chained_detail.json"
-[ -z "${WAX_SHORT:-}" ] && stats default_cmd python "$R/bench.py" --gpus 1 --no-cpu-baseline --detail-out "$OUT/default_cmd_detail.json"
+stats headline_chained python "$R/bench.py" --full --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline --no-secondary --chain-timed-region --detail-out "$OUT/headline_chained_detail.json"
+[ -z "${WAX_SHORT:-}" ] && stats default_cmd python "$R/bench.py" --full --gpus 1 --no-cpu-baseline --detail-out "$OUT/default_cmd_detail.json"
 WORKLOADS="b1m_q256 b1m_q1024 c5_shard c5_full clustered_k100 s10m_k300 s1m_k1000"
 [ -n "${WAX_SHORT:-}" ] && WORKLOADS="b1m_q256 c5_shard"
 for w in $WORKLOADS; do
-  stats gemm_$w python "$R/bench.py" --gpus 1 --steps 40 --warmup 8 --no-cpu-baseline --secondary $w --detail-out "$OUT/gemm_${w}_detail.json"
+  stats gemm_$w python "$R/bench.py" --full --gpus 1 --steps 40 --warmup 8 --no-cpu-baseline --secondary $w --detail-out "$OUT/gemm_${w}_detail.json"
 done
 if [ -n "${WAX_SHORT:-}" ]; then
   timeout 200 python tools/fuzz_select.py --seconds 100 --seed 17 > "$OUT/fuzz_select.txt" 2>&1
@@ -45,7 +45,7 @@ if [ -n "${WAX_SHORT:-}" ]; then
   ls -la "$OUT" > "$OUT/listing.txt"; tail -4 "$OUT/pytest_gpu.log"; cat "$OUT/bench_n1.json"; exit 0
 fi
 # 3. counters
-pmc fetch_headline FETCH_SIZE python "$R/bench.py" --gpus 1 --steps 20 --warmup 2 --no-cpu-baseline --no-secondary --detail-out "$OUT/fetch_headline_detail.json"
+pmc fetch_headline FETCH_SIZE python "$R/bench.py" --full --gpus 1 --steps 20 --warmup 2 --no-cpu-baseline --no-secondary --detail-out "$OUT/fetch_headline_detail.json"
 pmc fetch_768_shard FETCH_SIZE python "$R/tools/batch_bench.py" --dims 768 --rows 1250000 --nq 1024 --reps 2
 pmc fetch_768_full FETCH_SIZE python "$R/tools/batch_bench.py" --dims 768 --rows 10000000 --nq 1024 --reps 2
 pmc fetch_384_q256 FETCH_SIZE python "$R/tools/batch_bench.py" --dims 384 --rows 1000000 --nq 256 1024 --reps 2
@@ -53,9 +53,9 @@ SQ1="SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST
 pmc sq_768 "$SQ1" python "$R/tools/batch_bench.py" --dims 768 --rows 1250000 --nq 1024 --reps 2
 pmc sq2_768 "SQ_INSTS_LDS SQ_INSTS_VALU SQ_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_ACTIVE_INST_LDS" python "$R/tools/batch_bench.py" --dims 768 --rows 1250000 --nq 1024 --reps 2
 pmc sq_384 "$SQ1" python "$R/tools/batch_bench.py" --dims 384 --rows 1000000 --nq 256 1024 --reps 2
-# 4. the one-process shape (what `python bench.py --gpus N` runs), two shards on this one GPU: 10M + 1M + 10K + config 5, checksums = N = 1
-WAX_BENCH_SAME_DEVICE=1 timeout 900 python bench.py --gpus 2 --steps 40 --warmup 8 --detail-out "$OUT/one_process_2_shards_detail.json" > "$OUT/one_process_2_shards.json" 2> "$OUT/one_process_2_shards.err"
-timeout 900 python bench.py --gpus 1 --steps 40 --warmup 8 --no-cpu-baseline --traffic off --secondary s1m,s10k,c5_full --detail-out "$OUT/one_process_n1_detail.json" > "$OUT/one_process_n1.json" 2> /dev/null
+# 4. the one-process shape (what `python bench.py --full --gpus N` runs), two shards on this one GPU: 10M + 1M + 10K + config 5, checksums = N = 1
+WAX_BENCH_SAME_DEVICE=1 timeout 900 python bench.py --full --gpus 2 --steps 40 --warmup 8 --detail-out "$OUT/one_process_2_shards_detail.json" > "$OUT/one_process_2_shards.json" 2> "$OUT/one_process_2_shards.err"
+timeout 900 python bench.py --full --gpus 1 --steps 40 --warmup 8 --no-cpu-baseline --traffic off --secondary s1m,s10k,c5_full --detail-out "$OUT/one_process_n1_detail.json" > "$OUT/one_process_n1.json" 2> /dev/null
 # 5. the scaling matrix script, rehearsed on one GPU (all ranks on GPU 0, host exchange): plumbing only
 WAX_SCALE_SAME_DEVICE=1 WAX_SCALE_ROWS="10000 1000000" timeout 600 bash tools/scale_matrix.sh "$OUT/scale_rehearsal.jsonl" 2 > "$OUT/scale_rehearsal.txt" 2>&1
 rm -f "$OUT"/scale_rehearsal.jsonl.detail_*
