@@ -345,6 +345,11 @@ int wax_hip_stats(wax_hip_engine* e, wax_hip_stats_t* out);
  *   merge at once; 2 = like 1 with 192-entry lists whatever top_k (1 keeps 64-entry lists while top_k <= 8 per workgroup); "force_general"
  *   implies 0 for top_k > 192), "short_selects" / "short_select_failures" (read-only: short selections
  *   enqueued / that left the answer to the launches behind them),
+ *   "scan_mirror" (single queries, dims 384 / 768, cosine / dot, top_k <= 32, default variant, no "force_general": 1 (default) = stores of
+ *   more than 2 GiB of f32 rows stream the bf16 mirror instead (half the bytes), re-score the 64 best rows in f32 with the f32 scan's
+ *   arithmetic and release the answer only under the mirror's certificate — otherwise collect re-runs the query on the f32 scan; 2 = every
+ *   such store; 0 = never), "mirror_scans" / "mirror_scan_fallbacks" / "mirror_scan_unavailable" (read-only: single queries that took the
+ *   mirror / whose certificate failed and were re-run on the f32 scan / that took the f32 scan because the mirror could not be prepared),
  *   "filter_device_min" (wax_hip_search_filtered: allow-lists at least this long are resolved by the id -> row table in HBM, default 4096; -1 = never).
  * batched queries (bf16 MFMA GEMM + fused selection + exact re-score; exact answers whatever the setting)
  *   "batch_mode" (0 = never use the MFMA path), "batch_min" (smallest batch that may use it, default 1; below 16 queries a cost model

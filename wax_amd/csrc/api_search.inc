@@ -8,11 +8,6 @@
 static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, uint64_t* out_ticket,
                        bool try_only);
 
-static bool chain_scans(wax_hip_engine* e, int tk_mode) {
-    const int64_t sc = e->scan_chain.load();
-    return sc > 0 || (sc < 0 && tk_mode != 0);
-}
-
 int wax_hip_search_submit(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, uint64_t* out_ticket) {
     if (e && e->sh) return sh_submit(e, query, dims, top_k, out_ticket);
     return submit_impl(e, query, dims, top_k, out_ticket, false);
@@ -52,6 +47,18 @@ static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int
         s->timed = tk_mode != 0;
         const float qn = query_norm(query, dims);
         hipError_t err = hipSuccess;
+        s->mirror = false;
+        s->flag_wait = false;
+        bool mirrored = false;
+        if (scan_uses_mirror(e, k_eff)) {
+            rc = enqueue_mirror_scan(e, s, query, qn, k_eff, tk_mode, &mirrored);
+            if (rc != WAX_HIP_OK) break;
+        }
+        if (mirrored) {
+            err = hipEventRecord(s->ev_done, s->stream);
+            if (err != hipSuccess) { rc = fail(WAX_HIP_ERR_INTERNAL, std::string("event record: ") + hipGetErrorString(err)); break; }
+            break;
+        }
         const bool overlap = scan_overlaps_merge(e, others_in_flight);
         const bool qargs = scan_uses_query_args(e, k_eff, true, overlap);
         if (!qargs) {
@@ -155,6 +162,15 @@ static int collect_impl(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, f
             }
         } else {
             err = hipEventSynchronize(s->ev_done);   // commandBuffer completion (:577-582); later queries on the stream keep running
+        }
+        if (err == hipSuccess && s->mirror && __atomic_load_n(slot_cert_word(s->h_done), __ATOMIC_ACQUIRE) != 1u) {
+            // the mirror's certificate failed (ties, a clustered store, zero / NaN rows or query): this query is re-run on the f32 scan,
+            // on the same slot, and that answer is returned (the batched path's "uncertified queries are re-run exactly at collect")
+            e->st_mirror_fallbacks++;
+            rc = enqueue_scan(e, nullptr, s->q_norm, s->k_eff, s->k_eff, s->d_partials, s, s->h_hits, s->stream, nullptr, nullptr,
+                              /*chain=*/false, nullptr, nullptr, s->h_query);
+            if (rc != WAX_HIP_OK) err = hipErrorUnknown;
+            else err = hipStreamSynchronize(s->stream);
         }
         if (err != hipSuccess) {
             rc = fail(WAX_HIP_ERR_INTERNAL, std::string("search failed on device: ") + hipGetErrorString(err));

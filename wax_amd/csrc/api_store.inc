@@ -327,7 +327,9 @@ int wax_hip_remove(wax_hip_engine* e, uint64_t frame_id) {
                                   kBounceBytes, nullptr), WAX_HIP_ERR_INTERNAL, "frame id shift");
         HIP_TRY(hipStreamSynchronize(nullptr), WAX_HIP_ERR_INTERNAL, "row shift sync");
     }
-    { const int mrc = mirror_note_remove(e, (uint64_t)idx); if (mrc != WAX_HIP_OK) return mrc; }   // the mirror's tail follows the store's
+    // the mirror's tail follows the store's; if it cannot, the store has moved all the same: the mirror is converted again at its next
+    // use and the host bookkeeping below still runs (returning here would leave ids / count describing the store before the shift)
+    if (mirror_note_remove(e, (uint64_t)idx) != WAX_HIP_OK) { (void)hipGetLastError(); mirror_note_lost(e); }
     e->ids.erase(e->ids.begin() + idx);                   // :440
     e->idmap.erase_row(frame_id, (uint32_t)idx);
     e->count -= 1;                                        // :441

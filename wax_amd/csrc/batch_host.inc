@@ -8,9 +8,9 @@
 static double mirror_rows_to_convert(wax_hip_engine* e) {
     const BatchMirror& b = e->batch;
     if (b.mirror_valid.load(std::memory_order_acquire)) return 0.0;
-    if (b.stale || b.d_cb == nullptr || b.mirror_cap < e->capacity) return (double)e->count;
-    const uint64_t cnt = e->count;
-    return (double)(cnt > b.rows ? cnt - b.rows : 0) + (double)b.dirty.size();
+    if (b.stale.load() || b.d_cb == nullptr || b.mirror_cap < e->capacity) return (double)e->count;
+    const uint64_t cnt = e->count, rows = b.rows.load();
+    return (double)(cnt > rows ? cnt - rows : 0) + (double)b.n_dirty.load();
 }
 
 // Mutation hooks of the bf16 mirror and the id -> row table (exclusive engine lock held).
@@ -18,13 +18,18 @@ static void mirror_note_upsert(wax_hip_engine* e, uint64_t row) {
     BatchMirror& b = e->batch;
     b.mirror_valid = false;
     if (b.stale || row >= b.rows) return;                    // not mirrored yet: converted with the appended range
-    if (b.dirty.size() >= kMirrorMaxDirty) { b.stale = true; b.dirty.clear(); return; }
+    if (b.dirty.size() >= kMirrorMaxDirty) { b.stale = true; b.dirty.clear(); b.n_dirty = 0; return; }
     b.dirty.push_back((uint32_t)row);
+    b.n_dirty = b.dirty.size();
 }
 static void mirror_note_append(wax_hip_engine* e) { e->batch.mirror_valid = false; e->idhash.valid = false; }
 static void mirror_note_replaced(wax_hip_engine* e) {       // deserialize: every row is new
-    e->batch.mirror_valid = false; e->batch.stale = true; e->batch.dirty.clear(); e->batch.rows = 0;
+    e->batch.mirror_valid = false; e->batch.stale = true; e->batch.dirty.clear(); e->batch.n_dirty = 0; e->batch.rows = 0;
     e->idhash.valid = false; e->idhash.stale = true; e->idhash.rows = 0;
+}
+// a mutation the mirror could not follow (a failed row shift): convert everything at the next use
+static void mirror_note_lost(wax_hip_engine* e) {
+    e->batch.mirror_valid = false; e->batch.stale = true; e->batch.dirty.clear(); e->batch.n_dirty = 0;
 }
 // remove(frameId:) moved store rows (idx, count) down by one (MetalVectorEngine.swift:431-438): the mirror's tail follows (half the
 // bytes of the store's own move), and the listed dirty rows move with it. Called BEFORE count is decremented.
@@ -51,6 +56,7 @@ static int mirror_note_remove(wax_hip_engine* e, uint64_t idx) {
         b.dirty[w++] = r > idx ? r - 1 : r;
     }
     b.dirty.resize(w);
+    b.n_dirty = w;
     return WAX_HIP_OK;
 }
 
@@ -100,7 +106,7 @@ int ensure_mirror(wax_hip_engine* e, hipStream_t st) {
     }
     const uint64_t count = e->count;
     if (b.stale) {
-        b.rows = 0; b.dirty.clear(); b.stale = false;
+        b.rows = 0; b.dirty.clear(); b.n_dirty = 0; b.stale = false;
         HIP_TRY(hipMemsetAsync(b.d_maxnorm, 0, 2 * sizeof(unsigned int), st), WAX_HIP_ERR_INTERNAL, "batch memset");
     }
     if (b.rows > count) b.rows = count;                       // (cannot happen: removals move `rows` with them)
@@ -122,6 +128,7 @@ int ensure_mirror(wax_hip_engine* e, hipStream_t st) {
                 WAX_HIP_ERR_INTERNAL, "mirror kernel launch");
         converted += b.dirty.size();
         b.dirty.clear();
+        b.n_dirty = 0;
     }
     if (converted) {
         HIP_TRY(hipEventRecord(b.ev_ready, st), WAX_HIP_ERR_INTERNAL, "mirror ready record");

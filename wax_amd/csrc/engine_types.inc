@@ -162,6 +162,8 @@ constexpr int kShardRing = 8;
 // A scan's stage buffer: per-workgroup partial top-k lists, followed by one cache line holding the arrival ticket of the
 // fused final merge (scan_epilogue: zero between launches — the last arriver re-arms it).
 constexpr size_t kPartialsBytes = (size_t)MAX_GRID_BLOCKS * FUSED_MAX_K * sizeof(int64_t) + 128;
+// the mirror scan's certificate word: in the slot's pinned 64-byte completion block, behind the completion word
+inline uint32_t* slot_cert_word(uint64_t* h_done) { return reinterpret_cast<uint32_t*>(h_done + 2); }
 inline uint32_t* partials_ticket(int64_t* d_partials) {
     return reinterpret_cast<uint32_t*>(d_partials + (size_t)MAX_GRID_BLOCKS * FUSED_MAX_K);
 }
@@ -190,6 +192,8 @@ struct Slot {
     // per-ticket state
     int k_eff = 0;
     bool timed = false;
+    bool mirror = false;           // answered by the mirror scan: collect reads the certificate word and re-runs the f32 scan if it failed
+    float q_norm = 0.f;            // (mirror) the query's norm; the query itself is in h_query
     std::thread::id owner;         // the submitting thread (its outstanding-ticket count drops at collect, whoever collects)
 };
 
@@ -248,9 +252,12 @@ struct BatchMirror {
     // max ||v|| and max ||x - bf16(x)|| stay on the device (d_maxnorm, read there by the prep kernel) and only ever grow between full
     // conversions: a bound that is too large by a row that has since been overwritten or removed is still a bound.
     // Writers hold the exclusive engine lock; ensure_mirror holds `mu` under the shared one.
-    uint64_t rows = 0;                   // rows [0, rows) of the mirror match the store, except `dirty`
+    // `rows`, `stale` and `n_dirty` are atomics: mirror_rows_to_convert reads them without `mu` (a planning figure, now read by
+    // every large single query as well as by batches)
+    std::atomic<uint64_t> rows{0};       // rows [0, rows) of the mirror match the store, except `dirty`
     std::vector<uint32_t> dirty;         // rows < `rows` overwritten since (upserts); more than kMirrorMaxDirty of them = stale
-    bool stale = true;                   // convert everything again
+    std::atomic<uint64_t> n_dirty{0};    // dirty.size(), kept beside it
+    std::atomic<bool> stale{true};       // convert everything again
     uint32_t* d_dirty = nullptr;         // device copy of `dirty` for the listed-rows conversion
     hipEvent_t ev_ready = nullptr;       // recorded behind the last conversion: other workspaces' streams wait for it
     bool ev_pending = false;
@@ -449,6 +456,8 @@ struct wax_hip_engine {
     std::atomic<uint64_t> st_batch_inline_retries{0};  // ... of which inside the finish kernel (no host round trip)
     std::atomic<uint64_t> st_merged_scans{0};        // single-query scans whose last-arriving workgroup did the final merge (one launch per query)
     std::atomic<uint64_t> st_query_args{0};          // single-query scans that took their query through the kernel arguments
+    std::atomic<int64_t> scan_mirror{1};     // single queries on the bf16 mirror + f32 re-score + certificate: 1 (default) = stores of > SCAN_KWAY_MAX_BYTES of rows, 2 = always, 0 = never
+    std::atomic<uint64_t> st_mirror_scans{0}, st_mirror_fallbacks{0}, st_mirror_unavailable{0};
     // wax_hip_search_batch_submit_device tickets (guarded by bticket_mu)
     struct BatchTicket {
         BatchCtx* c = nullptr;           // null: the batch was answered at submit time (empty engine / loop path)

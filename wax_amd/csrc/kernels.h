@@ -107,6 +107,34 @@ inline bool scan_merges_in_kernel(int grid, int k, bool kway, uint32_t n_rows, u
                                             (uint64_t)n_rows * dims * sizeof(float) <= SCAN_KWAY_MAX_BYTES);
 }
 
+// ---- mirror_scan.hip: one query against the bf16 mirror, exact f32 re-score of the best MIRROR_KP rows, certificate ----
+constexpr int MIRROR_KP = 64;       // approximate candidates kept per workgroup and in total (k')
+constexpr int MIRROR_MAX_K = 32;    // largest k the mirror path answers
+struct MirrorScanArgs {
+    const unsigned short* mirror;   // [n_rows][dims] bf16 (cosine rows pre-normalised; batch_host.inc BatchMirror)
+    const float* store;             // [n_rows][dims] f32: the re-score reads the candidates' rows here
+    int64_t* partials;              // [grid][MIRROR_KP] per-workgroup sorted approximate keys
+    const uint64_t* ids;            // frame ids by local row (may be null)
+    wax_hip_hit* hits;              // [kpad] the answer (pinned host memory)
+    uint32_t* certified;            // 1 = the answer is the f32 scan's, 0 = re-run it there (pinned host memory)
+    const unsigned int* max_bits;   // the mirror's {max ||v||, max ||x - bf16(x)||} (device words)
+    uint32_t n_rows, row_base, dims;
+    int32_t k, kpad;
+    float q_norm;                   // ||query||_2 exactly as the f32 scan gets it
+    int32_t lists;                  // set by launch_mirror_scan: workgroups of the scan launch
+    int32_t use_measured;           // "batch_eps_measured": eps from the measured row error (else the worst case)
+};
+template <int DIMS>
+struct alignas(16) MirrorScanArgsQ {
+    MirrorScanArgs a;
+    alignas(16) float q[DIMS];
+};
+static_assert(sizeof(MirrorScanArgsQ<768>) <= 4096, "HIP kernel arguments are limited to 4 KB");
+bool mirror_scan_supported(uint32_t dims, int metric);
+int mirror_grid_for(uint32_t n_rows, uint32_t dims, int grid_cap);
+// Two launches on `st`: mirror_scan_kernel (the event pair of launch_timing(), if armed, binds to it) and mirror_finish_kernel.
+hipError_t launch_mirror_scan(const MirrorScanArgs& args, const float* query, int metric, int grid_cap, hipStream_t st);
+
 struct ScanVariantInfo {
     int unroll;          // row groups in flight per wave iteration
     int nt;              // 1 = non-temporal (streaming) loads

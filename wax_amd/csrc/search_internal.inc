@@ -232,3 +232,87 @@ void harvest_ring_event(wax_hip_engine* e, int r) {
 }
 
 
+
+// ---- one query on the bf16 mirror (mirror_scan.hip; DESIGN 4.1) ----------------------------------------------------------------
+int ensure_mirror(wax_hip_engine* e, hipStream_t st);   // batch_host.inc
+
+// chain single-query scans of different streams through an event ("scan_chain"; -1 = while kernels are timed)
+static bool chain_scans(wax_hip_engine* e, int tk_mode) {
+    const int64_t sc = e->scan_chain.load();
+    return sc > 0 || (sc < 0 && tk_mode != 0);
+}
+
+// Does a single query of this engine for k_eff results stream the bf16 mirror ("scan_mirror")? Shapes mirror_scan.hip has kernels
+// for, the default kernel variant, the fused path's k; in auto mode only stores above the one-launch boundary (SCAN_KWAY_MAX_BYTES:
+// below it a scan is latency-bound and merges in its own kernel, above it the f32 scan is bound by HBM bandwidth alone).
+bool scan_uses_mirror(wax_hip_engine* e, int k_eff) {
+    const int64_t mode = e->scan_mirror.load();
+    if (mode == 0 || k_eff < 1 || k_eff > MIRROR_MAX_K || !mirror_scan_supported(e->dims, e->metric)) return false;
+    if (e->variant.load() > 0 || e->force_general.load() != 0) return false;
+    if (e->grid_blocks.load() > SCAN_KWAY_MERGE_GRID) return false;
+    return mode >= 2 || e->count * (uint64_t)e->dims * sizeof(float) > SCAN_KWAY_MAX_BYTES;
+}
+
+// Enqueue the mirror scan + finish of one query on the slot's stream (the kpad hits and the certificate word land in the slot's pinned
+// memory). *took = false: the mirror could not be prepared (allocation, conversion launch) and nothing was enqueued — the caller takes
+// the f32 scan; a query never fails because of the mirror. Same chain and timing semantics as the fused f32 branch of enqueue_scan:
+// "time_kernels" 2 binds the event pair to the mirror_scan_kernel dispatch, 1 brackets the two launches.
+int enqueue_mirror_scan(wax_hip_engine* e, Slot* s, const float* query, float q_norm, int k_eff, int tk_mode, bool* took) {
+    *took = false;
+    BatchMirror& b = e->batch;
+    {
+        const std::string keep = g_last_error;
+        if (ensure_mirror(e, s->stream) != WAX_HIP_OK || b.d_cb == nullptr || b.d_maxnorm == nullptr) {
+            (void)hipGetLastError();                      // a refused allocation must not surface in the f32 launch behind it
+            g_last_error = keep;
+            e->st_mirror_unavailable++;
+            return WAX_HIP_OK;
+        }
+    }
+    std::memcpy(s->h_query, query, (size_t)e->dims * sizeof(float));   // for the f32 re-run at collect, if the certificate fails
+    s->q_norm = q_norm;
+    MirrorScanArgs m{};
+    m.mirror = b.d_cb;
+    m.store = e->d_store;
+    m.partials = s->d_partials;
+    m.ids = e->d_ids;
+    m.hits = s->h_hits;
+    m.certified = slot_cert_word(s->h_done);
+    m.max_bits = b.d_maxnorm;
+    m.n_rows = (uint32_t)e->count;
+    m.row_base = (uint32_t)e->row_base;
+    m.dims = e->dims;
+    m.k = k_eff;
+    m.kpad = k_eff;
+    m.q_norm = q_norm;
+    m.use_measured = e->batch_eps_measured.load() != 0 ? 1 : 0;
+    hipEvent_t ev0 = s->timed ? s->ev0 : nullptr, ev1 = s->timed ? s->ev1 : nullptr;
+    const bool bound = ev0 != nullptr && ev1 != nullptr && tk_mode == 2;
+    s->t_start = ev0;
+    s->t_end = ev1;
+    std::unique_lock<std::mutex> chain_guard(e->chain_mu, std::defer_lock);
+    if (chain_scans(e, tk_mode)) {
+        chain_guard.lock();
+        if (e->scan_done_valid) HIP_TRY(hipStreamWaitEvent(s->stream, e->chain_event, 0), WAX_HIP_ERR_INTERNAL, "scan chain wait");
+    }
+    if (ev0 && !bound) HIP_TRY(hipEventRecord(ev0, s->stream), WAX_HIP_ERR_INTERNAL, "event record");
+    if (bound) launch_timing() = LaunchTiming{ev0, ev1};
+    const hipError_t lerr = launch_mirror_scan(m, query, e->metric, (int)e->grid_blocks.load(), s->stream);
+    launch_timing() = LaunchTiming{};
+    HIP_TRY(lerr, WAX_HIP_ERR_INTERNAL, "mirror scan launch");
+    if (ev1 && !bound) HIP_TRY(hipEventRecord(ev1, s->stream), WAX_HIP_ERR_INTERNAL, "event record");
+    if (chain_guard.owns_lock()) {
+        HIP_TRY(hipEventRecord(e->scan_done, s->stream), WAX_HIP_ERR_INTERNAL, "scan chain record");
+        e->chain_event = e->scan_done;
+        e->chain_is_timing = false;
+        e->scan_done_valid = true;
+        chain_guard.unlock();
+    }
+    *took = true;
+    s->mirror = true;
+    e->st_mirror_scans++;
+    e->st_searches++;
+    e->st_rows += e->count;
+    e->st_bytes += e->count * (uint64_t)e->dims * 2ull + (uint64_t)MIRROR_KP * e->dims * 4ull;
+    return WAX_HIP_OK;
+}

@@ -43,6 +43,7 @@ int wax_hip_set_tuning(wax_hip_engine* e, const char* key, int64_t value) {
     else if (k == "merge_overlap_mb") e->merge_overlap_mb = value < 0 ? 0 : value;
     else if (k == "batch_qfrag") e->batch_qfrag = value != 0;
     else if (k == "scan_plain_mb") e->scan_plain_mb = value;
+    else if (k == "scan_mirror") { if (value < 0 || value > 2) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "scan_mirror must be 0, 1 or 2"); e->scan_mirror = value; }
     else if (k == "query_args") { if (value < 0 || value > 2) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "query_args must be 0, 1 or 2"); e->query_args = value; }
     else if (k == "batch_min") e->batch_min = value;
     else if (k == "batch_mode") e->batch_mode = value;
@@ -131,6 +132,10 @@ int64_t wax_hip_get_tuning(wax_hip_engine* e, const char* key) {
     if (k == "batch_qfrag") return e->batch_qfrag.load();
     if (k == "overlap_scans") return (int64_t)e->st_overlap_scans.load();
     if (k == "scan_plain_mb") return e->scan_plain_mb.load();
+    if (k == "scan_mirror") return e->scan_mirror.load();
+    if (k == "mirror_scans") return (int64_t)e->st_mirror_scans.load();
+    if (k == "mirror_scan_fallbacks") return (int64_t)e->st_mirror_fallbacks.load();
+    if (k == "mirror_scan_unavailable") return (int64_t)e->st_mirror_unavailable.load();
     if (k == "done_flag_waits") return (int64_t)e->st_flag_waits.load();
     if (k == "query_args_scans") return (int64_t)e->st_query_args.load();
     if (k == "merged_scans") return (int64_t)e->st_merged_scans.load();
