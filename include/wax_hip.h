@@ -304,6 +304,26 @@ int wax_hip_search_filtered(wax_hip_engine* e, const float* query, uint32_t dims
                             int has_min_score, float min_score,
                             uint64_t* out_ids, float* out_scores, uint32_t out_capacity, uint32_t* out_count);
 
+/* Batched filtered search: nq queries (row-major nq x dims), each with its own allow-list and score cut.
+ * Allow-lists: allow_begin and allow_len both NULL = no query has a list. Otherwise query q's list is
+ * allow_frame_ids[allow_begin[q] .. allow_begin[q] + allow_len[q]); allow_len[q] == WAX_HIP_NO_ALLOW_LIST = no list for q;
+ * length 0 = nothing allowed. Ranges may overlap; queries with the same (begin, len) share one list, which is resolved once and
+ * scored for all of them in one pass. A range that leaves [0, n_allow_ids) is refused (WAX_HIP_ERR_INVALID_ARGUMENT). Ids not in
+ * the engine are ignored; duplicate ids count once. min_scores NULL = no cut, otherwise query q drops results with
+ * score < min_scores[q] (NaN: no cut). Outputs as wax_hip_search_batch: row q at q * out_stride, out_counts[q] results.
+ * Row q equals wax_hip_search_filtered for that query, list and cut with out_capacity = out_stride, bit for bit; a query with
+ * neither list nor cut gets its wax_hip_search_batch row. The queries with a list are answered under one shared-lock
+ * acquisition (one snapshot of the store); those without one run first as one sub-batch of the unfiltered batched search.
+ * Up to FUSED_MAX_K (192) results and the specialised dimensions (64, 128, 256, 384, 512, 768, 1024, 1536): every list is
+ * sorted into a compact row list on the device and one gather launch scores all lists, with one synchronisation per call.
+ * Otherwise, and with "filter_batch" 0 or "force_general" set, each listed query takes the single-query filtered path. */
+#define WAX_HIP_NO_ALLOW_LIST UINT64_MAX
+int wax_hip_search_batch_filtered(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
+                                  const uint64_t* allow_frame_ids, uint64_t n_allow_ids,
+                                  const uint64_t* allow_begin, const uint64_t* allow_len,
+                                  const float* min_scores,
+                                  uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts);
+
 /* ---- persistence: "MV2V" vec segment, encoding 2 ------------------------- */
 
 /* serialize() (MetalVectorEngine.swift:682-714): byte-identical layout
@@ -350,7 +370,10 @@ int wax_hip_stats(wax_hip_engine* e, wax_hip_stats_t* out);
  *   arithmetic and release the answer only under the mirror's certificate — otherwise collect re-runs the query on the f32 scan; 2 = every
  *   such store; 0 = never), "mirror_scans" / "mirror_scan_fallbacks" / "mirror_scan_unavailable" (read-only: single queries that took the
  *   mirror / whose certificate failed and were re-run on the f32 scan / that took the f32 scan because the mirror could not be prepared),
- *   "filter_device_min" (wax_hip_search_filtered: allow-lists at least this long are resolved by the id -> row table in HBM, default 4096; -1 = never).
+ *   "filter_device_min" (wax_hip_search_filtered: allow-lists at least this long are resolved by the id -> row table in HBM, default 4096; -1 = never),
+ *   "filter_batch" (wax_hip_search_batch_filtered: 1 (default) = one gather pass for all allow-lists; 0 = the single-query filtered path
+ *   per query), "filter_batch_queries" / "filter_batch_fallbacks" (read-only: listed queries answered by the gather pass / by the
+ *   per-query path).
  * batched queries (bf16 MFMA GEMM + fused selection + exact re-score; exact answers whatever the setting)
  *   "batch_mode" (0 = never use the MFMA path), "batch_min" (smallest batch that may use it, default 1; below 16 queries a cost model
  *   picks between one GEMM pass over the bf16 mirror and nq f32 scans), "batch_workspaces" (concurrent batched searches per engine, default 4),

@@ -29,6 +29,7 @@ ERR_INTERNAL = -8
 MAX_RESULTS = 10000
 KEY_PAD = (1 << 63) - 1
 ID_PAD = (1 << 64) - 1
+NO_ALLOW_LIST = (1 << 64) - 1   # WAX_HIP_NO_ALLOW_LIST: allow_len entry of a query without an allow-list
 
 
 class Hit(ctypes.Structure):
@@ -98,6 +99,8 @@ SIGNATURES: Dict[str, tuple] = {
     "wax_hip_search_filtered": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int, _u64p,
                                                ctypes.c_uint64, ctypes.c_int, ctypes.c_float, _u64p, _f32p,
                                                ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    "wax_hip_search_batch_filtered": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, _u64p,
+                                                     ctypes.c_uint64, _u64p, _u64p, _f32p, _u64p, _f32p, ctypes.c_uint32, _u32p]),
     "wax_hip_merge_batch_hits_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                        ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
     "wax_hip_add_batch_device": (ctypes.c_int, [_engine_p, _u64p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32]),

@@ -218,6 +218,21 @@ struct FilterWork {
     wax_hip_hit* d_hits = nullptr;   // [WAX_HIP_MAX_RESULTS]
     wax_hip_hit* h_hits = nullptr;   // pinned [WAX_HIP_MAX_RESULTS]
     SelectWork sw{};
+    // wax_hip_search_batch_filtered (d_allow above holds the caller's packed lists)
+    float* d_bq = nullptr;           // [bq_cap] the batch's queries
+    uint64_t bq_cap = 0;
+    unsigned char* d_meta = nullptr; // [meta_cap] list descriptors, groups, work table, query slots, norms, merge spans (one upload)
+    uint64_t meta_cap = 0;
+    uint32_t* d_lrows = nullptr;     // [lrows_cap] compact row lists, one region per distinct list
+    uint64_t lrows_cap = 0;
+    uint32_t* d_lcnt = nullptr;      // [lcnt_cap] their device-side lengths
+    uint64_t lcnt_cap = 0;
+    uint64_t* d_lids = nullptr;      // [lids_cap] frame ids the bitmap route writes beside its rows (unused)
+    uint64_t lids_cap = 0;
+    int64_t* d_part = nullptr;       // [part_cap] per-(query, work item) partial key lists
+    uint64_t part_cap = 0;
+    wax_hip_hit* d_bhits = nullptr;  // [bhits_cap] merged hits, one row of k per fused query
+    uint64_t bhits_cap = 0;
 };
 
 void free_filter_work(FilterWork* f);
@@ -479,6 +494,8 @@ struct wax_hip_engine {
     IdHash idhash;
     std::atomic<int64_t> filter_device_min{4096}; // allow-lists at least this long are resolved on the device
     std::atomic<uint64_t> st_filter_device{0};    // filtered searches whose allow-list was resolved on the device
+    std::atomic<int64_t> filter_batch{1};         // wax_hip_search_batch_filtered: 1 = one gather pass for all lists, 0 = the per-query loop
+    std::atomic<uint64_t> st_filter_batch_queries{0}, st_filter_batch_fallbacks{0};
     // Write-combining of single-frame appends (the reference appends into a unified-memory buffer and the GPU simply
     // sees it, MetalVectorEngine.swift:340-351; with discrete HBM the analogue is a pinned staging area that the NEXT
     // reader — or a full staging area — uploads in one copy). The last `pend_rows` rows of [0, count) live only here.
@@ -552,6 +569,9 @@ int sh_search_batch_hits(wax_hip_engine* e, const float* queries, uint32_t nq, u
 int sh_batch_device(wax_hip_engine* e, const float* d_queries, uint32_t nq, uint32_t dims, int32_t top_k, wax_hip_hit* d_out_hits,
                     uint32_t out_stride, void* stream, uint64_t* ticket);
 int sh_batch_collect_device(wax_hip_engine* e, uint64_t ticket, uint32_t* out_fallbacks);
+int sh_search_batch_filtered(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k, const uint64_t* allow,
+                             uint64_t n_allow_ids, const uint64_t* allow_begin, const uint64_t* allow_len, const float* min_scores, uint64_t* out_ids,
+                             float* out_scores, uint32_t out_stride, uint32_t* out_counts);
 int sh_search_filtered(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, int has_allow, const uint64_t* allow,
                        uint64_t n_allow, int has_min, float min_score, uint64_t* out_ids, float* out_scores, uint32_t capacity,
                        uint32_t* out_count);

@@ -6,6 +6,8 @@
 //   idhash_probe_kernel    one thread per allowed id: probe, mark the row in a bitmap (atomicOr). The bitmap hands the
 //                          rows back ascending and unique — the order every selection path breaks ties in.
 //   bitmap_count / bitmap_scan / bitmap_emit   bitmap -> compact ascending row list + the rows' frame ids.
+//   rowlist_sort_kernel    batched filtered search: one workgroup per allow-list of <= ROWLIST_SORT_MAX ids probes, sorts the
+//                          rows in LDS (bitonic) and writes them ascending and unique with a device-side count.
 //
 // All HBM-latency work: at a 1M-id allow-list the probes are ~2M random 64-byte sector reads, a few tens of µs on the
 // device against 5.65 ms of cache-missing host probes (profiles/r01).
@@ -28,25 +30,81 @@ __global__ __launch_bounds__(256) void idhash_build_kernel(const uint64_t* __res
     while (atomicCAS(&table[h], 0u, row + 1u) != 0u) h = (h + 1u) & mask;
 }
 
-__global__ __launch_bounds__(256) void idhash_probe_kernel(const uint64_t* __restrict__ allow, uint64_t n_allow,
-                                                           const uint64_t* __restrict__ ids, const uint32_t* __restrict__ table,
-                                                           uint32_t mask, uint32_t* bitmap) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (i >= n_allow) return;
-    const uint64_t id = allow[i];
+constexpr uint32_t kNoRow = 0xffffffffu;
+
+// The row of frame id `id`, kNoRow if the store does not hold it.
+__device__ __forceinline__ uint32_t idhash_lowest_row(uint64_t id, const uint64_t* __restrict__ ids, const uint32_t* __restrict__ table,
+                                                      uint32_t mask) {
     uint32_t h = (uint32_t)mix64(id) & mask;
     // A store loaded from a segment may hold one frame id in several rows (deserialize keeps them as separate rows and the
     // host id map resolves the id to the FIRST of them, MetalVectorEngine.swift:809-811 / firstIndex(of:)). All rows of
     // one id sit in the same probe chain, in whatever order the build's CAS races left them: walk the chain to its end
     // and mark the LOWEST matching row, so the device path picks the row the host path picks, on every run.
-    uint32_t best = 0xffffffffu;
+    uint32_t best = kNoRow;
     for (;;) {
         const uint32_t s = table[h];
         if (s == 0u) break;   // end of the chain (an allowed id without a vector is simply absent, UnifiedSearch.swift:1243)
         if (ids[s - 1u] == id && s - 1u < best) best = s - 1u;
         h = (h + 1u) & mask;
     }
-    if (best != 0xffffffffu) atomicOr(&bitmap[best >> 5], 1u << (best & 31u));
+    return best;
+}
+
+__global__ __launch_bounds__(256) void idhash_probe_kernel(const uint64_t* __restrict__ allow, uint64_t n_allow,
+                                                           const uint64_t* __restrict__ ids, const uint32_t* __restrict__ table,
+                                                           uint32_t mask, uint32_t* bitmap) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_allow) return;
+    const uint32_t best = idhash_lowest_row(allow[i], ids, table, mask);
+    if (best != kNoRow) atomicOr(&bitmap[best >> 5], 1u << (best & 31u));
+}
+
+// One workgroup per list: probe every id into LDS (kNoRow for an id the store lacks), bitonic sort of the next power of two,
+// then keep the first of every run of equal rows (duplicate ids) and drop kNoRow; a workgroup-wide scan places the survivors.
+constexpr int kSortThreads = 1024;
+__global__ __launch_bounds__(kSortThreads) void rowlist_sort_kernel(const uint64_t* __restrict__ allow, const RowListDesc* __restrict__ desc,
+                                                                    const uint64_t* __restrict__ ids, const uint32_t* __restrict__ table,
+                                                                    uint32_t mask, uint32_t* __restrict__ rows_out, uint32_t* counts) {
+    extern __shared__ uint32_t srt[];              // [P]
+    __shared__ uint32_t wave_sum[kSortThreads / 64];
+    const RowListDesc d = desc[blockIdx.x];
+    const uint32_t t = threadIdx.x;
+    uint32_t P = 64;
+    while (P < d.len) P <<= 1;                     // len <= ROWLIST_SORT_MAX (host-checked)
+    for (uint32_t i = t; i < P; i += kSortThreads) srt[i] = i < d.len ? idhash_lowest_row(allow[d.allow_off + i], ids, table, mask) : kNoRow;
+    __syncthreads();
+    for (uint32_t kk = 2; kk <= P; kk <<= 1) {
+        for (uint32_t j = kk >> 1; j > 0; j >>= 1) {
+            for (uint32_t i = t; i < P; i += kSortThreads) {
+                const uint32_t l = i ^ j;
+                if (l > i) {
+                    const uint32_t x = srt[i], y = srt[l];
+                    if ((x > y) == ((i & kk) == 0)) { srt[i] = y; srt[l] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    const int lane = (int)(t & 63u), w = (int)(t >> 6);
+    uint32_t base = 0;
+    for (uint32_t c0 = 0; c0 < P; c0 += kSortThreads) {
+        const uint32_t i = c0 + t;
+        const uint32_t v = i < P ? srt[i] : kNoRow;
+        const bool keep = v != kNoRow && (i == 0 || srt[i - 1] != v);
+        const unsigned long long m = __ballot(keep);
+        const uint32_t before = (uint32_t)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        if (lane == 0) wave_sum[w] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t off = 0, all = 0;
+        for (int j = 0; j < kSortThreads / 64; ++j) {
+            if (j < w) off += wave_sum[j];
+            all += wave_sum[j];
+        }
+        if (keep) rows_out[d.row_off + base + off + before] = v;
+        base += all;
+        __syncthreads();                           // wave_sum is rewritten by the next chunk
+    }
+    if (t == 0) counts[d.count_slot] = base;
 }
 
 constexpr int kWordsPerThread = 4;
@@ -150,6 +208,23 @@ hipError_t launch_allow_probe(const uint64_t* d_allow, uint64_t n_allow, const u
                        table, (uint32_t)(slots - 1), bitmap);
     hipLaunchKernelGGL(bitmap_count_kernel, dim3(n_blocks), dim3(256), 0, st, bitmap, n_words, block_sum);
     hipLaunchKernelGGL(bitmap_scan_kernel, dim3(1), dim3(256), 0, st, block_sum, n_blocks, total);
+    return hipGetLastError();
+}
+
+hipError_t launch_rowlist_sort(const uint64_t* d_allow, const RowListDesc* d_desc, uint32_t n_lists, uint32_t max_len, const uint64_t* ids,
+                               const uint32_t* table, uint64_t slots, uint32_t* rows_out, uint32_t* counts, hipStream_t st) {
+    if (n_lists == 0) return hipSuccess;
+    if (max_len > ROWLIST_SORT_MAX) return hipErrorInvalidValue;
+    uint32_t P = 64;
+    while (P < max_len) P <<= 1;
+    const size_t smem = (size_t)P * sizeof(uint32_t);
+    static std::atomic<uint64_t> configured{0};   // per device (ensure_dynamic_lds)
+    if (smem > 64 * 1024 - 256) {
+        const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&rowlist_sort_kernel), 96 * 1024, configured);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(rowlist_sort_kernel, dim3(n_lists), dim3(kSortThreads), smem, st, d_allow, d_desc, ids, table,
+                       (uint32_t)(slots - 1), rows_out, counts);
     return hipGetLastError();
 }
 

@@ -157,6 +157,16 @@ hipError_t launch_scan(const ScanArgs& args, int metric, int variant, int cap, b
 int scan_grid_for(uint32_t n_rows, uint32_t dims, int variant, int grid_cap);
 
 // ---- multiscan.hip: the exact scan for a GROUP of queries in one pass over the store (fallback of the batched path) ----
+// One list group of the gather form (launch_scan_multi_listed): up to scan_multi_group() queries that share one compact row list.
+struct GatherGroup {
+    uint32_t row_off;      // the list is rows[row_off .. row_off + row_counts[count_slot])
+    uint32_t count_slot;
+    uint32_t q0, nq;       // its queries are qlist[q0 .. q0 + nq) (norms q_norm[q0 ..])
+    uint32_t part_off;     // partial list of query slot qi, share w: partials[(part_off + qi * n_items + w) * k ..]
+    uint32_t n_items;      // workgroups (work items) that share the list
+    uint32_t item0;        // its first work item
+    uint32_t pad;
+};
 struct ScanMultiArgs {
     const float* store;       // [n_rows][dims] f32
     const float* queries;     // query block in HBM, row-major x dims
@@ -165,11 +175,22 @@ struct ScanMultiArgs {
     int64_t* partials;        // [nq][grid][k] per-(query, workgroup) sorted keys
     uint32_t n_rows, row_base, dims, nq;
     int32_t k;
+    // gather form only (null otherwise): compact ascending row lists, their device-side counts, the groups and the work table
+    const uint32_t* rows;
+    const uint32_t* row_counts;
+    const GatherGroup* groups;
+    const uint32_t* item_group;   // [n_items] work item -> group
 };
 bool scan_multi_dims(uint32_t dims);                    // dims the kernel is specialised for (= launch_scan's table)
 uint32_t scan_multi_group(uint32_t dims, int k);        // queries per launch (0: not served — k > 192, other dims, lists too large for LDS)
 int scan_multi_grid(uint32_t n_rows, uint32_t dims, int grid_cap);   // workgroups launch_scan_multi will use
 hipError_t launch_scan_multi(const ScanMultiArgs& a, int metric, int grid_cap, hipStream_t stream, int* out_grid);
+// Gather form: one launch, n_items workgroups, every group's queries scored on its listed rows only (nq / n_rows unused).
+uint32_t scan_multi_listed_items(uint64_t max_rows, uint32_t dims, int grid_cap);   // work items for a list of at most max_rows rows
+hipError_t launch_scan_multi_listed(const ScanMultiArgs& a, int metric, uint32_t n_items, hipStream_t stream);
+// Per query b < nq: the d_spans[2b + 1] lists of k keys at d_in + d_spans[2b] * k -> row b of d_out (out_stride hits, padded).
+hipError_t launch_merge_keys_spans(const int64_t* d_in, const uint32_t* d_spans, int k, const uint64_t* d_ids, uint32_t row_base,
+                                   uint32_t n_rows, wax_hip_hit* d_out, uint32_t out_stride, uint32_t nq, hipStream_t stream);
 // Per query b < nq: the n_lists lists of k keys at d_in + b * n_lists * k -> the k smallest as hits (frame ids attached) in
 // row (d_qlist ? d_qlist[b] : b) of d_out_base, rows out_stride hits wide and padded to it.
 hipError_t launch_merge_keys_multi(const int64_t* d_in, uint32_t n_lists, int k, const uint64_t* d_ids, uint32_t row_base,
@@ -438,6 +459,15 @@ hipError_t launch_allow_probe(const uint64_t* d_allow, uint64_t n_allow, const u
                               hipStream_t st);
 hipError_t launch_allow_emit(const uint32_t* bitmap, uint32_t n_rows, const uint32_t* block_off, const uint64_t* ids,
                              uint32_t* rows_out, uint64_t* ids_out, hipStream_t st);
+// Batched allow-lists of at most ROWLIST_SORT_MAX ids: one workgroup per list probes the id -> row table, sorts the rows in LDS
+// and writes them ascending and unique to rows_out + row_off, their number to counts[count_slot]. No host round trip.
+constexpr uint32_t ROWLIST_SORT_MAX = 16384;
+struct RowListDesc {
+    uint64_t allow_off;    // the list is allow[allow_off .. allow_off + len)
+    uint32_t len, row_off, count_slot, pad;
+};
+hipError_t launch_rowlist_sort(const uint64_t* d_allow, const RowListDesc* d_desc, uint32_t n_lists, uint32_t max_len, const uint64_t* ids,
+                               const uint32_t* table, uint64_t slots, uint32_t* rows_out, uint32_t* counts, hipStream_t st);
 
 
 // ---- rrf.hip: reciprocal-rank fusion of ranked id lists, one workgroup per query ----

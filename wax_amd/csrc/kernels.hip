@@ -515,11 +515,17 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_keys_kernel(const int64_t
                                                                    uint32_t row_base, uint32_t n_rows,
                                                                    wax_hip_hit* __restrict__ out,
                                                                    const uint32_t* __restrict__ qlist, uint32_t out_stride,
-                                                                   const uint32_t* __restrict__ gate) {
+                                                                   const uint32_t* __restrict__ gate,
+                                                                   const uint32_t* __restrict__ spans = nullptr) {
     __shared__ int64_t lds[MERGE_WAVES * CAP + MERGE_WAVES + 2 * FUSED_MAX_K + 1];
     if (gate != nullptr && *gate == 0u) return;               // the short selection in front of this launch answered
-    // one workgroup per query (launch_merge_keys_multi); the single-query launch has one workgroup and out_stride = 0
-    in += (size_t)blockIdx.x * n_lists * (uint32_t)k;
+    // one workgroup per query (launch_merge_keys_multi / _spans); the single-query launch has one workgroup and out_stride = 0
+    if (spans != nullptr) {
+        in += (size_t)spans[2 * blockIdx.x] * (uint32_t)k;
+        n_lists = spans[2 * blockIdx.x + 1];
+    } else {
+        in += (size_t)blockIdx.x * n_lists * (uint32_t)k;
+    }
     out += (size_t)(qlist ? qlist[blockIdx.x] : blockIdx.x) * out_stride;
     int* counts = reinterpret_cast<int*>(lds + MERGE_WAVES * CAP);
     int64_t* fin = lds + MERGE_WAVES * CAP + MERGE_WAVES;
@@ -618,6 +624,18 @@ hipError_t launch_merge_keys_multi(const int64_t* d_in, uint32_t n_lists, int k,
     else
         hipLaunchKernelGGL((merge_keys_kernel<256>), dim3(nq), dim3(MERGE_THREADS), 0, st, d_in, n_lists, k, (int)out_stride, d_ids,
                            row_base, n_rows, d_out_base, d_qlist, out_stride, (const uint32_t*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_keys_spans(const int64_t* d_in, const uint32_t* d_spans, int k, const uint64_t* d_ids, uint32_t row_base,
+                                   uint32_t n_rows, wax_hip_hit* d_out, uint32_t out_stride, uint32_t nq, hipStream_t st) {
+    if (k > FUSED_MAX_K || k < 1 || out_stride < (uint32_t)k || nq == 0 || !d_spans) return hipErrorInvalidValue;
+    if (k <= 64)
+        hipLaunchKernelGGL((merge_keys_kernel<128>), dim3(nq), dim3(MERGE_THREADS), 0, st, d_in, 0u, k, (int)out_stride, d_ids,
+                           row_base, n_rows, d_out, (const uint32_t*)nullptr, out_stride, (const uint32_t*)nullptr, d_spans);
+    else
+        hipLaunchKernelGGL((merge_keys_kernel<256>), dim3(nq), dim3(MERGE_THREADS), 0, st, d_in, 0u, k, (int)out_stride, d_ids,
+                           row_base, n_rows, d_out, (const uint32_t*)nullptr, out_stride, (const uint32_t*)nullptr, d_spans);
     return hipGetLastError();
 }
 

@@ -113,7 +113,12 @@ __device__ inline void ms_halve_rows32(float (&v)[MS_M]) {
 // Which pair a lane ends with: value m = u * 16 + q, level L keeps bit L-1 of m = the lane's selection bit s_L with
 // s1 = b0^b2, s2 = b1^b2, s3 = b2^b3, s4 = b3 (b = lane bits; the XORs make mirror partners agree on the bits already
 // fixed), s5 = b4, s6 = b5: q = s1 + 2 s2 + 4 s3 + 8 s4 is a per-lane constant, u comes from the higher bits.
-template <int D4, int GROUP, int METRIC, int CAP>
+//
+// LISTED = true is the gather form of wax_hip_search_batch_filtered: workgroup blockIdx.x is work item blockIdx.x of a table
+// (a.item_group -> a.groups[]): one share of the rows of ONE compact row list (a.rows + row_off, ascending, a device-side count),
+// scored against the up to 16 queries that share that list. Position r of the list is row rows[r]; everything else — the loads
+// of a row, the lane mapping, the arithmetic, the key row_base + row — is the full-store form's, so distances are the same bits.
+template <int D4, int GROUP, int METRIC, int CAP, bool LISTED>
 __global__ __launch_bounds__(SCAN_THREADS) void scan_multi_kernel(ScanMultiArgs a) {
     constexpr int LOADS = D4 / GROUP;
     constexpr int RPW = WAVE / GROUP;
@@ -122,7 +127,19 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_multi_kernel(ScanMultiArgs 
     constexpr int OUT = MS_M >> LEVELS;          // complete sums per lane per chunk: 4 / 2 / 1
     static_assert(D4 % GROUP == 0 && (GROUP == 16 || GROUP == 32 || GROUP == 64), "GROUP");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const uint32_t nq = a.nq;
+    uint32_t nq = a.nq, n = a.n_rows, wg = blockIdx.x, nwg = gridDim.x, part0 = 0;
+    const uint32_t* qlist = a.qlist;
+    const float* qnorm = a.q_norm;
+    const uint32_t* __restrict__ rows = nullptr;
+    if constexpr (LISTED) {
+        const GatherGroup G = a.groups[a.item_group[blockIdx.x]];
+        nq = G.nq; n = a.row_counts[G.count_slot]; wg = blockIdx.x - G.item0; nwg = G.n_items; part0 = G.part_off;
+        qlist = a.qlist + G.q0; qnorm = a.q_norm + G.q0; rows = a.rows + G.row_off;
+    }
+    // partial list of query slot qi of this workgroup: [nq][grid][k] (full store) / [part_off + qi * n_items + wg] (listed)
+    auto partial_of = [&](uint32_t qi) -> int64_t* {
+        return a.partials + ((size_t)part0 + (size_t)qi * nwg + wg) * (size_t)a.k;
+    };
     f32x4* qs = reinterpret_cast<f32x4*>(smem);                                            // [16][D4] (slots >= nq: zeros)
     int64_t* lists = reinterpret_cast<int64_t*>(smem + (size_t)MS_NQ * D4 * 16);           // [SCAN_WAVES][16][CAP]
     MsState* state = reinterpret_cast<MsState*>(lists + (size_t)SCAN_WAVES * MS_NQ * CAP);  // [SCAN_WAVES][16]
@@ -133,15 +150,21 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_multi_kernel(ScanMultiArgs 
     const int wave = (int)(threadIdx.x >> 6);
     const int sub = lane / GROUP;
     const int gl = lane % GROUP;
-    const uint32_t n = a.n_rows;
     const int k = a.k;
+    if constexpr (LISTED) {
+        // a share beyond the list's device-side count (the grid was sized by an upper bound): empty partial lists
+        if (wg * (uint32_t)SCAN_WAVES >= (n + RPC - 1) / RPC) {
+            for (uint32_t i = threadIdx.x; i < nq * (uint32_t)k; i += SCAN_THREADS) partial_of(i / (uint32_t)k)[i % (uint32_t)k] = KEY_PAD;
+            return;
+        }
+    }
 
     for (uint32_t i = threadIdx.x; i < (uint32_t)MS_NQ * (uint32_t)D4; i += SCAN_THREADS) {
         const uint32_t qi = i / (uint32_t)D4, c = i - qi * (uint32_t)D4;
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-        qs[i] = qi < nq ? reinterpret_cast<const f32x4*>(a.queries)[(size_t)a.qlist[qi] * D4 + c] : zero;
+        qs[i] = qi < nq ? reinterpret_cast<const f32x4*>(a.queries)[(size_t)qlist[qi] * D4 + c] : zero;
     }
-    if (threadIdx.x < MS_NQ) qn_s[threadIdx.x] = threadIdx.x < nq ? a.q_norm[threadIdx.x] : 0.f;
+    if (threadIdx.x < MS_NQ) qn_s[threadIdx.x] = threadIdx.x < nq ? qnorm[threadIdx.x] : 0.f;
     for (uint32_t i = threadIdx.x; i < SCAN_WAVES * MS_NQ; i += SCAN_THREADS) { state[i].tau = KEY_PAD; state[i].cnt = 0; }
     __syncthreads();
 
@@ -160,25 +183,28 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_multi_kernel(ScanMultiArgs 
     const int last_of_group = (lane & ~(GROUP - 1)) | (GROUP - 1);
 
     const uint32_t nchunks = (n + RPC - 1) / RPC;
-    const uint32_t gwave = blockIdx.x * SCAN_WAVES + wave;
-    const uint32_t nwaves = gridDim.x * SCAN_WAVES;
+    const uint32_t gwave = wg * SCAN_WAVES + wave;
+    const uint32_t nwaves = nwg * SCAN_WAVES;
 
     // The rows of chunk c + 1 are requested BEFORE chunk c is scored (two register sets, the loop unrolled by two): a wave
     // computes ~4 400 VALU cycles per chunk — as long as the HBM round trip — and with two waves per SIMD nothing else would
     // cover that latency (PMC of the first version: waves parked 60 % of their cycles, VALU busy 45 %).
-    auto load_chunk = [&](f32x4 (&v)[MS_U][LOADS], uint32_t chunk) {
+    auto load_chunk = [&](f32x4 (&v)[MS_U][LOADS], uint32_t (&rr)[MS_U], uint32_t chunk) {
         const uint32_t rbase = chunk * RPC + sub;
 #pragma unroll
         for (int u = 0; u < MS_U; ++u) {
             const uint32_t r = rbase + u * RPW;
             const uint32_t rc = r < n ? r : n - 1;   // clamp: tail lanes re-read the last row, result discarded
-            const f32x4* p = store4 + (size_t)rc * D4 + gl;
+            const uint32_t row = LISTED ? rows[rc] : rc;
+            rr[u] = row;
+            const f32x4* p = store4 + (size_t)row * D4 + gl;
 #pragma unroll
             for (int j = 0; j < LOADS; ++j) v[u][j] = __builtin_nontemporal_load(p + j * GROUP);
         }
     };
-    auto score_chunk = [&](const f32x4 (&v)[MS_U][LOADS], uint32_t chunk) {
+    auto score_chunk = [&](const f32x4 (&v)[MS_U][LOADS], const uint32_t (&rr)[MS_U], uint32_t chunk) {
         const uint32_t rbase = chunk * RPC + sub;
+        const uint32_t rr0 = rr[0], rr1 = rr[1], rr2 = rr[2], rr3 = rr[3];   // (named: see row_norm)
         // ||v||^2 per row-group, scan_kernel's chain and reduction, then handed to every lane of the group
         // (four named scalars, not an array: a `b4 ? nb[1] : nb[0]` on an array is rewritten into a load from a lane-indexed
         // stack copy — scratch traffic in the hot loop)
@@ -231,12 +257,13 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_multi_kernel(ScanMultiArgs 
         for (int j = 0; j < OUT; ++j) {
             int u;
             float nrm;
-            if (GROUP == 16) { u = j; nrm = j == 0 ? nb0 : (j == 1 ? nb1 : (j == 2 ? nb2 : nb3)); }
-            else if (GROUP == 32) { u = b4 + 2 * j; nrm = j == 0 ? (b4 ? nb1 : nb0) : (b4 ? nb3 : nb2); }
-            else { u = b4 + 2 * b5; nrm = b5 ? (b4 ? nb3 : nb2) : (b4 ? nb1 : nb0); }
+            uint32_t row;
+            if (GROUP == 16) { u = j; nrm = j == 0 ? nb0 : (j == 1 ? nb1 : (j == 2 ? nb2 : nb3)); row = j == 0 ? rr0 : (j == 1 ? rr1 : (j == 2 ? rr2 : rr3)); }
+            else if (GROUP == 32) { u = b4 + 2 * j; nrm = j == 0 ? (b4 ? nb1 : nb0) : (b4 ? nb3 : nb2); row = j == 0 ? (b4 ? rr1 : rr0) : (b4 ? rr3 : rr2); }
+            else { u = b4 + 2 * b5; nrm = b5 ? (b4 ? nb3 : nb2) : (b4 ? nb1 : nb0); row = b5 ? (b4 ? rr3 : rr2) : (b4 ? rr1 : rr0); }
             const float d = ms_finish<METRIC>(part[j], nrm, qn_lane);
             const uint32_t r = rbase + (uint32_t)u * RPW;
-            const int64_t key = make_key(d, a.row_base + r);
+            const int64_t key = make_key(d, a.row_base + (LISTED ? row : r));
             const bool pass = q_live && (r < n) && (key < tau_lane);
             unsigned long long todo = __ballot(pass);
             while (todo != 0ull) {                               // rare after warm-up: one list at a time
@@ -265,23 +292,24 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_multi_kernel(ScanMultiArgs 
     };
     {
         f32x4 va[MS_U][LOADS], vb[MS_U][LOADS];
+        uint32_t ra[MS_U], rb[MS_U];
         // The prefetch is UNCONDITIONAL (past the end it re-requests the current chunk: L2 hits, discarded): behind a branch
         // the compiler no longer knows how many requests are outstanding and waits vmcnt(0) for the current set — which
         // drains the prefetch it was meant to overlap.
         uint32_t chunk = gwave;
         if (chunk < nchunks) {
-            load_chunk(va, chunk);
+            load_chunk(va, ra, chunk);
             for (;;) {
                 uint32_t nxt = chunk + nwaves;
-                load_chunk(vb, nxt < nchunks ? nxt : chunk);
+                load_chunk(vb, rb, nxt < nchunks ? nxt : chunk);
                 __builtin_amdgcn_sched_barrier(0);    // the requests go out before the first use of the current set
-                score_chunk(va, chunk);
+                score_chunk(va, ra, chunk);
                 chunk = nxt;
                 if (chunk >= nchunks) break;
                 nxt = chunk + nwaves;
-                load_chunk(va, nxt < nchunks ? nxt : chunk);
+                load_chunk(va, ra, nxt < nchunks ? nxt : chunk);
                 __builtin_amdgcn_sched_barrier(0);
-                score_chunk(vb, chunk);
+                score_chunk(vb, rb, chunk);
                 chunk = nxt;
                 if (chunk >= nchunks) break;
             }
@@ -299,7 +327,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_multi_kernel(ScanMultiArgs 
     for (uint32_t qi = 0; qi < nq; ++qi)
         block_rank_merge_impl((const lds_i64*)(lists + (size_t)qi * CAP), SCAN_WAVES, (int)(MS_NQ * CAP),
                               (const lds_i32*)(counts + qi * SCAN_WAVES), k,
-                              a.partials + ((size_t)qi * gridDim.x + blockIdx.x) * k);
+                              partial_of(qi));
 }
 
 // ---------------------------------------------------------------------------
@@ -354,26 +382,41 @@ int scan_multi_grid(uint32_t n_rows, uint32_t dims, int grid_cap) {
     return (int)blocks;
 }
 
-template <int D4, int GROUP, int METRIC, int CAP>
+template <int D4, int GROUP, int METRIC, int CAP, bool LISTED>
 static hipError_t ms_launch_one(const ScanMultiArgs& a, int grid, size_t smem, hipStream_t st) {
     static std::atomic<uint64_t> configured{0};   // per device (ensure_dynamic_lds)
     if (smem > 64 * 1024) {
-        hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_multi_kernel<D4, GROUP, METRIC, CAP>), 160 * 1024, configured);
+        hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_multi_kernel<D4, GROUP, METRIC, CAP, LISTED>), 160 * 1024, configured);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((scan_multi_kernel<D4, GROUP, METRIC, CAP>), dim3(grid), dim3(SCAN_THREADS), smem, st, a);
+    hipLaunchKernelGGL((scan_multi_kernel<D4, GROUP, METRIC, CAP, LISTED>), dim3(grid), dim3(SCAN_THREADS), smem, st, a);
     return hipGetLastError();
 }
 
-template <int D4, int GROUP>
+template <int D4, int GROUP, bool LISTED>
 static hipError_t ms_launch(const ScanMultiArgs& a, int metric, int cap, int grid, size_t smem, hipStream_t st) {
     switch (metric * 2 + (cap == 64 ? 0 : 1)) {
-        case MS_COS * 2: return ms_launch_one<D4, GROUP, MS_COS, 64>(a, grid, smem, st);
-        case MS_COS * 2 + 1: return ms_launch_one<D4, GROUP, MS_COS, 256>(a, grid, smem, st);
-        case MS_DOT * 2: return ms_launch_one<D4, GROUP, MS_DOT, 64>(a, grid, smem, st);
-        case MS_DOT * 2 + 1: return ms_launch_one<D4, GROUP, MS_DOT, 256>(a, grid, smem, st);
-        case MS_L2 * 2: return ms_launch_one<D4, GROUP, MS_L2, 64>(a, grid, smem, st);
-        case MS_L2 * 2 + 1: return ms_launch_one<D4, GROUP, MS_L2, 256>(a, grid, smem, st);
+        case MS_COS * 2: return ms_launch_one<D4, GROUP, MS_COS, 64, LISTED>(a, grid, smem, st);
+        case MS_COS * 2 + 1: return ms_launch_one<D4, GROUP, MS_COS, 256, LISTED>(a, grid, smem, st);
+        case MS_DOT * 2: return ms_launch_one<D4, GROUP, MS_DOT, 64, LISTED>(a, grid, smem, st);
+        case MS_DOT * 2 + 1: return ms_launch_one<D4, GROUP, MS_DOT, 256, LISTED>(a, grid, smem, st);
+        case MS_L2 * 2: return ms_launch_one<D4, GROUP, MS_L2, 64, LISTED>(a, grid, smem, st);
+        case MS_L2 * 2 + 1: return ms_launch_one<D4, GROUP, MS_L2, 256, LISTED>(a, grid, smem, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+template <bool LISTED>
+static hipError_t ms_dispatch(const ScanMultiArgs& a, int metric, int cap, int grid, size_t smem, hipStream_t st) {
+    switch (a.dims) {   // (D4, GROUP) = launch_scan's table
+        case 64: return ms_launch<16, 16, LISTED>(a, metric, cap, grid, smem, st);
+        case 128: return ms_launch<32, 32, LISTED>(a, metric, cap, grid, smem, st);
+        case 256: return ms_launch<64, 64, LISTED>(a, metric, cap, grid, smem, st);
+        case 384: return ms_launch<96, 32, LISTED>(a, metric, cap, grid, smem, st);
+        case 512: return ms_launch<128, 64, LISTED>(a, metric, cap, grid, smem, st);
+        case 768: return ms_launch<192, 64, LISTED>(a, metric, cap, grid, smem, st);
+        case 1024: return ms_launch<256, 64, LISTED>(a, metric, cap, grid, smem, st);
+        case 1536: return ms_launch<384, 64, LISTED>(a, metric, cap, grid, smem, st);
         default: return hipErrorInvalidValue;
     }
 }
@@ -385,17 +428,25 @@ hipError_t launch_scan_multi(const ScanMultiArgs& a, int metric, int grid_cap, h
     if (smem > 160 * 1024) return hipErrorInvalidValue;
     const int grid = scan_multi_grid(a.n_rows, a.dims, grid_cap);
     if (out_grid) *out_grid = grid;
-    switch (a.dims) {   // (D4, GROUP) = launch_scan's table
-        case 64: return ms_launch<16, 16>(a, metric, cap, grid, smem, st);
-        case 128: return ms_launch<32, 32>(a, metric, cap, grid, smem, st);
-        case 256: return ms_launch<64, 64>(a, metric, cap, grid, smem, st);
-        case 384: return ms_launch<96, 32>(a, metric, cap, grid, smem, st);
-        case 512: return ms_launch<128, 64>(a, metric, cap, grid, smem, st);
-        case 768: return ms_launch<192, 64>(a, metric, cap, grid, smem, st);
-        case 1024: return ms_launch<256, 64>(a, metric, cap, grid, smem, st);
-        case 1536: return ms_launch<384, 64>(a, metric, cap, grid, smem, st);
-        default: return hipErrorInvalidValue;
-    }
+    return ms_dispatch<false>(a, metric, cap, grid, smem, st);
+}
+
+uint32_t scan_multi_listed_items(uint64_t max_rows, uint32_t dims, int grid_cap) {
+    if (ms_group_lanes(dims) == 0 || max_rows == 0) return 1;
+    // ~8 chunks per wave: few enough workgroups that the per-workgroup query load and list merge stay small beside the rows
+    const uint64_t per_wg = (uint64_t)ms_rows_per_chunk(dims) * SCAN_WAVES * 8;
+    uint64_t w = (max_rows + per_wg - 1) / per_wg;
+    if (grid_cap <= 0) grid_cap = 512;
+    if (w > (uint64_t)grid_cap) w = (uint64_t)grid_cap;
+    return w < 1 ? 1u : (uint32_t)w;
+}
+
+hipError_t launch_scan_multi_listed(const ScanMultiArgs& a, int metric, uint32_t n_items, hipStream_t st) {
+    const int cap = scan_multi_cap(a.dims, a.k);
+    if (cap == 0 || n_items == 0 || !a.rows || !a.row_counts || !a.groups || !a.item_group) return hipErrorInvalidValue;
+    const size_t smem = scan_multi_lds_bytes(a.dims, cap);
+    if (smem > 160 * 1024) return hipErrorInvalidValue;
+    return ms_dispatch<true>(a, metric, cap, (int)n_items, smem, st);
 }
 
 }  // namespace wax

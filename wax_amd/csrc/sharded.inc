@@ -1186,6 +1186,53 @@ int sh_search_filtered(wax_hip_engine* e, const float* query, uint32_t dims, int
     return WAX_HIP_OK;
 }
 
+// Batched form: every shard answers the whole batch on its own rows (its own batched filtered call, on the handle's workers, in
+// parallel); then each query is merged exactly as sh_search_filtered merges one: stable by score, shard order on ties, then the cut.
+int sh_search_batch_filtered(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k, const uint64_t* allow,
+                             uint64_t n_allow_ids, const uint64_t* allow_begin, const uint64_t* allow_len, const float* min_scores,
+                             uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts) {
+    ShardedState* s = e->sh;
+    if (dims != e->dims) return fail(WAX_HIP_ERR_DIM_MISMATCH, dim_mismatch_msg(e->dims, dims));
+    if (out_stride == 0) return WAX_HIP_OK;
+    e->lock.lock_shared(holding(e) > 0);
+    struct Unlock { RWLock& l; ~Unlock() { l.unlock_shared(); } } unlock{e->lock};
+    const uint32_t limit = (uint32_t)clamp_topk(top_k);
+    const size_t G = s->subs.size();
+    std::vector<std::vector<uint64_t>> g_ids(G, std::vector<uint64_t>((size_t)nq * limit));
+    std::vector<std::vector<float>> g_scores(G, std::vector<float>((size_t)nq * limit));
+    std::vector<std::vector<uint32_t>> g_m(G, std::vector<uint32_t>(nq, 0));
+    std::vector<int> rcs(G, WAX_HIP_OK);
+    std::vector<std::string> errs(G);
+    auto one = [&](size_t g) {
+        rcs[g] = wax_hip_search_batch_filtered(s->subs[g], queries, nq, dims, top_k, allow, n_allow_ids, allow_begin, allow_len, nullptr,
+                                               g_ids[g].data(), g_scores[g].data(), limit, g_m[g].data());
+        if (rcs[g] != WAX_HIP_OK) errs[g] = g_last_error;   // thread-local: carry it to the caller
+    };
+    if (G == 1) one(0); else s->workers.run_all(one);
+    for (size_t g = 0; g < G; ++g)
+        if (rcs[g] != WAX_HIP_OK) return fail(rcs[g], errs[g]);
+    struct Hit { float score; uint64_t id; };
+    std::vector<Hit> all;
+    for (uint32_t q = 0; q < nq; ++q) {
+        all.clear();
+        for (size_t g = 0; g < G; ++g)
+            for (uint32_t i = 0; i < g_m[g][q]; ++i) all.push_back(Hit{g_scores[g][(size_t)q * limit + i], g_ids[g][(size_t)q * limit + i]});
+        std::stable_sort(all.begin(), all.end(), [](const Hit& a, const Hit& b) { return a.score > b.score; });
+        uint32_t m = 0;
+        uint64_t* ids = out_ids + (size_t)q * out_stride;
+        float* scores = out_scores + (size_t)q * out_stride;
+        for (size_t i = 0; i < all.size() && m < limit && m < out_stride; ++i, ++m) { ids[m] = all[i].id; scores[m] = all[i].score; }
+        if (min_scores) {   // `score < minScore` drops a candidate (NaN: no cut)
+            uint32_t keep = 0;
+            for (uint32_t i = 0; i < m; ++i)
+                if (!(scores[i] < min_scores[q])) { ids[keep] = ids[i]; scores[keep] = scores[i]; ++keep; }
+            m = keep;
+        }
+        out_counts[q] = m;
+    }
+    return WAX_HIP_OK;
+}
+
 // ---- persistence ------------------------------------------------------------------------------------------------------------
 
 int sh_serialize(wax_hip_engine* e, uint8_t** out_bytes, size_t* out_len) {
@@ -1349,7 +1396,7 @@ int64_t sh_get_tuning(wax_hip_engine* e, const std::string& k) {
     if (k == "rebalances") return (int64_t)s->rebalances.load();
     if (k == "parallel_collects") return (int64_t)s->parallel_collects.load();
     if (k == "parallel_submits") return (int64_t)s->parallel_submits.load();
-    if (k == "batch_queries" || k == "batch_fallbacks" || k == "batch_retries" || k == "onepass_queries" || k == "filter_device_searches" || k == "query_args_scans" || k == "batch_inline_retries" ||
+    if (k == "batch_queries" || k == "batch_fallbacks" || k == "batch_retries" || k == "onepass_queries" || k == "filter_device_searches" || k == "filter_batch_queries" || k == "filter_batch_fallbacks" || k == "query_args_scans" || k == "batch_inline_retries" ||
         k == "batch_multi_passes" || k == "batch_multi_queries" || k == "short_selects" || k == "short_select_failures" ||
         k == "mirror_scans" || k == "mirror_scan_fallbacks" || k == "mirror_scan_unavailable") {   // counters: summed over the shards
         int64_t t = 0;

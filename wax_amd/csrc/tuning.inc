@@ -66,6 +66,7 @@ int wax_hip_set_tuning(wax_hip_engine* e, const char* key, int64_t value) {
     else if (k == "batch_multi") e->batch_multi = value != 0;
     else if (k == "scan_chain") { if (value < -1 || value > 1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "scan_chain must be -1 (auto), 0 or 1"); e->scan_chain = value; }
     else if (k == "share_timing") e->share_timing = value != 0;   // 0: every chained scan records its own start event (one more packet between scans)
+    else if (k == "filter_batch") { if (value < 0 || value > 1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "filter_batch must be 0 or 1"); e->filter_batch = value; }
     else if (k == "filter_device_min") { if (value < -1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "filter_device_min must be >= -1"); e->filter_device_min = value; }
     else if (k == "batch_sample_div") { if (value < 4 || value > 4096) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_sample_div must be 4..4096"); e->batch_sample_div = value; }
     else if (k == "batch_workspaces") {
@@ -184,6 +185,9 @@ int64_t wax_hip_get_tuning(wax_hip_engine* e, const char* key) {
     if (k == "batch_multi_group_big") return (int64_t)scan_multi_group(e->dims, 192);   // ... k <= 192 (256-slot lists)
     if (k == "filter_device_min") return e->filter_device_min.load();
     if (k == "filter_device_searches") return (int64_t)e->st_filter_device.load();
+    if (k == "filter_batch") return e->filter_batch.load();
+    if (k == "filter_batch_queries") return (int64_t)e->st_filter_batch_queries.load();
+    if (k == "filter_batch_fallbacks") return (int64_t)e->st_filter_batch_fallbacks.load();
     if (k == "batch_queries") return (int64_t)e->st_batch_queries.load();
     if (k == "batch_fallbacks") return (int64_t)e->st_batch_fallbacks.load();
     if (k == "slots") return e->max_slots;

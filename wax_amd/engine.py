@@ -33,6 +33,31 @@ def _u64p(a: np.ndarray):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
 
 
+def pack_allow_lists(frameIds, nq: int):
+    """Per-query allow-lists -> (flat u64 ids, begin, length) for wax_hip_search_batch_filtered. frameIds None: no lists (begin and
+    length None). An entry None: no list (length NO_ALLOW_LIST). The same object given for several queries is packed once, so those
+    queries share one (begin, length) and the library resolves their list once."""
+    if frameIds is None:
+        return np.zeros(0, dtype=np.uint64), None, None
+    if len(frameIds) != nq:
+        raise EncodingError("searchBatchFiltered: frameIds must hold one entry per query")
+    begin = np.zeros(nq, dtype=np.uint64)
+    length = np.full(nq, _abi.NO_ALLOW_LIST, dtype=np.uint64)
+    parts, seen, off = [], {}, 0
+    for q, lst in enumerate(frameIds):
+        if lst is None:
+            continue
+        key = id(lst)
+        if key not in seen:
+            arr = np.ascontiguousarray(lst if isinstance(lst, np.ndarray) else list(lst), dtype=np.uint64).reshape(-1)
+            seen[key] = (off, arr.size)
+            parts.append(arr)
+            off += arr.size
+        begin[q], length[q] = seen[key]
+    flat = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint64)
+    return np.ascontiguousarray(flat, dtype=np.uint64), begin, length
+
+
 def clampTopK(topK: int) -> int:  # noqa: N802,N803 — MetalVectorEngine.clampTopK (:842-846)
     if topK < 1:
         return 1
@@ -295,6 +320,36 @@ class HIPVectorEngine:
         counts = np.zeros(nq, dtype=np.uint32)
         rc = self._lib.wax_hip_search_batch(self._h, _fp(qs), nq, width, int(topK), _u64p(ids), _fp(scores), kcap,
                                             counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+        raise_for_status(rc)
+        return ids, scores, counts
+
+    def searchBatchFiltered(self, vectors, topK: int, frameIds=None, minScore=None):  # noqa: N802,N803
+        """searchFiltered for a batch (wax_hip_search_batch_filtered): `frameIds` is None or a length-nq sequence whose entries
+        are None (no list) or an iterable of frame ids; `minScore` is None, one float, or a length-nq sequence (None entries: no
+        cut). Returns (ids[nq, kcap], scores, counts) like searchBatch; row q equals searchFiltered for that query."""
+        qs = _as_f32(vectors)
+        if qs.ndim != 2:
+            raise EncodingError("searchBatchFiltered: vectors must be [nq, dims]")
+        nq, width = qs.shape
+        kcap = max(1, min(clampTopK(topK), max(self.count, 1)))
+        ids = np.zeros((nq, kcap), dtype=np.uint64)
+        scores = np.zeros((nq, kcap), dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        flat, begin, length = pack_allow_lists(frameIds, nq)
+        cuts = None
+        if minScore is not None:
+            if np.ndim(minScore) == 0:
+                cuts = np.full(nq, float(minScore), dtype=np.float32)
+            else:
+                if len(minScore) != nq:
+                    raise EncodingError("searchBatchFiltered: minScore must hold one entry per query")
+                cuts = np.array([np.nan if m is None else float(m) for m in minScore], dtype=np.float32)
+        rc = self._lib.wax_hip_search_batch_filtered(
+            self._h, _fp(qs), nq, width, int(max(min(topK, 2**31 - 1), -2**31)),
+            None if flat.size == 0 else _u64p(flat), int(flat.size),
+            None if begin is None else _u64p(begin), None if length is None else _u64p(length),
+            None if cuts is None else _fp(cuts), _u64p(ids), _fp(scores), kcap,
+            counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
         raise_for_status(rc)
         return ids, scores, counts
 
