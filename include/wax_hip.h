@@ -165,6 +165,17 @@ int wax_hip_add_batch_device(wax_hip_engine* e, const uint64_t* frame_ids, const
 int wax_hip_apply_put_embeddings(wax_hip_engine* e, const uint8_t* payloads, uint64_t len, uint64_t* out_applied);
 /* remove(frameId:) — order-preserving delete, absent id is a no-op (MetalVectorEngine.swift:423-444). */
 int wax_hip_remove(wax_hip_engine* e, uint64_t frame_id);
+/* remove(frameId:) for many ids at once (the loop of VectorSearchSession.swift:188-192 as one call). The engine ends in exactly
+ * the state that calling wax_hip_remove(e, frame_ids[i]) for i = 0 .. n-1 would leave: absent ids are ignored, an id listed twice
+ * counts once, the surviving rows keep their order. *out_removed (may be NULL) = rows actually removed. n == 0 is a no-op.
+ * One exclusive-lock acquisition and ONE order-preserving compaction pass: every surviving row behind the first removed one moves
+ * down once, by the number of removed rows in front of it (store, frame ids, and the bf16 mirror with its norms, which is
+ * compacted, not converted again); the host's id vector and id map are fixed in one pass each. Extra device memory: the 64 MB
+ * bounce buffer and 4 bytes per removed row, whatever the store's size. Arguments, the row list's upload and the scratch
+ * allocation are checked before the first row moves. A store that holds one frame id in several rows (only wax_hip_deserialize
+ * can produce one; detected exactly, by the id map holding fewer ids than the store has rows) is answered by the per-id loop
+ * instead — same result, n passes. On a sharded handle every shard that owns listed ids compacts once. */
+int wax_hip_remove_batch(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, uint64_t* out_removed);
 /* reserveIfNeeded(for:) (MetalVectorEngine.swift:857-871): capacity doubling from 64, cap UInt32.max rows. */
 int wax_hip_reserve(wax_hip_engine* e, uint64_t rows);
 
@@ -400,6 +411,12 @@ int wax_hip_stats(wax_hip_engine* e, wax_hip_stats_t* out);
  *   single-query kernel; 0 = one scan per query),
  *   "batch_in_wait" (device-resident batches: 0 (default) = the library's stream is ordered behind the caller's `stream` by an event
  *   only while that stream still has work pending — a drained stream costs no marker / barrier packet; 1 = always, as before round 6).
+ * removeBatch (wax_hip_remove_batch)
+ *   "compact_window_rows" (source rows per window of the compaction pass; 0 (default) = as many as the bounce buffer holds of every
+ *   per-row array at once, larger values are capped there; a window whose shift is below its length goes through the bounce buffer,
+ *   one whose shift has reached this many rows moves directly and is as long as its shift),
+ *   get-only "remove_batches" (calls that removed rows in one pass), "remove_batch_rows" (rows they removed),
+ *   "remove_batch_bytes_written" (device bytes their passes wrote, bounce writes included).
  * get-only
  *   "variant_count", "scan_grid", "store_ptr" (device address of the f32 slab), "fused_max_k", "batch_queries", "query_args_scans", "merged_scans", "done_flag_waits",
  *   "batch_inline_retries", "batch_max_row_err_e9", "batch_fallbacks", "onepass_queries", "batch_max_k", "batch_retries",

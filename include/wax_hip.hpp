@@ -94,6 +94,12 @@ class VectorEngine {
                                 (uint32_t)(rowsRowMajor.size() / frameIds.size())));
     }
     void remove(uint64_t frameId) { check(wax_hip_remove(h_, frameId)); }
+    /// remove() for many ids in one compaction pass; returns the rows removed (absent ids are ignored, repeated ones count once).
+    uint64_t removeBatch(const std::vector<uint64_t>& frameIds) {
+        uint64_t removed = 0;
+        if (!frameIds.empty()) check(wax_hip_remove_batch(h_, frameIds.data(), frameIds.size(), &removed));
+        return removed;
+    }
     std::vector<uint8_t> serialize() {
         uint8_t* p = nullptr;
         size_t len = 0;

@@ -216,6 +216,24 @@ public actor HIPVectorEngine {
         dirty = true
     }
 
+    /// `remove(frameId:)` for many frames in ONE compaction pass (`wax_hip_remove_batch`): what
+    /// WaxVectorSearchSession.stageForCommit's loop over `pendingRemovedFrameIds` (VectorSearchSession.swift:188-192)
+    /// switches to. Absent ids are ignored, an id listed twice counts once; returns the rows removed.
+    @discardableResult
+    public func removeBatch(frameIds: [UInt64]) async throws -> Int {
+        guard !frameIds.isEmpty else { return 0 }
+        let h = handle
+        let removed: UInt64 = try await io.run {
+            var n: UInt64 = 0
+            try Self.check(frameIds.withUnsafeBufferPointer { ids in
+                wax_hip_remove_batch(h.raw, ids.baseAddress, UInt64(ids.count), &n)
+            })
+            return n
+        }
+        if removed > 0 { dirty = true }
+        return Int(removed)
+    }
+
     public func serialize() async throws -> Data {
         let h = handle
         return try await io.run {

@@ -105,6 +105,7 @@ SIGNATURES: Dict[str, tuple] = {
                                                        ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
     "wax_hip_add_batch_device": (ctypes.c_int, [_engine_p, _u64p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32]),
     "wax_hip_remove": (ctypes.c_int, [_engine_p, ctypes.c_uint64]),
+    "wax_hip_remove_batch": (ctypes.c_int, [_engine_p, _u64p, ctypes.c_uint64, _u64p]),
     "wax_hip_reserve": (ctypes.c_int, [_engine_p, ctypes.c_uint64]),
     "wax_hip_result_capacity": (ctypes.c_uint32, [ctypes.c_int32]),
     "wax_hip_search": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_int32, _u64p, _f32p, ctypes.c_uint32, _u32p]),

@@ -1,5 +1,5 @@
 // api_store.inc — part of engine.hip's translation unit (included there; not compiled alone).
-// C ABI: availability, create / destroy, accessors, reserve / add / add_batch / add_batch_device / apply_put_embeddings / remove
+// C ABI: availability, create / destroy, accessors, reserve / add / add_batch / add_batch_device / apply_put_embeddings / remove / remove_batch
 
 // ===========================================================================
 // C ABI
@@ -333,6 +333,89 @@ int wax_hip_remove(wax_hip_engine* e, uint64_t frame_id) {
     e->ids.erase(e->ids.begin() + idx);                   // :440
     e->idmap.erase_row(frame_id, (uint32_t)idx);
     e->count -= 1;                                        // :441
+    return WAX_HIP_OK;
+}
+
+int wax_hip_remove_batch(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, uint64_t* out_removed) {
+    if (out_removed) *out_removed = 0;
+    if (!e) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine is null");
+    if (e->sh) return sh_remove_batch(e, frame_ids, n, out_removed);
+    if (n == 0) return WAX_HIP_OK;
+    if (!frame_ids) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "removeBatch: null input");
+    REFUSE_IF_HOLDING(e);
+    bool repeated_ids = false;
+    {
+        DeviceGuard g(e->device);
+        WriteGuard w(e->lock);
+        sync_shard_work(e);
+        if (e->count == 0) return WAX_HIP_OK;                 // :425
+        { const int frc = flush_pending(e); if (frc != WAX_HIP_OK) return frc; }   // staged rows may be among the ids; the pass works on device rows
+        // One id -> one row is what the one-pass map relies on. Only deserialize can put a frame id into several rows, and the id
+        // map then holds fewer ids than the store has rows: such a store takes the per-id loop below.
+        repeated_ids = e->idmap.size() != e->count;
+        if (!repeated_ids) {
+            // ---- everything that can fail without touching the store ----
+            std::vector<uint32_t> rem;
+            rem.reserve((size_t)std::min<uint64_t>(n, e->count));
+            for (uint64_t i = 0; i < n; ++i) {
+                const int64_t r = e->idmap.find(frame_ids[i]);
+                if (r >= 0) rem.push_back((uint32_t)r);        // :426 absent ids are ignored
+            }
+            std::sort(rem.begin(), rem.end());
+            rem.erase(std::unique(rem.begin(), rem.end()), rem.end());   // an id listed twice counts once
+            if (rem.empty()) return WAX_HIP_OK;
+            const uint64_t m = rem.size();
+            e->batch.mirror_wanted = 0;
+            BatchMirror& b = e->batch;
+            const bool moves = rem[0] + m < e->count;          // false: the removed rows are the store's tail, nothing moves
+            uint32_t* d_rem = nullptr;
+            bool follow = false;                               // the mirror's rows move with the store's
+            uint64_t written = 0;
+            if (moves) {
+                if (!e->d_bounce)
+                    HIP_TRY(hipMalloc(&e->d_bounce, kBounceBytes), WAX_HIP_ERR_ALLOC, "Failed to allocate bounce buffer");
+                HIP_TRY(hipMalloc(&d_rem, (size_t)m * sizeof(uint32_t)), WAX_HIP_ERR_ALLOC, "Failed to allocate the removed-row list");
+                hipError_t err = hipMemcpy(d_rem, rem.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice);
+                if (err != hipSuccess) { (void)hipFree(d_rem); return fail(WAX_HIP_ERR_INTERNAL, std::string("removed-row list upload: ") + hipGetErrorString(err)); }
+                follow = !b.stale && b.d_cb != nullptr && rem[0] < b.rows;
+                if (b.ev_pending) { (void)hipEventSynchronize(b.ev_ready); b.ev_pending = false; }   // a conversion in flight reads the store and writes the mirror
+                // ---- the device pass ----
+                const int rc = compact_removed_rows(e, rem, d_rem, follow ? b.rows.load() : 0, &written);
+                (void)hipFree(d_rem);
+                if (rc != WAX_HIP_OK) { (void)hipGetLastError(); mirror_note_lost(e); return rc; }   // (a failed launch or copy: as in remove, the rows behind rem[0] are lost with it)
+            } else {
+                follow = true;                                 // the mirror's tail is simply cut off with the store's
+            }
+            // ---- host bookkeeping, committed after the device pass has completed ----
+            mirror_note_remove_batch(e, rem, follow);
+            for (uint32_t r : rem) e->idmap.erase_only(e->ids[r]);
+            e->idmap.renumber_removed(rem, e->count);
+            {
+                uint64_t wr = rem[0];
+                size_t p = 0;
+                for (uint64_t r = rem[0]; r < e->count; ++r) {
+                    if (p < m && rem[p] == r) { ++p; continue; }
+                    e->ids[wr++] = e->ids[r];
+                }
+                e->ids.resize((size_t)wr);
+            }
+            e->count -= m;                                     // :441, m times
+            e->st_remove_batches += 1;
+            e->st_remove_batch_rows += m;
+            e->st_remove_batch_bytes += written;
+            if (out_removed) *out_removed = m;
+            return WAX_HIP_OK;
+        }
+    }
+    // a store with a frame id in several rows: remove(frameId:) per id, exactly the loop this call stands for
+    uint64_t removed = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t before = e->count;
+        const int rc = wax_hip_remove(e, frame_ids[i]);
+        if (rc != WAX_HIP_OK) { if (out_removed) *out_removed = removed; return rc; }
+        if (e->count < before) removed += before - e->count;
+    }
+    if (out_removed) *out_removed = removed;
     return WAX_HIP_OK;
 }
 

@@ -60,6 +60,104 @@ static int mirror_note_remove(wax_hip_engine* e, uint64_t idx) {
     return WAX_HIP_OK;
 }
 
+// removeBatch: the rows `rem` (ascending, distinct) leave the store in one compaction pass (compact.hip; DESIGN 4.7). `mirror_rows`
+// > 0 = the mirror and its norms follow, rows below that fill. Enqueues on the null stream and waits for it; *bytes_written = device
+// bytes the pass wrote, bounce writes included. Nothing on the host side is touched here. Called BEFORE count drops.
+static int compact_removed_rows(wax_hip_engine* e, const std::vector<uint32_t>& rem, const uint32_t* d_rem, uint64_t mirror_rows,
+                                uint64_t* bytes_written) {
+    const uint32_t m = (uint32_t)rem.size();
+    const uint64_t count = e->count;
+    const uint32_t D = e->dims;
+    BatchMirror& b = e->batch;
+    struct Arr { char* base; uint64_t rb; uint64_t limit; uint64_t rank_limit; uint64_t sect; };
+    Arr arrs[kCompactMaxArrays];
+    int na = 0;
+    arrs[na++] = Arr{reinterpret_cast<char*>(e->d_store), (uint64_t)D * sizeof(float), count, m, 0};
+    arrs[na++] = Arr{reinterpret_cast<char*>(e->d_ids), sizeof(uint64_t), count, m, 0};
+    if (mirror_rows > 0) {
+        const uint64_t pl = (uint64_t)(std::lower_bound(rem.begin(), rem.end(), (uint32_t)std::min<uint64_t>(mirror_rows, 0xffffffffull)) - rem.begin());
+        arrs[na++] = Arr{reinterpret_cast<char*>(b.d_cb), (uint64_t)D * sizeof(unsigned short), mirror_rows, pl, 0};
+        arrs[na++] = Arr{reinterpret_cast<char*>(b.d_vn2), sizeof(float), mirror_rows, pl, 0};
+    }
+    // window = as many source rows as the bounce buffer holds of all arrays at once (each array has its own 256-byte-aligned section)
+    uint64_t per_row = 0;
+    for (int i = 0; i < na; ++i) per_row += arrs[i].rb;
+    uint64_t window = (kBounceBytes - 256ull * kCompactMaxArrays) / per_row;
+    if (window < 1) return fail(WAX_HIP_ERR_CAPACITY, "removeBatch: one row of every per-row array does not fit the bounce buffer");
+    const uint64_t want = (uint64_t)e->compact_window_rows.load();
+    if (want > 0 && want < window) window = want;
+    {
+        uint64_t off = 0;
+        for (int i = 0; i < na; ++i) { arrs[i].sect = off; off += (window * arrs[i].rb + 255ull) & ~255ull; }
+    }
+    const bool nt = (count - rem[0]) * arrs[0].rb > (64ull << 20);    // the tail is streamed once: keep it out of the caches when it is far larger than L2
+    char* bounce = static_cast<char*>(e->d_bounce);
+    uint64_t written = 0;
+    uint64_t w0 = rem[0];
+    uint32_t p = 0;
+    for (;;) {
+        while (p < m && rem[p] == w0) { ++p; ++w0; }                  // a window starts at a surviving row
+        if (w0 >= count) break;
+        const uint64_t shift = p;                                     // rank(w0) >= 1
+        const bool direct = shift >= window;                          // destination [w0 - shift, ...) ends at or below w0 for len <= shift
+        const uint64_t len = direct ? shift : window;
+        const uint64_t w1 = std::min<uint64_t>(count, w0 + len);
+        const uint32_t p1 = (uint32_t)(std::lower_bound(rem.begin() + p, rem.end(), (uint32_t)std::min<uint64_t>(w1, 0xffffffffull)) - rem.begin());
+        const uint64_t dst0 = w0 - shift;
+        RowCompactArgs a{};
+        a.rem = d_rem; a.p0 = p; a.p1 = p1; a.w0 = (uint32_t)w0; a.w1 = (uint32_t)w1; a.dst0 = (uint32_t)dst0;
+        uint64_t surv[kCompactMaxArrays];
+        int idx[kCompactMaxArrays];
+        for (int i = 0; i < na; ++i) {
+            const Arr& r = arrs[i];
+            if (r.limit <= w0) continue;                              // (the mirror ends below this window)
+            const uint64_t end = std::min(w1, r.limit);
+            const uint64_t rank_end = r.limit >= w1 ? p1 : r.rank_limit;
+            const int j = a.n_arrays++;
+            idx[j] = i;
+            surv[j] = (end - rank_end) - dst0;
+            a.arr[j].src = r.base;
+            a.arr[j].out = direct ? r.base + dst0 * r.rb : bounce + r.sect;
+            a.arr[j].row_bytes = (uint32_t)r.rb;
+            a.arr[j].limit = (uint32_t)std::min<uint64_t>(r.limit, 0xffffffffull);
+        }
+        HIP_TRY(launch_compact_rows(a, nt, nullptr), WAX_HIP_ERR_INTERNAL, "row compaction launch");
+        for (int j = 0; j < a.n_arrays; ++j) {
+            const Arr& r = arrs[idx[j]];
+            const uint64_t bytes = surv[j] * r.rb;
+            written += bytes;
+            if (direct || bytes == 0) continue;
+            HIP_TRY(hipMemcpyAsync(r.base + dst0 * r.rb, bounce + r.sect, bytes, hipMemcpyDeviceToDevice, nullptr), WAX_HIP_ERR_INTERNAL, "row compaction copy");
+            written += bytes;
+        }
+        w0 = w1;
+        p = p1;
+    }
+    HIP_TRY(hipStreamSynchronize(nullptr), WAX_HIP_ERR_INTERNAL, "row compaction sync");
+    *bytes_written = written;
+    return WAX_HIP_OK;
+}
+
+// ... and the mirror's / id table's bookkeeping for it, what mirror_note_remove does for one row (`followed`: the mirror's rows were
+// compacted with the store's)
+static void mirror_note_remove_batch(wax_hip_engine* e, const std::vector<uint32_t>& rem, bool followed) {
+    BatchMirror& b = e->batch;
+    e->idhash.valid = false; e->idhash.stale = true; e->idhash.rows = 0;
+    b.mirror_valid = false;
+    if (b.stale || b.d_cb == nullptr || rem[0] >= b.rows) return;    // nothing mirrored moved
+    if (!followed) { mirror_note_lost(e); return; }
+    auto rank = [&](uint64_t r) { return (uint64_t)(std::lower_bound(rem.begin(), rem.end(), (uint32_t)std::min<uint64_t>(r, 0xffffffffull)) - rem.begin()); };
+    b.rows -= rank(b.rows);
+    size_t w = 0;
+    for (size_t i = 0; i < b.dirty.size(); ++i) {
+        const uint32_t r = b.dirty[i];
+        if (std::binary_search(rem.begin(), rem.end(), r)) continue;
+        b.dirty[w++] = r - (uint32_t)rank(r);
+    }
+    b.dirty.resize(w);
+    b.n_dirty = w;
+}
+
 // The bf16 mirror of the store (+ ||v||^2, max ||v||, max rounding error): allocated at the first batched search, then kept in step
 // with the store incrementally — see BatchMirror. Concurrent batches serialise on the conversion's ENQUEUE only: nothing here waits
 // for the device (the converting stream records an event that every other workspace's stream waits for).

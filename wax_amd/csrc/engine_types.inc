@@ -104,6 +104,24 @@ class IdMap {
         for (size_t s = 0; s <= mask_; ++s)
             if (used_[s] && vals_[s] > row) --vals_[s];
     }
+    // After erase_only of the ids of the rows `rem` (ascending, distinct): every remaining row drops by the number of removed rows
+    // below it, in ONE pass over the table (n calls of erase_row are n passes). rank(r) comes from a bitmap of the removed rows
+    // with a running count per 64-row word — 1 bit + half a byte per 64 rows behind rem[0], cache-resident at 10M rows.
+    void renumber_removed(const std::vector<uint32_t>& rem, uint64_t rows) {
+        if (rem.empty()) return;
+        const uint64_t first = rem[0] & ~63ull;                    // word-aligned start of the affected range
+        const size_t words = (size_t)((rows - first + 63) / 64);
+        std::vector<uint64_t> bits(words, 0);
+        std::vector<uint32_t> before(words, 0);                    // removed rows below the word
+        for (uint32_t r : rem) bits[(r - first) >> 6] |= 1ull << ((r - first) & 63);
+        uint32_t run = 0;
+        for (size_t w = 0; w < words; ++w) { before[w] = run; run += (uint32_t)__builtin_popcountll(bits[w]); }
+        for (size_t s = 0; s <= mask_; ++s) {
+            if (!used_[s] || vals_[s] <= rem[0]) continue;
+            const uint64_t o = vals_[s] - first;
+            vals_[s] -= before[o >> 6] + (uint32_t)__builtin_popcountll(bits[o >> 6] & ((1ull << (o & 63)) - 1ull));
+        }
+    }
     void erase_only(uint64_t id) {
         size_t i = hash(id) & mask_;
         while (used_[i] && keys_[i] != id) i = (i + 1) & mask_;
@@ -415,6 +433,9 @@ struct wax_hip_engine {
 
     float* d_sink = nullptr;
     void* d_bounce = nullptr;
+    // wax_hip_remove_batch (DESIGN 4.7)
+    std::atomic<int64_t> compact_window_rows{0};   // source rows per window of the compaction pass; 0 = what the bounce buffer holds
+    std::atomic<uint64_t> st_remove_batches{0}, st_remove_batch_rows{0}, st_remove_batch_bytes{0};
 
     // tuning
     std::atomic<int64_t> grid_blocks{0};
@@ -561,6 +582,7 @@ void note_collect(wax_hip_engine* e, Slot* s) { note_collect_id(e, s->owner); }
 int sh_add_batch(wax_hip_engine* e, const uint64_t* frame_ids, const float* rows, uint64_t n, uint32_t dims);
 int sh_add_batch_device(wax_hip_engine* e, const uint64_t* frame_ids, const float* d_rows, uint64_t n, uint32_t dims);
 int sh_remove(wax_hip_engine* e, uint64_t frame_id);
+int sh_remove_batch(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, uint64_t* out_removed);
 int sh_reserve(wax_hip_engine* e, uint64_t rows);
 int sh_submit(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, uint64_t* out_ticket);
 int sh_collect(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, float* out_scores, uint32_t capacity, uint32_t* out_count);

@@ -248,6 +248,28 @@ hipError_t launch_stream_read(const float* d_src, uint64_t bytes, int nt, int gr
 hipError_t device_shift_down(void* base, uint64_t dst_off, uint64_t src_off, uint64_t bytes, void* bounce,
                              uint64_t bounce_bytes, hipStream_t stream);
 
+// Order-preserving removal of many rows in one pass (compact.hip). One launch moves the surviving rows of ONE window
+// [w0, w1) of source rows of up to four per-row arrays: row r goes to entry (r - rank(r)) - dst0 of the array's `out`, rank(r) =
+// entries of the ascending list `rem` below r. `out` is either a section of the bounce buffer or the array's own destination
+// (base + dst0 rows) when that range lies wholly below w0; the launch never reads what it writes. rem[p0, p1) is the list's slice
+// that falls into the window (p0 = rank(w0), p1 = rank(w1)); rows at or beyond an array's `limit` are left alone.
+constexpr int kCompactMaxArrays = 4;
+struct RowCompactArray {
+    const void* src;      // the array's base (row 0)
+    void* out;            // where the window's first destination row (dst0) goes
+    uint32_t row_bytes;   // 4 / 8: one unit per row; otherwise a multiple of 2
+    uint32_t limit;       // rows [limit, ...) do not exist in this array
+};
+struct RowCompactArgs {
+    const uint32_t* rem;
+    uint32_t p0, p1;
+    uint32_t w0, w1;
+    uint32_t dst0;        // w0 - rank(w0)
+    int n_arrays;
+    RowCompactArray arr[kCompactMaxArrays];
+};
+hipError_t launch_compact_rows(const RowCompactArgs& a, bool nontemporal, hipStream_t stream);
+
 
 // ---- batched queries (batch.hip): bf16 MFMA GEMM + select + exact f32 re-score + certificate ----
 // Per-query append counters of the LDS-tiled GEMM are device-scope atomics from every CU; packed, 1024 of them share

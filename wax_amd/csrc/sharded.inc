@@ -586,6 +586,34 @@ int sh_remove(wax_hip_engine* e, uint64_t frame_id) {
     return rc;
 }
 
+// removeBatch on a handle: the ids are grouped by owning shard and every shard that owns any compacts once (one pass over its own
+// rows behind its first removed one); the bases follow once at the end. The shards' passes run one after the other.
+int sh_remove_batch(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, uint64_t* out_removed) {
+    ShardedState* s = e->sh;
+    if (out_removed) *out_removed = 0;
+    if (n == 0) return WAX_HIP_OK;
+    if (!frame_ids) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "removeBatch: null input");
+    REFUSE_IF_HOLDING(e);
+    WriteGuard w(e->lock);
+    std::vector<std::vector<uint64_t>> per(s->subs.size());
+    for (uint64_t i = 0; i < n; ++i) {
+        int64_t local = -1;
+        const int g = sh_find(s, frame_ids[i], &local);
+        if (g >= 0) per[(size_t)g].push_back(frame_ids[i]);              // :426 absent ids are ignored
+    }
+    int rc = WAX_HIP_OK;
+    uint64_t total = 0;
+    for (size_t g = 0; g < per.size() && rc == WAX_HIP_OK; ++g) {
+        if (per[g].empty()) continue;
+        uint64_t got = 0;
+        rc = wax_hip_remove_batch(s->subs[g], per[g].data(), per[g].size(), &got);
+        total += got;
+    }
+    sh_update_bases(s);
+    if (out_removed) *out_removed = total;
+    return rc;
+}
+
 int sh_reserve(wax_hip_engine* e, uint64_t rows) {
     ShardedState* s = e->sh;
     REFUSE_IF_HOLDING(e);
@@ -1398,7 +1426,8 @@ int64_t sh_get_tuning(wax_hip_engine* e, const std::string& k) {
     if (k == "parallel_submits") return (int64_t)s->parallel_submits.load();
     if (k == "batch_queries" || k == "batch_fallbacks" || k == "batch_retries" || k == "onepass_queries" || k == "filter_device_searches" || k == "filter_batch_queries" || k == "filter_batch_fallbacks" || k == "query_args_scans" || k == "batch_inline_retries" ||
         k == "batch_multi_passes" || k == "batch_multi_queries" || k == "short_selects" || k == "short_select_failures" ||
-        k == "mirror_scans" || k == "mirror_scan_fallbacks" || k == "mirror_scan_unavailable") {   // counters: summed over the shards
+        k == "mirror_scans" || k == "mirror_scan_fallbacks" || k == "mirror_scan_unavailable" ||
+        k == "remove_batches" || k == "remove_batch_rows" || k == "remove_batch_bytes_written") {   // counters: summed over the shards
         int64_t t = 0;
         for (auto* sub : s->subs) t += wax_hip_get_tuning(sub, k.c_str());
         return t;

@@ -68,6 +68,7 @@ int wax_hip_set_tuning(wax_hip_engine* e, const char* key, int64_t value) {
     else if (k == "share_timing") e->share_timing = value != 0;   // 0: every chained scan records its own start event (one more packet between scans)
     else if (k == "filter_batch") { if (value < 0 || value > 1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "filter_batch must be 0 or 1"); e->filter_batch = value; }
     else if (k == "filter_device_min") { if (value < -1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "filter_device_min must be >= -1"); e->filter_device_min = value; }
+    else if (k == "compact_window_rows") { if (value < 0 || value > 0xffffffffll) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "compact_window_rows must be 0 (what the bounce buffer holds) .. 4294967295"); e->compact_window_rows = value; }
     else if (k == "batch_sample_div") { if (value < 4 || value > 4096) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_sample_div must be 4..4096"); e->batch_sample_div = value; }
     else if (k == "batch_workspaces") {
         if (value < 1 || value > 16) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_workspaces must be 1..16");
@@ -156,6 +157,10 @@ int64_t wax_hip_get_tuning(wax_hip_engine* e, const char* key) {
     }
     if (k == "mirror_rows_converted") return (int64_t)e->batch.rows_converted.load();   // bf16 mirror: rows converted so far / conversions enqueued
     if (k == "mirror_conversions") return (int64_t)e->batch.conversions.load();
+    if (k == "compact_window_rows") return e->compact_window_rows.load();
+    if (k == "remove_batches") return (int64_t)e->st_remove_batches.load();            // wax_hip_remove_batch calls that removed rows in one pass
+    if (k == "remove_batch_rows") return (int64_t)e->st_remove_batch_rows.load();      // rows they removed
+    if (k == "remove_batch_bytes_written") return (int64_t)e->st_remove_batch_bytes.load();   // device bytes their passes wrote (bounce writes included)
     if (k == "idhash_rows_inserted") return (int64_t)e->st_idhash_rows.load();
     if (k == "batch_min") return e->batch_min.load();
     if (k == "batch_mode") return e->batch_mode.load();

@@ -241,6 +241,20 @@ class HIPVectorEngine:
         if self.count != before:
             self._dirty = True
 
+    def removeBatch(self, frameIds: Sequence[int]) -> int:  # noqa: N802,N803
+        """remove(frameId:) for many ids in one compaction pass (the loop of VectorSearchSession.swift:188-192 as one call):
+        unknown ids are ignored, an id listed twice counts once, the surviving rows keep their order. Returns the rows removed."""
+        ids = np.ascontiguousarray(frameIds, dtype=np.uint64).reshape(-1)
+        n = int(ids.size)
+        if n == 0:
+            return 0
+        removed = ctypes.c_uint64(0)
+        rc = self._lib.wax_hip_remove_batch(self._h, _u64p(ids), n, ctypes.byref(removed))
+        raise_for_status(rc)
+        if removed.value:
+            self._dirty = True
+        return int(removed.value)
+
     def reserve(self, rows: int) -> None:
         raise_for_status(self._lib.wax_hip_reserve(self._h, int(rows)))
 
