@@ -213,12 +213,12 @@ def assert_parity(got_ids, got_scores, exp_ids, exp_scores, all_exp_scores=None,
         i = hi + 1
 
 
-def bf16_adversarial_unit_vector(dims):
-    """A unit vector (f32) whose bf16 rounding moves its self-similarity by ~2^-7: every non-zero element is (1 + 0.99 * 2^-8) * 2^-e,
+def bf16_adversarial_unit_vector(dims, frac=0.99, roll=0):
+    """(frac, roll: variants — every element loses frac * 2^-8 of itself, the non-zeros start at element `roll`.) A unit vector (f32) whose bf16 rounding moves its self-similarity by ~2^-7: every non-zero element is (1 + 0.99 * 2^-8) * 2^-e,
     just below a rounding midpoint at the bottom of its binade (so rounding takes 2^-8 of it away), with the exponents chosen
     greedily so that the squares sum to 1 — the normalisation the engine applies then changes nothing. ~20 non-zeros, rest 0."""
     import numpy as np
-    a = 2.0 ** -8 * 0.99
+    a = 2.0 ** -8 * frac
     rem, exps = (1 + a) ** -2, []
     for e in range(1, 14):
         c = int(rem // 4.0 ** -e)
@@ -227,4 +227,135 @@ def bf16_adversarial_unit_vector(dims):
         rem -= c * 4.0 ** -e
     x = np.zeros(dims, dtype=np.float64)
     x[:len(exps)] = [(1 + a) * 2.0 ** -e for e in exps]
-    return (x / np.sqrt(np.sum(x * x))).astype(np.float32)
+    return np.roll((x / np.sqrt(np.sum(x * x))).astype(np.float32), roll)
+
+
+# ---------------------------------------------------------------------------
+# constructions for the edges of the bf16 mirror's exactness argument (tests/test_mirror_edges_*.py)
+
+THRESHOLD = np.float32(1e-6)   # CosineDistance.metal:323, as an f32 constant (9.99999997e-7)
+
+
+def bf16_rne(x):
+    """f32 -> bf16 (round to nearest, ties to even) -> f32, in numpy integer arithmetic. NaN stays NaN (quieted), inf stays inf,
+    a finite value beyond the largest bf16 (above 3.3895e38) becomes inf, denormals round like any other value."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    b = x.view(np.uint32).astype(np.uint64)
+    nan = (b & 0x7fffffff) > 0x7f800000
+    r = ((b + 0x7fff + ((b >> 16) & 1)) >> 16) << 16
+    r = np.where(nan, ((b >> 16) | 0x40) << 16, r)
+    return r.astype(np.uint32).view(np.float32).reshape(x.shape)
+
+
+def _unit_orthogonal(rng, qhat, count):
+    """`count` unit vectors (f64) orthogonal to the unit vector qhat."""
+    u = rng.standard_normal((count, qhat.size))
+    u -= (u @ qhat)[:, None] * qhat[None, :]
+    return u / np.linalg.norm(u, axis=1)[:, None]
+
+
+ANTI_TOP = 100                 # rows of the sparse top
+ANTI_TOP_COS = -0.0500005      # best cosine: -0.05 with room for the f32 rounding of the rows (every f64 cosine stays <= -0.05)
+ANTI_TOP_STEP = 1e-3
+ANTI_GAP, ANTI_SPREAD = 0.02, 0.3
+
+
+def anti_correlated_corpus(n, dims, seed, zero_at=None):
+    """(rows f32 [n, dims], query f32 [dims]): unit rows that all lie in the half-space opposite the unit query (whose component
+    `zero_at`, if given, is exactly 0). The ANTI_TOP most
+    similar rows have cosines ANTI_TOP_COS - i * 1e-3; every other row lies at least ANTI_GAP below the last of them, uniformly over
+    a further ANTI_SPREAD. Rows are c * q + sqrt(1 - c^2) * u, u a unit vector orthogonal to q; their places in the store are shuffled."""
+    rng = np.random.default_rng(seed)
+    q = rng.standard_normal(dims)
+    if zero_at is not None:
+        q[zero_at] = 0.0
+    q = (q / np.linalg.norm(q)).astype(np.float32)
+    qhat = q.astype(np.float64) / np.linalg.norm(q.astype(np.float64))
+    c = np.empty(n)
+    c[:ANTI_TOP] = ANTI_TOP_COS - ANTI_TOP_STEP * np.arange(ANTI_TOP)
+    floor = c[ANTI_TOP - 1] - ANTI_GAP
+    c[ANTI_TOP:] = floor - ANTI_SPREAD * rng.random(n - ANTI_TOP)
+    c = c[rng.permutation(n)]
+    rows = c[:, None] * qhat[None, :] + np.sqrt(1.0 - c * c)[:, None] * _unit_orthogonal(rng, qhat, n)
+    return np.ascontiguousarray(rows, dtype=np.float32), q
+
+
+THRESHOLD_TOP_COS, THRESHOLD_COS_STEP = 0.955, 1e-3
+THRESHOLD_ULPS = 32            # norms 1e-6 * (1 + j * 2^-24), j in -32 .. 32
+
+
+def threshold_rows(q, count, dims, seed):
+    """`count` f32 rows c_i * q^ + sqrt(1 - c_i^2) * u_i (u_i a unit vector orthogonal to q) with distinct cosines c_i = 0.955 - i * 1e-3,
+    scaled so that their f64 norms are 1e-6 * (1 + j * 2^-24), j cycling through -32 .. 32: rows a few ulp on either side of the
+    `sqrt(m) > 1e-6` rule. Returns (rows, cosines, j)."""
+    rng = np.random.default_rng(seed)
+    qhat = np.asarray(q, dtype=np.float64)
+    qhat = qhat / np.linalg.norm(qhat)
+    assert qhat.size == dims
+    c = THRESHOLD_TOP_COS - THRESHOLD_COS_STEP * np.arange(count)
+    j = (np.arange(count) % (2 * THRESHOLD_ULPS + 1)) - THRESHOLD_ULPS
+    rows = c[:, None] * qhat[None, :] + np.sqrt(1.0 - c * c)[:, None] * _unit_orthogonal(rng, qhat, count)
+    rows *= (1e-6 * (1.0 + j * 2.0 ** -24))[:, None]
+    return np.ascontiguousarray(rows, dtype=np.float32), c, j
+
+
+def _dpp_group_sum(v, group):
+    """The engine's cross-lane sum tree over aligned groups of `group` lanes (quad swaps, half-row mirror, row mirror, row
+    broadcasts), in f32 on an array [..., 64]; the group's total is read from its last lane."""
+    v = np.asarray(v, dtype=np.float32)
+    lane = np.arange(64)
+    v = v + v[..., lane ^ 1]
+    v = v + v[..., lane ^ 2]
+    if group >= 8:
+        v = v + v[..., (lane & ~7) | (7 - (lane & 7))]
+    if group >= 16:
+        v = v + v[..., (lane & ~15) | (15 - (lane & 15))]
+    if group >= 32:
+        add = np.where((lane >> 4) & 1, v[..., (lane & ~15) - 1], np.float32(0))
+        v = v + add.astype(np.float32)
+    if group >= 64:
+        add = np.where(lane >= 32, v[..., np.full(64, 31)], np.float32(0))
+        v = v + add.astype(np.float32)
+    return v
+
+
+def _fma32(a, b, c):
+    """a * b + c rounded once to f32 (the product of two f32 is exact in f64; the f64 sum is then rounded to f32 — a double
+    rounding that differs from a fused multiply-add only on rare half-way cases, which does not matter to what this is used for:
+    showing that two f32 summation ORDERS disagree)."""
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+
+def f32_norm2_chain_order(rows):
+    """sum x^2 in f32 the way a 64-lane strided scalar chain does it: lane l owns the float4s l, l + 64, ... of the row and adds
+    x, y, z, w of each to ONE accumulator in turn; the 64 lanes are then summed by the cross-lane tree."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    n, dims = rows.shape
+    assert dims % 4 == 0
+    d4 = dims // 4
+    x = rows.reshape(n, d4, 4)
+    acc = np.zeros((n, 64), dtype=np.float32)
+    for base in range(0, d4, 64):
+        w = min(64, d4 - base)
+        for comp in range(4):
+            v = x[:, base:base + w, comp]
+            acc[:, :w] = _fma32(v, v, acc[:, :w])
+    return _dpp_group_sum(acc, 64)[:, 63]
+
+
+def f32_norm2_scan_order(rows, group):
+    """sum x^2 in f32 the way the f32 scan does it: `group` lanes per row, lane g owns the float4s g, g + group, ... and keeps
+    FOUR accumulators (one per component), summed (x + y) + (z + w), then the cross-lane tree over the group
+    (group = 32 at 384 dims, 64 at 768)."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    n, dims = rows.shape
+    d4 = dims // 4
+    assert dims % 4 == 0 and d4 % group == 0
+    x = rows.reshape(n, d4 // group, group, 4)
+    acc = np.zeros((n, group, 4), dtype=np.float32)
+    for jj in range(d4 // group):
+        acc = _fma32(x[:, jj], x[:, jj], acc)
+    lane_sum = (acc[..., 0] + acc[..., 1]) + (acc[..., 2] + acc[..., 3])
+    full = np.zeros((n, 64), dtype=np.float32)
+    full[:, 64 - group:] = lane_sum
+    return _dpp_group_sum(full, group)[:, 63]

@@ -59,8 +59,35 @@ __device__ inline unsigned short f32_to_bf16_rne(float x) {
 }
 
 // ---------------------------------------------------------------------------
-// f32 rows -> bf16 rows (RNE). normalize=1 (cosine): each row is scaled by 1/||v|| first (0 if
-// ||v|| <= 1e-6, CosineDistance.metal:323), so the GEMM epilogue is just d = 1 - acc.
+// sum x^2 of one row in the f32 scan's own order (kernels.hip: scan_body / scan_generic_kernel): G lanes per row, lane g owns the
+// float4s g, g + G, ... with one fma chain per component, hsum (x + y) + (z + w), group_sum<G>. Every aligned group of G lanes of
+// the wave computes the same row; the total is read from lane 63, the last lane of the last group. These are the bits of the `m`
+// finish_distance tests against 1e-6, so a row is a zero row in the mirror exactly when the scan scores it 0.
+template <int G>
+__device__ inline float scan_order_norm2(const float* __restrict__ row, uint32_t dims, int lane) {
+    f32x4 nrm = {0.f, 0.f, 0.f, 0.f};
+    const uint32_t gl = (uint32_t)lane % G;
+    if ((dims & 3u) == 0) {
+        const f32x4* row4 = reinterpret_cast<const f32x4*>(row);
+        for (uint32_t c = gl; c < (dims >> 2); c += G) {
+            const f32x4 v = row4[c];
+            nrm = __builtin_elementwise_fma(v, v, nrm);
+        }
+    } else {   // (the generic scan: G = 64, one element per lane and step in component x)
+        for (uint32_t c = gl; c < dims; c += G) {
+            const f32x4 v = {row[c], 0.f, 0.f, 0.f};
+            nrm = __builtin_elementwise_fma(v, v, nrm);
+        }
+    }
+    const float m = group_sum<G>((nrm.x + nrm.y) + (nrm.z + nrm.w));
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(m), 63));
+}
+
+// ---------------------------------------------------------------------------
+// f32 rows -> bf16 rows (RNE). normalize != 0 (cosine; the value is the f32 scan's lanes per row at this dimension: 16 / 32 / 64):
+// each row is scaled by 1/||v|| first, and a row the scan's rule `sqrt(m) > 1e-6` (CosineDistance.metal:323) scores 0 — a short
+// row, a NaN row — becomes a ZERO row, decided on the scan's own m (scan_order_norm2), so the GEMM epilogue is just d = 1 - acc
+// and a row's approximate distance is within eps of its exact one whichever side of the rule it is on.
 // Also emits ||v||^2 (L2 epilogue) and the global max ||v|| (certificate bound for dot / L2).
 // One wave per row; used for the corpus mirror and for the query block (rows in
 // [n_rows, n_rows_padded) are zero-filled).
@@ -102,8 +129,15 @@ __global__ __launch_bounds__(256) void mirror_kernel(const float* __restrict__ s
         }
         acc = group_sum<64>(acc);
         acc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 63));  // the total lives in lane 63
-        const float n = sqrtf(acc);
-        const float scale = normalize ? ((n > 1e-6f) ? 1.0f / n : 0.0f) : 1.0f;
+        float n = sqrtf(acc);
+        bool zero_row = false;     // cosine: the scan scores this row 0 (n <= 1e-6, or n is NaN)
+        if (normalize) {
+            const float m = normalize == 16 ? scan_order_norm2<16>(row, dims, lane)
+                          : normalize == 32 ? scan_order_norm2<32>(row, dims, lane) : scan_order_norm2<64>(row, dims, lane);
+            n = sqrtf(m);
+            zero_row = !(n > 1e-6f);
+        }
+        const float scale = normalize ? 1.0f / n : 1.0f;   // (n = inf: 0, and an inf element stays NaN — as its exact distance is)
         float e2 = 0.f;        // ||x - bf16(x)||^2 of this row (x - bf16(x) is exact in f32: both are floats of one binade or neighbours)
         auto rnd = [&](float x) -> unsigned short {
             const unsigned short b = f32_to_bf16_rne(x);
@@ -117,19 +151,19 @@ __global__ __launch_bounds__(256) void mirror_kernel(const float* __restrict__ s
             for (uint32_t c = lane; c < (dims >> 2); c += WAVE) {
                 const f32x4 v = row4[c];
                 u16x4 o;
-                o.x = rnd(v.x * scale); o.y = rnd(v.y * scale);
-                o.z = rnd(v.z * scale); o.w = rnd(v.w * scale);
+                o.x = rnd(zero_row ? 0.f : v.x * scale); o.y = rnd(zero_row ? 0.f : v.y * scale);
+                o.z = rnd(zero_row ? 0.f : v.z * scale); o.w = rnd(zero_row ? 0.f : v.w * scale);
                 out4[c] = o;
             }
         } else {
-            for (uint32_t c = lane; c < dims; c += WAVE) out[c] = rnd(row[c] * scale);
+            for (uint32_t c = lane; c < dims; c += WAVE) out[c] = rnd(zero_row ? 0.f : row[c] * scale);
         }
         e2 = group_sum<64>(e2);
         e2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e2), 63));
         const float err = sqrtf(e2);
         if (lane == 0) norm2[r] = acc;
         if (n == n && n > wave_max) wave_max = n;
-        if (err == err && err > wave_max_err) wave_max_err = err;   // a NaN / inf row never passes a threshold and sorts last exactly
+        if (err == err && err > wave_max_err) wave_max_err = err;   // (a row that keeps a NaN has a NaN / inf exact distance too: it sorts last on both sides)
     }
     if (max_norm_bits != nullptr) {
         if (lane == 0) { atomicMax(&block_max, __float_as_uint(wave_max)); atomicMax(&block_max_err, __float_as_uint(wave_max_err)); }
@@ -139,12 +173,19 @@ __global__ __launch_bounds__(256) void mirror_kernel(const float* __restrict__ s
     }
 }
 
+// mirror_kernel's `normalize` argument: 0, or the lanes per row of the f32 scan at this dimension (64 on the generic kernel)
+static int scan_group_if(int normalize, uint32_t dims) {
+    if (!normalize) return 0;
+    ScanVariantInfo info;
+    return scan_variant_info(dims, 0, &info) ? info.group : 64;
+}
+
 hipError_t launch_mirror(const float* src, uint32_t n_rows, uint32_t n_rows_padded, uint32_t dims, int normalize,
                          unsigned short* dst, float* norm2, unsigned int* max_norm_bits, hipStream_t st) {
     if (n_rows_padded == 0) return hipSuccess;
     uint64_t blocks = ((uint64_t)n_rows_padded + 3) / 4;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(mirror_kernel, dim3((unsigned)blocks), dim3(256), 0, st, src, n_rows, n_rows_padded, dims, normalize,
+    hipLaunchKernelGGL(mirror_kernel, dim3((unsigned)blocks), dim3(256), 0, st, src, n_rows, n_rows_padded, dims, scan_group_if(normalize, dims),
                        dst, norm2, max_norm_bits, (const uint32_t*)nullptr);
     return hipGetLastError();
 }
@@ -154,7 +195,7 @@ hipError_t launch_mirror_rows(const float* src, const uint32_t* d_rows, uint32_t
     if (n_listed == 0) return hipSuccess;
     uint64_t blocks = ((uint64_t)n_listed + 3) / 4;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(mirror_kernel, dim3((unsigned)blocks), dim3(256), 0, st, src, n_listed, n_listed, dims, normalize,
+    hipLaunchKernelGGL(mirror_kernel, dim3((unsigned)blocks), dim3(256), 0, st, src, n_listed, n_listed, dims, scan_group_if(normalize, dims),
                        dst, norm2, max_norm_bits, d_rows);
     return hipGetLastError();
 }
