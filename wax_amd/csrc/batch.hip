@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "row_math.h"
 #include "topk.h"
 
 
@@ -43,44 +44,16 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-enum { BM_COS = WAX_HIP_METRIC_COSINE, BM_DOT = WAX_HIP_METRIC_DOT, BM_L2 = WAX_HIP_METRIC_L2 };
 
 __device__ inline unsigned short f32_to_bf16_rne(float x) {
     unsigned int b = __float_as_uint(x);
     if ((b & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((b >> 16) | 0x0040u);  // quiet NaN
     b += 0x7fffu + ((b >> 16) & 1u);
     return (unsigned short)(b >> 16);
-}
-
-// ---------------------------------------------------------------------------
-// sum x^2 of one row in the f32 scan's own order (kernels.hip: scan_body / scan_generic_kernel): G lanes per row, lane g owns the
-// float4s g, g + G, ... with one fma chain per component, hsum (x + y) + (z + w), group_sum<G>. Every aligned group of G lanes of
-// the wave computes the same row; the total is read from lane 63, the last lane of the last group. These are the bits of the `m`
-// finish_distance tests against 1e-6, so a row is a zero row in the mirror exactly when the scan scores it 0.
-template <int G>
-__device__ inline float scan_order_norm2(const float* __restrict__ row, uint32_t dims, int lane) {
-    f32x4 nrm = {0.f, 0.f, 0.f, 0.f};
-    const uint32_t gl = (uint32_t)lane % G;
-    if ((dims & 3u) == 0) {
-        const f32x4* row4 = reinterpret_cast<const f32x4*>(row);
-        for (uint32_t c = gl; c < (dims >> 2); c += G) {
-            const f32x4 v = row4[c];
-            nrm = __builtin_elementwise_fma(v, v, nrm);
-        }
-    } else {   // (the generic scan: G = 64, one element per lane and step in component x)
-        for (uint32_t c = gl; c < dims; c += G) {
-            const f32x4 v = {row[c], 0.f, 0.f, 0.f};
-            nrm = __builtin_elementwise_fma(v, v, nrm);
-        }
-    }
-    const float m = group_sum<G>((nrm.x + nrm.y) + (nrm.z + nrm.w));
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(m), 63));
 }
 
 // ---------------------------------------------------------------------------
@@ -135,7 +108,7 @@ __global__ __launch_bounds__(256) void mirror_kernel(const float* __restrict__ s
             const float m = normalize == 16 ? scan_order_norm2<16>(row, dims, lane)
                           : normalize == 32 ? scan_order_norm2<32>(row, dims, lane) : scan_order_norm2<64>(row, dims, lane);
             n = sqrtf(m);
-            zero_row = !(n > 1e-6f);
+            zero_row = !(n > COS_NORM_FLOOR);
         }
         const float scale = normalize ? 1.0f / n : 1.0f;   // (n = inf: 0, and an inf element stays NaN — as its exact distance is)
         float e2 = 0.f;        // ||x - bf16(x)||^2 of this row (x - bf16(x) is exact in f32: both are floats of one binade or neighbours)
@@ -176,8 +149,8 @@ __global__ __launch_bounds__(256) void mirror_kernel(const float* __restrict__ s
 // mirror_kernel's `normalize` argument: 0, or the lanes per row of the f32 scan at this dimension (64 on the generic kernel)
 static int scan_group_if(int normalize, uint32_t dims) {
     if (!normalize) return 0;
-    ScanVariantInfo info;
-    return scan_variant_info(dims, 0, &info) ? info.group : 64;
+    const int group = scan_group_lanes(dims);
+    return group != 0 ? group : 64;
 }
 
 hipError_t launch_mirror(const float* src, uint32_t n_rows, uint32_t n_rows_padded, uint32_t dims, int normalize,
@@ -315,7 +288,7 @@ __global__ __launch_bounds__(256) void batch_gemm_kernel(GemmArgs a) {
     unsigned int* wcnt = reinterpret_cast<unsigned int*>(As) + 2 * GM;  // [4] staged-candidate counters, one per wave
     if (tid < GM) {
         tau_s[tid] = a.tau[m0 + tid];
-        if (METRIC == BM_L2) qn2[tid] = a.q_n2[m0 + tid];
+        if (METRIC == M_L2) qn2[tid] = a.q_n2[m0 + tid];
         if (tid < 4) wcnt[tid] = 0u;
     }
     __syncthreads();
@@ -328,7 +301,7 @@ __global__ __launch_bounds__(256) void batch_gemm_kernel(GemmArgs a) {
         for (int r = 0; r < 16; ++r) {
             const int qloc = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
             tq[i][r] = tau_s[qloc];
-            qq[i][r] = (METRIC == BM_L2) ? qn2[qloc] : 0.f;
+            qq[i][r] = (METRIC == M_L2) ? qn2[qloc] : 0.f;
         }
     const uint32_t slab_end = a.slab0 + a.slab_rows;
     uint32_t rowj[2];
@@ -340,7 +313,7 @@ __global__ __launch_bounds__(256) void batch_gemm_kernel(GemmArgs a) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             rowj[j] = n0 + wn * 64 + j * 32 + (lane & 31);
-            vn2j[j] = (METRIC == BM_L2 && rowj[j] < slab_end) ? a.v_n2[rowj[j]] : 0.f;
+            vn2j[j] = (METRIC == M_L2 && rowj[j] < slab_end) ? a.v_n2[rowj[j]] : 0.f;
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -350,7 +323,7 @@ __global__ __launch_bounds__(256) void batch_gemm_kernel(GemmArgs a) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const float dot = acc[i][j][r];
-                    const float sim = (METRIC == BM_L2) ? -((qq[i][r] + vn2j[j] - 2.0f * dot) + 0.0f) : dot;
+                    const float sim = (METRIC == M_L2) ? -((qq[i][r] + vn2j[j] - 2.0f * dot) + 0.0f) : dot;
                     best = __builtin_fmaxf(best, rowj[j] < slab_end ? sim : -__builtin_inff());   // NaN never wins (maxNum)
                 }
                 best = group_max32(best);
@@ -365,14 +338,14 @@ __global__ __launch_bounds__(256) void batch_gemm_kernel(GemmArgs a) {
     for (int j = 0; j < 2; ++j) {
         rowj[j] = n0 + wn * 64 + j * 32 + (lane & 31);
         const bool row_ok = rowj[j] < slab_end;
-        vn2j[j] = (METRIC == BM_L2 && row_ok) ? a.v_n2[rowj[j]] : 0.f;
+        vn2j[j] = (METRIC == M_L2 && row_ok) ? a.v_n2[rowj[j]] : 0.f;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float dot = acc[i][j][r];
                 float d;
-                if (METRIC == BM_L2) d = qq[i][r] + vn2j[j] - 2.0f * dot;
+                if (METRIC == M_L2) d = qq[i][r] + vn2j[j] - 2.0f * dot;
                 else d = 1.0f - dot;  // cosine: both operands were normalised by mirror_kernel; dot: USearch ip
                 d += 0.0f;
                 // NaN fails the test (such rows can never be candidates); padded queries have tau = -inf
@@ -394,7 +367,7 @@ __global__ __launch_bounds__(256) void batch_gemm_kernel(GemmArgs a) {
                     const int qloc = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                     const float dot = acc[i][j][r];
                     float d;
-                    if (METRIC == BM_L2) d = qq[i][r] + vn2j[j] - 2.0f * dot;
+                    if (METRIC == M_L2) d = qq[i][r] + vn2j[j] - 2.0f * dot;
                     else d = 1.0f - dot;
                     d = (d != d) ? __builtin_inff() : d;
                     dst[(size_t)(m0 + qloc) * a.dense_ld] = d + 0.0f;
@@ -424,7 +397,7 @@ __global__ __launch_bounds__(256) void batch_gemm_kernel(GemmArgs a) {
                         const int qloc = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                         const float dot = acc[i][j][r];
                         float d;
-                        if (METRIC == BM_L2) d = qq[i][r] + vn2j[j] - 2.0f * dot;
+                        if (METRIC == M_L2) d = qq[i][r] + vn2j[j] - 2.0f * dot;
                         else d = 1.0f - dot;
                         d += 0.0f;
                         const int64_t key = make_key(d, a.row_base + rowj[j]);
@@ -457,7 +430,7 @@ __global__ __launch_bounds__(256) void batch_gemm_kernel(GemmArgs a) {
                     const int qloc = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                     const float dot = acc[i][j][r];
                     float d;
-                    if (METRIC == BM_L2) d = qq[i][r] + vn2j[j] - 2.0f * dot;
+                    if (METRIC == M_L2) d = qq[i][r] + vn2j[j] - 2.0f * dot;
                     else d = 1.0f - dot;
                     d += 0.0f;
                     const uint32_t q = m0 + qloc;
@@ -1081,7 +1054,7 @@ static void rq_geometry(const GemmArgs& a, uint32_t* groups, uint32_t* per_group
 }
 
 static bool rq_eligible(const GemmArgs& a, int metric) {
-    return a.dense == nullptr && a.use_rega && metric != BM_L2 && rq_dims(a.dims);
+    return a.dense == nullptr && a.use_rega && metric != M_L2 && rq_dims(a.dims);
 }
 
 bool batch_gemm_segments(const GemmArgs& a, int metric, uint32_t* nseg, uint32_t* seg_slots) {
@@ -1145,9 +1118,9 @@ hipError_t launch_batch_gemm(const GemmArgs& a, int metric, hipStream_t st) {
     const uint32_t ctiles = (a.slab_rows + GN - 1) / GN;
     const dim3 grid(ctiles * a.nqt);
     switch (metric) {
-        case BM_COS: launch_kernel((batch_gemm_kernel<BM_COS>), grid, dim3(256), 0, st, a); break;
-        case BM_DOT: launch_kernel((batch_gemm_kernel<BM_DOT>), grid, dim3(256), 0, st, a); break;
-        case BM_L2: launch_kernel((batch_gemm_kernel<BM_L2>), grid, dim3(256), 0, st, a); break;
+        case M_COS: launch_kernel((batch_gemm_kernel<M_COS>), grid, dim3(256), 0, st, a); break;
+        case M_DOT: launch_kernel((batch_gemm_kernel<M_DOT>), grid, dim3(256), 0, st, a); break;
+        case M_L2: launch_kernel((batch_gemm_kernel<M_L2>), grid, dim3(256), 0, st, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -1279,36 +1252,7 @@ hipError_t launch_batch_reset(float* tau, uint32_t* cand_count, uint32_t* overfl
 }
 
 // ---------------------------------------------------------------------------
-// Exact f32 re-score of the candidates with scan_kernel's lane mapping and summation order.
-template <int METRIC>
-__device__ inline float finish_distance_b(float acc, float nrm, float q_norm) {
-    float d;
-    if (METRIC == BM_COS) {
-        const float vn = sqrtf(nrm);
-        const float sim = (vn > 1e-6f && q_norm > 1e-6f) ? acc / (vn * q_norm) : 0.0f;
-        d = 1.0f - sim;
-    } else if (METRIC == BM_DOT) {
-        d = 1.0f - acc;
-    } else {
-        d = acc;
-    }
-    d = (d != d) ? __builtin_inff() : d;
-    return d + 0.0f;
-}
-
-template <int METRIC>
-__device__ inline void accumulate_b(const f32x4& q, const f32x4& v, f32x4& acc, f32x4& nrm) {
-    if (METRIC == BM_L2) {
-        const f32x4 e = q - v;
-        acc = __builtin_elementwise_fma(e, e, acc);
-    } else {
-        acc = __builtin_elementwise_fma(q, v, acc);
-        if (METRIC == BM_COS) nrm = __builtin_elementwise_fma(v, v, nrm);
-    }
-}
-
-__device__ inline float hsum_b(const f32x4& a) { return (a.x + a.y) + (a.z + a.w); }
-
+// Exact f32 re-score of the candidates: row_distance / generic_row_distance (row_math.h), the bits of the single-query scan.
 template <int D4, int GROUP, int METRIC>
 __global__ __launch_bounds__(256) void rescore_kernel(RescoreArgs a) {
     constexpr int LOADS = D4 / GROUP;
@@ -1340,13 +1284,10 @@ __global__ __launch_bounds__(256) void rescore_kernel(RescoreArgs a) {
     lrow = (live && lrow < a.n_rows) ? lrow : 0;
     const f32x4* __restrict__ v4 = reinterpret_cast<const f32x4*>(a.store) + (size_t)lrow * D4 + gl;
     const f32x4* __restrict__ q4 = reinterpret_cast<const f32x4*>(a.queries) + (size_t)q * D4 + gl;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, nrm = {0.f, 0.f, 0.f, 0.f};
+    f32x4 qv[LOADS], v[LOADS];
 #pragma unroll
-    for (int j = 0; j < LOADS; ++j) accumulate_b<METRIC>(q4[j * GROUP], v4[j * GROUP], acc, nrm);
-    const float s = group_sum<GROUP>(hsum_b(acc));
-    float m = 0.f;
-    if (METRIC == BM_COS) m = group_sum<GROUP>(hsum_b(nrm));
-    const float d = finish_distance_b<METRIC>(s, m, a.q_norm[q]);
+    for (int j = 0; j < LOADS; ++j) { qv[j] = q4[j * GROUP]; v[j] = v4[j * GROUP]; }
+    const float d = row_distance<GROUP, LOADS, METRIC>(qv, v, a.q_norm[q]);
     if (in_range && gl == GROUP - 1) {
         if (a.dist_out != nullptr) a.dist_out[p] = d;
         else a.exact[(size_t)(a.by_slot ? qslot : q) * (uint32_t)a.kp + (p - qslot * (uint32_t)a.kp)] = live ? make_key(d, grow) : KEY_PAD;
@@ -1375,66 +1316,32 @@ __global__ __launch_bounds__(256) void rescore_generic_kernel(RescoreArgs a) {
     // (survivor-area mode and query lists are served by the specialised kernel only: launch_rescore refuses them here)
     lrow = (live && lrow < a.n_rows) ? lrow : 0;
     const uint32_t D = a.dims;
-    const float* row = a.store + (size_t)lrow * D;
-    const float* qv = a.queries + (size_t)q * D;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f}, nrm = {0.f, 0.f, 0.f, 0.f};
-    if ((D & 3u) == 0) {
-        const f32x4* row4 = reinterpret_cast<const f32x4*>(row);
-        const f32x4* q4 = reinterpret_cast<const f32x4*>(qv);
-        for (uint32_t c = lane; c < (D >> 2); c += WAVE) accumulate_b<METRIC>(q4[c], row4[c], acc, nrm);
-    } else {
-        for (uint32_t c = lane; c < D; c += WAVE) {
-            const f32x4 qq = {qv[c], 0.f, 0.f, 0.f};
-            const f32x4 vv = {row[c], 0.f, 0.f, 0.f};
-            accumulate_b<METRIC>(qq, vv, acc, nrm);
-        }
-    }
-    const float s = group_sum<64>(hsum_b(acc));
-    float m = 0.f;
-    if (METRIC == BM_COS) m = group_sum<64>(hsum_b(nrm));
-    const float d = finish_distance_b<METRIC>(s, m, a.q_norm[q]);
+    const float d = generic_row_distance<METRIC>(a.store + (size_t)lrow * D, a.queries + (size_t)q * D, D, lane, a.q_norm[q]);
     if (lane == WAVE - 1) {
         if (a.dist_out != nullptr) a.dist_out[pair] = d;
         else a.exact[pair] = live ? make_key(d, grow) : KEY_PAD;
     }
 }
 
-template <int D4, int GROUP>
-static hipError_t launch_rescore_t(const RescoreArgs& a, int metric, hipStream_t st) {
+template <int D4, int GROUP, int METRIC>
+static hipError_t launch_rescore_t(const RescoreArgs& a, hipStream_t st) {
     constexpr int RPW = WAVE / GROUP;
     const uint32_t total = a.nq * (uint32_t)a.kp;
-    const dim3 grid((total + 4 * RPW - 1) / (4 * RPW));
-    switch (metric) {
-        case BM_COS: hipLaunchKernelGGL((rescore_kernel<D4, GROUP, BM_COS>), grid, dim3(256), 0, st, a); break;
-        case BM_DOT: hipLaunchKernelGGL((rescore_kernel<D4, GROUP, BM_DOT>), grid, dim3(256), 0, st, a); break;
-        case BM_L2: hipLaunchKernelGGL((rescore_kernel<D4, GROUP, BM_L2>), grid, dim3(256), 0, st, a); break;
-        default: return hipErrorInvalidValue;
-    }
+    hipLaunchKernelGGL((rescore_kernel<D4, GROUP, METRIC>), dim3((total + 4 * RPW - 1) / (4 * RPW)), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
 hipError_t launch_rescore(const RescoreArgs& a, int metric, hipStream_t st) {
-    switch (a.dims) {  // must mirror launch_scan's (D4, GROUP) table so distances are bit-identical
-        case 64: return launch_rescore_t<16, 16>(a, metric, st);
-        case 128: return launch_rescore_t<32, 32>(a, metric, st);
-        case 256: return launch_rescore_t<64, 64>(a, metric, st);
-        case 384: return launch_rescore_t<96, 32>(a, metric, st);
-        case 512: return launch_rescore_t<128, 64>(a, metric, st);
-        case 768: return launch_rescore_t<192, 64>(a, metric, st);
-        case 1024: return launch_rescore_t<256, 64>(a, metric, st);
-        case 1536: return launch_rescore_t<384, 64>(a, metric, st);
-        default: break;
-    }
-    if (a.qlist != nullptr || a.by_slot) return hipErrorInvalidValue;   // query lists: specialised dims only
-    const uint32_t total = a.nq * (uint32_t)a.kp;
-    const dim3 grid((total + 3) / 4);
-    switch (metric) {
-        case BM_COS: hipLaunchKernelGGL((rescore_generic_kernel<BM_COS>), grid, dim3(256), 0, st, a); break;
-        case BM_DOT: hipLaunchKernelGGL((rescore_generic_kernel<BM_DOT>), grid, dim3(256), 0, st, a); break;
-        case BM_L2: hipLaunchKernelGGL((rescore_generic_kernel<BM_L2>), grid, dim3(256), 0, st, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_metric(metric, [&](auto m) {
+        constexpr int METRIC = decltype(m)::value;
+        if (scan_group_lanes(a.dims) != 0)
+            return with_scan_shape(a.dims, [&](auto s) { return launch_rescore_t<decltype(s)::D4, decltype(s)::GROUP, METRIC>(a, st); },
+                                   hipErrorInvalidValue);
+        if (a.qlist != nullptr || a.by_slot) return hipErrorInvalidValue;   // query lists: specialised dims only
+        const uint32_t total = a.nq * (uint32_t)a.kp;
+        hipLaunchKernelGGL((rescore_generic_kernel<METRIC>), dim3((total + 3) / 4), dim3(256), 0, st, a);
+        return hipGetLastError();
+    }, hipErrorInvalidValue);
 }
 
 // ---------------------------------------------------------------------------
@@ -1520,11 +1427,11 @@ hipError_t launch_finalize_batch(const int64_t* cand, uint32_t cand_cap, const u
 // a_max - eps > exact k-th decides whether the answer is provably exact; anything else is re-run on the exact path.
 
 // The register-resident filtering GEMM (survivors into per-workgroup segments): cosine / dot at these dimensions.
-bool batch_onepass_fast(uint32_t dims, int metric) { return metric != BM_L2 && rq_dims(dims); }
+bool batch_onepass_fast(uint32_t dims, int metric) { return metric != M_L2 && rq_dims(dims); }
 // Everything else the MFMA path serves (L2; any other multiple of 64, e.g. 1024 / 1536) runs the same one-pass pipeline on
 // the LDS-tiled 128 x 128 kernel: survivors are appended to one counted list per query.
 bool batch_onepass_dims(uint32_t dims, int metric) {
-    return (dims % 64u) == 0 && dims >= 64 && metric >= BM_COS && metric <= BM_L2;
+    return (dims % 64u) == 0 && dims >= 64 && metric >= M_COS && metric <= M_L2;
 }
 uint32_t batch_tile_rows(uint32_t dims, int metric) {
     if (!batch_onepass_fast(dims, metric)) return (uint32_t)GN;
@@ -1581,7 +1488,7 @@ __global__ __launch_bounds__(256) void batch_prep_kernel(PrepArgs a) {
     acc = group_sum<64>(acc);
     acc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 63));
     const float nf = sqrtf(acc);
-    const float scale = (a.metric == BM_COS) ? ((nf > 1e-6f) ? 1.0f / nf : 0.0f) : 1.0f;
+    const float scale = (a.metric == M_COS) ? ((nf > COS_NORM_FLOOR) ? 1.0f / nf : 0.0f) : 1.0f;
     double qe2 = 0.0;                                    // ||x - bf16(x)||^2 of the scaled query block row x (exact differences)
     for (uint32_t c = lane; c < D; c += WAVE) {
         const float x = row[c] * scale;
@@ -1618,11 +1525,11 @@ __global__ __launch_bounds__(256) void batch_prep_kernel(PrepArgs a) {
         // (Rounds 1-3 used 2^-8 (1 + 2^-10) here, i.e. a unit roundoff of 2^-9 per operand: half of the true worst case. Random
         // rounding errors are two orders of magnitude below either, which is why no test ever saw it; errors that line up with the
         // query could have defeated it. The measured bound is rigorous AND about what the old constant was.)
-        const double qn_d = a.metric == BM_COS ? 1.0 + 1e-6 : (double)c;
+        const double qn_d = a.metric == M_COS ? 1.0 + 1e-6 : (double)c;
         // the mirror's measured bounds, where its conversions left them (device words: no host round trip between a conversion and this launch)
         const float max_norm = a.max_bits != nullptr ? __uint_as_float(a.max_bits[0]) : 0.f;
         const float max_row_err = (a.max_bits != nullptr && a.use_measured) ? __uint_as_float(a.max_bits[1]) : 0.f;
-        const double vn_d = a.metric == BM_COS ? 1.0 + 1e-6 : (double)max_norm;
+        const double vn_d = a.metric == M_COS ? 1.0 + 1e-6 : (double)max_norm;
         const double u = 0.0078125 * (1.0 + 1.0 / 512.0) + (double)D * 5.97e-8 + 1e-6;          // worst case, relative to ||q|| max||v||
         double dot_err = u * qn_d * vn_d * 1.001;
         if (max_row_err > 0.f) {
@@ -1631,8 +1538,8 @@ __global__ __launch_bounds__(256) void batch_prep_kernel(PrepArgs a) {
             if (measured < dot_err) dot_err = measured;
         }
         float eps;
-        if (a.metric == BM_COS) eps = (float)(dot_err + 3e-6);
-        else if (a.metric == BM_DOT) eps = (float)(dot_err + 1e-6 * (1.0 + qn_d * vn_d));
+        if (a.metric == M_COS) eps = (float)(dot_err + 3e-6);
+        else if (a.metric == M_DOT) eps = (float)(dot_err + 1e-6 * (1.0 + qn_d * vn_d));
         else {   // L2: ||q||^2 + ||v||^2 - 2 q.v carries the factor 2 and the norms' own rounding
             const double ss = (double)c * (double)c + (double)max_norm * (double)max_norm;
             eps = (float)(2.0 * dot_err + 4e-6 * (1.0 + ss));
@@ -1665,9 +1572,9 @@ hipError_t launch_batch_gemm_sample(const GemmArgs& a, int metric, hipStream_t s
     if (!batch_onepass_fast(a.dims, metric)) {   // LDS-tiled kernel: one workgroup per (sampled tile, 128 queries)
         const dim3 grid(a.sample_tiles * a.nqt);
         switch (metric) {
-            case BM_COS: hipLaunchKernelGGL((batch_gemm_kernel<BM_COS, true>), grid, dim3(256), 0, st, a); break;
-            case BM_DOT: hipLaunchKernelGGL((batch_gemm_kernel<BM_DOT, true>), grid, dim3(256), 0, st, a); break;
-            default: hipLaunchKernelGGL((batch_gemm_kernel<BM_L2, true>), grid, dim3(256), 0, st, a); break;
+            case M_COS: hipLaunchKernelGGL((batch_gemm_kernel<M_COS, true>), grid, dim3(256), 0, st, a); break;
+            case M_DOT: hipLaunchKernelGGL((batch_gemm_kernel<M_DOT, true>), grid, dim3(256), 0, st, a); break;
+            default: hipLaunchKernelGGL((batch_gemm_kernel<M_L2, true>), grid, dim3(256), 0, st, a); break;
         }
         return hipGetLastError();
     }
@@ -1759,7 +1666,7 @@ hipError_t launch_pick_tau(const float* tile_max, uint32_t sample_tiles, uint32_
                            float* tau, int metric, hipStream_t st) {
     if (rank < 1 || rank > (uint32_t)PICK_J || sample_tiles == 0 || (nq_pad % 32u) != 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(pick_tau_kernel, dim3((nq + 31) / 32), dim3(1024), 0, st, tile_max, sample_tiles, nq, nq_pad, rank, tau,
-                       metric == BM_L2 ? 1 : 0);
+                       metric == M_L2 ? 1 : 0);
     return hipGetLastError();
 }
 
@@ -1838,7 +1745,7 @@ __global__ __launch_bounds__(SCAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
     for (int w = 0; w < SCAN_WAVES; ++w) total += counts[w];
     const int m = total < kp ? total : kp;                  // candidates to re-score
     __syncthreads();                                        // everyone has read counts / the lists before `sorted` reuses them
-    // exact f32 distance of every candidate with scan_kernel's (D4, GROUP) lane mapping and summation order
+    // exact f32 distance of every candidate (row_distance: the bits of the single-query scan)
     {
         const int sub = lane / GROUP, gl = lane % GROUP;
         const float qn = a.q_norm[q];
@@ -1864,13 +1771,7 @@ __global__ __launch_bounds__(SCAN_THREADS) __attribute__((amdgpu_waves_per_eu(8,
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int c = c0 + u * SCAN_WAVES * RPW + sub;
-                f32x4 acc = {0.f, 0.f, 0.f, 0.f}, nrm = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int j = 0; j < LOADS; ++j) accumulate_b<METRIC>(qv[j], v[u][j], acc, nrm);
-                const float s = group_sum<GROUP>(hsum_b(acc));
-                float mm = 0.f;
-                if (METRIC == BM_COS) mm = group_sum<GROUP>(hsum_b(nrm));
-                const float d = finish_distance_b<METRIC>(s, mm, qn);
+                const float d = row_distance<GROUP, LOADS, METRIC>(qv, v[u], qn);
                 if (c < m && gl == GROUP - 1) ex[c] = make_key(d, key_row(ck[u]));
             }
         }
@@ -2035,13 +1936,7 @@ __global__ __launch_bounds__(RETRY_WAVES * 64) void batch_retry_kernel(FinishArg
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const uint32_t ci = c0 + (uint32_t)(u * RPW + sub);
-                f32x4 acc = {0.f, 0.f, 0.f, 0.f}, nrm = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int j = 0; j < LOADS; ++j) accumulate_b<METRIC>(qv[j], v[u][j], acc, nrm);
-                const float s2 = group_sum<GROUP>(hsum_b(acc));
-                float mm = 0.f;
-                if (METRIC == BM_COS) mm = group_sum<GROUP>(hsum_b(nrm));
-                const float d = finish_distance_b<METRIC>(s2, mm, qn);
+                const float d = row_distance<GROUP, LOADS, METRIC>(qv, v[u], qn);
                 tk.push(make_key(d, grow[u]), ci < n && gl == GROUP - 1);
             }
         }
@@ -2071,30 +1966,19 @@ __global__ __launch_bounds__(RETRY_WAVES * 64) void batch_retry_kernel(FinishArg
     }
 }
 
-template <int D4, int GROUP>
-static hipError_t launch_retry_t(const FinishArgs& a, int metric, hipStream_t st) {
-    switch (metric) {
-        case BM_COS: hipLaunchKernelGGL((batch_retry_kernel<D4, GROUP, BM_COS>), dim3(a.nq), dim3(RETRY_WAVES * 64), 0, st, a); break;
-        case BM_DOT: hipLaunchKernelGGL((batch_retry_kernel<D4, GROUP, BM_DOT>), dim3(a.nq), dim3(RETRY_WAVES * 64), 0, st, a); break;
-        case BM_L2: hipLaunchKernelGGL((batch_retry_kernel<D4, GROUP, BM_L2>), dim3(a.nq), dim3(RETRY_WAVES * 64), 0, st, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
 // The device-side full retry behind a fused finish (same arguments; a.cert_dev must be the array that finish wrote).
-bool batch_retry_dims(uint32_t dims) { return dims == 128 || dims == 256 || dims == 384 || dims == 512 || dims == 768; }
+// It re-scores the filtering GEMM's survivors, so it exists where that GEMM does (batch_gemm_rq_kernel's dimensions).
+using RetryDims = DimList<128, 256, 384, 512, 768>;
+bool batch_retry_dims(uint32_t dims) { return in_dim_list(RetryDims{}, dims); }
 hipError_t launch_batch_retry(const FinishArgs& a, int metric, hipStream_t st) {
     if (a.nq == 0) return hipSuccess;
     if (a.cert_dev == nullptr || a.k < 1 || a.k > FUSED_MAX_K || a.qlist != nullptr) return hipErrorInvalidValue;   // any k' (fused or three-launch finish), k <= 192
-    switch (a.dims) {   // (D4, GROUP) as in launch_batch_finish / launch_scan
-        case 128: return launch_retry_t<32, 32>(a, metric, st);
-        case 256: return launch_retry_t<64, 64>(a, metric, st);
-        case 384: return launch_retry_t<96, 32>(a, metric, st);
-        case 512: return launch_retry_t<128, 64>(a, metric, st);
-        case 768: return launch_retry_t<192, 64>(a, metric, st);
-        default: return hipErrorInvalidValue;
-    }
+    return with_scan_shape(RetryDims{}, a.dims, [&](auto s) {
+        return with_metric(metric, [&](auto m) {
+            hipLaunchKernelGGL((batch_retry_kernel<decltype(s)::D4, decltype(s)::GROUP, decltype(m)::value>), dim3(a.nq), dim3(RETRY_WAVES * 64), 0, st, a);
+            return hipGetLastError();
+        }, hipErrorInvalidValue);
+    }, hipErrorInvalidValue);
 }
 
 // Large k' (193 .. 960): the same steps as three launches.
@@ -2162,35 +2046,20 @@ __global__ __launch_bounds__(1024) void finalize_big_kernel(FinishArgs a) {
     }
 }
 
-template <int D4, int GROUP>
-static hipError_t launch_finish_t(const FinishArgs& a, int metric, hipStream_t st) {
-    if (metric == BM_COS) hipLaunchKernelGGL((batch_finish_kernel<D4, GROUP, BM_COS>), dim3(a.nq), dim3(SCAN_THREADS), 0, st, a);
-    else if (metric == BM_DOT) hipLaunchKernelGGL((batch_finish_kernel<D4, GROUP, BM_DOT>), dim3(a.nq), dim3(SCAN_THREADS), 0, st, a);
-    else hipLaunchKernelGGL((batch_finish_kernel<D4, GROUP, BM_L2>), dim3(a.nq), dim3(SCAN_THREADS), 0, st, a);
-    return hipGetLastError();
-}
-
 // Dimensions with a fused finish kernel (= a specialised scan kernel); any other multiple of 64 takes the three-launch form
 // below, whose re-score has a generic-dims kernel.
-bool batch_finish_fused_dims(uint32_t dims) {
-    return dims == 64 || dims == 128 || dims == 256 || dims == 384 || dims == 512 || dims == 768 || dims == 1024 || dims == 1536;
-}
+bool batch_finish_fused_dims(uint32_t dims) { return scan_group_lanes(dims) != 0; }
 
 hipError_t launch_batch_finish(const FinishArgs& a, int metric, hipStream_t st) {
     if (a.nq == 0) return hipSuccess;
     if (!batch_onepass_dims(a.dims, metric) || a.k < 1 || a.k > a.kp) return hipErrorInvalidValue;
     if (a.kp <= FUSED_MAX_K && a.qlist == nullptr && batch_finish_fused_dims(a.dims)) {
-        switch (a.dims) {   // (D4, GROUP) must mirror launch_scan's table: distances bit-identical to the single-query path
-            case 64: return launch_finish_t<16, 16>(a, metric, st);
-            case 128: return launch_finish_t<32, 32>(a, metric, st);
-            case 256: return launch_finish_t<64, 64>(a, metric, st);
-            case 384: return launch_finish_t<96, 32>(a, metric, st);
-            case 512: return launch_finish_t<128, 64>(a, metric, st);
-            case 768: return launch_finish_t<192, 64>(a, metric, st);
-            case 1024: return launch_finish_t<256, 64>(a, metric, st);
-            case 1536: return launch_finish_t<384, 64>(a, metric, st);
-            default: return hipErrorInvalidValue;
-        }
+        return with_scan_shape(a.dims, [&](auto s) {
+            return with_metric(metric, [&](auto m) {
+                hipLaunchKernelGGL((batch_finish_kernel<decltype(s)::D4, decltype(s)::GROUP, decltype(m)::value>), dim3(a.nq), dim3(SCAN_THREADS), 0, st, a);
+                return hipGetLastError();
+            }, hipErrorInvalidValue);
+        }, hipErrorInvalidValue);
     }
     if (a.kp > 960 || a.sel == nullptr || a.exact == nullptr) return hipErrorInvalidValue;
     {

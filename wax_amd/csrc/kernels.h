@@ -90,7 +90,7 @@ struct alignas(16) ScanArgsQ {
 };
 static_assert(sizeof(ScanArgsQ<768>) <= 4096, "HIP kernel arguments are limited to 4 KB");
 // whether launch_scan can take the query through the kernel arguments for this shape (scan_kernel_qarg instantiations)
-inline bool scan_query_args_dims(uint32_t dims) { return dims == 384 || dims == 768; }
+bool scan_query_args_dims(uint32_t dims);
 constexpr int SCAN_FUSE_MERGE_GRID = 160;   // largest grid whose last-arriving workgroup does the final merge (any k <= FUSED_MAX_K)
 // k <= SCAN_KWAY_MAX_K: the last arriver merges the lists' HEADS (k rounds of a workgroup-wide minimum; cost independent of the number
 // of lists), so every grid the engine launches by default (<= 512 workgroups = two lists per thread) can merge in the scan kernel:

@@ -26,53 +26,16 @@
 #include <cstring>
 
 #include "kernels.h"
+#include "row_math.h"
 #include "topk.h"
 
 namespace wax {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-enum { M_COS = WAX_HIP_METRIC_COSINE, M_DOT = WAX_HIP_METRIC_DOT, M_L2 = WAX_HIP_METRIC_L2 };
 
 template <bool NT>
 __device__ inline f32x4 ld16(const f32x4* p) {
     if (NT) return __builtin_nontemporal_load(p);
     return *p;
 }
-
-// a3 + a6 (distance side): CosineDistance.metal:321-325 rule `sqrt(m) > 1e-6 ? dot/sqrt(m) : 0`,
-// extended to the true cosine the CPU path computes (divide by ||q|| as well;
-// SURVEY.md §7 "Query-norm semantics"); dot / l2 use USearch's ip / l2sq distances
-// (VectorMetric.swift:21-30). NaN -> +inf so it sorts last and is dropped on the host
-// like MetalVectorEngine.swift:597; "+ 0.0f" folds -0 into +0.
-template <int METRIC>
-__device__ inline float finish_distance(float acc, float nrm, float q_norm) {
-    float d;
-    if (METRIC == M_COS) {
-        const float vn = sqrtf(nrm);
-        const float sim = (vn > 1e-6f && q_norm > 1e-6f) ? acc / (vn * q_norm) : 0.0f;
-        d = 1.0f - sim;
-    } else if (METRIC == M_DOT) {
-        d = 1.0f - acc;
-    } else {
-        d = acc;
-    }
-    d = (d != d) ? __builtin_inff() : d;
-    return d + 0.0f;
-}
-
-template <int METRIC>
-__device__ inline void accumulate(const f32x4& q, const f32x4& v, f32x4& acc, f32x4& nrm) {
-    if (METRIC == M_L2) {
-        const f32x4 e = q - v;
-        acc = __builtin_elementwise_fma(e, e, acc);
-    } else {
-        acc = __builtin_elementwise_fma(q, v, acc);
-        if (METRIC == M_COS) nrm = __builtin_elementwise_fma(v, v, nrm);
-    }
-}
-
-__device__ inline float hsum(const f32x4& a) { return (a.x + a.y) + (a.z + a.w); }
 
 // Tail of the fused scan kernels: the workgroup's k best keys are in `fin` (LDS, ascending, KEY_PAD padded).
 // Ordinary launch: store them as this workgroup's partial list. Fused-merge launch (a.merge_out != nullptr): publish the
@@ -215,11 +178,8 @@ __device__ __forceinline__ void scan_body(const ScanArgs& a, const f32x4* __rest
         for (int u = 0; u < UNROLL; ++u) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f}, nrm = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int j = 0; j < LOADS; ++j) accumulate<METRIC>(q[j], v[u][j], acc, nrm);
-            float s = group_sum<GROUP>(hsum(acc));
-            float m = 0.f;
-            if (METRIC == M_COS) m = group_sum<GROUP>(hsum(nrm));
-            const float d = finish_distance<METRIC>(s, m, a.q_norm);
+            for (int j = 0; j < LOADS; ++j) accumulate<METRIC>(q[j], v[u][j], acc, nrm);   // (row_distance, spelt out: see row_math.h)
+            const float d = finish_row<GROUP, METRIC>(acc, nrm, a.q_norm);
             const uint32_t r = rbase + u * RPW;
             const bool valid = owner && (r < n);
             if (WRITE_DIST) {
@@ -253,8 +213,6 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_generic_kernel(ScanArgs a) 
     const int lane = lane_id();
     const int wave = (int)(threadIdx.x >> 6);
     const uint32_t n = a.n_rows, D = a.dims;
-    const bool vec4 = (D & 3u) == 0;
-    const uint32_t D4 = D >> 2;
 
     WaveTopK<CAP> tk;
     if (!WRITE_DIST) tk.init(lds + wave * CAP, a.k);
@@ -263,23 +221,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_generic_kernel(ScanArgs a) 
     const uint32_t nwaves = gridDim.x * SCAN_WAVES;
     for (uint32_t r = gwave; r < n; r += nwaves) {
         if (!WRITE_DIST) tk.make_room(1);
-        const float* row = a.store + (size_t)r * D;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f}, nrm = {0.f, 0.f, 0.f, 0.f};
-        if (vec4) {
-            const f32x4* row4 = reinterpret_cast<const f32x4*>(row);
-            const f32x4* q4 = reinterpret_cast<const f32x4*>(a.query);
-            for (uint32_t c = lane; c < D4; c += WAVE) accumulate<METRIC>(q4[c], row4[c], acc, nrm);
-        } else {
-            for (uint32_t c = lane; c < D; c += WAVE) {
-                const f32x4 qq = {a.query[c], 0.f, 0.f, 0.f};
-                const f32x4 vv = {row[c], 0.f, 0.f, 0.f};
-                accumulate<METRIC>(qq, vv, acc, nrm);
-            }
-        }
-        float s = group_sum<64>(hsum(acc));
-        float m = 0.f;
-        if (METRIC == M_COS) m = group_sum<64>(hsum(nrm));
-        const float d = finish_distance<METRIC>(s, m, a.q_norm);
+        const float d = generic_row_distance<METRIC>(a.store + (size_t)r * D, a.query, D, lane, a.q_norm);
         const bool valid = (lane == WAVE - 1);
         if (WRITE_DIST) {
             if (valid) a.dist_out[r] = d;
@@ -302,28 +244,19 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_generic_kernel(ScanArgs a) 
 // ---------------------------------------------------------------------------
 // variant registry
 
-struct DimSpec { uint32_t dims; int group; };
-static const DimSpec kDimSpecs[] = {
-    {64, 16}, {128, 32}, {256, 64}, {384, 32}, {512, 64}, {768, 64}, {1024, 64}, {1536, 64},
-};
-
 struct VariantSpec { int unroll; int nt; };
 // variant 0 is the production default; the others exist for on-device sweeps (tools/sweep.py).
-static const VariantSpec kVariants384[] = {{4, 1}, {4, 0}, {2, 1}, {2, 0}, {8, 1}, {8, 0}, {1, 1}};
-static const VariantSpec kVariants768[] = {{2, 1}, {2, 0}, {4, 1}, {1, 1}};
+static constexpr VariantSpec kVariants384[] = {{4, 1}, {4, 0}, {2, 1}, {2, 0}, {8, 1}, {8, 0}, {1, 1}};
+static constexpr VariantSpec kVariants768[] = {{2, 1}, {2, 0}, {4, 1}, {1, 1}};
 
-static int default_unroll(uint32_t dims, int group) {
-    const int loads = (int)(dims / 4) / group;
-    int u = 12 / loads;
-    if (u < 1) u = 1;
-    if (u > 4) u = 4;
-    return u;
+// row groups in flight per wave (speed only; the lanes per row, which fix the bits, come from row_math.h's table)
+static constexpr int default_unroll(int loads) {
+    const int u = 12 / loads;
+    return u < 1 ? 1 : (u > 4 ? 4 : u);
 }
-
-static const DimSpec* find_dim(uint32_t dims) {
-    for (const auto& s : kDimSpecs)
-        if (s.dims == dims) return &s;
-    return nullptr;
+template <typename S>
+static constexpr int production_unroll() {
+    return S::DIMS == 384 ? kVariants384[0].unroll : S::DIMS == 768 ? kVariants768[0].unroll : default_unroll(S::LOADS);
 }
 
 int scan_variant_count(uint32_t dims) {
@@ -334,16 +267,16 @@ int scan_variant_count(uint32_t dims) {
 
 bool scan_variant_info(uint32_t dims, int variant, ScanVariantInfo* out) {
     if (variant < 0 || variant >= scan_variant_count(dims)) return false;
-    const DimSpec* s = find_dim(dims);
-    if (!s) {
+    const int group = scan_group_lanes(dims);
+    if (group == 0) {
         *out = ScanVariantInfo{1, 0, 64, 1, 0};
         return true;
     }
     VariantSpec v;
     if (dims == 384) v = kVariants384[variant];
     else if (dims == 768) v = kVariants768[variant];
-    else v = VariantSpec{default_unroll(dims, s->group), 1};
-    *out = ScanVariantInfo{v.unroll, v.nt, s->group, (WAVE / s->group) * v.unroll, 1};
+    else v = VariantSpec{default_unroll((int)(dims / 4) / group), 1};
+    *out = ScanVariantInfo{v.unroll, v.nt, group, (WAVE / group) * v.unroll, 1};
     return true;
 }
 
@@ -407,28 +340,21 @@ static hipError_t launch_qarg_metric(const ScanArgs& a, int cap, int grid, hipSt
 }
 template <int D4, int GROUP, int UNROLL, bool NT>
 static hipError_t launch_qarg(const ScanArgs& a, int metric, int cap, int grid, hipStream_t st) {
-    switch (metric) {
-        case M_COS: return launch_qarg_metric<D4, GROUP, UNROLL, NT, M_COS>(a, cap, grid, st);
-        case M_DOT: return launch_qarg_metric<D4, GROUP, UNROLL, NT, M_DOT>(a, cap, grid, st);
-        case M_L2: return launch_qarg_metric<D4, GROUP, UNROLL, NT, M_L2>(a, cap, grid, st);
-    }
-    return hipErrorInvalidValue;
+    return with_metric(metric, [&](auto m) { return launch_qarg_metric<D4, GROUP, UNROLL, NT, decltype(m)::value>(a, cap, grid, st); },
+                       hipErrorInvalidValue);
 }
 
 template <int D4, int GROUP, int UNROLL, bool NT>
 static hipError_t launch_full(const ScanArgs& a, int metric, int cap, bool write_dist, int grid, hipStream_t st) {
-    switch (metric) {
-        case M_COS: return launch_metric<D4, GROUP, UNROLL, NT, M_COS>(a, cap, write_dist, grid, st);
-        case M_DOT: return launch_metric<D4, GROUP, UNROLL, NT, M_DOT>(a, cap, write_dist, grid, st);
-        case M_L2: return launch_metric<D4, GROUP, UNROLL, NT, M_L2>(a, cap, write_dist, grid, st);
-    }
-    return hipErrorInvalidValue;
+    return with_metric(metric, [&](auto m) { return launch_metric<D4, GROUP, UNROLL, NT, decltype(m)::value>(a, cap, write_dist, grid, st); },
+                       hipErrorInvalidValue);
 }
 
 // sweep-only variants: cosine, k <= 64, fused path; anything else falls back to variant 0
-template <int D4, int GROUP, int UNROLL, bool NT>
+template <int DIMS, int UNROLL, bool NT>
 static hipError_t launch_sweep(const ScanArgs& a, int grid, hipStream_t st) {
-    launch_kernel((scan_kernel<D4, GROUP, M_COS, UNROLL, NT, 128, false>), dim3(grid), dim3(SCAN_THREADS), 0, st, a);
+    using S = ScanShape<DIMS>;
+    launch_kernel((scan_kernel<S::D4, S::GROUP, M_COS, UNROLL, NT, 128, false>), dim3(grid), dim3(SCAN_THREADS), 0, st, a);
     return hipGetLastError();
 }
 
@@ -444,6 +370,11 @@ static hipError_t launch_generic_metric(const ScanArgs& a, int cap, bool write_d
     return hipGetLastError();
 }
 
+// Dimensions whose query can travel in the kernel arguments (scan_kernel_qarg instantiations): the BASELINE dimensions — where
+// launch latency is what a small store's query costs, and the arguments plus dims floats fit the 4 KB kernarg limit.
+using QueryArgDims = DimList<384, 768>;
+bool scan_query_args_dims(uint32_t dims) { return in_dim_list(QueryArgDims{}, dims); }
+
 hipError_t launch_scan(const ScanArgs& args, int metric, int variant, int cap, bool write_dist, int grid_cap,
                        hipStream_t st, int* out_grid, bool* out_merged) {
     if (variant < 0 || variant >= scan_variant_count(args.dims)) variant = 0;
@@ -456,48 +387,44 @@ hipError_t launch_scan(const ScanArgs& args, int metric, int variant, int cap, b
     const bool small = a.plain_loads != 0;             // a store that lives in the caches between queries (see below; the caller decides)
     if (!fuse) { a.merge_out = nullptr; a.arrive = nullptr; a.done_flag = nullptr; }
     if (out_merged) *out_merged = fuse;
-    // query in the kernel arguments: the BASELINE dimensions, default variant, fused path (the caller decides when — launch_scan
-    // only refuses what it has no kernel for, by falling through to the pointer form, which needs args.query)
+    // query in the kernel arguments: default variant, fused path (the caller decides when — launch_scan only refuses what it has no
+    // kernel for, by falling through to the pointer form, which needs args.query)
     // Small stores (a.plain_loads: the caller's rule) read their rows with ordinary loads instead of the streaming (non-temporal)
     // loads of the large-store kernels: 0.7 - 0.9 us per query faster up to ~30 MB of rows, equal to 230 MB, slower beyond
     // (profiles/HISTORY.md).
-    if (a.query_host != nullptr && !write_dist && variant == 0) {
-        if (a.dims == 384) return (fuse && small) ? launch_qarg<96, 32, 4, false>(a, metric, cap, grid, st) : launch_qarg<96, 32, 4, true>(a, metric, cap, grid, st);
-        if (a.dims == 768) return (fuse && small) ? launch_qarg<192, 64, 2, false>(a, metric, cap, grid, st) : launch_qarg<192, 64, 2, true>(a, metric, cap, grid, st);
+    if (a.query_host != nullptr && !write_dist && variant == 0 && scan_query_args_dims(a.dims)) {
+        return with_scan_shape(QueryArgDims{}, a.dims, [&](auto s) {
+            using S = decltype(s);
+            constexpr int U = production_unroll<S>();
+            return (fuse && small) ? launch_qarg<S::D4, S::GROUP, U, false>(a, metric, cap, grid, st)
+                                   : launch_qarg<S::D4, S::GROUP, U, true>(a, metric, cap, grid, st);
+        }, hipErrorInvalidValue);
     }
     if (a.query == nullptr) return hipErrorInvalidValue;
-    switch (a.dims) {
-        case 64: return launch_full<16, 16, 4, true>(a, metric, cap, write_dist, grid, st);
-        case 128: return launch_full<32, 32, 4, true>(a, metric, cap, write_dist, grid, st);
-        case 256: return launch_full<64, 64, 4, true>(a, metric, cap, write_dist, grid, st);
-        case 384:
-            switch (variant) {
-                case 1: return launch_sweep<96, 32, 4, false>(a, grid, st);
-                case 2: return launch_sweep<96, 32, 2, true>(a, grid, st);
-                case 3: return launch_sweep<96, 32, 2, false>(a, grid, st);
-                case 4: return launch_sweep<96, 32, 8, true>(a, grid, st);
-                case 5: return launch_sweep<96, 32, 8, false>(a, grid, st);
-                case 6: return launch_sweep<96, 32, 1, true>(a, grid, st);
-                default: return launch_full<96, 32, 4, true>(a, metric, cap, write_dist, grid, st);
-            }
-        case 512: return launch_full<128, 64, 4, true>(a, metric, cap, write_dist, grid, st);
-        case 768:
-            switch (variant) {
-                case 1: return launch_sweep<192, 64, 2, false>(a, grid, st);
-                case 2: return launch_sweep<192, 64, 4, true>(a, grid, st);
-                case 3: return launch_sweep<192, 64, 1, true>(a, grid, st);
-                default: return launch_full<192, 64, 2, true>(a, metric, cap, write_dist, grid, st);
-            }
-        case 1024: return launch_full<256, 64, 3, true>(a, metric, cap, write_dist, grid, st);
-        case 1536: return launch_full<384, 64, 2, true>(a, metric, cap, write_dist, grid, st);
-        default: break;
+    if (a.dims == 384) {
+        switch (variant) {
+            case 1: return launch_sweep<384, 4, false>(a, grid, st);
+            case 2: return launch_sweep<384, 2, true>(a, grid, st);
+            case 3: return launch_sweep<384, 2, false>(a, grid, st);
+            case 4: return launch_sweep<384, 8, true>(a, grid, st);
+            case 5: return launch_sweep<384, 8, false>(a, grid, st);
+            case 6: return launch_sweep<384, 1, true>(a, grid, st);
+            default: break;
+        }
+    } else if (a.dims == 768) {
+        switch (variant) {
+            case 1: return launch_sweep<768, 2, false>(a, grid, st);
+            case 2: return launch_sweep<768, 4, true>(a, grid, st);
+            case 3: return launch_sweep<768, 1, true>(a, grid, st);
+            default: break;
+        }
     }
-    switch (metric) {
-        case M_COS: return launch_generic_metric<M_COS>(a, cap, write_dist, grid, st);
-        case M_DOT: return launch_generic_metric<M_DOT>(a, cap, write_dist, grid, st);
-        case M_L2: return launch_generic_metric<M_L2>(a, cap, write_dist, grid, st);
-    }
-    return hipErrorInvalidValue;
+    if (scan_group_lanes(a.dims) == 0)
+        return with_metric(metric, [&](auto m) { return launch_generic_metric<decltype(m)::value>(a, cap, write_dist, grid, st); }, hipErrorInvalidValue);
+    return with_scan_shape(a.dims, [&](auto s) {
+        using S = decltype(s);
+        return launch_full<S::D4, S::GROUP, production_unroll<S>(), true>(a, metric, cap, write_dist, grid, st);
+    }, hipErrorInvalidValue);
 }
 
 // ---------------------------------------------------------------------------

@@ -18,6 +18,7 @@
 #include <cstring>
 
 #include "kernels.h"
+#include "row_math.h"
 #include "topk.h"
 
 namespace wax {
@@ -25,42 +26,9 @@ namespace wax {
 namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-enum { MM_COS = WAX_HIP_METRIC_COSINE, MM_DOT = WAX_HIP_METRIC_DOT, MM_L2 = WAX_HIP_METRIC_L2 };
-
 constexpr int MIRROR_UNROLL = 4;      // row groups in flight per wave: 3 x 4 dwordx4 loads per lane, as scan_kernel's 384-d form
-
-// ---- the f32 arithmetic of scan_kernel (kernels.hip), repeated verbatim: the re-scored distances must be bit-identical ----
-template <int METRIC>
-__device__ inline float finish_distance_m(float acc, float nrm, float q_norm) {
-    float d;
-    if (METRIC == MM_COS) {
-        const float vn = sqrtf(nrm);
-        const float sim = (vn > 1e-6f && q_norm > 1e-6f) ? acc / (vn * q_norm) : 0.0f;
-        d = 1.0f - sim;
-    } else if (METRIC == MM_DOT) {
-        d = 1.0f - acc;
-    } else {
-        d = acc;
-    }
-    d = (d != d) ? __builtin_inff() : d;
-    return d + 0.0f;
-}
-
-template <int METRIC>
-__device__ inline void accumulate_m(const f32x4& q, const f32x4& v, f32x4& acc, f32x4& nrm) {
-    if (METRIC == MM_L2) {
-        const f32x4 e = q - v;
-        acc = __builtin_elementwise_fma(e, e, acc);
-    } else {
-        acc = __builtin_elementwise_fma(q, v, acc);
-        if (METRIC == MM_COS) nrm = __builtin_elementwise_fma(v, v, nrm);
-    }
-}
-
-__device__ inline float hsum_m(const f32x4& a) { return (a.x + a.y) + (a.z + a.w); }
 
 // two bf16 in one dword -> two f32, exactly (element 2i is the low half)
 __device__ inline f32x2 widen(unsigned int w) {
@@ -70,10 +38,9 @@ __device__ inline f32x2 widen(unsigned int w) {
     return r;
 }
 
-// f32 scan's (GROUP, LOADS) at this dimension: scan_kernel<96, 32, ...> at 384, <192, 64, ...> at 768 (kernels.hip launch_scan)
-template <int DIMS> struct F32Shape;
-template <> struct F32Shape<384> { static constexpr int D4 = 96, GROUP = 32; };
-template <> struct F32Shape<768> { static constexpr int D4 = 192, GROUP = 64; };
+// The dimensions with a mirror scan: the BASELINE pair (three dwordx4 of bf16 per lane and row divide them; kernel arguments hold
+// the query). The exact re-score takes its lanes per row from ScanShape<DIMS> (row_math.h), like every exact path.
+using MirrorDims = DimList<384, 768>;
 
 // mirror lanes per row: three dwordx4 (24 bf16) per lane and row
 template <int DIMS> struct MirrorShape { static constexpr int D8 = DIMS / 8, GROUP = D8 / 3; };
@@ -109,7 +76,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void mirror_scan_kernel(MirrorScanArg
         q[j][0] = lo.xy; q[j][1] = lo.zw; q[j][2] = hi.xy; q[j][3] = hi.zw;
     }
     // cosine: mirror rows are unit vectors (or zero), so sim = acc / ||q||; the rule for a null query is the f32 scan's
-    const float inv_qn = a.q_norm > 1e-6f ? 1.0f / a.q_norm : 0.0f;
+    const float inv_qn = a.q_norm > COS_NORM_FLOOR ? 1.0f / a.q_norm : 0.0f;
 
     const u32x4* __restrict__ mirror4 = reinterpret_cast<const u32x4*>(a.mirror);
     WaveTopK<CAP> tk;
@@ -143,7 +110,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void mirror_scan_kernel(MirrorScanArg
             }
             const f32x2 s2 = (acc[0] + acc[1]) + (acc[2] + acc[3]);
             const float s = group_sum<GROUP>(s2.x + s2.y);
-            float d = METRIC == MM_COS ? 1.0f - s * inv_qn : 1.0f - s;
+            float d = METRIC == M_COS ? 1.0f - s * inv_qn : 1.0f - s;
             d = (d != d) ? __builtin_inff() : d;
             const uint32_t r = rbase + u * RPW;
             tk.push(make_key(d + 0.0f, a.row_base + r), owner && (r < n));
@@ -163,9 +130,9 @@ __global__ __launch_bounds__(SCAN_THREADS) void mirror_scan_kernel(MirrorScanArg
 
 template <int DIMS, int METRIC>
 __global__ __launch_bounds__(SCAN_THREADS) void mirror_finish_kernel(MirrorScanArgsQ<DIMS> aq) {
-    constexpr int D4 = F32Shape<DIMS>::D4;
-    constexpr int GROUP = F32Shape<DIMS>::GROUP;
-    constexpr int LOADS = D4 / GROUP;
+    constexpr int D4 = ScanShape<DIMS>::D4;
+    constexpr int GROUP = ScanShape<DIMS>::GROUP;
+    constexpr int LOADS = ScanShape<DIMS>::LOADS;
     constexpr int RPW = WAVE / GROUP;
     constexpr int ROWS_PER_PASS = RPW * SCAN_WAVES;
     constexpr int PASSES = MIRROR_KP / ROWS_PER_PASS;
@@ -180,7 +147,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void mirror_finish_kernel(MirrorScanA
     if (a.lists <= SCAN_THREADS) kway_merge<1>(a.partials, a.lists, MIRROR_KP, approx, xch);
     else kway_merge<2>(a.partials, a.lists, MIRROR_KP, approx, xch);
 
-    // (2) exact f32 re-score of those rows: scan_kernel's lane mapping, accumulation and finish at this dimension
+    // (2) exact f32 re-score of those rows: row_distance (row_math.h) at the f32 scan's shape for this dimension
     const char* ka = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
     const f32x4* q4 = reinterpret_cast<const f32x4*>(ka + offsetof(MirrorScanArgsQ<DIMS>, q));
     const int sub = lane / GROUP, gl = lane % GROUP;
@@ -204,13 +171,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void mirror_finish_kernel(MirrorScanA
     }
 #pragma unroll
     for (int p = 0; p < PASSES; ++p) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f}, nrm = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < LOADS; ++j) accumulate_m<METRIC>(q[j], v[p][j], acc, nrm);
-        const float s = group_sum<GROUP>(hsum_m(acc));
-        float m = 0.f;
-        if (METRIC == MM_COS) m = group_sum<GROUP>(hsum_m(nrm));
-        const float d = finish_distance_m<METRIC>(s, m, a.q_norm);
+        const float d = row_distance<GROUP, LOADS, METRIC>(q, v[p], a.q_norm);
         if (gl == GROUP - 1) exact[p * ROWS_PER_PASS + wave * RPW + sub] = live[p] ? make_key(d, grow[p]) : KEY_PAD;
     }
     __syncthreads();
@@ -248,15 +209,15 @@ __global__ __launch_bounds__(SCAN_THREADS) void mirror_finish_kernel(MirrorScanA
         const unsigned int* mb = a.max_bits;
         const float max_norm = __uint_as_float(mb[0]);
         const float max_row_err = a.use_measured ? __uint_as_float(mb[1]) : 0.f;
-        const double qn_d = METRIC == MM_COS ? 1.0 + 1e-6 : (double)a.q_norm;
-        const double vn_d = METRIC == MM_COS ? 1.0 + 1e-6 : (double)max_norm;
+        const double qn_d = METRIC == M_COS ? 1.0 + 1e-6 : (double)a.q_norm;
+        const double vn_d = METRIC == M_COS ? 1.0 + 1e-6 : (double)max_norm;
         const double u = 0.0078125 * (1.0 + 1.0 / 512.0) + (double)DIMS * 5.97e-8 + 1e-6;
         double dot_err = u * qn_d * vn_d * 1.001;
         if (max_row_err > 0.f) {
             const double measured = qn_d * (double)max_row_err * 1.001 + 3.0 * (double)DIMS * 5.97e-8 * qn_d * vn_d;
             if (measured < dot_err) dot_err = measured;
         }
-        float eps = METRIC == MM_COS ? (float)(dot_err + 3e-6) : (float)(dot_err + 1e-6 * (1.0 + qn_d * vn_d));
+        float eps = METRIC == M_COS ? (float)(dot_err + 3e-6) : (float)(dot_err + 1e-6 * (1.0 + qn_d * vn_d));
         eps = nextafterf(eps, __builtin_inff());             // the double -> float conversion may have rounded down
         const int64_t a_kp = approx[MIRROR_KP - 1], kth = sorted[a.k - 1];
         const float da = key_distance(a_kp), dk = key_distance(kth);
@@ -282,7 +243,7 @@ hipError_t launch_mirror_dims(const MirrorScanArgs& args, const float* query, in
 }  // namespace
 
 bool mirror_scan_supported(uint32_t dims, int metric) {
-    return (dims == 384 || dims == 768) && (metric == MM_COS || metric == MM_DOT);
+    return in_dim_list(MirrorDims{}, dims) && (metric == M_COS || metric == M_DOT);
 }
 
 int mirror_grid_for(uint32_t n_rows, uint32_t dims, int grid_cap) {
@@ -308,8 +269,11 @@ hipError_t launch_mirror_scan(const MirrorScanArgs& args, const float* query, in
     if (!mirror_scan_supported(args.dims, metric) || args.k < 1 || args.k > MIRROR_MAX_K || args.kpad < args.k || args.n_rows == 0)
         return hipErrorInvalidValue;
     const int grid = mirror_grid_for(args.n_rows, args.dims, grid_cap);
-    if (args.dims == 384) return metric == MM_COS ? launch_mirror_dims<384, MM_COS>(args, query, grid, st) : launch_mirror_dims<384, MM_DOT>(args, query, grid, st);
-    return metric == MM_COS ? launch_mirror_dims<768, MM_COS>(args, query, grid, st) : launch_mirror_dims<768, MM_DOT>(args, query, grid, st);
+    return with_scan_shape(MirrorDims{}, args.dims, [&](auto s) {
+        return with_metric_in<M_COS, M_DOT>(metric, [&](auto m) {
+            return launch_mirror_dims<decltype(s)::DIMS, decltype(m)::value>(args, query, grid, st);
+        }, hipErrorInvalidValue);
+    }, hipErrorInvalidValue);
 }
 
 }  // namespace wax

@@ -9,9 +9,9 @@
 // fetched, so the HBM traffic of the fallback is rows x dims x 4 bytes per GROUP of queries instead of per query.
 //
 // Bit-identity with the single-query path is the point (results must equal nq calls of wax_hip_search): a row's
-// distance is computed with scan_kernel's exact arithmetic — lane g of a GROUP-lane group owns float4s g, g + GROUP, ...,
-// one fma chain per component over j, hsum (x + y) + (z + w), the DPP tree of group_sum<GROUP>, finish_distance — so
-// (dims -> D4, GROUP) must mirror launch_scan's table. Only the loop order differs (queries inside rows).
+// distance is built from row_math.h's pieces at row_math.h's (dims -> GROUP) — lane g of a GROUP-lane group owns float4s
+// g, g + GROUP, ..., one fma chain per component over j, hsum, finish_distance — with the DPP tree of group_sum<GROUP>
+// replaced by a reduce-scatter that adds the same pairs (ms_halve). Only the loop order differs (queries inside rows).
 //
 // Layout per workgroup (4 waves, like scan_kernel):
 //   * the group's queries sit in LDS as float4 [nq][D4] (a lane re-reads its LOADS float4s per query: conflict-free
@@ -24,33 +24,12 @@
 // VALU budget: ~35 instructions per (query, row-group) against ~950 cycles of HBM time per row-group and SIMD at
 // 8 TB/s: about 12 queries ride on the stream for free, 16 cost ~1.3 passes — against 16 passes before.
 #include "kernels.h"
+#include "row_math.h"
 #include "topk.h"
 
 namespace wax {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) f32x4 lds_f32x4m;
-
-enum { MS_COS = WAX_HIP_METRIC_COSINE, MS_DOT = WAX_HIP_METRIC_DOT, MS_L2 = WAX_HIP_METRIC_L2 };
-
-// scan_kernel's arithmetic, restated verbatim (kernels.hip: finish_distance / accumulate / hsum) — any change there
-// must be made here too; tests/test_parity_gpu.py::test_multi_query_exact_scan_is_bit_identical pins the pair.
-template <int METRIC>
-__device__ inline float ms_finish(float acc, float nrm, float q_norm) {
-    float d;
-    if (METRIC == MS_COS) {
-        const float vn = sqrtf(nrm);
-        const float sim = (vn > 1e-6f && q_norm > 1e-6f) ? acc / (vn * q_norm) : 0.0f;
-        d = 1.0f - sim;
-    } else if (METRIC == MS_DOT) {
-        d = 1.0f - acc;
-    } else {
-        d = acc;
-    }
-    d = (d != d) ? __builtin_inff() : d;
-    return d + 0.0f;
-}
-__device__ inline float ms_hsum(const f32x4& a) { return (a.x + a.y) + (a.z + a.w); }
 
 // Per-(wave, query) selection state in LDS.
 struct MsState {
@@ -205,15 +184,15 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_multi_kernel(ScanMultiArgs 
     auto score_chunk = [&](const f32x4 (&v)[MS_U][LOADS], const uint32_t (&rr)[MS_U], uint32_t chunk) {
         const uint32_t rbase = chunk * RPC + sub;
         const uint32_t rr0 = rr[0], rr1 = rr[1], rr2 = rr[2], rr3 = rr[3];   // (named: see row_norm)
-        // ||v||^2 per row-group, scan_kernel's chain and reduction, then handed to every lane of the group
+        // ||v||^2 per row-group, the norm half of finish_row, then handed to every lane of the group
         // (four named scalars, not an array: a `b4 ? nb[1] : nb[0]` on an array is rewritten into a load from a lane-indexed
         // stack copy — scratch traffic in the hot loop)
         auto row_norm = [&](const f32x4 (&vu)[LOADS]) -> float {
-            if (METRIC != MS_COS) return 0.f;
+            if (METRIC != M_COS) return 0.f;
             f32x4 nrm = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int j = 0; j < LOADS; ++j) nrm = __builtin_elementwise_fma(vu[j], vu[j], nrm);
-            const float tot = group_sum<GROUP>(ms_hsum(nrm));                // valid in the group's last lane
+            for (int j = 0; j < LOADS; ++j) accumulate_norm(vu[j], nrm);
+            const float tot = group_sum<GROUP>(hsum(nrm));                   // valid in the group's last lane
             return __shfl(tot, last_of_group, 64);
         };
         const float nb0 = row_norm(v[0]), nb1 = row_norm(v[1]), nb2 = row_norm(v[2]), nb3 = row_norm(v[3]);
@@ -232,15 +211,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_multi_kernel(ScanMultiArgs 
             for (int u = 0; u < MS_U; ++u) {
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int j = 0; j < LOADS; ++j) {
-                    if (METRIC == MS_L2) {
-                        const f32x4 e = qa[j] - v[u][j];
-                        acc = __builtin_elementwise_fma(e, e, acc);
-                    } else {
-                        acc = __builtin_elementwise_fma(qa[j], v[u][j], acc);
-                    }
-                }
-                part[u * MS_NQ + qi] = ms_hsum(acc);
+                for (int j = 0; j < LOADS; ++j) accumulate_dot<METRIC>(qa[j], v[u][j], acc);
+                part[u * MS_NQ + qi] = hsum(acc);
             }
 #pragma unroll
             for (int j = 0; j < LOADS; ++j) qa[j] = qb[j];
@@ -261,7 +233,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_multi_kernel(ScanMultiArgs 
             if (GROUP == 16) { u = j; nrm = j == 0 ? nb0 : (j == 1 ? nb1 : (j == 2 ? nb2 : nb3)); row = j == 0 ? rr0 : (j == 1 ? rr1 : (j == 2 ? rr2 : rr3)); }
             else if (GROUP == 32) { u = b4 + 2 * j; nrm = j == 0 ? (b4 ? nb1 : nb0) : (b4 ? nb3 : nb2); row = j == 0 ? (b4 ? rr1 : rr0) : (b4 ? rr3 : rr2); }
             else { u = b4 + 2 * b5; nrm = b5 ? (b4 ? nb3 : nb2) : (b4 ? nb1 : nb0); row = b5 ? (b4 ? rr3 : rr2) : (b4 ? rr1 : rr0); }
-            const float d = ms_finish<METRIC>(part[j], nrm, qn_lane);
+            const float d = finish_distance<METRIC>(part[j], nrm, qn_lane);
             const uint32_t r = rbase + (uint32_t)u * RPW;
             const int64_t key = make_key(d, a.row_base + (LISTED ? row : r));
             const bool pass = q_live && (r < n) && (key < tau_lane);
@@ -331,27 +303,18 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_multi_kernel(ScanMultiArgs 
 }
 
 // ---------------------------------------------------------------------------
-// launch table: must mirror launch_scan's (dims -> D4, GROUP).
+// launch side: every specialised dimension of row_math.h's table
 
 size_t scan_multi_lds_bytes(uint32_t dims, int cap) {
     return (size_t)MS_NQ * dims * 4 + (size_t)SCAN_WAVES * MS_NQ * cap * 8 + (size_t)SCAN_WAVES * MS_NQ * sizeof(MsState) + (size_t)MS_NQ * 4 +
            (size_t)MS_NQ * SCAN_WAVES * 4 + 16;
 }
 
-static int ms_group_lanes(uint32_t dims) {
-    switch (dims) {
-        case 64: return 16;
-        case 128: case 384: return 32;
-        case 256: case 512: case 768: case 1024: case 1536: return 64;
-        default: return 0;
-    }
-}
-
-bool scan_multi_dims(uint32_t dims) { return ms_group_lanes(dims) != 0; }
+bool scan_multi_dims(uint32_t dims) { return scan_group_lanes(dims) != 0; }
 
 // A push offers at most 4 candidates to one list (the 4 lanes that share a query), so CAP >= k + 4.
 int scan_multi_cap(uint32_t dims, int k) {
-    if (ms_group_lanes(dims) == 0 || k < 1 || k > FUSED_MAX_K) return 0;
+    if (scan_group_lanes(dims) == 0 || k < 1 || k > FUSED_MAX_K) return 0;
     return (k + 4 <= 64) ? 64 : 256;
 }
 
@@ -364,7 +327,7 @@ uint32_t scan_multi_group(uint32_t dims, int k) {
 }
 
 // rows a wave consumes per chunk (MS_U row-groups)
-static int ms_rows_per_chunk(uint32_t dims) { return (WAVE / ms_group_lanes(dims)) * MS_U; }
+static int ms_rows_per_chunk(uint32_t dims) { return (WAVE / scan_group_lanes(dims)) * MS_U; }
 
 int scan_multi_grid(uint32_t n_rows, uint32_t dims, int grid_cap) {
     if (grid_cap <= 0) grid_cap = 512;
@@ -393,32 +356,16 @@ static hipError_t ms_launch_one(const ScanMultiArgs& a, int grid, size_t smem, h
     return hipGetLastError();
 }
 
-template <int D4, int GROUP, bool LISTED>
-static hipError_t ms_launch(const ScanMultiArgs& a, int metric, int cap, int grid, size_t smem, hipStream_t st) {
-    switch (metric * 2 + (cap == 64 ? 0 : 1)) {
-        case MS_COS * 2: return ms_launch_one<D4, GROUP, MS_COS, 64, LISTED>(a, grid, smem, st);
-        case MS_COS * 2 + 1: return ms_launch_one<D4, GROUP, MS_COS, 256, LISTED>(a, grid, smem, st);
-        case MS_DOT * 2: return ms_launch_one<D4, GROUP, MS_DOT, 64, LISTED>(a, grid, smem, st);
-        case MS_DOT * 2 + 1: return ms_launch_one<D4, GROUP, MS_DOT, 256, LISTED>(a, grid, smem, st);
-        case MS_L2 * 2: return ms_launch_one<D4, GROUP, MS_L2, 64, LISTED>(a, grid, smem, st);
-        case MS_L2 * 2 + 1: return ms_launch_one<D4, GROUP, MS_L2, 256, LISTED>(a, grid, smem, st);
-        default: return hipErrorInvalidValue;
-    }
-}
-
 template <bool LISTED>
 static hipError_t ms_dispatch(const ScanMultiArgs& a, int metric, int cap, int grid, size_t smem, hipStream_t st) {
-    switch (a.dims) {   // (D4, GROUP) = launch_scan's table
-        case 64: return ms_launch<16, 16, LISTED>(a, metric, cap, grid, smem, st);
-        case 128: return ms_launch<32, 32, LISTED>(a, metric, cap, grid, smem, st);
-        case 256: return ms_launch<64, 64, LISTED>(a, metric, cap, grid, smem, st);
-        case 384: return ms_launch<96, 32, LISTED>(a, metric, cap, grid, smem, st);
-        case 512: return ms_launch<128, 64, LISTED>(a, metric, cap, grid, smem, st);
-        case 768: return ms_launch<192, 64, LISTED>(a, metric, cap, grid, smem, st);
-        case 1024: return ms_launch<256, 64, LISTED>(a, metric, cap, grid, smem, st);
-        case 1536: return ms_launch<384, 64, LISTED>(a, metric, cap, grid, smem, st);
-        default: return hipErrorInvalidValue;
-    }
+    return with_scan_shape(a.dims, [&](auto s) {
+        using S = decltype(s);
+        return with_metric(metric, [&](auto m) {
+            constexpr int METRIC = decltype(m)::value;
+            return cap == 64 ? ms_launch_one<S::D4, S::GROUP, METRIC, 64, LISTED>(a, grid, smem, st)
+                             : ms_launch_one<S::D4, S::GROUP, METRIC, 256, LISTED>(a, grid, smem, st);
+        }, hipErrorInvalidValue);
+    }, hipErrorInvalidValue);
 }
 
 hipError_t launch_scan_multi(const ScanMultiArgs& a, int metric, int grid_cap, hipStream_t st, int* out_grid) {
@@ -432,7 +379,7 @@ hipError_t launch_scan_multi(const ScanMultiArgs& a, int metric, int grid_cap, h
 }
 
 uint32_t scan_multi_listed_items(uint64_t max_rows, uint32_t dims, int grid_cap) {
-    if (ms_group_lanes(dims) == 0 || max_rows == 0) return 1;
+    if (scan_group_lanes(dims) == 0 || max_rows == 0) return 1;
     // ~8 chunks per wave: few enough workgroups that the per-workgroup query load and list merge stay small beside the rows
     const uint64_t per_wg = (uint64_t)ms_rows_per_chunk(dims) * SCAN_WAVES * 8;
     uint64_t w = (max_rows + per_wg - 1) / per_wg;
