@@ -381,6 +381,13 @@ int wax_hip_stats(wax_hip_engine* e, wax_hip_stats_t* out);
  *   arithmetic and release the answer only under the mirror's certificate — otherwise collect re-runs the query on the f32 scan; 2 = every
  *   such store; 0 = never), "mirror_scans" / "mirror_scan_fallbacks" / "mirror_scan_unavailable" (read-only: single queries that took the
  *   mirror / whose certificate failed and were re-run on the f32 scan / that took the f32 scan because the mirror could not be prepared),
+ *   "mirror_share" (single queries in flight share passes over the mirror, up to 4 per pass, each answered exactly as it would be alone:
+ *   1 (default) = a query submitted while a mirror pass of this engine is still running is parked — the ticket is returned, nothing is
+ *   launched — and launched together with whatever else is parked when four are parked, when a collect is about to block, or by a submit
+ *   that finds no pass running; a lone query launches at once; 2 = always parked until a collect needs the answer or four are parked;
+ *   0 = never, one pass per query. Nothing is parked while "time_kernels" != 0 or scans are chained), "mirror_passes" /
+ *   "mirror_shared_passes" / "mirror_shared_queries" (read-only: scan launches over the mirror / of which with two or more queries /
+ *   queries those answered; "mirror_scans" keeps counting queries),
  *   "filter_device_min" (wax_hip_search_filtered: allow-lists at least this long are resolved by the id -> row table in HBM, default 4096; -1 = never),
  *   "filter_batch" (wax_hip_search_batch_filtered: 1 (default) = one gather pass for all allow-lists; 0 = the single-query filtered path
  *   per query), "filter_batch_queries" / "filter_batch_fallbacks" (read-only: listed queries answered by the gather pass / by the

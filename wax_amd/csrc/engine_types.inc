@@ -212,6 +212,11 @@ struct Slot {
     bool timed = false;
     bool mirror = false;           // answered by the mirror scan: collect reads the certificate word and re-runs the f32 scan if it failed
     float q_norm = 0.f;            // (mirror) the query's norm; the query itself is in h_query
+    // "mirror_share": this ticket was parked at submit (its query waits in h_query for a pass it can share). `shared` is written before
+    // the ticket is published and tells collect to look under the engine's share_mu; the other two are guarded by that mutex.
+    bool shared = false;
+    int park_rc = 0;               // what launching it returned (a failed launch surfaces at the ticket's collect)
+    std::string park_err;
     std::thread::id owner;         // the submitting thread (its outstanding-ticket count drops at collect, whoever collects)
 };
 
@@ -494,6 +499,16 @@ struct wax_hip_engine {
     std::atomic<uint64_t> st_query_args{0};          // single-query scans that took their query through the kernel arguments
     std::atomic<int64_t> scan_mirror{1};     // single queries on the bf16 mirror + f32 re-score + certificate: 1 (default) = stores of > SCAN_KWAY_MAX_BYTES of rows, 2 = always, 0 = never
     std::atomic<uint64_t> st_mirror_scans{0}, st_mirror_fallbacks{0}, st_mirror_unavailable{0};
+    // Single queries in flight share passes over the mirror ("mirror_share": 0 = never, 1 (default) = a query submitted while a mirror
+    // pass of this engine is still running is parked and launched with the others parked by then, 2 = always parked until a collect
+    // needs the answer or the group is full). Any thread may launch what another parked: the parked set, and every launch of a
+    // mirror pass that looks at it, is behind share_mu.
+    std::atomic<int64_t> mirror_share{1};
+    std::mutex share_mu;
+    std::vector<Slot*> parked;               // submit order; at most MIRROR_MAX_NQ - 1 between two calls
+    std::atomic<int> n_parked{0};            // parked.size(), readable without the mutex
+    hipEvent_t share_last = nullptr;         // ev_done of the last mirror pass launched (a slot's event: not owned); not ready = a pass in flight
+    std::atomic<uint64_t> st_mirror_passes{0}, st_mirror_shared_passes{0}, st_mirror_shared_queries{0};
     // wax_hip_search_batch_submit_device tickets (guarded by bticket_mu)
     struct BatchTicket {
         BatchCtx* c = nullptr;           // null: the batch was answered at submit time (empty engine / loop path)

@@ -135,6 +135,26 @@ int mirror_grid_for(uint32_t n_rows, uint32_t dims, int grid_cap);
 // Two launches on `st`: mirror_scan_kernel (the event pair of launch_timing(), if armed, binds to it) and mirror_finish_kernel.
 hipError_t launch_mirror_scan(const MirrorScanArgs& args, const float* query, int metric, int grid_cap, hipStream_t st);
 
+// Several single queries in ONE pass over the mirror ("mirror_share"): every loaded dword is widened once and multiplied
+// into one accumulator set per query, with the single-query kernel's operations in its order, so a query's candidates and its
+// certificate do not depend on what it rode with. The queries are read from device memory (they no longer fit the kernel arguments);
+// everything a query owns — partial lists, hits, certificate word, norm, k — is per member.
+constexpr int MIRROR_MAX_NQ = 4;    // queries per shared pass (2, 3 and 4 have their own instantiations)
+struct MirrorMember {
+    const float* query;             // [dims] f32 in HBM
+    int64_t* partials;              // [grid][MIRROR_KP]
+    wax_hip_hit* hits;              // [kpad] (pinned host memory)
+    uint32_t* certified;            // (pinned host memory)
+    float q_norm;
+    int32_t k, kpad;
+};
+struct MirrorGroupArgs {
+    MirrorScanArgs a;               // what the members share: mirror, store, ids, max_bits, n_rows, row_base, dims, lists, use_measured
+    MirrorMember m[MIRROR_MAX_NQ];
+};
+// Two launches on `st`: the NQ-query scan and a finish launch of NQ workgroups (one per query). 2 <= nq <= MIRROR_MAX_NQ.
+hipError_t launch_mirror_group(const MirrorGroupArgs& args, int nq, int metric, int grid_cap, hipStream_t st);
+
 struct ScanVariantInfo {
     int unroll;          // row groups in flight per wave iteration
     int nt;              // 1 = non-temporal (streaming) loads

@@ -130,101 +130,132 @@ __global__ __launch_bounds__(SCAN_THREADS) void mirror_scan_kernel(MirrorScanArg
 
 template <int DIMS, int METRIC>
 __global__ __launch_bounds__(SCAN_THREADS) void mirror_finish_kernel(MirrorScanArgsQ<DIMS> aq) {
-    constexpr int D4 = ScanShape<DIMS>::D4;
-    constexpr int GROUP = ScanShape<DIMS>::GROUP;
-    constexpr int LOADS = ScanShape<DIMS>::LOADS;
-    constexpr int RPW = WAVE / GROUP;
-    constexpr int ROWS_PER_PASS = RPW * SCAN_WAVES;
-    constexpr int PASSES = MIRROR_KP / ROWS_PER_PASS;
-    static_assert(MIRROR_KP % ROWS_PER_PASS == 0, "whole passes");
     const MirrorScanArgs& a = aq.a;
-    __shared__ int64_t approx[MIRROR_KP], exact[MIRROR_KP], sorted[MIRROR_KP], xch[2 * SCAN_WAVES];
-    const int t = (int)threadIdx.x;
+#define MIRROR_FINISH_QUERY reinterpret_cast<const f32x4*>((const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(MirrorScanArgsQ<DIMS>, q))
+#include "mirror_finish_body.inc"
+#undef MIRROR_FINISH_QUERY
+}
+
+// ---- several queries per pass ----------------------------------------------------------------------------------------------------
+// mirror_scan_kernel with NQ accumulator sets: the row loads, the clamp and the widening are shared, everything from the first fma to
+// the workgroup's list is per query and is the single-query kernel's code (four f32x2 chains, the (acc0+acc1)+(acc2+acc3) tree,
+// group_sum, 1 - s * inv_qn), so a member's approximate keys are the ones it would get alone.
+template <int DIMS, int METRIC, int NQ>
+__global__ __launch_bounds__(SCAN_THREADS) void mirror_scan_group_kernel(MirrorGroupArgs g) {
+    constexpr int D8 = MirrorShape<DIMS>::D8;
+    constexpr int GROUP = MirrorShape<DIMS>::GROUP;
+    constexpr int LOADS = D8 / GROUP;
+    constexpr int RPW = WAVE / GROUP;
+    constexpr int RPC = RPW * MIRROR_UNROLL;
+    constexpr int CAP = 128;
+    constexpr int PER_Q = SCAN_WAVES * CAP + SCAN_WAVES + MIRROR_KP;
+    static_assert(LOADS == 3 && D8 % GROUP == 0, "three dwordx4 per lane and row");
+    static_assert(NQ >= 2 && NQ <= MIRROR_MAX_NQ, "queries per pass");
+    const MirrorScanArgs& a = g.a;
+    __shared__ int64_t lds[NQ * PER_Q];
+
     const int lane = lane_id();
-    const int wave = t >> 6;
+    const int wave = (int)(threadIdx.x >> 6);
+    const int sub = lane / GROUP;
+    const int gl = lane % GROUP;
+    const bool owner = (gl == GROUP - 1);
+    const uint32_t n = a.n_rows;
 
-    // (1) the MIRROR_KP best approximate keys of the whole store
-    if (a.lists <= SCAN_THREADS) kway_merge<1>(a.partials, a.lists, MIRROR_KP, approx, xch);
-    else kway_merge<2>(a.partials, a.lists, MIRROR_KP, approx, xch);
-
-    // (2) exact f32 re-score of those rows: row_distance (row_math.h) at the f32 scan's shape for this dimension
-    const char* ka = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
-    const f32x4* q4 = reinterpret_cast<const f32x4*>(ka + offsetof(MirrorScanArgsQ<DIMS>, q));
-    const int sub = lane / GROUP, gl = lane % GROUP;
-    f32x4 q[LOADS];
+    f32x2 q[NQ][LOADS][4];
+    float inv_qn[NQ];
+    WaveTopK<CAP> tk[NQ];
 #pragma unroll
-    for (int j = 0; j < LOADS; ++j) q[j] = q4[gl + j * GROUP];
-    const f32x4* __restrict__ store4 = reinterpret_cast<const f32x4*>(a.store);
-    f32x4 v[PASSES][LOADS];
-    bool live[PASSES];
-    uint32_t grow[PASSES];
+    for (int i = 0; i < NQ; ++i) {
+        const f32x4* q4 = reinterpret_cast<const f32x4*>(g.m[i].query);
 #pragma unroll
-    for (int p = 0; p < PASSES; ++p) {   // every load of the wave in flight before the first product
-        const int i = p * ROWS_PER_PASS + wave * RPW + sub;
-        const int64_t key = approx[i];
-        grow[p] = key_row(key);
-        const uint32_t lrow = grow[p] - a.row_base;
-        live[p] = key != KEY_PAD && lrow < a.n_rows;
-        const f32x4* src = store4 + (size_t)(live[p] ? lrow : 0u) * D4 + gl;
-#pragma unroll
-        for (int j = 0; j < LOADS; ++j) v[p][j] = src[j * GROUP];
+        for (int j = 0; j < LOADS; ++j) {
+            const f32x4 lo = q4[2 * (gl + j * GROUP)], hi = q4[2 * (gl + j * GROUP) + 1];
+            q[i][j][0] = lo.xy; q[i][j][1] = lo.zw; q[i][j][2] = hi.xy; q[i][j][3] = hi.zw;
+        }
+        inv_qn[i] = g.m[i].q_norm > COS_NORM_FLOOR ? 1.0f / g.m[i].q_norm : 0.0f;
+        tk[i].init(lds + i * PER_Q + wave * CAP, MIRROR_KP);
     }
+
+    const u32x4* __restrict__ mirror4 = reinterpret_cast<const u32x4*>(a.mirror);
+    const uint32_t nchunks = (n + RPC - 1) / RPC;
+    const uint32_t gwave = blockIdx.x * SCAN_WAVES + wave;
+    const uint32_t nwaves = gridDim.x * SCAN_WAVES;
+
+    for (uint32_t chunk = gwave; chunk < nchunks; chunk += nwaves) {
+        const uint32_t rbase = chunk * RPC + sub;
 #pragma unroll
-    for (int p = 0; p < PASSES; ++p) {
-        const float d = row_distance<GROUP, LOADS, METRIC>(q, v[p], a.q_norm);
-        if (gl == GROUP - 1) exact[p * ROWS_PER_PASS + wave * RPW + sub] = live[p] ? make_key(d, grow[p]) : KEY_PAD;
+        for (int i = 0; i < NQ; ++i) tk[i].make_room(RPC);
+        u32x4 v[MIRROR_UNROLL][LOADS];
+#pragma unroll
+        for (int u = 0; u < MIRROR_UNROLL; ++u) {
+            const uint32_t r = rbase + u * RPW;
+            const uint32_t rc = r < n ? r : n - 1;  // clamp: tail lanes re-read the last row, result discarded
+            const u32x4* p = mirror4 + (size_t)rc * D8 + gl;
+#pragma unroll
+            for (int j = 0; j < LOADS; ++j) v[u][j] = __builtin_nontemporal_load(p + j * GROUP);
+        }
+#pragma unroll
+        for (int u = 0; u < MIRROR_UNROLL; ++u) {
+            f32x2 w[LOADS][4];              // widened once, used by every query
+#pragma unroll
+            for (int j = 0; j < LOADS; ++j) {
+                w[j][0] = widen(v[u][j].x); w[j][1] = widen(v[u][j].y); w[j][2] = widen(v[u][j].z); w[j][3] = widen(v[u][j].w);
+            }
+            const uint32_t r = rbase + u * RPW;
+#pragma unroll
+            for (int i = 0; i < NQ; ++i) {
+                f32x2 acc[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+#pragma unroll
+                for (int j = 0; j < LOADS; ++j) {
+                    acc[0] = __builtin_elementwise_fma(q[i][j][0], w[j][0], acc[0]);
+                    acc[1] = __builtin_elementwise_fma(q[i][j][1], w[j][1], acc[1]);
+                    acc[2] = __builtin_elementwise_fma(q[i][j][2], w[j][2], acc[2]);
+                    acc[3] = __builtin_elementwise_fma(q[i][j][3], w[j][3], acc[3]);
+                }
+                const f32x2 s2 = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+                const float s = group_sum<GROUP>(s2.x + s2.y);
+                float d = METRIC == M_COS ? 1.0f - s * inv_qn[i] : 1.0f - s;
+                d = (d != d) ? __builtin_inff() : d;
+                tk[i].push(make_key(d + 0.0f, a.row_base + r), owner && (r < n));
+            }
+        }
+    }
+
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+        tk[i].finalize();
+        int* counts = reinterpret_cast<int*>(lds + i * PER_Q + SCAN_WAVES * CAP);
+        if (lane == 0) counts[wave] = tk[i].cnt;
     }
     __syncthreads();
-
-    // (3) rank sort of the exact keys (unique rows; KEY_PAD ties broken by position)
-    if (t < MIRROR_KP) {
-        const int64_t key = exact[t];
-        int rank = 0;
-        for (int j = 0; j < MIRROR_KP; ++j) {
-            const int64_t o = exact[j];
-            rank += (o < key || (o == key && j < t)) ? 1 : 0;
-        }
-        sorted[rank] = key;
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+        int64_t* base = lds + i * PER_Q;
+        block_rank_merge<SCAN_WAVES>(base, CAP, reinterpret_cast<int*>(base + SCAN_WAVES * CAP), MIRROR_KP, base + SCAN_WAVES * CAP + SCAN_WAVES);
     }
     __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+        const int64_t* fin = lds + i * PER_Q + SCAN_WAVES * CAP + SCAN_WAVES;
+        int64_t* mine = g.m[i].partials + (size_t)blockIdx.x * MIRROR_KP;
+        for (int t = (int)threadIdx.x; t < MIRROR_KP; t += SCAN_THREADS) mine[t] = fin[t];
+    }
+}
 
-    // (4) the k best with frame ids; (5) the certificate
-    for (int i = t; i < a.kpad; i += SCAN_THREADS) {
-        wax_hip_hit h;
-        h.key = (i < a.k) ? sorted[i] : KEY_PAD;
-        h.frame_id = ID_PAD;
-        if (h.key != KEY_PAD) {
-            const uint32_t local = key_row(h.key) - a.row_base;
-            h.frame_id = (a.ids != nullptr && local < a.n_rows) ? a.ids[local] : (uint64_t)key_row(h.key);
-        }
-        a.hits[i] = h;
-    }
-    if (t == 0) {
-        // eps: batch_prep_kernel's bound (batch.hip) with the query-side rounding term gone — the query is not rounded. With x_v the
-        // f32 row that was rounded (normalised for cosine) and v~ its bf16 rounding, |q.v~ - q.x_v| <= ||q|| ||v~ - x_v||, bounded by
-        // ||q|| max_rows ||v~ - x_v|| (measured when the mirror was converted, + 0.1 % for its f32 accumulation); the f32 sums on
-        // either side and the normalisations stay inside 3 D 2^-24 of ||q|| max||v||; the exact distance carries ~1e-6 of its own.
-        // Without a measurement: the worst case of one rounded operand is below the batched path's two-operand constant, kept as is.
-        // Cosine divides by ||q||, so both norms are 1 there.
-        const unsigned int* mb = a.max_bits;
-        const float max_norm = __uint_as_float(mb[0]);
-        const float max_row_err = a.use_measured ? __uint_as_float(mb[1]) : 0.f;
-        const double qn_d = METRIC == M_COS ? 1.0 + 1e-6 : (double)a.q_norm;
-        const double vn_d = METRIC == M_COS ? 1.0 + 1e-6 : (double)max_norm;
-        const double u = 0.0078125 * (1.0 + 1.0 / 512.0) + (double)DIMS * 5.97e-8 + 1e-6;
-        double dot_err = u * qn_d * vn_d * 1.001;
-        if (max_row_err > 0.f) {
-            const double measured = qn_d * (double)max_row_err * 1.001 + 3.0 * (double)DIMS * 5.97e-8 * qn_d * vn_d;
-            if (measured < dot_err) dot_err = measured;
-        }
-        float eps = METRIC == M_COS ? (float)(dot_err + 3e-6) : (float)(dot_err + 1e-6 * (1.0 + qn_d * vn_d));
-        eps = nextafterf(eps, __builtin_inff());             // the double -> float conversion may have rounded down
-        const int64_t a_kp = approx[MIRROR_KP - 1], kth = sorted[a.k - 1];
-        const float da = key_distance(a_kp), dk = key_distance(kth);
-        const bool ok = a_kp != KEY_PAD && kth != KEY_PAD && __builtin_isfinite(da) && __builtin_isfinite(dk) &&
-                        __builtin_isfinite(eps) && a.q_norm == a.q_norm && (da - eps > dk);   // strict: ties stay uncertified
-        *a.certified = ok ? 1u : 0u;
-    }
+// one workgroup per member: the single-query finish with the member's own lists, hits, certificate word, norm and k
+template <int DIMS, int METRIC>
+__global__ __launch_bounds__(SCAN_THREADS) void mirror_finish_group_kernel(MirrorGroupArgs g) {
+    const MirrorMember& m = g.m[blockIdx.x];
+    MirrorScanArgs a = g.a;
+    a.partials = m.partials;
+    a.hits = m.hits;
+    a.certified = m.certified;
+    a.q_norm = m.q_norm;
+    a.k = m.k;
+    a.kpad = m.kpad;
+#define MIRROR_FINISH_QUERY reinterpret_cast<const f32x4*>(m.query)
+#include "mirror_finish_body.inc"
+#undef MIRROR_FINISH_QUERY
 }
 
 namespace {
@@ -238,6 +269,21 @@ hipError_t launch_mirror_dims(const MirrorScanArgs& args, const float* query, in
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
     hipLaunchKernelGGL((mirror_finish_kernel<DIMS, METRIC>), dim3(1), dim3(SCAN_THREADS), 0, st, aq);
+    return hipGetLastError();
+}
+template <int DIMS, int METRIC>
+hipError_t launch_group_dims(const MirrorGroupArgs& args, int nq, int grid, hipStream_t st) {
+    MirrorGroupArgs g = args;
+    g.a.lists = grid;
+    switch (nq) {
+        case 2: launch_kernel((mirror_scan_group_kernel<DIMS, METRIC, 2>), dim3(grid), dim3(SCAN_THREADS), 0, st, g); break;
+        case 3: launch_kernel((mirror_scan_group_kernel<DIMS, METRIC, 3>), dim3(grid), dim3(SCAN_THREADS), 0, st, g); break;
+        case 4: launch_kernel((mirror_scan_group_kernel<DIMS, METRIC, 4>), dim3(grid), dim3(SCAN_THREADS), 0, st, g); break;
+        default: return hipErrorInvalidValue;
+    }
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL((mirror_finish_group_kernel<DIMS, METRIC>), dim3(nq), dim3(SCAN_THREADS), 0, st, g);
     return hipGetLastError();
 }
 }  // namespace
@@ -272,6 +318,18 @@ hipError_t launch_mirror_scan(const MirrorScanArgs& args, const float* query, in
     return with_scan_shape(MirrorDims{}, args.dims, [&](auto s) {
         return with_metric_in<M_COS, M_DOT>(metric, [&](auto m) {
             return launch_mirror_dims<decltype(s)::DIMS, decltype(m)::value>(args, query, grid, st);
+        }, hipErrorInvalidValue);
+    }, hipErrorInvalidValue);
+}
+
+hipError_t launch_mirror_group(const MirrorGroupArgs& args, int nq, int metric, int grid_cap, hipStream_t st) {
+    if (!mirror_scan_supported(args.a.dims, metric) || nq < 2 || nq > MIRROR_MAX_NQ || args.a.n_rows == 0) return hipErrorInvalidValue;
+    for (int i = 0; i < nq; ++i)
+        if (args.m[i].k < 1 || args.m[i].k > MIRROR_MAX_K || args.m[i].kpad < args.m[i].k || args.m[i].query == nullptr) return hipErrorInvalidValue;
+    const int grid = mirror_grid_for(args.a.n_rows, args.a.dims, grid_cap);
+    return with_scan_shape(MirrorDims{}, args.a.dims, [&](auto s) {
+        return with_metric_in<M_COS, M_DOT>(metric, [&](auto m) {
+            return launch_group_dims<decltype(s)::DIMS, decltype(m)::value>(args, nq, grid, st);
         }, hipErrorInvalidValue);
     }, hipErrorInvalidValue);
 }

@@ -269,7 +269,7 @@ int enqueue_mirror_scan(wax_hip_engine* e, Slot* s, const float* query, float q_
             return WAX_HIP_OK;
         }
     }
-    std::memcpy(s->h_query, query, (size_t)e->dims * sizeof(float));   // for the f32 re-run at collect, if the certificate fails
+    if (query != s->h_query) std::memcpy(s->h_query, query, (size_t)e->dims * sizeof(float));   // for the f32 re-run at collect, if the certificate fails (a parked query is there already)
     s->q_norm = q_norm;
     MirrorScanArgs m{};
     m.mirror = b.d_cb;
@@ -311,8 +311,120 @@ int enqueue_mirror_scan(wax_hip_engine* e, Slot* s, const float* query, float q_
     *took = true;
     s->mirror = true;
     e->st_mirror_scans++;
+    e->st_mirror_passes++;
     e->st_searches++;
     e->st_rows += e->count;
     e->st_bytes += e->count * (uint64_t)e->dims * 2ull + (uint64_t)MIRROR_KP * e->dims * 4ull;
     return WAX_HIP_OK;
+}
+
+// ---- single queries in flight share a pass over the mirror ("mirror_share"; DESIGN 4.1) ----------------------------------------
+// A parked ticket holds its slot, the read lock and its query (the slot's pinned h_query) like every ticket; what it lacks is a launch.
+// Everything below runs under e->share_mu, on whichever thread got there first.
+
+// May this submit be parked or share a pass? Not while kernels are timed or scans are chained: calibration passes stay one kernel
+// per query.
+static int64_t mirror_share_mode(wax_hip_engine* e, int tk_mode) {
+    if (tk_mode != 0 || chain_scans(e, tk_mode)) return 0;
+    return e->mirror_share.load();
+}
+
+// the f32 scan of a parked query on its own slot and stream (the mirror could not be prepared)
+static int parked_take_f32(wax_hip_engine* e, Slot* s) {
+    s->mirror = false;
+    const int rc = enqueue_scan(e, nullptr, s->q_norm, s->k_eff, s->k_eff, s->d_partials, s, s->h_hits, s->stream, nullptr, nullptr,
+                                /*chain=*/false, nullptr, nullptr, s->h_query);
+    if (rc != WAX_HIP_OK) return rc;
+    HIP_TRY(hipEventRecord(s->ev_done, s->stream), WAX_HIP_ERR_INTERNAL, "event record");
+    return WAX_HIP_OK;
+}
+
+// One pass for `nq` >= 2 parked queries on the first one's stream: query uploads, the group scan, one finish workgroup per member,
+// and every member's ev_done behind the finish launch.
+static int enqueue_mirror_group(wax_hip_engine* e, Slot* const* grp, int nq, bool* took) {
+    *took = false;
+    BatchMirror& b = e->batch;
+    hipStream_t st = grp[0]->stream;
+    {
+        const std::string keep = g_last_error;
+        if (ensure_mirror(e, st) != WAX_HIP_OK || b.d_cb == nullptr || b.d_maxnorm == nullptr) {
+            (void)hipGetLastError();
+            g_last_error = keep;
+            e->st_mirror_unavailable += (uint64_t)nq;
+            return WAX_HIP_OK;
+        }
+    }
+    MirrorGroupArgs g{};
+    g.a.mirror = b.d_cb;
+    g.a.store = e->d_store;
+    g.a.ids = e->d_ids;
+    g.a.max_bits = b.d_maxnorm;
+    g.a.n_rows = (uint32_t)e->count;
+    g.a.row_base = (uint32_t)e->row_base;
+    g.a.dims = e->dims;
+    g.a.use_measured = e->batch_eps_measured.load() != 0 ? 1 : 0;
+    for (int i = 0; i < nq; ++i) {
+        Slot* s = grp[i];
+        HIP_TRY(hipMemcpyAsync(s->d_query, s->h_query, (size_t)e->dims * sizeof(float), hipMemcpyHostToDevice, st), WAX_HIP_ERR_INTERNAL, "query upload");
+        g.m[i].query = s->d_query;
+        g.m[i].partials = s->d_partials;
+        g.m[i].hits = s->h_hits;
+        g.m[i].certified = slot_cert_word(s->h_done);
+        g.m[i].q_norm = s->q_norm;
+        g.m[i].k = s->k_eff;
+        g.m[i].kpad = s->k_eff;
+        s->t_start = nullptr;
+        s->t_end = nullptr;
+    }
+    HIP_TRY(launch_mirror_group(g, nq, e->metric, (int)e->grid_blocks.load(), st), WAX_HIP_ERR_INTERNAL, "mirror group launch");
+    for (int i = 0; i < nq; ++i) {
+        HIP_TRY(hipEventRecord(grp[i]->ev_done, st), WAX_HIP_ERR_INTERNAL, "event record");
+        grp[i]->mirror = true;
+    }
+    *took = true;
+    e->st_mirror_scans += (uint64_t)nq;
+    e->st_mirror_passes++;
+    e->st_mirror_shared_passes++;
+    e->st_mirror_shared_queries += (uint64_t)nq;
+    e->st_searches += (uint64_t)nq;
+    e->st_rows += e->count * (uint64_t)nq;
+    e->st_bytes += e->count * (uint64_t)e->dims * 2ull + (uint64_t)nq * MIRROR_KP * e->dims * 4ull;
+    return WAX_HIP_OK;
+}
+
+// Launch whatever is parked (share_mu held). A launch that fails is reported by the collect of every ticket it carried.
+static void launch_parked(wax_hip_engine* e) {
+    std::vector<Slot*> grp;
+    grp.swap(e->parked);
+    e->n_parked.store(0);
+    if (grp.empty()) return;
+    const int nq = (int)grp.size();
+    bool took = false;
+    int rc;
+    if (nq == 1) rc = enqueue_mirror_scan(e, grp[0], grp[0]->h_query, grp[0]->q_norm, grp[0]->k_eff, 0, &took);   // alone after all: the lone query's kernels
+    else rc = enqueue_mirror_group(e, grp.data(), nq, &took);
+    if (rc == WAX_HIP_OK && took) {
+        if (nq == 1) {
+            const hipError_t err = hipEventRecord(grp[0]->ev_done, grp[0]->stream);
+            if (err != hipSuccess) rc = fail(WAX_HIP_ERR_INTERNAL, std::string("event record: ") + hipGetErrorString(err));
+        }
+        if (rc == WAX_HIP_OK) e->share_last = grp[0]->ev_done;
+    } else if (rc == WAX_HIP_OK) {
+        for (Slot* s : grp) {             // no mirror: every member takes the f32 scan on its own stream
+            const int frc = parked_take_f32(e, s);
+            if (frc != WAX_HIP_OK) { s->park_rc = frc; s->park_err = g_last_error; }
+        }
+    }
+    if (rc != WAX_HIP_OK) {
+        const std::string keep = g_last_error;
+        (void)hipStreamSynchronize(grp[0]->stream);   // nothing of a half-enqueued group still runs when its tickets report the error
+        (void)hipGetLastError();
+        g_last_error = keep;
+        for (Slot* s : grp) { s->park_rc = rc; s->park_err = keep; }
+    }
+}
+
+// is a mirror pass of this engine still running? (share_mu held)
+static bool mirror_pass_in_flight(wax_hip_engine* e) {
+    return e->share_last != nullptr && hipEventQuery(e->share_last) == hipErrorNotReady;
 }
