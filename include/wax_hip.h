@@ -335,6 +335,51 @@ int wax_hip_search_batch_filtered(wax_hip_engine* e, const float* queries, uint3
                                   const float* min_scores,
                                   uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts);
 
+/* ---- per-row attributes and the predicate search ------------------------------------------------------------ *
+ * passesFrameFilter (UnifiedSearch.swift:1241-1258) also drops vector-lane candidates by per-frame metadata: request.timeRange
+ * against FrameMeta.timestamp (TimeRange.contains, SearchRequest.swift:91-105), status == .deleted, supersededBy != nil and
+ * kind == "surrogate" — the last three excluded by the default FrameFilter(). Two optional per-row columns carry that metadata
+ * beside the store: int64 timestamp and uint32 flags. A store on which they were never set behaves as if every row were (0, 0)
+ * and allocates nothing for them. An appended row gets (0, 0); an upsert keeps its row's attributes; removals take the row's
+ * entry with them; reserve and growth keep them; wax_hip_deserialize drops them all (MV2V has no field for them, and
+ * wax_hip_serialize is unchanged). The host holds the authoritative copy; the device mirror is brought up to date by the first
+ * predicate search after a change (appended rows only, or everything from the lowest changed row). */
+#define WAX_HIP_FLAG_DELETED    0x1u   /* FrameMeta.status == .deleted (UnifiedSearch.swift:1249) */
+#define WAX_HIP_FLAG_SUPERSEDED 0x2u   /* FrameMeta.supersededBy != nil (UnifiedSearch.swift:1250) */
+#define WAX_HIP_FLAG_SURROGATE  0x4u   /* FrameMeta.kind == "surrogate" (UnifiedSearch.swift:1251-1254) */
+#define WAX_HIP_FLAG_USER_SHIFT 8      /* bits 8..31 are the caller's */
+/* FrameMeta.timestamp / status / supersededBy / kind of the listed frames (the values UnifiedSearch.swift:1245-1256 reads).
+ * timestamps NULL = leave every timestamp as it is, flags NULL likewise. Ids the engine does not hold are skipped; an id
+ * listed twice takes its last entry. *out_applied (may be NULL) = entries that named a held frame. A writer: exclusive lock,
+ * refused while the calling thread holds uncollected search tickets. */
+int wax_hip_set_attributes(wax_hip_engine* e, const uint64_t* frame_ids, const int64_t* timestamps, const uint32_t* flags,
+                           uint64_t n, uint64_t* out_applied);
+/* The same columns read back (the FrameMeta fields above). out_found[i] = 1 and the row's values, or 0 and (0, 0) for an id
+ * the engine does not hold. Any of the three output arrays may be NULL. */
+int wax_hip_get_attributes(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, int64_t* out_timestamps,
+                           uint32_t* out_flags, uint8_t* out_found);
+/* SearchRequest.timeRange (TimeRange.contains, SearchRequest.swift:91-105: after inclusive, before exclusive) and the flag
+ * exclusions of FrameFilter (UnifiedSearch.swift:1249-1254). A row passes iff !(has_after && ts < after) &&
+ * !(has_before && ts >= before) && (flags & deny_flags) == 0. */
+typedef struct wax_hip_row_predicate {
+    int32_t has_after;
+    int64_t after;
+    int32_t has_before;
+    int64_t before;
+    uint32_t deny_flags;
+} wax_hip_row_predicate;
+/* passesFrameFilter (UnifiedSearch.swift:1241-1258) as a PRE-filter: wax_hip_search_filtered's arguments plus the row predicate.
+ * Returns the best top_k among the rows that pass the predicate AND the allow-list (if given), best first, ties in ascending row
+ * order, fewer if fewer pass; then results with score < min_score are dropped. Distances are bit-identical to wax_hip_search's
+ * for the same rows. pred NULL, or one with no bound and no deny bit, is wax_hip_search_filtered. The predicate is evaluated on
+ * the device into a row bitmap; then either the passing rows are gathered and scored (few pass, top_k > 192, dims outside the
+ * specialised set, "force_general") or the f32 scan runs with the bitmap, skipping the loads of chunks without a passing row
+ * ("predicate_route", "predicate_scan_min_permille"). */
+int wax_hip_search_predicate(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k,
+                             int has_allow, const uint64_t* allow_frame_ids, uint64_t n_allow,
+                             int has_min_score, float min_score, const wax_hip_row_predicate* pred,
+                             uint64_t* out_ids, float* out_scores, uint32_t out_capacity, uint32_t* out_count);
+
 /* ---- persistence: "MV2V" vec segment, encoding 2 ------------------------- */
 
 /* serialize() (MetalVectorEngine.swift:682-714): byte-identical layout
@@ -424,6 +469,17 @@ int wax_hip_stats(wax_hip_engine* e, wax_hip_stats_t* out);
  *   one whose shift has reached this many rows moves directly and is as long as its shift),
  *   get-only "remove_batches" (calls that removed rows in one pass), "remove_batch_rows" (rows they removed),
  *   "remove_batch_bytes_written" (device bytes their passes wrote, bounce writes included).
+ * predicate search (wax_hip_search_predicate)
+ *   "predicate_route" (0 (default) = auto, 1 = always gather the passing rows — bitmap -> compact row list -> exact distances of the
+ *   listed rows -> general selection —, 2 = the masked f32 scan wherever it is eligible: top_k <= 192, a specialised dimension, no
+ *   "force_general"), "predicate_scan_min_permille" (the auto rule: the masked scan when at least this many rows per thousand pass;
+ *   default 500: where the first build's routes crossed for a random mask, between 1/8 and 1/2 passing; the committed kernels are
+ *   not timed yet: DESIGN 4.5),
+ *   get-only "predicate_searches" (calls with a non-empty predicate), "predicate_gather_searches" / "predicate_masked_scans" (those
+ *   answered by either route; a call whose predicate no row passes counts in neither), "predicate_chunks_skipped" (chunks of rows the
+ *   masked scans did not load), "attr_uploaded_rows" (rows of the attribute columns uploaded so far — an append uploads its own rows
+ *   only), "attr_device_rows" (rows the device columns are allocated for; 0 = the store never had attributes). wax_hip_stats'
+ *   bytes_scanned counts what a predicate search actually read: the gathered rows, or every row of the chunks it did not skip.
  * get-only
  *   "variant_count", "scan_grid", "store_ptr" (device address of the f32 slab), "fused_max_k", "batch_queries", "query_args_scans", "merged_scans", "done_flag_waits",
  *   "batch_inline_retries", "batch_max_row_err_e9", "batch_fallbacks", "onepass_queries", "batch_max_k", "batch_retries",

@@ -82,6 +82,28 @@ class VectorEngine {
         for (uint32_t i = 0; i < n; ++i) out[i] = {ids[i], scores[i]};
         return out;
     }
+    /// Per-row metadata for the predicate search (wax_hip_set_attributes): null = leave that column as it is.
+    uint64_t setAttributes(const std::vector<uint64_t>& frameIds, const std::vector<int64_t>* timestamps, const std::vector<uint32_t>* flags) {
+        uint64_t applied = 0;
+        if (!frameIds.empty())
+            check(wax_hip_set_attributes(h_, frameIds.data(), timestamps ? timestamps->data() : nullptr, flags ? flags->data() : nullptr,
+                                         frameIds.size(), &applied));
+        return applied;
+    }
+    /// searchFiltered plus the row predicate (time range, denied flag bits): best topK among the frames that pass.
+    std::vector<std::pair<uint64_t, float>> searchPredicate(const std::vector<float>& q, int topK, const std::vector<uint64_t>* allow,
+                                                            const float* minScore, const wax_hip_row_predicate& pred) {
+        const uint32_t cap = wax_hip_result_capacity(topK);
+        std::vector<uint64_t> ids(cap);
+        std::vector<float> scores(cap);
+        uint32_t n = 0;
+        check(wax_hip_search_predicate(h_, q.data(), (uint32_t)q.size(), topK, allow ? 1 : 0,
+                                       allow && !allow->empty() ? allow->data() : nullptr, allow ? allow->size() : 0,
+                                       minScore ? 1 : 0, minScore ? *minScore : 0.0f, &pred, ids.data(), scores.data(), cap, &n));
+        std::vector<std::pair<uint64_t, float>> out(n);
+        for (uint32_t i = 0; i < n; ++i) out[i] = {ids[i], scores[i]};
+        return out;
+    }
     /// Pending-embedding replay: WAL putEmbedding payloads back to back (UnifiedSearchEngineCache.swift:252-283).
     uint64_t applyPutEmbeddings(const uint8_t* payloads, uint64_t len) {
         uint64_t applied = 0;

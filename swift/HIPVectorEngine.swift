@@ -192,6 +192,55 @@ public actor HIPVectorEngine {
         }
     }
 
+    /// `FrameMeta.timestamp` and the status bits of `passesFrameFilter` (UnifiedSearch.swift:1245-1256) for the listed frames
+    /// (`wax_hip_set_attributes`): flag bit 0 deleted, 1 superseded, 2 surrogate, 8-31 the caller's. `nil` leaves that column as
+    /// it is; frames without a vector are skipped. Returns the entries that named a held frame.
+    @discardableResult
+    public func setAttributes(frameIds: [UInt64], timestamps: [Int64]?, flags: [UInt32]?) async throws -> Int {
+        guard !frameIds.isEmpty else { return 0 }
+        if let t = timestamps, t.count != frameIds.count { throw WaxError.encodingError(reason: "setAttributes: frameIds.count != timestamps.count") }
+        if let f = flags, f.count != frameIds.count { throw WaxError.encodingError(reason: "setAttributes: frameIds.count != flags.count") }
+        let h = handle
+        let applied: UInt64 = try await io.run {
+            var n: UInt64 = 0
+            try Self.check(frameIds.withUnsafeBufferPointer { ids in
+                (timestamps ?? []).withUnsafeBufferPointer { t in
+                    (flags ?? []).withUnsafeBufferPointer { f in
+                        wax_hip_set_attributes(h.raw, ids.baseAddress, timestamps == nil ? nil : t.baseAddress,
+                                               flags == nil ? nil : f.baseAddress, UInt64(ids.count), &n)
+                    }
+                }
+            })
+            return n
+        }
+        return Int(applied)
+    }
+
+    /// `search(vector:topK:allowlist:minScore:)` with the per-frame tests of `passesFrameFilter` applied on the device as well
+    /// (`wax_hip_search_predicate`): `after` / `before` are `SearchRequest.timeRange` (before exclusive, TimeRange.contains),
+    /// `denyFlags` the status bits the request's `FrameFilter` excludes. The best `topK` of the frames that pass.
+    public func search(vector: [Float], topK: Int, allowlist: Set<UInt64>?, minScore: Float?, after: Int64?, before: Int64?,
+                       denyFlags: UInt32) async throws -> [(frameId: UInt64, score: Float)] {
+        let h = handle
+        let limit = max(1, min(topK, 10_000))
+        let allowed: [UInt64]? = allowlist.map(Array.init)
+        return try await io.run {
+            var ids = [UInt64](repeating: 0, count: limit)
+            var scores = [Float](repeating: 0, count: limit)
+            var n: UInt32 = 0
+            var pred: wax_hip_row_predicate = .init(has_after: after == nil ? 0 : 1, after: after ?? 0, has_before: before == nil ? 0 : 1,
+                                                    before: before ?? 0, deny_flags: denyFlags)
+            try Self.check(vector.withUnsafeBufferPointer { q in
+                (allowed ?? []).withUnsafeBufferPointer { a in
+                    wax_hip_search_predicate(h.raw, q.baseAddress, UInt32(vector.count), Int32(clamping: topK),
+                                             allowed == nil ? 0 : 1, a.baseAddress, UInt64(a.count),
+                                             minScore == nil ? 0 : 1, minScore ?? 0, &pred, &ids, &scores, UInt32(limit), &n)
+                }
+            })
+            return (0..<Int(n)).map { (frameId: ids[$0], score: scores[$0]) }
+        }
+    }
+
     /// Pending-embedding replay without the [[Float]] detour: WAL putEmbedding payloads (WALEntryCodec.encode,
     /// WALEntryCodec.swift:39-54) concatenated, validated and applied inside the library as one addBatch.
     /// UnifiedSearchEngineCache.applyPendingEmbeddingsIfNeeded (:252-283) can call this with the raw payloads.

@@ -1,0 +1,119 @@
+#!/usr/bin/env python3
+"""The two routes of wax_hip_search_predicate against each other and against the unfiltered f32 scan.
+
+Store: --rows x 384 (default 1M), top-10, blocking calls, alternated runs, medians. For each pass fraction (1/64, 1/8, 1/2, 15/16)
+and each mask shape (a random deny bit, one contiguous time range) it times the gather route ("predicate_route" 1), the masked
+scan (2), today's alternative — searchFiltered with the allow-list of the passing ids — and, in the same alternation, the
+unfiltered f32 scan ("scan_mirror" 0, "mirror_share" 0). It prints one JSON line and, with --out, writes the same object to a file:
+the route table, the crossover of the random mask (the smallest measured fraction from which the masked scan is the faster route),
+masked / unfiltered at 15/16, and the bytes a contiguous 1/16 range read."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+import torch  # noqa: E402
+import wax_amd as wax  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--rows", type=int, default=1_000_000)
+ap.add_argument("--reps", type=int, default=15)
+ap.add_argument("--out", default=None)
+args = ap.parse_args()
+
+torch.cuda.set_device(0)
+dev = torch.device("cuda", 0)
+rows, dims, k = args.rows, 384, 10
+eng = wax.HIPVectorEngine(dimensions=dims)
+eng.reserve(rows)
+for r0, x in bench.device_rows(torch, 0, rows, dims, dev):
+    eng.addBatchDevice(np.arange(r0, r0 + x.shape[0], dtype=np.uint64), x)
+eng.setTuning("scan_mirror", 0)
+eng.setTuning("mirror_share", 0)
+ids = np.arange(rows, dtype=np.uint64)
+rng = np.random.default_rng(0)
+# bit 8 + j: a random mask that PASSES fraction FRACS[j] (the bit is set on the rows that fail); timestamps ascend with the row
+FRACS = [(1, 64), (1, 8), (1, 2), (15, 16)]
+flags = np.zeros(rows, dtype=np.uint32)
+u = rng.random(rows)
+for j, (a, b) in enumerate(FRACS):
+    flags[u >= a / b] |= np.uint32(1 << (8 + j))
+eng.setAttributes(ids, ids.astype(np.int64), flags)
+q = bench.unit_queries(4, dims)
+
+
+def timed(fn):
+    t0 = time.perf_counter()
+    fn()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def alternated(fns, reps):
+    """Every function once per round, in turn, `reps` rounds after one warm-up round: medians in ms."""
+    for f in fns.values():
+        f(0)
+    t = {name: [] for name in fns}
+    for i in range(reps):
+        for name, f in fns.items():
+            t[name].append(timed(lambda: f(i)))
+    return {name: round(statistics.median(v), 4) for name, v in t.items()}
+
+
+def routed(route, **kw):
+    def f(i):
+        eng.setTuning("predicate_route", route)
+        got = eng.searchFiltered(q[i % 4], k, **kw)
+        assert len(got[0]) == k
+    return f
+
+
+out = {"rows": rows, "dims": dims, "topk": k, "reps": args.reps, "table": []}
+for a, b in [(1, 64), (1, 16), (1, 8), (1, 2), (15, 16)]:     # 1/16: the contiguous range only (what the chunk skip is for)
+    span = rows * a // b
+    lo = min(rows // 7, rows - span)
+    shapes = [("contiguous", {"timeRange": (lo, lo + span)}, ids[lo:lo + span])]
+    if (a, b) in FRACS:
+        deny = 1 << (8 + FRACS.index((a, b)))
+        shapes.insert(0, ("random", {"denyFlags": deny}, ids[(flags & np.uint32(deny)) == 0]))
+    for shape, kw, passing in shapes:
+        m0, s0 = eng.getTuning("predicate_masked_scans"), eng.getTuning("predicate_chunks_skipped")
+        b0 = eng.stats().bytes_scanned
+        routed(2, **kw)(0)
+        scans = eng.getTuning("predicate_masked_scans") - m0
+        row = {"pass": f"{a}/{b}", "mask": shape, "passing_rows": int(len(passing)),
+               "masked_bytes_read": int(eng.stats().bytes_scanned - b0), "chunks_skipped": eng.getTuning("predicate_chunks_skipped") - s0}
+        assert scans == 1
+        row.update(alternated({
+            "gather_ms": routed(1, **kw),
+            "masked_ms": routed(2, **kw),
+            "allow_list_ms": lambda i, p=passing: eng.searchFiltered(q[i % 4], k, frameIds=p),
+            "unfiltered_ms": lambda i: eng.searchArrays(q[i % 4], k),
+        }, args.reps))
+        row["masked_over_unfiltered"] = round(row["masked_ms"] / row["unfiltered_ms"], 4)
+        out["table"].append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+eng.setTuning("predicate_route", 0)
+rand = [r for r in out["table"] if r["mask"] == "random"]
+# the crossover: the smallest measured fraction from which on the masked scan wins at every larger one too
+cross = None
+for r in rand:
+    if all(x["masked_ms"] <= x["gather_ms"] for x in rand[rand.index(r):]):
+        cross = r["pass"]
+        break
+out["random_mask_crossover_pass"] = cross
+out["random_mask_crossover_permille"] = None if cross is None else int(round(1000 * int(cross.split("/")[0]) / int(cross.split("/")[1])))
+out["masked_over_unfiltered_at_15_16"] = [r["masked_over_unfiltered"] for r in rand if r["pass"] == "15/16"][0]
+print(json.dumps(out))
+if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+eng.close()

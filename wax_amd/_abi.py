@@ -62,6 +62,18 @@ class RrfLane(ctypes.Structure):
                 ("pitch", ctypes.c_uint32), ("weight", ctypes.c_float)]
 
 
+class RowPredicate(ctypes.Structure):
+    """wax_hip_row_predicate (include/wax_hip.h)."""
+    _fields_ = [("has_after", ctypes.c_int32), ("after", ctypes.c_int64), ("has_before", ctypes.c_int32),
+                ("before", ctypes.c_int64), ("deny_flags", ctypes.c_uint32)]
+
+
+# wax_hip_set_attributes flag bits (WAX_HIP_FLAG_*); bits 8..31 are the caller's
+FLAG_DELETED = 0x1
+FLAG_SUPERSEDED = 0x2
+FLAG_SURROGATE = 0x4
+FLAG_USER_SHIFT = 8
+
 _engine_p = ctypes.c_void_p
 _f32p = ctypes.POINTER(ctypes.c_float)
 _u64p = ctypes.POINTER(ctypes.c_uint64)
@@ -101,6 +113,11 @@ SIGNATURES: Dict[str, tuple] = {
                                                ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
     "wax_hip_search_batch_filtered": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, _u64p,
                                                      ctypes.c_uint64, _u64p, _u64p, _f32p, _u64p, _f32p, ctypes.c_uint32, _u32p]),
+    "wax_hip_set_attributes": (ctypes.c_int, [_engine_p, _u64p, ctypes.POINTER(ctypes.c_int64), _u32p, ctypes.c_uint64, _u64p]),
+    "wax_hip_get_attributes": (ctypes.c_int, [_engine_p, _u64p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_int64), _u32p, _u8p]),
+    "wax_hip_search_predicate": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int, _u64p,
+                                                ctypes.c_uint64, ctypes.c_int, ctypes.c_float, ctypes.POINTER(RowPredicate),
+                                                _u64p, _f32p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
     "wax_hip_merge_batch_hits_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                        ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
     "wax_hip_add_batch_device": (ctypes.c_int, [_engine_p, _u64p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32]),

@@ -108,6 +108,7 @@ void wax_hip_engine_destroy(wax_hip_engine* e) {
         for (BatchCtx* c : e->bctx_all) free_bctx(c);
         for (FilterWork* f : e->filter_all) free_filter_work(f);
         (void)hipFree(e->idhash.d_table);
+        (void)hipFree(e->d_attr_ts); (void)hipFree(e->d_attr_flags);
     }
     (void)hipFree(e->d_store);
     (void)hipFree(e->d_ids);
@@ -331,6 +332,7 @@ int wax_hip_remove(wax_hip_engine* e, uint64_t frame_id) {
     // use and the host bookkeeping below still runs (returning here would leave ids / count describing the store before the shift)
     if (mirror_note_remove(e, (uint64_t)idx) != WAX_HIP_OK) { (void)hipGetLastError(); mirror_note_lost(e); }
     e->ids.erase(e->ids.begin() + idx);                   // :440
+    attr_note_remove(e, (uint64_t)idx);                   // the row's attributes go with its id
     e->idmap.erase_row(frame_id, (uint32_t)idx);
     e->count -= 1;                                        // :441
     return WAX_HIP_OK;
@@ -391,13 +393,20 @@ int wax_hip_remove_batch(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t 
             for (uint32_t r : rem) e->idmap.erase_only(e->ids[r]);
             e->idmap.renumber_removed(rem, e->count);
             {
-                uint64_t wr = rem[0];
+                // the id vector and the two attribute columns (which may end below `count`: the rows behind them are (0, 0)) in one pass
+                const uint64_t na = e->attr_ts.size();
+                uint64_t wr = rem[0], wa = rem[0];
                 size_t p = 0;
                 for (uint64_t r = rem[0]; r < e->count; ++r) {
                     if (p < m && rem[p] == r) { ++p; continue; }
                     e->ids[wr++] = e->ids[r];
+                    if (r < na) { e->attr_ts[wa] = e->attr_ts[r]; e->attr_flags[wa] = e->attr_flags[r]; ++wa; }
                 }
                 e->ids.resize((size_t)wr);
+                if (rem[0] < na) {
+                    e->attr_ts.resize((size_t)wa); e->attr_flags.resize((size_t)wa);
+                    attr_note_moved(e, rem[0]);
+                }
             }
             e->count -= m;                                     // :441, m times
             e->st_remove_batches += 1;

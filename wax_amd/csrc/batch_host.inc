@@ -27,6 +27,21 @@ static void mirror_note_replaced(wax_hip_engine* e) {       // deserialize: ever
     e->batch.mirror_valid = false; e->batch.stale = true; e->batch.dirty.clear(); e->batch.n_dirty = 0; e->batch.rows = 0;
     e->idhash.valid = false; e->idhash.stale = true; e->idhash.rows = 0;
 }
+// Mutation hooks of the per-row attribute columns (exclusive engine lock held). The device mirror is only ever marked: the next
+// predicate search uploads from the lowest marked row (ensure_attrs, api_predicate.inc).
+static void attr_note_moved(wax_hip_engine* e, uint64_t row) {
+    if (row < e->attr_stale_from) e->attr_stale_from = row;
+}
+static void attr_note_remove(wax_hip_engine* e, uint64_t idx) {   // remove(frameId:): the entry leaves as the id does
+    if (idx >= e->attr_ts.size()) return;                          // the row was (0, 0) like everything behind it
+    e->attr_ts.erase(e->attr_ts.begin() + (ptrdiff_t)idx);
+    e->attr_flags.erase(e->attr_flags.begin() + (ptrdiff_t)idx);
+    attr_note_moved(e, idx);
+}
+static void attr_note_replaced(wax_hip_engine* e) {               // deserialize / a shard emptied: every row is (0, 0) again
+    e->attr_ts.clear(); e->attr_flags.clear();
+    e->attr_stale_from = 0; e->attr_dev_rows = 0;
+}
 // a mutation the mirror could not follow (a failed row shift): convert everything at the next use
 static void mirror_note_lost(wax_hip_engine* e) {
     e->batch.mirror_valid = false; e->batch.stale = true; e->batch.dirty.clear(); e->batch.n_dirty = 0;
@@ -329,6 +344,8 @@ int grow_dev(T** p, uint64_t* cap, uint64_t want, size_t elem, const char* what)
 
 void free_filter_work(FilterWork* f) {
     if (!f) return;
+    (void)hipFree(f->d_pred_counts); (void)hipFree(f->d_partials);
+    if (f->h_pred_counts) (void)hipHostFree(f->h_pred_counts);
     (void)hipFree(f->d_rows); (void)hipFree(f->d_ids); (void)hipFree(f->d_dist); (void)hipFree(f->d_allow); (void)hipFree(f->d_bitmap);
     (void)hipFree(f->d_block_sum); (void)hipFree(f->d_total); (void)hipFree(f->d_query); (void)hipFree(f->d_qnorm); (void)hipFree(f->d_hits);
     (void)hipFree(f->d_bq); (void)hipFree(f->d_meta); (void)hipFree(f->d_lrows); (void)hipFree(f->d_lcnt); (void)hipFree(f->d_lids);

@@ -256,6 +256,10 @@ struct FilterWork {
     uint64_t part_cap = 0;
     wax_hip_hit* d_bhits = nullptr;  // [bhits_cap] merged hits, one row of k per fused query
     uint64_t bhits_cap = 0;
+    // wax_hip_search_predicate (allocated by its first call on this workspace)
+    uint32_t* d_pred_counts = nullptr;   // [2] passing rows, scan chunks that hold one (attr_mask_kernel)
+    uint32_t* h_pred_counts = nullptr;   // pinned [2]
+    int64_t* d_partials = nullptr;       // masked scan: kPartialsBytes, the per-workgroup lists + the short merge's flag words
 };
 
 void free_filter_work(FilterWork* f);
@@ -528,6 +532,25 @@ struct wax_hip_engine {
     std::vector<FilterWork*> filter_all, filter_free;
     int filter_max = 4;
     IdHash idhash;
+    // Per-row attributes (wax_hip_set_attributes; DESIGN 2). The host columns are authoritative, in row order beside `ids`; they may be
+    // SHORTER than the store: rows at or beyond their length are (0, 0) — what every appended row is — so the append paths do not touch
+    // them, and a store that never had attributes holds two empty vectors. Writers change them under the exclusive engine lock.
+    std::vector<int64_t> attr_ts;
+    std::vector<uint32_t> attr_flags;
+    // Device mirror, [attr_cap] of each, kept as the id -> row table is kept: rows [0, attr_dev_rows) below attr_stale_from match the
+    // host; the first predicate search after a change uploads [min of the two, count) on its workspace stream (ensure_attrs, under
+    // attr_mu and the shared engine lock). Writers (exclusive lock) only lower attr_stale_from.
+    std::mutex attr_mu;
+    int64_t* d_attr_ts = nullptr;
+    uint32_t* d_attr_flags = nullptr;
+    uint64_t attr_cap = 0, attr_dev_rows = 0;
+    uint64_t attr_stale_from = UINT64_MAX;        // lowest row whose device copy may differ from the host's
+    std::atomic<uint64_t> st_attr_uploaded{0};
+    std::atomic<int64_t> predicate_route{0};      // 0 = auto, 1 = always gather the passing rows, 2 = the masked scan wherever it is eligible
+    // auto rule: the masked scan when at least this many rows per thousand pass. 500 = the random mask's crossover of the FIRST build
+    // (between 1/8 and 1/2 passing, profiles/r13/c_routes_first_build.json); the committed kernels have not been timed (DESIGN 4.5).
+    std::atomic<int64_t> predicate_scan_min_permille{500};
+    std::atomic<uint64_t> st_predicate_searches{0}, st_predicate_gather{0}, st_predicate_masked{0}, st_predicate_skipped{0};
     std::atomic<int64_t> filter_device_min{4096}; // allow-lists at least this long are resolved on the device
     std::atomic<uint64_t> st_filter_device{0};    // filtered searches whose allow-list was resolved on the device
     std::atomic<int64_t> filter_batch{1};         // wax_hip_search_batch_filtered: 1 = one gather pass for all lists, 0 = the per-query loop
@@ -612,6 +635,12 @@ int sh_search_batch_filtered(wax_hip_engine* e, const float* queries, uint32_t n
 int sh_search_filtered(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, int has_allow, const uint64_t* allow,
                        uint64_t n_allow, int has_min, float min_score, uint64_t* out_ids, float* out_scores, uint32_t capacity,
                        uint32_t* out_count);
+int sh_set_attributes(wax_hip_engine* e, const uint64_t* frame_ids, const int64_t* timestamps, const uint32_t* flags, uint64_t n,
+                      uint64_t* out_applied);
+int sh_get_attributes(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, int64_t* out_ts, uint32_t* out_flags, uint8_t* out_found);
+int sh_search_predicate(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, int has_allow, const uint64_t* allow,
+                        uint64_t n_allow, int has_min, float min_score, const wax_hip_row_predicate* pred, uint64_t* out_ids,
+                        float* out_scores, uint32_t capacity, uint32_t* out_count);
 int sh_serialize(wax_hip_engine* e, uint8_t** out_bytes, size_t* out_len);
 int sh_deserialize(wax_hip_engine* e, const uint8_t* data, size_t len);
 void sh_destroy(wax_hip_engine* e);

@@ -197,18 +197,24 @@ uint32_t filter_bitmap_blocks(uint32_t n_rows) {
     return (n_words + (uint32_t)kWordsPerBlock - 1u) / (uint32_t)kWordsPerBlock;
 }
 
+hipError_t launch_bitmap_offsets(const uint32_t* bitmap, uint32_t n_rows, uint32_t* block_sum, uint32_t* total, hipStream_t st) {
+    const uint32_t n_words = (n_rows + 31u) / 32u;
+    const uint32_t n_blocks = filter_bitmap_blocks(n_rows);
+    hipLaunchKernelGGL(bitmap_count_kernel, dim3(n_blocks), dim3(256), 0, st, bitmap, n_words, block_sum);
+    hipLaunchKernelGGL(bitmap_scan_kernel, dim3(1), dim3(256), 0, st, block_sum, n_blocks, total);
+    return hipGetLastError();
+}
+
 hipError_t launch_allow_probe(const uint64_t* d_allow, uint64_t n_allow, const uint64_t* ids, uint32_t n_rows,
                               const uint32_t* table, uint64_t slots, uint32_t* bitmap, uint32_t* block_sum, uint32_t* total,
                               hipStream_t st) {
     const uint32_t n_words = (n_rows + 31u) / 32u;
-    const uint32_t n_blocks = filter_bitmap_blocks(n_rows);
     hipError_t err = hipMemsetAsync(bitmap, 0, (size_t)n_words * sizeof(uint32_t), st);
     if (err != hipSuccess) return err;
     hipLaunchKernelGGL(idhash_probe_kernel, dim3((unsigned)((n_allow + 255u) / 256u)), dim3(256), 0, st, d_allow, n_allow, ids,
                        table, (uint32_t)(slots - 1), bitmap);
-    hipLaunchKernelGGL(bitmap_count_kernel, dim3(n_blocks), dim3(256), 0, st, bitmap, n_words, block_sum);
-    hipLaunchKernelGGL(bitmap_scan_kernel, dim3(1), dim3(256), 0, st, block_sum, n_blocks, total);
-    return hipGetLastError();
+    if (block_sum == nullptr) return hipGetLastError();   // the caller finishes the bitmap first (predicate search) and asks for the offsets then
+    return launch_bitmap_offsets(bitmap, n_rows, block_sum, total, st);
 }
 
 hipError_t launch_rowlist_sort(const uint64_t* d_allow, const RowListDesc* d_desc, uint32_t n_lists, uint32_t max_len, const uint64_t* ids,

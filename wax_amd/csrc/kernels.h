@@ -496,6 +496,7 @@ hipError_t launch_finalize_batch(const int64_t* cand, uint32_t cand_cap, const u
 hipError_t launch_idhash_build(const uint64_t* ids, uint32_t row0, uint32_t n, uint32_t* table, uint64_t slots, hipStream_t st);   // rows [row0, n); row0 = 0 clears the table first
 uint32_t filter_bitmap_blocks(uint32_t n_rows);
 // probe + per-block popcounts + exclusive scan; *total = number of distinct allowed rows present in the store
+// (block_sum null: the probe alone — the bitmap is still to be narrowed; launch_bitmap_offsets follows when it is final)
 hipError_t launch_allow_probe(const uint64_t* d_allow, uint64_t n_allow, const uint64_t* ids, uint32_t n_rows,
                               const uint32_t* table, uint64_t slots, uint32_t* bitmap, uint32_t* block_sum, uint32_t* total,
                               hipStream_t st);
@@ -511,6 +512,37 @@ struct RowListDesc {
 hipError_t launch_rowlist_sort(const uint64_t* d_allow, const RowListDesc* d_desc, uint32_t n_lists, uint32_t max_len, const uint64_t* ids,
                                const uint32_t* table, uint64_t slots, uint32_t* rows_out, uint32_t* counts, hipStream_t st);
 
+
+// per-block popcounts + exclusive scan of a finished bitmap (what launch_allow_probe runs behind its probe); *total = bits set
+hipError_t launch_bitmap_offsets(const uint32_t* bitmap, uint32_t n_rows, uint32_t* block_sum, uint32_t* total, hipStream_t st);
+
+// ---- predicate.hip: per-row attributes -> row bitmap, and the f32 scan that honours it ----
+struct AttrMaskArgs {
+    const int64_t* ts;          // [n_rows] timestamps; null = every row 0
+    const uint32_t* flags;      // [n_rows] flag words; null = every row 0
+    uint32_t* bitmap;           // [ceil(n_rows / 32)] one bit per row; every word is written
+    uint32_t* counts;           // [2], zero before the launch: passing rows, scan chunks with at least one passing row
+    uint32_t n_rows;
+    uint32_t chunk_rows;        // rows per chunk of the masked scan (a power of two <= 64; 0 = do not count chunks)
+    int32_t and_bitmap;         // != 0: the bitmap already holds the allow-list's rows (filter.hip's probe): AND into it
+    int32_t has_after, has_before;
+    int64_t after, before;
+    uint32_t deny_flags;
+};
+hipError_t launch_attr_mask(const AttrMaskArgs& a, hipStream_t st);
+struct MaskedScanArgs {
+    const float* store;         // [n_rows][dims] f32
+    const float* query;         // [dims] f32 in HBM
+    const uint32_t* bitmap;     // [ceil(n_rows / 32)] rows that may be offered
+    int64_t* partials;          // [grid][k] per-workgroup sorted keys
+    uint32_t n_rows, row_base, dims;
+    int32_t k;
+    float q_norm;
+};
+bool scan_masked_dims(uint32_t dims);            // = the lane-shape table
+uint32_t scan_masked_chunk_rows(uint32_t dims);  // rows a wave consumes per iteration (the unit of the chunk skip); 0 = not served
+// cap: 128 (k <= 64) or 256 (k <= 192). The per-workgroup lists go through launch_merge_keys / launch_select_short.
+hipError_t launch_scan_masked(const MaskedScanArgs& a, int metric, int cap, int grid_cap, hipStream_t st, int* out_grid);
 
 // ---- rrf.hip: reciprocal-rank fusion of ranked id lists, one workgroup per query ----
 hipError_t launch_rrf_fuse(const wax_hip_rrf_lane* lanes, uint32_t n_lanes, uint32_t nq, int32_t k, uint64_t* out_ids,

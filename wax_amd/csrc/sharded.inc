@@ -411,9 +411,18 @@ int sh_move_all(ShardedState* s, size_t from, size_t to) {
         for (uint64_t r = dst_before; r < dst->count; ++r) dst->idmap.erase_only(dst->ids[(size_t)r]);
         dst->ids.resize((size_t)dst_before);
         dst->count = dst_before;
+        if (dst->attr_ts.size() > dst_before) { dst->attr_ts.resize((size_t)dst_before); dst->attr_flags.resize((size_t)dst_before); }
         mirror_note_replaced(dst);     // (rows were appended and taken back: the mirror and the id table start over)
         return rc;
     }
+    // the rows' attributes travel with them: dst's columns are padded to where the moved rows begin, then take src's
+    if (!src->attr_ts.empty()) {
+        dst->attr_ts.resize((size_t)dst_before, 0); dst->attr_flags.resize((size_t)dst_before, 0u);
+        dst->attr_ts.insert(dst->attr_ts.end(), src->attr_ts.begin(), src->attr_ts.end());
+        dst->attr_flags.insert(dst->attr_flags.end(), src->attr_flags.begin(), src->attr_flags.end());
+        attr_note_moved(dst, dst_before);
+    }
+    attr_note_replaced(src);
     // empty the source (capacity stays)
     src->count = 0;
     src->ids.clear();
@@ -1179,9 +1188,12 @@ int sh_search_batch_hits(wax_hip_engine* e, const float* queries, uint32_t nq, u
 
 // ---- filtered search: every shard pre-filters its own rows; the shards are in global row order, so a stable merge by
 // (score desc, shard asc) is the (distance asc, global row asc) order of one engine -------------------------------------
-int sh_search_filtered(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, int has_allow,
-                       const uint64_t* allow, uint64_t n_allow, int has_min, float min_score, uint64_t* out_ids,
-                       float* out_scores, uint32_t capacity, uint32_t* out_count) {
+// One query on a handle: every shard answers on its own rows at the same time (persistent per-shard workers) through `per_shard`
+// (shard engine, ids, scores, capacity, count) — the filtered or the predicate search — and the host merges: stable by score, so
+// (shard, position) order is kept on ties, then the cut at clamp(top_k) and the caller's capacity.
+template <typename PerShard>
+static int sh_fanout_filtered(wax_hip_engine* e, uint32_t dims, int32_t top_k, uint64_t* out_ids, float* out_scores, uint32_t capacity,
+                              uint32_t* out_count, PerShard per_shard) {
     ShardedState* s = e->sh;
     *out_count = 0;
     if (dims != e->dims) return fail(WAX_HIP_ERR_DIM_MISMATCH, dim_mismatch_msg(e->dims, dims));
@@ -1190,7 +1202,6 @@ int sh_search_filtered(wax_hip_engine* e, const float* query, uint32_t dims, int
     const uint32_t limit = (uint32_t)clamp_topk(top_k);
     struct Hit { float score; uint32_t shard; uint32_t pos; uint64_t id; };
     std::vector<Hit> all;
-    // every shard pre-filters its own rows at the same time (persistent per-shard workers), the host merges
     const size_t G = s->subs.size();
     std::vector<std::vector<uint64_t>> g_ids(G, std::vector<uint64_t>(limit));
     std::vector<std::vector<float>> g_scores(G, std::vector<float>(limit));
@@ -1198,8 +1209,7 @@ int sh_search_filtered(wax_hip_engine* e, const float* query, uint32_t dims, int
     std::vector<int> rcs(G, WAX_HIP_OK);
     std::vector<std::string> errs(G);
     auto one = [&](size_t g) {
-        rcs[g] = wax_hip_search_filtered(s->subs[g], query, dims, top_k, has_allow, allow, n_allow, has_min, min_score, g_ids[g].data(),
-                                         g_scores[g].data(), limit, &g_m[g]);
+        rcs[g] = per_shard(s->subs[g], g_ids[g].data(), g_scores[g].data(), limit, &g_m[g]);
         if (rcs[g] != WAX_HIP_OK) errs[g] = g_last_error;   // thread-local: carry it to the caller
     };
     if (G == 1) one(0); else s->workers.run_all(one);
@@ -1211,6 +1221,92 @@ int sh_search_filtered(wax_hip_engine* e, const float* query, uint32_t dims, int
     uint32_t m = 0;
     for (size_t i = 0; i < all.size() && m < limit && m < capacity; ++i, ++m) { out_ids[m] = all[i].id; out_scores[m] = all[i].score; }
     *out_count = m;
+    return WAX_HIP_OK;
+}
+
+int sh_search_filtered(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, int has_allow,
+                       const uint64_t* allow, uint64_t n_allow, int has_min, float min_score, uint64_t* out_ids,
+                       float* out_scores, uint32_t capacity, uint32_t* out_count) {
+    // every shard pre-filters its own rows
+    return sh_fanout_filtered(e, dims, top_k, out_ids, out_scores, capacity, out_count,
+                              [&](wax_hip_engine* sub, uint64_t* ids, float* scores, uint32_t cap, uint32_t* n) {
+                                  return wax_hip_search_filtered(sub, query, dims, top_k, has_allow, allow, n_allow, has_min, min_score, ids, scores, cap, n);
+                              });
+}
+
+// The predicate search on a handle: every shard masks and searches its own rows (its attribute columns follow its rows).
+int sh_search_predicate(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, int has_allow, const uint64_t* allow,
+                        uint64_t n_allow, int has_min, float min_score, const wax_hip_row_predicate* pred, uint64_t* out_ids,
+                        float* out_scores, uint32_t capacity, uint32_t* out_count) {
+    return sh_fanout_filtered(e, dims, top_k, out_ids, out_scores, capacity, out_count,
+                              [&](wax_hip_engine* sub, uint64_t* ids, float* scores, uint32_t cap, uint32_t* n) {
+                                  return wax_hip_search_predicate(sub, query, dims, top_k, has_allow, allow, n_allow, has_min, min_score, pred, ids, scores, cap, n);
+                              });
+}
+
+// setAttributes / getAttributes on a handle: the ids are grouped by owning shard (call order kept inside a group, so the last entry
+// of a repeated id still wins) and every shard that owns any is called once.
+int sh_set_attributes(wax_hip_engine* e, const uint64_t* frame_ids, const int64_t* timestamps, const uint32_t* flags, uint64_t n,
+                      uint64_t* out_applied) {
+    ShardedState* s = e->sh;
+    REFUSE_IF_HOLDING(e);
+    WriteGuard w(e->lock);
+    const size_t G = s->subs.size();
+    std::vector<std::vector<uint64_t>> ids(G);
+    std::vector<std::vector<int64_t>> ts(G);
+    std::vector<std::vector<uint32_t>> fl(G);
+    for (uint64_t i = 0; i < n; ++i) {
+        int64_t local = -1;
+        const int g = sh_find(s, frame_ids[i], &local);
+        if (g < 0) continue;
+        ids[(size_t)g].push_back(frame_ids[i]);
+        if (timestamps) ts[(size_t)g].push_back(timestamps[i]);
+        if (flags) fl[(size_t)g].push_back(flags[i]);
+    }
+    uint64_t total = 0;
+    for (size_t g = 0; g < G; ++g) {
+        if (ids[g].empty()) continue;
+        uint64_t got = 0;
+        const int rc = wax_hip_set_attributes(s->subs[g], ids[g].data(), timestamps ? ts[g].data() : nullptr, flags ? fl[g].data() : nullptr,
+                                              ids[g].size(), &got);
+        if (rc != WAX_HIP_OK) return rc;
+        total += got;
+    }
+    if (out_applied) *out_applied = total;
+    return WAX_HIP_OK;
+}
+
+int sh_get_attributes(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, int64_t* out_ts, uint32_t* out_flags, uint8_t* out_found) {
+    ShardedState* s = e->sh;
+    e->lock.lock_shared(holding(e) > 0);
+    struct Unlock { RWLock& l; ~Unlock() { l.unlock_shared(); } } unlock{e->lock};
+    const size_t G = s->subs.size();
+    std::vector<std::vector<uint64_t>> ids(G), at(G);
+    for (uint64_t i = 0; i < n; ++i) {
+        int64_t local = -1;
+        const int g = sh_find(s, frame_ids[i], &local);
+        if (out_ts) out_ts[i] = 0;
+        if (out_flags) out_flags[i] = 0u;
+        if (out_found) out_found[i] = 0;
+        if (g < 0) continue;
+        ids[(size_t)g].push_back(frame_ids[i]);
+        at[(size_t)g].push_back(i);
+    }
+    for (size_t g = 0; g < G; ++g) {
+        const size_t m = ids[g].size();
+        if (m == 0) continue;
+        std::vector<int64_t> ts(m);
+        std::vector<uint32_t> fl(m);
+        std::vector<uint8_t> found(m);
+        const int rc = wax_hip_get_attributes(s->subs[g], ids[g].data(), m, ts.data(), fl.data(), found.data());
+        if (rc != WAX_HIP_OK) return rc;
+        for (size_t j = 0; j < m; ++j) {
+            const uint64_t i = at[g][j];
+            if (out_ts) out_ts[i] = ts[j];
+            if (out_flags) out_flags[i] = fl[j];
+            if (out_found) out_found[i] = found[j];
+        }
+    }
     return WAX_HIP_OK;
 }
 
@@ -1427,7 +1523,9 @@ int64_t sh_get_tuning(wax_hip_engine* e, const std::string& k) {
     if (k == "batch_queries" || k == "batch_fallbacks" || k == "batch_retries" || k == "onepass_queries" || k == "filter_device_searches" || k == "filter_batch_queries" || k == "filter_batch_fallbacks" || k == "query_args_scans" || k == "batch_inline_retries" ||
         k == "batch_multi_passes" || k == "batch_multi_queries" || k == "short_selects" || k == "short_select_failures" ||
         k == "mirror_scans" || k == "mirror_scan_fallbacks" || k == "mirror_scan_unavailable" || k == "mirror_passes" || k == "mirror_shared_passes" || k == "mirror_shared_queries" ||
-        k == "remove_batches" || k == "remove_batch_rows" || k == "remove_batch_bytes_written") {   // counters: summed over the shards
+        k == "remove_batches" || k == "remove_batch_rows" || k == "remove_batch_bytes_written" ||
+        k == "predicate_searches" || k == "predicate_gather_searches" || k == "predicate_masked_scans" || k == "predicate_chunks_skipped" ||
+        k == "attr_uploaded_rows" || k == "attr_device_rows") {   // counters: summed over the shards
         int64_t t = 0;
         for (auto* sub : s->subs) t += wax_hip_get_tuning(sub, k.c_str());
         return t;

@@ -69,6 +69,8 @@ int wax_hip_set_tuning(wax_hip_engine* e, const char* key, int64_t value) {
     else if (k == "share_timing") e->share_timing = value != 0;   // 0: every chained scan records its own start event (one more packet between scans)
     else if (k == "filter_batch") { if (value < 0 || value > 1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "filter_batch must be 0 or 1"); e->filter_batch = value; }
     else if (k == "filter_device_min") { if (value < -1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "filter_device_min must be >= -1"); e->filter_device_min = value; }
+    else if (k == "predicate_route") { if (value < 0 || value > 2) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "predicate_route must be 0 (auto), 1 (gather) or 2 (masked scan)"); e->predicate_route = value; }
+    else if (k == "predicate_scan_min_permille") { if (value < 0 || value > 1001) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "predicate_scan_min_permille must be 0..1001"); e->predicate_scan_min_permille = value; }
     else if (k == "compact_window_rows") { if (value < 0 || value > 0xffffffffll) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "compact_window_rows must be 0 (what the bounce buffer holds) .. 4294967295"); e->compact_window_rows = value; }
     else if (k == "batch_sample_div") { if (value < 4 || value > 4096) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_sample_div must be 4..4096"); e->batch_sample_div = value; }
     else if (k == "batch_workspaces") {
@@ -166,6 +168,14 @@ int64_t wax_hip_get_tuning(wax_hip_engine* e, const char* key) {
     if (k == "remove_batches") return (int64_t)e->st_remove_batches.load();            // wax_hip_remove_batch calls that removed rows in one pass
     if (k == "remove_batch_rows") return (int64_t)e->st_remove_batch_rows.load();      // rows they removed
     if (k == "remove_batch_bytes_written") return (int64_t)e->st_remove_batch_bytes.load();   // device bytes their passes wrote (bounce writes included)
+    if (k == "predicate_route") return e->predicate_route.load();
+    if (k == "predicate_scan_min_permille") return e->predicate_scan_min_permille.load();
+    if (k == "predicate_searches") return (int64_t)e->st_predicate_searches.load();          // wax_hip_search_predicate calls with a non-empty predicate
+    if (k == "predicate_gather_searches") return (int64_t)e->st_predicate_gather.load();     // ... answered by gathering the passing rows
+    if (k == "predicate_masked_scans") return (int64_t)e->st_predicate_masked.load();        // ... answered by the masked f32 scan
+    if (k == "predicate_chunks_skipped") return (int64_t)e->st_predicate_skipped.load();     // chunks those scans did not load
+    if (k == "attr_uploaded_rows") return (int64_t)e->st_attr_uploaded.load();               // rows of the attribute columns uploaded so far
+    if (k == "attr_device_rows") return (int64_t)e->attr_cap;                                // rows the device columns are allocated for (0 = none)
     if (k == "idhash_rows_inserted") return (int64_t)e->st_idhash_rows.load();
     if (k == "batch_min") return e->batch_min.load();
     if (k == "batch_mode") return e->batch_mode.load();

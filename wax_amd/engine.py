@@ -276,10 +276,14 @@ class HIPVectorEngine:
         raise_for_status(rc)
         return ids[:got.value].copy(), scores[:got.value].copy()
 
-    def searchFiltered(self, vector, topK: int, frameIds=None, minScore=None) -> Tuple[np.ndarray, np.ndarray]:  # noqa: N802,N803
+    def searchFiltered(self, vector, topK: int, frameIds=None, minScore=None, timeRange=None,  # noqa: N802,N803
+                       denyFlags: int = 0) -> Tuple[np.ndarray, np.ndarray]:
         """The vector lane's candidate filters applied on the device (UnifiedSearch.swift:1241-1258): `frameIds` is
-        FrameFilter.frameIds (allow-list; None = no list, empty = nothing allowed), `minScore` is SearchRequest.minScore.
-        Returns the best topK among the ALLOWED frames (a pre-filter), best first, minus those scoring below minScore."""
+        FrameFilter.frameIds (allow-list; None = no list, empty = nothing allowed), `minScore` is SearchRequest.minScore,
+        `timeRange` = (after | None, before | None) is SearchRequest.timeRange against the rows' timestamps (after inclusive,
+        before exclusive: TimeRange.contains), `denyFlags` drops every row with one of these flag bits set (setAttributes).
+        Returns the best topK among the frames that PASS (a pre-filter), best first, minus those scoring below minScore.
+        A call without timeRange / denyFlags takes wax_hip_search_filtered, as before those arguments existed."""
         q = _as_f32(vector).reshape(-1)
         cap = self._result_capacity(topK)
         ids = np.empty(cap, dtype=np.uint64)
@@ -287,14 +291,53 @@ class HIPVectorEngine:
         got = ctypes.c_uint32(0)
         allow = None if frameIds is None else np.ascontiguousarray(list(frameIds) if not isinstance(frameIds, np.ndarray)
                                                                    else frameIds, dtype=np.uint64)
-        rc = self._lib.wax_hip_search_filtered(
-            self._h, _fp(q), q.size, int(max(min(topK, 2**31 - 1), -2**31)),
-            0 if allow is None else 1, None if allow is None or allow.size == 0 else _u64p(allow),
-            0 if allow is None else int(allow.size),
-            0 if minScore is None else 1, 0.0 if minScore is None else float(minScore),
-            _u64p(ids), _fp(scores), cap, ctypes.byref(got))
+        head = (self._h, _fp(q), q.size, int(max(min(topK, 2**31 - 1), -2**31)),
+                0 if allow is None else 1, None if allow is None or allow.size == 0 else _u64p(allow),
+                0 if allow is None else int(allow.size),
+                0 if minScore is None else 1, 0.0 if minScore is None else float(minScore))
+        tail = (_u64p(ids), _fp(scores), cap, ctypes.byref(got))
+        if timeRange is None and not denyFlags:
+            rc = self._lib.wax_hip_search_filtered(*head, *tail)
+        else:
+            after, before = (None, None) if timeRange is None else timeRange
+            pred = _abi.RowPredicate(0 if after is None else 1, 0 if after is None else int(after),
+                                     0 if before is None else 1, 0 if before is None else int(before), int(denyFlags) & 0xffffffff)
+            rc = self._lib.wax_hip_search_predicate(*head, ctypes.byref(pred), *tail)
         raise_for_status(rc)
         return ids[:got.value].copy(), scores[:got.value].copy()
+
+    def setAttributes(self, frameIds, timestamps=None, flags=None) -> int:  # noqa: N802,N803
+        """Per-row metadata for the predicate search: FrameMeta.timestamp as int64 `timestamps`, and `flags` (uint32; bit 0
+        deleted, bit 1 superseded, bit 2 surrogate, bits 8..31 the caller's). None leaves that column as it is. Ids the engine
+        does not hold are skipped; an id listed twice takes its last entry. Returns the entries that named a held frame."""
+        ids = np.ascontiguousarray(frameIds, dtype=np.uint64).reshape(-1)
+        n = int(ids.size)
+        if n == 0:
+            return 0
+        ts = None if timestamps is None else np.ascontiguousarray(timestamps, dtype=np.int64).reshape(-1)
+        fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint32).reshape(-1)
+        if (ts is not None and ts.size != n) or (fl is not None and fl.size != n):
+            raise EncodingError("setAttributes: one timestamp / flag word per frame id")
+        applied = ctypes.c_uint64(0)
+        rc = self._lib.wax_hip_set_attributes(
+            self._h, _u64p(ids), None if ts is None else ts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+            None if fl is None else fl.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), n, ctypes.byref(applied))
+        raise_for_status(rc)
+        return int(applied.value)
+
+    def getAttributes(self, frameIds) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:  # noqa: N802,N803
+        """(timestamps int64, flags uint32, found bool) of the listed frames; (0, 0, False) for an id the engine does not hold."""
+        ids = np.ascontiguousarray(frameIds, dtype=np.uint64).reshape(-1)
+        n = int(ids.size)
+        ts = np.zeros(n, dtype=np.int64)
+        fl = np.zeros(n, dtype=np.uint32)
+        found = np.zeros(n, dtype=np.uint8)
+        if n:
+            rc = self._lib.wax_hip_get_attributes(
+                self._h, _u64p(ids), n, ts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                fl.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), found.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+            raise_for_status(rc)
+        return ts, fl, found.astype(bool)
 
     def searchFilteredHits(self, vector, topK: int, allow) -> List[Tuple[int, float]]:  # noqa: N802,N803
         """searchFiltered as [(frameId, score)] (the shape the transcribed reference cases assert on)."""
