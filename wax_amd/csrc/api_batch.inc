@@ -37,8 +37,7 @@ static int search_batch_hits_impl(wax_hip_engine* e, const float* queries, uint3
         bool ran = false;
         {
             DeviceGuard g(e->device);
-            e->lock.lock_shared(holding(e) > 0);
-            struct Unlock { RWLock& l; ~Unlock() { l.unlock_shared(); } } unlock{e->lock};
+            ReadGuard rd(e);
             { const int frc = flush_pending(e); if (frc != WAX_HIP_OK) return frc; }
             if (e->row_base + e->count > 0x100000000ull)
                 return fail(WAX_HIP_ERR_CAPACITY, "row_base + count exceeds UInt32 row indices");
@@ -102,8 +101,7 @@ static int search_batch_hits_impl(wax_hip_engine* e, const float* queries, uint3
         bool ran = false;
         {
             DeviceGuard g(e->device);
-            e->lock.lock_shared(holding(e) > 0);
-            struct Unlock { RWLock& l; ~Unlock() { l.unlock_shared(); } } unlock{e->lock};
+            ReadGuard rd(e);
             { const int frc = flush_pending(e); if (frc != WAX_HIP_OK) return frc; }
             if (e->row_base + e->count > 0x100000000ull)
                 return fail(WAX_HIP_ERR_CAPACITY, "row_base + count exceeds UInt32 row indices");

@@ -1,5 +1,5 @@
 // api_fusion_filter.inc — part of engine.hip's translation unit (included there; not compiled alone).
-// C ABI: reciprocal-rank fusion and the filtered search (SURVEY 8f-4)
+// C ABI: reciprocal-rank fusion (SURVEY 8f-4); the filtered searches that used to share this file are in filter_host.inc
 
 // ---- rank fusion --------------------------------------------------------------
 
@@ -72,374 +72,4 @@ int wax_hip_rrf_fuse(const float* weights, const uint64_t* const* lists, const u
     if (out_sources) HIP_TRY(hipMemcpy(out_sources, d_src, (size_t)m * 4, hipMemcpyDeviceToHost), WAX_HIP_ERR_INTERNAL, "result download");
     *out_count = m;
     return WAX_HIP_OK;
-}
-
-// ---- filtered search --------------------------------------------------------
-
-// One query with an allow-list, on a pooled filter workspace; the caller holds the shared lock and has flushed pending rows.
-// *n = results written (before any score cut). Shared by wax_hip_search_filtered and the per-query path of the batched form.
-static int search_filtered_locked(wax_hip_engine* e, const float* query, uint32_t dims, int kpad, const uint64_t* allow_frame_ids,
-                                  uint64_t n_allow, uint64_t* out_ids, float* out_scores, uint32_t out_capacity, uint32_t* out_n) {
-    uint32_t n = 0;
-    *out_n = 0;
-    {
-        FilterWork* fp = nullptr;
-        { const int arc = acquire_filter_work(e, &fp); if (arc != WAX_HIP_OK) return arc; }
-        struct Release { wax_hip_engine* e; FilterWork* f; ~Release() { (void)hipStreamSynchronize(f->stream); release_filter_work(e, f); } } release{e, fp};
-        FilterWork& f = *fp;
-        hipStream_t st = f.stream;
-        // allowed frame ids -> local rows, ascending and unique (row order is the tie-break order of every path)
-        uint64_t m = 0;
-        const int64_t dev_min = e->filter_device_min.load();
-        if (e->count == 0 || n_allow == 0) {
-            m = 0;
-        } else if (dev_min >= 0 && n_allow >= (uint64_t)dev_min) {
-            // long lists: the probes are cache misses (~60 ns each on the host, 5.65 ms for 1M ids); on the device the
-            // same probes are a few tens of microseconds against the id -> row table in HBM (filter.hip), and the
-            // bitmap they mark hands the rows back ascending and unique
-            { const int hrc = ensure_idhash(e, st); if (hrc != WAX_HIP_OK) return hrc; }
-            const uint64_t n_words = (e->count + 31) / 32, n_blocks = filter_bitmap_blocks((uint32_t)e->count);
-            int grc = grow_dev(&f.d_allow, &f.allow_cap, n_allow, sizeof(uint64_t), "Failed to allocate allow-list");
-            if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_bitmap, &f.bitmap_words, n_words, sizeof(uint32_t), "Failed to allocate row bitmap");
-            if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_block_sum, &f.block_cap, n_blocks, sizeof(uint32_t), "Failed to allocate bitmap offsets");
-            const uint64_t m_max = n_allow < e->count ? n_allow : e->count;
-            if (grc == WAX_HIP_OK && f.cap < m_max) {
-                uint64_t cap = 1024;
-                while (cap < m_max) cap *= 2;
-                uint64_t c1 = f.cap, c2 = f.cap, c3 = f.cap;
-                grc = grow_dev(&f.d_rows, &c1, cap, sizeof(uint32_t), "Failed to allocate allowed-row list");
-                if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_ids, &c2, cap, sizeof(uint64_t), "Failed to allocate allowed-id list");
-                if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_dist, &c3, cap, sizeof(float), "Failed to allocate allowed-row distances");
-                f.cap = grc == WAX_HIP_OK ? cap : 0;
-            }
-            if (grc != WAX_HIP_OK) return grc;
-            HIP_TRY(hipMemcpyAsync(f.d_allow, allow_frame_ids, (size_t)n_allow * sizeof(uint64_t), hipMemcpyHostToDevice, st),
-                    WAX_HIP_ERR_INTERNAL, "allow-list upload");
-            HIP_TRY(launch_allow_probe(f.d_allow, n_allow, e->d_ids, (uint32_t)e->count, e->idhash.d_table, e->idhash.slots, f.d_bitmap,
-                                       f.d_block_sum, f.d_total, st), WAX_HIP_ERR_INTERNAL, "allow-list probe launch");
-            HIP_TRY(launch_allow_emit(f.d_bitmap, (uint32_t)e->count, f.d_block_sum, e->d_ids, f.d_rows, f.d_ids, st),
-                    WAX_HIP_ERR_INTERNAL, "allow-list compaction launch");
-            HIP_TRY(hipMemcpyAsync(f.h_total, f.d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, st), WAX_HIP_ERR_INTERNAL, "row count download");
-            HIP_TRY(hipStreamSynchronize(st), WAX_HIP_ERR_INTERNAL, "allow-list probe failed on device");
-            m = *f.h_total;
-            e->st_filter_device++;
-        } else {
-            std::vector<uint32_t> rows;
-            rows.reserve((size_t)n_allow);
-            for (uint64_t i = 0; i < n_allow; ++i) {
-                const int64_t r = e->idmap.find(allow_frame_ids[i]);
-                if (r >= 0) rows.push_back((uint32_t)r);
-            }
-            std::sort(rows.begin(), rows.end());
-            rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
-            m = rows.size();
-            if (m) {
-                std::vector<uint64_t> ids((size_t)m);
-                for (uint64_t i = 0; i < m; ++i) ids[i] = e->ids[rows[i]];
-                if (f.cap < m) {
-                    uint64_t cap = 1024;
-                    while (cap < m) cap *= 2;
-                    uint64_t c1 = f.cap, c2 = f.cap, c3 = f.cap;
-                    int grc = grow_dev(&f.d_rows, &c1, cap, sizeof(uint32_t), "Failed to allocate allowed-row list");
-                    if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_ids, &c2, cap, sizeof(uint64_t), "Failed to allocate allowed-id list");
-                    if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_dist, &c3, cap, sizeof(float), "Failed to allocate allowed-row distances");
-                    f.cap = grc == WAX_HIP_OK ? cap : 0;
-                    if (grc != WAX_HIP_OK) return grc;
-                }
-                // pageable sources: the runtime stages them before returning, so the vectors may die at the end of this block
-                HIP_TRY(hipMemcpyAsync(f.d_rows, rows.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, st), WAX_HIP_ERR_INTERNAL, "row list upload");
-                HIP_TRY(hipMemcpyAsync(f.d_ids, ids.data(), (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice, st), WAX_HIP_ERR_INTERNAL, "id list upload");
-                HIP_TRY(hipStreamSynchronize(st), WAX_HIP_ERR_INTERNAL, "row list upload");
-            }
-        }
-        if (m == 0) return WAX_HIP_OK;
-        const int k_eff = (uint64_t)kpad < m ? kpad : (int)m;
-        const float qn = query_norm(query, dims);
-        HIP_TRY(hipMemcpyAsync(f.d_query, query, (size_t)dims * sizeof(float), hipMemcpyHostToDevice, st), WAX_HIP_ERR_INTERNAL, "query upload");
-        HIP_TRY(hipMemcpyAsync(f.d_qnorm, &qn, sizeof(float), hipMemcpyHostToDevice, st), WAX_HIP_ERR_INTERNAL, "query norm upload");
-        RescoreArgs r{};   // exact f32 distances with scan_kernel's lane mapping and summation order
-        r.store = e->d_store; r.queries = f.d_query; r.q_norm = f.d_qnorm; r.rows = f.d_rows; r.dist_out = f.d_dist;
-        r.n_rows = (uint32_t)e->count; r.row_base = 0; r.dims = dims; r.nq = 1; r.cand_cap = 0; r.kp = (int)m;
-        HIP_TRY(launch_rescore(r, e->metric, st), WAX_HIP_ERR_INTERNAL, "distance kernel launch");
-        // keys of the compact list carry the POSITION in it; positions ascend with rows, so ties order as everywhere else
-        HIP_TRY(launch_select_general(f.d_dist, (uint32_t)m, 0u, k_eff, k_eff, f.d_ids, f.sw, f.d_hits, st),
-                WAX_HIP_ERR_INTERNAL, "select kernel launch");
-        HIP_TRY(hipMemcpyAsync(f.h_hits, f.d_hits, (size_t)k_eff * sizeof(wax_hip_hit), hipMemcpyDeviceToHost, st),
-                WAX_HIP_ERR_INTERNAL, "hits download");
-        HIP_TRY(hipStreamSynchronize(st), WAX_HIP_ERR_INTERNAL, "filtered search failed on device");
-        int rc = hits_to_results(e->metric, f.h_hits, (uint32_t)k_eff, out_ids, out_scores, out_capacity, &n);
-        if (rc != WAX_HIP_OK) return rc;
-        e->st_searches++;
-        e->st_rows += m;
-        e->st_bytes += m * (uint64_t)e->dims * 4ull;
-    }
-    *out_n = n;
-    return WAX_HIP_OK;
-}
-
-int wax_hip_search_filtered(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, int has_allow,
-                            const uint64_t* allow_frame_ids, uint64_t n_allow, int has_min_score, float min_score,
-                            uint64_t* out_ids, float* out_scores, uint32_t out_capacity, uint32_t* out_count) {
-    if (out_count) *out_count = 0;
-    if (!e) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine is null");
-    if (!query || !out_count || ((!out_ids || !out_scores) && out_capacity)) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "null argument");
-    if (has_allow && n_allow > 0 && !allow_frame_ids) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "allow-list is null");
-    if (e->sh) return sh_search_filtered(e, query, dims, top_k, has_allow, allow_frame_ids, n_allow, has_min_score, min_score, out_ids,
-                                         out_scores, out_capacity, out_count);
-    if (dims != e->dims) return fail(WAX_HIP_ERR_DIM_MISMATCH, dim_mismatch_msg(e->dims, dims));
-    const int kpad = clamp_topk(top_k);
-    uint32_t n = 0;
-    if (!has_allow) {
-        // no allow-list: the ordinary scan, then the score cut
-        int rc = wax_hip_search(e, query, dims, top_k, out_ids, out_scores, out_capacity, &n);
-        if (rc != WAX_HIP_OK) return rc;
-    } else {
-        DeviceGuard g(e->device);
-        e->lock.lock_shared(holding(e) > 0);
-        struct Unlock { RWLock& l; ~Unlock() { l.unlock_shared(); } } unlock{e->lock};
-        { const int frc = flush_pending(e); if (frc != WAX_HIP_OK) return frc; }
-        const int rc = search_filtered_locked(e, query, dims, kpad, allow_frame_ids, n_allow, out_ids, out_scores, out_capacity, &n);
-        if (rc != WAX_HIP_OK) return rc;
-    }
-    if (has_min_score) {  // `score < minScore` drops a candidate (UnifiedSearch.swift:1248); results are best-first
-        uint32_t keep = 0;
-        for (uint32_t i = 0; i < n; ++i)
-            if (!(out_scores[i] < min_score)) { out_ids[keep] = out_ids[i]; out_scores[keep] = out_scores[i]; ++keep; }
-        n = keep;
-    }
-    *out_count = n;
-    return WAX_HIP_OK;
-}
-
-// ---- batched filtered search ------------------------------------------------
-
-// The caller's arguments are sane for nq queries: both or neither of allow_begin / allow_len, every range inside the id array.
-static int check_batch_allow(uint32_t nq, const uint64_t* allow, uint64_t n_allow_ids, const uint64_t* allow_begin, const uint64_t* allow_len) {
-    if ((allow_begin == nullptr) != (allow_len == nullptr))
-        return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "allow_begin and allow_len must both be given or both be null");
-    if (!allow_len) return WAX_HIP_OK;
-    for (uint32_t q = 0; q < nq; ++q) {
-        const uint64_t len = allow_len[q];
-        if (len == WAX_HIP_NO_ALLOW_LIST) continue;
-        if (allow_begin[q] > n_allow_ids || len > n_allow_ids - allow_begin[q])
-            return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "allow-list range of query " + std::to_string(q) + " leaves the id array");
-        if (len > 0 && !allow) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "allow-list is null");
-    }
-    return WAX_HIP_OK;
-}
-
-static inline void apply_min_score(const float* min_scores, uint32_t q, uint64_t* ids, float* scores, uint32_t* n) {
-    if (!min_scores) return;
-    const float cut = min_scores[q];   // `score < minScore` drops a candidate, as in wax_hip_search_filtered (NaN: no cut)
-    uint32_t keep = 0;
-    for (uint32_t i = 0; i < *n; ++i)
-        if (!(scores[i] < cut)) { ids[keep] = ids[i]; scores[keep] = scores[i]; ++keep; }
-    *n = keep;
-}
-
-// The queries with an allow-list (fq), under the caller's shared lock: ONE gather pass for all their lists (filter.hip sorts the
-// lists into compact row lists, multiscan.hip's gather form scores every list against the queries that share it, the span merge
-// attaches frame ids), one download, one synchronisation. What that pass does not serve takes search_filtered_locked per query.
-static int batch_filtered_locked(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int kpad, const std::vector<uint32_t>& fq,
-                                 const uint64_t* allow, uint64_t n_allow_ids, const uint64_t* allow_begin, const uint64_t* allow_len,
-                                 const float* min_scores, uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts) {
-    const uint64_t count = e->count;
-    const int k = kpad < (int)out_stride ? kpad : (int)out_stride;   // the best out_stride of kpad: the same rows hits_to_results keeps
-    const uint32_t group = (k >= 1 && k <= FUSED_MAX_K) ? scan_multi_group(dims, k) : 0u;
-    if (e->filter_batch.load() == 0 || e->force_general.load() != 0 || group == 0) {
-        for (uint32_t q : fq) {
-            uint32_t n = 0;
-            const int rc = search_filtered_locked(e, queries + (size_t)q * dims, dims, kpad, allow_len[q] ? allow + allow_begin[q] : nullptr, allow_len[q],
-                                                  out_ids + (size_t)q * out_stride, out_scores + (size_t)q * out_stride, out_stride, &n);
-            if (rc != WAX_HIP_OK) return rc;
-            apply_min_score(min_scores, q, out_ids + (size_t)q * out_stride, out_scores + (size_t)q * out_stride, &n);
-            out_counts[q] = n;
-        }
-        e->st_filter_batch_fallbacks += fq.size();
-        return WAX_HIP_OK;
-    }
-    if (e->row_base + count > 0x100000000ull) return fail(WAX_HIP_ERR_CAPACITY, "row_base + count exceeds UInt32 row indices");
-    // distinct lists: queries with the same (begin, len) share one
-    struct List { uint64_t begin, len, ub; uint32_t row_off; std::vector<uint32_t> qs; };
-    std::vector<List> lists;
-    {
-        std::map<std::pair<uint64_t, uint64_t>, uint32_t> index;
-        for (uint32_t q : fq) {
-            const uint64_t len = count == 0 ? 0 : allow_len[q];
-            if (len == 0) continue;                               // nothing allowed: count 0
-            auto it = index.emplace(std::make_pair(allow_begin[q], len), (uint32_t)lists.size());
-            if (it.second) lists.push_back(List{allow_begin[q], len, len < count ? len : count, 0, {}});
-            lists[it.first->second].qs.push_back(q);
-        }
-    }
-    uint64_t rows_total = 0, long_max = 0;
-    uint32_t short_max = 0;
-    std::vector<RowListDesc> descs;
-    for (uint32_t li = 0; li < lists.size(); ++li) {
-        List& L = lists[li];
-        L.row_off = (uint32_t)rows_total;
-        rows_total += L.ub;
-        if (rows_total >= 0x80000000ull) return fail(WAX_HIP_ERR_CAPACITY, "allowed rows of one batch exceed 2^31");
-        if (L.len <= ROWLIST_SORT_MAX) {
-            descs.push_back(RowListDesc{L.begin, (uint32_t)L.len, L.row_off, li, 0u});
-            if (L.len > short_max) short_max = (uint32_t)L.len;
-        } else if (L.ub > long_max) {
-            long_max = L.ub;
-        }
-    }
-    // groups of up to `group` queries per list, work items sized by the list's upper bound (its device-side length is not read back)
-    std::vector<GatherGroup> groups;
-    std::vector<uint32_t> item_group, slot_q, spans;
-    std::vector<float> slot_norm;
-    uint64_t part_lists = 0;
-    const int grid_cap = (int)e->grid_blocks.load();
-    for (uint32_t li = 0; li < lists.size(); ++li) {
-        const List& L = lists[li];
-        const uint32_t W = scan_multi_listed_items(L.ub, dims, grid_cap);
-        for (size_t g0 = 0; g0 < L.qs.size(); g0 += group) {
-            const uint32_t gn = (uint32_t)std::min<size_t>(group, L.qs.size() - g0);
-            GatherGroup G{};
-            G.row_off = L.row_off; G.count_slot = li; G.q0 = (uint32_t)slot_q.size(); G.nq = gn;
-            G.part_off = (uint32_t)part_lists; G.n_items = W; G.item0 = (uint32_t)item_group.size();
-            for (uint32_t i = 0; i < gn; ++i) {
-                const uint32_t q = L.qs[g0 + i];
-                slot_q.push_back(q);
-                slot_norm.push_back(query_norm(queries + (size_t)q * dims, dims));
-                spans.push_back((uint32_t)(part_lists + (uint64_t)i * W));
-                spans.push_back(W);
-            }
-            for (uint32_t w = 0; w < W; ++w) item_group.push_back((uint32_t)groups.size());
-            groups.push_back(G);
-            part_lists += (uint64_t)gn * W;
-            if (part_lists >= 0x80000000ull / (uint64_t)k) return fail(WAX_HIP_ERR_CAPACITY, "too many partial lists in one batch");
-        }
-    }
-    for (uint32_t q : fq) out_counts[q] = 0;
-    const uint32_t P = (uint32_t)slot_q.size();
-    e->st_filter_batch_queries += fq.size();
-    e->st_searches += fq.size();
-    if (P == 0) return WAX_HIP_OK;
-
-    FilterWork* fp = nullptr;
-    { const int arc = acquire_filter_work(e, &fp); if (arc != WAX_HIP_OK) return arc; }
-    struct Release { wax_hip_engine* e; FilterWork* f; ~Release() { (void)hipStreamSynchronize(f->stream); release_filter_work(e, f); } } release{e, fp};
-    FilterWork& f = *fp;
-    hipStream_t st = f.stream;
-    { const int hrc = ensure_idhash(e, st); if (hrc != WAX_HIP_OK) return hrc; }
-    // one blob: descs | groups | item_group | slot_q | slot_norm | spans (16-byte aligned sections)
-    auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t o_desc = 0, o_grp = al(o_desc + descs.size() * sizeof(RowListDesc)), o_item = al(o_grp + groups.size() * sizeof(GatherGroup));
-    const size_t o_q = al(o_item + item_group.size() * 4), o_n = al(o_q + (size_t)P * 4), o_sp = al(o_n + (size_t)P * 4), meta_bytes = al(o_sp + (size_t)P * 8);
-    std::vector<unsigned char> meta(meta_bytes, 0);
-    std::memcpy(meta.data() + o_desc, descs.data(), descs.size() * sizeof(RowListDesc));
-    std::memcpy(meta.data() + o_grp, groups.data(), groups.size() * sizeof(GatherGroup));
-    std::memcpy(meta.data() + o_item, item_group.data(), item_group.size() * 4);
-    std::memcpy(meta.data() + o_q, slot_q.data(), (size_t)P * 4);
-    std::memcpy(meta.data() + o_n, slot_norm.data(), (size_t)P * 4);
-    std::memcpy(meta.data() + o_sp, spans.data(), (size_t)P * 8);
-    int grc = grow_dev(&f.d_meta, &f.meta_cap, meta_bytes, 1, "Failed to allocate batch filter tables");
-    if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_allow, &f.allow_cap, n_allow_ids, sizeof(uint64_t), "Failed to allocate allow-lists");
-    if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_bq, &f.bq_cap, (uint64_t)nq * dims, sizeof(float), "Failed to allocate batch queries");
-    if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_lrows, &f.lrows_cap, rows_total, sizeof(uint32_t), "Failed to allocate allowed-row lists");
-    if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_lcnt, &f.lcnt_cap, lists.size(), sizeof(uint32_t), "Failed to allocate allowed-row counts");
-    if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_part, &f.part_cap, part_lists * (uint64_t)k, sizeof(int64_t), "Failed to allocate gather partials");
-    if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_bhits, &f.bhits_cap, (uint64_t)P * k, sizeof(wax_hip_hit), "Failed to allocate batch filter hits");
-    if (grc == WAX_HIP_OK && long_max > 0) {
-        const uint64_t n_words = (count + 31) / 32, n_blocks = filter_bitmap_blocks((uint32_t)count);
-        grc = grow_dev(&f.d_bitmap, &f.bitmap_words, n_words, sizeof(uint32_t), "Failed to allocate row bitmap");
-        if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_block_sum, &f.block_cap, n_blocks, sizeof(uint32_t), "Failed to allocate bitmap offsets");
-        if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_lids, &f.lids_cap, long_max, sizeof(uint64_t), "Failed to allocate allowed-id list");
-    }
-    if (grc != WAX_HIP_OK) return grc;
-    const RowListDesc* d_desc = reinterpret_cast<const RowListDesc*>(f.d_meta + o_desc);
-    const GatherGroup* d_grp = reinterpret_cast<const GatherGroup*>(f.d_meta + o_grp);
-    const uint32_t* d_item = reinterpret_cast<const uint32_t*>(f.d_meta + o_item);
-    const uint32_t* d_slot_q = reinterpret_cast<const uint32_t*>(f.d_meta + o_q);
-    const float* d_slot_n = reinterpret_cast<const float*>(f.d_meta + o_n);
-    const uint32_t* d_spans = reinterpret_cast<const uint32_t*>(f.d_meta + o_sp);
-    // the caller's id array as it is (the lists are ranges of it; overlapping ranges travel once), the queries, the tables
-    HIP_TRY(hipMemcpyAsync(f.d_allow, allow, (size_t)n_allow_ids * sizeof(uint64_t), hipMemcpyHostToDevice, st), WAX_HIP_ERR_INTERNAL, "allow-list upload");
-    HIP_TRY(hipMemcpyAsync(f.d_bq, queries, (size_t)nq * dims * sizeof(float), hipMemcpyHostToDevice, st), WAX_HIP_ERR_INTERNAL, "query upload");
-    HIP_TRY(hipMemcpyAsync(f.d_meta, meta.data(), meta_bytes, hipMemcpyHostToDevice, st), WAX_HIP_ERR_INTERNAL, "batch filter table upload");
-    // lists -> compact ascending row lists with device-side counts; no host round trip before the scan
-    HIP_TRY(launch_rowlist_sort(f.d_allow, d_desc, (uint32_t)descs.size(), short_max, e->d_ids, e->idhash.d_table, e->idhash.slots, f.d_lrows,
-                                f.d_lcnt, st), WAX_HIP_ERR_INTERNAL, "allow-list sort launch");
-    for (uint32_t li = 0; li < lists.size(); ++li) {   // lists too long for LDS: the single-query path's bitmap route, one list at a time
-        const List& L = lists[li];
-        if (L.len <= ROWLIST_SORT_MAX) continue;
-        HIP_TRY(launch_allow_probe(f.d_allow + L.begin, L.len, e->d_ids, (uint32_t)count, e->idhash.d_table, e->idhash.slots, f.d_bitmap,
-                                   f.d_block_sum, f.d_lcnt + li, st), WAX_HIP_ERR_INTERNAL, "allow-list probe launch");
-        HIP_TRY(launch_allow_emit(f.d_bitmap, (uint32_t)count, f.d_block_sum, e->d_ids, f.d_lrows + L.row_off, f.d_lids, st),
-                WAX_HIP_ERR_INTERNAL, "allow-list compaction launch");
-        e->st_filter_device++;
-    }
-    ScanMultiArgs a{};
-    a.store = e->d_store; a.queries = f.d_bq; a.qlist = d_slot_q; a.q_norm = d_slot_n; a.partials = f.d_part;
-    a.n_rows = (uint32_t)count; a.row_base = (uint32_t)e->row_base; a.dims = dims; a.nq = 0; a.k = k;
-    a.rows = f.d_lrows; a.row_counts = f.d_lcnt; a.groups = d_grp; a.item_group = d_item;
-    HIP_TRY(launch_scan_multi_listed(a, e->metric, (uint32_t)item_group.size(), st), WAX_HIP_ERR_INTERNAL, "gather scan launch");
-    HIP_TRY(launch_merge_keys_spans(f.d_part, d_spans, k, e->d_ids, a.row_base, (uint32_t)count, f.d_bhits, (uint32_t)k, P, st),
-            WAX_HIP_ERR_INTERNAL, "gather merge launch");
-    std::vector<wax_hip_hit> hits((size_t)P * k);
-    HIP_TRY(hipMemcpyAsync(hits.data(), f.d_bhits, hits.size() * sizeof(wax_hip_hit), hipMemcpyDeviceToHost, st), WAX_HIP_ERR_INTERNAL, "hits download");
-    HIP_TRY(hipStreamSynchronize(st), WAX_HIP_ERR_INTERNAL, "batched filtered search failed on device");
-    for (uint32_t p = 0; p < P; ++p) {
-        const uint32_t q = slot_q[p];
-        uint32_t n = 0;
-        hits_to_results(e->metric, hits.data() + (size_t)p * k, (uint32_t)k, out_ids + (size_t)q * out_stride, out_scores + (size_t)q * out_stride,
-                        out_stride, &n);
-        apply_min_score(min_scores, q, out_ids + (size_t)q * out_stride, out_scores + (size_t)q * out_stride, &n);
-        out_counts[q] = n;
-    }
-    e->st_rows += rows_total;
-    e->st_bytes += rows_total * (uint64_t)dims * 4ull;
-    return WAX_HIP_OK;
-}
-
-int wax_hip_search_batch_filtered(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
-                                  const uint64_t* allow_frame_ids, uint64_t n_allow_ids, const uint64_t* allow_begin,
-                                  const uint64_t* allow_len, const float* min_scores, uint64_t* out_ids, float* out_scores,
-                                  uint32_t out_stride, uint32_t* out_counts) {
-    if (!e) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine is null");
-    if (nq == 0) return WAX_HIP_OK;
-    if (!queries || !out_counts) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "null input");
-    if ((!out_ids || !out_scores) && out_stride) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "output arrays are null");
-    { const int crc = check_batch_allow(nq, allow_frame_ids, n_allow_ids, allow_begin, allow_len); if (crc != WAX_HIP_OK) return crc; }
-    for (uint32_t q = 0; q < nq; ++q) out_counts[q] = 0;
-    if (e->sh) return sh_search_batch_filtered(e, queries, nq, dims, top_k, allow_frame_ids, n_allow_ids, allow_begin, allow_len, min_scores, out_ids,
-                                               out_scores, out_stride, out_counts);
-    if (dims != e->dims) return fail(WAX_HIP_ERR_DIM_MISMATCH, dim_mismatch_msg(e->dims, dims));
-    if (out_stride == 0) return WAX_HIP_OK;
-    std::vector<uint32_t> plain, fq;
-    for (uint32_t q = 0; q < nq; ++q) (allow_len && allow_len[q] != WAX_HIP_NO_ALLOW_LIST ? fq : plain).push_back(q);
-    if (!plain.empty()) {
-        // queries without a list: one sub-batch of the unfiltered batched search (its own lock acquisition), then the cut
-        std::vector<float> qs;
-        const float* src = queries;
-        if (plain.size() != nq) {
-            qs.resize(plain.size() * (size_t)dims);
-            for (size_t i = 0; i < plain.size(); ++i) std::memcpy(qs.data() + i * dims, queries + (size_t)plain[i] * dims, (size_t)dims * 4);
-            src = qs.data();
-        }
-        const uint32_t limit = (uint32_t)clamp_topk(top_k);
-        const uint32_t w = limit < out_stride ? limit : out_stride;
-        std::vector<wax_hip_hit> hits(plain.size() * (size_t)w);
-        std::vector<uint32_t> cnt(plain.size(), 0);
-        const int rc = search_batch_hits_impl(e, src, (uint32_t)plain.size(), dims, top_k, hits.data(), w, cnt.data());
-        if (rc != WAX_HIP_OK) return rc;
-        for (size_t i = 0; i < plain.size(); ++i) {
-            const uint32_t q = plain[i];
-            uint32_t n = 0;
-            hits_to_results(e->metric, hits.data() + i * w, w, out_ids + (size_t)q * out_stride, out_scores + (size_t)q * out_stride, out_stride, &n);
-            apply_min_score(min_scores, q, out_ids + (size_t)q * out_stride, out_scores + (size_t)q * out_stride, &n);
-            out_counts[q] = n;
-        }
-    }
-    if (fq.empty()) return WAX_HIP_OK;
-    DeviceGuard g(e->device);
-    e->lock.lock_shared(holding(e) > 0);
-    struct Unlock { RWLock& l; ~Unlock() { l.unlock_shared(); } } unlock{e->lock};
-    { const int frc = flush_pending(e); if (frc != WAX_HIP_OK) return frc; }
-    return batch_filtered_locked(e, queries, nq, dims, clamp_topk(top_k), fq, allow_frame_ids, n_allow_ids, allow_begin, allow_len,
-                                 min_scores, out_ids, out_scores, out_stride, out_counts);
 }

@@ -39,8 +39,9 @@ using namespace wax;
 //   api_search.inc         C ABI: search_submit / search_collect / search, result capacity
 //   api_batch.inc          C ABI: search_batch[_hits], the device-resident and ticketed batched entry points
 //   api_shard.inc          C ABI: the one-rank-per-GPU entry points (set_row_base, search_shard_device, merge_hits_device, merge_batch_hits_device, hits_to_results)
-//   api_fusion_filter.inc  C ABI: reciprocal-rank fusion and the filtered search
-//   api_predicate.inc      C ABI: per-row attributes (set / get) and the predicate search
+//   api_fusion_filter.inc  C ABI: reciprocal-rank fusion
+//   api_predicate.inc      C ABI: per-row attributes (set / get) and their device columns
+//   filter_host.inc        C ABI: the filtered searches — one query with an allow-list and / or a row predicate (one locked body), the batched allow-list form
 //   codec.inc              C ABI: MV2V encoding-2 serialize / deserialize (MetalVectorEngine.swift:682-815)
 //   tuning.inc             C ABI: stats, the tuning registry (set / get), the two timing microbenchmarks
 //   sharded.inc            the multi-GPU handle (one engine per device behind one handle): DESIGN 4.3
@@ -55,6 +56,7 @@ using namespace wax;
 #include "api_shard.inc"
 #include "api_fusion_filter.inc"
 #include "api_predicate.inc"
+#include "filter_host.inc"
 #include "codec.inc"
 #include "tuning.inc"
 }  // extern "C"

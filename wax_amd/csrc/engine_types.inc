@@ -250,7 +250,7 @@ struct FilterWork {
     uint64_t lrows_cap = 0;
     uint32_t* d_lcnt = nullptr;      // [lcnt_cap] their device-side lengths
     uint64_t lcnt_cap = 0;
-    uint64_t* d_lids = nullptr;      // [lids_cap] frame ids the bitmap route writes beside its rows (unused)
+    uint64_t* d_lids = nullptr;      // [lids_cap] frame ids the bitmap route writes beside its rows: allow_emit needs an id output; never read
     uint64_t lids_cap = 0;
     int64_t* d_part = nullptr;       // [part_cap] per-(query, work item) partial key lists
     uint64_t part_cap = 0;
@@ -467,7 +467,7 @@ struct wax_hip_engine {
     // in two, 200K 45.3 / 45.6, 400K 88.9 / 87.0, 700K 154.0 / 150.1, 1M 224.3 / 214.3, 1.25M 274.3 / 268.7.
     std::atomic<int64_t> merge_overlap_mb{400};
     std::atomic<uint64_t> st_overlap_scans{0};
-    std::atomic<uint64_t> st_short_selects{0};   // short selections enqueued (k > 192)
+    std::atomic<uint64_t> st_short_selects{0};   // short selections enqueued by enqueue_scan (k > 192 in front of the radix selection; 64 < k <= 192 in front of the second-launch merge)
     std::atomic<int64_t> batch_qfrag{1};     // 1 (default) = the prep kernel also writes the bf16 queries in MFMA A-fragment order and the register-resident GEMM loads them from there (coalesced); 0 = row-major reads
     std::atomic<int64_t> batch_min{1};       // fewer queries than this: always pipelined single-query scans (1..15: cost model below)
     std::atomic<int64_t> batch_mode{1};      // 0 = never use the MFMA path
@@ -603,6 +603,13 @@ int holding(wax_hip_engine* e) {   // uncollected tickets submitted by the calli
     auto it = e->outstanding.find(std::this_thread::get_id());
     return it == e->outstanding.end() ? 0 : it->second;
 }
+// The read side of WriteGuard: the shared lock for the scope, re-entrant for a thread that holds uncollected tickets (RWLock::lock_shared).
+struct ReadGuard {
+    RWLock& l;
+    const bool holder;   // the calling thread holds tickets of this engine
+    explicit ReadGuard(wax_hip_engine* e) : l(e->lock), holder(holding(e) > 0) { l.lock_shared(holder); }
+    ~ReadGuard() { l.unlock_shared(); }
+};
 void note_submit_id(wax_hip_engine* e, std::thread::id* owner) {
     *owner = std::this_thread::get_id();
     std::unique_lock<std::mutex> g(e->out_mu);

@@ -26,6 +26,29 @@ bool scan_uses_query_args(wax_hip_engine* e, int k_eff, bool has_general_slot, b
     return e->fuse_merge.load() != 0 && !overlap_merge && scan_merges_in_kernel(grid, k_eff, e->merge_kway.load() != 0, (uint32_t)e->count, e->dims);
 }
 
+// wave-list capacity of a fused scan that keeps k keys per workgroup (the CAP template argument of the scan and merge kernels)
+static inline int wave_list_cap(int k) { return k <= 64 ? 128 : 256; }
+
+// The second-launch merge of `grid` per-workgroup lists of k_eff keys (a fused scan that did not merge in its own kernel; the masked
+// scan): kpad hits in d_hits. 64 < k <= 192 (no k-way merge of the heads): the short selection merges the lists first — sorts their
+// first few entries and the prefixes below the k-th of those in LDS, ~15 us where the wave-list merge of grid x k keys takes 100 - 350
+// (1M rows, top-192, blocking: 0.60 -> 0.3 ms). Lists of k entries cannot have dropped a row of the answer: no certificate; the merge
+// kernel stays behind it, gated, for prefixes that overflow the LDS buffer (flag words: the ticket's cache line behind the lists).
+// *out_short (if given) = the short selection was enqueued.
+int enqueue_list_merge(wax_hip_engine* e, int64_t* d_partials, int grid, int k_eff, int kpad, int cap, uint32_t row_base, uint32_t n_rows,
+                       wax_hip_hit* d_hits, hipStream_t stream, bool* out_short) {
+    uint32_t* short_flags = nullptr;
+    if (e->select_short.load() != 0 && k_eff > SCAN_KWAY_MAX_K && select_short_viable(k_eff, grid, k_eff)) {
+        short_flags = partials_ticket(d_partials) + 8;
+        HIP_TRY(launch_select_short(d_partials, (uint32_t)grid, (uint32_t)k_eff, k_eff, kpad, e->d_ids, row_base, n_rows, short_flags, d_hits, stream),
+                WAX_HIP_ERR_INTERNAL, "short merge launch");
+    }
+    if (out_short) *out_short = short_flags != nullptr;
+    HIP_TRY(launch_merge_keys(d_partials, (uint32_t)grid * (uint32_t)k_eff, k_eff, kpad, e->d_ids, row_base, n_rows, d_hits, cap, stream, short_flags),
+            WAX_HIP_ERR_INTERNAL, "merge kernel launch");
+    return WAX_HIP_OK;
+}
+
 // d_query == nullptr: the query is `h_query` (host memory, read during this call) and travels in the kernel arguments.
 int enqueue_scan(wax_hip_engine* e, const float* d_query, float q_norm, int k_eff, int kpad, int64_t* d_partials,
                  Slot* general_slot, wax_hip_hit* d_hits, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
@@ -71,7 +94,7 @@ int enqueue_scan(wax_hip_engine* e, const float* d_query, float q_norm, int k_ef
     // chain wait inside the interval; 1: the pair is recorded in front of and behind the launch.
     const bool bound = ev0 != nullptr && ev1 != nullptr && tk_mode == 2;
     if (fused) {
-        const int cap = k_eff <= 64 ? 128 : 256;
+        const int cap = wave_list_cap(k_eff);
         bool record_start = ev0 != nullptr && !bound;
         if (!bound && chain_guard.owns_lock() && ev0 && ev1 && used_start && used_end && e->share_timing.load() != 0) {
             hipEvent_t& slot_ev = e->tev[e->tev_next % wax_hip_engine::kTimingRing];
@@ -118,22 +141,10 @@ int enqueue_scan(wax_hip_engine* e, const float* d_query, float q_norm, int k_ef
         if (merged) e->st_merged_scans++;
         if (out_flagged) *out_flagged = merged && done_flag != nullptr;   // the kernel itself publishes the completion word
         if (!merged) {
-            // 64 < k <= 192 (no k-way merge of the heads): the short selection merges the per-workgroup lists — sorts their first few
-            // entries and the prefixes below the k-th of those in LDS, ~15 us where the wave-list merge of grid x k keys takes 100 - 350
-            // (1M rows, top-192, blocking: 0.60 -> 0.3 ms). Lists of k entries cannot have dropped a row of the answer: no
-            // certificate; the merge kernel stays behind it, gated, for prefixes that overflow the LDS buffer (flag words: the
-            // ticket's cache line behind the lists).
-            uint32_t* short_flags = nullptr;
-            if (e->select_short.load() != 0 && k_eff > SCAN_KWAY_MAX_K && select_short_viable(k_eff, grid, k_eff)) {
-                short_flags = partials_ticket(d_partials) + 8;
-                HIP_TRY(launch_select_short(d_partials, (uint32_t)grid, (uint32_t)k_eff, k_eff, kpad, e->d_ids, a.row_base, a.n_rows,
-                                            short_flags, d_hits, stream),
-                        WAX_HIP_ERR_INTERNAL, "short merge launch");
-                e->st_short_selects++;
-            }
-            HIP_TRY(launch_merge_keys(d_partials, (uint32_t)grid * (uint32_t)k_eff, k_eff, kpad, e->d_ids, a.row_base,
-                                      a.n_rows, d_hits, cap, stream, short_flags),
-                    WAX_HIP_ERR_INTERNAL, "merge kernel launch");
+            bool short_selected = false;
+            const int mrc = enqueue_list_merge(e, d_partials, grid, k_eff, kpad, cap, a.row_base, a.n_rows, d_hits, stream, &short_selected);
+            if (mrc != WAX_HIP_OK) return mrc;
+            if (short_selected) e->st_short_selects++;
         }
     } else {
         if (!general_slot) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "top_k too large for the device-resident shard path (max 192)");
@@ -160,7 +171,7 @@ int enqueue_scan(wax_hip_engine* e, const float* d_query, float q_norm, int k_ef
             f.k = per_list; f.kpad = per_list; f.merge_out = nullptr; f.arrive = nullptr; f.done_flag = nullptr; f.query_host = nullptr;
             int lists = 0;
             if (bound) launch_timing() = LaunchTiming{ev0, ev1};
-            const hipError_t ferr = launch_scan(f, e->metric, 0, per_list <= 64 ? 128 : 256, false, (int)e->grid_blocks.load(), stream, &lists);
+            const hipError_t ferr = launch_scan(f, e->metric, 0, wave_list_cap(per_list), false, (int)e->grid_blocks.load(), stream, &lists);
             launch_timing() = LaunchTiming{};
             HIP_TRY(ferr, WAX_HIP_ERR_INTERNAL, "scan kernel launch");
             if (ev1 && !bound) HIP_TRY(hipEventRecord(ev1, stream), WAX_HIP_ERR_INTERNAL, "event record");

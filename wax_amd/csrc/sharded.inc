@@ -1146,16 +1146,14 @@ int sh_search_batch_hits(wax_hip_engine* e, const float* queries, uint32_t nq, u
     for (size_t i = 0; i < (size_t)nq * stride; ++i) out_hits[i] = wax_hip_hit{KEY_PAD, ID_PAD};
     if (stride == 0 || nq == 0) return WAX_HIP_OK;
     if (dims != e->dims) return fail(WAX_HIP_ERR_DIM_MISMATCH, dim_mismatch_msg(e->dims, dims));
-    const bool holder = holding(e) > 0;
-    e->lock.lock_shared(holder);
-    struct Unlock { RWLock& l; ~Unlock() { l.unlock_shared(); } } unlock{e->lock};
+    ReadGuard rd(e);
     const uint64_t total = sh_count(s);
     if (total == 0) return WAX_HIP_OK;
     uint32_t k = (uint32_t)clamp_topk(top_k);
     if (k > stride) k = stride;
     if ((uint64_t)k > total) k = (uint32_t)total;
     ShardBatchWork* w = nullptr;
-    int rc = sh_acquire_bwork(s, &w, holder);
+    int rc = sh_acquire_bwork(s, &w, rd.holder);
     if (rc != WAX_HIP_OK) return rc;
     struct Release { ShardedState* s; ShardBatchWork* w; ~Release() { sh_release_bwork(s, w); } } release{s, w};
     DeviceGuard dg(s->devices[0]);
@@ -1188,20 +1186,33 @@ int sh_search_batch_hits(wax_hip_engine* e, const float* queries, uint32_t nq, u
 
 // ---- filtered search: every shard pre-filters its own rows; the shards are in global row order, so a stable merge by
 // (score desc, shard asc) is the (distance asc, global row asc) order of one engine -------------------------------------
+struct ShardAnswer { const uint64_t* ids; const float* scores; uint32_t n; };
+
+// The shards' answers to one query, in shard order -> the handle's: stable by score descending, so (shard, position) order is kept on
+// ties, then the cut at `limit` and the caller's capacity. Returns the results written.
+struct ShardHit { float score; uint64_t id; };
+static uint32_t merge_shard_results(const std::vector<ShardAnswer>& parts, uint32_t limit, uint32_t capacity, uint64_t* out_ids, float* out_scores,
+                                    std::vector<ShardHit>& all) {   // `all`: scratch, reused by a caller that merges many queries
+    all.clear();
+    for (const ShardAnswer& p : parts)
+        for (uint32_t i = 0; i < p.n; ++i) all.push_back(ShardHit{p.scores[i], p.ids[i]});
+    std::stable_sort(all.begin(), all.end(), [](const ShardHit& a, const ShardHit& b) { return a.score > b.score; });
+    uint32_t m = 0;
+    for (; m < all.size() && m < limit && m < capacity; ++m) { out_ids[m] = all[m].id; out_scores[m] = all[m].score; }
+    return m;
+}
+
 // One query on a handle: every shard answers on its own rows at the same time (persistent per-shard workers) through `per_shard`
-// (shard engine, ids, scores, capacity, count) — the filtered or the predicate search — and the host merges: stable by score, so
-// (shard, position) order is kept on ties, then the cut at clamp(top_k) and the caller's capacity.
+// (shard engine, ids, scores, capacity, count) — the filtered or the predicate search — and the host merges them
+// (merge_shard_results) under the cut at clamp(top_k) and the caller's capacity.
 template <typename PerShard>
 static int sh_fanout_filtered(wax_hip_engine* e, uint32_t dims, int32_t top_k, uint64_t* out_ids, float* out_scores, uint32_t capacity,
                               uint32_t* out_count, PerShard per_shard) {
     ShardedState* s = e->sh;
     *out_count = 0;
     if (dims != e->dims) return fail(WAX_HIP_ERR_DIM_MISMATCH, dim_mismatch_msg(e->dims, dims));
-    e->lock.lock_shared(holding(e) > 0);
-    struct Unlock { RWLock& l; ~Unlock() { l.unlock_shared(); } } unlock{e->lock};
+    ReadGuard rd(e);
     const uint32_t limit = (uint32_t)clamp_topk(top_k);
-    struct Hit { float score; uint32_t shard; uint32_t pos; uint64_t id; };
-    std::vector<Hit> all;
     const size_t G = s->subs.size();
     std::vector<std::vector<uint64_t>> g_ids(G, std::vector<uint64_t>(limit));
     std::vector<std::vector<float>> g_scores(G, std::vector<float>(limit));
@@ -1213,14 +1224,13 @@ static int sh_fanout_filtered(wax_hip_engine* e, uint32_t dims, int32_t top_k, u
         if (rcs[g] != WAX_HIP_OK) errs[g] = g_last_error;   // thread-local: carry it to the caller
     };
     if (G == 1) one(0); else s->workers.run_all(one);
+    std::vector<ShardAnswer> parts(G);
     for (size_t g = 0; g < G; ++g) {
         if (rcs[g] != WAX_HIP_OK) return fail(rcs[g], errs[g]);
-        for (uint32_t i = 0; i < g_m[g]; ++i) all.push_back(Hit{g_scores[g][i], (uint32_t)g, i, g_ids[g][i]});
+        parts[g] = ShardAnswer{g_ids[g].data(), g_scores[g].data(), g_m[g]};
     }
-    std::stable_sort(all.begin(), all.end(), [](const Hit& a, const Hit& b) { return a.score > b.score; });   // stable: (shard, position) order kept on ties
-    uint32_t m = 0;
-    for (size_t i = 0; i < all.size() && m < limit && m < capacity; ++i, ++m) { out_ids[m] = all[i].id; out_scores[m] = all[i].score; }
-    *out_count = m;
+    std::vector<ShardHit> scratch;
+    *out_count = merge_shard_results(parts, limit, capacity, out_ids, out_scores, scratch);
     return WAX_HIP_OK;
 }
 
@@ -1278,8 +1288,7 @@ int sh_set_attributes(wax_hip_engine* e, const uint64_t* frame_ids, const int64_
 
 int sh_get_attributes(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, int64_t* out_ts, uint32_t* out_flags, uint8_t* out_found) {
     ShardedState* s = e->sh;
-    e->lock.lock_shared(holding(e) > 0);
-    struct Unlock { RWLock& l; ~Unlock() { l.unlock_shared(); } } unlock{e->lock};
+    ReadGuard rd(e);
     const size_t G = s->subs.size();
     std::vector<std::vector<uint64_t>> ids(G), at(G);
     for (uint64_t i = 0; i < n; ++i) {
@@ -1318,8 +1327,7 @@ int sh_search_batch_filtered(wax_hip_engine* e, const float* queries, uint32_t n
     ShardedState* s = e->sh;
     if (dims != e->dims) return fail(WAX_HIP_ERR_DIM_MISMATCH, dim_mismatch_msg(e->dims, dims));
     if (out_stride == 0) return WAX_HIP_OK;
-    e->lock.lock_shared(holding(e) > 0);
-    struct Unlock { RWLock& l; ~Unlock() { l.unlock_shared(); } } unlock{e->lock};
+    ReadGuard rd(e);
     const uint32_t limit = (uint32_t)clamp_topk(top_k);
     const size_t G = s->subs.size();
     std::vector<std::vector<uint64_t>> g_ids(G, std::vector<uint64_t>((size_t)nq * limit));
@@ -1335,23 +1343,14 @@ int sh_search_batch_filtered(wax_hip_engine* e, const float* queries, uint32_t n
     if (G == 1) one(0); else s->workers.run_all(one);
     for (size_t g = 0; g < G; ++g)
         if (rcs[g] != WAX_HIP_OK) return fail(rcs[g], errs[g]);
-    struct Hit { float score; uint64_t id; };
-    std::vector<Hit> all;
+    std::vector<ShardAnswer> parts(G);
+    std::vector<ShardHit> scratch;
     for (uint32_t q = 0; q < nq; ++q) {
-        all.clear();
-        for (size_t g = 0; g < G; ++g)
-            for (uint32_t i = 0; i < g_m[g][q]; ++i) all.push_back(Hit{g_scores[g][(size_t)q * limit + i], g_ids[g][(size_t)q * limit + i]});
-        std::stable_sort(all.begin(), all.end(), [](const Hit& a, const Hit& b) { return a.score > b.score; });
-        uint32_t m = 0;
+        for (size_t g = 0; g < G; ++g) parts[g] = ShardAnswer{g_ids[g].data() + (size_t)q * limit, g_scores[g].data() + (size_t)q * limit, g_m[g][q]};
         uint64_t* ids = out_ids + (size_t)q * out_stride;
         float* scores = out_scores + (size_t)q * out_stride;
-        for (size_t i = 0; i < all.size() && m < limit && m < out_stride; ++i, ++m) { ids[m] = all[i].id; scores[m] = all[i].score; }
-        if (min_scores) {   // `score < minScore` drops a candidate (NaN: no cut)
-            uint32_t keep = 0;
-            for (uint32_t i = 0; i < m; ++i)
-                if (!(scores[i] < min_scores[q])) { ids[keep] = ids[i]; scores[keep] = scores[i]; ++keep; }
-            m = keep;
-        }
+        uint32_t m = merge_shard_results(parts, limit, out_stride, ids, scores, scratch);
+        if (min_scores) apply_min_score(min_scores[q], ids, scores, &m);
         out_counts[q] = m;
     }
     return WAX_HIP_OK;
@@ -1361,8 +1360,7 @@ int sh_search_batch_filtered(wax_hip_engine* e, const float* queries, uint32_t n
 
 int sh_serialize(wax_hip_engine* e, uint8_t** out_bytes, size_t* out_len) {
     ShardedState* s = e->sh;
-    e->lock.lock_shared(holding(e) > 0);                                   // withReadLock (MetalVectorEngine.swift:683)
-    struct Unlock { RWLock& l; ~Unlock() { l.unlock_shared(); } } unlock{e->lock};
+    ReadGuard rd(e);                                                        // withReadLock (MetalVectorEngine.swift:683)
     for (auto* sub : s->subs) { const int frc = flush_pending(sub); if (frc != WAX_HIP_OK) return frc; }
     const uint64_t n = sh_count(s);
     const uint64_t vec_bytes = n * (uint64_t)e->dims * 4ull, id_bytes = n * 8ull;

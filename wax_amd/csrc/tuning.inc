@@ -242,7 +242,7 @@ int wax_hip_time_scan_kernel(wax_hip_engine* e, const float* query, uint32_t dim
         a.store = e->d_store; a.query = s->d_query; a.partials = s->d_partials; a.dist_out = nullptr;
         a.n_rows = (uint32_t)e->count; a.row_base = (uint32_t)e->row_base; a.dims = e->dims; a.k = k_eff;
         a.q_norm = query_norm(query, dims);
-        const int cap = k_eff <= 64 ? 128 : 256;
+        const int cap = wave_list_cap(k_eff);
         hipError_t err = hipMemcpyAsync(s->d_query, s->h_query, (size_t)dims * sizeof(float), hipMemcpyHostToDevice, s->stream);
         int grid = 0;
         for (int wu = 0; wu < 2 && err == hipSuccess; ++wu)
