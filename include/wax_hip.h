@@ -335,6 +335,25 @@ int wax_hip_search_batch_filtered(wax_hip_engine* e, const float* queries, uint3
                                   const float* min_scores,
                                   uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts);
 
+/* One query each against MANY stores of one device, in one pass: pair i is (engines[i], queries + i * dims). It stands in for
+ * VectorSearchEngine.search(vector:topK:) called once per store by a host that serves one store per user or agent: a vec segment is
+ * capped at 256 MiB (Constants.swift:49: at most 174 762 rows at 384-d), so one device holds hundreds of stores and its traffic is one
+ * query each against many of them — per store a call of its own pays its own upload, launch, completion and download.
+ * Row i of the outputs (at i * out_stride, out_counts[i] results) equals wax_hip_search(engines[i], query i, dims, top_k, ...) with
+ * out_capacity = out_stride: ids and scores bit for bit, ties in ascending row order, the same top_k clamp. An engine may be listed
+ * any number of times (its queries share passes over its store, up to 16 per pass); an empty engine gives count 0; n == 0 returns
+ * WAX_HIP_OK and touches nothing. Refused before any lock is taken or anything is launched, outputs untouched, the pair's index in
+ * wax_hip_last_error(): a NULL entry, a sharded handle, engines on different devices or of different metrics
+ * (WAX_HIP_ERR_INVALID_ARGUMENT); an engine whose dimensions != dims (WAX_HIP_ERR_DIM_MISMATCH, wax_hip_search's message).
+ * One snapshot: the shared locks of all distinct engines are held together for the call (taken in ascending address order of the
+ * handles; re-entrant for a thread that holds tickets), and rows staged by wax_hip_add just before the call are seen.
+ * Pairs whose engine holds at most "search_many_max_rows" rows, at the specialised dimensions and top_k <= 192 (<= 60 from 512-d
+ * up), are scored by ONE launch for all their stores, merged by one more, downloaded and synchronised once; every
+ * other pair, and every pair of an engine with "search_many" 0 or "force_general" set, runs the single-query search under the same
+ * locks. */
+int wax_hip_search_many(wax_hip_engine* const* engines, const float* queries, uint32_t n, uint32_t dims, int32_t top_k,
+                        uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts);
+
 /* ---- per-row attributes and the predicate search ------------------------------------------------------------ *
  * passesFrameFilter (UnifiedSearch.swift:1241-1258) also drops vector-lane candidates by per-frame metadata: request.timeRange
  * against FrameMeta.timestamp (TimeRange.contains, SearchRequest.swift:91-105), status == .deleted, supersededBy != nil and
@@ -436,7 +455,11 @@ int wax_hip_stats(wax_hip_engine* e, wax_hip_stats_t* out);
  *   "filter_device_min" (wax_hip_search_filtered: allow-lists at least this long are resolved by the id -> row table in HBM, default 4096; -1 = never),
  *   "filter_batch" (wax_hip_search_batch_filtered: 1 (default) = one gather pass for all allow-lists; 0 = the single-query filtered path
  *   per query), "filter_batch_queries" / "filter_batch_fallbacks" (read-only: listed queries answered by the gather pass / by the
- *   per-query path).
+ *   per-query path),
+ *   "search_many" (wax_hip_search_many: 1 (default) = this engine's pairs may share the call's pooled launch; 0 = each runs the
+ *   single-query search), "search_many_max_rows" (engines holding more rows than this always take the single-query search; default
+ *   262144, the first power of two above the vec segment cap at 384-d), "search_many_pooled" / "search_many_looped" (read-only: pairs
+ *   of this engine answered by the pooled launch / by the single-query search).
  * batched queries (bf16 MFMA GEMM + fused selection + exact re-score; exact answers whatever the setting)
  *   "batch_mode" (0 = never use the MFMA path), "batch_min" (smallest batch that may use it, default 1; below 16 queries a cost model
  *   picks between one GEMM pass over the bf16 mirror and nq f32 scans), "batch_workspaces" (concurrent batched searches per engine, default 4),

@@ -137,4 +137,23 @@ class VectorEngine {
     wax_hip_engine* h_ = nullptr;
 };
 
+/// One query each against many stores of one device in one pass (wax_hip_search_many): pair i is (engines[i], row i of `queries`,
+/// row-major engines.size() x dims). Returns per pair [(frameId, score)], each what engines[i]->search(query i, topK) returns.
+inline std::vector<std::vector<std::pair<uint64_t, float>>> searchMany(const std::vector<VectorEngine*>& engines,
+                                                                       const std::vector<float>& queries, int topK) {
+    const uint32_t n = (uint32_t)engines.size();
+    const uint32_t dims = n ? (uint32_t)(queries.size() / n) : 0;
+    const uint32_t stride = wax_hip_result_capacity(topK);
+    std::vector<wax_hip_engine*> raw(n);
+    for (uint32_t i = 0; i < n; ++i) raw[i] = engines[i] ? engines[i]->raw() : nullptr;
+    std::vector<uint64_t> ids((size_t)n * stride);
+    std::vector<float> scores((size_t)n * stride);
+    std::vector<uint32_t> counts(n);
+    check(wax_hip_search_many(raw.data(), queries.data(), n, dims, topK, ids.data(), scores.data(), stride, counts.data()));
+    std::vector<std::vector<std::pair<uint64_t, float>>> out(n);
+    for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back(ids[(size_t)i * stride + j], scores[(size_t)i * stride + j]);
+    return out;
+}
+
 }  // namespace wax_hip

@@ -5,8 +5,10 @@
 
 // try_only: never block waiting for a scratch slot (returns kSlotBusy) — used by callers that already hold
 // tickets, which must collect one instead of waiting (two such callers would starve each other).
+// caller_locked: the caller already holds the engine's shared lock and has flushed pending rows (wax_hip_search_many runs one
+// snapshot over many engines): the ticket then owns no lock — it is collected with caller_locked too, inside the same scope.
 static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, uint64_t* out_ticket,
-                       bool try_only);
+                       bool try_only, bool caller_locked = false);
 
 int wax_hip_search_submit(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, uint64_t* out_ticket) {
     if (e && e->sh) return sh_submit(e, query, dims, top_k, out_ticket);
@@ -14,11 +16,13 @@ int wax_hip_search_submit(wax_hip_engine* e, const float* query, uint32_t dims, 
 }
 
 static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, uint64_t* out_ticket,
-                       bool try_only) {
+                       bool try_only, bool caller_locked) {
     if (!e || !out_ticket) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine/ticket is null");
     DeviceGuard g(e->device);
-    e->lock.lock_shared(holding(e) > 0);             // withReadLock (:447)
-    { const int frc = flush_pending(e); if (frc != WAX_HIP_OK) { e->lock.unlock_shared(); return frc; } }   // staged single-frame appends reach HBM here
+    if (!caller_locked) {
+        e->lock.lock_shared(holding(e) > 0);             // withReadLock (:447)
+        { const int frc = flush_pending(e); if (frc != WAX_HIP_OK) { e->lock.unlock_shared(); return frc; } }   // staged single-frame appends reach HBM here
+    }
     bool others_in_flight = false;                     // uncollected single-query tickets of this engine, whoever holds them
     { std::unique_lock<std::mutex> tg(e->slot_mu); others_in_flight = !e->tickets.empty(); }
     Slot* s = nullptr;
@@ -112,7 +116,7 @@ static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int
     } while (0);
     if (rc != WAX_HIP_OK) {
         if (s) { (void)hipStreamSynchronize(s->stream); release_slot(e, s); }
-        e->lock.unlock_shared();
+        if (!caller_locked) e->lock.unlock_shared();
         return rc;
     }
     {
@@ -122,13 +126,13 @@ static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int
         *out_ticket = t;
     }
     note_submit(e, s);
-    return WAX_HIP_OK;  // shared lock stays held until collect
+    return WAX_HIP_OK;  // shared lock stays held until collect (caller_locked: until the caller's scope ends)
 }
 
 // Shared tail of collect: either converts to (ids, scores) or hands back the raw hits (padded to kcap).
 // `capacity`: entries the (ids, scores) arrays hold; `hits_cap`: entries of out_hits (every one is written).
 static int collect_impl(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, float* out_scores, uint32_t capacity,
-                        uint32_t* out_count, wax_hip_hit* out_hits, uint32_t hits_cap);
+                        uint32_t* out_count, wax_hip_hit* out_hits, uint32_t hits_cap, bool caller_locked = false);
 
 int wax_hip_search_collect(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, float* out_scores, uint32_t out_capacity,
                            uint32_t* out_count) {
@@ -137,7 +141,7 @@ int wax_hip_search_collect(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids
 }
 
 static int collect_impl(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, float* out_scores, uint32_t capacity,
-                        uint32_t* out_count, wax_hip_hit* out_hits, uint32_t hits_cap) {
+                        uint32_t* out_count, wax_hip_hit* out_hits, uint32_t hits_cap, bool caller_locked) {
     if (!e || !out_count) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine/out_count is null");
     DeviceGuard g(e->device);
     Slot* s = nullptr;
@@ -242,7 +246,7 @@ static int collect_impl(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, f
     }
     note_collect(e, s);
     release_slot(e, s);
-    e->lock.unlock_shared();
+    if (!caller_locked) e->lock.unlock_shared();   // (a ticket submitted with caller_locked never took it)
     return rc;
 }
 

@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -42,6 +43,7 @@ using namespace wax;
 //   api_fusion_filter.inc  C ABI: reciprocal-rank fusion
 //   api_predicate.inc      C ABI: per-row attributes (set / get) and their device columns
 //   filter_host.inc        C ABI: the filtered searches — one query with an allow-list and / or a row predicate (one locked body), the batched allow-list form
+//   search_many.inc        C ABI: wax_hip_search_many — one query each against many stores of one device under one snapshot, the eligible pairs in one pooled launch
 //   codec.inc              C ABI: MV2V encoding-2 serialize / deserialize (MetalVectorEngine.swift:682-815)
 //   tuning.inc             C ABI: stats, the tuning registry (set / get), the two timing microbenchmarks
 //   sharded.inc            the multi-GPU handle (one engine per device behind one handle): DESIGN 4.3
@@ -57,6 +59,7 @@ using namespace wax;
 #include "api_fusion_filter.inc"
 #include "api_predicate.inc"
 #include "filter_host.inc"
+#include "search_many.inc"
 #include "codec.inc"
 #include "tuning.inc"
 }  // extern "C"

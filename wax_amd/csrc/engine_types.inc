@@ -555,6 +555,12 @@ struct wax_hip_engine {
     std::atomic<uint64_t> st_filter_device{0};    // filtered searches whose allow-list was resolved on the device
     std::atomic<int64_t> filter_batch{1};         // wax_hip_search_batch_filtered: 1 = one gather pass for all lists, 0 = the per-query loop
     std::atomic<uint64_t> st_filter_batch_queries{0}, st_filter_batch_fallbacks{0};
+    // wax_hip_search_many (DESIGN 4.8): 1 = this engine's pairs may share the pooled launch, 0 = each takes the single-query search;
+    // stores above search_many_max_rows rows always do. 262 144 = the first power of two above the vec segment cap at 384-d
+    // (a placeholder until tools/search_many_bench.py has been run: DESIGN 4.8).
+    std::atomic<int64_t> search_many{1};
+    std::atomic<int64_t> search_many_max_rows{262144};
+    std::atomic<uint64_t> st_many_pooled{0}, st_many_looped{0};   // pairs of this engine answered by the pooled launch / by the single-query search
     // Write-combining of single-frame appends (the reference appends into a unified-memory buffer and the GPU simply
     // sees it, MetalVectorEngine.swift:340-351; with discrete HBM the analogue is a pinned staging area that the NEXT
     // reader — or a full staging area — uploads in one copy). The last `pend_rows` rows of [0, count) live only here.

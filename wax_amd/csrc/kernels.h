@@ -201,6 +201,22 @@ struct ScanMultiArgs {
     const GatherGroup* groups;
     const uint32_t* item_group;   // [n_items] work item -> group
 };
+// One group of the many-stores form (launch_scan_multi_pooled; wax_hip_search_many): up to scan_multi_group() queries against ONE of
+// the call's stores, whose rows [0, n_rows) are scanned contiguously by the group's n_items work items.
+struct PoolGroup {
+    const float* store;    // [n_rows][dims] f32: the group's own store
+    uint32_t n_rows;
+    uint32_t row_base;     // key of local row r: row_base + r
+    uint32_t q0, nq;       // its queries are qlist[q0 .. q0 + nq) (norms q_norm[q0 ..])
+    uint32_t part_off;     // partial list of query slot qi, share w: partials[(part_off + qi * n_items + w) * k ..]
+    uint32_t item0;        // its first work item
+    uint32_t n_items;      // workgroups (work items) that share the store
+    uint32_t pad;
+};
+struct ScanPoolArgs {
+    ScanMultiArgs a;       // queries, qlist, q_norm, partials, dims, k, item_group; store / n_rows / row_base / nq come from the group
+    const PoolGroup* pool;
+};
 bool scan_multi_dims(uint32_t dims);                    // dims the kernel is specialised for (= launch_scan's table)
 uint32_t scan_multi_group(uint32_t dims, int k);        // queries per launch (0: not served — k > 192, other dims, lists too large for LDS)
 int scan_multi_grid(uint32_t n_rows, uint32_t dims, int grid_cap);   // workgroups launch_scan_multi will use
@@ -208,9 +224,20 @@ hipError_t launch_scan_multi(const ScanMultiArgs& a, int metric, int grid_cap, h
 // Gather form: one launch, n_items workgroups, every group's queries scored on its listed rows only (nq / n_rows unused).
 uint32_t scan_multi_listed_items(uint64_t max_rows, uint32_t dims, int grid_cap);   // work items for a list of at most max_rows rows
 hipError_t launch_scan_multi_listed(const ScanMultiArgs& a, int metric, uint32_t n_items, hipStream_t stream);
+// Many-stores form: one launch, n_items workgroups, work item -> group -> store (a.store / n_rows / row_base / nq / rows unused).
+uint64_t scan_multi_chunks(uint32_t n_rows, uint32_t dims);                              // chunks (a wave's unit of rows) in n_rows
+uint32_t scan_multi_pooled_items(uint32_t n_rows, uint32_t dims, uint32_t share);        // work items of a store allowed `share` of the launch
+hipError_t launch_scan_multi_pooled(const ScanMultiArgs& a, const PoolGroup* d_pool, int metric, uint32_t n_items, hipStream_t stream);
 // Per query b < nq: the d_spans[2b + 1] lists of k keys at d_in + d_spans[2b] * k -> row b of d_out (out_stride hits, padded).
 hipError_t launch_merge_keys_spans(const int64_t* d_in, const uint32_t* d_spans, int k, const uint64_t* d_ids, uint32_t row_base,
                                    uint32_t n_rows, wax_hip_hit* d_out, uint32_t out_stride, uint32_t nq, hipStream_t stream);
+// The span merge with a store PER QUERY: query b's keys are rows of d_stores[b] (its id table, key base and row count).
+struct MergeStore {
+    const uint64_t* ids;   // frame ids by local row (may be null)
+    uint32_t row_base, n_rows;
+};
+hipError_t launch_merge_keys_stores(const int64_t* d_in, const uint32_t* d_spans, const MergeStore* d_stores, int k, wax_hip_hit* d_out,
+                                    uint32_t out_stride, uint32_t nq, hipStream_t stream);
 // Per query b < nq: the n_lists lists of k keys at d_in + b * n_lists * k -> the k smallest as hits (frame ids attached) in
 // row (d_qlist ? d_qlist[b] : b) of d_out_base, rows out_stride hits wide and padded to it.
 hipError_t launch_merge_keys_multi(const int64_t* d_in, uint32_t n_lists, int k, const uint64_t* d_ids, uint32_t row_base,

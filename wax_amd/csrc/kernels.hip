@@ -435,25 +435,11 @@ hipError_t launch_scan(const ScanArgs& args, int metric, int variant, int cap, b
 //   stage 2: the <= k surviving lists (k*k keys) go through the same wave-private selection,
 //            the workgroup rank-merges, and frame ids are looked up.
 // 10 240 keys (1024 workgroups, k = 10) cost ~1 push + 1 prune per wave instead of ~10 + 4.
+// (the body, shared by merge_keys_kernel and merge_keys_stores_kernel: `in` / `out` already point at this workgroup's lists and row)
 template <int CAP>
-__global__ __launch_bounds__(MERGE_THREADS) void merge_keys_kernel(const int64_t* __restrict__ in, uint32_t n_lists,
-                                                                   int k, int kpad,
-                                                                   const uint64_t* __restrict__ ids,
-                                                                   uint32_t row_base, uint32_t n_rows,
-                                                                   wax_hip_hit* __restrict__ out,
-                                                                   const uint32_t* __restrict__ qlist, uint32_t out_stride,
-                                                                   const uint32_t* __restrict__ gate,
-                                                                   const uint32_t* __restrict__ spans = nullptr) {
-    __shared__ int64_t lds[MERGE_WAVES * CAP + MERGE_WAVES + 2 * FUSED_MAX_K + 1];
-    if (gate != nullptr && *gate == 0u) return;               // the short selection in front of this launch answered
-    // one workgroup per query (launch_merge_keys_multi / _spans); the single-query launch has one workgroup and out_stride = 0
-    if (spans != nullptr) {
-        in += (size_t)spans[2 * blockIdx.x] * (uint32_t)k;
-        n_lists = spans[2 * blockIdx.x + 1];
-    } else {
-        in += (size_t)blockIdx.x * n_lists * (uint32_t)k;
-    }
-    out += (size_t)(qlist ? qlist[blockIdx.x] : blockIdx.x) * out_stride;
+__device__ __forceinline__ void merge_keys_body(int64_t* lds, const int64_t* __restrict__ in, uint32_t n_lists, int k, int kpad,
+                                                const uint64_t* __restrict__ ids, uint32_t row_base, uint32_t n_rows,
+                                                wax_hip_hit* __restrict__ out) {
     int* counts = reinterpret_cast<int*>(lds + MERGE_WAVES * CAP);
     int64_t* fin = lds + MERGE_WAVES * CAP + MERGE_WAVES;
     int* sel = reinterpret_cast<int*>(fin + FUSED_MAX_K);           // FUSED_MAX_K list indices
@@ -528,6 +514,41 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_keys_kernel(const int64_t
     }
 }
 
+template <int CAP>
+__global__ __launch_bounds__(MERGE_THREADS) void merge_keys_kernel(const int64_t* __restrict__ in, uint32_t n_lists,
+                                                                   int k, int kpad,
+                                                                   const uint64_t* __restrict__ ids,
+                                                                   uint32_t row_base, uint32_t n_rows,
+                                                                   wax_hip_hit* __restrict__ out,
+                                                                   const uint32_t* __restrict__ qlist, uint32_t out_stride,
+                                                                   const uint32_t* __restrict__ gate,
+                                                                   const uint32_t* __restrict__ spans = nullptr) {
+    __shared__ int64_t lds[MERGE_WAVES * CAP + MERGE_WAVES + 2 * FUSED_MAX_K + 1];
+    if (gate != nullptr && *gate == 0u) return;               // the short selection in front of this launch answered
+    // one workgroup per query (launch_merge_keys_multi / _spans); the single-query launch has one workgroup and out_stride = 0
+    if (spans != nullptr) {
+        in += (size_t)spans[2 * blockIdx.x] * (uint32_t)k;
+        n_lists = spans[2 * blockIdx.x + 1];
+    } else {
+        in += (size_t)blockIdx.x * n_lists * (uint32_t)k;
+    }
+    out += (size_t)(qlist ? qlist[blockIdx.x] : blockIdx.x) * out_stride;
+    merge_keys_body<CAP>(lds, in, n_lists, k, kpad, ids, row_base, n_rows, out);
+}
+
+// The span form with a store per query (wax_hip_search_many): workgroup b merges its span of lists and attaches frame ids from
+// stores[b]'s own table — the same key means different rows in different stores.
+template <int CAP>
+__global__ __launch_bounds__(MERGE_THREADS) void merge_keys_stores_kernel(const int64_t* __restrict__ in, int k, int kpad,
+                                                                          wax_hip_hit* __restrict__ out, uint32_t out_stride,
+                                                                          const uint32_t* __restrict__ spans,
+                                                                          const MergeStore* __restrict__ stores) {
+    __shared__ int64_t lds[MERGE_WAVES * CAP + MERGE_WAVES + 2 * FUSED_MAX_K + 1];
+    const MergeStore s = stores[blockIdx.x];
+    merge_keys_body<CAP>(lds, in + (size_t)spans[2 * blockIdx.x] * (uint32_t)k, spans[2 * blockIdx.x + 1], k, kpad, s.ids, s.row_base, s.n_rows,
+                         out + (size_t)blockIdx.x * out_stride);
+}
+
 hipError_t launch_merge_keys(const int64_t* d_in, uint32_t n_in, int k, int kpad, const uint64_t* d_ids,
                              uint32_t row_base, uint32_t n_rows, wax_hip_hit* d_out, int cap, hipStream_t st, const uint32_t* gate) {
     if (k > FUSED_MAX_K || k < 1 || kpad < k || n_in % (uint32_t)k != 0) return hipErrorInvalidValue;
@@ -563,6 +584,18 @@ hipError_t launch_merge_keys_spans(const int64_t* d_in, const uint32_t* d_spans,
     else
         hipLaunchKernelGGL((merge_keys_kernel<256>), dim3(nq), dim3(MERGE_THREADS), 0, st, d_in, 0u, k, (int)out_stride, d_ids,
                            row_base, n_rows, d_out, (const uint32_t*)nullptr, out_stride, (const uint32_t*)nullptr, d_spans);
+    return hipGetLastError();
+}
+
+hipError_t launch_merge_keys_stores(const int64_t* d_in, const uint32_t* d_spans, const MergeStore* d_stores, int k, wax_hip_hit* d_out,
+                                    uint32_t out_stride, uint32_t nq, hipStream_t st) {
+    if (k > FUSED_MAX_K || k < 1 || out_stride < (uint32_t)k || nq == 0 || !d_spans || !d_stores) return hipErrorInvalidValue;
+    if (k <= 64)
+        hipLaunchKernelGGL((merge_keys_stores_kernel<128>), dim3(nq), dim3(MERGE_THREADS), 0, st, d_in, k, (int)out_stride, d_out, out_stride,
+                           d_spans, d_stores);
+    else
+        hipLaunchKernelGGL((merge_keys_stores_kernel<256>), dim3(nq), dim3(MERGE_THREADS), 0, st, d_in, k, (int)out_stride, d_out, out_stride,
+                           d_spans, d_stores);
     return hipGetLastError();
 }
 

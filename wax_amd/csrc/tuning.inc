@@ -69,6 +69,8 @@ int wax_hip_set_tuning(wax_hip_engine* e, const char* key, int64_t value) {
     else if (k == "share_timing") e->share_timing = value != 0;   // 0: every chained scan records its own start event (one more packet between scans)
     else if (k == "filter_batch") { if (value < 0 || value > 1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "filter_batch must be 0 or 1"); e->filter_batch = value; }
     else if (k == "filter_device_min") { if (value < -1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "filter_device_min must be >= -1"); e->filter_device_min = value; }
+    else if (k == "search_many") { if (value < 0 || value > 1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "search_many must be 0 or 1"); e->search_many = value; }
+    else if (k == "search_many_max_rows") { if (value < 0 || value > 0xffffffffll) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "search_many_max_rows must be 0..4294967295"); e->search_many_max_rows = value; }
     else if (k == "predicate_route") { if (value < 0 || value > 2) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "predicate_route must be 0 (auto), 1 (gather) or 2 (masked scan)"); e->predicate_route = value; }
     else if (k == "predicate_scan_min_permille") { if (value < 0 || value > 1001) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "predicate_scan_min_permille must be 0..1001"); e->predicate_scan_min_permille = value; }
     else if (k == "compact_window_rows") { if (value < 0 || value > 0xffffffffll) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "compact_window_rows must be 0 (what the bounce buffer holds) .. 4294967295"); e->compact_window_rows = value; }
@@ -208,6 +210,10 @@ int64_t wax_hip_get_tuning(wax_hip_engine* e, const char* key) {
     if (k == "filter_batch") return e->filter_batch.load();
     if (k == "filter_batch_queries") return (int64_t)e->st_filter_batch_queries.load();
     if (k == "filter_batch_fallbacks") return (int64_t)e->st_filter_batch_fallbacks.load();
+    if (k == "search_many") return e->search_many.load();
+    if (k == "search_many_max_rows") return e->search_many_max_rows.load();
+    if (k == "search_many_pooled") return (int64_t)e->st_many_pooled.load();   // pairs of wax_hip_search_many answered by its pooled launch
+    if (k == "search_many_looped") return (int64_t)e->st_many_looped.load();   // ... by the single-query search under the call's lock
     if (k == "batch_queries") return (int64_t)e->st_batch_queries.load();
     if (k == "batch_fallbacks") return (int64_t)e->st_batch_fallbacks.load();
     if (k == "slots") return e->max_slots;

@@ -544,3 +544,27 @@ class HIPVectorEngine:
         ms = ctypes.c_double(0.0)
         raise_for_status(self._lib.wax_hip_time_stream_read(self._h, int(iters), ctypes.byref(ms)))
         return float(ms.value)
+
+
+def searchMany(engines, queries, topK: int):  # noqa: N802,N803
+    """One query each against many stores of one device in one pass (wax_hip_search_many): pair i is (engines[i], queries[i]).
+    Returns (ids, scores, counts) shaped like searchBatch's; row i is what engines[i].search(queries[i], topK) returns. An engine
+    may be listed any number of times. Whatever the C call refuses (a sharded engine, mixed metrics or dimensions) is raised."""
+    engines = list(engines)
+    qs = _as_f32(queries)
+    if qs.ndim != 2 or qs.shape[0] != len(engines):
+        raise EncodingError("searchMany: queries must be [len(engines), dims]")
+    n, width = qs.shape
+    if any(not isinstance(e, HIPVectorEngine) for e in engines):
+        raise TypeError("searchMany: engines must be HIPVectorEngine instances")
+    kcap = max(1, min(clampTopK(topK), max([e.count for e in engines] + [1])))   # row width of the arrays (passed as the stride)
+    ids = np.zeros((n, kcap), dtype=np.uint64)
+    scores = np.zeros((n, kcap), dtype=np.float32)
+    counts = np.zeros(n, dtype=np.uint32)
+    if n == 0:
+        return ids, scores, counts
+    handles = (ctypes.c_void_p * n)(*[e._h.value for e in engines])
+    rc = engines[0]._lib.wax_hip_search_many(handles, _fp(qs), n, width, int(max(min(topK, 2**31 - 1), -2**31)), _u64p(ids), _fp(scores),
+                                             kcap, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+    raise_for_status(rc)
+    return ids, scores, counts
