@@ -398,6 +398,25 @@ int wax_hip_search_predicate(wax_hip_engine* e, const float* query, uint32_t dim
                              int has_allow, const uint64_t* allow_frame_ids, uint64_t n_allow,
                              int has_min_score, float min_score, const wax_hip_row_predicate* pred,
                              uint64_t* out_ids, float* out_scores, uint32_t out_capacity, uint32_t* out_count);
+/* wax_hip_search_many with a row predicate and a score cut PER PAIR — what a host with one store per user needs, since no Wax query
+ * is unfiltered (the default FrameFilter() already drops deleted, superseded and surrogate frames). preds: n entries, or NULL = no
+ * pair has one; min_scores: n entries, or NULL = no cut (NaN = no cut for that pair). Row i equals, bit for bit,
+ * wax_hip_search_predicate(engines[i], query i, dims, top_k, 0, NULL, 0, min_scores != NULL, min_scores[i], &preds[i], ...) with
+ * out_capacity = out_stride: its ids, scores and count, ties in ascending row order, fewer results when fewer rows pass. A pair
+ * whose predicate has no bound and no deny bit is an ordinary wax_hip_search_many pair, and with preds == NULL and
+ * min_scores == NULL the call IS wax_hip_search_many (one body serves both). Refusals (their order, their messages, the pair's
+ * index, outputs untouched), the snapshot (shared locks of all distinct engines in ascending address order, staged rows flushed)
+ * and the routes are wax_hip_search_many's; n == 0 returns WAX_HIP_OK and touches nothing. Allow-lists per pair are NOT part of
+ * this call (wax_hip_search_predicate / wax_hip_search_batch_filtered take them, one store at a time).
+ * Pooled pairs (wax_hip_search_many's rule) of one engine share passes by predicate: the pairs with the same predicate — an unused
+ * bound's value does not count — form groups of up to 16, so queries that share a predicate share a pass. The predicates become row
+ * bitmaps in ONE launch ahead of the pooled scan, which then offers only rows whose bit is set; there is no host round trip for
+ * pass counts, and still one download and one synchronisation per call. A store on which attributes were never set reads as (0, 0)
+ * in every row: its predicates are decided on the host (the pair is unmasked, or its count is 0 without device work). Every other
+ * pair runs the single-query predicate search under the locks the call holds. The cut is applied on the host, whatever the route. */
+int wax_hip_search_many_predicate(wax_hip_engine* const* engines, const float* queries, uint32_t n, uint32_t dims, int32_t top_k,
+                                  const wax_hip_row_predicate* preds, const float* min_scores,
+                                  uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts);
 
 /* ---- persistence: "MV2V" vec segment, encoding 2 ------------------------- */
 
@@ -459,7 +478,8 @@ int wax_hip_stats(wax_hip_engine* e, wax_hip_stats_t* out);
  *   "search_many" (wax_hip_search_many: 1 (default) = this engine's pairs may share the call's pooled launch; 0 = each runs the
  *   single-query search), "search_many_max_rows" (engines holding more rows than this always take the single-query search; default
  *   262144, the first power of two above the vec segment cap at 384-d), "search_many_pooled" / "search_many_looped" (read-only: pairs
- *   of this engine answered by the pooled launch / by the single-query search).
+ *   of this engine answered by the pooled launch / by the single-query search), "search_many_masked" (read-only: pairs of
+ *   wax_hip_search_many_predicate answered by a pooled group that read a row bitmap — a non-empty predicate evaluated on the device).
  * batched queries (bf16 MFMA GEMM + fused selection + exact re-score; exact answers whatever the setting)
  *   "batch_mode" (0 = never use the MFMA path), "batch_min" (smallest batch that may use it, default 1; below 16 queries a cost model
  *   picks between one GEMM pass over the bf16 mirror and nq f32 scans), "batch_workspaces" (concurrent batched searches per engine, default 4),

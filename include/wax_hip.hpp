@@ -156,4 +156,29 @@ inline std::vector<std::vector<std::pair<uint64_t, float>>> searchMany(const std
     return out;
 }
 
+/// searchMany with a row predicate and a score cut per pair (wax_hip_search_many_predicate): `preds` / `minScores` hold one entry per
+/// pair or are empty (no pair has one; a NaN cut means none for that pair). Pair i is what engines[i]->searchPredicate(query i, topK,
+/// nullptr, cut i, pred i) returns.
+inline std::vector<std::vector<std::pair<uint64_t, float>>> searchManyFiltered(const std::vector<VectorEngine*>& engines,
+                                                                               const std::vector<float>& queries, int topK,
+                                                                               const std::vector<wax_hip_row_predicate>& preds,
+                                                                               const std::vector<float>& minScores = {}) {
+    const uint32_t n = (uint32_t)engines.size();
+    const uint32_t dims = n ? (uint32_t)(queries.size() / n) : 0;
+    const uint32_t stride = wax_hip_result_capacity(topK);
+    if ((!preds.empty() && preds.size() != n) || (!minScores.empty() && minScores.size() != n))
+        throw std::invalid_argument("searchManyFiltered: one predicate / score cut per pair, or none");
+    std::vector<wax_hip_engine*> raw(n);
+    for (uint32_t i = 0; i < n; ++i) raw[i] = engines[i] ? engines[i]->raw() : nullptr;
+    std::vector<uint64_t> ids((size_t)n * stride);
+    std::vector<float> scores((size_t)n * stride);
+    std::vector<uint32_t> counts(n);
+    check(wax_hip_search_many_predicate(raw.data(), queries.data(), n, dims, topK, preds.empty() ? nullptr : preds.data(),
+                                        minScores.empty() ? nullptr : minScores.data(), ids.data(), scores.data(), stride, counts.data()));
+    std::vector<std::vector<std::pair<uint64_t, float>>> out(n);
+    for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t j = 0; j < counts[i]; ++j) out[i].emplace_back(ids[(size_t)i * stride + j], scores[(size_t)i * stride + j]);
+    return out;
+}
+
 }  // namespace wax_hip

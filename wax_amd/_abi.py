@@ -115,6 +115,8 @@ SIGNATURES: Dict[str, tuple] = {
                                                      ctypes.c_uint64, _u64p, _u64p, _f32p, _u64p, _f32p, ctypes.c_uint32, _u32p]),
     "wax_hip_search_many": (ctypes.c_int, [ctypes.POINTER(_engine_p), _f32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, _u64p, _f32p,
                                            ctypes.c_uint32, _u32p]),
+    "wax_hip_search_many_predicate": (ctypes.c_int, [ctypes.POINTER(_engine_p), _f32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32,
+                                                     ctypes.POINTER(RowPredicate), _f32p, _u64p, _f32p, ctypes.c_uint32, _u32p]),
     "wax_hip_set_attributes": (ctypes.c_int, [_engine_p, _u64p, ctypes.POINTER(ctypes.c_int64), _u32p, ctypes.c_uint64, _u64p]),
     "wax_hip_get_attributes": (ctypes.c_int, [_engine_p, _u64p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_int64), _u32p, _u8p]),
     "wax_hip_search_predicate": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int, _u64p,

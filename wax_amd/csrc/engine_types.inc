@@ -561,6 +561,7 @@ struct wax_hip_engine {
     std::atomic<int64_t> search_many{1};
     std::atomic<int64_t> search_many_max_rows{262144};
     std::atomic<uint64_t> st_many_pooled{0}, st_many_looped{0};   // pairs of this engine answered by the pooled launch / by the single-query search
+    std::atomic<uint64_t> st_many_masked{0};                      // ... of the pooled ones, by a group that read a row bitmap (wax_hip_search_many_predicate)
     // Write-combining of single-frame appends (the reference appends into a unified-memory buffer and the GPU simply
     // sees it, MetalVectorEngine.swift:340-351; with discrete HBM the analogue is a pinned staging area that the NEXT
     // reader — or a full staging area — uploads in one copy). The last `pend_rows` rows of [0, count) live only here.

@@ -212,6 +212,7 @@ struct PoolGroup {
     uint32_t item0;        // its first work item
     uint32_t n_items;      // workgroups (work items) that share the store
     uint32_t pad;
+    const uint32_t* bitmap;   // masked launch only: [ceil(n_rows / 32)] rows that may be offered; null = every row (an unmasked group)
 };
 struct ScanPoolArgs {
     ScanMultiArgs a;       // queries, qlist, q_norm, partials, dims, k, item_group; store / n_rows / row_base / nq come from the group
@@ -228,6 +229,9 @@ hipError_t launch_scan_multi_listed(const ScanMultiArgs& a, int metric, uint32_t
 uint64_t scan_multi_chunks(uint32_t n_rows, uint32_t dims);                              // chunks (a wave's unit of rows) in n_rows
 uint32_t scan_multi_pooled_items(uint32_t n_rows, uint32_t dims, uint32_t share);        // work items of a store allowed `share` of the launch
 hipError_t launch_scan_multi_pooled(const ScanMultiArgs& a, const PoolGroup* d_pool, int metric, uint32_t n_items, hipStream_t stream);
+// The same launch when at least one group has a row bitmap (wax_hip_search_many_predicate): a row is offered only where its group's
+// bit is set; every row is still loaded. The unmasked launch above never reads PoolGroup::bitmap.
+hipError_t launch_scan_multi_pooled_masked(const ScanMultiArgs& a, const PoolGroup* d_pool, int metric, uint32_t n_items, hipStream_t stream);
 // Per query b < nq: the d_spans[2b + 1] lists of k keys at d_in + d_spans[2b] * k -> row b of d_out (out_stride hits, padded).
 hipError_t launch_merge_keys_spans(const int64_t* d_in, const uint32_t* d_spans, int k, const uint64_t* d_ids, uint32_t row_base,
                                    uint32_t n_rows, wax_hip_hit* d_out, uint32_t out_stride, uint32_t nq, hipStream_t stream);
@@ -557,6 +561,19 @@ struct AttrMaskArgs {
     uint32_t deny_flags;
 };
 hipError_t launch_attr_mask(const AttrMaskArgs& a, hipStream_t st);
+// The mask of MANY (store, predicate) pairs in one launch (wax_hip_search_many_predicate): work item i is one 256-row tile of record
+// d_item_rec[i]; a record's bitmap is d_bitmaps + word_off, every word of it written, bits of rows >= n_rows clear. No counters.
+struct AttrMaskRecord {
+    const int64_t* ts;          // [n_rows] timestamps; null = every row 0
+    const uint32_t* flags;      // [n_rows] flag words; null = every row 0
+    uint32_t n_rows;
+    uint32_t word_off;          // first word of the record's bitmap: bitmaps start on word boundaries, back to back
+    int32_t has_after, has_before;
+    int64_t after, before;
+    uint32_t deny_flags;
+    uint32_t item0;             // its first work item
+};
+hipError_t launch_attr_mask_pooled(const AttrMaskRecord* d_records, const uint32_t* d_item_rec, uint32_t n_items, uint32_t* d_bitmaps, hipStream_t st);
 struct MaskedScanArgs {
     const float* store;         // [n_rows][dims] f32
     const float* query;         // [dims] f32 in HBM

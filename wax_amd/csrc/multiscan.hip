@@ -101,15 +101,18 @@ __device__ inline void ms_halve_rows32(float (&v)[MS_M]) {
 // scan_multi_pooled_kernel is the many-stores form of wax_hip_search_many: the same work table, but a group (a.item_group -> pool[])
 // names its OWN store — base pointer, row count, key base — and its rows are contiguous, as in the full-store form. One launch then
 // scores every store's queries; a work item beyond its store's chunks (the shares are sized on the host) writes empty partial lists.
-// Both kernels are the one body of multiscan_body.inc (included, not called: the two existing forms keep their instructions).
+// MASKED = true is that form for wax_hip_search_many_predicate: a group may carry a row bitmap (PoolGroup::bitmap, written by
+// attr_mask_pooled_kernel just before), and a row is offered only where its bit is set. The rows, the loads, the lane mapping and
+// the arithmetic are the unmasked form's — a passing row's distance has the same bits — so the chunk's bits only gate the push.
+// All kernels are the one body of multiscan_body.inc (included, not called: the existing forms keep their instructions).
 template <int D4, int GROUP, int METRIC, int CAP, bool LISTED>
 __global__ __launch_bounds__(SCAN_THREADS) void scan_multi_kernel(ScanMultiArgs a) {
-    constexpr bool POOLED = false;
+    constexpr bool POOLED = false, MASKED = false;
     const PoolGroup* pool = nullptr;
 #include "multiscan_body.inc"
 }
 
-template <int D4, int GROUP, int METRIC, int CAP>
+template <int D4, int GROUP, int METRIC, int CAP, bool MASKED>
 __global__ __launch_bounds__(SCAN_THREADS) void scan_multi_pooled_kernel(ScanPoolArgs p) {
     constexpr bool LISTED = false, POOLED = true;
     const ScanMultiArgs& a = p.a;
@@ -223,18 +226,19 @@ uint64_t scan_multi_chunks(uint32_t n_rows, uint32_t dims) {
     return ((uint64_t)n_rows + ms_rows_per_chunk(dims) - 1) / ms_rows_per_chunk(dims);
 }
 
-template <int D4, int GROUP, int METRIC, int CAP>
+template <int D4, int GROUP, int METRIC, int CAP, bool MASKED>
 static hipError_t ms_launch_pooled(const ScanPoolArgs& p, int grid, size_t smem, hipStream_t st) {
     static std::atomic<uint64_t> configured{0};   // per device (ensure_dynamic_lds)
     if (smem > 64 * 1024) {
-        hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_multi_pooled_kernel<D4, GROUP, METRIC, CAP>), 160 * 1024, configured);
+        hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&scan_multi_pooled_kernel<D4, GROUP, METRIC, CAP, MASKED>), 160 * 1024, configured);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((scan_multi_pooled_kernel<D4, GROUP, METRIC, CAP>), dim3(grid), dim3(SCAN_THREADS), smem, st, p);
+    hipLaunchKernelGGL((scan_multi_pooled_kernel<D4, GROUP, METRIC, CAP, MASKED>), dim3(grid), dim3(SCAN_THREADS), smem, st, p);
     return hipGetLastError();
 }
 
-hipError_t launch_scan_multi_pooled(const ScanMultiArgs& a, const PoolGroup* d_pool, int metric, uint32_t n_items, hipStream_t st) {
+template <bool MASKED>
+static hipError_t ms_dispatch_pooled(const ScanMultiArgs& a, const PoolGroup* d_pool, int metric, uint32_t n_items, hipStream_t st) {
     const int cap = scan_multi_cap(a.dims, a.k);
     if (cap == 0 || n_items == 0 || !d_pool || !a.item_group || !a.queries || !a.qlist || !a.q_norm || !a.partials) return hipErrorInvalidValue;
     const size_t smem = scan_multi_lds_bytes(a.dims, cap);
@@ -244,10 +248,17 @@ hipError_t launch_scan_multi_pooled(const ScanMultiArgs& a, const PoolGroup* d_p
         using S = decltype(s);
         return with_metric(metric, [&](auto m) {
             constexpr int METRIC = decltype(m)::value;
-            return cap == 64 ? ms_launch_pooled<S::D4, S::GROUP, METRIC, 64>(p, (int)n_items, smem, st)
-                             : ms_launch_pooled<S::D4, S::GROUP, METRIC, 256>(p, (int)n_items, smem, st);
+            return cap == 64 ? ms_launch_pooled<S::D4, S::GROUP, METRIC, 64, MASKED>(p, (int)n_items, smem, st)
+                             : ms_launch_pooled<S::D4, S::GROUP, METRIC, 256, MASKED>(p, (int)n_items, smem, st);
         }, hipErrorInvalidValue);
     }, hipErrorInvalidValue);
+}
+
+hipError_t launch_scan_multi_pooled(const ScanMultiArgs& a, const PoolGroup* d_pool, int metric, uint32_t n_items, hipStream_t st) {
+    return ms_dispatch_pooled<false>(a, d_pool, metric, n_items, st);
+}
+hipError_t launch_scan_multi_pooled_masked(const ScanMultiArgs& a, const PoolGroup* d_pool, int metric, uint32_t n_items, hipStream_t st) {
+    return ms_dispatch_pooled<true>(a, d_pool, metric, n_items, st);
 }
 
 }  // namespace wax

@@ -1,17 +1,22 @@
 // multiscan_body.inc — the body of scan_multi_kernel / scan_multi_pooled_kernel (multiscan.hip includes it once per kernel; not compiled
-// alone). In scope: the template arguments D4, GROUP, METRIC, CAP; constexpr bool LISTED, POOLED; `a` (ScanMultiArgs); `pool`.
+// alone). In scope: the template arguments D4, GROUP, METRIC, CAP; constexpr bool LISTED, POOLED, MASKED; `a` (ScanMultiArgs); `pool`.
+// MASKED (the pooled form of wax_hip_search_many_predicate only): a group may carry a row bitmap, and a row is offered only where its
+// bit is set. Everything under `if constexpr (MASKED)` is absent from the other kernels, whose instructions stay as they were.
     constexpr int LOADS = D4 / GROUP;
     constexpr int RPW = WAVE / GROUP;
     constexpr int RPC = RPW * MS_U;
     constexpr int LEVELS = GROUP == 64 ? 6 : (GROUP == 32 ? 5 : 4);
     constexpr int OUT = MS_M >> LEVELS;          // complete sums per lane per chunk: 4 / 2 / 1
     static_assert(D4 % GROUP == 0 && (GROUP == 16 || GROUP == 32 || GROUP == 64), "GROUP");
+    static_assert((RPC & (RPC - 1)) == 0 && RPC <= 32, "a chunk's bits must sit inside one bitmap word");
+    static_assert(!MASKED || POOLED, "only the many-stores form has a masked kernel");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t nq = a.nq, n = a.n_rows, wg = blockIdx.x, nwg = gridDim.x, part0 = 0, row_base = a.row_base;
     const uint32_t* qlist = a.qlist;
     const float* qnorm = a.q_norm;
     const float* store = a.store;
     const uint32_t* __restrict__ rows = nullptr;
+    const uint32_t* __restrict__ mask = nullptr;   // MASKED: the group's row bitmap (null: every row may be offered)
     if constexpr (LISTED) {
         const GatherGroup G = a.groups[a.item_group[blockIdx.x]];
         nq = G.nq; n = a.row_counts[G.count_slot]; wg = blockIdx.x - G.item0; nwg = G.n_items; part0 = G.part_off;
@@ -21,6 +26,7 @@
         const PoolGroup G = pool[a.item_group[blockIdx.x]];
         nq = G.nq; n = G.n_rows; wg = blockIdx.x - G.item0; nwg = G.n_items; part0 = G.part_off;
         qlist = a.qlist + G.q0; qnorm = a.q_norm + G.q0; store = G.store; row_base = G.row_base;
+        if constexpr (MASKED) mask = G.bitmap;
     }
     // partial list of query slot qi of this workgroup: [nq][grid][k] (full store) / [part_off + qi * n_items + wg] (listed)
     auto partial_of = [&](uint32_t qi) -> int64_t* {
@@ -75,7 +81,18 @@
     // The rows of chunk c + 1 are requested BEFORE chunk c is scored (two register sets, the loop unrolled by two): a wave
     // computes ~4 400 VALU cycles per chunk — as long as the HBM round trip — and with two waves per SIMD nothing else would
     // cover that latency (PMC of the first version: waves parked 60 % of their cycles, VALU busy 45 %).
-    auto load_chunk = [&](f32x4 (&v)[MS_U][LOADS], uint32_t (&rr)[MS_U], uint32_t chunk) {
+    // MASKED: the bitmap word that holds the chunk's RPC bits travels with its rows — requested here, one chunk ahead of its use, and
+    // not looked at before chunk_bits() at scoring time, so the row requests behind it do not wait for it. The chunk is an aligned
+    // power-of-two run of rows, so its bits sit inside one word, the same for the whole wave: a scalar load (the bitmap is read
+    // through the constant address space — nothing in this kernel writes it) into scalar registers, not vector ones. Per-row
+    // attribute values never enter the kernel. Bit i of chunk_bits is row chunk * RPC + i; bits of rows >= n are clear in the bitmap.
+    typedef __attribute__((address_space(1))) const f32x4 glb_f32x4;
+    auto load_chunk = [&](f32x4 (&v)[MS_U][LOADS], uint32_t (&rr)[MS_U], uint32_t& word, uint32_t chunk) {
+        if constexpr (MASKED) {
+            typedef __attribute__((address_space(4))) const uint32_t const_u32;
+            const uint32_t r0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(chunk * RPC));   // < n: word r0 >> 5 exists
+            word = mask != nullptr ? ((const const_u32*)mask)[r0 >> 5] : ~0u;
+        }
         const uint32_t rbase = chunk * RPC + sub;
 #pragma unroll
         for (int u = 0; u < MS_U; ++u) {
@@ -85,10 +102,21 @@
             rr[u] = row;
             const f32x4* p = store4 + (size_t)row * D4 + gl;
 #pragma unroll
-            for (int j = 0; j < LOADS; ++j) v[u][j] = __builtin_nontemporal_load(p + j * GROUP);
+            for (int j = 0; j < LOADS; ++j) {
+                // MASKED: the rows are read as GLOBAL memory, not through the generic pointer the group table hands over. A skipped
+                // chunk's rows are still in flight when the next request names the same registers; for generic (flat) loads, which
+                // may complete out of order, the compiler drains every outstanding load first (vmcnt(0) ahead of the prefetch) —
+                // global loads return in order and need no such wait.
+                if constexpr (MASKED) v[u][j] = __builtin_nontemporal_load((const glb_f32x4*)p + j * GROUP);
+                else v[u][j] = __builtin_nontemporal_load(p + j * GROUP);
+            }
         }
     };
-    auto score_chunk = [&](const f32x4 (&v)[MS_U][LOADS], const uint32_t (&rr)[MS_U], uint32_t chunk) {
+    auto chunk_bits = [&](uint32_t word, uint32_t chunk) -> uint32_t {
+        const uint32_t r0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(chunk * RPC));
+        return (uint32_t)__builtin_amdgcn_readfirstlane((int)((word >> (r0 & 31u)) & (uint32_t)((1ull << RPC) - 1ull)));
+    };
+    auto score_chunk = [&](const f32x4 (&v)[MS_U][LOADS], const uint32_t (&rr)[MS_U], uint32_t bits, uint32_t chunk) {
         const uint32_t rbase = chunk * RPC + sub;
         const uint32_t rr0 = rr[0], rr1 = rr[1], rr2 = rr[2], rr3 = rr[3];   // (named: see row_norm)
         // ||v||^2 per row-group, the norm half of finish_row, then handed to every lane of the group
@@ -143,7 +171,8 @@
             const float d = finish_distance<METRIC>(part[j], nrm, qn_lane);
             const uint32_t r = rbase + (uint32_t)u * RPW;
             const int64_t key = make_key(d, row_base + (LISTED ? row : r));
-            const bool pass = q_live && (r < n) && (key < tau_lane);
+            bool pass = q_live && (r < n) && (key < tau_lane);
+            if constexpr (MASKED) pass = pass && ((bits >> (uint32_t)(sub + u * RPW)) & 1u) != 0u;
             unsigned long long todo = __ballot(pass);
             while (todo != 0ull) {                               // rare after warm-up: one list at a time
                 const int L = (int)__builtin_ctzll(todo);
@@ -172,23 +201,27 @@
     {
         f32x4 va[MS_U][LOADS], vb[MS_U][LOADS];
         uint32_t ra[MS_U], rb[MS_U];
+        uint32_t wa = 0u, wb = 0u;                    // MASKED: the bitmap word of the chunk each set holds (wave-uniform)
         // The prefetch is UNCONDITIONAL (past the end it re-requests the current chunk: L2 hits, discarded): behind a branch
         // the compiler no longer knows how many requests are outstanding and waits vmcnt(0) for the current set — which
-        // drains the prefetch it was meant to overlap.
+        // drains the prefetch it was meant to overlap. MASKED keeps it so: a chunk whose bits are all clear skips its SCORING (a
+        // wave-uniform branch around score_chunk), never its loads — which is why a masked group is charged the whole store.
         uint32_t chunk = gwave;
         if (chunk < nchunks) {
-            load_chunk(va, ra, chunk);
+            load_chunk(va, ra, wa, chunk);
             for (;;) {
                 uint32_t nxt = chunk + nwaves;
-                load_chunk(vb, rb, nxt < nchunks ? nxt : chunk);
+                load_chunk(vb, rb, wb, nxt < nchunks ? nxt : chunk);
                 __builtin_amdgcn_sched_barrier(0);    // the requests go out before the first use of the current set
-                score_chunk(va, ra, chunk);
+                uint32_t bits = MASKED ? chunk_bits(wa, chunk) : 0u;
+                if (!MASKED || bits != 0u) score_chunk(va, ra, bits, chunk);
                 chunk = nxt;
                 if (chunk >= nchunks) break;
                 nxt = chunk + nwaves;
-                load_chunk(va, ra, nxt < nchunks ? nxt : chunk);
+                load_chunk(va, ra, wa, nxt < nchunks ? nxt : chunk);
                 __builtin_amdgcn_sched_barrier(0);
-                score_chunk(vb, rb, chunk);
+                bits = MASKED ? chunk_bits(wb, chunk) : 0u;
+                if (!MASKED || bits != 0u) score_chunk(vb, rb, bits, chunk);
                 chunk = nxt;
                 if (chunk >= nchunks) break;
             }

@@ -4,6 +4,8 @@
 //   attr_mask_kernel     one lane per row: reads the timestamp and flag columns coalesced, evaluates the predicate, ballots, and
 //                        writes the row bitmap filter.hip's allow-list path already has (with an allow-list: ANDs into the bitmap
 //                        the probe kernel marked). Counts the passing rows and the scan chunks that hold one into two device words.
+//   attr_mask_pooled_kernel  the same reads, test, ballot and word writes for MANY (store, predicate) records in one launch
+//                        (wax_hip_search_many_predicate): one 256-row tile of one record per workgroup, no counters, no atomics.
 //   scan_masked_kernel   scan_body's structure (kernels.hip): the same (dims -> GROUP) table, the same loads, accumulate / finish_row
 //                        of row_math.h — a passing row's distance has the scan's bits. A wave reads its chunk's bits before the
 //                        loads; a chunk without a passing row costs no load at all (the test is wave-uniform); otherwise a key is
@@ -21,6 +23,12 @@ namespace wax {
 // at 1/64 passing where the allow-list form — the same launches from the bitmap on — took 0.11. That the same-address atomics are
 // the 0.2 ms in between is an inference from that table, not a kernel trace; this form is the remedy that inference calls for.
 constexpr uint32_t kMaskGrid = 1024;
+
+// passesFrameFilter's per-row test (UnifiedSearch.swift:1241-1258): the one device definition, used by both mask kernels.
+__device__ inline bool attr_row_passes(int32_t has_after, int64_t after, int32_t has_before, int64_t before, uint32_t deny_flags, int64_t ts, uint32_t fl) {
+    return !(has_after != 0 && ts < after) && !(has_before != 0 && ts >= before) && (fl & deny_flags) == 0u;
+}
+
 __global__ __launch_bounds__(256) void attr_mask_kernel(AttrMaskArgs a) {
     __shared__ uint32_t wave_counts[4][2];
     const uint32_t n_words = (a.n_rows + 31u) / 32u;
@@ -35,7 +43,7 @@ __global__ __launch_bounds__(256) void attr_mask_kernel(AttrMaskArgs a) {
         if (pass) {
             const int64_t ts = a.ts != nullptr ? a.ts[row] : 0;
             const uint32_t fl = a.flags != nullptr ? a.flags[row] : 0u;
-            pass = !(a.has_after != 0 && ts < a.after) && !(a.has_before != 0 && ts >= a.before) && (fl & a.deny_flags) == 0u;
+            pass = attr_row_passes(a.has_after, a.after, a.has_before, a.before, a.deny_flags, ts, fl);
             if (a.and_bitmap != 0) pass = pass && ((a.bitmap[row >> 5] >> (row & 31u)) & 1u) != 0u;   // (read by the wave that rewrites the word below)
         }
         const unsigned long long b = __ballot(pass);
@@ -61,6 +69,33 @@ hipError_t launch_attr_mask(const AttrMaskArgs& a, hipStream_t st) {
     if (a.chunk_rows > 64u || (a.chunk_rows & (a.chunk_rows - 1u)) != 0u) return hipErrorInvalidValue;
     const uint32_t n_tiles = (a.n_rows + 255u) / 256u;
     hipLaunchKernelGGL(attr_mask_kernel, dim3(n_tiles < kMaskGrid ? n_tiles : kMaskGrid), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+// Work item blockIdx.x is tile (blockIdx.x - item0) of record item_rec[blockIdx.x]: attr_mask_kernel's tile without its counters. A
+// wave's 64 rows are two whole words of the record's bitmap; lanes at or beyond n_rows vote false, so the last word's tail is clear.
+__global__ __launch_bounds__(256) void attr_mask_pooled_kernel(const AttrMaskRecord* __restrict__ records, const uint32_t* __restrict__ item_rec,
+                                                               uint32_t* __restrict__ bitmaps) {
+    const AttrMaskRecord r = records[item_rec[blockIdx.x]];
+    const uint32_t n_words = (r.n_rows + 31u) / 32u;
+    const int lane = lane_id();
+    const uint32_t row = (blockIdx.x - r.item0) * 256u + threadIdx.x;
+    bool pass = row < r.n_rows;
+    if (pass) {
+        const int64_t ts = r.ts != nullptr ? r.ts[row] : 0;
+        const uint32_t fl = r.flags != nullptr ? r.flags[row] : 0u;
+        pass = attr_row_passes(r.has_after, r.after, r.has_before, r.before, r.deny_flags, ts, fl);
+    }
+    const unsigned long long b = __ballot(pass);
+    const uint32_t w0 = (row - (uint32_t)lane) >> 5;
+    uint32_t* bitmap = bitmaps + r.word_off;
+    if (lane == 0 && w0 < n_words) bitmap[w0] = (uint32_t)b;
+    if (lane == 32 && w0 + 1u < n_words) bitmap[w0 + 1u] = (uint32_t)(b >> 32);
+}
+
+hipError_t launch_attr_mask_pooled(const AttrMaskRecord* d_records, const uint32_t* d_item_rec, uint32_t n_items, uint32_t* d_bitmaps, hipStream_t st) {
+    if (n_items == 0 || d_records == nullptr || d_item_rec == nullptr || d_bitmaps == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(attr_mask_pooled_kernel, dim3(n_items), dim3(256), 0, st, d_records, d_item_rec, d_bitmaps);
     return hipGetLastError();
 }
 

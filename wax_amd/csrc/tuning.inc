@@ -214,6 +214,7 @@ int64_t wax_hip_get_tuning(wax_hip_engine* e, const char* key) {
     if (k == "search_many_max_rows") return e->search_many_max_rows.load();
     if (k == "search_many_pooled") return (int64_t)e->st_many_pooled.load();   // pairs of wax_hip_search_many answered by its pooled launch
     if (k == "search_many_looped") return (int64_t)e->st_many_looped.load();   // ... by the single-query search under the call's lock
+    if (k == "search_many_masked") return (int64_t)e->st_many_masked.load();   // ... of the pooled ones: by a masked group (a non-empty predicate evaluated on the device)
     if (k == "batch_queries") return (int64_t)e->st_batch_queries.load();
     if (k == "batch_fallbacks") return (int64_t)e->st_batch_fallbacks.load();
     if (k == "slots") return e->max_slots;

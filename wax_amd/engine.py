@@ -568,3 +568,51 @@ def searchMany(engines, queries, topK: int):  # noqa: N802,N803
                                              kcap, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
     raise_for_status(rc)
     return ids, scores, counts
+
+
+def _per_pair(value, n: int, what: str, tuple_is_value: bool = False) -> list:
+    """One filter value for all n pairs, or a sequence of n (None entries: none for that pair) -> a list of n."""
+    if isinstance(value, (list, np.ndarray)) or (isinstance(value, tuple) and not tuple_is_value):
+        if len(value) != n:
+            raise EncodingError(f"searchManyFiltered: {what} must be one value or hold one entry per pair")
+        return list(value)
+    return [value] * n
+
+
+def searchManyFiltered(engines, queries, topK: int, timeRange=None, denyFlags=0, minScore=None):  # noqa: N802,N803
+    """searchMany with the row predicate and score cut of searchFiltered per pair (wax_hip_search_many_predicate): row i is what
+    engines[i].searchFiltered(queries[i], topK, timeRange=..., denyFlags=..., minScore=...) returns. Each filter is one value for all
+    pairs or a list of n with None entries allowed: `timeRange` = (after | None, before | None) (one such tuple is one value; a
+    LIST is per pair), `denyFlags` an int, `minScore` a float. Allow-lists per pair are not part of this call. Returns
+    (ids, scores, counts) like searchMany."""
+    engines = list(engines)
+    qs = _as_f32(queries)
+    if qs.ndim != 2 or qs.shape[0] != len(engines):
+        raise EncodingError("searchManyFiltered: queries must be [len(engines), dims]")
+    n, width = qs.shape
+    if any(not isinstance(e, HIPVectorEngine) for e in engines):
+        raise TypeError("searchManyFiltered: engines must be HIPVectorEngine instances")
+    kcap = max(1, min(clampTopK(topK), max([e.count for e in engines] + [1])))   # row width of the arrays (passed as the stride)
+    ids = np.zeros((n, kcap), dtype=np.uint64)
+    scores = np.zeros((n, kcap), dtype=np.float32)
+    counts = np.zeros(n, dtype=np.uint32)
+    if n == 0:
+        return ids, scores, counts
+    ranges, denies, cuts_in = _per_pair(timeRange, n, "timeRange", tuple_is_value=True), _per_pair(denyFlags, n, "denyFlags"), _per_pair(minScore, n, "minScore")
+    preds = None
+    if any(r is not None for r in ranges) or any(d for d in denies):
+        preds = (_abi.RowPredicate * n)()
+        for i in range(n):
+            after, before = (None, None) if ranges[i] is None else ranges[i]
+            preds[i] = _abi.RowPredicate(0 if after is None else 1, 0 if after is None else int(after),
+                                         0 if before is None else 1, 0 if before is None else int(before),
+                                         int(denies[i] or 0) & 0xffffffff)
+    cuts = None
+    if any(c is not None for c in cuts_in):
+        cuts = np.array([np.nan if c is None else float(c) for c in cuts_in], dtype=np.float32)
+    handles = (ctypes.c_void_p * n)(*[e._h.value for e in engines])
+    rc = engines[0]._lib.wax_hip_search_many_predicate(
+        handles, _fp(qs), n, width, int(max(min(topK, 2**31 - 1), -2**31)), preds, None if cuts is None else _fp(cuts),
+        _u64p(ids), _fp(scores), kcap, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+    raise_for_status(rc)
+    return ids, scores, counts
