@@ -471,6 +471,16 @@ int wax_hip_stats(wax_hip_engine* e, wax_hip_stats_t* out);
  *   0 = never, one pass per query. Nothing is parked while "time_kernels" != 0 or scans are chained), "mirror_passes" /
  *   "mirror_shared_passes" / "mirror_shared_queries" (read-only: scan launches over the mirror / of which with two or more queries /
  *   queries those answered; "mirror_scans" keeps counting queries),
+ *   "mirror_fill" (under "mirror_share" 1: 1 (default) = a caller who pipelines single queries gets full passes — a submit is also parked
+ *   when this engine has mirror tickets that are launched and not yet collected (a pass in flight, or finished tickets whose caller is
+ *   draining a pass and submits again at once), and a set that is not full is launched only by the collect of one of its own tickets or
+ *   by a submit that finds no such ticket; a collect that blocks on a running ticket holds it back. A query submitted behind finished
+ *   uncollected tickets by a caller who then stays away waits for that caller's next collect. 0 = the eager rule described under
+ *   "mirror_share"), "mirror_fill_holds" (read-only, counted under "mirror_fill" 1 only. A submit counts when no pass was in flight and
+ *   the eager rule would have launched there — the query alone, or the parked set it joined — and the rule left it parked behind a
+ *   launched uncollected ticket instead; a submit parked behind a pass in flight is parked under either rule and does not count, nor
+ *   does the submit that fills a set. A collect counts when it was about to block on a running ticket of another pass while a set was
+ *   parked and left that set parked),
  *   "filter_device_min" (wax_hip_search_filtered: allow-lists at least this long are resolved by the id -> row table in HBM, default 4096; -1 = never),
  *   "filter_batch" (wax_hip_search_batch_filtered: 1 (default) = one gather pass for all allow-lists; 0 = the single-query filtered path
  *   per query), "filter_batch_queries" / "filter_batch_fallbacks" (read-only: listed queries answered by the gather pass / by the

@@ -31,7 +31,7 @@ static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int
         if (e->count == 0) {                               // :448 — an empty ticket, no GPU work
             rc = acquire_slot(e, &s, try_only, holding(e) > 0);
             if (rc != WAX_HIP_OK) break;
-            s->k_eff = 0; s->timed = false; s->shared = false;
+            s->k_eff = 0; s->timed = false; s->shared = false; s->listed = false;
             break;
         }
         if (dims != e->dims || !query) {                   // validate (:449, 830-833)
@@ -55,23 +55,34 @@ static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int
         s->flag_wait = false;
         bool mirrored = false;
         s->shared = false;
+        s->listed = false;
         s->park_rc = WAX_HIP_OK;
         if (scan_uses_mirror(e, k_eff)) {
             const int64_t share = mirror_share_mode(e, tk_mode);
             std::unique_lock<std::mutex> sg(e->share_mu, std::defer_lock);
             if (share != 0) {
                 // "mirror_share": a query that arrives while a pass over the mirror is running waits for company — it is parked (its
-                // query in the slot's pinned h_query) and launched with whatever else is parked by then: when the set is full, when a
-                // collect is about to block, or by a submit that finds the GPU without a pass. A lone query launches at once, as ever.
+                // query in the slot's pinned h_query) and launched with whatever else is parked by then: when the set is full, by the
+                // collect of a parked ticket, or by a submit that finds the GPU without a pass. A lone query launches at once, as ever.
+                // "mirror_fill" 1 (mode 1): mirror tickets that are launched and not yet collected are either finished — their caller is
+                // draining a pass and its next submits are on the way — or a pass in flight; behind either a submit is parked, and it
+                // launches the set only when it fills it. (share_last alone is one event of the last pass: right after the collect of a
+                // group's first member its other members' events may not have signalled yet.) 0: the eager rule.
                 sg.lock();
-                if (share >= 2 || !e->parked.empty() || mirror_pass_in_flight(e)) {
+                const bool fill = share == 1 && e->mirror_fill.load() != 0;
+                const bool waiting = fill && !e->share_launched.empty();
+                if (share >= 2 || !e->parked.empty() || waiting || mirror_pass_in_flight(e)) {
                     std::memcpy(s->h_query, query, (size_t)dims * sizeof(float));
                     s->q_norm = qn;
                     s->mirror = true;
                     s->shared = true;
                     e->parked.push_back(s);
                     e->n_parked.store((int)e->parked.size());
-                    if ((int)e->parked.size() >= MIRROR_MAX_NQ || (share < 2 && !mirror_pass_in_flight(e))) launch_parked(e);
+                    if ((int)e->parked.size() >= MIRROR_MAX_NQ) launch_parked(e);
+                    else if (share < 2 && !mirror_pass_in_flight(e)) {
+                        if (waiting) e->st_mirror_fill_holds++;      // the eager rule would have launched here
+                        else launch_parked(e);
+                    }
                     break;
                 }
             }
@@ -81,6 +92,7 @@ static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int
             if (mirrored) {
                 err = hipEventRecord(s->ev_done, s->stream);
                 if (err != hipSuccess) { rc = fail(WAX_HIP_ERR_INTERNAL, std::string("event record: ") + hipGetErrorString(err)); break; }
+                if (share != 0) { s->listed = true; e->share_launched.push_back(s); }
                 break;
             }
         }
@@ -156,17 +168,26 @@ static int collect_impl(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, f
     *out_count = 0;
     if (s->k_eff == 0 && out_hits)
         for (uint32_t i = 0; i < hits_cap; ++i) out_hits[i] = wax_hip_hit{KEY_PAD, ID_PAD};
-    if (s->k_eff > 0 && (s->shared || e->n_parked.load() > 0)) {
-        // "mirror_share": a parked ticket is launched now, with everything parked beside it; any other collect that is about to block
-        // launches what is parked first (queued behind the pass in flight, so the GPU never waits for the host). Mode 2 launches only
-        // for a ticket that is itself parked.
+    if (s->k_eff > 0 && (s->shared || s->listed || e->n_parked.load() > 0)) {
+        // "mirror_share": a parked ticket is launched now, with everything parked beside it. Under "mirror_fill" 0 any other collect
+        // that is about to block launches what is parked first (queued behind the pass in flight, so the GPU never waits for the
+        // host); under "mirror_fill" 1 it holds the set — its caller submits again as soon as it returns, and those submits fill it.
+        // Mode 2 launches only for a ticket that is itself parked.
         std::unique_lock<std::mutex> sg(e->share_mu);
         const bool mine = std::find(e->parked.begin(), e->parked.end(), s) != e->parked.end();
         if (mine) launch_parked(e);
         else if (!e->parked.empty() && e->mirror_share.load() < 2) {
             const bool blocks = s->flag_wait ? __atomic_load_n(s->h_done, __ATOMIC_ACQUIRE) != s->done_seq
                                              : hipEventQuery(s->ev_done) == hipErrorNotReady;
-            if (blocks) launch_parked(e);
+            if (blocks) {
+                if (e->mirror_fill.load() != 0) e->st_mirror_fill_holds++;
+                else launch_parked(e);
+            }
+        }
+        if (s->listed) {               // (launch_parked lists a parked ticket: looked at after it)
+            auto it = std::find(e->share_launched.begin(), e->share_launched.end(), s);
+            if (it != e->share_launched.end()) e->share_launched.erase(it);
+            s->listed = false;
         }
         if (s->shared && s->park_rc != WAX_HIP_OK) rc = fail(s->park_rc, s->park_err);
     }

@@ -215,6 +215,7 @@ struct Slot {
     // "mirror_share": this ticket was parked at submit (its query waits in h_query for a pass it can share). `shared` is written before
     // the ticket is published and tells collect to look under the engine's share_mu; the other two are guarded by that mutex.
     bool shared = false;
+    bool listed = false;           // launched on the mirror and in the engine's share_launched until its collect ("mirror_fill")
     int park_rc = 0;               // what launching it returned (a failed launch surfaces at the ticket's collect)
     std::string park_err;
     std::thread::id owner;         // the submitting thread (its outstanding-ticket count drops at collect, whoever collects)
@@ -513,6 +514,14 @@ struct wax_hip_engine {
     std::atomic<int> n_parked{0};            // parked.size(), readable without the mutex
     hipEvent_t share_last = nullptr;         // ev_done of the last mirror pass launched (a slot's event: not owned); not ready = a pass in flight
     std::atomic<uint64_t> st_mirror_passes{0}, st_mirror_shared_passes{0}, st_mirror_shared_queries{0};
+    // "mirror_fill" (1 = default): under "mirror_share" 1 a caller who pipelines single queries gets full passes. Mirror tickets that
+    // are launched and not yet collected are a pass in flight or, finished, mean that their caller is draining a pass and its next
+    // submits are on the way: a submit that finds such tickets is parked, and neither it nor a collect that blocks on a running
+    // ticket launches a set that is not full. 0 = the eager rule (a blocking collect and a submit without a pass in flight launch
+    // whatever is parked).
+    std::atomic<int64_t> mirror_fill{1};
+    std::vector<Slot*> share_launched;       // mirror tickets launched and not yet collected (share_mu); no event of a parked slot is ever asked
+    std::atomic<uint64_t> st_mirror_fill_holds{0};   // submits parked or held by the rule + blocking collects that held the set back
     // wax_hip_search_batch_submit_device tickets (guarded by bticket_mu)
     struct BatchTicket {
         BatchCtx* c = nullptr;           // null: the batch was answered at submit time (empty engine / loop path)

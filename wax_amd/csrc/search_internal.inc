@@ -419,7 +419,10 @@ static void launch_parked(wax_hip_engine* e) {
             const hipError_t err = hipEventRecord(grp[0]->ev_done, grp[0]->stream);
             if (err != hipSuccess) rc = fail(WAX_HIP_ERR_INTERNAL, std::string("event record: ") + hipGetErrorString(err));
         }
-        if (rc == WAX_HIP_OK) e->share_last = grp[0]->ev_done;
+        if (rc == WAX_HIP_OK) {
+            e->share_last = grp[0]->ev_done;
+            for (Slot* s : grp) { s->listed = true; e->share_launched.push_back(s); }
+        }
     } else if (rc == WAX_HIP_OK) {
         for (Slot* s : grp) {             // no mirror: every member takes the f32 scan on its own stream
             const int frc = parked_take_f32(e, s);
