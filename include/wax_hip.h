@@ -481,6 +481,18 @@ int wax_hip_stats(wax_hip_engine* e, wax_hip_stats_t* out);
  *   launched uncollected ticket instead; a submit parked behind a pass in flight is parked under either rule and does not count, nor
  *   does the submit that fills a set. A collect counts when it was about to block on a running ticket of another pass while a set was
  *   parked and left that set parked),
+ *   "mirror_bits" (which mirror a single query that takes one streams: 0 (default) = auto — where "scan_mirror" is 1, the store holds more
+ *   than 2 GiB of f32 rows and top_k <= 16, the 8-bit code mirror: one byte per element, row-scaled, plus {scale, err} per row, built from
+ *   the f32 store (rows x (dims + 8) bytes). A row's key is a lower bound of its distance from its own measured error, the 64 best are
+ *   re-scored in f32 and the answer is released only under the certificate, else collect re-runs the query on the f32 scan as for bf16;
+ *   everything else takes the bf16 mirror. 8 = the code mirror wherever a mirror is taken and top_k <= 16; 16 = always bf16. Appended rows
+ *   are converted at the next query; any other mutation makes the code mirror stale as a whole, and a stale or missing one is rebuilt by
+ *   the third eligible query in a row since the last mutation — the first two take bf16. A parked set rides one mirror: bf16 if any member
+ *   has top_k > 16. Breaker: when 8 of the engine's last 32 8-bit queries were uncertified the next 1024 eligible queries take bf16),
+ *   "mirror8_passes" / "mirror8_fallbacks" / "mirror8_unavailable" / "mirror8_conversions" / "mirror8_rows_converted" /
+ *   "mirror8_breaker_trips" (read-only: scan launches over the code mirror, also counted in "mirror_passes" / 8-bit queries re-run on the
+ *   f32 scan, also in "mirror_scan_fallbacks" / queries sent to bf16 because the code mirror could not be allocated or converted /
+ *   conversions enqueued / rows they converted / times the breaker opened),
  *   "filter_device_min" (wax_hip_search_filtered: allow-lists at least this long are resolved by the id -> row table in HBM, default 4096; -1 = never),
  *   "filter_batch" (wax_hip_search_batch_filtered: 1 (default) = one gather pass for all allow-lists; 0 = the single-query filtered path
  *   per query), "filter_batch_queries" / "filter_batch_fallbacks" (read-only: listed queries answered by the gather pass / by the

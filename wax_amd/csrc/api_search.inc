@@ -52,12 +52,15 @@ static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int
         const float qn = query_norm(query, dims);
         hipError_t err = hipSuccess;
         s->mirror = false;
+        s->mirror8 = false;
+        s->want8 = false;
         s->flag_wait = false;
         bool mirrored = false;
         s->shared = false;
         s->listed = false;
         s->park_rc = WAX_HIP_OK;
         if (scan_uses_mirror(e, k_eff)) {
+            s->want8 = mirror8_take(e, k_eff);
             const int64_t share = mirror_share_mode(e, tk_mode);
             std::unique_lock<std::mutex> sg(e->share_mu, std::defer_lock);
             if (share != 0) {
@@ -86,7 +89,7 @@ static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int
                     break;
                 }
             }
-            rc = enqueue_mirror_scan(e, s, query, qn, k_eff, tk_mode, &mirrored);
+            rc = enqueue_mirror_scan(e, s, query, qn, k_eff, tk_mode, &mirrored, s->want8);
             if (rc != WAX_HIP_OK) break;
             if (mirrored && share != 0) e->share_last = s->ev_done;   // (recorded just below, still under share_mu)
             if (mirrored) {
@@ -223,10 +226,13 @@ static int collect_impl(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, f
         } else {
             err = hipEventSynchronize(s->ev_done);   // commandBuffer completion (:577-582); later queries on the stream keep running
         }
-        if (err == hipSuccess && s->mirror && __atomic_load_n(slot_cert_word(s->h_done), __ATOMIC_ACQUIRE) != 1u) {
+        const bool certified = err == hipSuccess && s->mirror && __atomic_load_n(slot_cert_word(s->h_done), __ATOMIC_ACQUIRE) == 1u;
+        if (err == hipSuccess && s->mirror && s->mirror8) mirror8_note_result(e, certified);
+        if (err == hipSuccess && s->mirror && !certified) {
             // the mirror's certificate failed (ties, a clustered store, zero / NaN rows or query): this query is re-run on the f32 scan,
             // on the same slot, and that answer is returned (the batched path's "uncertified queries are re-run exactly at collect")
             e->st_mirror_fallbacks++;
+            if (s->mirror8) e->st_mirror8_fallbacks++;
             rc = enqueue_scan(e, nullptr, s->q_norm, s->k_eff, s->k_eff, s->d_partials, s, s->h_hits, s->stream, nullptr, nullptr,
                               /*chain=*/false, nullptr, nullptr, s->h_query);
             if (rc != WAX_HIP_OK) err = hipErrorUnknown;

@@ -105,6 +105,8 @@ void wax_hip_engine_destroy(wax_hip_engine* e) {
         BatchMirror& b = e->batch;
         (void)hipFree(b.d_cb); (void)hipFree(b.d_vn2); (void)hipFree(b.d_maxnorm); (void)hipFree(b.d_dirty);
         if (b.ev_ready) (void)hipEventDestroy(b.ev_ready);
+        (void)hipFree(b.d_c8); (void)hipFree(b.d_c8_meta); (void)hipFree(b.d_c8_max);
+        if (b.ev8_ready) (void)hipEventDestroy(b.ev8_ready);
         for (BatchCtx* c : e->bctx_all) free_bctx(c);
         for (FilterWork* f : e->filter_all) free_filter_work(f);
         (void)hipFree(e->idhash.d_table);

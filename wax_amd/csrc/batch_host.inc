@@ -13,19 +13,26 @@ static double mirror_rows_to_convert(wax_hip_engine* e) {
     return (double)(cnt > rows ? cnt - rows : 0) + (double)b.n_dirty.load();
 }
 
+// The 8-bit code mirror's two hooks (exclusive engine lock held): an append leaves rows [rows8, count) to convert; everything else
+// starts it over. Either way the count of queries that wanted a rebuild starts again.
+static void c8_note_append(wax_hip_engine* e) { e->batch.c8_valid = false; e->batch.c8_wanted = 0; }
+static void c8_note_stale(wax_hip_engine* e) { e->batch.c8_valid = false; e->batch.c8_stale = true; e->batch.c8_wanted = 0; }
+
 // Mutation hooks of the bf16 mirror and the id -> row table (exclusive engine lock held).
 static void mirror_note_upsert(wax_hip_engine* e, uint64_t row) {
     BatchMirror& b = e->batch;
+    c8_note_stale(e);
     b.mirror_valid = false;
     if (b.stale || row >= b.rows) return;                    // not mirrored yet: converted with the appended range
     if (b.dirty.size() >= kMirrorMaxDirty) { b.stale = true; b.dirty.clear(); b.n_dirty = 0; return; }
     b.dirty.push_back((uint32_t)row);
     b.n_dirty = b.dirty.size();
 }
-static void mirror_note_append(wax_hip_engine* e) { e->batch.mirror_valid = false; e->idhash.valid = false; }
+static void mirror_note_append(wax_hip_engine* e) { e->batch.mirror_valid = false; e->idhash.valid = false; c8_note_append(e); }
 static void mirror_note_replaced(wax_hip_engine* e) {       // deserialize: every row is new
     e->batch.mirror_valid = false; e->batch.stale = true; e->batch.dirty.clear(); e->batch.n_dirty = 0; e->batch.rows = 0;
     e->idhash.valid = false; e->idhash.stale = true; e->idhash.rows = 0;
+    c8_note_stale(e);
 }
 // Mutation hooks of the per-row attribute columns (exclusive engine lock held). The device mirror is only ever marked: the next
 // predicate search uploads from the lowest marked row (ensure_attrs, api_predicate.inc).
@@ -44,6 +51,7 @@ static void attr_note_replaced(wax_hip_engine* e) {               // deserialize
 }
 // a mutation the mirror could not follow (a failed row shift): convert everything at the next use
 static void mirror_note_lost(wax_hip_engine* e) {
+    c8_note_stale(e);
     e->batch.mirror_valid = false; e->batch.stale = true; e->batch.dirty.clear(); e->batch.n_dirty = 0;
 }
 // remove(frameId:) moved store rows (idx, count) down by one (MetalVectorEngine.swift:431-438): the mirror's tail follows (half the
@@ -51,6 +59,7 @@ static void mirror_note_lost(wax_hip_engine* e) {
 static int mirror_note_remove(wax_hip_engine* e, uint64_t idx) {
     BatchMirror& b = e->batch;
     e->idhash.valid = false; e->idhash.stale = true; e->idhash.rows = 0;     // every later row changed its number
+    c8_note_stale(e);
     b.mirror_valid = false;
     if (b.stale || b.d_cb == nullptr || idx >= b.rows) return WAX_HIP_OK;
     if (b.ev_pending) { (void)hipEventSynchronize(b.ev_ready); b.ev_pending = false; }
@@ -158,6 +167,7 @@ static int compact_removed_rows(wax_hip_engine* e, const std::vector<uint32_t>& 
 static void mirror_note_remove_batch(wax_hip_engine* e, const std::vector<uint32_t>& rem, bool followed) {
     BatchMirror& b = e->batch;
     e->idhash.valid = false; e->idhash.stale = true; e->idhash.rows = 0;
+    c8_note_stale(e);
     b.mirror_valid = false;
     if (b.stale || b.d_cb == nullptr || rem[0] >= b.rows) return;    // nothing mirrored moved
     if (!followed) { mirror_note_lost(e); return; }
@@ -250,6 +260,58 @@ int ensure_mirror(wax_hip_engine* e, hipStream_t st) {
         b.conversions += 1;
     }
     b.mirror_valid.store(true, std::memory_order_release);
+    return WAX_HIP_OK;
+}
+
+// The 8-bit code mirror (mirror8_scan.hip): allocated and built by the query that wants it (search_internal.inc decides when), appended
+// rows converted at the next use, anything else converted again as a whole — see BatchMirror. Like ensure_mirror nothing here waits for
+// the device: the converting stream records ev8_ready, every other slot's stream waits for it.
+int ensure_mirror8(wax_hip_engine* e, hipStream_t st) {
+    BatchMirror& b = e->batch;
+    std::unique_lock<std::mutex> g(b.mu8);
+    if (b.c8_valid.load(std::memory_order_acquire) && b.c8_cap >= e->capacity) {
+        if (b.ev8_pending) {
+            if (hipEventQuery(b.ev8_ready) == hipSuccess) b.ev8_pending = false;
+            else HIP_TRY(hipStreamWaitEvent(st, b.ev8_ready, 0), WAX_HIP_ERR_INTERNAL, "code mirror ready wait");
+        }
+        return WAX_HIP_OK;
+    }
+    const uint32_t D = e->dims;
+    if (!b.d_c8_max) {
+        HIP_TRY(hipMalloc(&b.d_c8_max, sizeof(unsigned int)), WAX_HIP_ERR_ALLOC, "Failed to allocate code mirror scalars");
+        b.c8_stale = true;
+    }
+    if (!b.ev8_ready) HIP_TRY(hipEventCreateWithFlags(&b.ev8_ready, hipEventDisableTiming), WAX_HIP_ERR_INTERNAL, "event create");
+    if (b.ev8_pending) HIP_TRY(hipStreamWaitEvent(st, b.ev8_ready, 0), WAX_HIP_ERR_INTERNAL, "code mirror ready wait");
+    if (b.c8_cap < e->capacity || b.d_c8 == nullptr) {
+        // the store was reallocated: as for the bf16 mirror no reader can hold the old buffers (a mutation came first, under the
+        // exclusive lock); the codes do not move over, they are converted again
+        if (b.ev8_pending) { (void)hipEventSynchronize(b.ev8_ready); b.ev8_pending = false; }
+        (void)hipFree(b.d_c8); (void)hipFree(b.d_c8_meta);
+        b.d_c8 = nullptr; b.d_c8_meta = nullptr; b.c8_cap = 0; b.c8_stale = true;
+        unsigned char* nc = nullptr; float* nm = nullptr;
+        HIP_TRY(hipMalloc(&nc, (size_t)e->capacity * D), WAX_HIP_ERR_ALLOC, "Failed to allocate code mirror");
+        if (hipMalloc(&nm, (size_t)e->capacity * 2 * sizeof(float)) != hipSuccess) { (void)hipFree(nc); return fail(WAX_HIP_ERR_ALLOC, "Failed to allocate code mirror row words"); }
+        b.d_c8 = nc; b.d_c8_meta = nm; b.c8_cap = e->capacity;
+    }
+    const uint64_t count = e->count;
+    if (b.c8_stale) {
+        b.rows8 = 0; b.c8_stale = false;
+        HIP_TRY(hipMemsetAsync(b.d_c8_max, 0, sizeof(unsigned int), st), WAX_HIP_ERR_INTERNAL, "code mirror memset");
+    }
+    if (b.rows8 > count) b.rows8 = count;
+    if (b.rows8 < count) {
+        const uint64_t first = b.rows8, n_new = count - first;
+        const hipError_t err = launch_mirror8_build(e->d_store + first * D, (uint32_t)n_new, D, e->metric == WAX_HIP_METRIC_COSINE ? 1 : 0,
+                                                    b.d_c8 + first * D, b.d_c8_meta + 2 * first, b.d_c8_max, st);
+        if (err != hipSuccess) { b.c8_stale = true; return fail(WAX_HIP_ERR_INTERNAL, std::string("code mirror kernel launch: ") + hipGetErrorString(err)); }
+        HIP_TRY(hipEventRecord(b.ev8_ready, st), WAX_HIP_ERR_INTERNAL, "code mirror ready record");
+        b.ev8_pending = true;
+        b.rows8 = count;
+        b.rows8_converted += n_new;
+        b.conversions8 += 1;
+    }
+    b.c8_valid.store(true, std::memory_order_release);
     return WAX_HIP_OK;
 }
 

@@ -211,6 +211,8 @@ struct Slot {
     int k_eff = 0;
     bool timed = false;
     bool mirror = false;           // answered by the mirror scan: collect reads the certificate word and re-runs the f32 scan if it failed
+    bool mirror8 = false;          // ... and the mirror it rode was the 8-bit code mirror ("mirror_bits"): its certificate feeds the breaker
+    bool want8 = false;            // (parked) this query may ride the code mirror if the set it is launched with takes it
     float q_norm = 0.f;            // (mirror) the query's norm; the query itself is in h_query
     // "mirror_share": this ticket was parked at submit (its query waits in h_query for a pass it can share). `shared` is written before
     // the ticket is published and tells collect to look under the engine's share_mu; the other two are guarded by that mutex.
@@ -305,9 +307,25 @@ struct BatchMirror {
     hipEvent_t ev_ready = nullptr;       // recorded behind the last conversion: other workspaces' streams wait for it
     bool ev_pending = false;
     std::atomic<uint64_t> rows_converted{0}, conversions{0};   // statistics ("mirror_rows_converted" / "mirror_conversions")
-    std::atomic<int> mirror_wanted{0};   // small batches since the last mutation that a VALID mirror would have made cheaper
+    std::atomic<int> mirror_wanted{0};   // small batches since the last mutation that a VALID mirror would have made cheaper    // The 8-bit code mirror of the single-query scan (mirror8_scan.hip; DESIGN 4.1): codes + 128 and {scale, err} per row, built from
+    // the f32 store. Maintenance is deliberately simpler than the bf16 mirror's: appends convert rows [rows8, count); every other
+    // mutation (upsert, remove, removeBatch, deserialize, reallocation) marks it stale as a whole, and a stale or missing code mirror
+    // is rebuilt only when three eligible queries in a row since the last mutation wanted it (c8_wanted) — until then they take bf16.
+    std::mutex mu8;                      // serialises the (re)build only
+    unsigned char* d_c8 = nullptr;       // [c8_cap][dims] biased codes, row-major
+    float* d_c8_meta = nullptr;          // [c8_cap] float2 {scale, err}
+    unsigned int* d_c8_max = nullptr;    // one word: max ||v|| over the coded rows (grows between full conversions, like d_maxnorm)
+    uint64_t c8_cap = 0;
+    std::atomic<uint64_t> rows8{0};      // rows [0, rows8) are coded
+    std::atomic<bool> c8_valid{false};   // fast path: nothing to convert
+    std::atomic<bool> c8_stale{true};    // convert everything again
+    hipEvent_t ev8_ready = nullptr;      // recorded behind the last conversion: other slots' streams wait for it
+    bool ev8_pending = false;
+    std::atomic<int> c8_wanted{0};       // eligible queries since the last mutation that found the code mirror stale or missing
+    std::atomic<uint64_t> rows8_converted{0}, conversions8{0};   // "mirror8_rows_converted" / "mirror8_conversions"
 };
 
+constexpr int kBreakerWindow = 32, kBreakerFails = 8, kBreakerHold = 1024;   // "mirror_bits" breaker (wax_hip_engine::breaker_*)
 constexpr size_t kMirrorMaxDirty = 4096; // upserted rows remembered one by one; beyond that the mirror is converted again as a whole
 constexpr uint32_t kBatchMaxQ = 1024;   // queries per GEMM pass
 constexpr uint32_t kBatchSegBase = FUSED_MAX_K;   // slab pipeline: a candidate row = [0, kBatchSegBase) best list, then the survivor area
@@ -522,6 +540,17 @@ struct wax_hip_engine {
     std::atomic<int64_t> mirror_fill{1};
     std::vector<Slot*> share_launched;       // mirror tickets launched and not yet collected (share_mu); no event of a parked slot is ever asked
     std::atomic<uint64_t> st_mirror_fill_holds{0};   // submits parked or held by the rule + blocking collects that held the set back
+    // "mirror_bits": which mirror a single query that takes one streams. 0 (default) = auto: the 8-bit code mirror for k <= MIRROR8_MAX_K
+    // where "scan_mirror" is 1 and the store is above SCAN_KWAY_MAX_BYTES, else bf16; 8 = the code mirror wherever a mirror is taken
+    // (k <= MIRROR8_MAX_K); 16 = always bf16.
+    std::atomic<int64_t> mirror_bits{0};
+    std::atomic<uint64_t> st_mirror8_passes{0}, st_mirror8_fallbacks{0}, st_mirror8_unavailable{0}, st_mirror8_breaker_trips{0};
+    // Breaker: a corpus the 8-bit certificate cannot settle (tight clusters, duplicates) pays an 8-bit pass plus an f32 scan per query.
+    // If kBreakerFails of the last kBreakerWindow 8-bit queries were uncertified, the next kBreakerHold eligible queries take bf16;
+    // then the window starts again. (breaker_mu)
+    std::mutex breaker_mu;
+    uint32_t breaker_bits = 0;           // one bit per collected 8-bit query, newest in bit 0: 1 = uncertified
+    int64_t breaker_hold = 0;            // eligible queries still to send to bf16
     // wax_hip_search_batch_submit_device tickets (guarded by bticket_mu)
     struct BatchTicket {
         BatchCtx* c = nullptr;           // null: the batch was answered at submit time (empty engine / loop path)

@@ -155,6 +155,34 @@ struct MirrorGroupArgs {
 // Two launches on `st`: the NQ-query scan and a finish launch of NQ workgroups (one per query). 2 <= nq <= MIRROR_MAX_NQ.
 hipError_t launch_mirror_group(const MirrorGroupArgs& args, int nq, int metric, int grid_cap, hipStream_t st);
 
+// ---- mirror8_scan.hip: the same two launches over the 8-bit code mirror ("Eight bits per element") ----
+// Codes are row-scaled and stored with a +128 bias ([n_rows][dims] bytes); meta is [n_rows] {scale, err}, err an upper bound on
+// ||scale * code - x^||_2 of that row (+inf: a row that could not be coded). The key of a row is a LOWER BOUND of its distance, so the
+// certificate needs no store-wide error. Everything else a query owns travels in the bf16 structs above: `a.mirror` is unused,
+// `a.max_bits` points at one word, max ||v|| of the coded rows (dot's slack), `a.use_measured` is ignored.
+constexpr int MIRROR8_MAX_K = 16;   // largest k the code mirror answers: 64 candidates do not certify more (DESIGN 4.1's table)
+template <int DIMS>
+struct alignas(16) Mirror8ScanArgsQ {
+    MirrorScanArgs a;
+    const unsigned char* codes;
+    const float* meta;              // float2 per row
+    alignas(16) float q[DIMS];
+};
+static_assert(sizeof(Mirror8ScanArgsQ<768>) <= 4096, "HIP kernel arguments are limited to 4 KB");
+struct Mirror8GroupArgs {
+    MirrorGroupArgs g;
+    const unsigned char* codes;
+    const float* meta;
+};
+int mirror8_grid_for(uint32_t n_rows, uint32_t dims, int grid_cap);
+hipError_t launch_mirror8_scan(const MirrorScanArgs& args, const unsigned char* codes, const float* meta, const float* query, int metric,
+                               int grid_cap, hipStream_t st);
+hipError_t launch_mirror8_group(const MirrorGroupArgs& args, const unsigned char* codes, const float* meta, int nq, int metric,
+                                int grid_cap, hipStream_t st);
+// f32 rows -> codes + meta (mirror8_kernel: cosine rows normalised as mirror_kernel does); max_bits[0] = max ||v|| (atomic max)
+hipError_t launch_mirror8_build(const float* src, uint32_t n_rows, uint32_t dims, int normalize, unsigned char* codes, float* meta,
+                                unsigned int* max_bits, hipStream_t st);
+
 struct ScanVariantInfo {
     int unroll;          // row groups in flight per wave iteration
     int nt;              // 1 = non-temporal (streaming) loads

@@ -1,6 +1,7 @@
 // mirror_finish_body.inc — the body of mirror_scan.hip's finish kernels (included inside each of them; not compiled alone).
 // The finish of ONE query by one workgroup. Expects DIMS and METRIC (template parameters), `a` (the query's MirrorScanArgs) and
 // MIRROR_FINISH_QUERY (where the query's floats are: the kernel arguments for a lone query, device memory for a member of a group).
+// MIRROR_FINISH_EPS, if defined, replaces the bf16 mirror's eps in the certificate (step 5).
 // Text, not a function: the lone query's kernel then compiles to exactly the code it had before the group form existed.
     constexpr int D4 = ScanShape<DIMS>::D4;
     constexpr int GROUP = ScanShape<DIMS>::GROUP;
@@ -76,6 +77,10 @@
         // either side and the normalisations stay inside 3 D 2^-24 of ||q|| max||v||; the exact distance carries ~1e-6 of its own.
         // Without a measurement: the worst case of one rounded operand is below the batched path's two-operand constant, kept as is.
         // Cosine divides by ||q||, so both norms are 1 there.
+#ifdef MIRROR_FINISH_EPS
+        // (a unit whose approximate keys are lower bounds supplies its own slack: mirror8_scan.hip; `approx` then holds lb, not a)
+        const float eps = MIRROR_FINISH_EPS;
+#else
         const unsigned int* mb = a.max_bits;
         const float max_norm = __uint_as_float(mb[0]);
         const float max_row_err = a.use_measured ? __uint_as_float(mb[1]) : 0.f;
@@ -89,6 +94,7 @@
         }
         float eps = METRIC == M_COS ? (float)(dot_err + 3e-6) : (float)(dot_err + 1e-6 * (1.0 + qn_d * vn_d));
         eps = nextafterf(eps, __builtin_inff());             // the double -> float conversion may have rounded down
+#endif
         const int64_t a_kp = approx[MIRROR_KP - 1], kth = sorted[a.k - 1];
         const float da = key_distance(a_kp), dk = key_distance(kth);
         const bool ok = a_kp != KEY_PAD && kth != KEY_PAD && __builtin_isfinite(da) && __builtin_isfinite(dk) &&

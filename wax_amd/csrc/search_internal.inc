@@ -264,14 +264,66 @@ bool scan_uses_mirror(wax_hip_engine* e, int k_eff) {
     return mode >= 2 || e->count * (uint64_t)e->dims * sizeof(float) > SCAN_KWAY_MAX_BYTES;
 }
 
+// ---- which mirror ("mirror_bits"; DESIGN 4.1, "Eight bits per element") ----
+int ensure_mirror8(wax_hip_engine* e, hipStream_t st);   // batch_host.inc
+
+// May a single query of this engine that takes a mirror take the 8-bit code mirror? k <= MIRROR8_MAX_K, and either "mirror_bits" 8 or
+// auto mode on a store above the one-launch boundary ("scan_mirror" 2 with "mirror_bits" 0 stays bf16: forced small stores keep their path).
+static bool mirror8_eligible(wax_hip_engine* e, int k_eff) {
+    if (k_eff > MIRROR8_MAX_K) return false;
+    const int64_t bits = e->mirror_bits.load();
+    if (bits == 16) return false;
+    if (bits == 8) return true;
+    return e->scan_mirror.load() == 1 && e->count * (uint64_t)e->dims * sizeof(float) > SCAN_KWAY_MAX_BYTES;
+}
+
+// The decision for one eligible query, made once at its submit (it counts): not while the breaker holds; at once on a code mirror that
+// is valid or only lacks appended rows; a stale or missing one is rebuilt by the third query in a row since the last mutation that
+// wanted it — the first two take bf16.
+static bool mirror8_take(wax_hip_engine* e, int k_eff) {
+    if (!mirror8_eligible(e, k_eff)) return false;
+    {
+        std::unique_lock<std::mutex> bg(e->breaker_mu);
+        if (e->breaker_hold > 0) { --e->breaker_hold; return false; }
+    }
+    BatchMirror& b = e->batch;
+    if (b.c8_cap >= e->capacity && b.d_c8 != nullptr && (b.c8_valid.load(std::memory_order_acquire) || !b.c8_stale.load())) return true;
+    return b.c8_wanted.fetch_add(1) >= 2;
+}
+
+// The certificate of a collected 8-bit query feeds the breaker: kBreakerFails uncertified among the last kBreakerWindow send the next
+// kBreakerHold eligible queries to bf16, then the window starts again.
+static void mirror8_note_result(wax_hip_engine* e, bool certified) {
+    std::unique_lock<std::mutex> bg(e->breaker_mu);
+    e->breaker_bits = (e->breaker_bits << 1) | (certified ? 0u : 1u);
+    static_assert(kBreakerWindow == 32, "the window is one 32-bit word");
+    if (__builtin_popcount(e->breaker_bits) >= kBreakerFails) {
+        e->breaker_bits = 0;
+        e->breaker_hold = kBreakerHold;
+        e->st_mirror8_breaker_trips++;
+    }
+}
+
+// the code mirror for a launch on `st`: false = it could not be prepared (allocation, conversion launch) and the launch takes bf16
+static bool mirror8_ready(wax_hip_engine* e, hipStream_t st, uint64_t nq) {
+    const std::string keep = g_last_error;
+    BatchMirror& b = e->batch;
+    if (ensure_mirror8(e, st) == WAX_HIP_OK && b.d_c8 != nullptr && b.d_c8_meta != nullptr && b.d_c8_max != nullptr) return true;
+    (void)hipGetLastError();
+    g_last_error = keep;
+    e->st_mirror8_unavailable += nq;
+    return false;
+}
+
 // Enqueue the mirror scan + finish of one query on the slot's stream (the kpad hits and the certificate word land in the slot's pinned
 // memory). *took = false: the mirror could not be prepared (allocation, conversion launch) and nothing was enqueued — the caller takes
 // the f32 scan; a query never fails because of the mirror. Same chain and timing semantics as the fused f32 branch of enqueue_scan:
 // "time_kernels" 2 binds the event pair to the mirror_scan_kernel dispatch, 1 brackets the two launches.
-int enqueue_mirror_scan(wax_hip_engine* e, Slot* s, const float* query, float q_norm, int k_eff, int tk_mode, bool* took) {
+int enqueue_mirror_scan(wax_hip_engine* e, Slot* s, const float* query, float q_norm, int k_eff, int tk_mode, bool* took, bool want8 = false) {
     *took = false;
     BatchMirror& b = e->batch;
-    {
+    const bool use8 = want8 && mirror8_ready(e, s->stream, 1);
+    if (!use8) {
         const std::string keep = g_last_error;
         if (ensure_mirror(e, s->stream) != WAX_HIP_OK || b.d_cb == nullptr || b.d_maxnorm == nullptr) {
             (void)hipGetLastError();                      // a refused allocation must not surface in the f32 launch behind it
@@ -289,7 +341,7 @@ int enqueue_mirror_scan(wax_hip_engine* e, Slot* s, const float* query, float q_
     m.ids = e->d_ids;
     m.hits = s->h_hits;
     m.certified = slot_cert_word(s->h_done);
-    m.max_bits = b.d_maxnorm;
+    m.max_bits = use8 ? b.d_c8_max : b.d_maxnorm;
     m.n_rows = (uint32_t)e->count;
     m.row_base = (uint32_t)e->row_base;
     m.dims = e->dims;
@@ -308,7 +360,9 @@ int enqueue_mirror_scan(wax_hip_engine* e, Slot* s, const float* query, float q_
     }
     if (ev0 && !bound) HIP_TRY(hipEventRecord(ev0, s->stream), WAX_HIP_ERR_INTERNAL, "event record");
     if (bound) launch_timing() = LaunchTiming{ev0, ev1};
-    const hipError_t lerr = launch_mirror_scan(m, query, e->metric, (int)e->grid_blocks.load(), s->stream);
+    if (use8) m.mirror = nullptr;
+    const hipError_t lerr = use8 ? launch_mirror8_scan(m, b.d_c8, b.d_c8_meta, query, e->metric, (int)e->grid_blocks.load(), s->stream)
+                                 : launch_mirror_scan(m, query, e->metric, (int)e->grid_blocks.load(), s->stream);
     launch_timing() = LaunchTiming{};
     HIP_TRY(lerr, WAX_HIP_ERR_INTERNAL, "mirror scan launch");
     if (ev1 && !bound) HIP_TRY(hipEventRecord(ev1, s->stream), WAX_HIP_ERR_INTERNAL, "event record");
@@ -321,11 +375,13 @@ int enqueue_mirror_scan(wax_hip_engine* e, Slot* s, const float* query, float q_
     }
     *took = true;
     s->mirror = true;
+    s->mirror8 = use8;
     e->st_mirror_scans++;
     e->st_mirror_passes++;
+    if (use8) e->st_mirror8_passes++;
     e->st_searches++;
     e->st_rows += e->count;
-    e->st_bytes += e->count * (uint64_t)e->dims * 2ull + (uint64_t)MIRROR_KP * e->dims * 4ull;
+    e->st_bytes += e->count * (use8 ? (uint64_t)e->dims + 8ull : (uint64_t)e->dims * 2ull) + (uint64_t)MIRROR_KP * e->dims * 4ull;
     return WAX_HIP_OK;
 }
 
@@ -343,6 +399,7 @@ static int64_t mirror_share_mode(wax_hip_engine* e, int tk_mode) {
 // the f32 scan of a parked query on its own slot and stream (the mirror could not be prepared)
 static int parked_take_f32(wax_hip_engine* e, Slot* s) {
     s->mirror = false;
+    s->mirror8 = false;
     const int rc = enqueue_scan(e, nullptr, s->q_norm, s->k_eff, s->k_eff, s->d_partials, s, s->h_hits, s->stream, nullptr, nullptr,
                                 /*chain=*/false, nullptr, nullptr, s->h_query);
     if (rc != WAX_HIP_OK) return rc;
@@ -356,7 +413,10 @@ static int enqueue_mirror_group(wax_hip_engine* e, Slot* const* grp, int nq, boo
     *took = false;
     BatchMirror& b = e->batch;
     hipStream_t st = grp[0]->stream;
-    {
+    bool use8 = true;                      // one mirror per set: bf16 as soon as one member cannot ride the code mirror (k, breaker, rebuild count)
+    for (int i = 0; i < nq; ++i) use8 = use8 && grp[i]->want8;
+    use8 = use8 && mirror8_ready(e, st, (uint64_t)nq);
+    if (!use8) {
         const std::string keep = g_last_error;
         if (ensure_mirror(e, st) != WAX_HIP_OK || b.d_cb == nullptr || b.d_maxnorm == nullptr) {
             (void)hipGetLastError();
@@ -369,7 +429,8 @@ static int enqueue_mirror_group(wax_hip_engine* e, Slot* const* grp, int nq, boo
     g.a.mirror = b.d_cb;
     g.a.store = e->d_store;
     g.a.ids = e->d_ids;
-    g.a.max_bits = b.d_maxnorm;
+    g.a.max_bits = use8 ? b.d_c8_max : b.d_maxnorm;
+    if (use8) g.a.mirror = nullptr;
     g.a.n_rows = (uint32_t)e->count;
     g.a.row_base = (uint32_t)e->row_base;
     g.a.dims = e->dims;
@@ -387,19 +448,22 @@ static int enqueue_mirror_group(wax_hip_engine* e, Slot* const* grp, int nq, boo
         s->t_start = nullptr;
         s->t_end = nullptr;
     }
-    HIP_TRY(launch_mirror_group(g, nq, e->metric, (int)e->grid_blocks.load(), st), WAX_HIP_ERR_INTERNAL, "mirror group launch");
+    HIP_TRY(use8 ? launch_mirror8_group(g, b.d_c8, b.d_c8_meta, nq, e->metric, (int)e->grid_blocks.load(), st)
+                 : launch_mirror_group(g, nq, e->metric, (int)e->grid_blocks.load(), st), WAX_HIP_ERR_INTERNAL, "mirror group launch");
     for (int i = 0; i < nq; ++i) {
         HIP_TRY(hipEventRecord(grp[i]->ev_done, st), WAX_HIP_ERR_INTERNAL, "event record");
         grp[i]->mirror = true;
+        grp[i]->mirror8 = use8;
     }
     *took = true;
     e->st_mirror_scans += (uint64_t)nq;
     e->st_mirror_passes++;
     e->st_mirror_shared_passes++;
+    if (use8) e->st_mirror8_passes++;
     e->st_mirror_shared_queries += (uint64_t)nq;
     e->st_searches += (uint64_t)nq;
     e->st_rows += e->count * (uint64_t)nq;
-    e->st_bytes += e->count * (uint64_t)e->dims * 2ull + (uint64_t)nq * MIRROR_KP * e->dims * 4ull;
+    e->st_bytes += e->count * (use8 ? (uint64_t)e->dims + 8ull : (uint64_t)e->dims * 2ull) + (uint64_t)nq * MIRROR_KP * e->dims * 4ull;
     return WAX_HIP_OK;
 }
 
@@ -412,7 +476,7 @@ static void launch_parked(wax_hip_engine* e) {
     const int nq = (int)grp.size();
     bool took = false;
     int rc;
-    if (nq == 1) rc = enqueue_mirror_scan(e, grp[0], grp[0]->h_query, grp[0]->q_norm, grp[0]->k_eff, 0, &took);   // alone after all: the lone query's kernels
+    if (nq == 1) rc = enqueue_mirror_scan(e, grp[0], grp[0]->h_query, grp[0]->q_norm, grp[0]->k_eff, 0, &took, grp[0]->want8);   // alone after all: the lone query's kernels
     else rc = enqueue_mirror_group(e, grp.data(), nq, &took);
     if (rc == WAX_HIP_OK && took) {
         if (nq == 1) {

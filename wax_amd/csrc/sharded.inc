@@ -1521,6 +1521,7 @@ int64_t sh_get_tuning(wax_hip_engine* e, const std::string& k) {
     if (k == "batch_queries" || k == "batch_fallbacks" || k == "batch_retries" || k == "onepass_queries" || k == "filter_device_searches" || k == "filter_batch_queries" || k == "filter_batch_fallbacks" || k == "query_args_scans" || k == "batch_inline_retries" ||
         k == "batch_multi_passes" || k == "batch_multi_queries" || k == "short_selects" || k == "short_select_failures" ||
         k == "mirror_scans" || k == "mirror_scan_fallbacks" || k == "mirror_scan_unavailable" || k == "mirror_passes" || k == "mirror_shared_passes" || k == "mirror_shared_queries" || k == "mirror_fill_holds" ||
+        k == "mirror8_passes" || k == "mirror8_fallbacks" || k == "mirror8_unavailable" || k == "mirror8_conversions" || k == "mirror8_rows_converted" || k == "mirror8_breaker_trips" ||
         k == "remove_batches" || k == "remove_batch_rows" || k == "remove_batch_bytes_written" ||
         k == "predicate_searches" || k == "predicate_gather_searches" || k == "predicate_masked_scans" || k == "predicate_chunks_skipped" ||
         k == "attr_uploaded_rows" || k == "attr_device_rows") {   // counters: summed over the shards

@@ -45,6 +45,7 @@ int wax_hip_set_tuning(wax_hip_engine* e, const char* key, int64_t value) {
     else if (k == "scan_plain_mb") e->scan_plain_mb = value;
     else if (k == "scan_mirror") { if (value < 0 || value > 2) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "scan_mirror must be 0, 1 or 2"); e->scan_mirror = value; }
     else if (k == "mirror_share") { if (value < 0 || value > 2) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror_share must be 0, 1 or 2"); e->mirror_share = value; }
+    else if (k == "mirror_bits") { if (value != 0 && value != 8 && value != 16) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror_bits must be 0, 8 or 16"); e->mirror_bits = value; }
     else if (k == "mirror_fill") { if (value < 0 || value > 1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror_fill must be 0 or 1"); e->mirror_fill = value; }
     else if (k == "query_args") { if (value < 0 || value > 2) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "query_args must be 0, 1 or 2"); e->query_args = value; }
     else if (k == "batch_min") e->batch_min = value;
@@ -149,6 +150,13 @@ int64_t wax_hip_get_tuning(wax_hip_engine* e, const char* key) {
     if (k == "mirror_shared_passes") return (int64_t)e->st_mirror_shared_passes.load();      // ... of which with two or more queries
     if (k == "mirror_shared_queries") return (int64_t)e->st_mirror_shared_queries.load();    // queries answered by those
     if (k == "mirror_fill") return e->mirror_fill.load();
+    if (k == "mirror_bits") return e->mirror_bits.load();
+    if (k == "mirror8_passes") return (int64_t)e->st_mirror8_passes.load();              // passes over the 8-bit code mirror (lone or shared; also counted in "mirror_passes")
+    if (k == "mirror8_fallbacks") return (int64_t)e->st_mirror8_fallbacks.load();        // 8-bit queries whose certificate failed (also counted in "mirror_scan_fallbacks")
+    if (k == "mirror8_unavailable") return (int64_t)e->st_mirror8_unavailable.load();    // queries sent to bf16 because the code mirror could not be prepared
+    if (k == "mirror8_conversions") return (int64_t)e->batch.conversions8.load();        // code mirror: conversions enqueued / rows converted so far
+    if (k == "mirror8_rows_converted") return (int64_t)e->batch.rows8_converted.load();
+    if (k == "mirror8_breaker_trips") return (int64_t)e->st_mirror8_breaker_trips.load();
     if (k == "mirror_fill_holds") return (int64_t)e->st_mirror_fill_holds.load();            // submits parked / held and blocking collects that held the parked set back ("mirror_fill" 1)
     if (k == "done_flag_waits") return (int64_t)e->st_flag_waits.load();
     if (k == "query_args_scans") return (int64_t)e->st_query_args.load();
