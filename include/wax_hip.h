@@ -417,6 +417,29 @@ int wax_hip_search_predicate(wax_hip_engine* e, const float* query, uint32_t dim
 int wax_hip_search_many_predicate(wax_hip_engine* const* engines, const float* queries, uint32_t n, uint32_t dims, int32_t top_k,
                                   const wax_hip_row_predicate* preds, const float* min_scores,
                                   uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts);
+/* wax_hip_search_batch_filtered with a row predicate PER QUERY: nq queries against ONE store, each with its own allow-list, score cut
+ * and predicate. preds: nq entries, or NULL = no query has one; every other argument means what it means in
+ * wax_hip_search_batch_filtered. Row q equals, bit for bit (ids, scores, count, ties in ascending row order),
+ * wax_hip_search_predicate(e, query q, dims, top_k, has list q, list q, len q, min_scores != NULL, min_scores[q], &preds[q], ...)
+ * with out_capacity = out_stride. A query whose predicate has no bound and no deny bit is a wax_hip_search_batch_filtered query, and
+ * with preds == NULL the call IS wax_hip_search_batch_filtered (one body serves both): the same launches, the same counters.
+ * Refusals (their order, their messages, outputs untouched), the sharded dispatch and the snapshot are that call's.
+ * Queries with the same (begin, len | no list, predicate) — an unused bound's value does not count — share an ENTRY and its groups
+ * of up to 16 queries. Every entry becomes a compact ascending row list with a device-side count: a list of at most 16 384 ids by the
+ * LDS sort, rows that fail the predicate dropped before the sort; a longer list by the single-query route's launches (probe,
+ * attribute mask ANDed into the bitmap, compaction); an entry without a list straight from the attribute columns, ALL such entries of
+ * the call in three launches. One gather launch then scores every entry, one merge attaches ids: one download, one synchronisation,
+ * no host round trip for pass counts. Every group of 16 queries re-reads its entry's passing rows, so a predicate that
+ * passes most of a large store costs about nq / 16 passes over it. A store on which attributes were never set reads (0, 0) in every
+ * row: its predicates are decided on the host (the query loses its predicate, or its count is 0 without device work). Entries with a
+ * predicate are admitted in order of their first query while their upper bounds (min(len, count); count without a list) fit
+ * "predicate_batch_rows" row slots; the queries of the rest, and every query where wax_hip_search_batch_filtered itself falls back
+ * (top_k > 192, other dimensions, "filter_batch" 0, "force_general"), take the single-query predicate search under the lock held. */
+int wax_hip_search_batch_predicate(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
+                                   const uint64_t* allow_frame_ids, uint64_t n_allow_ids,
+                                   const uint64_t* allow_begin, const uint64_t* allow_len,
+                                   const float* min_scores, const wax_hip_row_predicate* preds,
+                                   uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts);
 
 /* ---- persistence: "MV2V" vec segment, encoding 2 ------------------------- */
 
@@ -496,7 +519,12 @@ int wax_hip_stats(wax_hip_engine* e, wax_hip_stats_t* out);
  *   "filter_device_min" (wax_hip_search_filtered: allow-lists at least this long are resolved by the id -> row table in HBM, default 4096; -1 = never),
  *   "filter_batch" (wax_hip_search_batch_filtered: 1 (default) = one gather pass for all allow-lists; 0 = the single-query filtered path
  *   per query), "filter_batch_queries" / "filter_batch_fallbacks" (read-only: listed queries answered by the gather pass / by the
- *   per-query path),
+ *   per-query path; wax_hip_search_batch_predicate counts its queries with a predicate and no list here too),
+ *   "predicate_batch_rows" (wax_hip_search_batch_predicate: row slots one call may spend on entries with a predicate, 0..2^31-1;
+ *   default 67108864 = 256 MB of row indices, a memory cap and not a tuned number; entries beyond it take the single-query predicate
+ *   search), "predicate_batch_queries" / "predicate_batch_classes" (read-only: queries with an effective predicate — not empty, and not
+ *   decided on the host for a store without attributes — that the batched gather pass answered / entries with a predicate it built;
+ *   "predicate_searches" counts such queries whatever the route),
  *   "search_many" (wax_hip_search_many: 1 (default) = this engine's pairs may share the call's pooled launch; 0 = each runs the
  *   single-query search), "search_many_max_rows" (engines holding more rows than this always take the single-query search; default
  *   262144, the first power of two above the vec segment cap at 384-d), "search_many_pooled" / "search_many_looped" (read-only: pairs

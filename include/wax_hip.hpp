@@ -67,6 +67,33 @@ class VectorEngine {
             for (uint32_t i = 0; i < counts[q]; ++i) out[q].emplace_back(ids[(size_t)q * stride + i], scores[(size_t)q * stride + i]);
         return out;
     }
+    /// searchBatchFiltered plus a row predicate per query (wax_hip_search_batch_predicate): `preds` holds one entry per query or is
+    /// empty (no query has one). Query q is what searchPredicate(query q, topK, allow[q], cut q, preds[q]) returns.
+    std::vector<std::vector<std::pair<uint64_t, float>>> searchBatchPredicate(const std::vector<float>& queries, uint32_t nq, int topK,
+                                                                              const std::vector<const std::vector<uint64_t>*>& allow,
+                                                                              const std::vector<float>* minScores,
+                                                                              const std::vector<wax_hip_row_predicate>& preds) {
+        if (!preds.empty() && preds.size() != nq) throw std::invalid_argument("searchBatchPredicate: one predicate per query, or none");
+        const uint32_t dims = nq ? (uint32_t)(queries.size() / nq) : 0;
+        const uint32_t stride = wax_hip_result_capacity(topK);
+        std::vector<uint64_t> flat, begin(nq), len(nq);
+        for (uint32_t q = 0; q < nq; ++q) {
+            const std::vector<uint64_t>* a = q < allow.size() ? allow[q] : nullptr;
+            begin[q] = flat.size();
+            len[q] = a ? a->size() : WAX_HIP_NO_ALLOW_LIST;
+            if (a) flat.insert(flat.end(), a->begin(), a->end());
+        }
+        std::vector<uint64_t> ids((size_t)nq * stride);
+        std::vector<float> scores((size_t)nq * stride);
+        std::vector<uint32_t> counts(nq);
+        check(wax_hip_search_batch_predicate(h_, queries.data(), nq, dims, topK, flat.data(), flat.size(), begin.data(), len.data(),
+                                             minScores ? minScores->data() : nullptr, preds.empty() ? nullptr : preds.data(), ids.data(),
+                                             scores.data(), stride, counts.data()));
+        std::vector<std::vector<std::pair<uint64_t, float>>> out(nq);
+        for (uint32_t q = 0; q < nq; ++q)
+            for (uint32_t i = 0; i < counts[q]; ++i) out[q].emplace_back(ids[(size_t)q * stride + i], scores[(size_t)q * stride + i]);
+        return out;
+    }
     void add(uint64_t frameId, const std::vector<float>& v) { check(wax_hip_add(h_, frameId, v.data(), (uint32_t)v.size())); }
     /// Allow-list / minScore filtered search (UnifiedSearch.swift:1241-1258): best topK among the allowed frames.
     std::vector<std::pair<uint64_t, float>> searchFiltered(const std::vector<float>& q, int topK,

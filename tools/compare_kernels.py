@@ -8,6 +8,8 @@ Each revision is checked out into a temporary worktree and every unit is compile
 One line per kernel (and per out-of-line device function): `identical`, or `DIFFERENT` with both resource lines
 (VGPRs, AGPR offset, SGPRs, LDS bytes, scratch bytes). Comments are dropped and local labels renumbered per function, so a
 kernel that only moved inside its file compares equal. Exit status 1 if anything differs.
+`--renamed OLD=NEW` (demangled names, repeatable) compares REV_A's OLD with REV_B's NEW: a kernel that became one instantiation of a
+template keeps its instructions under another symbol. Every mention of either symbol inside the text is replaced by one token first.
 """
 import argparse
 import os
@@ -95,6 +97,7 @@ def main():
     ap.add_argument("rev_b")
     ap.add_argument("--units", default=",".join(UNITS))
     ap.add_argument("--keep", default=None, help="keep the .s files in this directory")
+    ap.add_argument("--renamed", action="append", default=[], metavar="OLD=NEW", help="REV_A's kernel OLD is REV_B's kernel NEW (demangled names)")
     args = ap.parse_args()
     units = args.units.split(",")
     work = tempfile.mkdtemp(prefix="compare_kernels.")
@@ -119,6 +122,26 @@ def main():
         for u in units:
             a, b = parse(os.path.join(work, "a_%s.s" % u)), parse(os.path.join(work, "b_%s.s" % u))
             pretty = demangle(sorted(set(a) | set(b)))
+            for pair in args.renamed:
+                old, new = pair.split("=", 1)
+                olds = [m for m in a if old in pretty[m] and m not in b]       # (demangled names carry the signature: match by substring)
+                news = [m for m in b if new in pretty[m] and m not in a]
+                if len(olds) == 1 and len(news) == 1:
+                    # one entry under the old symbol on both sides. Made equal first: the symbol's own mentions, the section directive
+                    # (a template's instantiation sits in a comdat section of its own) and the kernel-argument size, which is printed
+                    # beside the name when it changed (a trailing argument the old kernel does not read)
+                    def strip(t):
+                        if t is None:
+                            return None
+                        t = t.replace(news[0], "@KERNEL").replace(olds[0], "@KERNEL")
+                        return "\n".join(x for x in t.split("\n") if x.split()[:1] not in ([".text"], [".section"], [".amdhsa_kernarg_size"]))
+                    karg = [[x.split()[1] for x in (t[1] or "").split("\n") if x.startswith(".amdhsa_kernarg_size")] for t in (a[olds[0]], b[news[0]])]
+                    a[olds[0]] = (strip(a[olds[0]][0]), strip(a[olds[0]][1]), a[olds[0]][2])
+                    b[olds[0]] = (strip(b[news[0]][0]), strip(b[news[0]][1]), b[news[0]][2])
+                    del b[news[0]]
+                    if karg[0] != karg[1]:
+                        new += "; kernarg bytes %s -> %s" % ("".join(karg[0]), "".join(karg[1]))
+                    pretty[olds[0]] = "%s  (now %s)" % (old, new)
             same = 0
             print("## %s: %d functions before, %d after" % (u, len(a), len(b)))
             for name in sorted(set(a) | set(b), key=lambda n: pretty[n]):

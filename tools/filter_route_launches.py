@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""The kernels each route of the single-query filtered / predicate search launches, in order.
+"""The kernels each route of the single-query filtered / predicate search launches, in order, and those of one batched predicate
+call.
 
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/filter_route_launches.py
     python tools/filter_route_launches.py --trace DIR/.../*_kernel_trace.csv > launches.txt
 
 Without --trace: a 4 099 x 384 cosine store with attributes, every route warmed once (workspaces, id table, attribute columns),
-then ONE call per route with a one-list rank fusion between two calls — its kernel is the separator in the trace.
+then ONE call per route with a one-list rank fusion between two calls — its kernel is the separator in the trace. The last call is
+the batched one: 256 queries, 16 distinct time windows of 1/16 of the rows, 16 queries each, no allow-list.
 With --trace: the dispatches of that run's kernel trace in start order, cut at the separators: one `name grid` line per launch
 under the route's title. Two builds launch the same sequence when their outputs are equal."""
 import argparse
@@ -30,6 +32,7 @@ CALLS = [
     ("predicate and long list, gather route", "long", B_HALF, 1, 10),
     ("predicate and long list, masked scan", "long", B_HALF, 2, 10),
 ]
+BATCH_TITLE = "batched predicates: 16 windows x 16 queries, no list (three row-list launches, one gather, one merge)"
 
 
 def run():
@@ -55,6 +58,18 @@ def run():
     for _, allow, deny, route, k in CALLS:
         rrfFusionArrays([(1.0, [1, 2, 3])])
         call(allow, deny, route, k)
+    eng.setTuning("predicate_route", 0)
+    qs = oracle.gaussian_unit_queries(256, dims)
+    windows = [(j * (n - n // 16) // 16 + 1, j * (n - n // 16) // 16 + 1 + n // 16) for j in range(16)]
+
+    def batched():
+        before = eng.getTuning("predicate_batch_queries")
+        _, _, counts = eng.searchBatchFiltered(qs, 10, timeRange=[windows[q // 16] for q in range(256)])
+        assert (counts == 10).all() and eng.getTuning("predicate_batch_queries") - before == 256
+
+    batched()
+    rrfFusionArrays([(1.0, [1, 2, 3])])
+    batched()
     eng.close()
 
 
@@ -73,9 +88,10 @@ def report(path):
         elif cur is not None:
             grid = [r.get(f"Grid_Size_{a}") for a in "XYZ"]
             cur.append(f"{name}  grid {r.get('Grid_Size') or 'x'.join(g for g in grid if g)}")
-    assert len(calls) == len(CALLS), f"{len(calls)} separators in the trace for {len(CALLS)} calls"
+    titles = [c[0] for c in CALLS] + [BATCH_TITLE]
+    assert len(calls) == len(titles), f"{len(calls)} separators in the trace for {len(titles)} calls"
     assert all(calls), "a call without a single kernel: the separators do not bracket the calls"
-    for (title, *_), launches in zip(CALLS, calls):
+    for title, launches in zip(titles, calls):
         print(f"## {title}")
         for ln in launches:
             print(ln)

@@ -113,6 +113,9 @@ SIGNATURES: Dict[str, tuple] = {
                                                ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
     "wax_hip_search_batch_filtered": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, _u64p,
                                                      ctypes.c_uint64, _u64p, _u64p, _f32p, _u64p, _f32p, ctypes.c_uint32, _u32p]),
+    "wax_hip_search_batch_predicate": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, _u64p,
+                                                      ctypes.c_uint64, _u64p, _u64p, _f32p, ctypes.POINTER(RowPredicate), _u64p, _f32p,
+                                                      ctypes.c_uint32, _u32p]),
     "wax_hip_search_many": (ctypes.c_int, [ctypes.POINTER(_engine_p), _f32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, _u64p, _f32p,
                                            ctypes.c_uint32, _u32p]),
     "wax_hip_search_many_predicate": (ctypes.c_int, [ctypes.POINTER(_engine_p), _f32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32,

@@ -593,6 +593,10 @@ struct wax_hip_engine {
     std::atomic<uint64_t> st_filter_device{0};    // filtered searches whose allow-list was resolved on the device
     std::atomic<int64_t> filter_batch{1};         // wax_hip_search_batch_filtered: 1 = one gather pass for all lists, 0 = the per-query loop
     std::atomic<uint64_t> st_filter_batch_queries{0}, st_filter_batch_fallbacks{0};
+    // wax_hip_search_batch_predicate: row slots one call may spend on entries with a predicate (an entry without a list costs `count`
+    // whatever passes). 2^26 slots = 256 MB of row indices: a memory cap, not a tuned number.
+    std::atomic<int64_t> predicate_batch_rows{1ll << 26};
+    std::atomic<uint64_t> st_predicate_batch_queries{0}, st_predicate_batch_classes{0};   // predicates the batched pass answered / entries with one it built
     // wax_hip_search_many (DESIGN 4.8): 1 = this engine's pairs may share the pooled launch, 0 = each takes the single-query search;
     // stores above search_many_max_rows rows always do. 262 144 = the first power of two above the vec segment cap at 384-d
     // (a placeholder until tools/search_many_bench.py has been run: DESIGN 4.8).
@@ -681,9 +685,9 @@ int sh_search_batch_hits(wax_hip_engine* e, const float* queries, uint32_t nq, u
 int sh_batch_device(wax_hip_engine* e, const float* d_queries, uint32_t nq, uint32_t dims, int32_t top_k, wax_hip_hit* d_out_hits,
                     uint32_t out_stride, void* stream, uint64_t* ticket);
 int sh_batch_collect_device(wax_hip_engine* e, uint64_t ticket, uint32_t* out_fallbacks);
-int sh_search_batch_filtered(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k, const uint64_t* allow,
-                             uint64_t n_allow_ids, const uint64_t* allow_begin, const uint64_t* allow_len, const float* min_scores, uint64_t* out_ids,
-                             float* out_scores, uint32_t out_stride, uint32_t* out_counts);
+int sh_search_batch_predicate(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k, const uint64_t* allow,
+                              uint64_t n_allow_ids, const uint64_t* allow_begin, const uint64_t* allow_len, const float* min_scores,
+                              const wax_hip_row_predicate* preds, uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts);
 int sh_search_filtered(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, int has_allow, const uint64_t* allow,
                        uint64_t n_allow, int has_min, float min_score, uint64_t* out_ids, float* out_scores, uint32_t capacity,
                        uint32_t* out_count);

@@ -7,7 +7,8 @@
 //                          rows back ascending and unique — the order every selection path breaks ties in.
 //   bitmap_count / bitmap_scan / bitmap_emit   bitmap -> compact ascending row list + the rows' frame ids.
 //   rowlist_sort_kernel    batched filtered search: one workgroup per allow-list of <= ROWLIST_SORT_MAX ids probes, sorts the
-//                          rows in LDS (bitonic) and writes them ascending and unique with a device-side count.
+//                          rows in LDS (bitonic) and writes them ascending and unique with a device-side count. PRED = true
+//                          (batched predicates) drops the probed rows that fail the list's row predicate before the sort.
 //
 // All HBM-latency work: at a 1M-id allow-list the probes are ~2M random 64-byte sector reads, a few tens of µs on the
 // device against 5.65 ms of cache-missing host probes (profiles/r01).
@@ -61,17 +62,34 @@ __global__ __launch_bounds__(256) void idhash_probe_kernel(const uint64_t* __res
 
 // One workgroup per list: probe every id into LDS (kNoRow for an id the store lacks), bitonic sort of the next power of two,
 // then keep the first of every run of equal rows (duplicate ids) and drop kNoRow; a workgroup-wide scan places the survivors.
+// PRED (wax_hip_search_batch_predicate): list blockIdx.x carries the row predicate preds[blockIdx.x]; a probed row that fails it
+// becomes kNoRow before the sort. PRED = false never reads `preds` and is the kernel of the lists without a predicate.
 constexpr int kSortThreads = 1024;
+template <bool PRED>
 __global__ __launch_bounds__(kSortThreads) void rowlist_sort_kernel(const uint64_t* __restrict__ allow, const RowListDesc* __restrict__ desc,
                                                                     const uint64_t* __restrict__ ids, const uint32_t* __restrict__ table,
-                                                                    uint32_t mask, uint32_t* __restrict__ rows_out, uint32_t* counts) {
+                                                                    uint32_t mask, uint32_t* __restrict__ rows_out, uint32_t* counts,
+                                                                    const RowListPred* __restrict__ preds) {
     extern __shared__ uint32_t srt[];              // [P]
     __shared__ uint32_t wave_sum[kSortThreads / 64];
     const RowListDesc d = desc[blockIdx.x];
     const uint32_t t = threadIdx.x;
     uint32_t P = 64;
     while (P < d.len) P <<= 1;                     // len <= ROWLIST_SORT_MAX (host-checked)
-    for (uint32_t i = t; i < P; i += kSortThreads) srt[i] = i < d.len ? idhash_lowest_row(allow[d.allow_off + i], ids, table, mask) : kNoRow;
+    if constexpr (PRED) {
+        const RowListPred p = preds[blockIdx.x];
+        for (uint32_t i = t; i < P; i += kSortThreads) {
+            uint32_t row = i < d.len ? idhash_lowest_row(allow[d.allow_off + i], ids, table, mask) : kNoRow;
+            if (row != kNoRow) {
+                const int64_t ts = p.ts != nullptr ? p.ts[row] : 0;
+                const uint32_t fl = p.flags != nullptr ? p.flags[row] : 0u;
+                if (!attr_row_passes(p.has_after, p.after, p.has_before, p.before, p.deny_flags, ts, fl)) row = kNoRow;
+            }
+            srt[i] = row;
+        }
+    } else {
+        for (uint32_t i = t; i < P; i += kSortThreads) srt[i] = i < d.len ? idhash_lowest_row(allow[d.allow_off + i], ids, table, mask) : kNoRow;
+    }
     __syncthreads();
     for (uint32_t kk = 2; kk <= P; kk <<= 1) {
         for (uint32_t j = kk >> 1; j > 0; j >>= 1) {
@@ -217,20 +235,25 @@ hipError_t launch_allow_probe(const uint64_t* d_allow, uint64_t n_allow, const u
     return launch_bitmap_offsets(bitmap, n_rows, block_sum, total, st);
 }
 
-hipError_t launch_rowlist_sort(const uint64_t* d_allow, const RowListDesc* d_desc, uint32_t n_lists, uint32_t max_len, const uint64_t* ids,
-                               const uint32_t* table, uint64_t slots, uint32_t* rows_out, uint32_t* counts, hipStream_t st) {
+hipError_t launch_rowlist_sort(const uint64_t* d_allow, const RowListDesc* d_desc, const RowListPred* d_preds, uint32_t n_lists, uint32_t max_len,
+                               const uint64_t* ids, const uint32_t* table, uint64_t slots, uint32_t* rows_out, uint32_t* counts, hipStream_t st) {
     if (n_lists == 0) return hipSuccess;
     if (max_len > ROWLIST_SORT_MAX) return hipErrorInvalidValue;
     uint32_t P = 64;
     while (P < max_len) P <<= 1;
     const size_t smem = (size_t)P * sizeof(uint32_t);
-    static std::atomic<uint64_t> configured{0};   // per device (ensure_dynamic_lds)
+    static std::atomic<uint64_t> configured{0}, configured_pred{0};   // per device (ensure_dynamic_lds), per instantiation
     if (smem > 64 * 1024 - 256) {
-        const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&rowlist_sort_kernel), 96 * 1024, configured);
+        const hipError_t e = d_preds ? ensure_dynamic_lds(reinterpret_cast<const void*>(&rowlist_sort_kernel<true>), 96 * 1024, configured_pred)
+                                     : ensure_dynamic_lds(reinterpret_cast<const void*>(&rowlist_sort_kernel<false>), 96 * 1024, configured);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(rowlist_sort_kernel, dim3(n_lists), dim3(kSortThreads), smem, st, d_allow, d_desc, ids, table,
-                       (uint32_t)(slots - 1), rows_out, counts);
+    if (d_preds)
+        hipLaunchKernelGGL(rowlist_sort_kernel<true>, dim3(n_lists), dim3(kSortThreads), smem, st, d_allow, d_desc, ids, table,
+                           (uint32_t)(slots - 1), rows_out, counts, d_preds);
+    else
+        hipLaunchKernelGGL(rowlist_sort_kernel<false>, dim3(n_lists), dim3(kSortThreads), smem, st, d_allow, d_desc, ids, table,
+                           (uint32_t)(slots - 1), rows_out, counts, d_preds);
     return hipGetLastError();
 }
 

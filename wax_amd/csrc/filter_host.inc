@@ -1,6 +1,7 @@
 // filter_host.inc — part of engine.hip's translation unit (included there; not compiled alone).
 // C ABI: the filtered searches, host side (SURVEY 8f-4; DESIGN 4.5; passesFrameFilter, UnifiedSearch.swift:1241-1258) — one query with an
-// allow-list and / or a row predicate (one locked body, built from the steps below), and the batched allow-list form
+// allow-list and / or a row predicate (one locked body, built from the steps below), and the batched form (a list, a predicate and a
+// cut per query)
 
 // ---- the steps --------------------------------------------------------------------
 
@@ -9,6 +10,16 @@ static inline bool predicate_is_empty(const wax_hip_row_predicate* p) {
 }
 static inline bool predicate_passes(const wax_hip_row_predicate& p, int64_t ts, uint32_t fl) {
     return !(p.has_after != 0 && ts < p.after) && !(p.has_before != 0 && ts >= p.before) && (fl & p.deny_flags) == 0u;
+}
+
+// A row predicate with the values of its unused bounds set to 0: two pairs whose predicates test the same thing compare equal.
+static inline wax_hip_row_predicate normalised_predicate(const wax_hip_row_predicate* p) {
+    wax_hip_row_predicate r{};
+    if (!p) return r;
+    r.has_after = p->has_after != 0; r.after = r.has_after ? p->after : 0;
+    r.has_before = p->has_before != 0; r.before = r.has_before ? p->before : 0;
+    r.deny_flags = p->deny_flags;
+    return r;
 }
 
 // `score < minScore` drops a candidate (UnifiedSearch.swift:1248); results are best-first. A NaN cut keeps everything.
@@ -281,64 +292,129 @@ static int check_batch_allow(uint32_t nq, const uint64_t* allow, uint64_t n_allo
     return WAX_HIP_OK;
 }
 
-// The queries with an allow-list (fq), under the caller's shared lock: ONE gather pass for all their lists (filter.hip sorts the
-// lists into compact row lists, multiscan.hip's gather form scores every list against the queries that share it, the span merge
-// attaches frame ids), one download, one synchronisation. What that pass does not serve takes search_rows_locked per query.
+// How the queries of one batched call are filtered: the caller's list arrays as they came (begin / len may be null: no query has a
+// list) and the effective predicates (null: no query has one) — normalised, and empty where there is nothing to test per row.
+struct BatchFilters {
+    const uint64_t* allow;
+    const uint64_t* begin;
+    const uint64_t* len;
+    const wax_hip_row_predicate* eff;
+    bool listed(uint32_t q) const { return len != nullptr && len[q] != WAX_HIP_NO_ALLOW_LIST; }
+    uint64_t length(uint32_t q) const { return listed(q) ? len[q] : 0; }
+    const uint64_t* ids(uint32_t q) const { return length(q) ? allow + begin[q] : nullptr; }
+    const wax_hip_row_predicate* pred(uint32_t q) const { return eff != nullptr && !predicate_is_empty(&eff[q]) ? &eff[q] : nullptr; }
+};
+
+// The queries with an allow-list, a predicate or both (fq), under the caller's shared lock: ONE gather pass for all of them. Queries
+// with the same (list, predicate) share an ENTRY; every entry becomes a compact ascending row list with a device-side count
+// (filter.hip sorts the short lists, a predicate's failures dropped before the sort; a long list takes the bitmap route, ANDed with
+// the attribute mask; an entry without a list comes straight from the attribute columns, predicate.hip), multiscan.hip's gather form
+// scores every row list against the queries that share it, the span merge attaches frame ids: one download, one synchronisation, no
+// host round trip for a count. What that pass does not serve takes search_rows_locked per query.
 static int batch_filtered_locked(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int kpad, const std::vector<uint32_t>& fq,
-                                 const uint64_t* allow, uint64_t n_allow_ids, const uint64_t* allow_begin, const uint64_t* allow_len,
-                                 const float* min_scores, uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts) {
+                                 const BatchFilters& F, uint64_t n_allow_ids, const float* min_scores, uint64_t* out_ids, float* out_scores,
+                                 uint32_t out_stride, uint32_t* out_counts) {
     const uint64_t count = e->count;
     const int k = kpad < (int)out_stride ? kpad : (int)out_stride;   // the best out_stride of kpad: the same rows hits_to_results keeps
     const uint32_t group = (k >= 1 && k <= FUSED_MAX_K) ? scan_multi_group(dims, k) : 0u;
+    auto one = [&](uint32_t q) -> int {   // query q through the single-query body (which counts its own predicate search), then its cut
+        uint32_t n = 0;
+        const int rc = search_rows_locked(e, queries + (size_t)q * dims, dims, kpad, F.listed(q) ? 1 : 0, F.ids(q), F.length(q), F.pred(q),
+                                          out_ids + (size_t)q * out_stride, out_scores + (size_t)q * out_stride, out_stride, &n);
+        if (rc != WAX_HIP_OK) return rc;
+        if (min_scores) apply_min_score(min_scores[q], out_ids + (size_t)q * out_stride, out_scores + (size_t)q * out_stride, &n);
+        out_counts[q] = n;
+        return WAX_HIP_OK;
+    };
     if (e->filter_batch.load() == 0 || e->force_general.load() != 0 || group == 0) {
-        for (uint32_t q : fq) {
-            uint32_t n = 0;
-            const int rc = search_rows_locked(e, queries + (size_t)q * dims, dims, kpad, 1, allow_len[q] ? allow + allow_begin[q] : nullptr, allow_len[q], nullptr,
-                                              out_ids + (size_t)q * out_stride, out_scores + (size_t)q * out_stride, out_stride, &n);
-            if (rc != WAX_HIP_OK) return rc;
-            if (min_scores) apply_min_score(min_scores[q], out_ids + (size_t)q * out_stride, out_scores + (size_t)q * out_stride, &n);
-            out_counts[q] = n;
-        }
+        for (uint32_t q : fq) { const int rc = one(q); if (rc != WAX_HIP_OK) return rc; }
         e->st_filter_batch_fallbacks += fq.size();
         return WAX_HIP_OK;
     }
     if (e->row_base + count > 0x100000000ull) return fail(WAX_HIP_ERR_CAPACITY, "row_base + count exceeds UInt32 row indices");
-    // distinct lists: queries with the same (begin, len) share one
-    struct List { uint64_t begin, len, ub; uint32_t row_off; std::vector<uint32_t> qs; };
-    std::vector<List> lists;
+    // distinct entries: queries with the same (begin, len | no list, predicate) share one
+    struct Entry { uint64_t begin, len, ub; uint32_t row_off; const wax_hip_row_predicate* pred; bool admitted; std::vector<uint32_t> qs; };
+    std::vector<Entry> lists;
     {
-        std::map<std::pair<uint64_t, uint64_t>, uint32_t> index;
+        typedef std::tuple<uint64_t, uint64_t, int32_t, int64_t, int32_t, int64_t, uint32_t> EntryKey;
+        std::map<EntryKey, uint32_t> index;
         for (uint32_t q : fq) {
-            const uint64_t len = count == 0 ? 0 : allow_len[q];
+            const bool listed = F.listed(q);
+            const uint64_t len = count == 0 ? 0 : (listed ? F.length(q) : WAX_HIP_NO_ALLOW_LIST);
             if (len == 0) continue;                               // nothing allowed: count 0
-            auto it = index.emplace(std::make_pair(allow_begin[q], len), (uint32_t)lists.size());
-            if (it.second) lists.push_back(List{allow_begin[q], len, len < count ? len : count, 0, {}});
+            const wax_hip_row_predicate* p = F.pred(q);
+            const uint64_t begin = listed ? F.begin[q] : 0;
+            const EntryKey key = p ? EntryKey(begin, len, p->has_after, p->after, p->has_before, p->before, p->deny_flags) : EntryKey(begin, len, 0, 0, 0, 0, 0u);
+            auto it = index.emplace(key, (uint32_t)lists.size());
+            if (it.second) lists.push_back(Entry{begin, len, listed && len < count ? len : count, 0, p, true, {}});
             lists[it.first->second].qs.push_back(q);
         }
     }
-    uint64_t rows_total = 0, long_max = 0;
-    uint32_t short_max = 0;
-    std::vector<RowListDesc> descs;
+    // the row-slot budget of the entries with a predicate, in order of their first query (an entry without a list costs `count` slots
+    // whatever passes); what does not fit takes the single-query body below
+    std::vector<uint32_t> looped;
+    uint64_t pred_entries = 0;
+    {
+        const uint64_t budget = (uint64_t)e->predicate_batch_rows.load();
+        uint64_t used = 0;
+        for (Entry& L : lists) {
+            if (!L.pred) continue;
+            if (L.ub <= budget - used) { used += L.ub; ++pred_entries; continue; }
+            L.admitted = false;
+            looped.insert(looped.end(), L.qs.begin(), L.qs.end());
+        }
+    }
+    uint64_t rows_total = 0, long_max = 0, attr_items = 0;
+    uint32_t short_max = 0, short_max_pred = 0;
+    bool any_listed = false;
+    std::vector<RowListDesc> descs, descs_pred;
+    std::vector<RowListPred> sort_preds;
+    std::vector<AttrRowsRecord> records;
+    std::vector<uint32_t> item_rec;
+    const uint32_t long_blocks = filter_bitmap_blocks((uint32_t)count);   // the bitmap route's share of d_block_sum; the records' slots follow it
+    auto pred_fields = [](const wax_hip_row_predicate& p, auto& out) {
+        out.has_after = p.has_after; out.has_before = p.has_before; out.after = p.after; out.before = p.before; out.deny_flags = p.deny_flags;
+    };
     for (uint32_t li = 0; li < lists.size(); ++li) {
-        List& L = lists[li];
+        Entry& L = lists[li];
+        if (!L.admitted) continue;
         L.row_off = (uint32_t)rows_total;
         rows_total += L.ub;
         if (rows_total >= 0x80000000ull) return fail(WAX_HIP_ERR_CAPACITY, "allowed rows of one batch exceed 2^31");
-        if (L.len <= ROWLIST_SORT_MAX) {
+        if (L.len == WAX_HIP_NO_ALLOW_LIST) {
+            AttrRowsRecord r{};
+            r.n_rows = (uint32_t)count; r.row_off = L.row_off; r.count_slot = li;
+            r.n_items = (uint32_t)((count + ATTR_ROWS_ITEM - 1) / ATTR_ROWS_ITEM); r.item0 = (uint32_t)attr_items; r.block0 = long_blocks + (uint32_t)attr_items;
+            pred_fields(*L.pred, r);
+            for (uint32_t i = 0; i < r.n_items; ++i) item_rec.push_back((uint32_t)records.size());
+            attr_items += r.n_items;
+            if (attr_items >= 0x80000000ull) return fail(WAX_HIP_ERR_CAPACITY, "too many work items in one batch");
+            records.push_back(r);
+            continue;
+        }
+        any_listed = true;
+        if (L.len > ROWLIST_SORT_MAX) {
+            if (L.ub > long_max) long_max = L.ub;
+        } else if (L.pred) {
+            RowListPred sp{};
+            pred_fields(*L.pred, sp);
+            sort_preds.push_back(sp);
+            descs_pred.push_back(RowListDesc{L.begin, (uint32_t)L.len, L.row_off, li, 0u});
+            if (L.len > short_max_pred) short_max_pred = (uint32_t)L.len;
+        } else {
             descs.push_back(RowListDesc{L.begin, (uint32_t)L.len, L.row_off, li, 0u});
             if (L.len > short_max) short_max = (uint32_t)L.len;
-        } else if (L.ub > long_max) {
-            long_max = L.ub;
         }
     }
-    // groups of up to `group` queries per list, work items sized by the list's upper bound (its device-side length is not read back)
+    // groups of up to `group` queries per entry, work items sized by the entry's upper bound (its device-side length is not read back)
     std::vector<GatherGroup> groups;
     std::vector<uint32_t> item_group, slot_q, spans;
     std::vector<float> slot_norm;
     uint64_t part_lists = 0;
     const int grid_cap = (int)e->grid_blocks.load();
     for (uint32_t li = 0; li < lists.size(); ++li) {
-        const List& L = lists[li];
+        const Entry& L = lists[li];
+        if (!L.admitted) continue;
         const uint32_t W = scan_multi_listed_items(L.ub, dims, grid_cap);
         for (size_t g0 = 0; g0 < L.qs.size(); g0 += group) {
             const uint32_t gn = (uint32_t)std::min<size_t>(group, L.qs.size() - g0);
@@ -360,21 +436,53 @@ static int batch_filtered_locked(wax_hip_engine* e, const float* queries, uint32
     }
     for (uint32_t q : fq) out_counts[q] = 0;
     const uint32_t P = (uint32_t)slot_q.size();
-    e->st_filter_batch_queries += fq.size();
-    e->st_searches += fq.size();
+    const uint64_t passed = fq.size() - looped.size();
+    e->st_filter_batch_queries += passed;
+    e->st_searches += passed;
+    if (F.eff) {
+        // the predicates this pass answers (one without a row to offer included); a looped query is counted by the single-query body
+        std::vector<uint8_t> is_looped(nq, 0);
+        for (uint32_t q : looped) is_looped[q] = 1;
+        uint64_t n = 0;
+        for (uint32_t q : fq) n += (F.pred(q) != nullptr && !is_looped[q]) ? 1u : 0u;
+        e->st_predicate_searches += n;
+        e->st_predicate_batch_queries += n;
+        e->st_predicate_batch_classes += pred_entries;
+    }
+    // Ahead of the pass and of its workspace: the single-query body leases a workspace of its own, and a call that held one while it
+    // waited for another could wait for a call doing the same.
+    for (uint32_t q : looped) { const int rc = one(q); if (rc != WAX_HIP_OK) return rc; }
+    e->st_filter_batch_fallbacks += looped.size();
     if (P == 0) return WAX_HIP_OK;
 
     FilterLease lease(e);
     if (lease.rc != WAX_HIP_OK) return lease.rc;
     FilterWork& f = lease.work();
     hipStream_t st = f.stream;
-    { const int hrc = ensure_idhash(e, st); if (hrc != WAX_HIP_OK) return hrc; }
-    // one blob: descs | groups | item_group | slot_q | slot_norm | spans (16-byte aligned sections)
+    if (any_listed) { const int hrc = ensure_idhash(e, st); if (hrc != WAX_HIP_OK) return hrc; }
+    const int64_t* d_ts = nullptr;
+    const uint32_t* d_fl = nullptr;
+    if (pred_entries != 0) {
+        // the attribute columns, once, on this stream under the lock held (null: a store without attributes reads (0, 0) in every row)
+        { const int arc = ensure_attrs(e, st, &d_ts, &d_fl); if (arc != WAX_HIP_OK) return arc; }
+        for (AttrRowsRecord& r : records) { r.ts = d_ts; r.flags = d_fl; }
+        for (RowListPred& sp : sort_preds) { sp.ts = d_ts; sp.flags = d_fl; }
+        if (long_max > 0 && !f.d_pred_counts)
+            HIP_TRY(hipMalloc(&f.d_pred_counts, 2 * sizeof(uint32_t)), WAX_HIP_ERR_ALLOC, "Failed to allocate predicate counters");
+    }
+    // one blob: descs | descs with a predicate | their predicates | attribute records | their work table | groups | item_group | slot_q |
+    // slot_norm | spans (16-byte aligned sections)
     auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    const size_t o_desc = 0, o_grp = al(o_desc + descs.size() * sizeof(RowListDesc)), o_item = al(o_grp + groups.size() * sizeof(GatherGroup));
+    const size_t o_desc = 0, o_dpred = al(o_desc + descs.size() * sizeof(RowListDesc)), o_spred = al(o_dpred + descs_pred.size() * sizeof(RowListDesc));
+    const size_t o_rec = al(o_spred + sort_preds.size() * sizeof(RowListPred)), o_irec = al(o_rec + records.size() * sizeof(AttrRowsRecord));
+    const size_t o_grp = al(o_irec + item_rec.size() * 4), o_item = al(o_grp + groups.size() * sizeof(GatherGroup));
     const size_t o_q = al(o_item + item_group.size() * 4), o_n = al(o_q + (size_t)P * 4), o_sp = al(o_n + (size_t)P * 4), meta_bytes = al(o_sp + (size_t)P * 8);
     std::vector<unsigned char> meta(meta_bytes, 0);
     std::memcpy(meta.data() + o_desc, descs.data(), descs.size() * sizeof(RowListDesc));
+    std::memcpy(meta.data() + o_dpred, descs_pred.data(), descs_pred.size() * sizeof(RowListDesc));
+    std::memcpy(meta.data() + o_spred, sort_preds.data(), sort_preds.size() * sizeof(RowListPred));
+    std::memcpy(meta.data() + o_rec, records.data(), records.size() * sizeof(AttrRowsRecord));
+    std::memcpy(meta.data() + o_irec, item_rec.data(), item_rec.size() * 4);
     std::memcpy(meta.data() + o_grp, groups.data(), groups.size() * sizeof(GatherGroup));
     std::memcpy(meta.data() + o_item, item_group.data(), item_group.size() * 4);
     std::memcpy(meta.data() + o_q, slot_q.data(), (size_t)P * 4);
@@ -388,30 +496,49 @@ static int batch_filtered_locked(wax_hip_engine* e, const float* queries, uint32
     if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_part, &f.part_cap, part_lists * (uint64_t)k, sizeof(int64_t), "Failed to allocate gather partials");
     if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_bhits, &f.bhits_cap, (uint64_t)P * k, sizeof(wax_hip_hit), "Failed to allocate batch filter hits");
     if (grc == WAX_HIP_OK && long_max > 0) {
-        const uint64_t n_words = (count + 31) / 32, n_blocks = filter_bitmap_blocks((uint32_t)count);
+        const uint64_t n_words = (count + 31) / 32;
         grc = grow_dev(&f.d_bitmap, &f.bitmap_words, n_words, sizeof(uint32_t), "Failed to allocate row bitmap");
-        if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_block_sum, &f.block_cap, n_blocks, sizeof(uint32_t), "Failed to allocate bitmap offsets");
         if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_lids, &f.lids_cap, long_max, sizeof(uint64_t), "Failed to allocate allowed-id list");
     }
+    if (grc == WAX_HIP_OK && (long_max > 0 || attr_items > 0))
+        grc = grow_dev(&f.d_block_sum, &f.block_cap, (uint64_t)long_blocks + attr_items, sizeof(uint32_t), "Failed to allocate bitmap offsets");
     if (grc != WAX_HIP_OK) return grc;
     const RowListDesc* d_desc = reinterpret_cast<const RowListDesc*>(f.d_meta + o_desc);
+    const RowListDesc* d_desc_pred = reinterpret_cast<const RowListDesc*>(f.d_meta + o_dpred);
+    const RowListPred* d_sort_preds = reinterpret_cast<const RowListPred*>(f.d_meta + o_spred);
+    const AttrRowsRecord* d_rec = reinterpret_cast<const AttrRowsRecord*>(f.d_meta + o_rec);
+    const uint32_t* d_item_rec = reinterpret_cast<const uint32_t*>(f.d_meta + o_irec);
     const GatherGroup* d_grp = reinterpret_cast<const GatherGroup*>(f.d_meta + o_grp);
     const uint32_t* d_item = reinterpret_cast<const uint32_t*>(f.d_meta + o_item);
     const uint32_t* d_slot_q = reinterpret_cast<const uint32_t*>(f.d_meta + o_q);
     const float* d_slot_n = reinterpret_cast<const float*>(f.d_meta + o_n);
     const uint32_t* d_spans = reinterpret_cast<const uint32_t*>(f.d_meta + o_sp);
     // the caller's id array as it is (the lists are ranges of it; overlapping ranges travel once), the queries, the tables
-    HIP_TRY(hipMemcpyAsync(f.d_allow, allow, (size_t)n_allow_ids * sizeof(uint64_t), hipMemcpyHostToDevice, st), WAX_HIP_ERR_INTERNAL, "allow-list upload");
+    HIP_TRY(hipMemcpyAsync(f.d_allow, F.allow, (size_t)n_allow_ids * sizeof(uint64_t), hipMemcpyHostToDevice, st), WAX_HIP_ERR_INTERNAL, "allow-list upload");
     HIP_TRY(hipMemcpyAsync(f.d_bq, queries, (size_t)nq * dims * sizeof(float), hipMemcpyHostToDevice, st), WAX_HIP_ERR_INTERNAL, "query upload");
     HIP_TRY(hipMemcpyAsync(f.d_meta, meta.data(), meta_bytes, hipMemcpyHostToDevice, st), WAX_HIP_ERR_INTERNAL, "batch filter table upload");
-    // lists -> compact ascending row lists with device-side counts; no host round trip before the scan
-    HIP_TRY(launch_rowlist_sort(f.d_allow, d_desc, (uint32_t)descs.size(), short_max, e->d_ids, e->idhash.d_table, e->idhash.slots, f.d_lrows,
+    // entries -> compact ascending row lists with device-side counts; no host round trip before the scan
+    HIP_TRY(launch_rowlist_sort(f.d_allow, d_desc, nullptr, (uint32_t)descs.size(), short_max, e->d_ids, e->idhash.d_table, e->idhash.slots, f.d_lrows,
                                 f.d_lcnt, st), WAX_HIP_ERR_INTERNAL, "allow-list sort launch");
+    HIP_TRY(launch_rowlist_sort(f.d_allow, d_desc_pred, d_sort_preds, (uint32_t)descs_pred.size(), short_max_pred, e->d_ids, e->idhash.d_table,
+                                e->idhash.slots, f.d_lrows, f.d_lcnt, st), WAX_HIP_ERR_INTERNAL, "allow-list sort launch");
+    if (!records.empty())   // every entry without a list, straight from the attribute columns: three launches whatever their number
+        HIP_TRY(launch_attr_rows(d_rec, (uint32_t)records.size(), d_item_rec, (uint32_t)item_rec.size(), f.d_block_sum, f.d_lrows, f.d_lcnt, st),
+                WAX_HIP_ERR_INTERNAL, "attribute row-list launch");
     for (uint32_t li = 0; li < lists.size(); ++li) {   // lists too long for LDS: the single-query path's bitmap route, one list at a time
-        const List& L = lists[li];
-        if (L.len <= ROWLIST_SORT_MAX) continue;
+        const Entry& L = lists[li];
+        if (!L.admitted || L.len == WAX_HIP_NO_ALLOW_LIST || L.len <= ROWLIST_SORT_MAX) continue;
         HIP_TRY(launch_allow_probe(f.d_allow + L.begin, L.len, e->d_ids, (uint32_t)count, e->idhash.d_table, e->idhash.slots, f.d_bitmap,
-                                   f.d_block_sum, f.d_lcnt + li, st), WAX_HIP_ERR_INTERNAL, "allow-list probe launch");
+                                   L.pred ? nullptr : f.d_block_sum, L.pred ? nullptr : f.d_lcnt + li, st), WAX_HIP_ERR_INTERNAL, "allow-list probe launch");
+        if (L.pred) {
+            AttrMaskArgs ma{};
+            ma.ts = d_ts; ma.flags = d_fl;
+            ma.bitmap = f.d_bitmap; ma.counts = f.d_pred_counts; ma.n_rows = (uint32_t)count; ma.chunk_rows = 0; ma.and_bitmap = 1;
+            pred_fields(*L.pred, ma);
+            HIP_TRY(hipMemsetAsync(f.d_pred_counts, 0, 2 * sizeof(uint32_t), st), WAX_HIP_ERR_INTERNAL, "predicate counters");
+            HIP_TRY(launch_attr_mask(ma, st), WAX_HIP_ERR_INTERNAL, "attribute mask launch");
+            HIP_TRY(launch_bitmap_offsets(f.d_bitmap, (uint32_t)count, f.d_block_sum, f.d_lcnt + li, st), WAX_HIP_ERR_INTERNAL, "bitmap offsets launch");
+        }
         HIP_TRY(launch_allow_emit(f.d_bitmap, (uint32_t)count, f.d_block_sum, e->d_ids, f.d_lrows + L.row_off, f.d_lids, st),
                 WAX_HIP_ERR_INTERNAL, "allow-list compaction launch");
         e->st_filter_device++;
@@ -424,7 +551,10 @@ static int batch_filtered_locked(wax_hip_engine* e, const float* queries, uint32
     HIP_TRY(launch_merge_keys_spans(f.d_part, d_spans, k, e->d_ids, a.row_base, (uint32_t)count, f.d_bhits, (uint32_t)k, P, st),
             WAX_HIP_ERR_INTERNAL, "gather merge launch");
     std::vector<wax_hip_hit> hits((size_t)P * k);
+    std::vector<uint32_t> lcnt(pred_entries != 0 ? lists.size() : 0);   // what the entries with a predicate passed: for the accounting only
     HIP_TRY(hipMemcpyAsync(hits.data(), f.d_bhits, hits.size() * sizeof(wax_hip_hit), hipMemcpyDeviceToHost, st), WAX_HIP_ERR_INTERNAL, "hits download");
+    if (!lcnt.empty())
+        HIP_TRY(hipMemcpyAsync(lcnt.data(), f.d_lcnt, lcnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st), WAX_HIP_ERR_INTERNAL, "row count download");
     HIP_TRY(hipStreamSynchronize(st), WAX_HIP_ERR_INTERNAL, "batched filtered search failed on device");
     for (uint32_t p = 0; p < P; ++p) {
         const uint32_t q = slot_q[p];
@@ -434,29 +564,57 @@ static int batch_filtered_locked(wax_hip_engine* e, const float* queries, uint32
         if (min_scores) apply_min_score(min_scores[q], out_ids + (size_t)q * out_stride, out_scores + (size_t)q * out_stride, &n);
         out_counts[q] = n;
     }
-    e->st_rows += rows_total;
-    e->st_bytes += rows_total * (uint64_t)dims * 4ull;
+    // an entry without a predicate is charged its upper bound, one with a predicate the rows it passed
+    uint64_t rows_read = 0;
+    for (uint32_t li = 0; li < lists.size(); ++li)
+        if (lists[li].admitted) rows_read += lists[li].pred ? (uint64_t)lcnt[li] : lists[li].ub;
+    e->st_rows += rows_read;
+    e->st_bytes += rows_read * (uint64_t)dims * 4ull;
     return WAX_HIP_OK;
 }
 
-int wax_hip_search_batch_filtered(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
-                                  const uint64_t* allow_frame_ids, uint64_t n_allow_ids, const uint64_t* allow_begin,
-                                  const uint64_t* allow_len, const float* min_scores, uint64_t* out_ids, float* out_scores,
-                                  uint32_t out_stride, uint32_t* out_counts) {
+int wax_hip_search_batch_predicate(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
+                                   const uint64_t* allow_frame_ids, uint64_t n_allow_ids, const uint64_t* allow_begin,
+                                   const uint64_t* allow_len, const float* min_scores, const wax_hip_row_predicate* preds,
+                                   uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts) {
     if (!e) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine is null");
     if (nq == 0) return WAX_HIP_OK;
     if (!queries || !out_counts) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "null input");
     if ((!out_ids || !out_scores) && out_stride) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "output arrays are null");
     { const int crc = check_batch_allow(nq, allow_frame_ids, n_allow_ids, allow_begin, allow_len); if (crc != WAX_HIP_OK) return crc; }
     for (uint32_t q = 0; q < nq; ++q) out_counts[q] = 0;
-    if (e->sh) return sh_search_batch_filtered(e, queries, nq, dims, top_k, allow_frame_ids, n_allow_ids, allow_begin, allow_len, min_scores, out_ids,
-                                               out_scores, out_stride, out_counts);
+    if (e->sh) return sh_search_batch_predicate(e, queries, nq, dims, top_k, allow_frame_ids, n_allow_ids, allow_begin, allow_len, min_scores, preds,
+                                                out_ids, out_scores, out_stride, out_counts);
     if (dims != e->dims) return fail(WAX_HIP_ERR_DIM_MISMATCH, dim_mismatch_msg(e->dims, dims));
     if (out_stride == 0) return WAX_HIP_OK;
+    // The effective predicates: normalised, and — on a store that never had attributes, where every row reads (0, 0) — decided here,
+    // once for all rows: the query loses its predicate, or its count stays 0 without device work (`dead`).
+    std::vector<wax_hip_row_predicate> eff;
+    std::vector<uint8_t> dead;
+    bool any_pred = false;
+    for (uint32_t q = 0; preds && q < nq && !any_pred; ++q) any_pred = !predicate_is_empty(&preds[q]);
+    if (any_pred) {
+        bool has_attrs;
+        { ReadGuard rd(e); has_attrs = !e->attr_ts.empty(); }
+        eff.resize(nq);
+        dead.assign(nq, 0);
+        for (uint32_t q = 0; q < nq; ++q) {
+            wax_hip_row_predicate np = normalised_predicate(&preds[q]);
+            if (!predicate_is_empty(&np) && !has_attrs) {
+                if (predicate_passes(np, 0, 0u)) np = wax_hip_row_predicate{};
+                else dead[q] = 1;
+            }
+            eff[q] = np;
+        }
+    }
+    const BatchFilters F{allow_frame_ids, allow_begin, allow_len, any_pred ? eff.data() : nullptr};
     std::vector<uint32_t> plain, fq;
-    for (uint32_t q = 0; q < nq; ++q) (allow_len && allow_len[q] != WAX_HIP_NO_ALLOW_LIST ? fq : plain).push_back(q);
+    for (uint32_t q = 0; q < nq; ++q) {
+        if (any_pred && dead[q]) continue;
+        (F.listed(q) || F.pred(q) ? fq : plain).push_back(q);
+    }
     if (!plain.empty()) {
-        // queries without a list: one sub-batch of the unfiltered batched search (its own lock acquisition), then the cut
+        // queries with neither list nor predicate: one sub-batch of the unfiltered batched search (its own lock acquisition), then the cut
         std::vector<float> qs;
         const float* src = queries;
         if (plain.size() != nq) {
@@ -482,6 +640,13 @@ int wax_hip_search_batch_filtered(wax_hip_engine* e, const float* queries, uint3
     DeviceGuard g(e->device);
     ReadGuard rd(e);
     { const int frc = flush_pending(e); if (frc != WAX_HIP_OK) return frc; }
-    return batch_filtered_locked(e, queries, nq, dims, clamp_topk(top_k), fq, allow_frame_ids, n_allow_ids, allow_begin, allow_len,
-                                 min_scores, out_ids, out_scores, out_stride, out_counts);
+    return batch_filtered_locked(e, queries, nq, dims, clamp_topk(top_k), fq, F, n_allow_ids, min_scores, out_ids, out_scores, out_stride, out_counts);
+}
+
+int wax_hip_search_batch_filtered(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
+                                  const uint64_t* allow_frame_ids, uint64_t n_allow_ids, const uint64_t* allow_begin,
+                                  const uint64_t* allow_len, const float* min_scores, uint64_t* out_ids, float* out_scores,
+                                  uint32_t out_stride, uint32_t* out_counts) {
+    return wax_hip_search_batch_predicate(e, queries, nq, dims, top_k, allow_frame_ids, n_allow_ids, allow_begin, allow_len, min_scores, nullptr,
+                                          out_ids, out_scores, out_stride, out_counts);
 }

@@ -568,14 +568,29 @@ struct RowListDesc {
     uint64_t allow_off;    // the list is allow[allow_off .. allow_off + len)
     uint32_t len, row_off, count_slot, pad;
 };
-hipError_t launch_rowlist_sort(const uint64_t* d_allow, const RowListDesc* d_desc, uint32_t n_lists, uint32_t max_len, const uint64_t* ids,
-                               const uint32_t* table, uint64_t slots, uint32_t* rows_out, uint32_t* counts, hipStream_t st);
+// Batched predicates: the predicate of list i of a launch, parallel to d_desc (RowListDesc keeps its layout). A probed row that fails
+// it is dropped before the sort. Null columns: every row reads (0, 0).
+struct RowListPred {
+    const int64_t* ts;
+    const uint32_t* flags;
+    int32_t has_after, has_before;
+    int64_t after, before;
+    uint32_t deny_flags;
+    uint32_t pad;
+};
+// d_preds null: lists without a predicate (the kernel of wax_hip_search_batch_filtered as it was); otherwise one entry per list.
+hipError_t launch_rowlist_sort(const uint64_t* d_allow, const RowListDesc* d_desc, const RowListPred* d_preds, uint32_t n_lists, uint32_t max_len,
+                               const uint64_t* ids, const uint32_t* table, uint64_t slots, uint32_t* rows_out, uint32_t* counts, hipStream_t st);
 
 
 // per-block popcounts + exclusive scan of a finished bitmap (what launch_allow_probe runs behind its probe); *total = bits set
 hipError_t launch_bitmap_offsets(const uint32_t* bitmap, uint32_t n_rows, uint32_t* block_sum, uint32_t* total, hipStream_t st);
 
 // ---- predicate.hip: per-row attributes -> row bitmap, and the f32 scan that honours it ----
+// passesFrameFilter's per-row test (UnifiedSearch.swift:1241-1258): the one device definition, used by every kernel that reads the columns.
+__device__ inline bool attr_row_passes(int32_t has_after, int64_t after, int32_t has_before, int64_t before, uint32_t deny_flags, int64_t ts, uint32_t fl) {
+    return !(has_after != 0 && ts < after) && !(has_before != 0 && ts >= before) && (fl & deny_flags) == 0u;
+}
 struct AttrMaskArgs {
     const int64_t* ts;          // [n_rows] timestamps; null = every row 0
     const uint32_t* flags;      // [n_rows] flag words; null = every row 0
@@ -602,6 +617,26 @@ struct AttrMaskRecord {
     uint32_t item0;             // its first work item
 };
 hipError_t launch_attr_mask_pooled(const AttrMaskRecord* d_records, const uint32_t* d_item_rec, uint32_t n_items, uint32_t* d_bitmaps, hipStream_t st);
+// The attribute columns straight to compact ascending row lists, for MANY predicates of one call (wax_hip_search_batch_predicate:
+// the entries without an allow-list). Work item i is ATTR_ROWS_ITEM consecutive rows of record d_item_rec[i]. Three plain launches
+// ordered by the stream: per-item counts of passing rows -> per record an exclusive scan of its counts (the total to
+// counts[count_slot]) -> the passing rows, ascending, at rows_out[row_off ..]. No bitmap, no atomics; 24 B read per row per record.
+constexpr uint32_t ATTR_ROWS_ITEM = 4096;   // 16 tiles of 256 rows, one row per lane
+struct AttrRowsRecord {
+    const int64_t* ts;          // [n_rows] timestamps; null = every row 0
+    const uint32_t* flags;      // [n_rows] flag words; null = every row 0
+    uint32_t n_rows;
+    int32_t has_after, has_before;
+    uint32_t deny_flags;
+    int64_t after, before;
+    uint32_t row_off;           // its row list starts at rows_out[row_off] (room for n_rows)
+    uint32_t count_slot;        // its length goes to counts[count_slot]
+    uint32_t item0, n_items;    // its work items: [item0, item0 + ceil(n_rows / ATTR_ROWS_ITEM))
+    uint32_t block0;            // its first slot of block_sum ([n_items] of them)
+    uint32_t pad;
+};
+hipError_t launch_attr_rows(const AttrRowsRecord* d_records, uint32_t n_records, const uint32_t* d_item_rec, uint32_t n_items, uint32_t* block_sum,
+                            uint32_t* rows_out, uint32_t* counts, hipStream_t st);
 struct MaskedScanArgs {
     const float* store;         // [n_rows][dims] f32
     const float* query;         // [dims] f32 in HBM

@@ -6,6 +6,9 @@
 //                        the probe kernel marked). Counts the passing rows and the scan chunks that hold one into two device words.
 //   attr_mask_pooled_kernel  the same reads, test, ballot and word writes for MANY (store, predicate) records in one launch
 //                        (wax_hip_search_many_predicate): one 256-row tile of one record per workgroup, no counters, no atomics.
+//   attr_rows_count / scan / emit_kernel   the columns straight to compact ascending row lists with device-side counts, for MANY
+//                        predicates in three plain launches (wax_hip_search_batch_predicate: the entries without an allow-list):
+//                        work items of 4 096 rows, the same reads and test, ranks from ballots; no bitmap, no atomics.
 //   scan_masked_kernel   scan_body's structure (kernels.hip): the same (dims -> GROUP) table, the same loads, accumulate / finish_row
 //                        of row_math.h — a passing row's distance has the scan's bits. A wave reads its chunk's bits before the
 //                        loads; a chunk without a passing row costs no load at all (the test is wave-uniform); otherwise a key is
@@ -24,10 +27,7 @@ namespace wax {
 // the 0.2 ms in between is an inference from that table, not a kernel trace; this form is the remedy that inference calls for.
 constexpr uint32_t kMaskGrid = 1024;
 
-// passesFrameFilter's per-row test (UnifiedSearch.swift:1241-1258): the one device definition, used by both mask kernels.
-__device__ inline bool attr_row_passes(int32_t has_after, int64_t after, int32_t has_before, int64_t before, uint32_t deny_flags, int64_t ts, uint32_t fl) {
-    return !(has_after != 0 && ts < after) && !(has_before != 0 && ts >= before) && (fl & deny_flags) == 0u;
-}
+// (the per-row test itself, attr_row_passes, is in kernels.h: filter.hip's list sort applies it too)
 
 __global__ __launch_bounds__(256) void attr_mask_kernel(AttrMaskArgs a) {
     __shared__ uint32_t wave_counts[4][2];
@@ -96,6 +96,116 @@ __global__ __launch_bounds__(256) void attr_mask_pooled_kernel(const AttrMaskRec
 hipError_t launch_attr_mask_pooled(const AttrMaskRecord* d_records, const uint32_t* d_item_rec, uint32_t n_items, uint32_t* d_bitmaps, hipStream_t st) {
     if (n_items == 0 || d_records == nullptr || d_item_rec == nullptr || d_bitmaps == nullptr) return hipErrorInvalidValue;
     hipLaunchKernelGGL(attr_mask_pooled_kernel, dim3(n_items), dim3(256), 0, st, d_records, d_item_rec, d_bitmaps);
+    return hipGetLastError();
+}
+
+// ---- attribute columns -> row lists, many records per launch (wax_hip_search_batch_predicate) ----
+constexpr int kAttrTiles = (int)(ATTR_ROWS_ITEM / 256u);
+static_assert(kAttrTiles * 4 == 64, "the emit kernel scans one (tile, wave) count per lane");
+
+// The wave's votes on its 64 rows of each of the item's 16 tiles: tile t of item i is rows i * 4096 + t * 256 .. + 255 of the record,
+// one row per lane, both columns read coalesced. Rows at or beyond n_rows vote false.
+__device__ inline void attr_rows_votes(const AttrRowsRecord& r, uint32_t item, unsigned long long (&b)[kAttrTiles]) {
+    const uint64_t row0 = (uint64_t)item * ATTR_ROWS_ITEM + threadIdx.x;
+#pragma unroll
+    for (int t = 0; t < kAttrTiles; ++t) {
+        const uint64_t row = row0 + (uint64_t)t * 256u;
+        bool pass = row < (uint64_t)r.n_rows;
+        if (pass) {
+            const int64_t ts = r.ts != nullptr ? r.ts[row] : 0;
+            const uint32_t fl = r.flags != nullptr ? r.flags[row] : 0u;
+            pass = attr_row_passes(r.has_after, r.after, r.has_before, r.before, r.deny_flags, ts, fl);
+        }
+        b[t] = __ballot(pass);
+    }
+}
+
+__global__ __launch_bounds__(256) void attr_rows_count_kernel(const AttrRowsRecord* __restrict__ records, const uint32_t* __restrict__ item_rec,
+                                                              uint32_t* __restrict__ block_sum) {
+    __shared__ uint32_t wave_cnt[4];
+    const AttrRowsRecord r = records[item_rec[blockIdx.x]];
+    const uint32_t item = blockIdx.x - r.item0;
+    unsigned long long b[kAttrTiles];
+    attr_rows_votes(r, item, b);
+    uint32_t n = 0;                                             // wave-uniform
+#pragma unroll
+    for (int t = 0; t < kAttrTiles; ++t) n += (uint32_t)__popcll(b[t]);
+    if (lane_id() == 0) wave_cnt[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) block_sum[r.block0 + item] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+}
+
+// One workgroup per record: exclusive scan of its items' counts in place, the record's total to counts[count_slot].
+__global__ __launch_bounds__(256) void attr_rows_scan_kernel(const AttrRowsRecord* __restrict__ records, uint32_t* block_sum, uint32_t* counts) {
+    __shared__ uint32_t wave_sum[4];
+    const AttrRowsRecord r = records[blockIdx.x];
+    uint32_t* bs = block_sum + r.block0;
+    const int lane = lane_id(), w = (int)(threadIdx.x >> 6);
+    uint32_t carry = 0;
+    for (uint32_t b0 = 0; b0 < r.n_items; b0 += 256u) {
+        const uint32_t i = b0 + threadIdx.x;
+        const uint32_t v = i < r.n_items ? bs[i] : 0u;
+        uint32_t inc = v;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = __shfl_up(inc, d, 64);
+            if (lane >= d) inc += o;
+        }
+        if (lane == 63) wave_sum[w] = inc;
+        __syncthreads();
+        uint32_t base = 0, all = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j < w) base += wave_sum[j];
+            all += wave_sum[j];
+        }
+        if (i < r.n_items) bs[i] = carry + base + inc - v;
+        carry += all;
+        __syncthreads();                                        // wave_sum is rewritten by the next chunk
+    }
+    if (threadIdx.x == 0) counts[r.count_slot] = carry;
+}
+
+// The count kernel's items once more: the votes again, then every passing row at its rank. Rows ascend with (tile, wave, lane), so the
+// rank of a row is its item's offset + the passing rows of the (tile, wave) pairs before its own + the passing lanes below it.
+__global__ __launch_bounds__(256) void attr_rows_emit_kernel(const AttrRowsRecord* __restrict__ records, const uint32_t* __restrict__ item_rec,
+                                                             const uint32_t* __restrict__ block_off, uint32_t* __restrict__ rows_out) {
+    __shared__ uint32_t cnt[kAttrTiles * 4];                    // [tile][wave]
+    const AttrRowsRecord r = records[item_rec[blockIdx.x]];
+    const uint32_t item = blockIdx.x - r.item0;
+    const int lane = lane_id(), w = (int)(threadIdx.x >> 6);
+    unsigned long long b[kAttrTiles];
+    attr_rows_votes(r, item, b);
+#pragma unroll
+    for (int t = 0; t < kAttrTiles; ++t)
+        if (lane == 0) cnt[t * 4 + w] = (uint32_t)__popcll(b[t]);
+    __syncthreads();
+    const uint32_t mine = cnt[lane];                            // 64 (tile, wave) pairs, one per lane, in row order
+    uint32_t inc = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += o;
+    }
+    const uint32_t ex = inc - mine;
+    uint32_t* out = rows_out + r.row_off + block_off[r.block0 + item];
+    const uint32_t row0 = item * ATTR_ROWS_ITEM + threadIdx.x;  // (a passing row is < n_rows: no wrap)
+#pragma unroll
+    for (int t = 0; t < kAttrTiles; ++t) {
+        const uint32_t off = __shfl(ex, t * 4 + w, 64);
+        const unsigned long long m = b[t];
+        const uint32_t below = (uint32_t)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        if ((m >> lane) & 1ull) out[off + below] = row0 + (uint32_t)t * 256u;
+    }
+}
+
+hipError_t launch_attr_rows(const AttrRowsRecord* d_records, uint32_t n_records, const uint32_t* d_item_rec, uint32_t n_items, uint32_t* block_sum,
+                            uint32_t* rows_out, uint32_t* counts, hipStream_t st) {
+    if (n_records == 0 || n_items == 0 || d_records == nullptr || d_item_rec == nullptr || block_sum == nullptr || rows_out == nullptr || counts == nullptr)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(attr_rows_count_kernel, dim3(n_items), dim3(256), 0, st, d_records, d_item_rec, block_sum);
+    hipLaunchKernelGGL(attr_rows_scan_kernel, dim3(n_records), dim3(256), 0, st, d_records, block_sum, counts);
+    hipLaunchKernelGGL(attr_rows_emit_kernel, dim3(n_items), dim3(256), 0, st, d_records, d_item_rec, block_sum, rows_out);
     return hipGetLastError();
 }
 

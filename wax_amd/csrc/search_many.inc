@@ -6,16 +6,6 @@
 // predicate and a score cut: the predicates of the pooled pairs become row bitmaps in one more launch ahead of the scan, which then
 // offers only the rows whose bit is set. One body serves both entry points (search_many_impl).
 
-// A row predicate with the values of its unused bounds set to 0: two pairs whose predicates test the same thing compare equal.
-static inline wax_hip_row_predicate normalised_predicate(const wax_hip_row_predicate* p) {
-    wax_hip_row_predicate r{};
-    if (!p) return r;
-    r.has_after = p->has_after != 0; r.after = r.has_after ? p->after : 0;
-    r.has_before = p->has_before != 0; r.before = r.has_before ? p->before : 0;
-    r.deny_flags = p->deny_flags;
-    return r;
-}
-
 // The pairs of one pooled engine that share a normalised predicate: they share passes over the store (up to 16 per pass) and, unless
 // the predicate is empty, one row bitmap.
 struct ManyClass {

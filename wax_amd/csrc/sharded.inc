@@ -1321,9 +1321,10 @@ int sh_get_attributes(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, 
 
 // Batched form: every shard answers the whole batch on its own rows (its own batched filtered call, on the handle's workers, in
 // parallel); then each query is merged exactly as sh_search_filtered merges one: stable by score, shard order on ties, then the cut.
-int sh_search_batch_filtered(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k, const uint64_t* allow,
-                             uint64_t n_allow_ids, const uint64_t* allow_begin, const uint64_t* allow_len, const float* min_scores,
-                             uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts) {
+// preds (null: none) go to every shard as they are: a row's attributes live with the shard that owns the row.
+int sh_search_batch_predicate(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k, const uint64_t* allow,
+                              uint64_t n_allow_ids, const uint64_t* allow_begin, const uint64_t* allow_len, const float* min_scores,
+                              const wax_hip_row_predicate* preds, uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts) {
     ShardedState* s = e->sh;
     if (dims != e->dims) return fail(WAX_HIP_ERR_DIM_MISMATCH, dim_mismatch_msg(e->dims, dims));
     if (out_stride == 0) return WAX_HIP_OK;
@@ -1336,8 +1337,8 @@ int sh_search_batch_filtered(wax_hip_engine* e, const float* queries, uint32_t n
     std::vector<int> rcs(G, WAX_HIP_OK);
     std::vector<std::string> errs(G);
     auto one = [&](size_t g) {
-        rcs[g] = wax_hip_search_batch_filtered(s->subs[g], queries, nq, dims, top_k, allow, n_allow_ids, allow_begin, allow_len, nullptr,
-                                               g_ids[g].data(), g_scores[g].data(), limit, g_m[g].data());
+        rcs[g] = wax_hip_search_batch_predicate(s->subs[g], queries, nq, dims, top_k, allow, n_allow_ids, allow_begin, allow_len, nullptr, preds,
+                                                g_ids[g].data(), g_scores[g].data(), limit, g_m[g].data());
         if (rcs[g] != WAX_HIP_OK) errs[g] = g_last_error;   // thread-local: carry it to the caller
     };
     if (G == 1) one(0); else s->workers.run_all(one);
@@ -1523,7 +1524,7 @@ int64_t sh_get_tuning(wax_hip_engine* e, const std::string& k) {
         k == "mirror_scans" || k == "mirror_scan_fallbacks" || k == "mirror_scan_unavailable" || k == "mirror_passes" || k == "mirror_shared_passes" || k == "mirror_shared_queries" || k == "mirror_fill_holds" ||
         k == "mirror8_passes" || k == "mirror8_fallbacks" || k == "mirror8_unavailable" || k == "mirror8_conversions" || k == "mirror8_rows_converted" || k == "mirror8_breaker_trips" ||
         k == "remove_batches" || k == "remove_batch_rows" || k == "remove_batch_bytes_written" ||
-        k == "predicate_searches" || k == "predicate_gather_searches" || k == "predicate_masked_scans" || k == "predicate_chunks_skipped" ||
+        k == "predicate_searches" || k == "predicate_batch_queries" || k == "predicate_batch_classes" || k == "predicate_gather_searches" || k == "predicate_masked_scans" || k == "predicate_chunks_skipped" ||
         k == "attr_uploaded_rows" || k == "attr_device_rows") {   // counters: summed over the shards
         int64_t t = 0;
         for (auto* sub : s->subs) t += wax_hip_get_tuning(sub, k.c_str());

@@ -70,6 +70,7 @@ int wax_hip_set_tuning(wax_hip_engine* e, const char* key, int64_t value) {
     else if (k == "scan_chain") { if (value < -1 || value > 1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "scan_chain must be -1 (auto), 0 or 1"); e->scan_chain = value; }
     else if (k == "share_timing") e->share_timing = value != 0;   // 0: every chained scan records its own start event (one more packet between scans)
     else if (k == "filter_batch") { if (value < 0 || value > 1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "filter_batch must be 0 or 1"); e->filter_batch = value; }
+    else if (k == "predicate_batch_rows") { if (value < 0 || value > 0x7fffffffll) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "predicate_batch_rows must be 0..2147483647"); e->predicate_batch_rows = value; }
     else if (k == "filter_device_min") { if (value < -1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "filter_device_min must be >= -1"); e->filter_device_min = value; }
     else if (k == "search_many") { if (value < 0 || value > 1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "search_many must be 0 or 1"); e->search_many = value; }
     else if (k == "search_many_max_rows") { if (value < 0 || value > 0xffffffffll) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "search_many_max_rows must be 0..4294967295"); e->search_many_max_rows = value; }
@@ -221,6 +222,9 @@ int64_t wax_hip_get_tuning(wax_hip_engine* e, const char* key) {
     if (k == "filter_batch") return e->filter_batch.load();
     if (k == "filter_batch_queries") return (int64_t)e->st_filter_batch_queries.load();
     if (k == "filter_batch_fallbacks") return (int64_t)e->st_filter_batch_fallbacks.load();
+    if (k == "predicate_batch_rows") return e->predicate_batch_rows.load();
+    if (k == "predicate_batch_queries") return (int64_t)e->st_predicate_batch_queries.load();   // non-empty predicates answered by the batched gather pass
+    if (k == "predicate_batch_classes") return (int64_t)e->st_predicate_batch_classes.load();   // (list, predicate) entries with a predicate that pass built
     if (k == "search_many") return e->search_many.load();
     if (k == "search_many_max_rows") return e->search_many_max_rows.load();
     if (k == "search_many_pooled") return (int64_t)e->st_many_pooled.load();   // pairs of wax_hip_search_many answered by its pooled launch

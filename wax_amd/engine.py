@@ -380,10 +380,13 @@ class HIPVectorEngine:
         raise_for_status(rc)
         return ids, scores, counts
 
-    def searchBatchFiltered(self, vectors, topK: int, frameIds=None, minScore=None):  # noqa: N802,N803
-        """searchFiltered for a batch (wax_hip_search_batch_filtered): `frameIds` is None or a length-nq sequence whose entries
-        are None (no list) or an iterable of frame ids; `minScore` is None, one float, or a length-nq sequence (None entries: no
-        cut). Returns (ids[nq, kcap], scores, counts) like searchBatch; row q equals searchFiltered for that query."""
+    def searchBatchFiltered(self, vectors, topK: int, frameIds=None, minScore=None, timeRange=None, denyFlags=0):  # noqa: N802,N803
+        """searchFiltered for a batch (wax_hip_search_batch_filtered / wax_hip_search_batch_predicate): `frameIds` is None or a
+        length-nq sequence whose entries are None (no list) or an iterable of frame ids; `minScore` is None, one float, or a length-nq
+        sequence (None entries: no cut). `timeRange` and `denyFlags` are each one value for all queries or a list of nq with None
+        entries allowed, by searchManyFiltered's rules: one (after | None, before | None) tuple is one value, a LIST is per query.
+        Returns (ids[nq, kcap], scores, counts) like searchBatch; row q equals searchFiltered for that query. A call without
+        timeRange / denyFlags takes wax_hip_search_batch_filtered, as before those arguments existed."""
         qs = _as_f32(vectors)
         if qs.ndim != 2:
             raise EncodingError("searchBatchFiltered: vectors must be [nq, dims]")
@@ -401,12 +404,20 @@ class HIPVectorEngine:
                 if len(minScore) != nq:
                     raise EncodingError("searchBatchFiltered: minScore must hold one entry per query")
                 cuts = np.array([np.nan if m is None else float(m) for m in minScore], dtype=np.float32)
-        rc = self._lib.wax_hip_search_batch_filtered(
-            self._h, _fp(qs), nq, width, int(max(min(topK, 2**31 - 1), -2**31)),
-            None if flat.size == 0 else _u64p(flat), int(flat.size),
-            None if begin is None else _u64p(begin), None if length is None else _u64p(length),
-            None if cuts is None else _fp(cuts), _u64p(ids), _fp(scores), kcap,
-            counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+        ranges = _per_pair(timeRange, nq, "timeRange", tuple_is_value=True, who="searchBatchFiltered", per="query")
+        denies = _per_pair(denyFlags, nq, "denyFlags", who="searchBatchFiltered", per="query")
+        preds = None
+        if any(r is not None for r in ranges) or any(d for d in denies):
+            preds = _row_predicates(ranges, denies)
+        head = (self._h, _fp(qs), nq, width, int(max(min(topK, 2**31 - 1), -2**31)),
+                None if flat.size == 0 else _u64p(flat), int(flat.size),
+                None if begin is None else _u64p(begin), None if length is None else _u64p(length),
+                None if cuts is None else _fp(cuts))
+        tail = (_u64p(ids), _fp(scores), kcap, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+        if preds is None:
+            rc = self._lib.wax_hip_search_batch_filtered(*head, *tail)
+        else:
+            rc = self._lib.wax_hip_search_batch_predicate(*head, preds, *tail)
         raise_for_status(rc)
         return ids, scores, counts
 
@@ -570,13 +581,25 @@ def searchMany(engines, queries, topK: int):  # noqa: N802,N803
     return ids, scores, counts
 
 
-def _per_pair(value, n: int, what: str, tuple_is_value: bool = False) -> list:
-    """One filter value for all n pairs, or a sequence of n (None entries: none for that pair) -> a list of n."""
+def _per_pair(value, n: int, what: str, tuple_is_value: bool = False, who: str = "searchManyFiltered", per: str = "pair") -> list:
+    """One filter value for all n pairs (queries), or a sequence of n (None entries: none for that one) -> a list of n."""
     if isinstance(value, (list, np.ndarray)) or (isinstance(value, tuple) and not tuple_is_value):
         if len(value) != n:
-            raise EncodingError(f"searchManyFiltered: {what} must be one value or hold one entry per pair")
+            raise EncodingError(f"{who}: {what} must be one value or hold one entry per {per}")
         return list(value)
     return [value] * n
+
+
+def _row_predicates(ranges: list, denies: list):
+    """n (after | None, before | None) tuples (or None) and n deny masks (or None) -> wax_hip_row_predicate[n]."""
+    n = len(ranges)
+    preds = (_abi.RowPredicate * n)()
+    for i in range(n):
+        after, before = (None, None) if ranges[i] is None else ranges[i]
+        preds[i] = _abi.RowPredicate(0 if after is None else 1, 0 if after is None else int(after),
+                                     0 if before is None else 1, 0 if before is None else int(before),
+                                     int(denies[i] or 0) & 0xffffffff)
+    return preds
 
 
 def searchManyFiltered(engines, queries, topK: int, timeRange=None, denyFlags=0, minScore=None):  # noqa: N802,N803
@@ -601,12 +624,7 @@ def searchManyFiltered(engines, queries, topK: int, timeRange=None, denyFlags=0,
     ranges, denies, cuts_in = _per_pair(timeRange, n, "timeRange", tuple_is_value=True), _per_pair(denyFlags, n, "denyFlags"), _per_pair(minScore, n, "minScore")
     preds = None
     if any(r is not None for r in ranges) or any(d for d in denies):
-        preds = (_abi.RowPredicate * n)()
-        for i in range(n):
-            after, before = (None, None) if ranges[i] is None else ranges[i]
-            preds[i] = _abi.RowPredicate(0 if after is None else 1, 0 if after is None else int(after),
-                                         0 if before is None else 1, 0 if before is None else int(before),
-                                         int(denies[i] or 0) & 0xffffffff)
+        preds = _row_predicates(ranges, denies)
     cuts = None
     if any(c is not None for c in cuts_in):
         cuts = np.array([np.nan if c is None else float(c) for c in cuts_in], dtype=np.float32)
