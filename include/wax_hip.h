@@ -599,6 +599,15 @@ int wax_hip_time_scan_kernel(wax_hip_engine* e, const float* query, uint32_t dim
 /* Pure streaming-read microbenchmark over the engine's own store (sum of all
  * float4s, no top-k): the node's achievable read bandwidth for this layout. */
 int wax_hip_time_stream_read(wax_hip_engine* e, uint32_t iters, double* out_avg_ms);
+/* Diagnostic read-out of the 8-bit code mirror ("mirror_bits"; tests hold the conversion kernel and its upkeep to a float64
+ * reference through it; no product path calls it). Copies what the device holds for rows [first_row, first_row + n_rows):
+ * out_codes = n_rows * dims biased bytes (code + 128) as stored, out_meta = n_rows * 2 floats {scale, err}; *out_max_norm = the
+ * mirror's max-norm word, *out_rows_coded = the number of rows coded. n_rows == 0 reports the last two only (out_codes and
+ * out_meta may then be NULL). It never builds or refreshes the mirror, waits for a conversion still in flight, and changes no
+ * counter and no breaker state. WAX_HIP_ERR_INVALID_ARGUMENT: a sharded handle, a code mirror that is absent or not valid (after
+ * any mutation, until a query has rebuilt it), a range beyond the coded rows, a needed pointer that is NULL. */
+int wax_hip_mirror8_snapshot(wax_hip_engine* e, uint64_t first_row, uint64_t n_rows, uint8_t* out_codes, float* out_meta,
+                             float* out_max_norm, uint64_t* out_rows_coded);
 
 #ifdef __cplusplus
 }

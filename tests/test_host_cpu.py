@@ -27,6 +27,26 @@ def test_library_exports_every_declared_symbol(hip_lib):
     assert hip_lib.wax_hip_abi_version() == 2
 
 
+def test_mirror8_snapshot_entry_is_declared_bound_and_refuses_a_null_engine(hip_lib):
+    """The code mirror's diagnostic read-out: exported, declared in the header and in _abi.py with the header's argument list, the
+    ABI version unchanged by it, and a NULL engine (or a NULL word pointer) refused with a message before any device is touched."""
+    from wax_amd import _abi
+    name = "wax_hip_mirror8_snapshot"
+    assert name in _abi.declared_symbols() and hasattr(hip_lib, name)
+    text = " ".join(open(_abi.HEADER_PATH).read().split())
+    assert ("int wax_hip_mirror8_snapshot(wax_hip_engine* e, uint64_t first_row, uint64_t n_rows, uint8_t* out_codes, float* out_meta, "
+            "float* out_max_norm, uint64_t* out_rows_coded);") in text
+    restype, argtypes = _abi.SIGNATURES[name]
+    assert restype is ctypes.c_int and argtypes == [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint8),
+                                                    ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                                                    ctypes.POINTER(ctypes.c_uint64)]
+    assert "#define WAX_HIP_ABI_VERSION 2\n" in open(_abi.HEADER_PATH).read() and hip_lib.wax_hip_abi_version() == 2
+    max_norm, rows = ctypes.c_float(-1.0), ctypes.c_uint64(77)
+    rc = hip_lib.wax_hip_mirror8_snapshot(None, 0, 0, None, None, ctypes.byref(max_norm), ctypes.byref(rows))
+    assert rc == _abi.ERR_INVALID_ARGUMENT and "null" in _abi.last_error()
+    assert max_norm.value == -1.0 and rows.value == 77
+
+
 def test_library_is_a_gfx950_code_object():
     from wax_amd import build
     path = build.build()

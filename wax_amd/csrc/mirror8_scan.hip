@@ -320,8 +320,11 @@ __global__ __launch_bounds__(SCAN_THREADS) void mirror8_finish_group_kernel(Mirr
 //           NaN) becomes zero — mirror_kernel's rule and expression; dot: v.
 //   scale   max|x^| / 127; code = rint(x^ / scale) clamped to +-127 (a zero row: scale 0, codes 0).
 //   err     sqrt(sum_i fma(scale, code_i, -x^_i)^2): each difference is rounded once (relative 2^-24), the sum of D squares and the root
-//           lose at most (D / 2 + 2) 2^-24 relative, so err * (1 + D 2^-23), then nextafter, is an upper bound.
-//   A row whose scale or err is not finite (an inf / NaN element, overflow) gets err = +inf and scale 0.
+//           lose at most (D / 2 + 2) 2^-24 relative, so err * (1 + D 2^-23), then nextafter, is an upper bound. The differences are
+//           squared and summed in units of 2^ex, scale = f * 2^ex (ldexpf: exact), and the root is scaled back: for a row of ordinary
+//           magnitude that changes no bit, and a row of 1e-30 or 1e+21 — whose squared differences are 0 or +inf in f32 — gets the err
+//           it has instead of 2^-149 (no bound at all) or +inf.
+//   A row with an inf / NaN element (or whose scale or err is still not finite) gets err = +inf and scale 0.
 __global__ __launch_bounds__(256) void mirror8_kernel(const float* __restrict__ src, uint32_t n_rows, uint32_t dims, int normalize,
                                                       unsigned char* __restrict__ codes, float* __restrict__ meta,
                                                       unsigned int* __restrict__ max_norm_bits) {
@@ -356,6 +359,8 @@ __global__ __launch_bounds__(256) void mirror8_kernel(const float* __restrict__ 
         bad = __ballot(bad) != 0ull;
         float scale = amax / 127.0f;
         if (!__builtin_isfinite(scale)) { bad = true; scale = 0.f; }
+        int ex = 0;                              // scale = f * 2^ex, f in [0.5, 1): the differences are squared in units of 2^ex
+        (void)frexpf(scale, &ex);
         float e2 = 0.f;
         unsigned int* out = reinterpret_cast<unsigned int*>(codes + (size_t)r * dims);
         for (uint32_t c = lane; c < d4; c += WAVE) {
@@ -366,7 +371,7 @@ __global__ __launch_bounds__(256) void mirror8_kernel(const float* __restrict__ 
             for (int i = 0; i < 4; ++i) {
                 float t = (scale > 0.f && x[i] == x[i]) ? x[i] / scale : 0.f;
                 t = rintf(fminf(fmaxf(t, -127.0f), 127.0f));
-                const float d = fmaf(scale, t, -x[i]);
+                const float d = ldexpf(fmaf(scale, t, -x[i]), -ex);
                 e2 = fmaf(d, d, e2);
                 word |= (unsigned int)((int)t + 128) << (8 * i);
             }
@@ -374,9 +379,11 @@ __global__ __launch_bounds__(256) void mirror8_kernel(const float* __restrict__ 
         }
         e2 = group_sum<64>(e2);
         e2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e2), 63));
-        float err = sqrtf(e2) * (1.0f + (float)dims * 1.1920929e-7f);
-        err = nextafterf(err, __builtin_inff());
-        if (bad || !__builtin_isfinite(err)) err = __builtin_inff();
+        float errn = sqrtf(e2) * (1.0f + (float)dims * 1.1920929e-7f);
+        errn = nextafterf(errn, __builtin_inff());
+        float err = ldexpf(errn, ex);
+        if (ldexpf(err, -ex) < errn) err = nextafterf(err, __builtin_inff());     // back in the subnormal range: rounded up, never down
+        if (bad || !__builtin_isfinite(err)) { err = __builtin_inff(); scale = 0.f; }
         if (lane == 0) { meta[2 * (size_t)r] = scale; meta[2 * (size_t)r + 1] = err; }
         if (n == n && n > wave_max) wave_max = n;
     }

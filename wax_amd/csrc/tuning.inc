@@ -318,3 +318,32 @@ int wax_hip_time_stream_read(wax_hip_engine* e, uint32_t iters, double* out_avg_
     return rc;
 }
 
+
+// Diagnostic read-out of the 8-bit code mirror as the device holds it (tests/test_mirror8_edges_gpu.py): a copy, never a build or a
+// refresh, no counter and no breaker state touched. Refused unless the code mirror is valid, so it never hands out rows that are not coded.
+int wax_hip_mirror8_snapshot(wax_hip_engine* e, uint64_t first_row, uint64_t n_rows, uint8_t* out_codes, float* out_meta,
+                             float* out_max_norm, uint64_t* out_rows_coded) {
+    if (!e || !out_max_norm || !out_rows_coded || (n_rows > 0 && (!out_codes || !out_meta))) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    SHARDED_UNSUPPORTED(e, "wax_hip_mirror8_snapshot");
+    DeviceGuard g(e->device);
+    ReadGuard rg(e);
+    BatchMirror& b = e->batch;
+    std::unique_lock<std::mutex> mg(b.mu8);
+    if (!b.c8_valid.load(std::memory_order_acquire) || b.d_c8 == nullptr || b.d_c8_meta == nullptr || b.d_c8_max == nullptr || b.c8_cap < e->capacity)
+        return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror8_snapshot: the code mirror is absent or not valid");
+    const uint64_t rows = b.rows8.load();
+    if (first_row > rows || n_rows > rows - first_row)
+        return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror8_snapshot: rows [" + std::to_string(first_row) + ", " + std::to_string(first_row) + " + " +
+                                                  std::to_string(n_rows) + ") exceed the " + std::to_string(rows) + " coded rows");
+    if (b.ev8_pending) HIP_TRY(hipEventSynchronize(b.ev8_ready), WAX_HIP_ERR_INTERNAL, "code mirror ready wait");
+    const size_t D = e->dims;
+    unsigned int max_bits = 0u;
+    HIP_TRY(hipMemcpy(&max_bits, b.d_c8_max, sizeof(max_bits), hipMemcpyDeviceToHost), WAX_HIP_ERR_INTERNAL, "mirror8_snapshot copy");
+    if (n_rows > 0) {
+        HIP_TRY(hipMemcpy(out_codes, b.d_c8 + first_row * D, (size_t)n_rows * D, hipMemcpyDeviceToHost), WAX_HIP_ERR_INTERNAL, "mirror8_snapshot copy");
+        HIP_TRY(hipMemcpy(out_meta, b.d_c8_meta + 2 * first_row, (size_t)n_rows * 2 * sizeof(float), hipMemcpyDeviceToHost), WAX_HIP_ERR_INTERNAL, "mirror8_snapshot copy");
+    }
+    std::memcpy(out_max_norm, &max_bits, sizeof(float));
+    *out_rows_coded = rows;
+    return WAX_HIP_OK;
+}

@@ -556,6 +556,20 @@ class HIPVectorEngine:
         raise_for_status(self._lib.wax_hip_time_stream_read(self._h, int(iters), ctypes.byref(ms)))
         return float(ms.value)
 
+    def mirror8Snapshot(self, first: int = 0, n=None):  # noqa: N802
+        """What the device holds of the 8-bit code mirror for rows [first, first + n) (n None: up to the last coded row), for tests
+        (wax_hip_mirror8_snapshot): (codes uint8 [n, dims], scale f32 [n], err f32 [n], max_norm, rows_coded). Raises unless the code
+        mirror is valid; it is never built or refreshed here."""
+        max_norm, rows = ctypes.c_float(0.0), ctypes.c_uint64(0)
+        if n is None:
+            raise_for_status(self._lib.wax_hip_mirror8_snapshot(self._h, 0, 0, None, None, ctypes.byref(max_norm), ctypes.byref(rows)))
+            n = max(int(rows.value) - int(first), 0)
+        codes = np.zeros((int(n), self.dimensions), dtype=np.uint8)
+        meta = np.zeros((int(n), 2), dtype=np.float32)
+        raise_for_status(self._lib.wax_hip_mirror8_snapshot(self._h, int(first), int(n), codes.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                                            _fp(meta), ctypes.byref(max_norm), ctypes.byref(rows)))
+        return codes, meta[:, 0].copy(), meta[:, 1].copy(), float(max_norm.value), int(rows.value)
+
 
 def searchMany(engines, queries, topK: int):  # noqa: N802,N803
     """One query each against many stores of one device in one pass (wax_hip_search_many): pair i is (engines[i], queries[i]).
