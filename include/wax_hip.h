@@ -480,7 +480,9 @@ int wax_hip_stats(wax_hip_engine* e, wax_hip_stats_t* out);
  *   selection behind it answers; 64 < top_k <= 192 on grids that do not merge in the scan kernel = the same workgroup is the final
  *   merge (nothing can have been dropped: no certificate), the wave-list merge stays behind it, gated; 0 = the long path / the wave-list
  *   merge at once; 2 = like 1 with 192-entry lists whatever top_k (1 keeps 64-entry lists while top_k <= 8 per workgroup); "force_general"
- *   implies 0 for top_k > 192), "short_selects" / "short_select_failures" (read-only: short selections
+ *   implies 0 for top_k > 192), "select_grid" (0 (default) = the radix selection's histogram and compaction passes run
+ *   min(2048, ceil(rows / 256)) workgroups; 1..2048 = at most that many, so that a thread takes several trips of its loops on a small
+ *   store: for tests), "short_selects" / "short_select_failures" (read-only: short selections
  *   enqueued / that left the answer to the launches behind them),
  *   "scan_mirror" (single queries, dims 384 / 768, cosine / dot, top_k <= 32, default variant, no "force_general": 1 (default) = stores of
  *   more than 2 GiB of f32 rows stream the bf16 mirror instead (half the bytes), re-score the 64 best rows in f32 with the f32 scan's

@@ -470,6 +470,7 @@ struct wax_hip_engine {
     std::atomic<int64_t> variant{-1};
     std::atomic<int64_t> time_kernels{0};
     std::atomic<int64_t> force_general{0};
+    std::atomic<int64_t> select_grid{0};     // workgroups of the radix selection's histogram and compaction passes: 0 = min(2048, ceil(rows / 256)), else at most this many (1..2048; tests drive the multi-trip loops on small stores)
     std::atomic<int64_t> select_short{1};    // k > 192: select from the fused scan's per-workgroup lists first (one launch, certified); 0 = the distance pass + radix selection at once
     std::atomic<int64_t> stream_nt{1};
     std::atomic<int64_t> scan_plain_mb{32};  // single-query scans with the query in their arguments: stores up to this many MB read their rows with ordinary loads (-1 = grids <= 160 workgroups)

@@ -96,7 +96,7 @@ static int gather_topk(wax_hip_engine* e, FilterWork& f, const float* query, uin
     r.n_rows = (uint32_t)e->count; r.row_base = 0; r.dims = dims; r.nq = 1; r.cand_cap = 0; r.kp = (int)m;
     HIP_TRY(launch_rescore(r, e->metric, st), WAX_HIP_ERR_INTERNAL, "distance kernel launch");
     // keys of the compact list carry the POSITION in it; positions ascend with rows, so ties order as everywhere else
-    HIP_TRY(launch_select_general(f.d_dist, (uint32_t)m, 0u, k_eff, k_eff, f.d_ids, f.sw, f.d_hits, st), WAX_HIP_ERR_INTERNAL, "select kernel launch");
+    HIP_TRY(launch_select_general(f.d_dist, (uint32_t)m, 0u, k_eff, k_eff, f.d_ids, f.sw, f.d_hits, st, nullptr, (int)e->select_grid.load()), WAX_HIP_ERR_INTERNAL, "select kernel launch");
     HIP_TRY(hipMemcpyAsync(f.h_hits, f.d_hits, (size_t)k_eff * sizeof(wax_hip_hit), hipMemcpyDeviceToHost, st), WAX_HIP_ERR_INTERNAL, "hits download");
     HIP_TRY(hipStreamSynchronize(st), WAX_HIP_ERR_INTERNAL, sync_what);
     const int rc = hits_to_results(e->metric, f.h_hits, (uint32_t)k_eff, out_ids, out_scores, out_capacity, out_n);

@@ -304,7 +304,8 @@ struct SelectWork {
 // `gate` (may be null = run): device word; every kernel of the chain returns at once while *gate == 0 (the short selection answered).
 hipError_t launch_select_general(const float* d_dist, uint32_t n_rows, uint32_t row_base, int k, int kpad,
                                  const uint64_t* d_ids, const SelectWork& w, wax_hip_hit* d_out,
-                                 hipStream_t stream, const uint32_t* gate = nullptr);
+                                 hipStream_t stream, const uint32_t* gate = nullptr, int grid_cap = 0);
+// (grid_cap: 0 = min(2048, ceil(n_rows / 256)) workgroups for the histogram and compaction passes, else at most grid_cap (<= 2048) of them.)
 // Short selection over the fused scan's per-workgroup lists (`lists` x `per_list` keys, each ascending, KEY_PAD-padded: every
 // workgroup's `per_list` best). ONE workgroup sorts the lists' first few entries in LDS to get a tight upper bound of the k-th key,
 // gathers the lists' prefixes below it, sorts those and writes the k best as hits. per_list >= k (the fused path's final merge for

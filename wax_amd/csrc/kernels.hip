@@ -854,10 +854,12 @@ __global__ __launch_bounds__(256) void keys_to_hits_kernel(const int64_t* __rest
 }
 
 hipError_t launch_select_general(const float* d_dist, uint32_t n_rows, uint32_t row_base, int k, int kpad,
-                                 const uint64_t* d_ids, const SelectWork& w, wax_hip_hit* d_out, hipStream_t st, const uint32_t* gate) {
-    if (k < 1 || (uint32_t)k > n_rows || k > WAX_HIP_MAX_RESULTS || kpad < k) return hipErrorInvalidValue;
+                                 const uint64_t* d_ids, const SelectWork& w, wax_hip_hit* d_out, hipStream_t st, const uint32_t* gate,
+                                 int grid_cap) {
+    if (k < 1 || (uint32_t)k > n_rows || k > WAX_HIP_MAX_RESULTS || kpad < k || grid_cap < 0 || grid_cap > 2048) return hipErrorInvalidValue;
     int grid = (int)((n_rows + 255) / 256);
     if (grid > 2048) grid = 2048;
+    if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;   // ("select_grid": fewer workgroups, more trips of a thread's loops)
     for (int pass = 0; pass < SEL_PASSES; ++pass)
         hipLaunchKernelGGL(select_hist_kernel, dim3(grid), dim3(256), 0, st, d_dist, n_rows, row_base, pass, (uint32_t)k, w.state,
                            w.hist, w.counter, gate);

@@ -204,7 +204,7 @@ int enqueue_scan(wax_hip_engine* e, const float* d_query, float q_norm, int k_ef
             chain_guard.unlock();
         }
         HIP_TRY(launch_select_general(general_slot->d_dist, a.n_rows, a.row_base, k_eff, kpad, e->d_ids,
-                                      general_slot->sw, d_hits, stream, a.gate),
+                                      general_slot->sw, d_hits, stream, a.gate, (int)e->select_grid.load()),
                 WAX_HIP_ERR_INTERNAL, "select kernel launch");
     }
     e->st_searches++;

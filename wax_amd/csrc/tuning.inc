@@ -35,6 +35,7 @@ int wax_hip_set_tuning(wax_hip_engine* e, const char* key, int64_t value) {
     else if (k == "variant") e->variant = value;
     else if (k == "time_kernels") e->time_kernels = value;
     else if (k == "force_general") e->force_general = value;
+    else if (k == "select_grid") { if (value < 0 || value > 2048) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "select_grid must be 0 (auto) .. 2048"); e->select_grid = value; }
     else if (k == "select_short") { if (value < 0 || value > 2) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "select_short must be 0, 1 or 2"); e->select_short = value; }
     else if (k == "stream_nt") e->stream_nt = value;
     else if (k == "fuse_merge") e->fuse_merge = value != 0;
@@ -116,6 +117,7 @@ int64_t wax_hip_get_tuning(wax_hip_engine* e, const char* key) {
     if (k == "time_kernels") return e->time_kernels.load();
     if (k == "force_general") return e->force_general.load();
     if (k == "select_short") return e->select_short.load();
+    if (k == "select_grid") return e->select_grid.load();
     if (k == "short_selects") return (int64_t)e->st_short_selects.load();
     if (k == "short_select_failures") {   // short selections whose certificate failed (the long path answered): device words of every slot; a blocking read
         int64_t t = 0;
