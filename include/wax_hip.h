@@ -393,7 +393,9 @@ typedef struct wax_hip_row_predicate {
  * for the same rows. pred NULL, or one with no bound and no deny bit, is wax_hip_search_filtered. The predicate is evaluated on
  * the device into a row bitmap; then either the passing rows are gathered and scored (few pass, top_k > 192, dims outside the
  * specialised set, "force_general") or the f32 scan runs with the bitmap, skipping the loads of chunks without a passing row
- * ("predicate_route", "predicate_scan_min_permille"). */
+ * ("predicate_route", "predicate_scan_min_permille"). On a store above 2 GiB of f32 rows that scan streams the bf16
+ * mirror under the same bitmap instead, re-scores its 64 best passing rows in f32 and returns them only under the mirror scan's
+ * certificate — the same answer bit for bit; without the certificate the f32 scan answers ("predicate_mirror"). */
 int wax_hip_search_predicate(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k,
                              int has_allow, const uint64_t* allow_frame_ids, uint64_t n_allow,
                              int has_min_score, float min_score, const wax_hip_row_predicate* pred,
@@ -568,13 +570,25 @@ int wax_hip_stats(wax_hip_engine* e, wax_hip_stats_t* out);
  *   "predicate_route" (0 (default) = auto, 1 = always gather the passing rows — bitmap -> compact row list -> exact distances of the
  *   listed rows -> general selection —, 2 = the masked f32 scan wherever it is eligible: top_k <= 192, a specialised dimension, no
  *   "force_general"), "predicate_scan_min_permille" (the auto rule: the masked scan when at least this many rows per thousand pass;
- *   default 500: where the first build's routes crossed for a random mask, between 1/8 and 1/2 passing; the committed kernels are
- *   not timed yet: DESIGN 4.5),
+ *   default 500: where the first build's routes crossed for a random mask, between 1/8 and 1/2 passing; at 10M rows the committed
+ *   f32 scan crosses the gather between 1/2 and 15/16, the mirror form between 1/8 and 1/2: DESIGN 4.5),
+ *   "predicate_mirror" (a form of the masked scan, not a route of its own: where "predicate_route" sends a query to the masked scan,
+ *   cosine or dot at 384 / 768 dimensions, top_k <= 32, the default "variant", "grid_blocks" <= 512 and more than 64 rows pass, the scan
+ *   streams the bf16 mirror under the bitmap — 16 / 8 rows per chunk —, the 64 best approximate keys among the passing rows are re-scored
+ *   in f32, and the answer is returned only under the single-query mirror scan's certificate: then it is the masked f32 scan's bit for
+ *   bit; otherwise the masked f32 scan answers on the same bitmap. 0 = never; 1 (default) = auto: stores of more than 2 GiB of f32 rows
+ *   while "scan_mirror" != 0; 2 = every store; other values are refused. A mirror that cannot be allocated or converted sends the query
+ *   to the f32 scan: no query fails because of it),
+ *   get-only "predicate_mirror_scans" / "predicate_mirror_fallbacks" / "predicate_mirror_unavailable" (masked scans answered from the
+ *   mirror under the certificate / re-run on the masked f32 scan because the certificate failed / sent there because the mirror could
+ *   not be prepared; each of them counts once in "predicate_masked_scans"),
  *   get-only "predicate_searches" (calls with a non-empty predicate), "predicate_gather_searches" / "predicate_masked_scans" (those
  *   answered by either route; a call whose predicate no row passes counts in neither), "predicate_chunks_skipped" (chunks of rows the
  *   masked scans did not load), "attr_uploaded_rows" (rows of the attribute columns uploaded so far — an append uploads its own rows
  *   only), "attr_device_rows" (rows the device columns are allocated for; 0 = the store never had attributes). wax_hip_stats'
- *   bytes_scanned counts what a predicate search actually read: the gathered rows, or every row of the chunks it did not skip.
+ *   bytes_scanned counts what a predicate search actually read: the gathered rows, or every row of the chunks it did not skip (the
+ *   mirror form: its chunks at two bytes per element plus the 64 re-scored f32 rows, and the f32 scan's figures on top when the
+ *   certificate failed; "predicate_chunks_skipped" then counts the mirror's chunks, and the f32 scan's too on a fallback).
  * get-only
  *   "variant_count", "scan_grid", "store_ptr" (device address of the f32 slab), "fused_max_k", "batch_queries", "query_args_scans", "merged_scans", "done_flag_waits",
  *   "batch_inline_retries", "batch_max_row_err_e9", "batch_fallbacks", "onepass_queries", "batch_max_k", "batch_retries",

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""The two routes of wax_hip_search_predicate against each other and against the unfiltered f32 scan.
+"""The routes of wax_hip_search_predicate against each other and against the unfiltered scans.
 
 Store: --rows x 384 (default 1M), top-10, blocking calls, alternated runs, medians. For each pass fraction (1/64, 1/8, 1/2, 15/16)
 and each mask shape (a random deny bit, one contiguous time range) it times the gather route ("predicate_route" 1), the masked
-scan (2), today's alternative — searchFiltered with the allow-list of the passing ids — and, in the same alternation, the
-unfiltered f32 scan ("scan_mirror" 0, "mirror_share" 0). It prints one JSON line and, with --out, writes the same object to a file:
-the route table, the crossover of the random mask (the smallest measured fraction from which the masked scan is the faster route),
-masked / unfiltered at 15/16, and the bytes a contiguous 1/16 range read."""
+f32 scan (2 with "predicate_mirror" 0), the masked scan's mirror form (2 with "predicate_mirror" 2), today's alternative —
+searchFiltered with the allow-list of the passing ids — and, in the same alternation, the unfiltered f32 scan ("scan_mirror" 0) and
+the unfiltered lone bf16 mirror pass ("scan_mirror" 2, "mirror_bits" 16); "mirror_share" is 0 throughout. It prints one JSON line
+and, with --out, writes the same object to a file: the route table with each form's run-to-run spread (the interquartile range of
+its alternated times), the crossover of the random mask (the smallest measured fraction from which the masked f32 scan is faster than
+the gather), the same for the mirror form, masked / unfiltered and mirror / masked at 15/16, and the bytes both scans read."""
 import argparse
 import json
 import os
@@ -37,6 +39,7 @@ for r0, x in bench.device_rows(torch, 0, rows, dims, dev):
     eng.addBatchDevice(np.arange(r0, r0 + x.shape[0], dtype=np.uint64), x)
 eng.setTuning("scan_mirror", 0)
 eng.setTuning("mirror_share", 0)
+eng.setTuning("mirror_bits", 16)
 ids = np.arange(rows, dtype=np.uint64)
 rng = np.random.default_rng(0)
 # bit 8 + j: a random mask that PASSES fraction FRACS[j] (the bit is set on the rows that fail); timestamps ascend with the row
@@ -56,24 +59,39 @@ def timed(fn):
 
 
 def alternated(fns, reps):
-    """Every function once per round, in turn, `reps` rounds after one warm-up round: medians in ms."""
+    """Every function once per round, in turn, `reps` rounds after one warm-up round: medians in ms, and under name + "_iqr" the
+    interquartile range of the same times (the run-to-run spread a difference of medians has to exceed)."""
     for f in fns.values():
         f(0)
     t = {name: [] for name in fns}
     for i in range(reps):
         for name, f in fns.items():
             t[name].append(timed(lambda: f(i)))
-    return {name: round(statistics.median(v), 4) for name, v in t.items()}
+    res = {name: round(statistics.median(v), 4) for name, v in t.items()}
+    for name, v in t.items():
+        qs = statistics.quantiles(v, n=4) if len(v) >= 2 else [v[0], v[0], v[0]]
+        res[name.replace("_ms", "") + "_iqr_ms"] = round(qs[2] - qs[0], 4)
+    return res
 
 
-def routed(route, **kw):
+def routed(route, mirror=0, **kw):
     def f(i):
         eng.setTuning("predicate_route", route)
+        eng.setTuning("predicate_mirror", mirror)
         got = eng.searchFiltered(q[i % 4], k, **kw)
         assert len(got[0]) == k
     return f
 
 
+def unfiltered(scan_mirror):
+    def f(i):
+        eng.setTuning("scan_mirror", scan_mirror)
+        got = eng.searchArrays(q[i % 4], k)
+        assert len(got[0]) == k
+    return f
+
+
+MIRROR_COUNTERS = ("predicate_mirror_scans", "predicate_mirror_fallbacks", "predicate_mirror_unavailable")
 out = {"rows": rows, "dims": dims, "topk": k, "reps": args.reps, "table": []}
 for a, b in [(1, 64), (1, 16), (1, 8), (1, 2), (15, 16)]:     # 1/16: the contiguous range only (what the chunk skip is for)
     span = rows * a // b
@@ -90,16 +108,29 @@ for a, b in [(1, 64), (1, 16), (1, 8), (1, 2), (15, 16)]:     # 1/16: the contig
         row = {"pass": f"{a}/{b}", "mask": shape, "passing_rows": int(len(passing)),
                "masked_bytes_read": int(eng.stats().bytes_scanned - b0), "chunks_skipped": eng.getTuning("predicate_chunks_skipped") - s0}
         assert scans == 1
+        c0 = [eng.getTuning(c) for c in MIRROR_COUNTERS]
+        b0, s0 = eng.stats().bytes_scanned, eng.getTuning("predicate_chunks_skipped")
+        routed(2, 2, **kw)(0)
+        row["mirror_bytes_read"] = int(eng.stats().bytes_scanned - b0)        # (a fallback adds the f32 scan's bytes)
+        row["mirror_chunks_skipped"] = eng.getTuning("predicate_chunks_skipped") - s0
         row.update(alternated({
             "gather_ms": routed(1, **kw),
-            "masked_ms": routed(2, **kw),
+            "masked_ms": routed(2, 0, **kw),
+            "masked_mirror_ms": routed(2, 2, **kw),
             "allow_list_ms": lambda i, p=passing: eng.searchFiltered(q[i % 4], k, frameIds=p),
-            "unfiltered_ms": lambda i: eng.searchArrays(q[i % 4], k),
+            "unfiltered_ms": unfiltered(0),
+            "unfiltered_bf16_ms": unfiltered(2),
         }, args.reps))
+        for c, v0 in zip(MIRROR_COUNTERS, c0):                                # over the probe, the warm-up and the timed rounds
+            row[c] = eng.getTuning(c) - v0
         row["masked_over_unfiltered"] = round(row["masked_ms"] / row["unfiltered_ms"], 4)
+        row["mirror_over_masked"] = round(row["masked_mirror_ms"] / row["masked_ms"], 4)
+        row["mirror_over_unfiltered_bf16"] = round(row["masked_mirror_ms"] / row["unfiltered_bf16_ms"], 4)
         out["table"].append(row)
         print(json.dumps(row), file=sys.stderr, flush=True)
 eng.setTuning("predicate_route", 0)
+eng.setTuning("predicate_mirror", 1)
+eng.setTuning("scan_mirror", 0)
 rand = [r for r in out["table"] if r["mask"] == "random"]
 # the crossover: the smallest measured fraction from which on the masked scan wins at every larger one too
 cross = None
@@ -110,6 +141,16 @@ for r in rand:
 out["random_mask_crossover_pass"] = cross
 out["random_mask_crossover_permille"] = None if cross is None else int(round(1000 * int(cross.split("/")[0]) / int(cross.split("/")[1])))
 out["masked_over_unfiltered_at_15_16"] = [r["masked_over_unfiltered"] for r in rand if r["pass"] == "15/16"][0]
+# the same for the mirror form against the gather, and the decision figure: mirror / masked f32 at 15/16 beside both spreads
+cross = None
+for r in rand:
+    if all(x["masked_mirror_ms"] <= x["gather_ms"] for x in rand[rand.index(r):]):
+        cross = r["pass"]
+        break
+out["random_mask_mirror_crossover_pass"] = cross
+at = [r for r in rand if r["pass"] == "15/16"][0]
+out["mirror_over_masked_at_15_16"] = at["mirror_over_masked"]
+out["mirror_faster_at_15_16_beyond_spread"] = bool(at["masked_ms"] - at["masked_mirror_ms"] > max(at["masked_iqr_ms"], at["masked_mirror_iqr_ms"]))
 print(json.dumps(out))
 if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

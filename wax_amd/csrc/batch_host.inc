@@ -406,8 +406,9 @@ int grow_dev(T** p, uint64_t* cap, uint64_t want, size_t elem, const char* what)
 
 void free_filter_work(FilterWork* f) {
     if (!f) return;
-    (void)hipFree(f->d_pred_counts); (void)hipFree(f->d_partials);
+    (void)hipFree(f->d_pred_counts); (void)hipFree(f->d_partials); (void)hipFree(f->d_mirror_out);
     if (f->h_pred_counts) (void)hipHostFree(f->h_pred_counts);
+    if (f->h_mirror_out) (void)hipHostFree(f->h_mirror_out);
     (void)hipFree(f->d_rows); (void)hipFree(f->d_ids); (void)hipFree(f->d_dist); (void)hipFree(f->d_allow); (void)hipFree(f->d_bitmap);
     (void)hipFree(f->d_block_sum); (void)hipFree(f->d_total); (void)hipFree(f->d_query); (void)hipFree(f->d_qnorm); (void)hipFree(f->d_hits);
     (void)hipFree(f->d_bq); (void)hipFree(f->d_meta); (void)hipFree(f->d_lrows); (void)hipFree(f->d_lcnt); (void)hipFree(f->d_lids);

@@ -260,11 +260,16 @@ struct FilterWork {
     wax_hip_hit* d_bhits = nullptr;  // [bhits_cap] merged hits, one row of k per fused query
     uint64_t bhits_cap = 0;
     // wax_hip_search_predicate (allocated by its first call on this workspace)
-    uint32_t* d_pred_counts = nullptr;   // [2] passing rows, scan chunks that hold one (attr_mask_kernel)
-    uint32_t* h_pred_counts = nullptr;   // pinned [2]
+    uint32_t* d_pred_counts = nullptr;   // [kPredCounts] passing rows, scan chunks that hold one, mirror chunks that hold one (attr_mask_kernel)
+    uint32_t* h_pred_counts = nullptr;   // pinned [kPredCounts]
     int64_t* d_partials = nullptr;       // masked scan: kPartialsBytes, the per-workgroup lists + the short merge's flag words
+    // the masked scan's mirror form ("predicate_mirror"): what mirror_finish_kernel writes — [MIRROR_MAX_K] hits, then one slot whose
+    // first word is the certificate — so that one copy brings both to the host
+    wax_hip_hit* d_mirror_out = nullptr; // [MIRROR_MAX_K + 1]
+    wax_hip_hit* h_mirror_out = nullptr; // pinned [MIRROR_MAX_K + 1]
 };
 
+constexpr size_t kPredCounts = 3;        // words of FilterWork::d_pred_counts (AttrMaskArgs::counts)
 void free_filter_work(FilterWork* f);
 
 // id -> row table in HBM (filter.hip): built at the first long allow-list, rebuilt lazily after a mutation.
@@ -587,9 +592,14 @@ struct wax_hip_engine {
     std::atomic<uint64_t> st_attr_uploaded{0};
     std::atomic<int64_t> predicate_route{0};      // 0 = auto, 1 = always gather the passing rows, 2 = the masked scan wherever it is eligible
     // auto rule: the masked scan when at least this many rows per thousand pass. 500 = the random mask's crossover of the FIRST build
-    // (between 1/8 and 1/2 passing, profiles/r13/c_routes_first_build.json); the committed kernels have not been timed (DESIGN 4.5).
+    // (between 1/8 and 1/2 passing, profiles/r13/c_routes_first_build.json). At 10M rows the committed f32 scan crosses the gather
+    // between 1/2 and 15/16, its mirror form between 1/8 and 1/2 (profiles/r20/predicate_mirror.json; DESIGN 4.5): not retuned.
     std::atomic<int64_t> predicate_scan_min_permille{500};
     std::atomic<uint64_t> st_predicate_searches{0}, st_predicate_gather{0}, st_predicate_masked{0}, st_predicate_skipped{0};
+    // the masked scan over the bf16 mirror + f32 re-score + certificate (DESIGN 4.5): 1 (default) = stores of > SCAN_KWAY_MAX_BYTES of
+    // rows while "scan_mirror" != 0, 2 = every store, 0 = never
+    std::atomic<int64_t> predicate_mirror{1};
+    std::atomic<uint64_t> st_predicate_mirror_scans{0}, st_predicate_mirror_fallbacks{0}, st_predicate_mirror_unavailable{0};
     std::atomic<int64_t> filter_device_min{4096}; // allow-lists at least this long are resolved on the device
     std::atomic<uint64_t> st_filter_device{0};    // filtered searches whose allow-list was resolved on the device
     std::atomic<int64_t> filter_batch{1};         // wax_hip_search_batch_filtered: 1 = one gather pass for all lists, 0 = the per-query loop

@@ -107,16 +107,21 @@ static int gather_topk(wax_hip_engine* e, FilterWork& f, const float* query, uin
     return WAX_HIP_OK;
 }
 
+// the per-workgroup key lists of either masked scan (+ the short merge's flag words, zero from the start)
+static int reserve_partials(FilterWork& f) {
+    if (f.d_partials) return WAX_HIP_OK;
+    HIP_TRY(hipMalloc(&f.d_partials, kPartialsBytes), WAX_HIP_ERR_ALLOC, "Failed to allocate top-k stage buffer");
+    HIP_TRY(hipMemsetAsync(partials_ticket(f.d_partials), 0, 128, f.stream), WAX_HIP_ERR_INTERNAL, "top-k stage buffer");
+    return WAX_HIP_OK;
+}
+
 // The masked-scan tail: f.d_bitmap marks the m passing rows, live_chunks of the scan's chunks hold one. The f32 scan's rows, loads and
 // arithmetic; chunks without a passing row are not read; the per-workgroup lists go through the second-launch merge.
 static int masked_scan_topk(wax_hip_engine* e, FilterWork& f, const float* query, uint32_t dims, uint64_t m, uint64_t live_chunks, int kpad,
                             uint64_t* out_ids, float* out_scores, uint32_t out_capacity, uint32_t* out_n, const char* sync_what) {
     hipStream_t st = f.stream;
     const uint32_t count = (uint32_t)e->count, chunk_rows = scan_masked_chunk_rows(dims);
-    if (!f.d_partials) {
-        HIP_TRY(hipMalloc(&f.d_partials, kPartialsBytes), WAX_HIP_ERR_ALLOC, "Failed to allocate top-k stage buffer");
-        HIP_TRY(hipMemsetAsync(partials_ticket(f.d_partials), 0, 128, st), WAX_HIP_ERR_INTERNAL, "top-k stage buffer");
-    }
+    { const int prc = reserve_partials(f); if (prc != WAX_HIP_OK) return prc; }
     const int k_eff = (uint64_t)kpad < m ? kpad : (int)m;
     const int cap = wave_list_cap(k_eff);
     HIP_TRY(hipMemcpyAsync(f.d_query, query, (size_t)dims * sizeof(float), hipMemcpyHostToDevice, st), WAX_HIP_ERR_INTERNAL, "query upload");
@@ -139,12 +144,72 @@ static int masked_scan_topk(wax_hip_engine* e, FilterWork& f, const float* query
     return WAX_HIP_OK;
 }
 
+// May a predicate query for kpad results that the route rule sends to the masked scan stream the bf16 mirror ("predicate_mirror")?
+// scan_uses_mirror's conditions (search_internal.inc) with this key in the place of "scan_mirror"; in auto mode "scan_mirror" 0
+// switches this form off too. ("force_general" has already kept the query from the masked scan.)
+static bool predicate_uses_mirror(wax_hip_engine* e, int kpad) {
+    const int64_t mode = e->predicate_mirror.load();
+    if (mode == 0 || kpad < 1 || kpad > MIRROR_MAX_K || !mirror_scan_supported(e->dims, e->metric)) return false;
+    if (e->variant.load() > 0 || e->grid_blocks.load() > SCAN_KWAY_MERGE_GRID) return false;
+    return mode >= 2 || (e->scan_mirror.load() != 0 && e->count * (uint64_t)e->dims * sizeof(float) > SCAN_KWAY_MAX_BYTES);
+}
+
+// The masked scan's mirror form (mirror_scan.hip; DESIGN 4.5): the bf16 mirror under the bitmap, the MIRROR_KP best approximate keys
+// among the m > MIRROR_KP passing rows re-scored in f32, the answer released under the certificate — then it is the masked f32 scan's,
+// bit for bit. live_mirror_chunks of the mirror kernel's chunks hold a passing row. Without a mirror, or without the certificate, the
+// masked f32 scan answers on the same bitmap: no query fails because of the mirror.
+static int masked_mirror_topk(wax_hip_engine* e, FilterWork& f, const float* query, uint32_t dims, uint64_t m, uint64_t live_chunks,
+                              uint64_t live_mirror_chunks, int kpad, uint64_t* out_ids, float* out_scores, uint32_t out_capacity, uint32_t* out_n,
+                              const char* sync_what) {
+    hipStream_t st = f.stream;
+    BatchMirror& b = e->batch;
+    {
+        const std::string keep = g_last_error;
+        if (ensure_mirror(e, st) != WAX_HIP_OK || b.d_cb == nullptr || b.d_maxnorm == nullptr) {
+            (void)hipGetLastError();                          // a refused allocation must not surface in the f32 launch behind it
+            g_last_error = keep;
+            e->st_predicate_mirror_unavailable++;
+            return masked_scan_topk(e, f, query, dims, m, live_chunks, kpad, out_ids, out_scores, out_capacity, out_n, sync_what);
+        }
+    }
+    { const int prc = reserve_partials(f); if (prc != WAX_HIP_OK) return prc; }
+    constexpr size_t out_bytes = (size_t)(MIRROR_MAX_K + 1) * sizeof(wax_hip_hit);
+    if (!f.d_mirror_out) HIP_TRY(hipMalloc(&f.d_mirror_out, out_bytes), WAX_HIP_ERR_ALLOC, "Failed to allocate mirror scan results");
+    if (!f.h_mirror_out) HIP_TRY(hipHostMalloc(&f.h_mirror_out, out_bytes, hipHostMallocDefault), WAX_HIP_ERR_ALLOC, "Failed to allocate mirror scan results");
+    const uint32_t count = (uint32_t)e->count, chunk_rows = mirror_masked_chunk_rows(dims);
+    MirrorScanArgs a{};
+    a.mirror = b.d_cb; a.store = e->d_store; a.partials = f.d_partials; a.ids = e->d_ids;
+    a.hits = f.d_mirror_out; a.certified = reinterpret_cast<uint32_t*>(f.d_mirror_out + MIRROR_MAX_K); a.max_bits = b.d_maxnorm;
+    a.n_rows = count; a.row_base = (uint32_t)e->row_base; a.dims = dims; a.k = kpad; a.kpad = kpad;   // (kpad <= MIRROR_MAX_K < m)
+    a.q_norm = query_norm(query, dims);
+    a.use_measured = e->batch_eps_measured.load() != 0 ? 1 : 0;
+    HIP_TRY(launch_mirror_scan_masked(a, f.d_bitmap, query, e->metric, (int)e->grid_blocks.load(), st), WAX_HIP_ERR_INTERNAL, "masked mirror scan launch");
+    HIP_TRY(hipMemcpyAsync(f.h_mirror_out, f.d_mirror_out, out_bytes, hipMemcpyDeviceToHost, st), WAX_HIP_ERR_INTERNAL, "hits download");
+    HIP_TRY(hipStreamSynchronize(st), WAX_HIP_ERR_INTERNAL, sync_what);
+    const uint64_t n_chunks = ((uint64_t)count + chunk_rows - 1) / chunk_rows;
+    e->st_predicate_skipped += n_chunks - live_mirror_chunks;
+    e->st_rows += live_mirror_chunks * chunk_rows;
+    e->st_bytes += live_mirror_chunks * chunk_rows * (uint64_t)dims * 2ull + (uint64_t)MIRROR_KP * dims * 4ull;
+    if (*reinterpret_cast<const uint32_t*>(f.h_mirror_out + MIRROR_MAX_K) == 0u) {
+        // the f32 route on the same bitmap: it counts the query (once) and adds its own figures
+        e->st_predicate_mirror_fallbacks++;
+        return masked_scan_topk(e, f, query, dims, m, live_chunks, kpad, out_ids, out_scores, out_capacity, out_n, sync_what);
+    }
+    const int rc = hits_to_results(e->metric, f.h_mirror_out, (uint32_t)kpad, out_ids, out_scores, out_capacity, out_n);
+    if (rc != WAX_HIP_OK) return rc;
+    e->st_searches++;
+    e->st_predicate_masked++;
+    e->st_predicate_mirror_scans++;
+    return WAX_HIP_OK;
+}
+
 // ---- one query ----------------------------------------------------------------------
 
 // One query with an allow-list (has_allow), a non-empty predicate (pred != nullptr) or both, on a pooled filter workspace; the caller
 // holds the shared lock and has flushed pending rows. *out_n = results written (before any score cut). A list below
 // "filter_device_min" is staged from the host; otherwise the passing rows are a device-side bitmap ([allow-list probe,] attribute
-// mask), answered by gathering them or — predicate only — by the masked scan.
+// mask), answered by gathering them or — predicate only — by the masked scan, over the f32 store or, on a large store, over the bf16
+// mirror under the certificate ("predicate_mirror").
 static int search_rows_locked(wax_hip_engine* e, const float* query, uint32_t dims, int kpad, int has_allow, const uint64_t* allow_frame_ids,
                               uint64_t n_allow, const wax_hip_row_predicate* pred, uint64_t* out_ids, float* out_scores,
                               uint32_t out_capacity, uint32_t* out_n) {
@@ -176,9 +241,9 @@ static int search_rows_locked(wax_hip_engine* e, const float* query, uint32_t di
         if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_block_sum, &f.block_cap, n_blocks, sizeof(uint32_t), "Failed to allocate bitmap offsets");
         if (grc != WAX_HIP_OK) return grc;
         if (pred && !f.h_pred_counts)   // each word on its own test: a call that got one and was refused the other must not leave the next call a null pointer
-            HIP_TRY(hipHostMalloc(&f.h_pred_counts, 2 * sizeof(uint32_t), hipHostMallocDefault), WAX_HIP_ERR_ALLOC, "Failed to allocate predicate counters");
+            HIP_TRY(hipHostMalloc(&f.h_pred_counts, kPredCounts * sizeof(uint32_t), hipHostMallocDefault), WAX_HIP_ERR_ALLOC, "Failed to allocate predicate counters");
         if (pred && !f.d_pred_counts)
-            HIP_TRY(hipMalloc(&f.d_pred_counts, 2 * sizeof(uint32_t)), WAX_HIP_ERR_ALLOC, "Failed to allocate predicate counters");
+            HIP_TRY(hipMalloc(&f.d_pred_counts, kPredCounts * sizeof(uint32_t)), WAX_HIP_ERR_ALLOC, "Failed to allocate predicate counters");
         if (has_allow) {
             // without a predicate the probe's launch also sums the bitmap (block offsets, total): the list is the whole filter
             { const int hrc = ensure_idhash(e, st); if (hrc != WAX_HIP_OK) return hrc; }
@@ -200,20 +265,24 @@ static int search_rows_locked(wax_hip_engine* e, const float* query, uint32_t di
         } else {
             const bool scan_shape = scan_masked_dims(dims) && kpad <= FUSED_MAX_K && e->force_general.load() == 0;   // kpad = clamp(top_k): top_k > 192 gathers
             const uint32_t chunk_rows = scan_shape ? scan_masked_chunk_rows(dims) : 0u;
+            const uint32_t mirror_chunk_rows = scan_shape && predicate_uses_mirror(e, kpad) ? mirror_masked_chunk_rows(dims) : 0u;   // 0 = the mirror form is not taken
             AttrMaskArgs ma{};
-            ma.ts = d_ts; ma.flags = d_fl; ma.bitmap = f.d_bitmap; ma.counts = f.d_pred_counts; ma.n_rows = count; ma.chunk_rows = chunk_rows;
+            ma.ts = d_ts; ma.flags = d_fl; ma.bitmap = f.d_bitmap; ma.counts = f.d_pred_counts; ma.n_rows = count; ma.chunk_rows = chunk_rows; ma.chunk_rows2 = mirror_chunk_rows;
             ma.and_bitmap = has_allow ? 1 : 0;
             ma.has_after = pred->has_after != 0; ma.has_before = pred->has_before != 0; ma.after = pred->after; ma.before = pred->before; ma.deny_flags = pred->deny_flags;
-            HIP_TRY(hipMemsetAsync(f.d_pred_counts, 0, 2 * sizeof(uint32_t), st), WAX_HIP_ERR_INTERNAL, "predicate counters");
+            HIP_TRY(hipMemsetAsync(f.d_pred_counts, 0, kPredCounts * sizeof(uint32_t), st), WAX_HIP_ERR_INTERNAL, "predicate counters");
             HIP_TRY(launch_attr_mask(ma, st), WAX_HIP_ERR_INTERNAL, "attribute mask launch");
-            HIP_TRY(hipMemcpyAsync(f.h_pred_counts, f.d_pred_counts, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st), WAX_HIP_ERR_INTERNAL, "row count download");
+            HIP_TRY(hipMemcpyAsync(f.h_pred_counts, f.d_pred_counts, kPredCounts * sizeof(uint32_t), hipMemcpyDeviceToHost, st), WAX_HIP_ERR_INTERNAL, "row count download");
             HIP_TRY(hipStreamSynchronize(st), WAX_HIP_ERR_INTERNAL, "attribute mask failed on device");
             m = f.h_pred_counts[0];
             if (m == 0) return WAX_HIP_OK;
             // ---- route ----
             const int64_t route = e->predicate_route.load();
-            if (scan_shape && route != 1 && (route == 2 || m * 1000ull >= (uint64_t)e->predicate_scan_min_permille.load() * (uint64_t)count))
+            if (scan_shape && route != 1 && (route == 2 || m * 1000ull >= (uint64_t)e->predicate_scan_min_permille.load() * (uint64_t)count)) {
+                if (mirror_chunk_rows != 0u && m > (uint64_t)MIRROR_KP)   // with MIRROR_KP or fewer passing rows the finish cannot certify
+                    return masked_mirror_topk(e, f, query, dims, m, f.h_pred_counts[1], f.h_pred_counts[2], kpad, out_ids, out_scores, out_capacity, out_n, sync_what);
                 return masked_scan_topk(e, f, query, dims, m, f.h_pred_counts[1], kpad, out_ids, out_scores, out_capacity, out_n, sync_what);
+            }
             { const int lrc = reserve_row_lists(f, m); if (lrc != WAX_HIP_OK) return lrc; }
             HIP_TRY(launch_bitmap_offsets(f.d_bitmap, count, f.d_block_sum, f.d_total, st), WAX_HIP_ERR_INTERNAL, "bitmap offsets launch");
             HIP_TRY(launch_allow_emit(f.d_bitmap, count, f.d_block_sum, e->d_ids, f.d_rows, f.d_ids, st), WAX_HIP_ERR_INTERNAL, "row compaction launch");
@@ -468,7 +537,7 @@ static int batch_filtered_locked(wax_hip_engine* e, const float* queries, uint32
         for (AttrRowsRecord& r : records) { r.ts = d_ts; r.flags = d_fl; }
         for (RowListPred& sp : sort_preds) { sp.ts = d_ts; sp.flags = d_fl; }
         if (long_max > 0 && !f.d_pred_counts)
-            HIP_TRY(hipMalloc(&f.d_pred_counts, 2 * sizeof(uint32_t)), WAX_HIP_ERR_ALLOC, "Failed to allocate predicate counters");
+            HIP_TRY(hipMalloc(&f.d_pred_counts, kPredCounts * sizeof(uint32_t)), WAX_HIP_ERR_ALLOC, "Failed to allocate predicate counters");
     }
     // one blob: descs | descs with a predicate | their predicates | attribute records | their work table | groups | item_group | slot_q |
     // slot_norm | spans (16-byte aligned sections)
@@ -535,7 +604,7 @@ static int batch_filtered_locked(wax_hip_engine* e, const float* queries, uint32
             ma.ts = d_ts; ma.flags = d_fl;
             ma.bitmap = f.d_bitmap; ma.counts = f.d_pred_counts; ma.n_rows = (uint32_t)count; ma.chunk_rows = 0; ma.and_bitmap = 1;
             pred_fields(*L.pred, ma);
-            HIP_TRY(hipMemsetAsync(f.d_pred_counts, 0, 2 * sizeof(uint32_t), st), WAX_HIP_ERR_INTERNAL, "predicate counters");
+            HIP_TRY(hipMemsetAsync(f.d_pred_counts, 0, kPredCounts * sizeof(uint32_t), st), WAX_HIP_ERR_INTERNAL, "predicate counters");
             HIP_TRY(launch_attr_mask(ma, st), WAX_HIP_ERR_INTERNAL, "attribute mask launch");
             HIP_TRY(launch_bitmap_offsets(f.d_bitmap, (uint32_t)count, f.d_block_sum, f.d_lcnt + li, st), WAX_HIP_ERR_INTERNAL, "bitmap offsets launch");
         }

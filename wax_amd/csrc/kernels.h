@@ -134,6 +134,11 @@ bool mirror_scan_supported(uint32_t dims, int metric);
 int mirror_grid_for(uint32_t n_rows, uint32_t dims, int grid_cap);
 // Two launches on `st`: mirror_scan_kernel (the event pair of launch_timing(), if armed, binds to it) and mirror_finish_kernel.
 hipError_t launch_mirror_scan(const MirrorScanArgs& args, const float* query, int metric, int grid_cap, hipStream_t st);
+// The same two launches under a row bitmap (predicate.hip's: every word written, bits of rows >= n_rows clear): mirror_scan_masked_kernel
+// loads only the chunks (mirror_masked_chunk_rows(dims) aligned rows: 16 at 384-d, 8 at 768-d) that hold a passing row and offers only
+// passing rows; the finish is unchanged. The caller sends only bitmaps with more than MIRROR_KP passing rows: fewer cannot certify.
+uint32_t mirror_masked_chunk_rows(uint32_t dims);   // 0 = no mirror scan at this dimension
+hipError_t launch_mirror_scan_masked(const MirrorScanArgs& args, const uint32_t* bitmap, const float* query, int metric, int grid_cap, hipStream_t st);
 
 // Several single queries in ONE pass over the mirror ("mirror_share"): every loaded dword is widened once and multiplied
 // into one accumulator set per query, with the single-query kernel's operations in its order, so a query's candidates and its
@@ -596,9 +601,10 @@ struct AttrMaskArgs {
     const int64_t* ts;          // [n_rows] timestamps; null = every row 0
     const uint32_t* flags;      // [n_rows] flag words; null = every row 0
     uint32_t* bitmap;           // [ceil(n_rows / 32)] one bit per row; every word is written
-    uint32_t* counts;           // [2], zero before the launch: passing rows, scan chunks with at least one passing row
+    uint32_t* counts;           // [3], zero before the launch: passing rows, chunks of chunk_rows / of chunk_rows2 rows with at least one passing row
     uint32_t n_rows;
     uint32_t chunk_rows;        // rows per chunk of the masked scan (a power of two <= 64; 0 = do not count chunks)
+    uint32_t chunk_rows2;       // a second chunk size, counted into counts[2] (the mirror form's; 0 = not counted, the word stays untouched)
     int32_t and_bitmap;         // != 0: the bitmap already holds the allow-list's rows (filter.hip's probe): AND into it
     int32_t has_after, has_before;
     int64_t after, before;

@@ -14,6 +14,8 @@
 //                             a_KP - eps > d_k     (a_KP: the KP-th approximate distance, d_k: the exact k-th)
 //                         Every row outside the candidates has an approximate distance >= a_KP, hence an exact one >= a_KP - eps > d_k:
 //                         the answer is the f32 scan's. Otherwise the host re-runs the query on the f32 scan (api_search.inc).
+//   mirror_scan_masked_kernel  the first launch under a row bitmap (a predicate search, filter_host.inc): chunks without a passing row
+//                         are not loaded, only passing rows are offered; the same finish, the same certificate over the passing rows.
 #include <cstddef>
 #include <cstring>
 
@@ -114,6 +116,101 @@ __global__ __launch_bounds__(SCAN_THREADS) void mirror_scan_kernel(MirrorScanArg
             d = (d != d) ? __builtin_inff() : d;
             const uint32_t r = rbase + u * RPW;
             tk.push(make_key(d + 0.0f, a.row_base + r), owner && (r < n));
+        }
+    }
+
+    int* counts = reinterpret_cast<int*>(lds + SCAN_WAVES * CAP);
+    int64_t* fin = lds + SCAN_WAVES * CAP + SCAN_WAVES;
+    tk.finalize();
+    if (lane == 0) counts[wave] = tk.cnt;
+    __syncthreads();
+    block_rank_merge<SCAN_WAVES>(lds, CAP, counts, MIRROR_KP, fin);
+    __syncthreads();
+    int64_t* mine = a.partials + (size_t)blockIdx.x * MIRROR_KP;
+    for (int t = (int)threadIdx.x; t < MIRROR_KP; t += SCAN_THREADS) mine[t] = fin[t];
+}
+
+// ---- under a row bitmap (wax_hip_search_predicate) ---------------------------------------------------------------------
+// mirror_scan_kernel with the row bitmap of predicate.hip, in scan_masked_kernel's form: the wave's chunk of RPC rows is the unit of
+// the skip test; its bits are requested one iteration ahead and made wave-uniform; a chunk without a passing row is not loaded; a row
+// is offered only when its bit is set. Everything between the loads and the key is the unmasked kernel's text, so a passing row's
+// approximate key is the one it gets without a mask, and the workgroup's list holds the MIRROR_KP best approximate keys among ITS
+// passing rows. The finish is mirror_finish_kernel as it is: eps is bounded by maxima over the whole store, the passing rows among them.
+template <int DIMS, int METRIC>
+__global__ __launch_bounds__(SCAN_THREADS) void mirror_scan_masked_kernel(MirrorScanArgsQ<DIMS> aq, const uint32_t* __restrict__ bitmap) {
+    constexpr int D8 = MirrorShape<DIMS>::D8;
+    constexpr int GROUP = MirrorShape<DIMS>::GROUP;
+    constexpr int LOADS = D8 / GROUP;
+    constexpr int RPW = WAVE / GROUP;
+    constexpr int RPC = RPW * MIRROR_UNROLL;
+    constexpr int CAP = 128;
+    static_assert(LOADS == 3 && D8 % GROUP == 0, "three dwordx4 per lane and row");
+    static_assert((RPC & (RPC - 1)) == 0 && RPC <= 32, "a chunk's bits must sit inside one bitmap word");
+    const MirrorScanArgs& a = aq.a;
+    __shared__ int64_t lds[SCAN_WAVES * CAP + SCAN_WAVES + MIRROR_KP];
+
+    const int lane = lane_id();
+    const int wave = (int)(threadIdx.x >> 6);
+    const int sub = lane / GROUP;
+    const int gl = lane % GROUP;
+    const bool owner = (gl == GROUP - 1);
+    const uint32_t n = a.n_rows;
+
+    // the query slice of this lane, straight from the kernel arguments (aq is the first argument: its offsets are the segment's)
+    const char* ka = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
+    const f32x4* q4 = reinterpret_cast<const f32x4*>(ka + offsetof(MirrorScanArgsQ<DIMS>, q));
+    f32x2 q[LOADS][4];
+#pragma unroll
+    for (int j = 0; j < LOADS; ++j) {
+        const f32x4 lo = q4[2 * (gl + j * GROUP)], hi = q4[2 * (gl + j * GROUP) + 1];
+        q[j][0] = lo.xy; q[j][1] = lo.zw; q[j][2] = hi.xy; q[j][3] = hi.zw;
+    }
+    const float inv_qn = a.q_norm > COS_NORM_FLOOR ? 1.0f / a.q_norm : 0.0f;
+
+    const u32x4* __restrict__ mirror4 = reinterpret_cast<const u32x4*>(a.mirror);
+    WaveTopK<CAP> tk;
+    tk.init(lds + wave * CAP, MIRROR_KP);
+
+    const uint32_t nchunks = (n + RPC - 1) / RPC;
+    const uint32_t gwave = blockIdx.x * SCAN_WAVES + wave;
+    const uint32_t nwaves = gridDim.x * SCAN_WAVES;
+
+    // (one iteration ahead: predicate.hip, scan_masked_kernel)
+    uint32_t word = gwave < nchunks ? bitmap[(gwave * RPC) >> 5] : 0u;
+    for (uint32_t chunk = gwave; chunk < nchunks; chunk += nwaves) {
+        const uint32_t r0 = chunk * RPC;                     // < n: word r0 >> 5 exists; bits of rows >= n are clear
+        const uint32_t bits = (uint32_t)__builtin_amdgcn_readfirstlane((int)((word >> (r0 & 31u)) & (uint32_t)((1ull << RPC) - 1ull)));
+        const uint32_t next = chunk + nwaves;
+        if (next < nchunks) word = bitmap[(next * RPC) >> 5];
+        if (bits == 0u) continue;                            // wave-uniform: no row of the chunk may be offered, so none is loaded
+        const uint32_t rbase = r0 + sub;
+        tk.make_room(RPC);
+        u32x4 v[MIRROR_UNROLL][LOADS];
+#pragma unroll
+        for (int u = 0; u < MIRROR_UNROLL; ++u) {
+            const uint32_t r = rbase + u * RPW;
+            const uint32_t rc = r < n ? r : n - 1;  // clamp: tail lanes re-read the last row, result discarded
+            const u32x4* p = mirror4 + (size_t)rc * D8 + gl;
+#pragma unroll
+            for (int j = 0; j < LOADS; ++j) v[u][j] = __builtin_nontemporal_load(p + j * GROUP);
+        }
+#pragma unroll
+        for (int u = 0; u < MIRROR_UNROLL; ++u) {
+            f32x2 acc[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+#pragma unroll
+            for (int j = 0; j < LOADS; ++j) {
+                acc[0] = __builtin_elementwise_fma(q[j][0], widen(v[u][j].x), acc[0]);
+                acc[1] = __builtin_elementwise_fma(q[j][1], widen(v[u][j].y), acc[1]);
+                acc[2] = __builtin_elementwise_fma(q[j][2], widen(v[u][j].z), acc[2]);
+                acc[3] = __builtin_elementwise_fma(q[j][3], widen(v[u][j].w), acc[3]);
+            }
+            const f32x2 s2 = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+            const float s = group_sum<GROUP>(s2.x + s2.y);
+            float d = METRIC == M_COS ? 1.0f - s * inv_qn : 1.0f - s;
+            d = (d != d) ? __builtin_inff() : d;
+            const uint32_t r = rbase + u * RPW;
+            const bool bit = ((bits >> (uint32_t)(sub + u * RPW)) & 1u) != 0u;
+            tk.push(make_key(d + 0.0f, a.row_base + r), owner && (r < n) && bit);
         }
     }
 
@@ -272,6 +369,18 @@ hipError_t launch_mirror_dims(const MirrorScanArgs& args, const float* query, in
     return hipGetLastError();
 }
 template <int DIMS, int METRIC>
+hipError_t launch_mirror_masked_dims(const MirrorScanArgs& args, const uint32_t* bitmap, const float* query, int grid, hipStream_t st) {
+    MirrorScanArgsQ<DIMS> aq;
+    aq.a = args;
+    aq.a.lists = grid;
+    std::memcpy(aq.q, query, sizeof(aq.q));
+    launch_kernel((mirror_scan_masked_kernel<DIMS, METRIC>), dim3(grid), dim3(SCAN_THREADS), 0, st, aq, bitmap);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL((mirror_finish_kernel<DIMS, METRIC>), dim3(1), dim3(SCAN_THREADS), 0, st, aq);
+    return hipGetLastError();
+}
+template <int DIMS, int METRIC>
 hipError_t launch_group_dims(const MirrorGroupArgs& args, int nq, int grid, hipStream_t st) {
     MirrorGroupArgs g = args;
     g.a.lists = grid;
@@ -318,6 +427,21 @@ hipError_t launch_mirror_scan(const MirrorScanArgs& args, const float* query, in
     return with_scan_shape(MirrorDims{}, args.dims, [&](auto s) {
         return with_metric_in<M_COS, M_DOT>(metric, [&](auto m) {
             return launch_mirror_dims<decltype(s)::DIMS, decltype(m)::value>(args, query, grid, st);
+        }, hipErrorInvalidValue);
+    }, hipErrorInvalidValue);
+}
+
+uint32_t mirror_masked_chunk_rows(uint32_t dims) {
+    return in_dim_list(MirrorDims{}, dims) ? (uint32_t)(WAVE / (dims / 24)) * MIRROR_UNROLL : 0u;   // RPC of mirror_scan_masked_kernel
+}
+
+hipError_t launch_mirror_scan_masked(const MirrorScanArgs& args, const uint32_t* bitmap, const float* query, int metric, int grid_cap, hipStream_t st) {
+    if (!mirror_scan_supported(args.dims, metric) || args.k < 1 || args.k > MIRROR_MAX_K || args.kpad < args.k || args.n_rows == 0 || bitmap == nullptr)
+        return hipErrorInvalidValue;
+    const int grid = mirror_grid_for(args.n_rows, args.dims, grid_cap);
+    return with_scan_shape(MirrorDims{}, args.dims, [&](auto s) {
+        return with_metric_in<M_COS, M_DOT>(metric, [&](auto m) {
+            return launch_mirror_masked_dims<decltype(s)::DIMS, decltype(m)::value>(args, bitmap, query, grid, st);
         }, hipErrorInvalidValue);
     }, hipErrorInvalidValue);
 }

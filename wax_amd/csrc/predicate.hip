@@ -3,7 +3,8 @@
 //
 //   attr_mask_kernel     one lane per row: reads the timestamp and flag columns coalesced, evaluates the predicate, ballots, and
 //                        writes the row bitmap filter.hip's allow-list path already has (with an allow-list: ANDs into the bitmap
-//                        the probe kernel marked). Counts the passing rows and the scan chunks that hold one into two device words.
+//                        the probe kernel marked). Counts the passing rows and the scan chunks that hold one into two device words,
+//                        and the live chunks of a second size (the mirror form's) into a third.
 //   attr_mask_pooled_kernel  the same reads, test, ballot and word writes for MANY (store, predicate) records in one launch
 //                        (wax_hip_search_many_predicate): one 256-row tile of one record per workgroup, no counters, no atomics.
 //   attr_rows_count / scan / emit_kernel   the columns straight to compact ascending row lists with device-side counts, for MANY
@@ -20,7 +21,7 @@
 
 namespace wax {
 
-// The two counters take ONE pair of device atomics per workgroup: a workgroup walks 256-row tiles grid-strided, keeps its counts in
+// The counters take ONE set of device atomics per workgroup: a workgroup walks 256-row tiles grid-strided, keeps its counts in
 // registers, and the grid is capped at kMaskGrid. The first build had every wave add for itself (15 600 waves at 1M rows, all on
 // the same two words). What is measured of that build (profiles/r13/c_routes_first_build.json): its gather route took 0.32 ms
 // at 1/64 passing where the allow-list form — the same launches from the bitmap on — took 0.11. That the same-address atomics are
@@ -30,13 +31,15 @@ constexpr uint32_t kMaskGrid = 1024;
 // (the per-row test itself, attr_row_passes, is in kernels.h: filter.hip's list sort applies it too)
 
 __global__ __launch_bounds__(256) void attr_mask_kernel(AttrMaskArgs a) {
-    __shared__ uint32_t wave_counts[4][2];
+    __shared__ uint32_t wave_counts[4][3];
     const uint32_t n_words = (a.n_rows + 31u) / 32u;
     const uint32_t n_tiles = (a.n_rows + 255u) / 256u;
     const int lane = lane_id();
     const int wave = (int)(threadIdx.x >> 6);
-    const unsigned long long firsts = a.chunk_rows >= 64u ? 1ull : (a.chunk_rows != 0u ? ~0ull / ((1ull << a.chunk_rows) - 1ull) : 0ull);
-    uint32_t n_pass = 0, n_chunks = 0;                          // wave-uniform
+    // bit i * c of firsts(c): the first row of every aligned run of c rows among the wave's 64 (0: chunks of that size are not counted)
+    auto firsts_of = [](uint32_t c) { return c >= 64u ? 1ull : (c != 0u ? ~0ull / ((1ull << c) - 1ull) : 0ull); };
+    const unsigned long long firsts = firsts_of(a.chunk_rows), firsts2 = firsts_of(a.chunk_rows2);
+    uint32_t n_pass = 0, n_chunks = 0, n_chunks2 = 0;           // wave-uniform
     for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint32_t row = tile * 256u + threadIdx.x;
         bool pass = row < a.n_rows;
@@ -55,10 +58,13 @@ __global__ __launch_bounds__(256) void attr_mask_kernel(AttrMaskArgs a) {
         unsigned long long x = b;
         for (uint32_t s = 1; s < a.chunk_rows; s <<= 1) x |= x >> s;
         n_chunks += (uint32_t)__popcll(x & firsts);
+        unsigned long long x2 = b;                              // the same for the second chunk size (the mirror form's: filter_host.inc)
+        for (uint32_t s = 1; s < a.chunk_rows2; s <<= 1) x2 |= x2 >> s;
+        n_chunks2 += (uint32_t)__popcll(x2 & firsts2);
     }
-    if (lane == 0) { wave_counts[wave][0] = n_pass; wave_counts[wave][1] = n_chunks; }
+    if (lane == 0) { wave_counts[wave][0] = n_pass; wave_counts[wave][1] = n_chunks; wave_counts[wave][2] = n_chunks2; }
     __syncthreads();
-    if (threadIdx.x < 2u) {
+    if (threadIdx.x < 3u) {
         const uint32_t v = wave_counts[0][threadIdx.x] + wave_counts[1][threadIdx.x] + wave_counts[2][threadIdx.x] + wave_counts[3][threadIdx.x];
         if (v != 0u) atomicAdd(&a.counts[threadIdx.x], v);
     }
@@ -67,6 +73,7 @@ __global__ __launch_bounds__(256) void attr_mask_kernel(AttrMaskArgs a) {
 hipError_t launch_attr_mask(const AttrMaskArgs& a, hipStream_t st) {
     if (a.n_rows == 0 || a.bitmap == nullptr || a.counts == nullptr) return hipErrorInvalidValue;
     if (a.chunk_rows > 64u || (a.chunk_rows & (a.chunk_rows - 1u)) != 0u) return hipErrorInvalidValue;
+    if (a.chunk_rows2 > 64u || (a.chunk_rows2 & (a.chunk_rows2 - 1u)) != 0u) return hipErrorInvalidValue;
     const uint32_t n_tiles = (a.n_rows + 255u) / 256u;
     hipLaunchKernelGGL(attr_mask_kernel, dim3(n_tiles < kMaskGrid ? n_tiles : kMaskGrid), dim3(256), 0, st, a);
     return hipGetLastError();

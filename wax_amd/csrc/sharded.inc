@@ -1525,6 +1525,7 @@ int64_t sh_get_tuning(wax_hip_engine* e, const std::string& k) {
         k == "mirror8_passes" || k == "mirror8_fallbacks" || k == "mirror8_unavailable" || k == "mirror8_conversions" || k == "mirror8_rows_converted" || k == "mirror8_breaker_trips" ||
         k == "remove_batches" || k == "remove_batch_rows" || k == "remove_batch_bytes_written" ||
         k == "predicate_searches" || k == "predicate_batch_queries" || k == "predicate_batch_classes" || k == "predicate_gather_searches" || k == "predicate_masked_scans" || k == "predicate_chunks_skipped" ||
+        k == "predicate_mirror_scans" || k == "predicate_mirror_fallbacks" || k == "predicate_mirror_unavailable" ||
         k == "attr_uploaded_rows" || k == "attr_device_rows") {   // counters: summed over the shards
         int64_t t = 0;
         for (auto* sub : s->subs) t += wax_hip_get_tuning(sub, k.c_str());

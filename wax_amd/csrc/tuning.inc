@@ -76,6 +76,7 @@ int wax_hip_set_tuning(wax_hip_engine* e, const char* key, int64_t value) {
     else if (k == "search_many") { if (value < 0 || value > 1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "search_many must be 0 or 1"); e->search_many = value; }
     else if (k == "search_many_max_rows") { if (value < 0 || value > 0xffffffffll) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "search_many_max_rows must be 0..4294967295"); e->search_many_max_rows = value; }
     else if (k == "predicate_route") { if (value < 0 || value > 2) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "predicate_route must be 0 (auto), 1 (gather) or 2 (masked scan)"); e->predicate_route = value; }
+    else if (k == "predicate_mirror") { if (value < 0 || value > 2) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "predicate_mirror must be 0 (never), 1 (auto) or 2 (every store)"); e->predicate_mirror = value; }
     else if (k == "predicate_scan_min_permille") { if (value < 0 || value > 1001) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "predicate_scan_min_permille must be 0..1001"); e->predicate_scan_min_permille = value; }
     else if (k == "compact_window_rows") { if (value < 0 || value > 0xffffffffll) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "compact_window_rows must be 0 (what the bounce buffer holds) .. 4294967295"); e->compact_window_rows = value; }
     else if (k == "batch_sample_div") { if (value < 4 || value > 4096) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_sample_div must be 4..4096"); e->batch_sample_div = value; }
@@ -190,6 +191,10 @@ int64_t wax_hip_get_tuning(wax_hip_engine* e, const char* key) {
     if (k == "predicate_gather_searches") return (int64_t)e->st_predicate_gather.load();     // ... answered by gathering the passing rows
     if (k == "predicate_masked_scans") return (int64_t)e->st_predicate_masked.load();        // ... answered by the masked f32 scan
     if (k == "predicate_chunks_skipped") return (int64_t)e->st_predicate_skipped.load();     // chunks those scans did not load
+    if (k == "predicate_mirror") return e->predicate_mirror.load();
+    if (k == "predicate_mirror_scans") return (int64_t)e->st_predicate_mirror_scans.load();              // masked scans answered from the bf16 mirror under the certificate
+    if (k == "predicate_mirror_fallbacks") return (int64_t)e->st_predicate_mirror_fallbacks.load();      // ... whose certificate failed: the masked f32 scan answered
+    if (k == "predicate_mirror_unavailable") return (int64_t)e->st_predicate_mirror_unavailable.load();  // ... sent to the f32 scan because the mirror could not be prepared
     if (k == "attr_uploaded_rows") return (int64_t)e->st_attr_uploaded.load();               // rows of the attribute columns uploaded so far
     if (k == "attr_device_rows") return (int64_t)e->attr_cap;                                // rows the device columns are allocated for (0 = none)
     if (k == "idhash_rows_inserted") return (int64_t)e->st_idhash_rows.load();
