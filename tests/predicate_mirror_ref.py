@@ -111,7 +111,7 @@ def mirror_of(metric, rows):
 
 
 def finish_eps(metric, dims, q_norm, max_norm, max_row_err, use_measured=True):
-    """eps of the certificate, written out from mirror_finish_body.inc (step 5): its doubles, its constants, its final round up to f32."""
+    """eps of the certificate, written out from Bf16Eps in mirror_finish.h (step 5 of mirror_finish): its doubles, its constants, its final round up to f32."""
     qn = 1.0 + 1e-6 if metric == COS else float(q_norm)
     vn = 1.0 + 1e-6 if metric == COS else float(max_norm)
     u = 0.0078125 * (1.0 + 1.0 / 512.0) + dims * 5.97e-8 + 1e-6

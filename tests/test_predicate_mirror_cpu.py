@@ -1,6 +1,6 @@
 """The float64 model of the masked scan's mirror form ("predicate_mirror"), on the CPU: bf16 rounding (round to nearest
 even), the mask, the 64 best approximate distances among the passing rows, the exact d_k and the finish kernel's eps written out
-from mirror_finish_body.inc (predicate_mirror_ref.py). Nothing here runs engine code.
+from mirror_finish.h (predicate_mirror_ref.py). Nothing here runs engine code.
 
 What it establishes for tests/test_predicate_mirror_gpu.py: on every (store, mask, query, k) where that test asserts zero fallbacks
 the margin a_64 - eps - d_k is above MARGIN_FLOOR, several times the f32 summation error of the kernels on both sides of the
@@ -28,7 +28,7 @@ def test_the_mirror_is_bf16_round_to_nearest_even_of_the_normalised_row():
 
 
 def test_eps_is_the_finish_kernels():
-    """The numbers of mirror_finish_body.inc, by hand: cosine at 768-d with a measured row error of 1.25e-3, and the unmeasured worst case."""
+    """The numbers of Bf16Eps (mirror_finish.h), by hand: cosine at 768-d with a measured row error of 1.25e-3, and the unmeasured worst case."""
     e = R.finish_eps(R.COS, 768, 1.0, 1.0, 1.25e-3)
     by_hand = (1.0 + 1e-6) * float(np.float32(1.25e-3)) * 1.001 + 3.0 * 768 * 5.97e-8 * (1.0 + 1e-6) ** 2 + 3e-6
     assert by_hand <= e <= by_hand * (1 + 2.0 ** -22)

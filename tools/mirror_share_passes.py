@@ -81,6 +81,7 @@ def main():
                 "passes_on_8_bits": eng.getTuning("mirror8_passes") - p8 if bits == 8 else 0, "groups": args.reps, "passes": passes,
                 "fallbacks": eng.getTuning("mirror_scan_fallbacks") - f0,
                 "ms_per_group_median": round(med * 1e3, 4), "ms_per_group_min": round(min(times) * 1e3, 4),
+                "ms_per_group_iqr": round(float(np.subtract(*np.percentile(times, [75, 25]))) * 1e3, 4),
                 "ms_per_query": round(med * 1e3 / n, 4), "mirror_TBps": round(args.rows * row_bytes / med / 1e12, 3)}
         print(json.dumps(line), flush=True)
         lines.append(line)

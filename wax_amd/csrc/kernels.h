@@ -108,6 +108,8 @@ inline bool scan_merges_in_kernel(int grid, int k, bool kway, uint32_t n_rows, u
 }
 
 // ---- mirror_scan.hip: one query against the bf16 mirror, exact f32 re-score of the best MIRROR_KP rows, certificate ----
+// Every scan kernel of mirror_scan.hip and mirror8_scan.hip is one function, mirror_pass (mirror_pass.h), over a row format; every
+// finish kernel is mirror_finish (mirror_finish.h).
 constexpr int MIRROR_KP = 64;       // approximate candidates kept per workgroup and in total (k')
 constexpr int MIRROR_MAX_K = 32;    // largest k the mirror path answers
 struct MirrorScanArgs {
@@ -131,19 +133,18 @@ struct alignas(16) MirrorScanArgsQ {
 };
 static_assert(sizeof(MirrorScanArgsQ<768>) <= 4096, "HIP kernel arguments are limited to 4 KB");
 bool mirror_scan_supported(uint32_t dims, int metric);
-int mirror_grid_for(uint32_t n_rows, uint32_t dims, int grid_cap);
 // Two launches on `st`: mirror_scan_kernel (the event pair of launch_timing(), if armed, binds to it) and mirror_finish_kernel.
 hipError_t launch_mirror_scan(const MirrorScanArgs& args, const float* query, int metric, int grid_cap, hipStream_t st);
 // The same two launches under a row bitmap (predicate.hip's: every word written, bits of rows >= n_rows clear): mirror_scan_masked_kernel
 // loads only the chunks (mirror_masked_chunk_rows(dims) aligned rows: 16 at 384-d, 8 at 768-d) that hold a passing row and offers only
 // passing rows; the finish is unchanged. The caller sends only bitmaps with more than MIRROR_KP passing rows: fewer cannot certify.
-uint32_t mirror_masked_chunk_rows(uint32_t dims);   // 0 = no mirror scan at this dimension
+uint32_t mirror_masked_chunk_rows(uint32_t dims);   // the pass's own rows per wave iteration; 0 = no mirror scan at this dimension
 hipError_t launch_mirror_scan_masked(const MirrorScanArgs& args, const uint32_t* bitmap, const float* query, int metric, int grid_cap, hipStream_t st);
 
 // Several single queries in ONE pass over the mirror ("mirror_share"): every loaded dword is widened once and multiplied
-// into one accumulator set per query, with the single-query kernel's operations in its order, so a query's candidates and its
-// certificate do not depend on what it rode with. The queries are read from device memory (they no longer fit the kernel arguments);
-// everything a query owns — partial lists, hits, certificate word, norm, k — is per member.
+// into one accumulator set per query by the function that serves the lone query (mirror_pass with NQ > 1), so a query's candidates and
+// its certificate do not depend on what it rode with. The queries are read from device memory (they no longer fit the kernel
+// arguments); everything a query owns — partial lists, hits, certificate word, norm, k — is per member.
 constexpr int MIRROR_MAX_NQ = 4;    // queries per shared pass (2, 3 and 4 have their own instantiations)
 struct MirrorMember {
     const float* query;             // [dims] f32 in HBM
@@ -179,7 +180,6 @@ struct Mirror8GroupArgs {
     const unsigned char* codes;
     const float* meta;
 };
-int mirror8_grid_for(uint32_t n_rows, uint32_t dims, int grid_cap);
 hipError_t launch_mirror8_scan(const MirrorScanArgs& args, const unsigned char* codes, const float* meta, const float* query, int metric,
                                int grid_cap, hipStream_t st);
 hipError_t launch_mirror8_group(const MirrorGroupArgs& args, const unsigned char* codes, const float* meta, int nq, int metric,

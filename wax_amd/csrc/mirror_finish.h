@@ -1,8 +1,41 @@
-// mirror_finish_body.inc — the body of mirror_scan.hip's finish kernels (included inside each of them; not compiled alone).
-// The finish of ONE query by one workgroup. Expects DIMS and METRIC (template parameters), `a` (the query's MirrorScanArgs) and
-// MIRROR_FINISH_QUERY (where the query's floats are: the kernel arguments for a lone query, device memory for a member of a group).
-// MIRROR_FINISH_EPS, if defined, replaces the bf16 mirror's eps in the certificate (step 5).
-// Text, not a function: the lone query's kernel then compiles to exactly the code it had before the group form existed.
+// mirror_finish.h — the finish of ONE query by one workgroup, behind a pass over either mirror (device code; mirror_scan.hip and
+// mirror8_scan.hip include it). The four finish kernels say where the query's MirrorScanArgs and floats are (the kernel arguments for
+// a lone query, MirrorMember for a member of a group) and which EPS the certificate subtracts:
+//   struct EPS { template <int DIMS, int METRIC> static __device__ float eps(const MirrorScanArgs& a); };
+#pragma once
+#include "kernels.h"
+#include "row_math.h"
+#include "topk.h"
+
+namespace wax {
+
+// The bf16 mirror's eps: batch_prep_kernel's bound (batch.hip) with the query-side rounding term gone — the query is not rounded. With
+// x_v the f32 row that was rounded (normalised for cosine) and v~ its bf16 rounding, |q.v~ - q.x_v| <= ||q|| ||v~ - x_v||, bounded by
+// ||q|| max_rows ||v~ - x_v|| (measured when the mirror was converted, + 0.1 % for its f32 accumulation); the f32 sums on
+// either side and the normalisations stay inside 3 D 2^-24 of ||q|| max||v||; the exact distance carries ~1e-6 of its own.
+// Without a measurement: the worst case of one rounded operand is below the batched path's two-operand constant, kept as is.
+// Cosine divides by ||q||, so both norms are 1 there.
+struct Bf16Eps {
+    template <int DIMS, int METRIC>
+    static __device__ __forceinline__ float eps(const MirrorScanArgs& a) {
+        const unsigned int* mb = a.max_bits;
+        const float max_norm = __uint_as_float(mb[0]);
+        const float max_row_err = a.use_measured ? __uint_as_float(mb[1]) : 0.f;
+        const double qn_d = METRIC == M_COS ? 1.0 + 1e-6 : (double)a.q_norm;
+        const double vn_d = METRIC == M_COS ? 1.0 + 1e-6 : (double)max_norm;
+        const double u = 0.0078125 * (1.0 + 1.0 / 512.0) + (double)DIMS * 5.97e-8 + 1e-6;
+        double dot_err = u * qn_d * vn_d * 1.001;
+        if (max_row_err > 0.f) {
+            const double measured = qn_d * (double)max_row_err * 1.001 + 3.0 * (double)DIMS * 5.97e-8 * qn_d * vn_d;
+            if (measured < dot_err) dot_err = measured;
+        }
+        const float eps = METRIC == M_COS ? (float)(dot_err + 3e-6) : (float)(dot_err + 1e-6 * (1.0 + qn_d * vn_d));
+        return nextafterf(eps, __builtin_inff());             // the double -> float conversion may have rounded down
+    }
+};
+
+template <int DIMS, int METRIC, class EPS>
+__device__ __forceinline__ void mirror_finish(const MirrorScanArgs& a, const f32x4* q4) {
     constexpr int D4 = ScanShape<DIMS>::D4;
     constexpr int GROUP = ScanShape<DIMS>::GROUP;
     constexpr int LOADS = ScanShape<DIMS>::LOADS;
@@ -20,7 +53,6 @@
     else kway_merge<2>(a.partials, a.lists, MIRROR_KP, approx, xch);
 
     // (2) exact f32 re-score of those rows: row_distance (row_math.h) at the f32 scan's shape for this dimension
-    const f32x4* q4 = MIRROR_FINISH_QUERY;
     const int sub = lane / GROUP, gl = lane % GROUP;
     f32x4 q[LOADS];
 #pragma unroll
@@ -59,7 +91,7 @@
     }
     __syncthreads();
 
-    // (4) the k best with frame ids; (5) the certificate
+    // (4) the k best with frame ids
     for (int i = t; i < a.kpad; i += SCAN_THREADS) {
         wax_hip_hit h;
         h.key = (i < a.k) ? sorted[i] : KEY_PAD;
@@ -70,34 +102,15 @@
         }
         a.hits[i] = h;
     }
+    // (5) the certificate: `approx` holds approximate distances (Bf16Eps) or lower bounds (a unit that supplies its own slack)
     if (t == 0) {
-        // eps: batch_prep_kernel's bound (batch.hip) with the query-side rounding term gone — the query is not rounded. With x_v the
-        // f32 row that was rounded (normalised for cosine) and v~ its bf16 rounding, |q.v~ - q.x_v| <= ||q|| ||v~ - x_v||, bounded by
-        // ||q|| max_rows ||v~ - x_v|| (measured when the mirror was converted, + 0.1 % for its f32 accumulation); the f32 sums on
-        // either side and the normalisations stay inside 3 D 2^-24 of ||q|| max||v||; the exact distance carries ~1e-6 of its own.
-        // Without a measurement: the worst case of one rounded operand is below the batched path's two-operand constant, kept as is.
-        // Cosine divides by ||q||, so both norms are 1 there.
-#ifdef MIRROR_FINISH_EPS
-        // (a unit whose approximate keys are lower bounds supplies its own slack: mirror8_scan.hip; `approx` then holds lb, not a)
-        const float eps = MIRROR_FINISH_EPS;
-#else
-        const unsigned int* mb = a.max_bits;
-        const float max_norm = __uint_as_float(mb[0]);
-        const float max_row_err = a.use_measured ? __uint_as_float(mb[1]) : 0.f;
-        const double qn_d = METRIC == M_COS ? 1.0 + 1e-6 : (double)a.q_norm;
-        const double vn_d = METRIC == M_COS ? 1.0 + 1e-6 : (double)max_norm;
-        const double u = 0.0078125 * (1.0 + 1.0 / 512.0) + (double)DIMS * 5.97e-8 + 1e-6;
-        double dot_err = u * qn_d * vn_d * 1.001;
-        if (max_row_err > 0.f) {
-            const double measured = qn_d * (double)max_row_err * 1.001 + 3.0 * (double)DIMS * 5.97e-8 * qn_d * vn_d;
-            if (measured < dot_err) dot_err = measured;
-        }
-        float eps = METRIC == M_COS ? (float)(dot_err + 3e-6) : (float)(dot_err + 1e-6 * (1.0 + qn_d * vn_d));
-        eps = nextafterf(eps, __builtin_inff());             // the double -> float conversion may have rounded down
-#endif
+        const float eps = EPS::template eps<DIMS, METRIC>(a);
         const int64_t a_kp = approx[MIRROR_KP - 1], kth = sorted[a.k - 1];
         const float da = key_distance(a_kp), dk = key_distance(kth);
         const bool ok = a_kp != KEY_PAD && kth != KEY_PAD && __builtin_isfinite(da) && __builtin_isfinite(dk) &&
                         __builtin_isfinite(eps) && a.q_norm == a.q_norm && (da - eps > dk);   // strict: ties stay uncertified
         *a.certified = ok ? 1u : 0u;
     }
+}
+
+}  // namespace wax
