@@ -624,6 +624,13 @@ int wax_hip_time_stream_read(wax_hip_engine* e, uint32_t iters, double* out_avg_
  * any mutation, until a query has rebuilt it), a range beyond the coded rows, a needed pointer that is NULL. */
 int wax_hip_mirror8_snapshot(wax_hip_engine* e, uint64_t first_row, uint64_t n_rows, uint8_t* out_codes, float* out_meta,
                              float* out_max_norm, uint64_t* out_rows_coded);
+/* Diagnostic read-out of the 8-bit pass's keys (tests hold the scan's arithmetic to an integer model through it; no product path
+ * calls it): out_keys[r] = the f32 key — a lower bound of the distance, -inf for a row that is always a candidate — that the lone
+ * 8-bit scan computes for `query` (dims floats) at coded row r, by the scan's own body. n_keys must equal the number of rows coded
+ * (wax_hip_mirror8_snapshot's *out_rows_coded). It never builds or refreshes the mirror, waits for a conversion still in flight,
+ * and changes no counter and no breaker state. WAX_HIP_ERR_INVALID_ARGUMENT: a sharded handle, a code mirror that is absent or not
+ * valid, another n_keys, a NULL pointer. */
+int wax_hip_mirror8_keys(wax_hip_engine* e, const float* query, float* out_keys, uint64_t n_keys);
 
 #ifdef __cplusplus
 }

@@ -108,8 +108,8 @@ inline bool scan_merges_in_kernel(int grid, int k, bool kway, uint32_t n_rows, u
 }
 
 // ---- mirror_scan.hip: one query against the bf16 mirror, exact f32 re-score of the best MIRROR_KP rows, certificate ----
-// Every scan kernel of mirror_scan.hip and mirror8_scan.hip is one function, mirror_pass (mirror_pass.h), over a row format; every
-// finish kernel is mirror_finish (mirror_finish.h).
+// Every scan kernel of mirror_scan.hip is one function, mirror_pass (mirror_pass.h); those of mirror8_scan.hip are code8_pass, its
+// sibling on the matrix pipe; every finish kernel is mirror_finish (mirror_finish.h).
 constexpr int MIRROR_KP = 64;       // approximate candidates kept per workgroup and in total (k')
 constexpr int MIRROR_MAX_K = 32;    // largest k the mirror path answers
 struct MirrorScanArgs {
@@ -184,6 +184,10 @@ hipError_t launch_mirror8_scan(const MirrorScanArgs& args, const unsigned char* 
                                int grid_cap, hipStream_t st);
 hipError_t launch_mirror8_group(const MirrorGroupArgs& args, const unsigned char* codes, const float* meta, int nq, int metric,
                                 int grid_cap, hipStream_t st);
+// The lone pass's key of every row (mirror8_keys_kernel: the scan's body, writing keys_out[n_rows] instead of keeping lists). A diagnostic:
+// args.partials, hits, certified, store, ids and max_bits are not used.
+hipError_t launch_mirror8_keys(const MirrorScanArgs& args, const unsigned char* codes, const float* meta, const float* query, int metric,
+                               int grid_cap, float* keys_out, hipStream_t st);
 // f32 rows -> codes + meta (mirror8_kernel: cosine rows normalised as mirror_kernel does); max_bits[0] = max ||v|| (atomic max)
 hipError_t launch_mirror8_build(const float* src, uint32_t n_rows, uint32_t dims, int normalize, unsigned char* codes, float* meta,
                                 unsigned int* max_bits, hipStream_t st);

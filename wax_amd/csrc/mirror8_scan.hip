@@ -2,20 +2,20 @@
 // per element").
 //
 // mirror_scan.hip's pass runs at the HBM read rate, so the next factor is again bytes per pass: one byte per element plus 8 bytes per
-// row instead of two bytes per element. The pass is mirror_scan.hip's — mirror_pass (mirror_pass.h) for the scan of one query
-// (mirror8_scan_kernel) or of 2-4 (mirror8_scan_group_kernel), mirror_finish (mirror_finish.h) for the exact re-score — over another
-// row format, Code8Rows, with another certificate:
+// row instead of two bytes per element. The pass has mirror_pass's frame (mirror_pass.h: persistent grid, one WaveTopK list per wave
+// and query, the workgroup rank merge, MIRROR_KP keys per workgroup and query, the clamp of tail rows) and mirror_finish
+// (mirror_finish.h) for the exact re-score, but the sums run on the matrix pipe — code8_pass below — with another certificate:
 //   the row       D bytes: code_i + 128, code_i = rint(x^_i / scale) in [-127, 127], scale = max|x^| / 127 of THAT row (x^: the f32 row,
-//                 normalised for cosine as mirror_kernel does). A lane still owns 24 elements of a row: three dwordx2 loads, GROUP =
-//                 D / 24 lanes, so 16 lanes cover a whole 128-byte line. v_cvt_f32_ubyteN turns a byte into a float in one full-rate
-//                 instruction; the bias leaves through the first accumulator chain, which starts at -128 * (the lane's sum of q).
+//                 normalised for cosine as mirror_kernel does). One v_xor per dword takes the bias off.
+//   the query     three int8 digits per element (QueryPlanes): q^_i = delta * m_i, m_i = 16384 a_i + 128 b_i + c_i, so that
+//                 sum_i m_i code_i is three exact integer dots — one v_mfma_i32_16x16x64_i8 column each.
 //   the key       meta[row] = {scale, err}, err >= ||scale * code - x^||_2 (measured per row by mirror8_kernel, rounded up). With
-//                 s = scale * sum_i q_i code_i:  |s - q.x^| <= ||q|| err, so
+//                 s = delta * scale * sum_i m_i code_i:  |s - q.x^| <= ||q|| err (up to the slack below), so
 //                     cosine  lb = 1 - s / ||q|| - err          dot  lb = 1 - s - ||q|| err
-//                 is a LOWER BOUND of the row's distance (up to the slack below). A NaN lb, and err = +inf, give -inf: such a row is
-//                 always a candidate and is re-scored exactly.
+//                 is a LOWER BOUND of the row's distance. A NaN lb, and err = +inf, give -inf: such a row is always a candidate and
+//                 is re-scored exactly.
 //   certificate   lb_KP - slack > d_k, strict. Every row outside the candidates has lb >= lb_KP, hence an exact distance
-//                 >= lb_KP - slack > d_k. slack (mirror8_slack) holds what err does not — see there.
+//                 >= lb_KP - slack > d_k. slack (Mirror8Slack) holds what err does not — see there.
 #include <cstring>
 
 #include "mirror_finish.h"
@@ -25,57 +25,230 @@ namespace wax {
 
 namespace {
 
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-// the wave's maximum in every lane (the build kernel only)
+// the wave's maximum in every lane (the build kernel and the query's quantiser)
 __device__ inline float wave_max64(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
 }
 
-// The code mirror as a row format of mirror_pass: three dwordx2 (24 codes) per lane and row, 8 row groups in flight (3 x 8 dwordx2
-// loads per lane = the bytes in flight of the bf16 pass), {scale, err} beside every row, the key a lower bound of the distance.
-struct Code8Rows {
-    using Vec = u32x2;
-    using Side = f32x2;                   // {scale, err}
-    static constexpr int UNROLL = 8;
-    static __device__ __forceinline__ Side side(const Side* meta, uint32_t r) {
-        return __builtin_nontemporal_load(meta + r);     // (every lane of the group: one address, one request)
-    }
-    // four biased codes in one dword -> floats (element 4i is the low byte); each conversion is one v_cvt_f32_ubyteN. Chains 0 and 1
-    // take the low and the high pair of dword x, chains 2 and 3 those of dword y.
-    static __device__ __forceinline__ f32x2 part(const Vec& v, int c) {
-        const unsigned int w = v[c >> 1];
-        f32x2 r;
-        r.x = (c & 1) ? (float)((w >> 16) & 0xffu) : (float)(w & 0xffu);
-        r.y = (c & 1) ? (float)(w >> 24) : (float)((w >> 8) & 0xffu);
-        return r;
-    }
-    // -128 * (the sum of a lane's 24 query elements): the bias leaves through the first chain. 128 * x is exact; the sum's own rounding
-    // is in the slack.
-    static __device__ __forceinline__ float start(const f32x2 (&q)[3][4]) {
-        f32x2 t = {0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < 3; ++j) t += (q[j][0] + q[j][1]) + (q[j][2] + q[j][3]);
-        return -128.0f * (t.x + t.y);
-    }
-    template <int METRIC>
-    static __device__ __forceinline__ float key(float sum, Side meta, float inv_qn, float q_norm) {
-        const float s = meta.x * sum;
-        const float lb = METRIC == M_COS ? (1.0f - s * inv_qn) - meta.y : (1.0f - s) - q_norm * meta.y;
-        return (lb != lb) ? -__builtin_inff() : lb;
-    }
+// A 16-row tile is one MFMA operand A: lane l holds 16 codes of row (l & 15) per k-step, bytes [64 s + 16 (l >> 4), + 16) of the row at
+// step s — the sum over k does not care which 16 elements a lane holds as long as operand B holds the same ones, and this choice
+// makes every load instruction read 64 contiguous bytes of each row, two of them a whole 128-byte line. The code loads are plain:
+// a line is read by two instructions and must stay in the vector L1 between them (non-temporal loads cost 0.04-0.08 ms of a 0.63 ms
+// pass). One tile per wave iteration: two, three and four tiles in flight, and a second register buffer loaded one iteration ahead,
+// measured no faster for four queries and 0.01 ms slower for one (profiles/r22).
+template <int DIMS>
+struct Code8Tiles {
+    static constexpr int TILE = 16;                    // rows per MFMA = rows per wave iteration; one make_room takes them
+    static constexpr int KSTEPS = DIMS / 64;           // MFMAs (and dwordx4 loads per lane) per tile: 96 B in flight per lane at 384-d
+    static constexpr int RPC = TILE;
+    static_assert(DIMS % 64 == 0, "whole k-steps");
 };
 
+// The query as three balanced base-128 digits per element, exact by construction:
+//   M = 63 * 16384 + 63 * 128 + 63, delta = max|q| / M, m_i = rint(q_i * (1 / delta)) clamped to [-M, M] (one division per wave, one
+//   product per element: both rounded, 2^-23 |m_i| <= 1/8 between them), m_i = 16384 a_i + 128 b_i + c_i with every digit in
+//   [-64, 63], so ||q^ - q|| <= delta sqrt(D) (1/2 + 1/8) <= 1.18e-5 ||q|| at 384-d whatever the elements; tests/mirror8_planes_ref.py
+//   restates it and tests/test_mirror8_planes_cpu.py finds 5.7e-6 at most, inside delta sqrt(D) / 2 every time.
+// A query with a non-finite element gets delta = NaN: every s is NaN, every key -inf, the 64th key is not finite and the finish
+// refuses the certificate. The all-zero query — and one whose delta would be subnormal, max|q| < 1.3e-32, where 1 / delta leaves
+// the f32 range — gets delta = 0 and digits 0 (s = 0, like the f32 sum to within 1e-30 ||v||).
+constexpr int PLANE_M = 63 * 16384 + 63 * 128 + 63;
+
+// delta of the query at q4: the whole wave reads it once
+template <int DIMS>
+__device__ __forceinline__ float query_delta(const f32x4* q4, int lane) {
+    float amax = 0.f;
+    bool bad = false;
+#pragma unroll
+    for (int c = 0; c < (DIMS / 4 + WAVE - 1) / WAVE; ++c) {
+        const int idx = lane + c * WAVE;
+        if (idx < DIMS / 4) {
+            const f32x4 v = q4[idx];
+            bad = bad || !__builtin_isfinite(v.x) || !__builtin_isfinite(v.y) || !__builtin_isfinite(v.z) || !__builtin_isfinite(v.w);
+            amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+        }
+    }
+    amax = wave_max64(amax);
+    const float delta = __fdiv_rn(amax, (float)PLANE_M);
+    return __ballot(bad) != 0ull ? __builtin_nanf("") : delta >= 1.17549435e-38f ? delta : 0.f;
+}
+
+// digit `plane` (0: a, 1: b, 2: c, else 0) of the 16 elements at q, as the bytes of one MFMA operand
+__device__ __forceinline__ i32x4 query_digits(const float* q, float inv_delta, int plane) {
+    const f32x4* q4 = reinterpret_cast<const f32x4*>(q);
+    i32x4 out;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const f32x4 v = q4[w];
+        const float x[4] = {v.x, v.y, v.z, v.w};
+        unsigned int word = 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float t = x[j] * inv_delta;
+            t = rintf(fminf(fmaxf(t, -(float)PLANE_M), (float)PLANE_M));
+            const int m = (int)t;
+            const int c = ((m + 64) & 127) - 64, m1 = (m - c) >> 7;
+            const int b = ((m1 + 64) & 127) - 64, a = (m1 - b) >> 7;
+            const int d = plane == 0 ? a : plane == 1 ? b : plane == 2 ? c : 0;
+            word |= ((unsigned int)d & 0xffu) << (8 * j);
+        }
+        out[w] = (int)word;
+    }
+    return out;
+}
+
+// v's value in lane Q of every quad
+template <int Q>
+__device__ __forceinline__ float quad_bcast(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), Q * 0x55, 0xF, 0xF, true));
+}
+
+// The key of one row for one query, from the integer sum S = sum_i m_i code_i (as a float: exact or rounded by code8_sum), delta,
+// the row's {scale, err} and the query's norm: the ONE float epilogue of every form of the pass.
+template <int METRIC>
+__device__ __forceinline__ float code8_key(float S, float delta, f32x2 meta, float inv_qn, float q_norm) {
+    const float s = (delta * meta.x) * S;
+    const float lb = METRIC == M_COS ? (1.0f - s * inv_qn) - meta.y : (1.0f - s) - q_norm * meta.y;
+    return (lb != lb) ? -__builtin_inff() : lb;
+}
+
+// S from the three plane sums (each below 2^24 in magnitude: the conversions are exact); two roundings
+__device__ __forceinline__ float code8_sum(float pa, float pb, float pc) {
+    return __builtin_fmaf(16384.0f, pa, __builtin_fmaf(128.0f, pb, pc));
+}
+
+// ONE pass of NQ queries over the code mirror on the matrix pipe: mirror_pass's sibling. Operand B's 16 columns are (query, plane):
+// column 4 i + t holds digit plane t of query i (t = 3: zeros), for the whole launch, KSTEPS x 4 VGPRs whatever NQ. The accumulator of
+// lane l holds rows 4 (l >> 4) + reg, reg = 0 .. 3, of column l & 15; the three planes of a query sit in one quad, so three quad
+// broadcasts and two fma give every lane of the quad S of its query for the four rows, and lane t of the quad keeps row
+// 4 (l >> 4) + t: the wave then holds the tile's 16 rows x 4 queries, one key per lane, and one push per query offers 16 rows.
+// The integer sums are exact and the float epilogue is one function of (S, delta, meta, norm), so a row's key for a query is the same
+// alone and in a pass of 2, 3 or 4. WRITE_KEYS (mirror8_keys_kernel, a diagnostic): every key is written to keys_out[row] and no
+// list is kept.
+template <int DIMS, int METRIC, int NQ, bool WRITE_KEYS, class QUERIES>
+__device__ __forceinline__ void code8_pass(const unsigned char* __restrict__ codes, const f32x2* __restrict__ sides, const MirrorScanArgs& a,
+                                           const QUERIES& qs, float* __restrict__ keys_out, int64_t* lds) {
+    using T = Code8Tiles<DIMS>;
+    constexpr int KSTEPS = T::KSTEPS, TILE = T::TILE, RPC = T::RPC;
+    static_assert(NQ >= 1 && NQ <= MIRROR_MAX_NQ && MIRROR_MAX_NQ * 4 <= 16, "four columns per query");
+
+    const int lane = lane_id();
+    const int wave = (int)(threadIdx.x >> 6);
+    const int col = lane & 15, kg = lane >> 4;        // operand A: row col of the tile, bytes 16 kg of every 64; operand B: column col
+    const int myq = col >> 2, plane = col & 3;        // the query and plane of this lane's column; after the combine: row 4 kg + plane
+    const bool live = myq < NQ;
+    const uint32_t n = a.n_rows;
+
+    // this lane's query: delta, the norm, and the digits of its plane at the lane's k-slices
+    float delta = 0.f, qn = 0.f;
+    const float* mine = reinterpret_cast<const float*>(qs.floats(0));
+    WaveTopK<MIRROR_CAP> tk[NQ];
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+        const float di = query_delta<DIMS>(qs.floats(i), lane);
+        if (myq == i) { delta = di; qn = qs.norm(i); mine = reinterpret_cast<const float*>(qs.floats(i)); }
+        if constexpr (!WRITE_KEYS) tk[i].init(lds + i * MIRROR_PASS_LDS + wave * MIRROR_CAP, MIRROR_KP);
+    }
+    // cosine: mirror rows are unit vectors (or zero), so sim = s / ||q||; the rule for a null query is the f32 scan's
+    const float inv_qn = qn > COS_NORM_FLOOR ? 1.0f / qn : 0.0f;
+    i32x4 b[KSTEPS];
+    const float inv_delta = delta > 0.f ? __fdiv_rn(1.0f, delta) : 0.f;      // (delta = 0 or NaN: no digits)
+#pragma unroll
+    for (int s = 0; s < KSTEPS; ++s) b[s] = query_digits(mine + s * 64 + kg * 16, inv_delta, live ? plane : 3);
+
+    const uint32_t nchunks = (n + RPC - 1) / RPC;
+    const uint32_t gwave = blockIdx.x * SCAN_WAVES + wave;
+    const uint32_t nwaves = gridDim.x * SCAN_WAVES;
+    const u32x4* __restrict__ rows = reinterpret_cast<const u32x4*>(codes);
+
+    for (uint32_t chunk = gwave; chunk < nchunks; chunk += nwaves) {
+        const uint32_t ra = chunk * TILE + col;                  // the row this lane loads codes of
+        const uint32_t r = chunk * TILE + 4 * kg + plane;        // the row this lane will hold the key of
+        const u32x4* p = rows + (size_t)(ra < n ? ra : n - 1) * (DIMS / 16) + kg;   // clamp: tail lanes re-read the last row
+        u32x4 v[KSTEPS];
+#pragma unroll
+        for (int s = 0; s < KSTEPS; ++s) v[s] = p[s * 4];        // every load of the iteration is issued before the first product
+        const f32x2 side = __builtin_nontemporal_load(sides + (r < n ? r : n - 1));
+        if constexpr (!WRITE_KEYS) {
+#pragma unroll
+            for (int i = 0; i < NQ; ++i) tk[i].make_room(RPC);
+        }
+        i32x4 acc = {0, 0, 0, 0};
+#pragma unroll
+        for (int s = 0; s < KSTEPS; ++s) {
+            const u32x4 x = v[s] ^ 0x80808080u;
+            acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, x), b[s], acc, 0, 0, 0);
+        }
+        float S = 0.f;
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const float pl = (float)acc[reg];
+            const float Sr = code8_sum(quad_bcast<0>(pl), quad_bcast<1>(pl), quad_bcast<2>(pl));
+            S = plane == reg ? Sr : S;
+        }
+        const float d = code8_key<METRIC>(S, delta, side, inv_qn, qn);
+        const bool offer = live && r < n;
+        if constexpr (WRITE_KEYS) {
+            if (offer && myq == 0) keys_out[r] = d + 0.0f;
+        } else {
+            const int64_t key = make_key(d + 0.0f, a.row_base + r);
+#pragma unroll
+            for (int i = 0; i < NQ; ++i) tk[i].push(key, offer && myq == i);
+        }
+    }
+    if constexpr (WRITE_KEYS) return;
+
+    // per query: the waves' lists -> the workgroup's MIRROR_KP best -> partials[blockIdx.x]
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+        tk[i].finalize();
+        int* counts = reinterpret_cast<int*>(lds + i * MIRROR_PASS_LDS + SCAN_WAVES * MIRROR_CAP);
+        if (lane == 0) counts[wave] = tk[i].cnt;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+        int64_t* base = lds + i * MIRROR_PASS_LDS;
+        block_rank_merge<SCAN_WAVES>(base, MIRROR_CAP, reinterpret_cast<int*>(base + SCAN_WAVES * MIRROR_CAP), MIRROR_KP,
+                                     base + SCAN_WAVES * MIRROR_CAP + SCAN_WAVES);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+        const int64_t* fin = lds + i * MIRROR_PASS_LDS + SCAN_WAVES * MIRROR_CAP + SCAN_WAVES;
+        int64_t* out = qs.partials(i) + (size_t)blockIdx.x * MIRROR_KP;
+        for (int t = (int)threadIdx.x; t < MIRROR_KP; t += SCAN_THREADS) out[t] = fin[t];
+    }
+}
+
+// launch(ScanShape<dims>, metric constant, grid) at the instantiation of (dims, metric), with the grid of code8_pass at that dimension
+template <typename F>
+inline hipError_t with_code8_pass(uint32_t n_rows, uint32_t dims, int metric, int grid_cap, F&& launch) {
+    return with_scan_shape(MirrorDims{}, dims, [&](auto s) {
+        return with_metric_in<M_COS, M_DOT>(metric, [&](auto m) {
+            return launch(s, m, mirror_pass_grid(n_rows, Code8Tiles<decltype(s)::DIMS>::RPC, grid_cap));
+        }, hipErrorInvalidValue);
+    }, hipErrorInvalidValue);
+}
+
 // What the per-row err does not hold, as a bound on (lb as computed) - (the row's exact distance as row_distance computes it):
-//  (a) the f32 accumulation of sum_i q_i (code_i + 128) - 128 Q, Q the lane's rounded sum of its q_i. Every path from a term to the
-//      group's total crosses at most 11 roundings (3 fma, 2 + 1 adds of the lane's tree, <= 5 DPP adds), Q's own sum 23; the terms'
-//      magnitudes sum to at most (255 + 128) ||q||_1, so with u = 2^-24
-//          |computed - sum_i q_i code_i| <= (11 * 383 + 23 * 128) u ||q||_1 (1 + O(u)) < 8192 u sqrt(D) ||q||,
-//      times scale <= max||v|| / 127 (cosine: 1 / 127);
+//  (a) the query's digits and the combine. s is delta * scale * S~ with S~ the twice-rounded 16384 P_a + 128 P_b + P_c (the plane
+//      sums themselves are exact integers). With q^ = delta * m and x~ = scale * code:
+//        - the query's rounding: |q^.x~ - q.x~| <= ||q^ - q|| ||x~|| <= (delta sqrt(D) / 2) (||x^|| + err), and delta = max|q| / M
+//          <= ||q|| / 1 040 319, so at most 0.625 sqrt(D) / 1 040 319 ||q|| (||v|| + err) = 1.18e-5 ||q|| (||v|| + err) at 384-d
+//          (err <= ||v||: < 2.4e-5 ||q|| ||v|| even for a row coded as badly as can be);
+//        - the two fma roundings: each is relative 2^-24 of a partial sum, and by Cauchy-Schwarz delta scale |16384 P_a| (and the
+//          smaller partial sums) <= ~||q^|| ||x~|| <= 1.01 ||q|| ||v||: < 4 u ||q|| ||v||.
+//      Together < (1.25 sqrt(D) / 1 040 319 + 4 u) ||q|| ||v|| = 2.4e-5 (384-d), 3.4e-5 (768-d), below the
+//      8192 u sqrt(D) / 127 ||q|| max||v|| = 7.5e-5 (384-d), 1.07e-4 (768-d) that this term has always been (it was sized for the f32
+//      accumulation of the biased sum): both scale with sqrt(D), the factor of three between them holds at every D. The value stays;
 //  (b) 3 D u ||q|| max||v|| for the f32 sums and normalisations on either side, as in the bf16 certificate;
-//  (c) the roundings of scale * acc, / ||q||, the two subtractions, and the exact distance's own ~1e-6: 3e-6 (cosine),
+//  (c) the roundings of delta * scale * S, / ||q||, the two subtractions, and the exact distance's own ~1e-6: 3e-6 (cosine),
 //      3e-6 (1 + ||q|| max||v||) (dot) — a row that matters has |lb| <= 2 (1 + ||q|| max||v||).
 // Cosine divides by ||q||, so both norms are 1 there.
 struct Mirror8Slack {
@@ -94,18 +267,22 @@ struct Mirror8Slack {
 }  // namespace
 
 template <int DIMS, int METRIC>
-__global__ __launch_bounds__(SCAN_THREADS) void mirror8_scan_kernel(Mirror8ScanArgsQ<DIMS> aq) {
+__global__ __launch_bounds__(SCAN_THREADS, 2) void mirror8_scan_kernel(Mirror8ScanArgsQ<DIMS> aq) {
     __shared__ int64_t lds[MIRROR_PASS_LDS];
-    mirror_pass<Code8Rows, DIMS, METRIC, 1, false>(reinterpret_cast<const u32x2*>(aq.codes), reinterpret_cast<const f32x2*>(aq.meta), aq.a,
-                                                    LoneQuery<Mirror8ScanArgsQ<DIMS>>{aq.a}, nullptr, lds);
+    code8_pass<DIMS, METRIC, 1, false>(aq.codes, reinterpret_cast<const f32x2*>(aq.meta), aq.a, LoneQuery<Mirror8ScanArgsQ<DIMS>>{aq.a}, nullptr, lds);
 }
 
 template <int DIMS, int METRIC, int NQ>
-__global__ __launch_bounds__(SCAN_THREADS) void mirror8_scan_group_kernel(Mirror8GroupArgs ga) {
+__global__ __launch_bounds__(SCAN_THREADS, 2) void mirror8_scan_group_kernel(Mirror8GroupArgs ga) {
     static_assert(NQ >= 2, "a lone query has mirror8_scan_kernel");
     __shared__ int64_t lds[NQ * MIRROR_PASS_LDS];
-    mirror_pass<Code8Rows, DIMS, METRIC, NQ, false>(reinterpret_cast<const u32x2*>(ga.codes), reinterpret_cast<const f32x2*>(ga.meta), ga.g.a,
-                                                     MemberQueries{ga.g.m}, nullptr, lds);
+    code8_pass<DIMS, METRIC, NQ, false>(ga.codes, reinterpret_cast<const f32x2*>(ga.meta), ga.g.a, MemberQueries{ga.g.m}, nullptr, lds);
+}
+
+// the lone pass's keys, every row's (wax_hip_mirror8_keys: a diagnostic)
+template <int DIMS, int METRIC>
+__global__ __launch_bounds__(SCAN_THREADS, 2) void mirror8_keys_kernel(Mirror8ScanArgsQ<DIMS> aq, float* keys_out) {
+    code8_pass<DIMS, METRIC, 1, true>(aq.codes, reinterpret_cast<const f32x2*>(aq.meta), aq.a, LoneQuery<Mirror8ScanArgsQ<DIMS>>{aq.a}, keys_out, nullptr);
 }
 
 template <int DIMS, int METRIC>
@@ -202,7 +379,7 @@ hipError_t launch_mirror8_scan(const MirrorScanArgs& args, const unsigned char* 
                                int grid_cap, hipStream_t st) {
     if (!mirror_launch_ok(args, metric, MIRROR8_MAX_K) || codes == nullptr || meta == nullptr || args.max_bits == nullptr)
         return hipErrorInvalidValue;
-    return with_mirror_pass<Code8Rows>(args.n_rows, args.dims, metric, grid_cap, [&](auto s, auto m, int grid) {
+    return with_code8_pass(args.n_rows, args.dims, metric, grid_cap, [&](auto s, auto m, int grid) {
         constexpr int D = decltype(s)::DIMS, M = decltype(m)::value;
         Mirror8ScanArgsQ<D> aq;
         aq.a = args;
@@ -215,11 +392,27 @@ hipError_t launch_mirror8_scan(const MirrorScanArgs& args, const unsigned char* 
     });
 }
 
+hipError_t launch_mirror8_keys(const MirrorScanArgs& args, const unsigned char* codes, const float* meta, const float* query, int metric,
+                               int grid_cap, float* keys_out, hipStream_t st) {
+    if (!mirror_launch_ok(args, metric, MIRROR8_MAX_K) || codes == nullptr || meta == nullptr || keys_out == nullptr) return hipErrorInvalidValue;
+    return with_code8_pass(args.n_rows, args.dims, metric, grid_cap, [&](auto s, auto m, int grid) {
+        constexpr int D = decltype(s)::DIMS, M = decltype(m)::value;
+        Mirror8ScanArgsQ<D> aq;
+        aq.a = args;
+        aq.a.lists = grid;
+        aq.codes = codes;
+        aq.meta = meta;
+        std::memcpy(aq.q, query, sizeof(aq.q));
+        hipLaunchKernelGGL((mirror8_keys_kernel<D, M>), dim3(grid), dim3(SCAN_THREADS), 0, st, aq, keys_out);
+        return hipGetLastError();
+    });
+}
+
 hipError_t launch_mirror8_group(const MirrorGroupArgs& args, const unsigned char* codes, const float* meta, int nq, int metric,
                                 int grid_cap, hipStream_t st) {
     if (!mirror_launch_ok(args.a, metric, MIRROR8_MAX_K, args.m, nq) || codes == nullptr || meta == nullptr || args.a.max_bits == nullptr)
         return hipErrorInvalidValue;
-    return with_mirror_pass<Code8Rows>(args.a.n_rows, args.a.dims, metric, grid_cap, [&](auto s, auto m, int grid) {
+    return with_code8_pass(args.a.n_rows, args.a.dims, metric, grid_cap, [&](auto s, auto m, int grid) {
         constexpr int D = decltype(s)::DIMS, M = decltype(m)::value;
         Mirror8GroupArgs ga;
         ga.g = args;

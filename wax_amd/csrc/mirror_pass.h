@@ -1,5 +1,6 @@
 // mirror_pass.h — ONE pass of NQ queries over a compressed mirror of the store, optionally under a row bitmap: the scan body of every
-// kernel of mirror_scan.hip and mirror8_scan.hip, and the host side that goes with it.
+// kernel of mirror_scan.hip, and the host side of every pass, mirror8_scan.hip's included. The 8-bit pass has a
+// body of its own on the matrix pipe (code8_pass, mirror8_scan.hip) inside the same frame: queries, grid rule, lists, partials.
 //
 // scan_kernel's structure: persistent grid, GROUP lanes per row, non-temporal loads, ROWS::UNROLL row groups in flight, the f32 query
 // slices in VGPRs, four f32x2 chains per query, DPP group sums, one WaveTopK list per wave and query, the workgroup rank merge,
@@ -7,7 +8,7 @@
 // of them run this one function, so a row's key for a query is the same whatever the query rode with and whether or not a bitmap was
 // there. The certificates of the finish (mirror_finish.h) rest on that.
 //
-// ROWS, the row format, holds what differs between the mirrors (static members only):
+// ROWS, the row format (Bf16Rows, mirror_scan.hip), holds what a mirror's rows are (static members only):
 //   Vec, UNROLL        the load vector (a lane owns 24 elements of a row: three Vec per row) and the row groups in flight
 //   Side, side(p, r)   what a row carries beside its elements, loaded with them (nothing for bf16)
 //   part(v, c)         the f32x2 that chain c multiplies, from one loaded Vec

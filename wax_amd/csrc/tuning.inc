@@ -354,3 +354,36 @@ int wax_hip_mirror8_snapshot(wax_hip_engine* e, uint64_t first_row, uint64_t n_r
     *out_rows_coded = rows;
     return WAX_HIP_OK;
 }
+
+// Diagnostic read-out of the keys of the 8-bit pass (tests/test_mirror8_mfma_gpu.py): the lower bound the lone scan computes for
+// `query` at every coded row, by the scan's own body. Like the snapshot: never a build or a refresh, no counter and no breaker state
+// touched, refused unless the code mirror is valid. No product path calls it.
+int wax_hip_mirror8_keys(wax_hip_engine* e, const float* query, float* out_keys, uint64_t n_keys) {
+    if (!e || !query || !out_keys) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    SHARDED_UNSUPPORTED(e, "wax_hip_mirror8_keys");
+    DeviceGuard g(e->device);
+    ReadGuard rg(e);
+    BatchMirror& b = e->batch;
+    std::unique_lock<std::mutex> mg(b.mu8);
+    if (!b.c8_valid.load(std::memory_order_acquire) || b.d_c8 == nullptr || b.d_c8_meta == nullptr || b.d_c8_max == nullptr || b.c8_cap < e->capacity)
+        return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror8_keys: the code mirror is absent or not valid");
+    const uint64_t rows = b.rows8.load();
+    if (rows == 0 || rows > e->count || n_keys != rows)
+        return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror8_keys: out_keys holds " + std::to_string(n_keys) + " keys, the code mirror " + std::to_string(rows) + " rows");
+    if (!mirror_scan_supported(e->dims, e->metric)) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror8_keys: no 8-bit pass at this dimension and metric");
+    if (b.ev8_pending) HIP_TRY(hipEventSynchronize(b.ev8_ready), WAX_HIP_ERR_INTERNAL, "code mirror ready wait");
+    MirrorScanArgs m{};
+    m.n_rows = (uint32_t)rows;
+    m.row_base = (uint32_t)e->row_base;
+    m.dims = e->dims;
+    m.k = 1;
+    m.kpad = 1;
+    m.q_norm = query_norm(query, e->dims);
+    float* d_keys = nullptr;
+    HIP_TRY(hipMalloc(&d_keys, (size_t)rows * sizeof(float)), WAX_HIP_ERR_INTERNAL, "mirror8_keys allocation");
+    hipError_t err = launch_mirror8_keys(m, b.d_c8, b.d_c8_meta, query, e->metric, (int)e->grid_blocks.load(), d_keys, nullptr);
+    if (err == hipSuccess) err = hipMemcpy(out_keys, d_keys, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost);
+    (void)hipFree(d_keys);
+    HIP_TRY(err, WAX_HIP_ERR_INTERNAL, "mirror8_keys");
+    return WAX_HIP_OK;
+}

@@ -570,6 +570,17 @@ class HIPVectorEngine:
                                                             _fp(meta), ctypes.byref(max_norm), ctypes.byref(rows)))
         return codes, meta[:, 0].copy(), meta[:, 1].copy(), float(max_norm.value), int(rows.value)
 
+    def mirror8Keys(self, query):  # noqa: N802
+        """The f32 key (a lower bound of the distance) that the lone 8-bit scan computes for `query` at every coded row, for tests
+        (wax_hip_mirror8_keys): f32 [rows_coded]. Raises unless the code mirror is valid; it is never built or refreshed here."""
+        q = _as_f32(query)
+        if q.shape != (self.dimensions,):
+            raise EncodingError("mirror8Keys: query must be [dims]")
+        rows = self.mirror8Snapshot(0, 0)[4]
+        keys = np.zeros(rows, dtype=np.float32)
+        raise_for_status(self._lib.wax_hip_mirror8_keys(self._h, _fp(q), _fp(keys), rows))
+        return keys
+
 
 def searchMany(engines, queries, topK: int):  # noqa: N802,N803
     """One query each against many stores of one device in one pass (wax_hip_search_many): pair i is (engines[i], queries[i]).
