@@ -106,10 +106,10 @@ def test_new_tuning_keys_are_documented_and_summed_over_shards():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     header = open(os.path.join(root, "include", "wax_hip.h")).read()
     tuning = open(os.path.join(root, "wax_amd", "csrc", "tuning.inc")).read()
-    sharded = open(os.path.join(root, "wax_amd", "csrc", "sharded.inc")).read()
+    import re
+    rows = dict(re.findall(r'^ *\{"([a-z_0-9]+)",(.*)$', tuning, re.M))   # the tuning table: {"name", how to set, how to get, what a sharded handle answers}
     for key in ("predicate_batch_rows", "predicate_batch_queries", "predicate_batch_classes"):
-        assert f'"{key}"' in header and f'k == "{key}"' in tuning
-    setter = tuning[tuning.index("int wax_hip_set_tuning("):tuning.index("wax_hip_get_tuning(")]
-    assert '"predicate_batch_rows"' in setter and '"predicate_batch_queries"' not in setter and '"predicate_batch_classes"' not in setter
-    getter = sharded[sharded.index("int64_t sh_get_tuning("):]
-    assert '"predicate_batch_queries"' in getter and '"predicate_batch_classes"' in getter
+        assert f'"{key}"' in header and key in rows
+    assert "not_set()" not in rows["predicate_batch_rows"]
+    for key in ("predicate_batch_queries", "predicate_batch_classes"):   # counters: not settable, summed over the shards
+        assert "not_set()" in rows[key] and "not_get()" not in rows[key] and re.search(r"SUM_SHARDS\},", rows[key])

@@ -86,18 +86,33 @@ def test_product_never_imports_oracle():
 
 def test_every_settable_tuning_key_is_documented_in_the_header():
     """The boundary is include/wax_hip.h: a key wax_hip_set_tuning accepts (single-device engine or sharded handle) that the header's
-    tunables block does not name is an undocumented switch behind the shipping ABI."""
+    tunables block does not name is an undocumented switch behind the shipping ABI. The keys of an engine are the rows of the table in
+    tuning.inc (one line each, `{"name", how to set, how to get, what a sharded handle answers}`), the handle's own are the branches of
+    sh_set_tuning; both sets, and the rows a handle sums, are the ones tests/golden/tuning_registry.json recorded."""
+    import json
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     src = open(os.path.join(root, "wax_amd", "csrc", "tuning.inc")).read()       # (engine.hip's translation unit, cut into files in round 6)
-    i = src.index("int wax_hip_set_tuning(")
-    keys = set(re.findall(r'k == "([a-z_0-9]+)"', src[i:src.index("wax_hip_get_tuning(", i)]))
+    rows = re.findall(r'^ *\{"([a-z_0-9]+)",(.*)$', src, re.M)
+    names = [name for name, _ in rows]
+    assert len(names) == len(set(names)), sorted(n for n in set(names) if names.count(n) > 1)
+    settable = {name for name, rest in rows if "not_set()" not in rest}
+    readable = {name for name, rest in rows if "not_get()" not in rest}
+    summed = {name for name, rest in rows if re.search(r"SUM_SHARDS\},", rest)}
+    assert all(re.search(r"(FIRST_SHARD|SUM_SHARDS)\},", rest) for _, rest in rows)
     sh = open(os.path.join(root, "wax_amd", "csrc", "sharded.inc")).read()
     i = sh.index("int sh_set_tuning(")
-    keys |= set(re.findall(r'k == "([a-z_0-9]+)"', sh[i:sh.index("sh_get_tuning(", i)]))
+    handle = set(re.findall(r'k == "([a-z_0-9]+)"', sh[i:sh.index("sh_get_tuning(", i)]))
+    keys = settable | handle
     documented = set(re.findall(r'"([a-z_0-9]+)"', open(os.path.join(root, "include", "wax_hip.h")).read()))
     assert len(keys) > 30 and {"time_kernels", "merge_overlap_mb", "batch_qfrag", "exchange", "shard_min_mb"} <= keys
     assert keys <= documented, sorted(keys - documented)
+    recorded = json.load(open(os.path.join(root, "tests", "golden", "tuning_registry.json")))["keys"]
+    assert sorted(settable) == recorded["settable"], sorted(settable ^ set(recorded["settable"]))
+    assert sorted(readable) == recorded["readable"], sorted(readable ^ set(recorded["readable"]))
+    assert sorted(handle) == recorded["sharded_settable"], sorted(handle ^ set(recorded["sharded_settable"]))
+    # what the handle summed when the record was made: the names of its own condition that are keys of an engine
+    assert summed == set(recorded["sharded_readable"]) & set(recorded["readable"]), sorted(summed ^ (set(recorded["sharded_readable"]) & set(recorded["readable"])))
 
 
 def test_create_argument_validation(hip_lib):
@@ -630,15 +645,15 @@ def test_bench_counter_passes_are_bounded():
 
 
 def test_every_tuning_key_is_documented_in_the_header():
-    """include/wax_hip.h is the only interface: every key wax_hip_set_tuning / wax_hip_get_tuning accept (tuning.inc, and the sharded
-    handle's own keys in sharded.inc) is named in its comment block — a key a maintainer cannot find does not exist."""
+    """include/wax_hip.h is the only interface: every key wax_hip_set_tuning / wax_hip_get_tuning accept (the table in tuning.inc, and the
+    sharded handle's own keys in sharded.inc) is named in its comment block — a key a maintainer cannot find does not exist."""
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = ""
-    for name in ("tuning.inc", "sharded.inc"):
-        with open(os.path.join(root, "wax_amd", "csrc", name)) as f:
-            src += f.read()
-    keys = sorted(set(re.findall(r'k == "([a-z0-9_]+)"', src)))
+    with open(os.path.join(root, "wax_amd", "csrc", "tuning.inc")) as f:
+        keys = set(re.findall(r'^ *\{"([a-z0-9_]+)",', f.read(), re.M))                  # the rows of the table: every key of an engine
+    with open(os.path.join(root, "wax_amd", "csrc", "sharded.inc")) as f:
+        keys |= set(re.findall(r'k == "([a-z0-9_]+)"', f.read()))                        # the handle's own, still branches
+    keys = sorted(keys)
     assert len(keys) >= 60
     with open(os.path.join(root, "include", "wax_hip.h")) as f:
         header = f.read()

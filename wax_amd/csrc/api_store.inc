@@ -45,8 +45,9 @@ int wax_hip_engine_create(uint8_t metric, uint32_t dims, int device_id, wax_hip_
     e->metric = metric;
     e->dims = dims;
     if (const char* v = std::getenv("WAX_HIP_BATCH_REGA")) {  // default of the "batch_rega" tunable (A/B runs of the whole test suite)
-        const long m = std::strtol(v, nullptr, 10);
-        if (m == 0 || m == 1 || m == 5) e->batch_rega = m;
+        const std::string keep = g_last_error;                // a value the key's row (tuning.inc) refuses is ignored silently
+        // (e->sh is still null here, also for a shard of a handle: the call cannot be handed over to the sharded path)
+        if (wax_hip_set_tuning(e, "batch_rega", std::strtol(v, nullptr, 10)) != WAX_HIP_OK) g_last_error = keep;
     }
     int rc = resize_store(e, WAX_HIP_INITIAL_RESERVE);  // :225-229
     if (rc == WAX_HIP_OK) {

@@ -1484,14 +1484,13 @@ int sh_set_tuning(wax_hip_engine* e, const std::string& k, int64_t value) {
         if (sh_count(s) == 0) s->block_rows = 0;                  // an empty handle chooses again at its first rows / reserve
         return WAX_HIP_OK;
     }
-    if (k == "batch_workspaces") {   // concurrent batched searches per handle (and per shard, below)
-        if (value < 1 || value > 16) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_workspaces must be 1..16");
-        std::unique_lock<std::mutex> g(s->bw_mu);
-        s->bw_max = (int)value;
-    }
-    for (auto* sub : s->subs) {   // everything else is a per-shard setting
+    for (auto* sub : s->subs) {   // everything else is a per-shard setting, checked by its row (tuning.inc)
         int rc = wax_hip_set_tuning(sub, k.c_str(), value);
         if (rc != WAX_HIP_OK) return rc;
+    }
+    if (k == "batch_workspaces") {   // concurrent batched searches per shard (above) and per handle
+        std::unique_lock<std::mutex> g(s->bw_mu);
+        s->bw_max = (int)value;
     }
     return WAX_HIP_OK;
 }
@@ -1519,14 +1518,8 @@ int64_t sh_get_tuning(wax_hip_engine* e, const std::string& k) {
     if (k == "rebalances") return (int64_t)s->rebalances.load();
     if (k == "parallel_collects") return (int64_t)s->parallel_collects.load();
     if (k == "parallel_submits") return (int64_t)s->parallel_submits.load();
-    if (k == "batch_queries" || k == "batch_fallbacks" || k == "batch_retries" || k == "onepass_queries" || k == "filter_device_searches" || k == "filter_batch_queries" || k == "filter_batch_fallbacks" || k == "query_args_scans" || k == "batch_inline_retries" ||
-        k == "batch_multi_passes" || k == "batch_multi_queries" || k == "short_selects" || k == "short_select_failures" ||
-        k == "mirror_scans" || k == "mirror_scan_fallbacks" || k == "mirror_scan_unavailable" || k == "mirror_passes" || k == "mirror_shared_passes" || k == "mirror_shared_queries" || k == "mirror_fill_holds" ||
-        k == "mirror8_passes" || k == "mirror8_fallbacks" || k == "mirror8_unavailable" || k == "mirror8_conversions" || k == "mirror8_rows_converted" || k == "mirror8_breaker_trips" ||
-        k == "remove_batches" || k == "remove_batch_rows" || k == "remove_batch_bytes_written" ||
-        k == "predicate_searches" || k == "predicate_batch_queries" || k == "predicate_batch_classes" || k == "predicate_gather_searches" || k == "predicate_masked_scans" || k == "predicate_chunks_skipped" ||
-        k == "predicate_mirror_scans" || k == "predicate_mirror_fallbacks" || k == "predicate_mirror_unavailable" ||
-        k == "attr_uploaded_rows" || k == "attr_device_rows") {   // counters: summed over the shards
+    const TuningRow* row = tuning_row(k);   // tuning.inc: a shard's keys and what the handle answers for each
+    if (row && row->sharded == SUM_SHARDS) {
         int64_t t = 0;
         for (auto* sub : s->subs) t += wax_hip_get_tuning(sub, k.c_str());
         return t;

@@ -1,5 +1,6 @@
 // tuning.inc — part of engine.hip's translation unit (included there; not compiled alone).
-// C ABI: stats, the tuning registry (set / get), the two timing microbenchmarks
+// C ABI: stats, the tuning table and the set / get calls that look a key up in it (the one place a key or a counter is added), the two
+// timing microbenchmarks, the code mirror's diagnostic read-outs
 
 // ---- observability / tuning -----------------------------------------------
 
@@ -27,85 +28,237 @@ int wax_hip_stats(wax_hip_engine* e, wax_hip_stats_t* out) {
     return WAX_HIP_OK;
 }
 
+}  // extern "C"
+
+// ---- the tuning table -------------------------------------------------------
+// One row per key of a single-device engine: how wax_hip_set_tuning checks and stores a value, what wax_hip_get_tuning loads, and
+// what a sharded handle answers (sh_get_tuning). A key or a counter is added HERE and documented in include/wax_hip.h; nothing
+// else names it. (The keys of the sharded handle itself, "exchange", "shard_min_mb", ..., are code in sharded.inc.)
+namespace {
+
+using Knob = std::atomic<int64_t> wax_hip_engine::*;
+using Counter = std::atomic<uint64_t> wax_hip_engine::*;
+struct TuningSet {
+    enum Kind : uint8_t { NONE, ANY, FLAG, RANGE, ONE_OF, MASK, FN } kind;
+    Knob knob;                              // ANY .. MASK: where the value goes (FLAG: as value != 0)
+    int64_t a, b, c;                        // RANGE and FN: [a, b]. ONE_OF: a, b or c. MASK: the bits of a
+    const char* refusal;                    // the message of a refused value
+    int (*fn)(wax_hip_engine*, int64_t);    // FN: a side effect or a target that is no Knob; called with a value in [a, b], returns the status
+};
+struct TuningGet {                          // at most one is set; none: the key reads -1
+    Knob knob;
+    Counter counter;
+    int64_t (*fn)(wax_hip_engine*);
+};
+enum TuningSharded : uint8_t { FIRST_SHARD, SUM_SHARDS };   // what a sharded handle answers: its first shard's value / the sum over its shards
+struct TuningRow { const char* name; TuningSet set; TuningGet get; TuningSharded sharded; };
+
+constexpr TuningSet not_set() { return {TuningSet::NONE, nullptr, 0, 0, 0, nullptr, nullptr}; }
+constexpr TuningSet set_any(Knob k) { return {TuningSet::ANY, k, 0, 0, 0, nullptr, nullptr}; }
+constexpr TuningSet set_flag(Knob k) { return {TuningSet::FLAG, k, 0, 0, 0, nullptr, nullptr}; }
+constexpr TuningSet set_range(Knob k, int64_t lo, int64_t hi, const char* refusal) { return {TuningSet::RANGE, k, lo, hi, 0, refusal, nullptr}; }
+constexpr TuningSet set_one_of(Knob k, int64_t a, int64_t b, int64_t c, const char* refusal) { return {TuningSet::ONE_OF, k, a, b, c, refusal, nullptr}; }
+constexpr TuningSet set_mask(Knob k, int64_t bits, const char* refusal) { return {TuningSet::MASK, k, bits, 0, 0, refusal, nullptr}; }
+constexpr TuningSet set_fn(int (*fn)(wax_hip_engine*, int64_t), int64_t lo, int64_t hi, const char* refusal) { return {TuningSet::FN, nullptr, lo, hi, 0, refusal, fn}; }
+constexpr TuningGet not_get() { return {nullptr, nullptr, nullptr}; }
+constexpr TuningGet get_knob(Knob k) { return {k, nullptr, nullptr}; }
+constexpr TuningGet get_counter(Counter c) { return {nullptr, c, nullptr}; }
+constexpr TuningGet get_fn(int64_t (*fn)(wax_hip_engine*)) { return {nullptr, nullptr, fn}; }
+#define GET_EXPR(expr) get_fn([](wax_hip_engine* e) -> int64_t { return (int64_t)(expr); })
+
+// the FN setters (the row's range, where it has one, is checked before they are called)
+int set_batch_workspaces(wax_hip_engine* e, int64_t v) { std::unique_lock<std::mutex> g(e->bctx_mu); e->bctx_max = (int)v; return WAX_HIP_OK; }
+int set_streams(wax_hip_engine* e, int64_t v) { std::unique_lock<std::mutex> g(e->slot_mu); e->n_streams = (int)v; return WAX_HIP_OK; }
+int set_slots(wax_hip_engine* e, int64_t v) { std::unique_lock<std::mutex> g(e->slot_mu); e->max_slots = (int)v; return WAX_HIP_OK; }
+int set_retry_hint(wax_hip_engine* e, int64_t v) { e->retry_hint = (int)v; return WAX_HIP_OK; }   // > 0: the next `v` clean batches still carry the device-side retry kernel (set by collect; tests force it)
+int set_merge_overlap_mb(wax_hip_engine* e, int64_t v) { e->merge_overlap_mb = v < 0 ? 0 : v; return WAX_HIP_OK; }
+int set_batch_first(wax_hip_engine* e, int64_t v) {
+    if (v < 128 || v > kBatchFirstSlab || v % 128) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_first must be a multiple of 128 in 128..2048");
+    e->batch_first = v;
+    return WAX_HIP_OK;
+}
+int set_reset_stats(wax_hip_engine* e, int64_t) {
+    e->st_searches = 0; e->st_rows = 0; e->st_bytes = 0;
+    {
+        DeviceGuard g(e->device);
+        for (int r = 0; r < kShardRing; ++r) harvest_ring_event(e, r);
+    }
+    std::unique_lock<std::mutex> sg(e->st_mu);
+    e->st_last_ms = 0; e->st_total_ms = 0; e->st_timed = 0;
+    e->st_gemm_ms = 0; e->st_gemm_timed = 0; e->st_gemm_rows = 0; e->st_gemm_queries = 0;
+    return WAX_HIP_OK;
+}
+// the getters that read device words (blocking)
+int64_t get_short_select_failures(wax_hip_engine* e) {   // short selections whose certificate failed (the long path answered): every slot's
+    int64_t t = 0;
+    DeviceGuard g(e->device);
+    (void)hipDeviceSynchronize();
+    std::unique_lock<std::mutex> tg(e->slot_mu);
+    for (Slot* sl : e->all_slots) {
+        uint32_t f[4] = {0u, 0u, 0u, 0u};
+        if (sl->sw_ready && sl->sw.flags && hipMemcpy(f, sl->sw.flags, sizeof(f), hipMemcpyDeviceToHost) == hipSuccess) t += f[1];
+        if (sl->d_partials && hipMemcpy(f, partials_ticket(sl->d_partials) + 8, sizeof(f), hipMemcpyDeviceToHost) == hipSuccess) t += f[1];   // the fused path's short merge
+    }
+    for (int r = 0; r < kShardRing; ++r) {
+        uint32_t f[4] = {0u, 0u, 0u, 0u};
+        if (e->ring_d_partials[r] && hipMemcpy(f, partials_ticket(e->ring_d_partials[r]) + 8, sizeof(f), hipMemcpyDeviceToHost) == hipSuccess) t += f[1];
+    }
+    return t;
+}
+double mirror_measured_bound(wax_hip_engine* e, int which) {   // the mirror's measured bounds: 0 = the largest norm, 1 = the largest row error
+    unsigned int bits[2] = {0u, 0u};
+    if (e->batch.d_maxnorm) {
+        DeviceGuard g(e->device);
+        (void)hipDeviceSynchronize();
+        (void)hipMemcpy(bits, e->batch.d_maxnorm, sizeof(bits), hipMemcpyDeviceToHost);
+    }
+    float f[2];
+    std::memcpy(f, bits, sizeof(f));
+    return (double)f[which];
+}
+
+constexpr TuningRow kTuning[] = {
+    {"grid_blocks", set_any(&wax_hip_engine::grid_blocks), get_knob(&wax_hip_engine::grid_blocks), FIRST_SHARD},
+    {"variant", set_any(&wax_hip_engine::variant), get_knob(&wax_hip_engine::variant), FIRST_SHARD},
+    {"variant_count", not_set(), GET_EXPR(scan_variant_count(e->dims)), FIRST_SHARD},
+    {"scan_grid", not_set(), GET_EXPR(scan_grid_for((uint32_t)e->count, e->dims, (int)e->variant.load(), (int)e->grid_blocks.load())), FIRST_SHARD},
+    {"fused_max_k", not_set(), GET_EXPR(FUSED_MAX_K), FIRST_SHARD},
+    {"time_kernels", set_any(&wax_hip_engine::time_kernels), get_knob(&wax_hip_engine::time_kernels), FIRST_SHARD},
+    {"force_general", set_any(&wax_hip_engine::force_general), get_knob(&wax_hip_engine::force_general), FIRST_SHARD},
+    {"select_grid", set_range(&wax_hip_engine::select_grid, 0, 2048, "select_grid must be 0 (auto) .. 2048"), get_knob(&wax_hip_engine::select_grid), FIRST_SHARD},
+    {"select_short", set_range(&wax_hip_engine::select_short, 0, 2, "select_short must be 0, 1 or 2"), get_knob(&wax_hip_engine::select_short), FIRST_SHARD},
+    {"short_selects", not_set(), get_counter(&wax_hip_engine::st_short_selects), SUM_SHARDS},
+    {"short_select_failures", not_set(), get_fn(get_short_select_failures), SUM_SHARDS},
+    {"stream_nt", set_any(&wax_hip_engine::stream_nt), get_knob(&wax_hip_engine::stream_nt), FIRST_SHARD},
+    {"fuse_merge", set_flag(&wax_hip_engine::fuse_merge), get_knob(&wax_hip_engine::fuse_merge), FIRST_SHARD},
+    {"merged_scans", not_set(), get_counter(&wax_hip_engine::st_merged_scans), FIRST_SHARD},   // a counter, yet not summed: as found, to be decided
+    {"done_flag", set_flag(&wax_hip_engine::done_flag), get_knob(&wax_hip_engine::done_flag), FIRST_SHARD},
+    {"done_flag_waits", not_set(), get_counter(&wax_hip_engine::st_flag_waits), FIRST_SHARD},   // a counter, yet not summed: as found, to be decided
+    {"merge_kway", set_flag(&wax_hip_engine::merge_kway), get_knob(&wax_hip_engine::merge_kway), FIRST_SHARD},
+    {"merge_overlap_mb", set_fn(set_merge_overlap_mb, INT64_MIN, INT64_MAX, nullptr), get_knob(&wax_hip_engine::merge_overlap_mb), FIRST_SHARD},
+    {"overlap_scans", not_set(), get_counter(&wax_hip_engine::st_overlap_scans), FIRST_SHARD},   // a counter, yet not summed: as found, to be decided
+    {"query_args", set_range(&wax_hip_engine::query_args, 0, 2, "query_args must be 0, 1 or 2"), get_knob(&wax_hip_engine::query_args), FIRST_SHARD},
+    {"query_args_scans", not_set(), get_counter(&wax_hip_engine::st_query_args), SUM_SHARDS},
+    {"scan_plain_mb", set_any(&wax_hip_engine::scan_plain_mb), get_knob(&wax_hip_engine::scan_plain_mb), FIRST_SHARD},
+    {"scan_chain", set_range(&wax_hip_engine::scan_chain, -1, 1, "scan_chain must be -1 (auto), 0 or 1"), get_knob(&wax_hip_engine::scan_chain), FIRST_SHARD},
+    {"share_timing", set_flag(&wax_hip_engine::share_timing), get_knob(&wax_hip_engine::share_timing), FIRST_SHARD},   // 0: every chained scan records its own start event (one more packet between scans)
+    {"streams", set_fn(set_streams, 1, kMaxStreams, "streams must be 1..4"), GET_EXPR(e->n_streams), FIRST_SHARD},
+    {"slots", set_fn(set_slots, 1, 64, "slots must be 1..64"), GET_EXPR(e->max_slots), FIRST_SHARD},
+    {"store_ptr", not_set(), GET_EXPR((uintptr_t)e->d_store), FIRST_SHARD},   // diagnosis: where the slab sits (tools/bimodal_probe.py)
+    {"reset_stats", set_fn(set_reset_stats, INT64_MIN, INT64_MAX, nullptr), not_get(), FIRST_SHARD},
+    {"scan_mirror", set_range(&wax_hip_engine::scan_mirror, 0, 2, "scan_mirror must be 0, 1 or 2"), get_knob(&wax_hip_engine::scan_mirror), FIRST_SHARD},
+    {"mirror_scans", not_set(), get_counter(&wax_hip_engine::st_mirror_scans), SUM_SHARDS},
+    {"mirror_scan_fallbacks", not_set(), get_counter(&wax_hip_engine::st_mirror_fallbacks), SUM_SHARDS},
+    {"mirror_scan_unavailable", not_set(), get_counter(&wax_hip_engine::st_mirror_unavailable), SUM_SHARDS},
+    {"mirror_share", set_range(&wax_hip_engine::mirror_share, 0, 2, "mirror_share must be 0, 1 or 2"), get_knob(&wax_hip_engine::mirror_share), FIRST_SHARD},
+    {"mirror_passes", not_set(), get_counter(&wax_hip_engine::st_mirror_passes), SUM_SHARDS},   // scan launches over the mirror, whatever they carried
+    {"mirror_shared_passes", not_set(), get_counter(&wax_hip_engine::st_mirror_shared_passes), SUM_SHARDS},   // ... of which with two or more queries
+    {"mirror_shared_queries", not_set(), get_counter(&wax_hip_engine::st_mirror_shared_queries), SUM_SHARDS},   // queries answered by those
+    {"mirror_fill", set_range(&wax_hip_engine::mirror_fill, 0, 1, "mirror_fill must be 0 or 1"), get_knob(&wax_hip_engine::mirror_fill), FIRST_SHARD},
+    {"mirror_fill_holds", not_set(), get_counter(&wax_hip_engine::st_mirror_fill_holds), SUM_SHARDS},   // submits parked / held and blocking collects that held the parked set back ("mirror_fill" 1)
+    {"mirror_bits", set_one_of(&wax_hip_engine::mirror_bits, 0, 8, 16, "mirror_bits must be 0, 8 or 16"), get_knob(&wax_hip_engine::mirror_bits), FIRST_SHARD},
+    {"mirror8_passes", not_set(), get_counter(&wax_hip_engine::st_mirror8_passes), SUM_SHARDS},   // passes over the 8-bit code mirror (lone or shared; also counted in "mirror_passes")
+    {"mirror8_fallbacks", not_set(), get_counter(&wax_hip_engine::st_mirror8_fallbacks), SUM_SHARDS},   // 8-bit queries whose certificate failed (also counted in "mirror_scan_fallbacks")
+    {"mirror8_unavailable", not_set(), get_counter(&wax_hip_engine::st_mirror8_unavailable), SUM_SHARDS},   // queries sent to bf16 because the code mirror could not be prepared
+    {"mirror8_breaker_trips", not_set(), get_counter(&wax_hip_engine::st_mirror8_breaker_trips), SUM_SHARDS},
+    {"mirror8_conversions", not_set(), GET_EXPR(e->batch.conversions8.load()), SUM_SHARDS},   // code mirror: conversions enqueued / rows converted so far
+    {"mirror8_rows_converted", not_set(), GET_EXPR(e->batch.rows8_converted.load()), SUM_SHARDS},
+    {"mirror_conversions", not_set(), GET_EXPR(e->batch.conversions.load()), FIRST_SHARD},        // bf16 mirror: conversions enqueued / rows converted so far. A counter, yet not summed (its 8-bit twin is): as found, to be decided
+    {"mirror_rows_converted", not_set(), GET_EXPR(e->batch.rows_converted.load()), FIRST_SHARD},  // a counter, yet not summed (its 8-bit twin is): as found, to be decided
+    {"batch_min", set_any(&wax_hip_engine::batch_min), get_knob(&wax_hip_engine::batch_min), FIRST_SHARD},
+    {"batch_mode", set_any(&wax_hip_engine::batch_mode), get_knob(&wax_hip_engine::batch_mode), FIRST_SHARD},
+    {"batch_max_k", not_set(), GET_EXPR(kBatchMaxK), FIRST_SHARD},
+    {"batch_queries", not_set(), get_counter(&wax_hip_engine::st_batch_queries), SUM_SHARDS},
+    {"batch_fallbacks", not_set(), get_counter(&wax_hip_engine::st_batch_fallbacks), SUM_SHARDS},
+    {"batch_qfrag", set_flag(&wax_hip_engine::batch_qfrag), get_knob(&wax_hip_engine::batch_qfrag), FIRST_SHARD},
+    {"batch_rega", set_one_of(&wax_hip_engine::batch_rega, 0, 1, 5, "batch_rega must be 0, 1 or 5"), get_knob(&wax_hip_engine::batch_rega), FIRST_SHARD},
+    {"batch_dyn_tail", set_range(&wax_hip_engine::batch_dyn_tail, 0, 1, "batch_dyn_tail must be 0 or 1"), get_knob(&wax_hip_engine::batch_dyn_tail), FIRST_SHARD},
+    {"batch_host_multi", set_range(&wax_hip_engine::batch_host_multi, 0, 1, "batch_host_multi must be 0 or 1"), get_knob(&wax_hip_engine::batch_host_multi), FIRST_SHARD},
+    {"batch_in_wait", set_range(&wax_hip_engine::batch_in_wait, 0, 1, "batch_in_wait must be 0 or 1"), get_knob(&wax_hip_engine::batch_in_wait), FIRST_SHARD},
+    {"batch_debug", set_mask(&wax_hip_engine::batch_debug, 4096 | 16384 | 65536, "batch_debug: bits 4096, 16384, 65536 only"), not_get(), FIRST_SHARD},
+    {"batch_prof_ptr", set_any(&wax_hip_engine::batch_prof_ptr), not_get(), FIRST_SHARD},
+    {"batch_workspaces", set_fn(set_batch_workspaces, 1, 16, "batch_workspaces must be 1..16"), GET_EXPR(e->bctx_max), FIRST_SHARD},
+    {"batch_first", set_fn(set_batch_first, INT64_MIN, INT64_MAX, nullptr), get_knob(&wax_hip_engine::batch_first), FIRST_SHARD},
+    {"batch_growth", set_range(&wax_hip_engine::batch_growth, 1, 64, "batch_growth must be 1..64"), get_knob(&wax_hip_engine::batch_growth), FIRST_SHARD},
+    {"batch_slab_mb", set_range(&wax_hip_engine::batch_slab_mb, 1, 4096, "batch_slab_mb must be 1..4096"), get_knob(&wax_hip_engine::batch_slab_mb), FIRST_SHARD},
+    {"batch_onepass", set_any(&wax_hip_engine::batch_onepass), get_knob(&wax_hip_engine::batch_onepass), FIRST_SHARD},
+    {"batch_onepass_tiles", set_range(&wax_hip_engine::batch_onepass_tiles, 32, INT64_MAX, "batch_onepass_tiles must be >= 32"), get_knob(&wax_hip_engine::batch_onepass_tiles), FIRST_SHARD},
+    {"onepass_queries", not_set(), get_counter(&wax_hip_engine::st_onepass_queries), SUM_SHARDS},
+    {"batch_kp_fused", set_flag(&wax_hip_engine::batch_kp_fused), get_knob(&wax_hip_engine::batch_kp_fused), FIRST_SHARD},
+    {"batch_survivors", set_range(&wax_hip_engine::batch_survivors, 2, 64, "batch_survivors must be 2..64"), get_knob(&wax_hip_engine::batch_survivors), FIRST_SHARD},
+    {"batch_sample_div", set_range(&wax_hip_engine::batch_sample_div, 4, 4096, "batch_sample_div must be 4..4096"), get_knob(&wax_hip_engine::batch_sample_div), FIRST_SHARD},
+    {"batch_eps_measured", set_flag(&wax_hip_engine::batch_eps_measured), get_knob(&wax_hip_engine::batch_eps_measured), FIRST_SHARD},
+    {"batch_max_norm_e6", not_set(), GET_EXPR(mirror_measured_bound(e, 0) * 1e6), FIRST_SHARD},
+    {"batch_max_row_err_e9", not_set(), GET_EXPR(mirror_measured_bound(e, 1) * 1e9), FIRST_SHARD},
+    {"retry_hint", set_fn(set_retry_hint, 0, 1024, "retry_hint must be 0..1024"), GET_EXPR(e->retry_hint.load()), FIRST_SHARD},
+    {"batch_retry", set_range(&wax_hip_engine::batch_retry, 0, 2, "batch_retry must be 0, 1 or 2"), get_knob(&wax_hip_engine::batch_retry), FIRST_SHARD},
+    {"batch_retries", not_set(), get_counter(&wax_hip_engine::st_batch_retries), SUM_SHARDS},
+    {"batch_inline_retries", not_set(), get_counter(&wax_hip_engine::st_batch_inline_retries), SUM_SHARDS},
+    {"batch_multi", set_flag(&wax_hip_engine::batch_multi), get_knob(&wax_hip_engine::batch_multi), FIRST_SHARD},
+    {"batch_multi_passes", not_set(), get_counter(&wax_hip_engine::st_multi_passes), SUM_SHARDS},
+    {"batch_multi_queries", not_set(), get_counter(&wax_hip_engine::st_multi_queries), SUM_SHARDS},
+    {"batch_multi_group", not_set(), GET_EXPR(scan_multi_group(e->dims, 10)), FIRST_SHARD},        // queries per shared exact pass, k <= 60 (64-slot lists)
+    {"batch_multi_group_big", not_set(), GET_EXPR(scan_multi_group(e->dims, 192)), FIRST_SHARD},   // ... k <= 192 (256-slot lists)
+    {"idhash_rows_inserted", not_set(), get_counter(&wax_hip_engine::st_idhash_rows), FIRST_SHARD},   // a counter, yet not summed: as found, to be decided
+    {"filter_device_min", set_range(&wax_hip_engine::filter_device_min, -1, INT64_MAX, "filter_device_min must be >= -1"), get_knob(&wax_hip_engine::filter_device_min), FIRST_SHARD},
+    {"filter_device_searches", not_set(), get_counter(&wax_hip_engine::st_filter_device), SUM_SHARDS},
+    {"filter_batch", set_range(&wax_hip_engine::filter_batch, 0, 1, "filter_batch must be 0 or 1"), get_knob(&wax_hip_engine::filter_batch), FIRST_SHARD},
+    {"filter_batch_queries", not_set(), get_counter(&wax_hip_engine::st_filter_batch_queries), SUM_SHARDS},
+    {"filter_batch_fallbacks", not_set(), get_counter(&wax_hip_engine::st_filter_batch_fallbacks), SUM_SHARDS},
+    {"predicate_route", set_range(&wax_hip_engine::predicate_route, 0, 2, "predicate_route must be 0 (auto), 1 (gather) or 2 (masked scan)"), get_knob(&wax_hip_engine::predicate_route), FIRST_SHARD},
+    {"predicate_scan_min_permille", set_range(&wax_hip_engine::predicate_scan_min_permille, 0, 1001, "predicate_scan_min_permille must be 0..1001"), get_knob(&wax_hip_engine::predicate_scan_min_permille), FIRST_SHARD},
+    {"predicate_searches", not_set(), get_counter(&wax_hip_engine::st_predicate_searches), SUM_SHARDS},   // wax_hip_search_predicate calls with a non-empty predicate
+    {"predicate_gather_searches", not_set(), get_counter(&wax_hip_engine::st_predicate_gather), SUM_SHARDS},   // ... answered by gathering the passing rows
+    {"predicate_masked_scans", not_set(), get_counter(&wax_hip_engine::st_predicate_masked), SUM_SHARDS},   // ... answered by the masked f32 scan
+    {"predicate_chunks_skipped", not_set(), get_counter(&wax_hip_engine::st_predicate_skipped), SUM_SHARDS},   // chunks those scans did not load
+    {"predicate_mirror", set_range(&wax_hip_engine::predicate_mirror, 0, 2, "predicate_mirror must be 0 (never), 1 (auto) or 2 (every store)"), get_knob(&wax_hip_engine::predicate_mirror), FIRST_SHARD},
+    {"predicate_mirror_scans", not_set(), get_counter(&wax_hip_engine::st_predicate_mirror_scans), SUM_SHARDS},   // masked scans answered from the bf16 mirror under the certificate
+    {"predicate_mirror_fallbacks", not_set(), get_counter(&wax_hip_engine::st_predicate_mirror_fallbacks), SUM_SHARDS},   // ... whose certificate failed: the masked f32 scan answered
+    {"predicate_mirror_unavailable", not_set(), get_counter(&wax_hip_engine::st_predicate_mirror_unavailable), SUM_SHARDS},   // ... sent to the f32 scan because the mirror could not be prepared
+    {"predicate_batch_rows", set_range(&wax_hip_engine::predicate_batch_rows, 0, 0x7fffffffll, "predicate_batch_rows must be 0..2147483647"), get_knob(&wax_hip_engine::predicate_batch_rows), FIRST_SHARD},
+    {"predicate_batch_queries", not_set(), get_counter(&wax_hip_engine::st_predicate_batch_queries), SUM_SHARDS},   // non-empty predicates answered by the batched gather pass
+    {"predicate_batch_classes", not_set(), get_counter(&wax_hip_engine::st_predicate_batch_classes), SUM_SHARDS},   // (list, predicate) entries with a predicate that pass built
+    {"attr_uploaded_rows", not_set(), get_counter(&wax_hip_engine::st_attr_uploaded), SUM_SHARDS},   // rows of the attribute columns uploaded so far
+    {"attr_device_rows", not_set(), GET_EXPR(e->attr_cap), SUM_SHARDS},   // rows the device columns are allocated for (0 = none)
+    {"search_many", set_range(&wax_hip_engine::search_many, 0, 1, "search_many must be 0 or 1"), get_knob(&wax_hip_engine::search_many), FIRST_SHARD},
+    {"search_many_max_rows", set_range(&wax_hip_engine::search_many_max_rows, 0, 0xffffffffll, "search_many_max_rows must be 0..4294967295"), get_knob(&wax_hip_engine::search_many_max_rows), FIRST_SHARD},
+    {"search_many_pooled", not_set(), get_counter(&wax_hip_engine::st_many_pooled), FIRST_SHARD},   // pairs of wax_hip_search_many answered by its pooled launch. A counter, yet not summed: as found, to be decided
+    {"search_many_looped", not_set(), get_counter(&wax_hip_engine::st_many_looped), FIRST_SHARD},   // ... by the single-query search under the call's lock. A counter, yet not summed: as found, to be decided
+    {"search_many_masked", not_set(), get_counter(&wax_hip_engine::st_many_masked), FIRST_SHARD},   // ... of the pooled ones: by a masked group (a non-empty predicate evaluated on the device). A counter, yet not summed: as found, to be decided
+    {"compact_window_rows", set_range(&wax_hip_engine::compact_window_rows, 0, 0xffffffffll, "compact_window_rows must be 0 (what the bounce buffer holds) .. 4294967295"), get_knob(&wax_hip_engine::compact_window_rows), FIRST_SHARD},
+    {"remove_batches", not_set(), get_counter(&wax_hip_engine::st_remove_batches), SUM_SHARDS},   // wax_hip_remove_batch calls that removed rows in one pass
+    {"remove_batch_rows", not_set(), get_counter(&wax_hip_engine::st_remove_batch_rows), SUM_SHARDS},   // rows they removed
+    {"remove_batch_bytes_written", not_set(), get_counter(&wax_hip_engine::st_remove_batch_bytes), SUM_SHARDS},   // device bytes their passes wrote (bounce writes included)
+};
+#undef GET_EXPR
+
+const TuningRow* tuning_row(const std::string& k) {
+    for (const TuningRow& r : kTuning)
+        if (k == r.name) return &r;
+    return nullptr;
+}
+const char* tuning_refusal(const TuningSet& s, int64_t v) {   // the row's message for a value it refuses, null for one it takes
+    switch (s.kind) {
+        case TuningSet::RANGE: case TuningSet::FN: return v < s.a || v > s.b ? s.refusal : nullptr;
+        case TuningSet::ONE_OF: return v != s.a && v != s.b && v != s.c ? s.refusal : nullptr;
+        case TuningSet::MASK: return (v & ~s.a) ? s.refusal : nullptr;
+        default: return nullptr;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
 int wax_hip_set_tuning(wax_hip_engine* e, const char* key, int64_t value) {
     if (!e || !key) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "null argument");
     const std::string k(key);
     if (e->sh) return sh_set_tuning(e, k, value);
-    if (k == "grid_blocks") e->grid_blocks = value;
-    else if (k == "variant") e->variant = value;
-    else if (k == "time_kernels") e->time_kernels = value;
-    else if (k == "force_general") e->force_general = value;
-    else if (k == "select_grid") { if (value < 0 || value > 2048) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "select_grid must be 0 (auto) .. 2048"); e->select_grid = value; }
-    else if (k == "select_short") { if (value < 0 || value > 2) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "select_short must be 0, 1 or 2"); e->select_short = value; }
-    else if (k == "stream_nt") e->stream_nt = value;
-    else if (k == "fuse_merge") e->fuse_merge = value != 0;
-    else if (k == "done_flag") e->done_flag = value != 0;
-    else if (k == "merge_kway") e->merge_kway = value != 0;
-    else if (k == "merge_overlap_mb") e->merge_overlap_mb = value < 0 ? 0 : value;
-    else if (k == "batch_qfrag") e->batch_qfrag = value != 0;
-    else if (k == "scan_plain_mb") e->scan_plain_mb = value;
-    else if (k == "scan_mirror") { if (value < 0 || value > 2) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "scan_mirror must be 0, 1 or 2"); e->scan_mirror = value; }
-    else if (k == "mirror_share") { if (value < 0 || value > 2) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror_share must be 0, 1 or 2"); e->mirror_share = value; }
-    else if (k == "mirror_bits") { if (value != 0 && value != 8 && value != 16) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror_bits must be 0, 8 or 16"); e->mirror_bits = value; }
-    else if (k == "mirror_fill") { if (value < 0 || value > 1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror_fill must be 0 or 1"); e->mirror_fill = value; }
-    else if (k == "query_args") { if (value < 0 || value > 2) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "query_args must be 0, 1 or 2"); e->query_args = value; }
-    else if (k == "batch_min") e->batch_min = value;
-    else if (k == "batch_mode") e->batch_mode = value;
-    else if (k == "batch_rega") { if (value != 0 && value != 1 && value != 5) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_rega must be 0, 1 or 5"); e->batch_rega = value; }
-    else if (k == "batch_dyn_tail") { if (value != 0 && value != 1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_dyn_tail must be 0 or 1"); e->batch_dyn_tail = value; }
-    else if (k == "batch_host_multi") { if (value != 0 && value != 1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_host_multi must be 0 or 1"); e->batch_host_multi = value; }
-    else if (k == "batch_in_wait") { if (value != 0 && value != 1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_in_wait must be 0 or 1"); e->batch_in_wait = value; }
-    else if (k == "batch_debug") { if (value & ~(int64_t)(4096 | 16384 | 65536)) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_debug: bits 4096, 16384, 65536 only"); e->batch_debug = value; }
-    else if (k == "batch_prof_ptr") e->batch_prof_ptr = value;
-    else if (k == "batch_onepass") e->batch_onepass = value;
-    else if (k == "batch_onepass_tiles") { if (value < 32) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_onepass_tiles must be >= 32"); e->batch_onepass_tiles = value; }
-    else if (k == "batch_kp_fused") e->batch_kp_fused = value != 0;
-    else if (k == "batch_survivors") { if (value < 2 || value > 64) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_survivors must be 2..64"); e->batch_survivors = value; }
-    else if (k == "batch_eps_measured") e->batch_eps_measured = value != 0;
-    else if (k == "retry_hint") {   // > 0: the next `value` clean batches still carry the device-side retry kernel (set by collect; tests force it)
-        if (value < 0 || value > 1024) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "retry_hint must be 0..1024");
-        e->retry_hint = (int)value;
-    }
-    else if (k == "batch_retry") { if (value < 0 || value > 2) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_retry must be 0, 1 or 2"); e->batch_retry = value; }
-    else if (k == "batch_multi") e->batch_multi = value != 0;
-    else if (k == "scan_chain") { if (value < -1 || value > 1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "scan_chain must be -1 (auto), 0 or 1"); e->scan_chain = value; }
-    else if (k == "share_timing") e->share_timing = value != 0;   // 0: every chained scan records its own start event (one more packet between scans)
-    else if (k == "filter_batch") { if (value < 0 || value > 1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "filter_batch must be 0 or 1"); e->filter_batch = value; }
-    else if (k == "predicate_batch_rows") { if (value < 0 || value > 0x7fffffffll) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "predicate_batch_rows must be 0..2147483647"); e->predicate_batch_rows = value; }
-    else if (k == "filter_device_min") { if (value < -1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "filter_device_min must be >= -1"); e->filter_device_min = value; }
-    else if (k == "search_many") { if (value < 0 || value > 1) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "search_many must be 0 or 1"); e->search_many = value; }
-    else if (k == "search_many_max_rows") { if (value < 0 || value > 0xffffffffll) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "search_many_max_rows must be 0..4294967295"); e->search_many_max_rows = value; }
-    else if (k == "predicate_route") { if (value < 0 || value > 2) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "predicate_route must be 0 (auto), 1 (gather) or 2 (masked scan)"); e->predicate_route = value; }
-    else if (k == "predicate_mirror") { if (value < 0 || value > 2) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "predicate_mirror must be 0 (never), 1 (auto) or 2 (every store)"); e->predicate_mirror = value; }
-    else if (k == "predicate_scan_min_permille") { if (value < 0 || value > 1001) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "predicate_scan_min_permille must be 0..1001"); e->predicate_scan_min_permille = value; }
-    else if (k == "compact_window_rows") { if (value < 0 || value > 0xffffffffll) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "compact_window_rows must be 0 (what the bounce buffer holds) .. 4294967295"); e->compact_window_rows = value; }
-    else if (k == "batch_sample_div") { if (value < 4 || value > 4096) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_sample_div must be 4..4096"); e->batch_sample_div = value; }
-    else if (k == "batch_workspaces") {
-        if (value < 1 || value > 16) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_workspaces must be 1..16");
-        std::unique_lock<std::mutex> g(e->bctx_mu);
-        e->bctx_max = (int)value;
-    }
-    else if (k == "batch_first") { if (value < 128 || value > kBatchFirstSlab || value % 128) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_first must be a multiple of 128 in 128..2048"); e->batch_first = value; }
-    else if (k == "batch_growth") { if (value < 1 || value > 64) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_growth must be 1..64"); e->batch_growth = value; }
-    else if (k == "batch_slab_mb") { if (value < 1 || value > 4096) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "batch_slab_mb must be 1..4096"); e->batch_slab_mb = value; }
-    else if (k == "streams") {
-        if (value < 1 || value > kMaxStreams) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "streams must be 1..4");
-        std::unique_lock<std::mutex> g(e->slot_mu);
-        e->n_streams = (int)value;
-    } else if (k == "slots") {
-        if (value < 1 || value > 64) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "slots must be 1..64");
-        std::unique_lock<std::mutex> g(e->slot_mu);
-        e->max_slots = (int)value;
-    } else if (k == "reset_stats") {
-        e->st_searches = 0; e->st_rows = 0; e->st_bytes = 0;
-        {
-            DeviceGuard g(e->device);
-            for (int r = 0; r < kShardRing; ++r) harvest_ring_event(e, r);
-        }
-        std::unique_lock<std::mutex> sg(e->st_mu);
-        e->st_last_ms = 0; e->st_total_ms = 0; e->st_timed = 0;
-        e->st_gemm_ms = 0; e->st_gemm_timed = 0; e->st_gemm_rows = 0; e->st_gemm_queries = 0;
-    } else return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "unknown tuning key '" + k + "'");
+    const TuningRow* r = tuning_row(k);
+    if (!r || r->set.kind == TuningSet::NONE) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "unknown tuning key '" + k + "'");
+    if (const char* refusal = tuning_refusal(r->set, value)) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, refusal);
+    if (r->set.kind == TuningSet::FN) return r->set.fn(e, value);
+    e->*(r->set.knob) = r->set.kind == TuningSet::FLAG ? (int64_t)(value != 0) : value;
     return WAX_HIP_OK;
 }
 
@@ -113,139 +266,11 @@ int64_t wax_hip_get_tuning(wax_hip_engine* e, const char* key) {
     if (!e || !key) return -1;
     const std::string k(key);
     if (e->sh) return sh_get_tuning(e, k);
-    if (k == "grid_blocks") return e->grid_blocks.load();
-    if (k == "variant") return e->variant.load();
-    if (k == "time_kernels") return e->time_kernels.load();
-    if (k == "force_general") return e->force_general.load();
-    if (k == "select_short") return e->select_short.load();
-    if (k == "select_grid") return e->select_grid.load();
-    if (k == "short_selects") return (int64_t)e->st_short_selects.load();
-    if (k == "short_select_failures") {   // short selections whose certificate failed (the long path answered): device words of every slot; a blocking read
-        int64_t t = 0;
-        DeviceGuard g(e->device);
-        (void)hipDeviceSynchronize();
-        std::unique_lock<std::mutex> tg(e->slot_mu);
-        for (Slot* sl : e->all_slots) {
-            uint32_t f[4] = {0u, 0u, 0u, 0u};
-            if (sl->sw_ready && sl->sw.flags && hipMemcpy(f, sl->sw.flags, sizeof(f), hipMemcpyDeviceToHost) == hipSuccess) t += f[1];
-            if (sl->d_partials && hipMemcpy(f, partials_ticket(sl->d_partials) + 8, sizeof(f), hipMemcpyDeviceToHost) == hipSuccess) t += f[1];   // the fused path's short merge
-        }
-        for (int r = 0; r < kShardRing; ++r) {
-            uint32_t f[4] = {0u, 0u, 0u, 0u};
-            if (e->ring_d_partials[r] && hipMemcpy(f, partials_ticket(e->ring_d_partials[r]) + 8, sizeof(f), hipMemcpyDeviceToHost) == hipSuccess) t += f[1];
-        }
-        return t;
-    }
-    if (k == "stream_nt") return e->stream_nt.load();
-    if (k == "fuse_merge") return e->fuse_merge.load();
-    if (k == "query_args") return e->query_args.load();
-    if (k == "done_flag") return e->done_flag.load();
-    if (k == "merge_kway") return e->merge_kway.load();
-    if (k == "merge_overlap_mb") return e->merge_overlap_mb.load();
-    if (k == "batch_qfrag") return e->batch_qfrag.load();
-    if (k == "overlap_scans") return (int64_t)e->st_overlap_scans.load();
-    if (k == "scan_plain_mb") return e->scan_plain_mb.load();
-    if (k == "scan_mirror") return e->scan_mirror.load();
-    if (k == "mirror_scans") return (int64_t)e->st_mirror_scans.load();
-    if (k == "mirror_scan_fallbacks") return (int64_t)e->st_mirror_fallbacks.load();
-    if (k == "mirror_scan_unavailable") return (int64_t)e->st_mirror_unavailable.load();
-    if (k == "mirror_share") return e->mirror_share.load();
-    if (k == "mirror_passes") return (int64_t)e->st_mirror_passes.load();                    // scan launches over the mirror, whatever they carried
-    if (k == "mirror_shared_passes") return (int64_t)e->st_mirror_shared_passes.load();      // ... of which with two or more queries
-    if (k == "mirror_shared_queries") return (int64_t)e->st_mirror_shared_queries.load();    // queries answered by those
-    if (k == "mirror_fill") return e->mirror_fill.load();
-    if (k == "mirror_bits") return e->mirror_bits.load();
-    if (k == "mirror8_passes") return (int64_t)e->st_mirror8_passes.load();              // passes over the 8-bit code mirror (lone or shared; also counted in "mirror_passes")
-    if (k == "mirror8_fallbacks") return (int64_t)e->st_mirror8_fallbacks.load();        // 8-bit queries whose certificate failed (also counted in "mirror_scan_fallbacks")
-    if (k == "mirror8_unavailable") return (int64_t)e->st_mirror8_unavailable.load();    // queries sent to bf16 because the code mirror could not be prepared
-    if (k == "mirror8_conversions") return (int64_t)e->batch.conversions8.load();        // code mirror: conversions enqueued / rows converted so far
-    if (k == "mirror8_rows_converted") return (int64_t)e->batch.rows8_converted.load();
-    if (k == "mirror8_breaker_trips") return (int64_t)e->st_mirror8_breaker_trips.load();
-    if (k == "mirror_fill_holds") return (int64_t)e->st_mirror_fill_holds.load();            // submits parked / held and blocking collects that held the parked set back ("mirror_fill" 1)
-    if (k == "done_flag_waits") return (int64_t)e->st_flag_waits.load();
-    if (k == "query_args_scans") return (int64_t)e->st_query_args.load();
-    if (k == "merged_scans") return (int64_t)e->st_merged_scans.load();
-    if (k == "batch_inline_retries") return (int64_t)e->st_batch_inline_retries.load();
-    if (k == "retry_hint") return e->retry_hint.load();
-    if (k == "batch_eps_measured") return e->batch_eps_measured.load();
-    if (k == "batch_max_row_err_e9" || k == "batch_max_norm_e6") {   // the mirror's measured bounds (device words; a blocking read)
-        unsigned int bits[2] = {0u, 0u};
-        if (e->batch.d_maxnorm) {
-            DeviceGuard g(e->device);
-            (void)hipDeviceSynchronize();
-            (void)hipMemcpy(bits, e->batch.d_maxnorm, sizeof(bits), hipMemcpyDeviceToHost);
-        }
-        float f[2];
-        std::memcpy(f, bits, sizeof(f));
-        return k == "batch_max_norm_e6" ? (int64_t)((double)f[0] * 1e6) : (int64_t)((double)f[1] * 1e9);
-    }
-    if (k == "mirror_rows_converted") return (int64_t)e->batch.rows_converted.load();   // bf16 mirror: rows converted so far / conversions enqueued
-    if (k == "mirror_conversions") return (int64_t)e->batch.conversions.load();
-    if (k == "compact_window_rows") return e->compact_window_rows.load();
-    if (k == "remove_batches") return (int64_t)e->st_remove_batches.load();            // wax_hip_remove_batch calls that removed rows in one pass
-    if (k == "remove_batch_rows") return (int64_t)e->st_remove_batch_rows.load();      // rows they removed
-    if (k == "remove_batch_bytes_written") return (int64_t)e->st_remove_batch_bytes.load();   // device bytes their passes wrote (bounce writes included)
-    if (k == "predicate_route") return e->predicate_route.load();
-    if (k == "predicate_scan_min_permille") return e->predicate_scan_min_permille.load();
-    if (k == "predicate_searches") return (int64_t)e->st_predicate_searches.load();          // wax_hip_search_predicate calls with a non-empty predicate
-    if (k == "predicate_gather_searches") return (int64_t)e->st_predicate_gather.load();     // ... answered by gathering the passing rows
-    if (k == "predicate_masked_scans") return (int64_t)e->st_predicate_masked.load();        // ... answered by the masked f32 scan
-    if (k == "predicate_chunks_skipped") return (int64_t)e->st_predicate_skipped.load();     // chunks those scans did not load
-    if (k == "predicate_mirror") return e->predicate_mirror.load();
-    if (k == "predicate_mirror_scans") return (int64_t)e->st_predicate_mirror_scans.load();              // masked scans answered from the bf16 mirror under the certificate
-    if (k == "predicate_mirror_fallbacks") return (int64_t)e->st_predicate_mirror_fallbacks.load();      // ... whose certificate failed: the masked f32 scan answered
-    if (k == "predicate_mirror_unavailable") return (int64_t)e->st_predicate_mirror_unavailable.load();  // ... sent to the f32 scan because the mirror could not be prepared
-    if (k == "attr_uploaded_rows") return (int64_t)e->st_attr_uploaded.load();               // rows of the attribute columns uploaded so far
-    if (k == "attr_device_rows") return (int64_t)e->attr_cap;                                // rows the device columns are allocated for (0 = none)
-    if (k == "idhash_rows_inserted") return (int64_t)e->st_idhash_rows.load();
-    if (k == "batch_min") return e->batch_min.load();
-    if (k == "batch_mode") return e->batch_mode.load();
-    if (k == "batch_rega") return e->batch_rega.load();
-    if (k == "batch_dyn_tail") return e->batch_dyn_tail.load();
-    if (k == "batch_in_wait") return e->batch_in_wait.load();
-    if (k == "batch_host_multi") return e->batch_host_multi.load();
-    if (k == "batch_slab_mb") return e->batch_slab_mb.load();
-    if (k == "batch_growth") return e->batch_growth.load();
-    if (k == "batch_first") return e->batch_first.load();
-    if (k == "batch_onepass") return e->batch_onepass.load();
-    if (k == "batch_onepass_tiles") return e->batch_onepass_tiles.load();
-    if (k == "batch_kp_fused") return e->batch_kp_fused.load();
-    if (k == "batch_survivors") return e->batch_survivors.load();
-    if (k == "batch_sample_div") return e->batch_sample_div.load();
-    if (k == "batch_workspaces") return e->bctx_max;
-    if (k == "batch_max_k") return kBatchMaxK;
-    if (k == "onepass_queries") return (int64_t)e->st_onepass_queries.load();
-    if (k == "scan_chain") return e->scan_chain.load();
-    if (k == "share_timing") return e->share_timing.load();
-    if (k == "batch_retry") return e->batch_retry.load();
-    if (k == "batch_retries") return (int64_t)e->st_batch_retries.load();
-    if (k == "batch_multi") return e->batch_multi.load();
-    if (k == "batch_multi_passes") return (int64_t)e->st_multi_passes.load();
-    if (k == "batch_multi_queries") return (int64_t)e->st_multi_queries.load();
-    if (k == "batch_multi_group") return (int64_t)scan_multi_group(e->dims, 10);        // queries per shared exact pass, k <= 60 (64-slot lists)
-    if (k == "batch_multi_group_big") return (int64_t)scan_multi_group(e->dims, 192);   // ... k <= 192 (256-slot lists)
-    if (k == "filter_device_min") return e->filter_device_min.load();
-    if (k == "filter_device_searches") return (int64_t)e->st_filter_device.load();
-    if (k == "filter_batch") return e->filter_batch.load();
-    if (k == "filter_batch_queries") return (int64_t)e->st_filter_batch_queries.load();
-    if (k == "filter_batch_fallbacks") return (int64_t)e->st_filter_batch_fallbacks.load();
-    if (k == "predicate_batch_rows") return e->predicate_batch_rows.load();
-    if (k == "predicate_batch_queries") return (int64_t)e->st_predicate_batch_queries.load();   // non-empty predicates answered by the batched gather pass
-    if (k == "predicate_batch_classes") return (int64_t)e->st_predicate_batch_classes.load();   // (list, predicate) entries with a predicate that pass built
-    if (k == "search_many") return e->search_many.load();
-    if (k == "search_many_max_rows") return e->search_many_max_rows.load();
-    if (k == "search_many_pooled") return (int64_t)e->st_many_pooled.load();   // pairs of wax_hip_search_many answered by its pooled launch
-    if (k == "search_many_looped") return (int64_t)e->st_many_looped.load();   // ... by the single-query search under the call's lock
-    if (k == "search_many_masked") return (int64_t)e->st_many_masked.load();   // ... of the pooled ones: by a masked group (a non-empty predicate evaluated on the device)
-    if (k == "batch_queries") return (int64_t)e->st_batch_queries.load();
-    if (k == "batch_fallbacks") return (int64_t)e->st_batch_fallbacks.load();
-    if (k == "slots") return e->max_slots;
-    if (k == "streams") return e->n_streams;
-    if (k == "variant_count") return scan_variant_count(e->dims);
-    if (k == "scan_grid") return scan_grid_for((uint32_t)e->count, e->dims, (int)e->variant.load(), (int)e->grid_blocks.load());
-    if (k == "fused_max_k") return FUSED_MAX_K;
-    if (k == "store_ptr") return (int64_t)(uintptr_t)e->d_store;   // diagnosis: where the slab sits (tools/bimodal_probe.py)
-    return -1;
+    const TuningRow* r = tuning_row(k);
+    if (!r) return -1;
+    if (r->get.knob) return (e->*(r->get.knob)).load();
+    if (r->get.counter) return (int64_t)(e->*(r->get.counter)).load();
+    return r->get.fn ? r->get.fn(e) : -1;
 }
 
 int wax_hip_time_scan_kernel(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, uint32_t iters,
