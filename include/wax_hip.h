@@ -631,6 +631,12 @@ int wax_hip_mirror8_snapshot(wax_hip_engine* e, uint64_t first_row, uint64_t n_r
  * and changes no counter and no breaker state. WAX_HIP_ERR_INVALID_ARGUMENT: a sharded handle, a code mirror that is absent or not
  * valid, another n_keys, a NULL pointer. */
 int wax_hip_mirror8_keys(wax_hip_engine* e, const float* query, float* out_keys, uint64_t n_keys);
+/* Diagnostic of the mirror finish's candidate selection (tests compare its two ways through it; no product path calls it). `lists`
+ * = n_lists (1 to 512) lists of 64 keys each, every list ascending and padded with INT64_MAX, no key twice. On the current device,
+ * in one workgroup with the finish's own shared-memory layout: out_selected[64] = the 64 smallest keys as the finish picks them
+ * (the gathered prefixes where they fit its buffer, else the k-way merge), out_merged[64] = the k-way merge alone, *out_gathered =
+ * 1 where the gather answered. Blocking. */
+int wax_hip_mirror_select_probe(const int64_t* lists, uint32_t n_lists, int64_t* out_selected, int64_t* out_merged, int32_t* out_gathered);
 
 #ifdef __cplusplus
 }

@@ -160,6 +160,18 @@ struct MirrorGroupArgs {
 };
 // Two launches on `st`: the NQ-query scan and a finish launch of NQ workgroups (one per query). 2 <= nq <= MIRROR_MAX_NQ.
 hipError_t launch_mirror_group(const MirrorGroupArgs& args, int nq, int metric, int grid_cap, hipStream_t st);
+// The members' queries into device memory in ONE launch in front of the scan (mirror_group_queries_kernel, one workgroup per member):
+// src[i] is pinned host memory the device reads directly (dims floats, dims a multiple of 4), dst[i] the member's MirrorMember::query.
+struct MirrorQueryCopies {
+    const float* src[MIRROR_MAX_NQ];
+    float* dst[MIRROR_MAX_NQ];
+    uint32_t dims;
+};
+hipError_t launch_mirror_group_queries(const MirrorQueryCopies& c, int nq, hipStream_t st);
+// A diagnostic (wax_hip_mirror_select_probe): step (1) of mirror_finish as the finish runs it (gather_select, kway_merge where it
+// overflows) into out[0 .. MIRROR_KP), kway_merge alone on the same lists into out[MIRROR_KP .. 2 MIRROR_KP), *gathered = 1 where
+// gather_select answered. d_lists: [lists][MIRROR_KP] sorted keys, KEY_PAD-padded, 1 <= lists <= SCAN_KWAY_MERGE_GRID. One workgroup.
+hipError_t launch_mirror_select_probe(const int64_t* d_lists, int lists, int64_t* d_out, int* d_gathered, hipStream_t st);
 
 // ---- mirror8_scan.hip: the same two launches over the 8-bit code mirror ("Eight bits per element") ----
 // Codes are row-scaled and stored with a +128 bias ([n_rows][dims] bytes); meta is [n_rows] {scale, err}, err an upper bound on

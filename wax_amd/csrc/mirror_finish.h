@@ -43,14 +43,22 @@ __device__ __forceinline__ void mirror_finish(const MirrorScanArgs& a, const f32
     constexpr int ROWS_PER_PASS = RPW * SCAN_WAVES;
     constexpr int PASSES = MIRROR_KP / ROWS_PER_PASS;
     static_assert(MIRROR_KP % ROWS_PER_PASS == 0, "whole passes");
-    __shared__ int64_t approx[MIRROR_KP], exact[MIRROR_KP], sorted[MIRROR_KP], xch[2 * SCAN_WAVES];
+    static_assert(GATHER_CAP == 2 * MIRROR_KP && 2 * SCAN_WAVES * sizeof(int64_t) >= (1 + SCAN_WAVES) * sizeof(int), "the selection's buffers are (2)-(3)'s and the merge's");
+    __shared__ int64_t approx[MIRROR_KP], work[2 * MIRROR_KP], xch[2 * SCAN_WAVES];
+    int64_t* const exact = work;                  // (2), (3); until then `work` is the selection's gather buffer, and `xch` its control
+                                                  // words before it is the merge's: gather_select leaves through a barrier on both ways out
+    int64_t* const sorted = work + MIRROR_KP;
     const int t = (int)threadIdx.x;
     const int lane = lane_id();
     const int wave = t >> 6;
 
-    // (1) the MIRROR_KP best approximate keys of the whole store
-    if (a.lists <= SCAN_THREADS) kway_merge<1>(a.partials, a.lists, MIRROR_KP, approx, xch);
-    else kway_merge<2>(a.partials, a.lists, MIRROR_KP, approx, xch);
+    // (1) the MIRROR_KP best approximate keys of the whole store: the lists' prefixes under a bound from their heads, sorted in LDS
+    // (gather_select, topk.h); the k-way merge of the heads, whose answer that is, when they overflow the buffer
+    if (a.lists <= SCAN_THREADS) {
+        if (!gather_select<1>(a.partials, a.lists, MIRROR_KP, approx, work, reinterpret_cast<int*>(xch))) kway_merge<1>(a.partials, a.lists, MIRROR_KP, approx, xch);
+    } else {
+        if (!gather_select<2>(a.partials, a.lists, MIRROR_KP, approx, work, reinterpret_cast<int*>(xch))) kway_merge<2>(a.partials, a.lists, MIRROR_KP, approx, xch);
+    }
 
     // (2) exact f32 re-score of those rows: row_distance (row_math.h) at the f32 scan's shape for this dimension
     const int sub = lane / GROUP, gl = lane % GROUP;

@@ -11,7 +11,9 @@
 //                 mirror_scan_masked_kernel   the same under a row bitmap (a predicate search, filter_host.inc): chunks without a
 //                                             passing row are not loaded, only passing rows are offered
 //                 mirror_scan_group_kernel    2-4 queries ("mirror_share"), read from device memory: one load of a row serves all
-//   the finish  mirror_finish (mirror_finish.h), one workgroup per query: k-way merge of the lists' heads -> the MIRROR_KP best
+//                                             (mirror_group_queries_kernel in front of it copies them there from pinned host memory)
+//   the finish  mirror_finish (mirror_finish.h), one workgroup per query: the lists' prefixes under a bound from their heads, sorted
+//               (gather_select; the k-way merge of the heads when they overflow its buffer) -> the MIRROR_KP best
 //               approximate keys of the store, exact f32 re-score of those rows with scan_kernel's own lane mapping and summation order
 //               (bit-identical distances), sort, the k best, frame ids, and the certificate
 //                   a_KP - eps > d_k     (a_KP: the KP-th approximate distance, d_k: the exact k-th)
@@ -85,6 +87,48 @@ template <int DIMS, int METRIC>
 __global__ __launch_bounds__(SCAN_THREADS) void mirror_finish_group_kernel(MirrorGroupArgs g) {
     const MirrorMember& m = g.m[blockIdx.x];
     mirror_finish<DIMS, METRIC, Bf16Eps>(member_args(g.a, m), reinterpret_cast<const f32x4*>(m.query));
+}
+
+// the queries of a shared pass from the slots' pinned host buffers into their device buffers, one workgroup per member
+__global__ __launch_bounds__(SCAN_THREADS) void mirror_group_queries_kernel(MirrorQueryCopies c) {
+    const f32x4* __restrict__ src = reinterpret_cast<const f32x4*>(c.src[blockIdx.x]);
+    f32x4* __restrict__ dst = reinterpret_cast<f32x4*>(c.dst[blockIdx.x]);
+    for (uint32_t i = threadIdx.x; i < c.dims / 4u; i += SCAN_THREADS) dst[i] = src[i];
+}
+
+hipError_t launch_mirror_group_queries(const MirrorQueryCopies& c, int nq, hipStream_t st) {
+    if (nq < 1 || nq > MIRROR_MAX_NQ || c.dims == 0u || (c.dims & 3u) != 0u) return hipErrorInvalidValue;
+    for (int i = 0; i < nq; ++i)
+        if (c.src[i] == nullptr || c.dst[i] == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mirror_group_queries_kernel, dim3(nq), dim3(SCAN_THREADS), 0, st, c);
+    return hipGetLastError();
+}
+
+// mirror_finish's step (1) with mirror_finish's LDS layout and aliasing, then the k-way merge alone (launch_mirror_select_probe)
+__global__ __launch_bounds__(SCAN_THREADS) void mirror_select_probe_kernel(const int64_t* __restrict__ lists_keys, int lists, int64_t* __restrict__ out,
+                                                                           int* __restrict__ gathered) {
+    __shared__ int64_t approx[MIRROR_KP], work[2 * MIRROR_KP], xch[2 * SCAN_WAVES];
+    const int t = (int)threadIdx.x;
+    bool took;
+    if (lists <= SCAN_THREADS) {
+        took = gather_select<1>(lists_keys, lists, MIRROR_KP, approx, work, reinterpret_cast<int*>(xch));
+        if (!took) kway_merge<1>(lists_keys, lists, MIRROR_KP, approx, xch);
+    } else {
+        took = gather_select<2>(lists_keys, lists, MIRROR_KP, approx, work, reinterpret_cast<int*>(xch));
+        if (!took) kway_merge<2>(lists_keys, lists, MIRROR_KP, approx, xch);
+    }
+    if (t < MIRROR_KP) out[t] = approx[t];
+    if (t == 0) *gathered = took ? 1 : 0;
+    __syncthreads();
+    if (lists <= SCAN_THREADS) kway_merge<1>(lists_keys, lists, MIRROR_KP, approx, xch);
+    else kway_merge<2>(lists_keys, lists, MIRROR_KP, approx, xch);
+    if (t < MIRROR_KP) out[MIRROR_KP + t] = approx[t];
+}
+
+hipError_t launch_mirror_select_probe(const int64_t* d_lists, int lists, int64_t* d_out, int* d_gathered, hipStream_t st) {
+    if (d_lists == nullptr || d_out == nullptr || d_gathered == nullptr || lists < 1 || lists > SCAN_KWAY_MERGE_GRID) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mirror_select_probe_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, d_lists, lists, d_out, d_gathered);
+    return hipGetLastError();
 }
 
 bool mirror_scan_supported(uint32_t dims, int metric) {

@@ -407,8 +407,9 @@ static int parked_take_f32(wax_hip_engine* e, Slot* s) {
     return WAX_HIP_OK;
 }
 
-// One pass for `nq` >= 2 parked queries on the first one's stream: query uploads, the group scan, one finish workgroup per member,
-// and every member's ev_done behind the finish launch.
+// One pass for `nq` >= 2 parked queries on the first one's stream: one launch that copies the members' queries from their pinned
+// h_query into their d_query (a hipMemcpyAsync per member cost the host as much as a launch each, in the gap in front of the scan),
+// the group scan, one finish workgroup per member, and every member's ev_done behind the finish launch.
 static int enqueue_mirror_group(wax_hip_engine* e, Slot* const* grp, int nq, bool* took) {
     *took = false;
     BatchMirror& b = e->batch;
@@ -435,9 +436,12 @@ static int enqueue_mirror_group(wax_hip_engine* e, Slot* const* grp, int nq, boo
     g.a.row_base = (uint32_t)e->row_base;
     g.a.dims = e->dims;
     g.a.use_measured = e->batch_eps_measured.load() != 0 ? 1 : 0;
+    MirrorQueryCopies qc{};
+    qc.dims = e->dims;
     for (int i = 0; i < nq; ++i) {
         Slot* s = grp[i];
-        HIP_TRY(hipMemcpyAsync(s->d_query, s->h_query, (size_t)e->dims * sizeof(float), hipMemcpyHostToDevice, st), WAX_HIP_ERR_INTERNAL, "query upload");
+        qc.src[i] = s->h_query;
+        qc.dst[i] = s->d_query;
         g.m[i].query = s->d_query;
         g.m[i].partials = s->d_partials;
         g.m[i].hits = s->h_hits;
@@ -448,6 +452,7 @@ static int enqueue_mirror_group(wax_hip_engine* e, Slot* const* grp, int nq, boo
         s->t_start = nullptr;
         s->t_end = nullptr;
     }
+    HIP_TRY(launch_mirror_group_queries(qc, nq, st), WAX_HIP_ERR_INTERNAL, "query upload");
     HIP_TRY(use8 ? launch_mirror8_group(g, b.d_c8, b.d_c8_meta, nq, e->metric, (int)e->grid_blocks.load(), st)
                  : launch_mirror_group(g, nq, e->metric, (int)e->grid_blocks.load(), st), WAX_HIP_ERR_INTERNAL, "mirror group launch");
     for (int i = 0; i < nq; ++i) {

@@ -31,7 +31,8 @@ int alloc_slot(wax_hip_engine* e, Slot** out) {
     if ((err = hipEventCreateWithFlags(&s->ev_done, hipEventDisableTiming)) != hipSuccess) return bail(WAX_HIP_ERR_ALLOC, "event", err);
     const size_t qbytes = (size_t)e->dims * sizeof(float);
     if ((err = hipMalloc(&s->d_query, qbytes)) != hipSuccess) return bail(WAX_HIP_ERR_ALLOC, "transient query buffer", err);
-    if ((err = hipHostMalloc(&s->h_query, qbytes, hipHostMallocDefault)) != hipSuccess) return bail(WAX_HIP_ERR_ALLOC, "pinned query buffer", err);
+    // (device-mapped, as hipHostMallocDefault is: mirror_group_queries_kernel reads a parked query straight from h_query)
+    if ((err = hipHostMalloc(&s->h_query, qbytes, hipHostMallocDefault | hipHostMallocMapped)) != hipSuccess) return bail(WAX_HIP_ERR_ALLOC, "pinned query buffer", err);
     if ((err = hipMalloc(&s->d_partials, kPartialsBytes)) != hipSuccess) return bail(WAX_HIP_ERR_ALLOC, "top-k stage buffer", err);
     if ((err = hipMemset(partials_ticket(s->d_partials), 0, 128)) != hipSuccess) return bail(WAX_HIP_ERR_ALLOC, "top-k stage buffer", err);
     // hipMemset on device memory may return before the fill has run, and the slot's scans run on non-blocking streams the

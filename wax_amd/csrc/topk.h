@@ -304,4 +304,90 @@ __device__ __attribute__((noinline)) void kway_merge(const int64_t* partials, in
     __syncthreads();
 }
 
+// ---- the mirror finish (mirror_finish.h), k = MIRROR_KP = 64 behind ~500 lists: kway_merge's answer without its k barrier rounds ----
+// (select_short_kernel's scheme, kernels.hip, at the finish's size.) The lists are sorted and their keys distinct rows, so any U with at
+// least k keys <= U bounds the k-th key, and the keys <= U are a prefix of every list:
+//   (1) U: thread (wave w, lane l) owns lists 4 l + w (+ SCAN_THREADS), so every wave holds a quarter of the lists whatever their
+//       number. A lane's value is the distance word of its smallest head; the wave ranks its 64 values in registers (readlane, no
+//       LDS) and takes the (k / SCAN_WAVES)-th; U is the largest of the four with every row under it. k / SCAN_WAVES lanes of each wave
+//       have a head <= U: k distinct keys. (Looser than the k-th smallest head of all, by about a quarter more keys on a random store.)
+//   (2) every list's prefix <= U into `buf` (GATHER_CAP keys of LDS) through one LDS counter (by estimate ~85 keys at ~500 lists of a random store);
+//   (3) rank sort of the gathered keys: the first k into fin[0..k), KEY_PAD behind them when the lists hold fewer.
+// Returns false, with fin untouched, when more than GATHER_CAP keys are <= U (the best rows in a few workgroups' lists, equal
+// distances, fewer than k live heads above two lists): the caller runs kway_merge, whose answer this is in every other case.
+// Ends with a barrier on either way out, so `ctl` (1 + SCAN_WAVES ints of LDS) and `buf` may be reused at once by the caller.
+constexpr int GATHER_CAP = 128;
+template <int LISTS>
+__device__ __attribute__((noinline)) bool gather_select(const int64_t* __restrict__ partials, int nlists, int k, int64_t* fin, int64_t* buf, int* ctl) {
+    const int t = (int)threadIdx.x;
+    const int lane = t & 63, wave = t >> 6;
+    int64_t h[LISTS][4];
+    int x = INT32_MAX;
+#pragma unroll
+    for (int j = 0; j < LISTS; ++j) {
+        const int list = lane * SCAN_WAVES + wave + j * SCAN_THREADS;
+        const int64_t* lst = partials + (size_t)list * k;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) h[j][i] = (list < nlists && i < k) ? lst[i] : KEY_PAD;
+        const int hi = (int)(h[j][0] >> 32);
+        x = hi < x ? hi : x;
+    }
+    // (1)
+    int rank = 0;
+#pragma unroll
+    for (int l = 0; l < 64; ++l) {
+        const int o = __builtin_amdgcn_readlane(x, l);
+        rank += (o < x || (o == x && l < lane)) ? 1 : 0;
+    }
+    const int quota = k / SCAN_WAVES;
+    if (rank == quota - 1) ctl[1 + wave] = x;                      // ranks are a permutation of 0 .. 63: one lane
+    if (t == 0) ctl[0] = 0;
+    __syncthreads();
+    int u32 = ctl[1];
+#pragma unroll
+    for (int w = 1; w < SCAN_WAVES; ++w) u32 = ctl[1 + w] > u32 ? ctl[1 + w] : u32;
+    const int64_t bound = (int64_t)(((uint64_t)(uint32_t)u32 << 32) | 0xffffffffull);
+    // (2)
+#pragma unroll
+    for (int j = 0; j < LISTS; ++j) {
+        const int64_t* lst = partials + (size_t)(lane * SCAN_WAVES + wave + j * SCAN_THREADS) * k;
+        for (int i = 0; i < k;) {
+            const int sel = i & 3;
+            const int64_t key = sel == 0 ? h[j][0] : sel == 1 ? h[j][1] : sel == 2 ? h[j][2] : h[j][3];
+            if (key == KEY_PAD || key > bound) break;
+            const int pos = atomicAdd(&ctl[0], 1);
+            if (pos >= GATHER_CAP) break;                          // overflow: the count alone is read below
+            buf[pos] = key;
+            ++i;
+            if ((i & 3) == 0 && i < k) {                           // (h[j][0] != KEY_PAD: the list exists)
+#pragma unroll
+                for (int n = 0; n < 4; ++n) h[j][n] = (i + n < k) ? lst[i + n] : KEY_PAD;
+            }
+        }
+    }
+    __syncthreads();
+    const int c = ctl[0];
+    if (c > GATHER_CAP) {                                          // workgroup-uniform
+        // `ctl` may be the k-way merge's exchange slots (mirror_finish: xch), which its first round writes before its first barrier:
+        // every thread has read the count before any thread leaves
+        __syncthreads();
+        return false;
+    }
+    // (3)
+    if (t < GATHER_CAP) {
+        const int64_t key = t < c ? buf[t] : KEY_PAD;
+        int r = 0;
+        int j = 0;
+        for (; j + 4 <= c; j += 4) {
+#pragma unroll
+            for (int n = 0; n < 4; ++n) r += (buf[j + n] < key) ? 1 : 0;
+        }
+        for (; j < c; ++j) r += (buf[j] < key) ? 1 : 0;
+        if (t < c && r < k) fin[r] = key;
+        if (t >= c && t < k) fin[t] = KEY_PAD;
+    }
+    __syncthreads();
+    return true;
+}
+
 }  // namespace wax

@@ -412,3 +412,27 @@ int wax_hip_mirror8_keys(wax_hip_engine* e, const float* query, float* out_keys,
     HIP_TRY(err, WAX_HIP_ERR_INTERNAL, "mirror8_keys");
     return WAX_HIP_OK;
 }
+
+// Diagnostic for tests/test_mirror_gap_gpu.py: the mirror finish's choice of its MIRROR_KP approximate candidates, both ways, on lists
+// the caller makes up (launch_mirror_select_probe). No engine, no product path.
+int wax_hip_mirror_select_probe(const int64_t* lists, uint32_t n_lists, int64_t* out_selected, int64_t* out_merged, int32_t* out_gathered) {
+    if (!lists || !out_selected || !out_merged || !out_gathered) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_lists < 1 || n_lists > (uint32_t)SCAN_KWAY_MERGE_GRID) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror_select_probe: 1 to 512 lists");
+    const size_t in_bytes = (size_t)n_lists * MIRROR_KP * sizeof(int64_t), out_bytes = 2 * (size_t)MIRROR_KP * sizeof(int64_t);
+    char* d = nullptr;
+    HIP_TRY(hipMalloc(&d, in_bytes + out_bytes + sizeof(int)), WAX_HIP_ERR_INTERNAL, "mirror_select_probe allocation");
+    int64_t* d_out = reinterpret_cast<int64_t*>(d + in_bytes);
+    int* d_gathered = reinterpret_cast<int*>(d + in_bytes + out_bytes);
+    int64_t host_out[2 * MIRROR_KP];
+    int gathered = 0;
+    hipError_t err = hipMemcpy(d, lists, in_bytes, hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = launch_mirror_select_probe(reinterpret_cast<const int64_t*>(d), (int)n_lists, d_out, d_gathered, nullptr);
+    if (err == hipSuccess) err = hipMemcpy(host_out, d_out, out_bytes, hipMemcpyDeviceToHost);
+    if (err == hipSuccess) err = hipMemcpy(&gathered, d_gathered, sizeof(int), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    HIP_TRY(err, WAX_HIP_ERR_INTERNAL, "mirror_select_probe");
+    std::memcpy(out_selected, host_out, out_bytes / 2);
+    std::memcpy(out_merged, host_out + MIRROR_KP, out_bytes / 2);
+    *out_gathered = gathered;
+    return WAX_HIP_OK;
+}
