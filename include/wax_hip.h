@@ -400,6 +400,32 @@ int wax_hip_search_predicate(wax_hip_engine* e, const float* query, uint32_t dim
                              int has_allow, const uint64_t* allow_frame_ids, uint64_t n_allow,
                              int has_min_score, float min_score, const wax_hip_row_predicate* pred,
                              uint64_t* out_ids, float* out_scores, uint32_t out_capacity, uint32_t* out_count);
+/* passesFrameFilter (UnifiedSearch.swift:1241-1258) as a PRE-filter on a TICKET: wax_hip_search_predicate without an allow-list, in
+ * the pipelined form of wax_hip_search_submit. The ticket is collected by wax_hip_search_collect (one ticket namespace) and what it
+ * returns equals, bit for bit, wax_hip_search_predicate(e, query, dims, top_k, 0, NULL, 0, has_min_score, min_score, pred, ...):
+ * ids, scores, count, ties in ascending row order. Like every ticket it holds the engine's shared lock until it is collected; a
+ * writer on a thread that holds one is refused. Routing at submit ("Predicate tickets"): NULL arguments and a dimension
+ * mismatch are refused as wax_hip_search_predicate refuses them; a predicate with no bound and no deny bit makes the call
+ * wax_hip_search_submit, with the cut applied at collect; an empty engine gives an empty ticket; a store on which attributes were
+ * never set decides the predicate on the host (an ordinary ticket, or one of count 0 without device work). Otherwise the ticket
+ * RIDES a pass over the 8-bit code mirror under a row bitmap — on a single-device engine, where "predicate_mirror" and "mirror_bits"
+ * (and its breaker) admit top_k, and one of the engine's four bitmap entries is free or already holds this predicate for the store
+ * as it is — parked, filled and launched like an unfiltered mirror ticket ("mirror_share", "mirror_fill") and in the same sets: a
+ * set with a masked member runs the masked form of the pass, its unfiltered members beside it. A bitmap is built once per
+ * (predicate, store state) on the launching stream, without a host synchronisation. Every other ticket is DEFERRED: its collect runs
+ * the blocking call's body under the lock the ticket holds (a sharded handle, L2, other dimensions, top_k > 16, "predicate_mirror" 0,
+ * "force_general", no free bitmap entry, a bitmap known to hold 64 rows or fewer). A ticket that rode without its certificate is
+ * answered by that body as well. */
+int wax_hip_search_predicate_submit(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, int has_min_score,
+                                    float min_score, const wax_hip_row_predicate* pred, uint64_t* out_ticket);
+/* What became of the predicate tickets of this engine, in the way of wax_hip_mirror8_snapshot (a read-out, no tuning key): submitted
+ * (non-empty predicates), rode (launched in a masked pass), masked_passes, certified, fallbacks (rode, answered by the blocking
+ * body), deferred, host_decided, bitmap_builds, bitmap_hits (tickets that found their bitmap in an entry). A sharded handle reports
+ * its own `submitted` and `deferred`; the other fields are 0 there. */
+typedef struct wax_hip_predicate_ticket_stats_t {
+    uint64_t submitted, rode, masked_passes, certified, fallbacks, deferred, host_decided, bitmap_builds, bitmap_hits;
+} wax_hip_predicate_ticket_stats_t;
+int wax_hip_predicate_ticket_stats(wax_hip_engine* e, wax_hip_predicate_ticket_stats_t* out);
 /* wax_hip_search_many with a row predicate and a score cut PER PAIR — what a host with one store per user needs, since no Wax query
  * is unfiltered (the default FrameFilter() already drops deleted, superseded and surrogate frames). preds: n entries, or NULL = no
  * pair has one; min_scores: n entries, or NULL = no cut (NaN = no cut for that pair). Row i equals, bit for bit,

@@ -8,7 +8,14 @@ searchFiltered with the allow-list of the passing ids — and, in the same alter
 the unfiltered lone bf16 mirror pass ("scan_mirror" 2, "mirror_bits" 16); "mirror_share" is 0 throughout. It prints one JSON line
 and, with --out, writes the same object to a file: the route table with each form's run-to-run spread (the interquartile range of
 its alternated times), the crossover of the random mask (the smallest measured fraction from which the masked f32 scan is faster than
-the gather), the same for the mirror form, masked / unfiltered and mirror / masked at 15/16, and the bytes both scans read."""
+the gather), the same for the mirror form, masked / unfiltered and mirror / masked at 15/16, and the bytes both scans read.
+
+--pipelined N (default 4; 0 skips it) adds the pipelined legs under the product's own settings ("scan_mirror" 1, "mirror_share" 1,
+"mirror_bits" 0, "predicate_route" 0, "predicate_mirror" 1): for a random mask passing 15/16, one passing 1/2 and a contiguous range
+of 1/16 of the rows, the blocking predicate query (median of --reps calls) beside submitFiltered tickets with N in flight (time per
+query over --pipelined-queries queries, and what predicateTicketStats() says became of them), and the unfiltered submit / collect
+pair with N in flight. --skip-routes leaves the route table out (the pipelined legs alone, for alternated A/B runs at 10M rows). A
+library without the ticket entry point reports null for the pipelined predicate legs."""
 import argparse
 import json
 import os
@@ -28,6 +35,9 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--rows", type=int, default=1_000_000)
 ap.add_argument("--reps", type=int, default=15)
 ap.add_argument("--out", default=None)
+ap.add_argument("--pipelined", type=int, default=4, help="queries in flight of the pipelined legs (0: no such legs)")
+ap.add_argument("--pipelined-queries", type=int, default=400)
+ap.add_argument("--skip-routes", action="store_true", help="leave the route table out")
 args = ap.parse_args()
 
 torch.cuda.set_device(0)
@@ -91,8 +101,73 @@ def unfiltered(scan_mirror):
     return f
 
 
+def pipelined_legs(depth, n):
+    """The blocking predicate query, predicate tickets with `depth` in flight and unfiltered tickets with `depth` in flight."""
+    from collections import deque
+    for key, value in (("scan_mirror", 1), ("mirror_share", 1), ("mirror_bits", 0), ("predicate_route", 0), ("predicate_mirror", 1)):
+        eng.setTuning(key, value)
+    qs = bench.unit_queries(64, dims)
+
+    def pipeline(submit):
+        """ms per query of n queries with `depth` in flight, after a warm-up of 8 * depth"""
+        inflight = deque()
+        t0 = 0.0
+        for i in range(-8 * depth, n):
+            if i == 0:
+                while inflight:
+                    eng.collect(inflight.popleft(), k)
+                t0 = time.perf_counter()
+            if len(inflight) == depth:
+                got = eng.collect(inflight.popleft(), k)
+                assert len(got[0]) == k
+            inflight.append(submit(qs[i % 64]))
+        while inflight:
+            eng.collect(inflight.popleft(), k)
+        return (time.perf_counter() - t0) * 1e3 / n
+
+    legs = {"in_flight": depth, "queries": n, "masks": []}
+    span = rows // 16
+    lo = min(rows // 7, rows - span)
+    for name, kw in (("random 15/16", {"denyFlags": 1 << (8 + FRACS.index((15, 16)))}), ("random 1/2", {"denyFlags": 1 << (8 + FRACS.index((1, 2)))}),
+                     ("contiguous 1/16", {"timeRange": (lo, lo + span)})):
+        eng.searchFiltered(qs[0], k, **kw)
+        times = [timed(lambda i=i: eng.searchFiltered(qs[i % 64], k, **kw)) for i in range(max(args.reps, 5))]
+        quart = statistics.quantiles(times, n=4)
+        leg = {"mask": name, "blocking_ms": round(statistics.median(times), 4), "blocking_iqr_ms": round(quart[2] - quart[0], 4)}
+        try:
+            before = eng.predicateTicketStats()
+            ms = pipeline(lambda v: eng.submitFiltered(v, k, **kw))
+            after = eng.predicateTicketStats()
+            leg.update({"pipelined_ms_per_query": round(ms, 4), "pipelined_over_blocking_rate": round(leg["blocking_ms"] / ms, 3),
+                        "tickets": {key: after[key] - before[key] for key in after}})
+        except wax.WaxError:
+            leg.update({"pipelined_ms_per_query": None, "pipelined_over_blocking_rate": None, "tickets": None})
+        legs["masks"].append(leg)
+        print(json.dumps(leg), file=sys.stderr, flush=True)
+    ms = pipeline(lambda v: eng.submit(v, k))
+    legs["unfiltered_pipelined_ms_per_query"] = round(ms, 4)
+    legs["unfiltered_pipelined_qps"] = round(1e3 / ms, 1)
+    return legs
+
+
 MIRROR_COUNTERS = ("predicate_mirror_scans", "predicate_mirror_fallbacks", "predicate_mirror_unavailable")
 out = {"rows": rows, "dims": dims, "topk": k, "reps": args.reps, "table": []}
+
+
+def emit(doc):
+    print(json.dumps(doc))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+    eng.close()
+
+
+if args.skip_routes:
+    out["pipelined"] = pipelined_legs(args.pipelined, args.pipelined_queries) if args.pipelined > 0 else None
+    emit(out)
+    sys.exit(0)
 for a, b in [(1, 64), (1, 16), (1, 8), (1, 2), (15, 16)]:     # 1/16: the contiguous range only (what the chunk skip is for)
     span = rows * a // b
     lo = min(rows // 7, rows - span)
@@ -151,10 +226,6 @@ out["random_mask_mirror_crossover_pass"] = cross
 at = [r for r in rand if r["pass"] == "15/16"][0]
 out["mirror_over_masked_at_15_16"] = at["mirror_over_masked"]
 out["mirror_faster_at_15_16_beyond_spread"] = bool(at["masked_ms"] - at["masked_mirror_ms"] > max(at["masked_iqr_ms"], at["masked_mirror_iqr_ms"]))
-print(json.dumps(out))
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
-eng.close()
+if args.pipelined > 0:
+    out["pipelined"] = pipelined_legs(args.pipelined, args.pipelined_queries)
+emit(out)

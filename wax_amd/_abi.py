@@ -68,6 +68,12 @@ class RowPredicate(ctypes.Structure):
                 ("before", ctypes.c_int64), ("deny_flags", ctypes.c_uint32)]
 
 
+class PredicateTicketStats(ctypes.Structure):
+    """wax_hip_predicate_ticket_stats_t (include/wax_hip.h)."""
+    _fields_ = [(name, ctypes.c_uint64) for name in ("submitted", "rode", "masked_passes", "certified", "fallbacks", "deferred",
+                                                     "host_decided", "bitmap_builds", "bitmap_hits")]
+
+
 # wax_hip_set_attributes flag bits (WAX_HIP_FLAG_*); bits 8..31 are the caller's
 FLAG_DELETED = 0x1
 FLAG_SUPERSEDED = 0x2
@@ -125,6 +131,9 @@ SIGNATURES: Dict[str, tuple] = {
     "wax_hip_search_predicate": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int, _u64p,
                                                 ctypes.c_uint64, ctypes.c_int, ctypes.c_float, ctypes.POINTER(RowPredicate),
                                                 _u64p, _f32p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    "wax_hip_search_predicate_submit": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int, ctypes.c_float,
+                                                       ctypes.POINTER(RowPredicate), _u64p]),
+    "wax_hip_predicate_ticket_stats": (ctypes.c_int, [_engine_p, ctypes.POINTER(PredicateTicketStats)]),
     "wax_hip_merge_batch_hits_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                        ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
     "wax_hip_add_batch_device": (ctypes.c_int, [_engine_p, _u64p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32]),

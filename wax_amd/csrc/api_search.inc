@@ -1,5 +1,5 @@
 // api_search.inc — part of engine.hip's translation unit (included there; not compiled alone).
-// C ABI: search_submit / search_collect / search, result capacity
+// C ABI: search_submit / search_collect / search, result capacity; the routing of predicate tickets (wax_hip_search_predicate_submit, filter_host.inc)
 
 // ---- search ---------------------------------------------------------------
 
@@ -7,16 +7,35 @@
 // tickets, which must collect one instead of waiting (two such callers would starve each other).
 // caller_locked: the caller already holds the engine's shared lock and has flushed pending rows (wax_hip_search_many runs one
 // snapshot over many engines): the ticket then owns no lock — it is collected with caller_locked too, inside the same scope.
+// x: what wax_hip_search_predicate_submit adds to the ticket (TicketExtras, engine_types.inc)
 static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, uint64_t* out_ticket,
-                       bool try_only, bool caller_locked = false);
+                       bool try_only, bool caller_locked = false, const TicketExtras* x = nullptr);
 
 int wax_hip_search_submit(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, uint64_t* out_ticket) {
     if (e && e->sh) return sh_submit(e, query, dims, top_k, out_ticket);
     return submit_impl(e, query, dims, top_k, out_ticket, false);
 }
 
+// filter_host.inc
+static inline bool predicate_passes(const wax_hip_row_predicate& p, int64_t ts, uint32_t fl);
+static bool predicate_uses_mirror(wax_hip_engine* e, int kpad);
+static int search_rows_locked(wax_hip_engine* e, const float* query, uint32_t dims, int kpad, int has_allow, const uint64_t* allow_frame_ids,
+                              uint64_t n_allow, const wax_hip_row_predicate* pred, uint64_t* out_ids, float* out_scores,
+                              uint32_t out_capacity, uint32_t* out_n);
+static inline void apply_min_score(float cut, uint64_t* ids, float* scores, uint32_t* n);
+
+// what every ticket starts from
+static void reset_ticket_extras(Slot* s, const TicketExtras* x, int32_t top_k) {
+    s->has_cut = x != nullptr && x->has_cut != 0;
+    s->cut = x != nullptr ? x->cut : 0.f;
+    s->has_pred = false;
+    s->pred_deferred = false;
+    s->pred_entry = -1;
+    s->top_k = top_k;
+}
+
 static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, uint64_t* out_ticket,
-                       bool try_only, bool caller_locked) {
+                       bool try_only, bool caller_locked, const TicketExtras* x) {
     if (!e || !out_ticket) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine/ticket is null");
     DeviceGuard g(e->device);
     if (!caller_locked) {
@@ -32,6 +51,7 @@ static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int
             rc = acquire_slot(e, &s, try_only, holding(e) > 0);
             if (rc != WAX_HIP_OK) break;
             s->k_eff = 0; s->timed = false; s->shared = false; s->listed = false;
+            reset_ticket_extras(s, x, top_k);
             break;
         }
         if (dims != e->dims || !query) {                   // validate (:449, 830-833)
@@ -59,8 +79,31 @@ static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int
         s->shared = false;
         s->listed = false;
         s->park_rc = WAX_HIP_OK;
-        if (scan_uses_mirror(e, k_eff)) {
-            s->want8 = mirror8_take(e, k_eff);
+        reset_ticket_extras(s, x, top_k);
+        // ---- a ticket with a row predicate: decided on the host, riding a masked pass over the code mirror, or deferred ----
+        bool ride = false;
+        if (x != nullptr && x->pred != nullptr) {
+            e->pt_submitted++;
+            if (e->attr_ts.empty()) {
+                // a store on which attributes were never set reads (0, 0) in every row: every row passes or none does
+                e->pt_host_decided++;
+                if (!predicate_passes(*x->pred, 0, 0u)) { s->k_eff = 0; s->timed = false; break; }   // count 0, no device work
+            } else {
+                s->has_pred = true;
+                s->pred = *x->pred;
+                std::memcpy(s->h_query, query, (size_t)dims * sizeof(float));     // the blocking body's, should it answer at collect
+                s->q_norm = qn;
+                ride = e->force_general.load() == 0 && predicate_uses_mirror(e, k_eff) && mirror8_take(e, k_eff);
+                if (ride) {
+                    s->pred_entry = pred_entry_acquire(e, s->pred);
+                    uint64_t passing = 0, tiles = 0;
+                    ride = s->pred_entry >= 0 && !(pred_entry_counts(e, s->pred_entry, false, &passing, &tiles) && passing <= (uint64_t)MIRROR_KP);
+                }
+                if (!ride) { pred_ticket_defer(e, s); break; }
+            }
+        }
+        if (ride || (!s->has_pred && scan_uses_mirror(e, k_eff))) {
+            s->want8 = ride ? true : mirror8_take(e, k_eff);
             const int64_t share = mirror_share_mode(e, tk_mode);
             std::unique_lock<std::mutex> sg(e->share_mu, std::defer_lock);
             if (share != 0) {
@@ -89,11 +132,18 @@ static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int
                     break;
                 }
             }
-            rc = enqueue_mirror_scan(e, s, query, qn, k_eff, tk_mode, &mirrored, s->want8);
+            if (ride) {
+                // alone and at once: the masked pass of one member (its query is in h_query already)
+                if (!mirror8_ready(e, s->stream, 1)) { pred_ticket_defer(e, s); break; }
+                Slot* one[1] = {s};
+                rc = enqueue_mirror_group(e, one, 1, &mirrored, 1);
+            } else {
+                rc = enqueue_mirror_scan(e, s, query, qn, k_eff, tk_mode, &mirrored, s->want8);
+            }
             if (rc != WAX_HIP_OK) break;
             if (mirrored && share != 0) e->share_last = s->ev_done;   // (recorded just below, still under share_mu)
             if (mirrored) {
-                err = hipEventRecord(s->ev_done, s->stream);
+                err = ride ? hipSuccess : hipEventRecord(s->ev_done, s->stream);   // (the group launch has recorded its members')
                 if (err != hipSuccess) { rc = fail(WAX_HIP_ERR_INTERNAL, std::string("event record: ") + hipGetErrorString(err)); break; }
                 if (share != 0) { s->listed = true; e->share_launched.push_back(s); }
                 break;
@@ -130,7 +180,7 @@ static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int
         }
     } while (0);
     if (rc != WAX_HIP_OK) {
-        if (s) { (void)hipStreamSynchronize(s->stream); release_slot(e, s); }
+        if (s) { (void)hipStreamSynchronize(s->stream); pred_entry_release(e, s->pred_entry); s->pred_entry = -1; release_slot(e, s); }
         if (!caller_locked) e->lock.unlock_shared();
         return rc;
     }
@@ -194,7 +244,18 @@ static int collect_impl(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, f
         }
         if (s->shared && s->park_rc != WAX_HIP_OK) rc = fail(s->park_rc, s->park_err);
     }
-    if (s->k_eff > 0 && rc == WAX_HIP_OK) {
+    // a predicate ticket that did not ride, or rode without a certificate: the blocking body, under the lock the ticket holds
+    auto blocking_body = [&]() -> int {
+        if ((!out_ids || !out_scores) && capacity > 0) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "output arrays are null");
+        return search_rows_locked(e, s->h_query, e->dims, clamp_topk(s->top_k), 0, nullptr, 0, &s->pred, out_ids, out_scores, capacity, out_count);
+    };
+    bool deferred = false;
+    if (s->has_pred) {
+        if (s->shared) { std::unique_lock<std::mutex> sg(e->share_mu); deferred = s->pred_deferred; }   // (the set's launch may have written it)
+        else deferred = s->pred_deferred;
+        if (deferred && rc == WAX_HIP_OK) rc = out_hits ? fail(WAX_HIP_ERR_INTERNAL, "a predicate ticket has no raw-hit form") : blocking_body();
+    }
+    if (s->k_eff > 0 && rc == WAX_HIP_OK && !deferred) {
         hipError_t err = hipSuccess;
         if (s->flag_wait) {
             // poll the completion word the kernel's last workgroup publishes behind the hits (system-scope release). The stream is
@@ -226,9 +287,22 @@ static int collect_impl(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, f
         } else {
             err = hipEventSynchronize(s->ev_done);   // commandBuffer completion (:577-582); later queries on the stream keep running
         }
-        const bool certified = err == hipSuccess && s->mirror && __atomic_load_n(slot_cert_word(s->h_done), __ATOMIC_ACQUIRE) == 1u;
-        if (err == hipSuccess && s->mirror && s->mirror8) mirror8_note_result(e, certified);
-        if (err == hipSuccess && s->mirror && !certified) {
+        bool certified = err == hipSuccess && s->mirror && __atomic_load_n(slot_cert_word(s->h_done), __ATOMIC_ACQUIRE) == 1u;
+        bool tells = true;                 // the certificate says something about the corpus: it feeds the "mirror_bits" breaker
+        if (err == hipSuccess && s->mirror && s->has_pred) {
+            // a bitmap of MIRROR_KP or fewer passing rows never certifies (the blocking call does not take the mirror there either)
+            uint64_t passing = 0, tiles = 0;
+            if (!pred_entry_counts(e, s->pred_entry, true, &passing, &tiles) || passing <= (uint64_t)MIRROR_KP) { certified = false; tells = false; }
+            if (certified) { e->pt_certified++; e->st_predicate_searches++; }
+        }
+        if (err == hipSuccess && s->mirror && s->mirror8 && tells) mirror8_note_result(e, certified);
+        if (err == hipSuccess && s->mirror && !certified && s->has_pred) {
+            e->pt_fallbacks++;
+            e->st_mirror_fallbacks++;
+            if (s->mirror8) e->st_mirror8_fallbacks++;
+            rc = out_hits ? fail(WAX_HIP_ERR_INTERNAL, "a predicate ticket has no raw-hit form") : blocking_body();
+            deferred = true;               // answered: nothing below converts hits
+        } else if (err == hipSuccess && s->mirror && !certified) {
             // the mirror's certificate failed (ties, a clustered store, zero / NaN rows or query): this query is re-run on the f32 scan,
             // on the same slot, and that answer is returned (the batched path's "uncertified queries are re-run exactly at collect")
             e->st_mirror_fallbacks++;
@@ -249,7 +323,7 @@ static int collect_impl(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, f
             (void)hipStreamSynchronize(s->stream);
             (void)hipGetLastError();
             g_last_error = keep;
-        } else {
+        } else if (!deferred) {
             if (s->timed) {
                 float ms = 0.f;
                 if (s->t_start && s->t_end && hipEventElapsedTime(&ms, s->t_start, s->t_end) == hipSuccess) {
@@ -271,6 +345,9 @@ static int collect_impl(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, f
             }
         }
     }
+    if (rc == WAX_HIP_OK && s->has_cut && !out_hits && out_ids && out_scores) apply_min_score(s->cut, out_ids, out_scores, out_count);
+    pred_entry_release(e, s->pred_entry);
+    s->pred_entry = -1;
     note_collect(e, s);
     release_slot(e, s);
     if (!caller_locked) e->lock.unlock_shared();   // (a ticket submitted with caller_locked never took it)

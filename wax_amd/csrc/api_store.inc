@@ -112,6 +112,10 @@ void wax_hip_engine_destroy(wax_hip_engine* e) {
         for (FilterWork* f : e->filter_all) free_filter_work(f);
         (void)hipFree(e->idhash.d_table);
         (void)hipFree(e->d_attr_ts); (void)hipFree(e->d_attr_flags);
+        for (PredEntry& p : e->pred_entries) {
+            (void)hipFree(p.d_bitmap); (void)hipFree(p.d_counts); (void)hipHostFree(p.h_counts);
+            if (p.built_ev) (void)hipEventDestroy(p.built_ev);
+        }
     }
     (void)hipFree(e->d_store);
     (void)hipFree(e->d_ids);

@@ -38,7 +38,7 @@ using namespace wax;
 //   search_internal.inc    one query -> one scan: which launch form a scan takes and how it is enqueued (`enqueue_scan`), hits -> results (MetalVectorEngine.swift:446-627, VectorMetric.swift:32-43)
 //   batch_host.inc         batched queries, host side: the incremental bf16 mirror and id table, pooled batch workspaces, the one-pass planner, the launch chain (`batch_enqueue`) and the exactness ladder behind it
 //   api_store.inc          C ABI: availability, create / destroy, accessors, reserve / add / add_batch / add_batch_device / apply_put_embeddings / remove / remove_batch
-//   api_search.inc         C ABI: search_submit / search_collect / search, result capacity
+//   api_search.inc         C ABI: search_submit / search_collect / search, result capacity; the routing of predicate tickets
 //   api_batch.inc          C ABI: search_batch[_hits], the device-resident and ticketed batched entry points
 //   api_shard.inc          C ABI: the one-rank-per-GPU entry points (set_row_base, search_shard_device, merge_hits_device, merge_batch_hits_device, hits_to_results)
 //   api_fusion_filter.inc  C ABI: reciprocal-rank fusion

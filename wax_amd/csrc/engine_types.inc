@@ -55,7 +55,10 @@ class RWLock {
         cv_.wait(g, [&] { return !writer_ && readers_ == 0; });
         --writers_waiting_;
         writer_ = true;
+        epoch_.fetch_add(1, std::memory_order_relaxed);   // every writer: what is cached per store state (the predicate tickets' bitmaps) is of an older epoch now
     }
+    // the number of exclusive acquisitions so far: constant while a shared lock is held
+    uint64_t epoch() const { return epoch_.load(std::memory_order_relaxed); }
     void unlock() {
         std::unique_lock<std::mutex> g(m_);
         writer_ = false;
@@ -68,6 +71,7 @@ class RWLock {
     int readers_ = 0;
     int writers_waiting_ = 0;
     bool writer_ = false;
+    std::atomic<uint64_t> epoch_{0};
 };
 
 struct WriteGuard {
@@ -187,6 +191,7 @@ inline uint32_t* partials_ticket(int64_t* d_partials) {
 }
 
 constexpr int kMaxStreams = 4;
+constexpr size_t kPredCounts = 3;        // words of FilterWork::d_pred_counts and PredEntry::d_counts (AttrMaskArgs::counts)
 
 struct Slot {
     int index = 0;
@@ -221,7 +226,36 @@ struct Slot {
     int park_rc = 0;               // what launching it returned (a failed launch surfaces at the ticket's collect)
     std::string park_err;
     std::thread::id owner;         // the submitting thread (its outstanding-ticket count drops at collect, whoever collects)
+    // wax_hip_search_predicate_submit (DESIGN 4.5): the score cut applied at collect; the predicate (normalised, non-empty) of a ticket
+    // that rides a masked pass or is deferred to the blocking body, and the bitmap entry it holds a use of (-1: none). `pred_deferred`
+    // may be set by the launch of the set the ticket was parked in (share_mu), so collect reads it behind that mutex.
+    bool has_cut = false;
+    float cut = 0.f;
+    bool has_pred = false;
+    bool pred_deferred = false;    // answered at collect by the blocking body (search_rows_locked) under the lock the ticket holds
+    wax_hip_row_predicate pred{};
+    int pred_entry = -1;
+    int32_t top_k = 0;             // as the caller gave it (the blocking body clamps it itself)
 };
+
+// A row bitmap of one predicate on one state of the store (wax_hip_engine::pred_entries): what the predicate tickets' masked passes
+// read. Built on the stream of the first pass that needs it, in front of that pass, without a host synchronisation; its passing-row
+// count travels to pinned memory behind the build and is known once `built_ev` has completed.
+struct PredEntry {
+    wax_hip_row_predicate pred{};
+    uint64_t epoch = 0;              // RWLock::epoch() of the store state the bitmap describes
+    bool assigned = false;           // pred / epoch are set
+    bool built = false;              // the build is enqueued (built_ev recorded on build_stream)
+    uint32_t* d_bitmap = nullptr;
+    uint64_t words = 0;              // capacity of d_bitmap
+    uint32_t* d_counts = nullptr;    // [kPredCounts] attr_mask_kernel's: passing rows, 16-row tiles that hold one
+    uint32_t* h_counts = nullptr;    // pinned [kPredCounts]
+    hipEvent_t built_ev = nullptr;
+    hipStream_t build_stream = nullptr;
+    int users = 0;                   // parked or uncollected tickets: an entry in use is never evicted or rebuilt
+    uint64_t last_use = 0;
+};
+constexpr int kPredEntries = 4;
 
 // Workspace of one wax_hip_search_filtered call: pooled (filter_max per engine, allocated on demand) with its own stream,
 // so filtered searches run concurrently with each other and with every other read entry point.
@@ -269,7 +303,6 @@ struct FilterWork {
     wax_hip_hit* h_mirror_out = nullptr; // pinned [MIRROR_MAX_K + 1]
 };
 
-constexpr size_t kPredCounts = 3;        // words of FilterWork::d_pred_counts (AttrMaskArgs::counts)
 void free_filter_work(FilterWork* f);
 
 // id -> row table in HBM (filter.hip): built at the first long allow-list, rebuilt lazily after a mutation.
@@ -600,6 +633,13 @@ struct wax_hip_engine {
     // rows while "scan_mirror" != 0, 2 = every store, 0 = never
     std::atomic<int64_t> predicate_mirror{1};
     std::atomic<uint64_t> st_predicate_mirror_scans{0}, st_predicate_mirror_fallbacks{0}, st_predicate_mirror_unavailable{0};
+    // Predicate tickets (wax_hip_search_predicate_submit; DESIGN 4.5): the bitmap entries (pred_mu) and the counters of
+    // wax_hip_predicate_ticket_stats. A sharded handle keeps its own pt_submitted / pt_deferred here and nothing else.
+    std::mutex pred_mu;
+    PredEntry pred_entries[kPredEntries];
+    uint64_t pred_tick = 0;
+    std::atomic<uint64_t> pt_submitted{0}, pt_rode{0}, pt_masked_passes{0}, pt_certified{0}, pt_fallbacks{0}, pt_deferred{0}, pt_host_decided{0},
+        pt_bitmap_builds{0}, pt_bitmap_hits{0};
     std::atomic<int64_t> filter_device_min{4096}; // allow-lists at least this long are resolved on the device
     std::atomic<uint64_t> st_filter_device{0};    // filtered searches whose allow-list was resolved on the device
     std::atomic<int64_t> filter_batch{1};         // wax_hip_search_batch_filtered: 1 = one gather pass for all lists, 0 = the per-query loop
@@ -689,7 +729,14 @@ int sh_add_batch_device(wax_hip_engine* e, const uint64_t* frame_ids, const floa
 int sh_remove(wax_hip_engine* e, uint64_t frame_id);
 int sh_remove_batch(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, uint64_t* out_removed);
 int sh_reserve(wax_hip_engine* e, uint64_t rows);
-int sh_submit(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, uint64_t* out_ticket);
+// What wax_hip_search_predicate_submit adds to a ticket: the score cut its collect applies and, if not null, its row predicate —
+// normalised and not empty (DESIGN 4.5, "Predicate tickets").
+struct TicketExtras {
+    int has_cut;
+    float cut;
+    const wax_hip_row_predicate* pred;
+};
+int sh_submit(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, uint64_t* out_ticket, const TicketExtras* x = nullptr);
 int sh_collect(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, float* out_scores, uint32_t capacity, uint32_t* out_count);
 int sh_search_batch_hits(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k, wax_hip_hit* out_hits,
                          uint32_t stride, uint32_t* out_counts);
@@ -707,7 +754,7 @@ int sh_set_attributes(wax_hip_engine* e, const uint64_t* frame_ids, const int64_
 int sh_get_attributes(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, int64_t* out_ts, uint32_t* out_flags, uint8_t* out_found);
 int sh_search_predicate(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, int has_allow, const uint64_t* allow,
                         uint64_t n_allow, int has_min, float min_score, const wax_hip_row_predicate* pred, uint64_t* out_ids,
-                        float* out_scores, uint32_t capacity, uint32_t* out_count);
+                        float* out_scores, uint32_t capacity, uint32_t* out_count, bool caller_locked = false);
 int sh_serialize(wax_hip_engine* e, uint8_t** out_bytes, size_t* out_len);
 int sh_deserialize(wax_hip_engine* e, const uint8_t* data, size_t len);
 void sh_destroy(wax_hip_engine* e);

@@ -1,6 +1,7 @@
 // filter_host.inc — part of engine.hip's translation unit (included there; not compiled alone).
 // C ABI: the filtered searches, host side (SURVEY 8f-4; DESIGN 4.5; passesFrameFilter, UnifiedSearch.swift:1241-1258) — one query with an
-// allow-list and / or a row predicate (one locked body, built from the steps below), and the batched form (a list, a predicate and a
+// allow-list and / or a row predicate (one locked body, built from the steps below), the predicate search as a ticket
+// (wax_hip_search_predicate_submit: the routing is submit_impl's, api_search.inc), and the batched form (a list, a predicate and a
 // cut per query)
 
 // ---- the steps --------------------------------------------------------------------
@@ -342,6 +343,30 @@ int wax_hip_search_predicate(wax_hip_engine* e, const float* query, uint32_t dim
                                        out_capacity, out_count);
     return search_filtered_entry(e, query, dims, top_k, has_allow, allow_frame_ids, n_allow, has_min_score, min_score, pred, out_ids, out_scores,
                                  out_capacity, out_count);
+}
+
+// ---- predicate tickets (DESIGN 4.5) -------------------------------------------
+
+// wax_hip_search_predicate without an allow-list, as a ticket of wax_hip_search_collect. The routing is submit_impl's
+// (api_search.inc): decided on the host where the store has no attributes, riding a masked pass over the code mirror where
+// the rules of both ("predicate_mirror", "mirror_bits") and a free bitmap entry allow it, deferred to the blocking body otherwise.
+int wax_hip_search_predicate_submit(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, int has_min_score, float min_score,
+                                    const wax_hip_row_predicate* pred, uint64_t* out_ticket) {
+    if (!e) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine is null");
+    if (!query || !out_ticket) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (dims != e->dims) return fail(WAX_HIP_ERR_DIM_MISMATCH, dim_mismatch_msg(e->dims, dims));
+    const wax_hip_row_predicate np = normalised_predicate(pred);
+    const TicketExtras x{has_min_score, min_score, predicate_is_empty(&np) ? nullptr : &np};   // empty: wax_hip_search_submit and the cut
+    if (e->sh) return sh_submit(e, query, dims, top_k, out_ticket, &x);
+    return submit_impl(e, query, dims, top_k, out_ticket, false, false, &x);
+}
+
+int wax_hip_predicate_ticket_stats(wax_hip_engine* e, wax_hip_predicate_ticket_stats_t* out) {
+    if (!e || !out) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine/out is null");
+    out->submitted = e->pt_submitted.load(); out->rode = e->pt_rode.load(); out->masked_passes = e->pt_masked_passes.load();
+    out->certified = e->pt_certified.load(); out->fallbacks = e->pt_fallbacks.load(); out->deferred = e->pt_deferred.load();
+    out->host_decided = e->pt_host_decided.load(); out->bitmap_builds = e->pt_bitmap_builds.load(); out->bitmap_hits = e->pt_bitmap_hits.load();
+    return WAX_HIP_OK;
 }
 
 // ---- batched filtered search ------------------------------------------------

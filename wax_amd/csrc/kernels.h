@@ -151,6 +151,7 @@ struct MirrorMember {
     int64_t* partials;              // [grid][MIRROR_KP]
     wax_hip_hit* hits;              // [kpad] (pinned host memory)
     uint32_t* certified;            // (pinned host memory)
+    const uint32_t* bitmap;         // the masked 8-bit pass: the rows this member may be offered (predicate.hip's bitmap), nullptr = every row; every other kernel ignores it
     float q_norm;
     int32_t k, kpad;
 };
@@ -196,6 +197,11 @@ hipError_t launch_mirror8_scan(const MirrorScanArgs& args, const unsigned char* 
                                int grid_cap, hipStream_t st);
 hipError_t launch_mirror8_group(const MirrorGroupArgs& args, const unsigned char* codes, const float* meta, int nq, int metric,
                                 int grid_cap, hipStream_t st);
+// The pass of 1 <= nq <= MIRROR_MAX_NQ members of which at least one has a MirrorMember::bitmap (every word written, bits of rows >=
+// n_rows clear): mirror8_scan_masked_group_kernel skips the 16-row tiles no member may be offered a row of and offers every member only
+// its own passing rows; the finish launch is launch_mirror8_group's. A member whose bitmap holds MIRROR_KP or fewer rows is never certified.
+hipError_t launch_mirror8_group_masked(const MirrorGroupArgs& args, const unsigned char* codes, const float* meta, int nq, int metric,
+                                       int grid_cap, hipStream_t st);
 // The lone pass's key of every row (mirror8_keys_kernel: the scan's body, writing keys_out[n_rows] instead of keeping lists). A diagnostic:
 // args.partials, hits, certified, store, ids and max_bits are not used.
 hipError_t launch_mirror8_keys(const MirrorScanArgs& args, const unsigned char* codes, const float* meta, const float* query, int metric,

@@ -130,7 +130,13 @@ __device__ __forceinline__ float code8_sum(float pa, float pb, float pc) {
 // The integer sums are exact and the float epilogue is one function of (S, delta, meta, norm), so a row's key for a query is the same
 // alone and in a pass of 2, 3 or 4. WRITE_KEYS (mirror8_keys_kernel, a diagnostic): every key is written to keys_out[row] and no
 // list is kept.
-template <int DIMS, int METRIC, int NQ, bool WRITE_KEYS, class QUERIES>
+// MASKED (the predicate tickets' pass): every member may carry a row bitmap (qs.bitmap(i); predicate.hip's: every word
+// written, bits of rows >= n clear; null = every row may be offered). A tile's 16 bits are half a word — tile c is half c & 1 of
+// word c >> 1 — and every lane reads the word of ITS query (one address per quad column group, the dead columns read 0), one
+// iteration ahead like mirror_pass. A tile whose bits are zero for every live member is skipped before its loads and make_room (the
+// ballot makes the test wave-uniform); otherwise a lane's key is offered only where bit 4 kg + plane of its own query is set. The
+// sums and the epilogue do not see the bitmap: a row's key is what it is unmasked.
+template <int DIMS, int METRIC, int NQ, bool WRITE_KEYS, bool MASKED, class QUERIES>
 __device__ __forceinline__ void code8_pass(const unsigned char* __restrict__ codes, const f32x2* __restrict__ sides, const MirrorScanArgs& a,
                                            const QUERIES& qs, float* __restrict__ keys_out, int64_t* lds) {
     using T = Code8Tiles<DIMS>;
@@ -147,11 +153,13 @@ __device__ __forceinline__ void code8_pass(const unsigned char* __restrict__ cod
     // this lane's query: delta, the norm, and the digits of its plane at the lane's k-slices
     float delta = 0.f, qn = 0.f;
     const float* mine = reinterpret_cast<const float*>(qs.floats(0));
+    const uint32_t* my_bitmap = nullptr;
     WaveTopK<MIRROR_CAP> tk[NQ];
 #pragma unroll
     for (int i = 0; i < NQ; ++i) {
         const float di = query_delta<DIMS>(qs.floats(i), lane);
         if (myq == i) { delta = di; qn = qs.norm(i); mine = reinterpret_cast<const float*>(qs.floats(i)); }
+        if constexpr (MASKED) { if (myq == i) my_bitmap = qs.bitmap(i); }
         if constexpr (!WRITE_KEYS) tk[i].init(lds + i * MIRROR_PASS_LDS + wave * MIRROR_CAP, MIRROR_KP);
     }
     // cosine: mirror rows are unit vectors (or zero), so sim = s / ||q||; the rule for a null query is the f32 scan's
@@ -166,7 +174,17 @@ __device__ __forceinline__ void code8_pass(const unsigned char* __restrict__ cod
     const uint32_t nwaves = gridDim.x * SCAN_WAVES;
     const u32x4* __restrict__ rows = reinterpret_cast<const u32x4*>(codes);
 
+    // the word of this lane's query that holds tile c's bits (c < nchunks: row 16 c < n, so word c >> 1 exists)
+    auto tile_word = [&](uint32_t c) -> uint32_t { return !live ? 0u : my_bitmap == nullptr ? 0xffffffffu : my_bitmap[c >> 1]; };
+    uint32_t word = 0u, bits = 0xffffu;
+    if constexpr (MASKED) word = gwave < nchunks ? tile_word(gwave) : 0u;   // one iteration ahead
     for (uint32_t chunk = gwave; chunk < nchunks; chunk += nwaves) {
+        if constexpr (MASKED) {
+            bits = (word >> ((chunk & 1u) * 16u)) & 0xffffu;
+            const uint32_t next = chunk + nwaves;
+            if (next < nchunks) word = tile_word(next);
+            if (__ballot(bits != 0u) == 0ull) continue;          // wave-uniform: no member may be offered a row of the tile, so none is loaded
+        }
         const uint32_t ra = chunk * TILE + col;                  // the row this lane loads codes of
         const uint32_t r = chunk * TILE + 4 * kg + plane;        // the row this lane will hold the key of
         const u32x4* p = rows + (size_t)(ra < n ? ra : n - 1) * (DIMS / 16) + kg;   // clamp: tail lanes re-read the last row
@@ -192,7 +210,8 @@ __device__ __forceinline__ void code8_pass(const unsigned char* __restrict__ cod
             S = plane == reg ? Sr : S;
         }
         const float d = code8_key<METRIC>(S, delta, side, inv_qn, qn);
-        const bool offer = live && r < n;
+        bool offer = live && r < n;
+        if constexpr (MASKED) offer = offer && ((bits >> (uint32_t)(4 * kg + plane)) & 1u) != 0u;
         if constexpr (WRITE_KEYS) {
             if (offer && myq == 0) keys_out[r] = d + 0.0f;
         } else {
@@ -269,20 +288,27 @@ struct Mirror8Slack {
 template <int DIMS, int METRIC>
 __global__ __launch_bounds__(SCAN_THREADS, 2) void mirror8_scan_kernel(Mirror8ScanArgsQ<DIMS> aq) {
     __shared__ int64_t lds[MIRROR_PASS_LDS];
-    code8_pass<DIMS, METRIC, 1, false>(aq.codes, reinterpret_cast<const f32x2*>(aq.meta), aq.a, LoneQuery<Mirror8ScanArgsQ<DIMS>>{aq.a}, nullptr, lds);
+    code8_pass<DIMS, METRIC, 1, false, false>(aq.codes, reinterpret_cast<const f32x2*>(aq.meta), aq.a, LoneQuery<Mirror8ScanArgsQ<DIMS>>{aq.a}, nullptr, lds);
 }
 
 template <int DIMS, int METRIC, int NQ>
 __global__ __launch_bounds__(SCAN_THREADS, 2) void mirror8_scan_group_kernel(Mirror8GroupArgs ga) {
     static_assert(NQ >= 2, "a lone query has mirror8_scan_kernel");
     __shared__ int64_t lds[NQ * MIRROR_PASS_LDS];
-    code8_pass<DIMS, METRIC, NQ, false>(ga.codes, reinterpret_cast<const f32x2*>(ga.meta), ga.g.a, MemberQueries{ga.g.m}, nullptr, lds);
+    code8_pass<DIMS, METRIC, NQ, false, false>(ga.codes, reinterpret_cast<const f32x2*>(ga.meta), ga.g.a, MemberQueries{ga.g.m}, nullptr, lds);
+}
+
+// the pass of 1 .. 4 members of which at least one carries a row bitmap (MirrorMember::bitmap): the predicate tickets' pass
+template <int DIMS, int METRIC, int NQ>
+__global__ __launch_bounds__(SCAN_THREADS, 2) void mirror8_scan_masked_group_kernel(Mirror8GroupArgs ga) {
+    __shared__ int64_t lds[NQ * MIRROR_PASS_LDS];
+    code8_pass<DIMS, METRIC, NQ, false, true>(ga.codes, reinterpret_cast<const f32x2*>(ga.meta), ga.g.a, MemberQueries{ga.g.m}, nullptr, lds);
 }
 
 // the lone pass's keys, every row's (wax_hip_mirror8_keys: a diagnostic)
 template <int DIMS, int METRIC>
 __global__ __launch_bounds__(SCAN_THREADS, 2) void mirror8_keys_kernel(Mirror8ScanArgsQ<DIMS> aq, float* keys_out) {
-    code8_pass<DIMS, METRIC, 1, true>(aq.codes, reinterpret_cast<const f32x2*>(aq.meta), aq.a, LoneQuery<Mirror8ScanArgsQ<DIMS>>{aq.a}, keys_out, nullptr);
+    code8_pass<DIMS, METRIC, 1, true, false>(aq.codes, reinterpret_cast<const f32x2*>(aq.meta), aq.a, LoneQuery<Mirror8ScanArgsQ<DIMS>>{aq.a}, keys_out, nullptr);
 }
 
 template <int DIMS, int METRIC>
@@ -423,6 +449,30 @@ hipError_t launch_mirror8_group(const MirrorGroupArgs& args, const unsigned char
             launch_kernel((mirror8_scan_group_kernel<D, M, decltype(c)::value>), dim3(grid), dim3(SCAN_THREADS), 0, st, ga);
             return launch_finish((mirror8_finish_group_kernel<D, M>), nq, st, ga);
         });
+    });
+}
+
+hipError_t launch_mirror8_group_masked(const MirrorGroupArgs& args, const unsigned char* codes, const float* meta, int nq, int metric,
+                                       int grid_cap, hipStream_t st) {
+    if (!mirror_scan_supported(args.a.dims, metric) || args.a.n_rows == 0 || nq < 1 || nq > MIRROR_MAX_NQ || codes == nullptr || meta == nullptr ||
+        args.a.max_bits == nullptr)
+        return hipErrorInvalidValue;
+    for (int i = 0; i < nq; ++i)
+        if (args.m[i].k < 1 || args.m[i].k > MIRROR8_MAX_K || args.m[i].kpad < args.m[i].k || args.m[i].query == nullptr) return hipErrorInvalidValue;
+    return with_code8_pass(args.a.n_rows, args.a.dims, metric, grid_cap, [&](auto s, auto m, int grid) {
+        constexpr int D = decltype(s)::DIMS, M = decltype(m)::value;
+        Mirror8GroupArgs ga;
+        ga.g = args;
+        ga.g.a.lists = grid;
+        ga.codes = codes;
+        ga.meta = meta;
+        switch (nq) {
+            case 1: launch_kernel((mirror8_scan_masked_group_kernel<D, M, 1>), dim3(grid), dim3(SCAN_THREADS), 0, st, ga); break;
+            case 2: launch_kernel((mirror8_scan_masked_group_kernel<D, M, 2>), dim3(grid), dim3(SCAN_THREADS), 0, st, ga); break;
+            case 3: launch_kernel((mirror8_scan_masked_group_kernel<D, M, 3>), dim3(grid), dim3(SCAN_THREADS), 0, st, ga); break;
+            default: launch_kernel((mirror8_scan_masked_group_kernel<D, M, 4>), dim3(grid), dim3(SCAN_THREADS), 0, st, ga); break;
+        }
+        return launch_finish((mirror8_finish_group_kernel<D, M>), nq, st, ga);
     });
 }
 

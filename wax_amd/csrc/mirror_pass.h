@@ -59,6 +59,7 @@ struct MemberQueries {
     __device__ __forceinline__ const f32x4* floats(int i) const { return reinterpret_cast<const f32x4*>(m[i].query); }
     __device__ __forceinline__ float norm(int i) const { return m[i].q_norm; }
     __device__ __forceinline__ int64_t* partials(int i) const { return m[i].partials; }
+    __device__ __forceinline__ const uint32_t* bitmap(int i) const { return m[i].bitmap; }   // (the masked 8-bit pass only)
 };
 // what the finish of member `m` gets: the shared arguments with the member's own lists, hits, certificate word, norm and k
 __device__ __forceinline__ MirrorScanArgs member_args(MirrorScanArgs a, const MirrorMember& m) {

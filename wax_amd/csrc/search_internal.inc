@@ -407,16 +407,123 @@ static int parked_take_f32(wax_hip_engine* e, Slot* s) {
     return WAX_HIP_OK;
 }
 
-// One pass for `nq` >= 2 parked queries on the first one's stream: one launch that copies the members' queries from their pinned
+// ---- predicate tickets: the bitmap entries (wax_hip_search_predicate_submit; DESIGN 4.5) ---------------------------------------
+}  // namespace
+static int ensure_attrs(wax_hip_engine* e, hipStream_t st, const int64_t** d_ts, const uint32_t** d_flags);   // api_predicate.inc (file scope, like every api_*.inc)
+namespace {
+
+static inline bool same_predicate(const wax_hip_row_predicate& a, const wax_hip_row_predicate& b) {   // both normalised
+    return a.has_after == b.has_after && a.after == b.after && a.has_before == b.has_before && a.before == b.before && a.deny_flags == b.deny_flags;
+}
+
+// A use of the entry of `np` (normalised) on the store as it is (shared lock held: the epoch stands still): the entry that has it, or
+// one without a user — never assigned first, else the least recently used — that the first pass will build. -1: all four are in use.
+static int pred_entry_acquire(wax_hip_engine* e, const wax_hip_row_predicate& np) {
+    std::unique_lock<std::mutex> g(e->pred_mu);
+    const uint64_t epoch = e->lock.epoch();
+    int victim = -1;
+    for (int i = 0; i < kPredEntries; ++i) {
+        PredEntry& p = e->pred_entries[i];
+        if (p.assigned && p.epoch == epoch && same_predicate(p.pred, np)) {
+            p.users++;
+            p.last_use = ++e->pred_tick;
+            e->pt_bitmap_hits++;
+            return i;
+        }
+        if (p.users != 0) continue;
+        if (victim < 0 || (!p.assigned && e->pred_entries[victim].assigned) ||
+            (p.assigned == e->pred_entries[victim].assigned && p.last_use < e->pred_entries[victim].last_use))
+            victim = i;
+    }
+    if (victim < 0) return -1;
+    PredEntry& p = e->pred_entries[victim];
+    p.pred = np; p.epoch = epoch; p.assigned = true; p.built = false; p.users = 1; p.last_use = ++e->pred_tick;
+    return victim;
+}
+
+static void pred_entry_release(wax_hip_engine* e, int idx) {
+    if (idx < 0) return;
+    std::unique_lock<std::mutex> g(e->pred_mu);
+    if (e->pred_entries[idx].users > 0) e->pred_entries[idx].users--;
+}
+
+// The entry's counts — passing rows, 16-row tiles that hold one — once they have reached the host. wait: block until they have (a
+// collect behind the pass finds them there); otherwise false while the build is not enqueued or still running.
+static bool pred_entry_counts(wax_hip_engine* e, int idx, bool wait, uint64_t* passing, uint64_t* tiles) {
+    std::unique_lock<std::mutex> g(e->pred_mu);
+    PredEntry& p = e->pred_entries[idx];
+    if (!p.built) return false;
+    if (wait) { if (hipEventSynchronize(p.built_ev) != hipSuccess) return false; }
+    else if (hipEventQuery(p.built_ev) != hipSuccess) { (void)hipGetLastError(); return false; }
+    *passing = p.h_counts[0];
+    *tiles = p.h_counts[1];
+    return true;
+}
+
+// The entry's bitmap for a pass on `st`: built there, in front of the pass, by the first pass that needs it (attribute columns,
+// attr_mask_kernel, the counts on their way to pinned memory, an event — no host synchronisation); a pass on another stream waits
+// for that event.
+static int pred_entry_prepare(wax_hip_engine* e, int idx, hipStream_t st, const uint32_t** bitmap) {
+    std::unique_lock<std::mutex> g(e->pred_mu);
+    PredEntry& p = e->pred_entries[idx];
+    if (!p.built) {
+        const uint32_t count = (uint32_t)e->count;
+        const uint64_t n_words = ((uint64_t)count + 31) / 32;
+        if (p.words < n_words) {             // (no user but this pass's members: nothing reads the old words)
+            const uint64_t cap = ((e->capacity > e->count ? e->capacity : e->count) + 31) / 32;
+            (void)hipFree(p.d_bitmap);
+            p.d_bitmap = nullptr; p.words = 0;
+            HIP_TRY(hipMalloc(&p.d_bitmap, (size_t)cap * sizeof(uint32_t)), WAX_HIP_ERR_ALLOC, "Failed to allocate row bitmap");
+            p.words = cap;
+        }
+        if (!p.d_counts) HIP_TRY(hipMalloc(&p.d_counts, kPredCounts * sizeof(uint32_t)), WAX_HIP_ERR_ALLOC, "Failed to allocate predicate counters");
+        if (!p.h_counts) HIP_TRY(hipHostMalloc(&p.h_counts, kPredCounts * sizeof(uint32_t), hipHostMallocDefault), WAX_HIP_ERR_ALLOC, "Failed to allocate predicate counters");
+        if (!p.built_ev) HIP_TRY(hipEventCreateWithFlags(&p.built_ev, hipEventDisableTiming), WAX_HIP_ERR_ALLOC, "Failed to allocate event");
+        const int64_t* d_ts = nullptr;
+        const uint32_t* d_fl = nullptr;
+        { const int arc = ensure_attrs(e, st, &d_ts, &d_fl); if (arc != WAX_HIP_OK) return arc; }
+        AttrMaskArgs ma{};
+        ma.ts = d_ts; ma.flags = d_fl; ma.bitmap = p.d_bitmap; ma.counts = p.d_counts; ma.n_rows = count; ma.chunk_rows = 16; ma.chunk_rows2 = 0; ma.and_bitmap = 0;
+        ma.has_after = p.pred.has_after != 0; ma.has_before = p.pred.has_before != 0; ma.after = p.pred.after; ma.before = p.pred.before; ma.deny_flags = p.pred.deny_flags;
+        HIP_TRY(hipMemsetAsync(p.d_counts, 0, kPredCounts * sizeof(uint32_t), st), WAX_HIP_ERR_INTERNAL, "predicate counters");
+        HIP_TRY(launch_attr_mask(ma, st), WAX_HIP_ERR_INTERNAL, "attribute mask launch");
+        HIP_TRY(hipMemcpyAsync(p.h_counts, p.d_counts, kPredCounts * sizeof(uint32_t), hipMemcpyDeviceToHost, st), WAX_HIP_ERR_INTERNAL, "row count download");
+        HIP_TRY(hipEventRecord(p.built_ev, st), WAX_HIP_ERR_INTERNAL, "event record");
+        p.built = true;
+        p.build_stream = st;
+        e->pt_bitmap_builds++;
+    } else if (p.build_stream != st) {
+        HIP_TRY(hipStreamWaitEvent(st, p.built_ev, 0), WAX_HIP_ERR_INTERNAL, "bitmap wait");
+    }
+    *bitmap = p.d_bitmap;
+    return WAX_HIP_OK;
+}
+
+// a parked or just submitted predicate ticket that cannot ride after all: the blocking body answers it at collect
+static void pred_ticket_defer(wax_hip_engine* e, Slot* s) {
+    s->pred_deferred = true;
+    s->mirror = false;
+    s->mirror8 = false;
+    e->pt_deferred++;
+}
+
+// One pass for `nq` parked queries on the first one's stream: one launch that copies the members' queries from their pinned
 // h_query into their d_query (a hipMemcpyAsync per member cost the host as much as a launch each, in the gap in front of the scan),
-// the group scan, one finish workgroup per member, and every member's ev_done behind the finish launch.
-static int enqueue_mirror_group(wax_hip_engine* e, Slot* const* grp, int nq, bool* took) {
+// the group scan, one finish workgroup per member, and every member's ev_done behind the finish launch. nq >= 2 — or a set with a
+// predicate ticket in it, of any size from 1: then the pass is the masked 8-bit one (unmasked members pass a null bitmap), the
+// bitmaps are built or waited for in front of it, and the caller has made sure of the code mirror (use8_hint = 1).
+static int enqueue_mirror_group(wax_hip_engine* e, Slot* const* grp, int nq, bool* took, int use8_hint = -1) {
     *took = false;
     BatchMirror& b = e->batch;
     hipStream_t st = grp[0]->stream;
-    bool use8 = true;                      // one mirror per set: bf16 as soon as one member cannot ride the code mirror (k, breaker, rebuild count)
-    for (int i = 0; i < nq; ++i) use8 = use8 && grp[i]->want8;
-    use8 = use8 && mirror8_ready(e, st, (uint64_t)nq);
+    int n_masked = 0;
+    for (int i = 0; i < nq; ++i) n_masked += grp[i]->has_pred ? 1 : 0;
+    bool use8 = use8_hint >= 0 ? use8_hint != 0 : true;   // one mirror per set: bf16 as soon as one member cannot ride the code mirror (k, breaker, rebuild count)
+    if (use8_hint < 0) {
+        for (int i = 0; i < nq; ++i) use8 = use8 && grp[i]->want8;
+        use8 = use8 && mirror8_ready(e, st, (uint64_t)nq);
+    }
+    if (n_masked != 0 && !use8) return fail(WAX_HIP_ERR_INTERNAL, "a masked pass needs the code mirror");
     if (!use8) {
         const std::string keep = g_last_error;
         if (ensure_mirror(e, st) != WAX_HIP_OK || b.d_cb == nullptr || b.d_maxnorm == nullptr) {
@@ -438,6 +545,8 @@ static int enqueue_mirror_group(wax_hip_engine* e, Slot* const* grp, int nq, boo
     g.a.use_measured = e->batch_eps_measured.load() != 0 ? 1 : 0;
     MirrorQueryCopies qc{};
     qc.dims = e->dims;
+    int one_entry = -1;                    // the entry every member reads, if there is one such (the accounting below)
+    bool one = n_masked == nq;
     for (int i = 0; i < nq; ++i) {
         Slot* s = grp[i];
         qc.src[i] = s->h_query;
@@ -446,15 +555,25 @@ static int enqueue_mirror_group(wax_hip_engine* e, Slot* const* grp, int nq, boo
         g.m[i].partials = s->d_partials;
         g.m[i].hits = s->h_hits;
         g.m[i].certified = slot_cert_word(s->h_done);
+        g.m[i].bitmap = nullptr;
         g.m[i].q_norm = s->q_norm;
         g.m[i].k = s->k_eff;
         g.m[i].kpad = s->k_eff;
         s->t_start = nullptr;
         s->t_end = nullptr;
+        if (s->has_pred) {
+            const int prc = pred_entry_prepare(e, s->pred_entry, st, &g.m[i].bitmap);
+            if (prc != WAX_HIP_OK) return prc;
+            if (one_entry < 0) one_entry = s->pred_entry;
+            else if (one_entry != s->pred_entry) one = false;
+        }
     }
     HIP_TRY(launch_mirror_group_queries(qc, nq, st), WAX_HIP_ERR_INTERNAL, "query upload");
-    HIP_TRY(use8 ? launch_mirror8_group(g, b.d_c8, b.d_c8_meta, nq, e->metric, (int)e->grid_blocks.load(), st)
-                 : launch_mirror_group(g, nq, e->metric, (int)e->grid_blocks.load(), st), WAX_HIP_ERR_INTERNAL, "mirror group launch");
+    if (n_masked != 0)
+        HIP_TRY(launch_mirror8_group_masked(g, b.d_c8, b.d_c8_meta, nq, e->metric, (int)e->grid_blocks.load(), st), WAX_HIP_ERR_INTERNAL, "masked mirror group launch");
+    else
+        HIP_TRY(use8 ? launch_mirror8_group(g, b.d_c8, b.d_c8_meta, nq, e->metric, (int)e->grid_blocks.load(), st)
+                     : launch_mirror_group(g, nq, e->metric, (int)e->grid_blocks.load(), st), WAX_HIP_ERR_INTERNAL, "mirror group launch");
     for (int i = 0; i < nq; ++i) {
         HIP_TRY(hipEventRecord(grp[i]->ev_done, st), WAX_HIP_ERR_INTERNAL, "event record");
         grp[i]->mirror = true;
@@ -463,12 +582,19 @@ static int enqueue_mirror_group(wax_hip_engine* e, Slot* const* grp, int nq, boo
     *took = true;
     e->st_mirror_scans += (uint64_t)nq;
     e->st_mirror_passes++;
-    e->st_mirror_shared_passes++;
+    if (nq >= 2) { e->st_mirror_shared_passes++; e->st_mirror_shared_queries += (uint64_t)nq; }
     if (use8) e->st_mirror8_passes++;
-    e->st_mirror_shared_queries += (uint64_t)nq;
     e->st_searches += (uint64_t)nq;
-    e->st_rows += e->count * (uint64_t)nq;
-    e->st_bytes += e->count * (use8 ? (uint64_t)e->dims + 8ull : (uint64_t)e->dims * 2ull) + (uint64_t)nq * MIRROR_KP * e->dims * 4ull;
+    // what the pass reads: every tile, unless every member reads the same bitmap and its count of live tiles has reached the host
+    // (from the second pass on that entry on); members with different bitmaps are charged every tile — an upper bound
+    uint64_t rows_read = e->count, live_tiles = 0, passing = 0;
+    if (n_masked != 0) {
+        e->pt_masked_passes++;
+        e->pt_rode += (uint64_t)n_masked;
+        if (one && pred_entry_counts(e, one_entry, false, &passing, &live_tiles)) rows_read = live_tiles * 16ull;
+    }
+    e->st_rows += rows_read * (uint64_t)nq;
+    e->st_bytes += rows_read * (use8 ? (uint64_t)e->dims + 8ull : (uint64_t)e->dims * 2ull) + (uint64_t)nq * MIRROR_KP * e->dims * 4ull;
     return WAX_HIP_OK;
 }
 
@@ -478,13 +604,31 @@ static void launch_parked(wax_hip_engine* e) {
     grp.swap(e->parked);
     e->n_parked.store(0);
     if (grp.empty()) return;
+    // A set with a predicate ticket in it takes the masked pass over the code mirror. Where that mirror cannot be had — an unmasked
+    // member does not want it, or it cannot be prepared — the masked members leave the set for the blocking body and the rest goes on
+    // as ever.
+    bool masked = false, all8 = true;
+    for (Slot* s : grp) { masked = masked || s->has_pred; all8 = all8 && s->want8; }
+    int use8_hint = -1;
+    if (masked) {
+        use8_hint = all8 && mirror8_ready(e, grp[0]->stream, (uint64_t)grp.size()) ? 1 : 0;
+        if (use8_hint == 0) {
+            std::vector<Slot*> rest;
+            for (Slot* s : grp) { if (s->has_pred) pred_ticket_defer(e, s); else rest.push_back(s); }
+            grp.swap(rest);
+            masked = false;
+            if (grp.empty()) return;
+            if (all8) use8_hint = 0; else use8_hint = -1;   // (not prepared: bf16 without asking again; else the set decides as ever)
+        }
+    }
     const int nq = (int)grp.size();
+    const bool lone = nq == 1 && !masked;
     bool took = false;
     int rc;
-    if (nq == 1) rc = enqueue_mirror_scan(e, grp[0], grp[0]->h_query, grp[0]->q_norm, grp[0]->k_eff, 0, &took, grp[0]->want8);   // alone after all: the lone query's kernels
-    else rc = enqueue_mirror_group(e, grp.data(), nq, &took);
+    if (lone) rc = enqueue_mirror_scan(e, grp[0], grp[0]->h_query, grp[0]->q_norm, grp[0]->k_eff, 0, &took, grp[0]->want8 && use8_hint != 0);   // alone after all: the lone query's kernels
+    else rc = enqueue_mirror_group(e, grp.data(), nq, &took, use8_hint);
     if (rc == WAX_HIP_OK && took) {
-        if (nq == 1) {
+        if (lone) {
             const hipError_t err = hipEventRecord(grp[0]->ev_done, grp[0]->stream);
             if (err != hipSuccess) rc = fail(WAX_HIP_ERR_INTERNAL, std::string("event record: ") + hipGetErrorString(err));
         }

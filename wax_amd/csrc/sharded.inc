@@ -58,6 +58,13 @@ struct ShardSlot {
     std::vector<uint64_t> sub_tickets;      // ticket path: one ticket per shard that holds rows (0 = none)
     int only_shard = -1;                    // ticket path with ONE shard holding rows: collect goes straight to that engine
     int32_t top_k = 0;
+    // wax_hip_search_predicate_submit on a handle: the score cut of the ticket, and a ticket with a predicate — always deferred: its
+    // collect runs sh_search_predicate under the lock the ticket holds
+    bool has_cut = false;
+    float cut = 0.f;
+    bool pred_deferred = false;
+    wax_hip_row_predicate pred{};
+    std::vector<float> query;
 };
 
 // Persistent per-shard worker threads: per-shard host work (single-query submits — one kernel launch each —, filtered search,
@@ -648,7 +655,7 @@ int sh_reserve(wax_hip_engine* e, uint64_t rows) {
 
 // ---- single-query search ---------------------------------------------------------------------------------------------
 
-int sh_submit(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, uint64_t* out_ticket) {
+int sh_submit(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, uint64_t* out_ticket, const TicketExtras* x) {
     ShardedState* s = e->sh;
     if (!out_ticket) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine/ticket is null");
     e->lock.lock_shared(holding(e) > 0);
@@ -659,8 +666,17 @@ int sh_submit(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_
         rc = sh_acquire_slot(s, &sl, holding(e) > 0);
         if (rc != WAX_HIP_OK) break;
         sl->kpad = 0; sl->host_path = false; sl->top_k = top_k; sl->sub_tickets.clear(); sl->only_shard = -1;
+        sl->has_cut = x != nullptr && x->has_cut != 0; sl->cut = x != nullptr ? x->cut : 0.f; sl->pred_deferred = false;
+        if (x != nullptr && x->pred != nullptr) e->pt_submitted++;
         if (total == 0) break;                                             // :448 empty engine: an empty ticket
         if (dims != e->dims || !query) { rc = fail(WAX_HIP_ERR_DIM_MISMATCH, dim_mismatch_msg(e->dims, query ? dims : 0)); break; }
+        if (x != nullptr && x->pred != nullptr) {                          // no fan-out of predicate tickets: the blocking body at collect
+            sl->pred_deferred = true;
+            sl->pred = *x->pred;
+            sl->query.assign(query, query + dims);
+            e->pt_deferred++;
+            break;
+        }
         const int limit = clamp_topk(top_k);
         const size_t G = s->subs.size();
         const bool rccl_wanted = s->exchange.load() == 1;
@@ -786,7 +802,11 @@ int sh_collect(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, float* out
     int rc = WAX_HIP_OK;
     *out_count = 0;
     if ((!out_ids || !out_scores) && capacity > 0) rc = fail(WAX_HIP_ERR_INVALID_ARGUMENT, "output arrays are null");
-    if (sl->host_path && sl->only_shard >= 0) {
+    if (sl->pred_deferred) {
+        if (rc == WAX_HIP_OK)   // (the cut is the shards' own, as in the blocking call)
+            rc = sh_search_predicate(e, sl->query.data(), e->dims, sl->top_k, 0, nullptr, 0, sl->has_cut ? 1 : 0, sl->cut, &sl->pred, out_ids, out_scores,
+                                     capacity, out_count, /*caller_locked=*/true);
+    } else if (sl->host_path && sl->only_shard >= 0) {
         // one shard holds every row: its keys are already global (row_base), its answer is the answer
         const size_t g = (size_t)sl->only_shard;
         if (rc == WAX_HIP_OK) rc = collect_impl(s->subs[g], sl->sub_tickets[g], out_ids, out_scores, capacity, out_count, nullptr, 0);
@@ -820,6 +840,7 @@ int sh_collect(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, float* out
         DeviceGuard dg(s->devices[0]);
         (void)hipEventSynchronize(sl->done);
     }
+    if (rc == WAX_HIP_OK && sl->has_cut && !sl->pred_deferred && out_ids && out_scores) apply_min_score(sl->cut, out_ids, out_scores, out_count);
     note_collect_id(e, sl->owner);
     sh_release_slot(s, sl);
     e->lock.unlock_shared();
@@ -1207,11 +1228,12 @@ static uint32_t merge_shard_results(const std::vector<ShardAnswer>& parts, uint3
 // (merge_shard_results) under the cut at clamp(top_k) and the caller's capacity.
 template <typename PerShard>
 static int sh_fanout_filtered(wax_hip_engine* e, uint32_t dims, int32_t top_k, uint64_t* out_ids, float* out_scores, uint32_t capacity,
-                              uint32_t* out_count, PerShard per_shard) {
+                              uint32_t* out_count, PerShard per_shard, bool caller_locked = false) {
     ShardedState* s = e->sh;
     *out_count = 0;
     if (dims != e->dims) return fail(WAX_HIP_ERR_DIM_MISMATCH, dim_mismatch_msg(e->dims, dims));
-    ReadGuard rd(e);
+    // (caller_locked: the collect of a deferred predicate ticket, which holds the handle's shared lock itself)
+    std::unique_ptr<ReadGuard> rd(caller_locked ? nullptr : new ReadGuard(e));
     const uint32_t limit = (uint32_t)clamp_topk(top_k);
     const size_t G = s->subs.size();
     std::vector<std::vector<uint64_t>> g_ids(G, std::vector<uint64_t>(limit));
@@ -1247,11 +1269,11 @@ int sh_search_filtered(wax_hip_engine* e, const float* query, uint32_t dims, int
 // The predicate search on a handle: every shard masks and searches its own rows (its attribute columns follow its rows).
 int sh_search_predicate(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, int has_allow, const uint64_t* allow,
                         uint64_t n_allow, int has_min, float min_score, const wax_hip_row_predicate* pred, uint64_t* out_ids,
-                        float* out_scores, uint32_t capacity, uint32_t* out_count) {
+                        float* out_scores, uint32_t capacity, uint32_t* out_count, bool caller_locked) {
     return sh_fanout_filtered(e, dims, top_k, out_ids, out_scores, capacity, out_count,
                               [&](wax_hip_engine* sub, uint64_t* ids, float* scores, uint32_t cap, uint32_t* n) {
                                   return wax_hip_search_predicate(sub, query, dims, top_k, has_allow, allow, n_allow, has_min, min_score, pred, ids, scores, cap, n);
-                              });
+                              }, caller_locked);
 }
 
 // setAttributes / getAttributes on a handle: the ids are grouped by owning shard (call order kept inside a group, so the last entry

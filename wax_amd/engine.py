@@ -356,6 +356,27 @@ class HIPVectorEngine:
         raise_for_status(rc)
         return int(t.value)
 
+    def submitFiltered(self, vector, topK: int, minScore=None, timeRange=None, denyFlags: int = 0) -> int:  # noqa: N802,N803
+        """searchFiltered without an allow-list as a ticket (wax_hip_search_predicate_submit): collect(ticket, topK) returns what
+        searchFiltered(vector, topK, minScore=..., timeRange=..., denyFlags=...) returns, bit for bit. Several such tickets in flight
+        — and unfiltered ones beside them — share passes over the 8-bit code mirror on a store that takes it; every other ticket is
+        answered by the blocking search at its collect. The ticket holds the engine's read lock until it is collected."""
+        q = _as_f32(vector).reshape(-1)
+        pred = ticket_predicate(timeRange, denyFlags)
+        t = ctypes.c_uint64(0)
+        rc = self._lib.wax_hip_search_predicate_submit(self._h, _fp(q), q.size, int(max(min(topK, 2**31 - 1), -2**31)),
+                                                       0 if minScore is None else 1, 0.0 if minScore is None else float(minScore),
+                                                       ctypes.byref(pred), ctypes.byref(t))
+        raise_for_status(rc)
+        return int(t.value)
+
+    def predicateTicketStats(self) -> dict:  # noqa: N802
+        """What became of the submitFiltered tickets (wax_hip_predicate_ticket_stats): submitted, rode, masked_passes, certified,
+        fallbacks, deferred, host_decided, bitmap_builds, bitmap_hits."""
+        st = _abi.PredicateTicketStats()
+        raise_for_status(self._lib.wax_hip_predicate_ticket_stats(self._h, ctypes.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in _abi.PredicateTicketStats._fields_}
+
     def collect(self, ticket: int, topK: int) -> Tuple[np.ndarray, np.ndarray]:  # noqa: N803
         """`topK` sizes the result arrays: pass what was given to submit() (a smaller value truncates to the best)."""
         cap = clampTopK(topK)   # the ticket was answered on the row count at submit time: size by topK alone
@@ -604,6 +625,20 @@ def searchMany(engines, queries, topK: int):  # noqa: N802,N803
                                              kcap, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
     raise_for_status(rc)
     return ids, scores, counts
+
+
+def ticket_predicate(timeRange=None, denyFlags=0) -> "_abi.RowPredicate":  # noqa: N803
+    """submitFiltered's row predicate: `timeRange` None or (after | None, before | None), `denyFlags` a mask of 32 bits."""
+    if timeRange is not None and (not isinstance(timeRange, (tuple, list)) or len(timeRange) != 2):
+        raise EncodingError("submitFiltered: timeRange must be None or (after | None, before | None)")
+    after, before = (None, None) if timeRange is None else timeRange
+    for bound in (after, before):
+        if bound is not None and not (isinstance(bound, (int, np.integer)) and -2**63 <= int(bound) < 2**63):
+            raise EncodingError("submitFiltered: a timeRange bound must be an int64 or None")
+    if not isinstance(denyFlags, (int, np.integer)) or not 0 <= int(denyFlags) <= 0xffffffff:
+        raise EncodingError("submitFiltered: denyFlags must be a mask of 32 bits")
+    return _abi.RowPredicate(0 if after is None else 1, 0 if after is None else int(after),
+                             0 if before is None else 1, 0 if before is None else int(before), int(denyFlags))
 
 
 def _per_pair(value, n: int, what: str, tuple_is_value: bool = False, who: str = "searchManyFiltered", per: str = "pair") -> list:
