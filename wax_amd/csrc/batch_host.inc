@@ -290,7 +290,7 @@ int ensure_mirror8(wax_hip_engine* e, hipStream_t st) {
         (void)hipFree(b.d_c8); (void)hipFree(b.d_c8_meta);
         b.d_c8 = nullptr; b.d_c8_meta = nullptr; b.c8_cap = 0; b.c8_stale = true;
         unsigned char* nc = nullptr; float* nm = nullptr;
-        HIP_TRY(hipMalloc(&nc, (size_t)e->capacity * D), WAX_HIP_ERR_ALLOC, "Failed to allocate code mirror");
+        HIP_TRY(hipMalloc(&nc, mirror8_bytes(e->capacity, D)), WAX_HIP_ERR_ALLOC, "Failed to allocate code mirror");   // whole tiles
         if (hipMalloc(&nm, (size_t)e->capacity * 2 * sizeof(float)) != hipSuccess) { (void)hipFree(nc); return fail(WAX_HIP_ERR_ALLOC, "Failed to allocate code mirror row words"); }
         b.d_c8 = nc; b.d_c8_meta = nm; b.c8_cap = e->capacity;
     }
@@ -302,8 +302,9 @@ int ensure_mirror8(wax_hip_engine* e, hipStream_t st) {
     if (b.rows8 > count) b.rows8 = count;
     if (b.rows8 < count) {
         const uint64_t first = b.rows8, n_new = count - first;
-        const hipError_t err = launch_mirror8_build(e->d_store + first * D, (uint32_t)n_new, D, e->metric == WAX_HIP_METRIC_COSINE ? 1 : 0,
-                                                    b.d_c8 + first * D, b.d_c8_meta + 2 * first, b.d_c8_max, st);
+        // the bases and the first row: the range may begin inside a tile (mirror8_layout.h)
+        const hipError_t err = launch_mirror8_build(e->d_store, first, (uint32_t)n_new, D, e->metric == WAX_HIP_METRIC_COSINE ? 1 : 0,
+                                                    b.d_c8, b.d_c8_meta, b.d_c8_max, st);
         if (err != hipSuccess) { b.c8_stale = true; return fail(WAX_HIP_ERR_INTERNAL, std::string("code mirror kernel launch: ") + hipGetErrorString(err)); }
         HIP_TRY(hipEventRecord(b.ev8_ready, st), WAX_HIP_ERR_INTERNAL, "code mirror ready record");
         b.ev8_pending = true;

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "mirror8_layout.h"
 
 using namespace wax;
 

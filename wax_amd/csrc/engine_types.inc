@@ -350,7 +350,7 @@ struct BatchMirror {
     // mutation (upsert, remove, removeBatch, deserialize, reallocation) marks it stale as a whole, and a stale or missing code mirror
     // is rebuilt only when three eligible queries in a row since the last mutation wanted it (c8_wanted) — until then they take bf16.
     std::mutex mu8;                      // serialises the (re)build only
-    unsigned char* d_c8 = nullptr;       // [c8_cap][dims] biased codes, row-major
+    unsigned char* d_c8 = nullptr;       // biased codes in 16-row tiles, MFMA operand order (mirror8_layout.h): ceil16(c8_cap) * dims bytes
     float* d_c8_meta = nullptr;          // [c8_cap] float2 {scale, err}
     unsigned int* d_c8_max = nullptr;    // one word: max ||v|| over the coded rows (grows between full conversions, like d_maxnorm)
     uint64_t c8_cap = 0;

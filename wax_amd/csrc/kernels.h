@@ -175,7 +175,8 @@ hipError_t launch_mirror_group_queries(const MirrorQueryCopies& c, int nq, hipSt
 hipError_t launch_mirror_select_probe(const int64_t* d_lists, int lists, int64_t* d_out, int* d_gathered, hipStream_t st);
 
 // ---- mirror8_scan.hip: the same two launches over the 8-bit code mirror ("Eight bits per element") ----
-// Codes are row-scaled and stored with a +128 bias ([n_rows][dims] bytes); meta is [n_rows] {scale, err}, err an upper bound on
+// Codes are row-scaled and stored with a +128 bias, in 16-row tiles in MFMA operand order (mirror8_layout.h: ceil16(n_rows) * dims
+// bytes); meta is [n_rows] {scale, err}, err an upper bound on
 // ||scale * code - x^||_2 of that row (+inf: a row that could not be coded). The key of a row is a LOWER BOUND of its distance, so the
 // certificate needs no store-wide error. Everything else a query owns travels in the bf16 structs above: `a.mirror` is unused,
 // `a.max_bits` points at one word, max ||v|| of the coded rows (dot's slack), `a.use_measured` is ignored.
@@ -206,9 +207,11 @@ hipError_t launch_mirror8_group_masked(const MirrorGroupArgs& args, const unsign
 // args.partials, hits, certified, store, ids and max_bits are not used.
 hipError_t launch_mirror8_keys(const MirrorScanArgs& args, const unsigned char* codes, const float* meta, const float* query, int metric,
                                int grid_cap, float* keys_out, hipStream_t st);
-// f32 rows -> codes + meta (mirror8_kernel: cosine rows normalised as mirror_kernel does); max_bits[0] = max ||v|| (atomic max)
-hipError_t launch_mirror8_build(const float* src, uint32_t n_rows, uint32_t dims, int normalize, unsigned char* codes, float* meta,
-                                unsigned int* max_bits, hipStream_t st);
+// f32 rows [first_row, first_row + n_rows) -> codes + meta (mirror8_kernel: cosine rows normalised as mirror_kernel does);
+// max_bits[0] = max ||v|| (atomic max). src, codes and meta are the BASES of the store and of the two buffers (row 0): the codes go
+// where mirror8_layout.h puts them, and a range may begin or end inside a 16-row tile (its other rows are left as they are).
+hipError_t launch_mirror8_build(const float* src, uint64_t first_row, uint32_t n_rows, uint32_t dims, int normalize, unsigned char* codes,
+                                float* meta, unsigned int* max_bits, hipStream_t st);
 
 struct ScanVariantInfo {
     int unroll;          // row groups in flight per wave iteration

@@ -18,6 +18,7 @@
 //                 >= lb_KP - slack > d_k. slack (Mirror8Slack) holds what err does not — see there.
 #include <cstring>
 
+#include "mirror8_layout.h"
 #include "mirror_finish.h"
 #include "mirror_pass.h"
 
@@ -36,17 +37,38 @@ __device__ inline float wave_max64(float v) {
 }
 
 // A 16-row tile is one MFMA operand A: lane l holds 16 codes of row (l & 15) per k-step, bytes [64 s + 16 (l >> 4), + 16) of the row at
-// step s — the sum over k does not care which 16 elements a lane holds as long as operand B holds the same ones, and this choice
-// makes every load instruction read 64 contiguous bytes of each row, two of them a whole 128-byte line. The code loads are plain:
-// a line is read by two instructions and must stay in the vector L1 between them (non-temporal loads cost 0.04-0.08 ms of a 0.63 ms
-// pass). One tile per wave iteration: two, three and four tiles in flight, and a second register buffer loaded one iteration ahead,
-// measured no faster for four queries and 0.01 ms slower for one (profiles/r22).
-template <int DIMS>
+// step s — the sum over k does not care which 16 elements a lane holds as long as operand B holds the same ones. The buffer is stored
+// in that order (mirror8_layout.h), so load s of a wave is 1024 contiguous bytes of the tile.
+// How a pass reads its tiles — the kernels below all run Code8Shipped; tools/code8_shape_probe.hip times the others on the same body:
+//   TILED   the buffer is in mirror8_layout.h's order; else row-major ([row][element]: an instruction touches sixteen 64-byte
+//           halves of lines, and every line must stay in the vector L1 between the two instructions that read it)
+//   NT      non-temporal code loads
+//   TILES   tiles per wave iteration, all loaded before the first product
+//   AHEAD   the wave's first iteration is loaded in front of the query prologue (query_delta, query_digits: about a thousand
+//           instructions that depend on no row), which then runs under the first miss
+template <bool TILED_, bool NT_, int TILES_, bool AHEAD_>
+struct Code8Loads {
+    static constexpr bool TILED = TILED_, NT = NT_, AHEAD = AHEAD_;
+    static constexpr int TILES = TILES_;
+    static_assert(TILES >= 1 && TILES <= 2, "tiles per wave iteration");
+    static __host__ __device__ constexpr size_t offset(uint64_t row, uint32_t element, uint32_t dims) {
+        return TILED ? mirror8_offset(row, element, dims) : (size_t)row * dims + element;
+    }
+};
+// What profiles/r26/a_code8_shape_probe.jsonl chose (10M x 384, lone / four queries, ms): row-major plain 0.627 / 0.679 and non-temporal
+// 0.669 / 0.731; tiled plain 0.632 / 0.682, tiled non-temporal 0.570 / 0.625. Whole lines that nothing reads twice need no place
+// in the cache. Two tiles per iteration change neither form by more than the spread (0.572 / 0.625), and neither does AHEAD
+// (0.570 / 0.625) — which keeps the tile's registers live across the prologue: 26 VGPRs more, three waves per SIMD instead of four
+// at 384-d and spills at 768-d. Not shipped.
+using Code8Shipped = Code8Loads<true, true, 1, false>;
+
+template <int DIMS, class LOADS = Code8Shipped>
 struct Code8Tiles {
-    static constexpr int TILE = 16;                    // rows per MFMA = rows per wave iteration; one make_room takes them
+    static constexpr int TILE = 16;                    // rows per MFMA; one make_room takes an iteration's
     static constexpr int KSTEPS = DIMS / 64;           // MFMAs (and dwordx4 loads per lane) per tile: 96 B in flight per lane at 384-d
-    static constexpr int RPC = TILE;
+    static constexpr int RPC = TILE * LOADS::TILES;    // rows per wave iteration
     static_assert(DIMS % 64 == 0, "whole k-steps");
+    static_assert(TILE == (int)MIRROR8_TILE_ROWS, "the layout's tile is the operand's");
 };
 
 // The query as three balanced base-128 digits per element, exact by construction:
@@ -136,12 +158,13 @@ __device__ __forceinline__ float code8_sum(float pa, float pb, float pc) {
 // iteration ahead like mirror_pass. A tile whose bits are zero for every live member is skipped before its loads and make_room (the
 // ballot makes the test wave-uniform); otherwise a lane's key is offered only where bit 4 kg + plane of its own query is set. The
 // sums and the epilogue do not see the bitmap: a row's key is what it is unmasked.
-template <int DIMS, int METRIC, int NQ, bool WRITE_KEYS, bool MASKED, class QUERIES>
+template <int DIMS, int METRIC, int NQ, bool WRITE_KEYS, bool MASKED, class QUERIES, class LOADS = Code8Shipped>
 __device__ __forceinline__ void code8_pass(const unsigned char* __restrict__ codes, const f32x2* __restrict__ sides, const MirrorScanArgs& a,
                                            const QUERIES& qs, float* __restrict__ keys_out, int64_t* lds) {
-    using T = Code8Tiles<DIMS>;
-    constexpr int KSTEPS = T::KSTEPS, TILE = T::TILE, RPC = T::RPC;
+    using T = Code8Tiles<DIMS, LOADS>;
+    constexpr int KSTEPS = T::KSTEPS, TILE = T::TILE, RPC = T::RPC, TILES = LOADS::TILES;
     static_assert(NQ >= 1 && NQ <= MIRROR_MAX_NQ && MIRROR_MAX_NQ * 4 <= 16, "four columns per query");
+    static_assert(!MASKED || TILES == 1, "the skip test and the bitmap word are a tile's");
 
     const int lane = lane_id();
     const int wave = (int)(threadIdx.x >> 6);
@@ -149,6 +172,27 @@ __device__ __forceinline__ void code8_pass(const unsigned char* __restrict__ cod
     const int myq = col >> 2, plane = col & 3;        // the query and plane of this lane's column; after the combine: row 4 kg + plane
     const bool live = myq < NQ;
     const uint32_t n = a.n_rows;
+
+    const uint32_t nchunks = (n + RPC - 1) / RPC;
+    const uint32_t gwave = blockIdx.x * SCAN_WAVES + wave;
+    const uint32_t nwaves = gridDim.x * SCAN_WAVES;
+
+    // the codes of the iteration's tiles: every load is issued before the first product. The clamp makes tail lanes re-read the last
+    // row (a tile past the last one, TILES > 1, reads it in every lane): no byte that the writer did not write reaches a key.
+    u32x4 v[TILES][KSTEPS];
+    auto load_tiles = [&](uint32_t chunk) {
+#pragma unroll
+        for (int u = 0; u < TILES; ++u) {
+            const uint32_t ra = (chunk * TILES + u) * TILE + col;        // the row this lane loads codes of
+            const uint32_t rc = ra < n ? ra : n - 1;
+#pragma unroll
+            for (int s = 0; s < KSTEPS; ++s) {
+                const u32x4* p = reinterpret_cast<const u32x4*>(codes + LOADS::offset(rc, 64 * s + 16 * kg, DIMS));
+                v[u][s] = LOADS::NT ? __builtin_nontemporal_load(p) : *p;
+            }
+        }
+    };
+    if constexpr (LOADS::AHEAD) { if (gwave < nchunks) load_tiles(gwave); }
 
     // this lane's query: delta, the norm, and the digits of its plane at the lane's k-slices
     float delta = 0.f, qn = 0.f;
@@ -169,11 +213,6 @@ __device__ __forceinline__ void code8_pass(const unsigned char* __restrict__ cod
 #pragma unroll
     for (int s = 0; s < KSTEPS; ++s) b[s] = query_digits(mine + s * 64 + kg * 16, inv_delta, live ? plane : 3);
 
-    const uint32_t nchunks = (n + RPC - 1) / RPC;
-    const uint32_t gwave = blockIdx.x * SCAN_WAVES + wave;
-    const uint32_t nwaves = gridDim.x * SCAN_WAVES;
-    const u32x4* __restrict__ rows = reinterpret_cast<const u32x4*>(codes);
-
     // the word of this lane's query that holds tile c's bits (c < nchunks: row 16 c < n, so word c >> 1 exists)
     auto tile_word = [&](uint32_t c) -> uint32_t { return !live ? 0u : my_bitmap == nullptr ? 0xffffffffu : my_bitmap[c >> 1]; };
     uint32_t word = 0u, bits = 0xffffu;
@@ -185,39 +224,43 @@ __device__ __forceinline__ void code8_pass(const unsigned char* __restrict__ cod
             if (next < nchunks) word = tile_word(next);
             if (__ballot(bits != 0u) == 0ull) continue;          // wave-uniform: no member may be offered a row of the tile, so none is loaded
         }
-        const uint32_t ra = chunk * TILE + col;                  // the row this lane loads codes of
-        const uint32_t r = chunk * TILE + 4 * kg + plane;        // the row this lane will hold the key of
-        const u32x4* p = rows + (size_t)(ra < n ? ra : n - 1) * (DIMS / 16) + kg;   // clamp: tail lanes re-read the last row
-        u32x4 v[KSTEPS];
+        if (!LOADS::AHEAD || chunk != gwave) load_tiles(chunk);
+        f32x2 side[TILES];
 #pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) v[s] = p[s * 4];        // every load of the iteration is issued before the first product
-        const f32x2 side = __builtin_nontemporal_load(sides + (r < n ? r : n - 1));
+        for (int u = 0; u < TILES; ++u) {
+            const uint32_t r = (chunk * TILES + u) * TILE + 4 * kg + plane;      // the row this lane will hold the key of
+            side[u] = __builtin_nontemporal_load(sides + (r < n ? r : n - 1));
+        }
         if constexpr (!WRITE_KEYS) {
 #pragma unroll
             for (int i = 0; i < NQ; ++i) tk[i].make_room(RPC);
         }
-        i32x4 acc = {0, 0, 0, 0};
 #pragma unroll
-        for (int s = 0; s < KSTEPS; ++s) {
-            const u32x4 x = v[s] ^ 0x80808080u;
-            acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, x), b[s], acc, 0, 0, 0);
-        }
-        float S = 0.f;
+        for (int u = 0; u < TILES; ++u) {
+            const uint32_t r = (chunk * TILES + u) * TILE + 4 * kg + plane;
+            i32x4 acc = {0, 0, 0, 0};
 #pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            const float pl = (float)acc[reg];
-            const float Sr = code8_sum(quad_bcast<0>(pl), quad_bcast<1>(pl), quad_bcast<2>(pl));
-            S = plane == reg ? Sr : S;
-        }
-        const float d = code8_key<METRIC>(S, delta, side, inv_qn, qn);
-        bool offer = live && r < n;
-        if constexpr (MASKED) offer = offer && ((bits >> (uint32_t)(4 * kg + plane)) & 1u) != 0u;
-        if constexpr (WRITE_KEYS) {
-            if (offer && myq == 0) keys_out[r] = d + 0.0f;
-        } else {
-            const int64_t key = make_key(d + 0.0f, a.row_base + r);
+            for (int s = 0; s < KSTEPS; ++s) {
+                const u32x4 x = v[u][s] ^ 0x80808080u;
+                acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, x), b[s], acc, 0, 0, 0);
+            }
+            float S = 0.f;
 #pragma unroll
-            for (int i = 0; i < NQ; ++i) tk[i].push(key, offer && myq == i);
+            for (int reg = 0; reg < 4; ++reg) {
+                const float pl = (float)acc[reg];
+                const float Sr = code8_sum(quad_bcast<0>(pl), quad_bcast<1>(pl), quad_bcast<2>(pl));
+                S = plane == reg ? Sr : S;
+            }
+            const float d = code8_key<METRIC>(S, delta, side[u], inv_qn, qn);
+            bool offer = live && r < n;
+            if constexpr (MASKED) offer = offer && ((bits >> (uint32_t)(4 * kg + plane)) & 1u) != 0u;
+            if constexpr (WRITE_KEYS) {
+                if (offer && myq == 0) keys_out[r] = d + 0.0f;
+            } else {
+                const int64_t key = make_key(d + 0.0f, a.row_base + r);
+#pragma unroll
+                for (int i = 0; i < NQ; ++i) tk[i].push(key, offer && myq == i);
+            }
         }
     }
     if constexpr (WRITE_KEYS) return;
@@ -324,7 +367,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void mirror8_finish_group_kernel(Mirr
 }
 
 // ---------------------------------------------------------------------------
-// f32 rows -> biased codes + {scale, err}. One wave per row. The f32 STORE is read, never the bf16 mirror (the errors would add).
+// f32 rows -> biased codes + {scale, err}. One wave per row (mirror8_code_row), a tile per workgroup and four steps (mirror8_kernel). The f32 STORE is read, never the bf16 mirror (the errors would add).
 //   x^      cosine: v * (1 / sqrt(m)), m = the scan's own sum of squares (scan_order_norm2), a row the scan scores 0 (sqrt(m) <= 1e-6,
 //           NaN) becomes zero — mirror_kernel's rule and expression; dot: v.
 //   scale   max|x^| / 127; code = rint(x^ / scale) clamped to +-127 (a zero row: scale 0, codes 0).
@@ -334,66 +377,85 @@ __global__ __launch_bounds__(SCAN_THREADS) void mirror8_finish_group_kernel(Mirr
 //           magnitude that changes no bit, and a row of 1e-30 or 1e+21 — whose squared differences are 0 or +inf in f32 — gets the err
 //           it has instead of 2^-149 (no bound at all) or +inf.
 //   A row with an inf / NaN element (or whose scale or err is still not finite) gets err = +inf and scale 0.
-__global__ __launch_bounds__(256) void mirror8_kernel(const float* __restrict__ src, uint32_t n_rows, uint32_t dims, int normalize,
-                                                      unsigned char* __restrict__ codes, float* __restrict__ meta,
+// one row by one wave: its codes into the buffer at `codes` where mirror8_offset has row r, {scale, err} to meta_row; returns sqrt(m)
+__device__ __forceinline__ float mirror8_code_row(const float* __restrict__ row, uint32_t dims, int normalize, int lane,
+                                                  unsigned char* __restrict__ codes, uint32_t r, float* __restrict__ meta_row) {
+    const uint32_t d4 = dims >> 2;
+    const f32x4* row4 = reinterpret_cast<const f32x4*>(row);
+    const float m = normalize == 16 ? scan_order_norm2<16>(row, dims, lane)
+                  : normalize == 32 ? scan_order_norm2<32>(row, dims, lane) : scan_order_norm2<64>(row, dims, lane);
+    const float n = sqrtf(m);
+    const bool zero_row = normalize && !(n > COS_NORM_FLOOR);
+    const float inv = normalize ? 1.0f / n : 1.0f;
+    float amax = 0.f;
+    bool bad = false;
+    for (uint32_t c = lane; c < d4; c += WAVE) {
+        const f32x4 v = row4[c];
+        const float x[4] = {zero_row ? 0.f : v.x * inv, zero_row ? 0.f : v.y * inv, zero_row ? 0.f : v.z * inv, zero_row ? 0.f : v.w * inv};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            bad = bad || !__builtin_isfinite(x[i]);
+            amax = fmaxf(amax, fabsf(x[i]));
+        }
+    }
+    amax = wave_max64(amax);
+    bad = __ballot(bad) != 0ull;
+    float scale = amax / 127.0f;
+    if (!__builtin_isfinite(scale)) { bad = true; scale = 0.f; }
+    int ex = 0;                              // scale = f * 2^ex, f in [0.5, 1): the differences are squared in units of 2^ex
+    (void)frexpf(scale, &ex);
+    float e2 = 0.f;
+    for (uint32_t c = lane; c < d4; c += WAVE) {
+        const f32x4 v = row4[c];
+        const float x[4] = {zero_row ? 0.f : v.x * inv, zero_row ? 0.f : v.y * inv, zero_row ? 0.f : v.z * inv, zero_row ? 0.f : v.w * inv};
+        unsigned int word = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float t = (scale > 0.f && x[i] == x[i]) ? x[i] / scale : 0.f;
+            t = rintf(fminf(fmaxf(t, -127.0f), 127.0f));
+            const float d = ldexpf(fmaf(scale, t, -x[i]), -ex);
+            e2 = fmaf(d, d, e2);
+            word |= (unsigned int)((int)t + 128) << (8 * i);
+        }
+        *reinterpret_cast<unsigned int*>(codes + mirror8_offset(r, 4 * c, dims)) = word;
+    }
+    e2 = group_sum<64>(e2);
+    e2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e2), 63));
+    float errn = sqrtf(e2) * (1.0f + (float)dims * 1.1920929e-7f);
+    errn = nextafterf(errn, __builtin_inff());
+    float err = ldexpf(errn, ex);
+    if (ldexpf(err, -ex) < errn) err = nextafterf(err, __builtin_inff());     // back in the subnormal range: rounded up, never down
+    if (bad || !__builtin_isfinite(err)) { err = __builtin_inff(); scale = 0.f; }
+    if (lane == 0) { meta_row[0] = scale; meta_row[1] = err; }
+    return n;
+}
+
+// Rows [first_row, first_row + n_rows) of the store at `src` into the buffers at `codes` and `meta` (all three: the base, row 0).
+// A workgroup takes whole 16-row tiles of mirror8_layout.h, its four waves rows 4 j + w of the tile in step j = 0 .. 3, and every
+// lane stores its dword where mirror8_offset puts it: a row's 16-byte units are 256 bytes apart, the four waves fill 64 contiguous
+// bytes at a time and the four steps the 256, all from one CU within a few microseconds, so the lines are whole when the L2 lets
+// them go. No LDS, no barrier, the parent's registers: the conversion is bound by the latency of a row's two passes and lives on
+// eight waves per SIMD (staging tiles in LDS for whole-line stores cost 20-30 VGPRs and took 10.3-10.5 ms for 10M rows against
+// 7.9: profiles/r26). An appended range may begin or end inside a tile: a row outside it is skipped. The grid is one workgroup per
+// touched tile (at most 4096), so a small append runs on a quarter of the workgroups that one per four rows would give it, each
+// doing its four steps one after the other: a few microseconds at the sizes an append has.
+__global__ __launch_bounds__(256) void mirror8_kernel(const float* __restrict__ src, uint32_t first_row, uint32_t n_rows, uint32_t dims,
+                                                      int normalize, unsigned char* __restrict__ codes, float* __restrict__ meta,
                                                       unsigned int* __restrict__ max_norm_bits) {
     __shared__ unsigned int block_max;
     const int lane = lane_id();
-    const uint32_t gwave = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const uint32_t nwaves = gridDim.x * 4;
-    const uint32_t d4 = dims >> 2;
+    const uint32_t wave = threadIdx.x >> 6;
     if (threadIdx.x == 0) block_max = 0u;
     __syncthreads();
     float wave_max = 0.f;
-    for (uint32_t r = gwave; r < n_rows; r += nwaves) {
-        const float* row = src + (size_t)r * dims;
-        const f32x4* row4 = reinterpret_cast<const f32x4*>(row);
-        const float m = normalize == 16 ? scan_order_norm2<16>(row, dims, lane)
-                      : normalize == 32 ? scan_order_norm2<32>(row, dims, lane) : scan_order_norm2<64>(row, dims, lane);
-        const float n = sqrtf(m);
-        const bool zero_row = normalize && !(n > COS_NORM_FLOOR);
-        const float inv = normalize ? 1.0f / n : 1.0f;
-        float amax = 0.f;
-        bool bad = false;
-        for (uint32_t c = lane; c < d4; c += WAVE) {
-            const f32x4 v = row4[c];
-            const float x[4] = {zero_row ? 0.f : v.x * inv, zero_row ? 0.f : v.y * inv, zero_row ? 0.f : v.z * inv, zero_row ? 0.f : v.w * inv};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                bad = bad || !__builtin_isfinite(x[i]);
-                amax = fmaxf(amax, fabsf(x[i]));
-            }
-        }
-        amax = wave_max64(amax);
-        bad = __ballot(bad) != 0ull;
-        float scale = amax / 127.0f;
-        if (!__builtin_isfinite(scale)) { bad = true; scale = 0.f; }
-        int ex = 0;                              // scale = f * 2^ex, f in [0.5, 1): the differences are squared in units of 2^ex
-        (void)frexpf(scale, &ex);
-        float e2 = 0.f;
-        unsigned int* out = reinterpret_cast<unsigned int*>(codes + (size_t)r * dims);
-        for (uint32_t c = lane; c < d4; c += WAVE) {
-            const f32x4 v = row4[c];
-            const float x[4] = {zero_row ? 0.f : v.x * inv, zero_row ? 0.f : v.y * inv, zero_row ? 0.f : v.z * inv, zero_row ? 0.f : v.w * inv};
-            unsigned int word = 0u;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float t = (scale > 0.f && x[i] == x[i]) ? x[i] / scale : 0.f;
-                t = rintf(fminf(fmaxf(t, -127.0f), 127.0f));
-                const float d = ldexpf(fmaf(scale, t, -x[i]), -ex);
-                e2 = fmaf(d, d, e2);
-                word |= (unsigned int)((int)t + 128) << (8 * i);
-            }
-            out[c] = word;
-        }
-        e2 = group_sum<64>(e2);
-        e2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e2), 63));
-        float errn = sqrtf(e2) * (1.0f + (float)dims * 1.1920929e-7f);
-        errn = nextafterf(errn, __builtin_inff());
-        float err = ldexpf(errn, ex);
-        if (ldexpf(err, -ex) < errn) err = nextafterf(err, __builtin_inff());     // back in the subnormal range: rounded up, never down
-        if (bad || !__builtin_isfinite(err)) { err = __builtin_inff(); scale = 0.f; }
-        if (lane == 0) { meta[2 * (size_t)r] = scale; meta[2 * (size_t)r + 1] = err; }
+    const uint32_t end_row = first_row + n_rows;                     // (the launcher keeps a tile's last row inside 32 bits)
+    const uint32_t tile0 = first_row / MIRROR8_TILE_ROWS, tile_end = (end_row + MIRROR8_TILE_ROWS - 1) / MIRROR8_TILE_ROWS;
+    for (uint32_t x = 0;; ++x) {                                     // step x & 3 of the workgroup's tile number x >> 2
+        const uint32_t tile = tile0 + (x >> 2) * gridDim.x + blockIdx.x;
+        if (tile >= tile_end) break;
+        const uint32_t r = tile * MIRROR8_TILE_ROWS + (x & 3u) * 4u + wave;
+        if (r < first_row || r >= end_row) continue;
+        const float n = mirror8_code_row(src + (size_t)r * dims, dims, normalize, lane, codes, r, meta + 2 * (size_t)r);
         if (n == n && n > wave_max) wave_max = n;
     }
     if (lane == 0) atomicMax(&block_max, __float_as_uint(wave_max));
@@ -476,14 +538,14 @@ hipError_t launch_mirror8_group_masked(const MirrorGroupArgs& args, const unsign
     });
 }
 
-hipError_t launch_mirror8_build(const float* src, uint32_t n_rows, uint32_t dims, int normalize, unsigned char* codes, float* meta,
-                                unsigned int* max_bits, hipStream_t st) {
+hipError_t launch_mirror8_build(const float* src, uint64_t first_row, uint32_t n_rows, uint32_t dims, int normalize, unsigned char* codes,
+                                float* meta, unsigned int* max_bits, hipStream_t st) {
     if (n_rows == 0) return hipSuccess;
-    if (!in_dim_list(MirrorDims{}, dims)) return hipErrorInvalidValue;
-    uint64_t blocks = ((uint64_t)n_rows + 3) / 4;
+    if (!in_dim_list(MirrorDims{}, dims) || first_row + n_rows > 0xffffffffull - MIRROR8_TILE_ROWS) return hipErrorInvalidValue;
+    uint64_t blocks = (first_row + n_rows + MIRROR8_TILE_ROWS - 1) / MIRROR8_TILE_ROWS - first_row / MIRROR8_TILE_ROWS;   // the tiles the range touches
     if (blocks > 4096) blocks = 4096;
     const int group = normalize ? scan_group_lanes(dims) : 0;
-    hipLaunchKernelGGL(mirror8_kernel, dim3((unsigned)blocks), dim3(256), 0, st, src, n_rows, dims, group, codes, meta, max_bits);
+    hipLaunchKernelGGL(mirror8_kernel, dim3((unsigned)blocks), dim3(256), 0, st, src, (uint32_t)first_row, n_rows, dims, group, codes, meta, max_bits);
     return hipGetLastError();
 }
 

@@ -372,7 +372,18 @@ int wax_hip_mirror8_snapshot(wax_hip_engine* e, uint64_t first_row, uint64_t n_r
     unsigned int max_bits = 0u;
     HIP_TRY(hipMemcpy(&max_bits, b.d_c8_max, sizeof(max_bits), hipMemcpyDeviceToHost), WAX_HIP_ERR_INTERNAL, "mirror8_snapshot copy");
     if (n_rows > 0) {
-        HIP_TRY(hipMemcpy(out_codes, b.d_c8 + first_row * D, (size_t)n_rows * D, hipMemcpyDeviceToHost), WAX_HIP_ERR_INTERNAL, "mirror8_snapshot copy");
+        // the device holds 16-row tiles in operand order (mirror8_layout.h); the caller gets rows: the tiles of the range come over as
+        // they are, a few thousand at a time, and every 16-byte unit is put where its row has it
+        constexpr uint64_t CHUNK_ROWS = 4096 * MIRROR8_TILE_ROWS;
+        std::vector<uint8_t> tiles;
+        for (uint64_t row0 = first_row / MIRROR8_TILE_ROWS * MIRROR8_TILE_ROWS; row0 < first_row + n_rows; row0 += CHUNK_ROWS) {
+            const uint64_t lo = std::max(row0, first_row), hi = std::min(row0 + CHUNK_ROWS, first_row + n_rows);
+            tiles.resize(mirror8_bytes(hi - row0, (uint32_t)D));
+            HIP_TRY(hipMemcpy(tiles.data(), b.d_c8 + mirror8_offset(row0, 0, (uint32_t)D), tiles.size(), hipMemcpyDeviceToHost), WAX_HIP_ERR_INTERNAL, "mirror8_snapshot copy");
+            for (uint64_t r = lo; r < hi; ++r)
+                for (uint32_t el = 0; el < D; el += 16)
+                    std::memcpy(out_codes + (r - first_row) * D + el, tiles.data() + mirror8_offset(r - row0, el, (uint32_t)D), 16);
+        }
         HIP_TRY(hipMemcpy(out_meta, b.d_c8_meta + 2 * first_row, (size_t)n_rows * 2 * sizeof(float), hipMemcpyDeviceToHost), WAX_HIP_ERR_INTERNAL, "mirror8_snapshot copy");
     }
     std::memcpy(out_max_norm, &max_bits, sizeof(float));
