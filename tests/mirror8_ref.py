@@ -154,6 +154,27 @@ class Coded:
         return lb_kp - slack(self.x.shape[1], self.metric, qn, self.max_norm) - d[k - 1]
 
 
+class MaskedModel:
+    """The certificate of a masked pass (the predicate tickets'): lower bounds and exact distances of every (row, query) of one
+    store, and the slack per query."""
+
+    def __init__(self, metric, rows, qs):
+        coded = Coded(rows, metric)
+        self.lb = np.stack([lower_bounds(q, coded.codes, coded.scale, coded.err, metric) for q in qs], axis=1)
+        self.exact = np.stack([exact_distances(rows, q, metric) for q in qs], axis=1)
+        self.slack = np.array([slack(rows.shape[1], metric, float(np.linalg.norm(q.astype(np.float64))), coded.max_norm) for q in qs])
+
+    def margin(self, mask, q, k):
+        """lb_64 - slack - d_k: the 64 best lower bounds among the passing rows, the exact k-th distance among those 64 rows."""
+        rows = np.flatnonzero(mask)
+        if len(rows) <= KP:
+            return -np.inf
+        lb = self.lb[rows, q]
+        cand = np.argsort(lb, kind="stable")[:KP]
+        d = np.sort(self.exact[rows[cand], q])
+        return float(lb[cand[-1]] - self.slack[q] - d[k - 1])
+
+
 # ---------------------------------------------------------------------------
 # The device's code mirror held to float64 (test_mirror8_edges_gpu.py reads it through mirror8Snapshot; test_mirror8_cpu.py proves
 # that an IEEE f32 quantiser passes every check below and that a halved err, a swapped byte pair or a wrong scale does not).

@@ -131,10 +131,12 @@ def test_conversion_kernel_against_f64_row_by_row(wax, name):
         eng.mirror8Snapshot(1, len(rows))
 
 
-@pytest.mark.parametrize("n", [1, 3, 4, 5, 255, 256, 257, 16385])
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 255, 256, 257, 16385, 65553])
 def test_conversion_kernel_row_counts(wax, n):
-    """One wave per row, four waves per block, at most 4 096 blocks: 16 385 rows make a wave take a second row, the small counts
-    leave waves of the last block without one. Every row is written (each satisfies (a)); as an append onto 64 coded rows the same
+    """A workgroup per 16-row tile, its four waves rows 4 j + w of the tile in four steps, at most 4 096 workgroups: the small counts
+    leave waves, steps and most of the only tile without a row, 255 to 257 rows end before, at and behind a tile's last row, 16 385
+    rows are 1 025 workgroups of one tile each (the last tile a single row), and 65 553 rows are 4 098 tiles, so workgroups 0 and 1
+    take a second tile, the last one ragged. Every row is written (each satisfies (a)); as an append onto 64 coded rows the same
     count must leave those 64 byte for byte as they were. (What lies beyond the last coded row cannot be read: the snapshot refuses
     the range.)"""
     dims = 384
@@ -162,6 +164,47 @@ def test_conversion_kernel_row_counts(wax, n):
     for a, b in zip(before[:3], after[:3]):
         assert np.array_equal(a.view(np.uint8), b[:64].view(np.uint8)), f"append of {n}: the rows coded before it changed"
     check_mirror(eng, np.vstack([base, rows]), 0, f"64 + {n} rows")
+
+
+@pytest.mark.parametrize("metric,dims", [(0, 384), (1, 384), (0, 768)], ids=["cosine-384", "dot-384", "cosine-768"])
+def test_an_append_from_inside_a_tile_over_more_than_4096_tiles(wax, metric, dims):
+    """21 rows coded, 65 600 appended: the range begins inside tile 1 and touches tiles 1 .. 4 101, 4 101 tiles for 4 096 workgroups, so
+    workgroups 0 .. 4 take a second tile, `tile0 + gridDim.x + blockIdx.x` with tile0 = 1 — the one term of the writer that no
+    smaller append and no store written from row 0 exercises. The next query converts exactly the appended rows; the mirror then
+    satisfies (a) row by row and equals a fresh engine's over the same rows bit for bit: codes, scale, err, the max-norm word, and
+    the keys of three queries."""
+    first, more = 21, 65_600
+    rows, queries = R.corpus_for(metric, first + more, dims, seed=87), R.queries_for(dims)
+    ids = np.arange(first + more, dtype=np.uint64)
+    eng = wax.HIPVectorEngine(metric=wax.VectorMetric(metric), dimensions=dims)
+    fresh = None
+    try:
+        eng.reserve(first + more)                                    # no new slab at the append: only the appended rows are converted
+        eng.addBatch(ids[:first], rows[:first])
+        eng.setTuning("mirror_bits", 8)
+        warm(eng, queries[0])
+        eng.addBatch(ids[first:], rows[first:])
+        c = counters(eng)
+        answer(eng, queries[0], 10, 2)
+        d = delta(eng, c)
+        assert (d["mirror8_conversions"], d["mirror8_rows_converted"], d["mirror8_passes"]) == (1, more, 1), d
+        ctx = f"metric {metric} dims {dims}: {first} + {more} rows"
+        check_mirror(eng, rows, metric, ctx)
+        fresh = make_engine(wax, metric, dims, rows, ids)
+        warm(fresh, queries[0])
+        a, b = eng.mirror8Snapshot(), fresh.mirror8Snapshot()
+        assert a[4] == b[4] == first + more
+        assert np.array_equal(a[0], b[0]), f"{ctx}: codes, first difference at (row, element) {np.argwhere(a[0] != b[0])[0]}"
+        for x, y, what in ((a[1], b[1], "scale"), (a[2], b[2], "err")):
+            differ = np.flatnonzero(x.view(np.uint32) != y.view(np.uint32))
+            assert differ.size == 0, f"{ctx}: {what} of {differ.size} rows, the first {differ[0]}"
+        assert np.float32(a[3]).view(np.uint32) == np.float32(b[3]).view(np.uint32), f"{ctx}: max-norm word"
+        for i, q in enumerate(queries[:3]):
+            assert np.array_equal(eng.mirror8Keys(q).view(np.uint32), fresh.mirror8Keys(q).view(np.uint32)), f"{ctx}: keys of query {i}"
+    finally:
+        eng.close()
+        if fresh is not None:
+            fresh.close()
 
 
 # ---- (b) the mirror after every kind of mutation --------------------------------------------------------------------------------

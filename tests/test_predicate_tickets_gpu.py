@@ -8,7 +8,7 @@ predicate_mirror_ref's (20 005 x 384 and 3 001 x 768, cosine and dot: neither ro
 under "predicate_mirror" 2, "mirror_bits" 8, "scan_mirror" 2 and "mirror_share" 2, so a set is exactly what a test parks: tickets wait
 until four are parked or one of them is collected.
 
-Zero fallbacks are asserted only where the float64 model of the 8-bit certificate (mirror8_ref: quantise, lower_bounds, slack; below:
+Zero fallbacks are asserted only where the float64 model of the 8-bit certificate (mirror8_ref: quantise, lower_bounds, slack; MaskedModel:
 the 64 best passing lower bounds and their exact k-th distance) leaves lb_64 - slack - d_k >= MARGIN_FLOOR — the f32-against-f64 error
 that floor was sized for is <= 5.5e-4 — and that margin is asserted first, so a failure names the side that moved."""
 import functools
@@ -79,24 +79,7 @@ def mask_of(n, dims, name):
 
 # ---- the float64 model of the masked 8-bit certificate ---------------------------------------------------------------------------------
 
-class Model8:
-    """Lower bounds and exact distances of every (row, query) of one store, and the slack per query."""
-
-    def __init__(self, metric, rows, qs):
-        coded = M8.Coded(rows, metric)
-        self.lb = np.stack([M8.lower_bounds(q, coded.codes, coded.scale, coded.err, metric) for q in qs], axis=1)
-        self.exact = np.stack([M8.exact_distances(rows, q, metric) for q in qs], axis=1)
-        self.slack = np.array([M8.slack(rows.shape[1], metric, float(np.linalg.norm(q.astype(np.float64))), coded.max_norm) for q in qs])
-
-    def margin(self, mask, q, k):
-        """lb_64 - slack - d_k: the 64 best lower bounds among the passing rows, the exact k-th distance among those 64 rows."""
-        rows = np.flatnonzero(mask)
-        if len(rows) <= M8.KP:
-            return -np.inf
-        lb = self.lb[rows, q]
-        cand = np.argsort(lb, kind="stable")[:M8.KP]
-        d = np.sort(self.exact[rows[cand], q])
-        return float(lb[cand[-1]] - self.slack[q] - d[k - 1])
+Model8 = M8.MaskedModel          # (shared with masked_iterations_ref.py)
 
 
 @functools.lru_cache(maxsize=None)
