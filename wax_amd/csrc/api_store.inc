@@ -338,9 +338,15 @@ int wax_hip_remove(wax_hip_engine* e, uint64_t frame_id) {
     // the mirror's tail follows the store's; if it cannot, the store has moved all the same: the mirror is converted again at its next
     // use and the host bookkeeping below still runs (returning here would leave ids / count describing the store before the shift)
     if (mirror_note_remove(e, (uint64_t)idx) != WAX_HIP_OK) { (void)hipGetLastError(); mirror_note_lost(e); }
+    const bool repeated_ids = e->idmap.size() != e->count;   // only deserialize can put a frame id into several rows
     e->ids.erase(e->ids.begin() + idx);                   // :440
     attr_note_remove(e, (uint64_t)idx);                   // the row's attributes go with its id
     e->idmap.erase_row(frame_id, (uint32_t)idx);
+    if (repeated_ids) {
+        // firstIndex(of:) semantics: the id now means the next row that holds it (the map held the first one, so any other lies behind it)
+        const auto next = std::find(e->ids.begin() + idx, e->ids.end(), frame_id);
+        if (next != e->ids.end()) e->idmap.put(frame_id, (uint32_t)(next - e->ids.begin()));
+    }
     e->count -= 1;                                        // :441
     return WAX_HIP_OK;
 }
