@@ -663,6 +663,14 @@ int wax_hip_mirror8_keys(wax_hip_engine* e, const float* query, float* out_keys,
  * (the gathered prefixes where they fit its buffer, else the k-way merge), out_merged[64] = the k-way merge alone, *out_gathered =
  * 1 where the gather answered. Blocking. */
 int wax_hip_mirror_select_probe(const int64_t* lists, uint32_t n_lists, int64_t* out_selected, int64_t* out_merged, int32_t* out_gathered);
+/* Diagnostic of the selection frame of a mirror pass — the wave lists, their prunes and the workgroup merge — on keys the caller
+ * makes up (tests hold it to a host model through it; no product path calls it). `keys` = nq (1 to 4) arrays of n_slots (1 to 2^24)
+ * keys, one per row slot and query; INT64_MAX marks a slot that is not offered to that query (a tail row, a masked row), and no
+ * other key occurs twice in one array. On the current device a launch of `grid` (1 to 8) workgroups walks the slots as a pass walks
+ * its 16-row tiles: wave g of the 4 * grid takes slots [16 c, 16 c + 16) for c = g, g + 4 * grid, ... and offers each query its
+ * keys there. out_partials[(q * grid + b) * 64 ..] = the 64 keys workgroup b keeps for query q: the smallest it was offered,
+ * ascending, INT64_MAX behind them. Blocking. */
+int wax_hip_mirror_lists_probe(const int64_t* keys, uint32_t nq, uint64_t n_slots, uint32_t grid, int64_t* out_partials);
 
 #ifdef __cplusplus
 }

@@ -167,6 +167,8 @@ SIGNATURES: Dict[str, tuple] = {
     "wax_hip_mirror8_keys": (ctypes.c_int, [_engine_p, _f32p, _f32p, ctypes.c_uint64]),
     "wax_hip_mirror_select_probe": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.c_uint32, ctypes.POINTER(ctypes.c_int64),
                                                    ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)]),
+    "wax_hip_mirror_lists_probe": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
+                                                  ctypes.POINTER(ctypes.c_int64)]),
 }
 
 

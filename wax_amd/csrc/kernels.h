@@ -173,6 +173,10 @@ hipError_t launch_mirror_group_queries(const MirrorQueryCopies& c, int nq, hipSt
 // overflows) into out[0 .. MIRROR_KP), kway_merge alone on the same lists into out[MIRROR_KP .. 2 MIRROR_KP), *gathered = 1 where
 // gather_select answered. d_lists: [lists][MIRROR_KP] sorted keys, KEY_PAD-padded, 1 <= lists <= SCAN_KWAY_MERGE_GRID. One workgroup.
 hipError_t launch_mirror_select_probe(const int64_t* d_lists, int lists, int64_t* d_out, int* d_gathered, hipStream_t st);
+// A diagnostic (wax_hip_mirror_lists_probe): the selection frame of a pass (mirror_pass.h: PassLists, as the 8-bit pass runs it) over
+// made-up keys. d_keys: [nq][n_slots], KEY_PAD = not offered; a launch of `grid` workgroups walks the slots in 16-row tiles as
+// code8_pass walks rows (wave gwave, stride nwaves) and leaves d_partials[(q * grid + block) * MIRROR_KP ..]. 1 <= nq <= MIRROR_MAX_NQ.
+hipError_t launch_mirror_lists_probe(const int64_t* d_keys, int nq, uint32_t n_slots, int grid, int64_t* d_partials, hipStream_t st);
 
 // ---- mirror8_scan.hip: the same two launches over the 8-bit code mirror ("Eight bits per element") ----
 // Codes are row-scaled and stored with a +128 bias, in 16-row tiles in MFMA operand order (mirror8_layout.h: ceil16(n_rows) * dims

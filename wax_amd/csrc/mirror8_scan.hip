@@ -158,7 +158,7 @@ __device__ __forceinline__ float code8_sum(float pa, float pb, float pc) {
 // iteration ahead like mirror_pass. A tile whose bits are zero for every live member is skipped before its loads and make_room (the
 // ballot makes the test wave-uniform); otherwise a lane's key is offered only where bit 4 kg + plane of its own query is set. The
 // sums and the epilogue do not see the bitmap: a row's key is what it is unmasked.
-template <int DIMS, int METRIC, int NQ, bool WRITE_KEYS, bool MASKED, class QUERIES, class LOADS = Code8Shipped>
+template <int DIMS, int METRIC, int NQ, bool WRITE_KEYS, bool MASKED, class QUERIES, class LOADS = Code8Shipped, class FRAME = FrameShipped>
 __device__ __forceinline__ void code8_pass(const unsigned char* __restrict__ codes, const f32x2* __restrict__ sides, const MirrorScanArgs& a,
                                            const QUERIES& qs, float* __restrict__ keys_out, int64_t* lds) {
     using T = Code8Tiles<DIMS, LOADS>;
@@ -176,6 +176,10 @@ __device__ __forceinline__ void code8_pass(const unsigned char* __restrict__ cod
     const uint32_t nchunks = (n + RPC - 1) / RPC;
     const uint32_t gwave = blockIdx.x * SCAN_WAVES + wave;
     const uint32_t nwaves = gridDim.x * SCAN_WAVES;
+
+    PassLists<NQ, FRAME> lists;                         // (WRITE_KEYS keeps none)
+    lists.clk.begin();
+    if constexpr (!WRITE_KEYS) lists.init(lds, wave);
 
     // the codes of the iteration's tiles: every load is issued before the first product. The clamp makes tail lanes re-read the last
     // row (a tile past the last one, TILES > 1, reads it in every lane): no byte that the writer did not write reaches a key.
@@ -198,13 +202,11 @@ __device__ __forceinline__ void code8_pass(const unsigned char* __restrict__ cod
     float delta = 0.f, qn = 0.f;
     const float* mine = reinterpret_cast<const float*>(qs.floats(0));
     const uint32_t* my_bitmap = nullptr;
-    WaveTopK<MIRROR_CAP> tk[NQ];
 #pragma unroll
     for (int i = 0; i < NQ; ++i) {
         const float di = query_delta<DIMS>(qs.floats(i), lane);
         if (myq == i) { delta = di; qn = qs.norm(i); mine = reinterpret_cast<const float*>(qs.floats(i)); }
         if constexpr (MASKED) { if (myq == i) my_bitmap = qs.bitmap(i); }
-        if constexpr (!WRITE_KEYS) tk[i].init(lds + i * MIRROR_PASS_LDS + wave * MIRROR_CAP, MIRROR_KP);
     }
     // cosine: mirror rows are unit vectors (or zero), so sim = s / ||q||; the rule for a null query is the f32 scan's
     const float inv_qn = qn > COS_NORM_FLOOR ? 1.0f / qn : 0.0f;
@@ -217,6 +219,7 @@ __device__ __forceinline__ void code8_pass(const unsigned char* __restrict__ cod
     auto tile_word = [&](uint32_t c) -> uint32_t { return !live ? 0u : my_bitmap == nullptr ? 0xffffffffu : my_bitmap[c >> 1]; };
     uint32_t word = 0u, bits = 0xffffu;
     if constexpr (MASKED) word = gwave < nchunks ? tile_word(gwave) : 0u;   // one iteration ahead
+    lists.clk.loop_begin();
     for (uint32_t chunk = gwave; chunk < nchunks; chunk += nwaves) {
         if constexpr (MASKED) {
             bits = (word >> ((chunk & 1u) * 16u)) & 0xffffu;
@@ -231,10 +234,7 @@ __device__ __forceinline__ void code8_pass(const unsigned char* __restrict__ cod
             const uint32_t r = (chunk * TILES + u) * TILE + 4 * kg + plane;      // the row this lane will hold the key of
             side[u] = __builtin_nontemporal_load(sides + (r < n ? r : n - 1));
         }
-        if constexpr (!WRITE_KEYS) {
-#pragma unroll
-            for (int i = 0; i < NQ; ++i) tk[i].make_room(RPC);
-        }
+        if constexpr (!WRITE_KEYS) lists.room(RPC);
 #pragma unroll
         for (int u = 0; u < TILES; ++u) {
             const uint32_t r = (chunk * TILES + u) * TILE + 4 * kg + plane;
@@ -259,33 +259,13 @@ __device__ __forceinline__ void code8_pass(const unsigned char* __restrict__ cod
             } else {
                 const int64_t key = make_key(d + 0.0f, a.row_base + r);
 #pragma unroll
-                for (int i = 0; i < NQ; ++i) tk[i].push(key, offer && myq == i);
+                for (int i = 0; i < NQ; ++i) lists.offer(i, key, offer && myq == i);
             }
         }
     }
     if constexpr (WRITE_KEYS) return;
 
-    // per query: the waves' lists -> the workgroup's MIRROR_KP best -> partials[blockIdx.x]
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-        tk[i].finalize();
-        int* counts = reinterpret_cast<int*>(lds + i * MIRROR_PASS_LDS + SCAN_WAVES * MIRROR_CAP);
-        if (lane == 0) counts[wave] = tk[i].cnt;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-        int64_t* base = lds + i * MIRROR_PASS_LDS;
-        block_rank_merge<SCAN_WAVES>(base, MIRROR_CAP, reinterpret_cast<int*>(base + SCAN_WAVES * MIRROR_CAP), MIRROR_KP,
-                                     base + SCAN_WAVES * MIRROR_CAP + SCAN_WAVES);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-        const int64_t* fin = lds + i * MIRROR_PASS_LDS + SCAN_WAVES * MIRROR_CAP + SCAN_WAVES;
-        int64_t* out = qs.partials(i) + (size_t)blockIdx.x * MIRROR_KP;
-        for (int t = (int)threadIdx.x; t < MIRROR_KP; t += SCAN_THREADS) out[t] = fin[t];
-    }
+    lists.finish(qs);
 }
 
 // launch(ScanShape<dims>, metric constant, grid) at the instantiation of (dims, metric), with the grid of code8_pass at that dimension
@@ -352,6 +332,32 @@ __global__ __launch_bounds__(SCAN_THREADS, 2) void mirror8_scan_masked_group_ker
 template <int DIMS, int METRIC>
 __global__ __launch_bounds__(SCAN_THREADS, 2) void mirror8_keys_kernel(Mirror8ScanArgsQ<DIMS> aq, float* keys_out) {
     code8_pass<DIMS, METRIC, 1, true, false>(aq.codes, reinterpret_cast<const f32x2*>(aq.meta), aq.a, LoneQuery<Mirror8ScanArgsQ<DIMS>>{aq.a}, keys_out, nullptr);
+}
+
+// the frame alone on made-up keys (wax_hip_mirror_lists_probe: a diagnostic): code8_pass's walk and its lane-to-(query, row) map,
+// with keys[q][slot] where the pass computes a key and KEY_PAD where it offers none
+struct ProbePartials {
+    int64_t* out;
+    __device__ __forceinline__ int64_t* partials(int i) const { return out + (size_t)i * gridDim.x * MIRROR_KP; }
+};
+template <int NQ>
+__global__ __launch_bounds__(SCAN_THREADS, 2) void mirror_lists_probe_kernel(const int64_t* __restrict__ keys, uint32_t n_slots, int64_t* __restrict__ out) {
+    __shared__ int64_t lds[NQ * MIRROR_PASS_LDS];
+    constexpr int TILE = 16;
+    const int lane = lane_id();
+    const int wave = (int)(threadIdx.x >> 6);
+    const int myq = (lane & 15) >> 2, row = 4 * (lane >> 4) + (lane & 3);
+    const uint32_t nchunks = (n_slots + TILE - 1) / TILE;
+    PassLists<NQ> lists;
+    lists.init(lds, wave);
+    for (uint32_t chunk = blockIdx.x * SCAN_WAVES + wave; chunk < nchunks; chunk += gridDim.x * SCAN_WAVES) {
+        const uint32_t slot = chunk * TILE + row;
+        const int64_t key = (myq < NQ && slot < n_slots) ? keys[(size_t)myq * n_slots + slot] : KEY_PAD;
+        lists.room(TILE);
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) lists.offer(i, key, key != KEY_PAD && myq == i);
+    }
+    lists.finish(ProbePartials{out});
 }
 
 template <int DIMS, int METRIC>
@@ -536,6 +542,18 @@ hipError_t launch_mirror8_group_masked(const MirrorGroupArgs& args, const unsign
         }
         return launch_finish((mirror8_finish_group_kernel<D, M>), nq, st, ga);
     });
+}
+
+hipError_t launch_mirror_lists_probe(const int64_t* d_keys, int nq, uint32_t n_slots, int grid, int64_t* d_partials, hipStream_t st) {
+    if (d_keys == nullptr || d_partials == nullptr || nq < 1 || nq > MIRROR_MAX_NQ || n_slots == 0 || grid < 1 || grid > SCAN_KWAY_MERGE_GRID)
+        return hipErrorInvalidValue;
+    switch (nq) {
+        case 1: hipLaunchKernelGGL(mirror_lists_probe_kernel<1>, dim3(grid), dim3(SCAN_THREADS), 0, st, d_keys, n_slots, d_partials); break;
+        case 2: hipLaunchKernelGGL(mirror_lists_probe_kernel<2>, dim3(grid), dim3(SCAN_THREADS), 0, st, d_keys, n_slots, d_partials); break;
+        case 3: hipLaunchKernelGGL(mirror_lists_probe_kernel<3>, dim3(grid), dim3(SCAN_THREADS), 0, st, d_keys, n_slots, d_partials); break;
+        default: hipLaunchKernelGGL(mirror_lists_probe_kernel<4>, dim3(grid), dim3(SCAN_THREADS), 0, st, d_keys, n_slots, d_partials); break;
+    }
+    return hipGetLastError();
 }
 
 hipError_t launch_mirror8_build(const float* src, uint64_t first_row, uint32_t n_rows, uint32_t dims, int normalize, unsigned char* codes,

@@ -72,6 +72,116 @@ __device__ __forceinline__ MirrorScanArgs member_args(MirrorScanArgs a, const Mi
     return a;
 }
 
+// ---- the selection frame of a pass: the lists of one wave for the NQ queries, and their way into partials[blockIdx.x] ----
+// What a pass does with its keys, spelled once: init, then per wave iteration room(rows) and one offer per query, then finish.
+// Whatever FRAME says, the workgroup's partials are the MIRROR_KP smallest keys offered in the workgroup, ascending, KEY_PAD behind
+// them: FRAME only chooses how the wave lists get there ("The selection frame").
+//   SORTED  a list that a prune has left full keeps its first MIRROR_KP slots sorted from then on, so every later prune of it is
+//           wave_prune_sorted (topk.h): the keys pushed since, ranked against a sorted prefix — less than half the broadcast reads
+//           and compares of the general prune — and the final prune of a list that nothing was pushed to since is no prune at all.
+//   Clock   hooks around the frame's phases; empty in every kernel of the library (tools/code8_shape_probe.hip times with them).
+// No bound crosses a wave, let alone a workgroup: what a workgroup keeps depends on its own rows alone.
+struct NoClock {
+    __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ void loop_begin() {}
+    __device__ __forceinline__ void prune_in() {}
+    __device__ __forceinline__ void prune_out() {}
+    __device__ __forceinline__ void loop_end() {}
+    __device__ __forceinline__ void done() {}
+};
+template <bool SORTED_, class CLOCK_ = NoClock>
+struct PassFrame {
+    static constexpr bool SORTED = SORTED_;
+    using Clock = CLOCK_;
+};
+using FramePlain = PassFrame<false>;      // the frame as it was before PassLists: the general prune every time
+using FrameShipped = PassFrame<true>;     // (profiles/r29: 0.604 against 0.620 ms for four queries over 10M x 384, 0.571 against 0.574 for one)
+
+template <int NQ, class FRAME = FrameShipped>
+struct PassLists {
+    static_assert(NQ >= 1 && NQ <= MIRROR_MAX_NQ, "queries per pass");
+    WaveTopK<MIRROR_CAP> tk[NQ];
+    unsigned full;      // SORTED, bit i: a prune has left MIRROR_KP keys in list i
+    int64_t* lds;
+    int wave;
+    typename FRAME::Clock clk;
+
+    // `lds_`: NQ * MIRROR_PASS_LDS words of the kernel's
+    __device__ __forceinline__ void init(int64_t* lds_, int wave_) {
+        lds = lds_;
+        wave = wave_;
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) tk[i].init(lds + i * MIRROR_PASS_LDS + wave * MIRROR_CAP, MIRROR_KP);
+        full = 0u;
+    }
+
+    // what a prune left, back in scalar registers (a noinline call returns in vector registers)
+    __device__ __forceinline__ void pruned(int i, int cnt, int64_t tau) {
+        tk[i].cnt = __builtin_amdgcn_readfirstlane(cnt);
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)tau);
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tau >> 32));
+        tk[i].tau = (int64_t)(((uint64_t)hi << 32) | lo);
+    }
+    __device__ __forceinline__ void prune(int i) {
+        if constexpr (FRAME::SORTED) {
+            if ((full >> i) & 1u) {
+                if (tk[i].cnt == MIRROR_KP) return;       // nothing pushed since the last prune: sorted as it stands
+                const PruneOut r = wave_prune_sorted<MIRROR_CAP>((lds_i64*)tk[i].buf, tk[i].cnt);
+                pruned(i, r.cnt, r.tau);
+                return;
+            }
+        }
+        const PruneOut r = wave_prune<MIRROR_CAP, true>((lds_i64*)tk[i].buf, tk[i].cnt, tk[i].k);
+        pruned(i, r.cnt, r.tau);
+        if constexpr (FRAME::SORTED) full |= (tk[i].cnt == MIRROR_KP ? 1u : 0u) << i;
+    }
+
+    // room for `rows` (<= MIRROR_CAP - MIRROR_KP) more keys in every list of the wave
+    __device__ __forceinline__ void room(int rows) {
+        bool shortof = false;
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) shortof = shortof || tk[i].cnt > MIRROR_CAP - rows;
+        if (shortof) {
+            clk.prune_in();
+#pragma unroll
+            for (int i = 0; i < NQ; ++i)
+                if (tk[i].cnt > MIRROR_CAP - rows) prune(i);
+            clk.prune_out();
+        }
+    }
+
+    // every lane of the wave, together: `key` to query i's list where `valid` (room() has made the room)
+    __device__ __forceinline__ void offer(int i, int64_t key, bool valid) { tk[i].push(key, valid); }
+
+    // per query: the waves' lists -> the workgroup's MIRROR_KP best -> partials(i)[blockIdx.x]; every thread of the workgroup
+    template <class QUERIES>
+    __device__ __forceinline__ void finish(const QUERIES& qs) {
+        clk.loop_end();
+        const int lane = lane_id();
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) {
+            prune(i);
+            int* counts = reinterpret_cast<int*>(lds + i * MIRROR_PASS_LDS + SCAN_WAVES * MIRROR_CAP);
+            if (lane == 0) counts[wave] = tk[i].cnt;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) {
+            int64_t* base = lds + i * MIRROR_PASS_LDS;
+            block_rank_merge<SCAN_WAVES>(base, MIRROR_CAP, reinterpret_cast<int*>(base + SCAN_WAVES * MIRROR_CAP), MIRROR_KP,
+                                         base + SCAN_WAVES * MIRROR_CAP + SCAN_WAVES);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) {
+            const int64_t* fin = lds + i * MIRROR_PASS_LDS + SCAN_WAVES * MIRROR_CAP + SCAN_WAVES;
+            int64_t* mine = qs.partials(i) + (size_t)blockIdx.x * MIRROR_KP;
+            for (int t = (int)threadIdx.x; t < MIRROR_KP; t += SCAN_THREADS) mine[t] = fin[t];
+        }
+        clk.done();
+    }
+};
+
 // `lds`: NQ * MIRROR_PASS_LDS words of the kernel's. `bitmap` (MASKED; predicate.hip's: every word written, bits of rows >= n clear):
 // the wave's chunk of RPC rows is the unit of the skip test, in scan_masked_kernel's form.
 template <class ROWS, int DIMS, int METRIC, int NQ, bool MASKED, class QUERIES>
@@ -92,7 +202,8 @@ __device__ __forceinline__ void mirror_pass(const typename ROWS::Vec* __restrict
     // the query slices of this lane: elements [8c, 8c + 8) of vector c = gl + j * GROUP
     f32x2 q[NQ][LOADS][4];
     float start[NQ], qn[NQ], inv_qn[NQ];
-    WaveTopK<MIRROR_CAP> tk[NQ];
+    PassLists<NQ> lists;
+    lists.init(lds, wave);
 #pragma unroll
     for (int i = 0; i < NQ; ++i) {
         const f32x4* q4 = qs.floats(i);
@@ -105,7 +216,6 @@ __device__ __forceinline__ void mirror_pass(const typename ROWS::Vec* __restrict
         qn[i] = qs.norm(i);
         // cosine: mirror rows are unit vectors (or zero), so sim = acc / ||q||; the rule for a null query is the f32 scan's
         inv_qn[i] = qn[i] > COS_NORM_FLOOR ? 1.0f / qn[i] : 0.0f;
-        tk[i].init(lds + i * MIRROR_PASS_LDS + wave * MIRROR_CAP, MIRROR_KP);
     }
 
     const uint32_t nchunks = (n + RPC - 1) / RPC;
@@ -123,8 +233,7 @@ __device__ __forceinline__ void mirror_pass(const typename ROWS::Vec* __restrict
             if (bits == 0u) continue;                            // wave-uniform: no row of the chunk may be offered, so none is loaded
         }
         const uint32_t rbase = chunk * RPC + sub;
-#pragma unroll
-        for (int i = 0; i < NQ; ++i) tk[i].make_room(RPC);
+        lists.room(RPC);
         typename ROWS::Vec v[UNROLL][LOADS];
         typename ROWS::Side side[UNROLL];
 #pragma unroll
@@ -154,32 +263,12 @@ __device__ __forceinline__ void mirror_pass(const typename ROWS::Vec* __restrict
                 const f32x2 s2 = (acc[0] + acc[1]) + (acc[2] + acc[3]);
                 const float s = group_sum<GROUP>(s2.x + s2.y);
                 const float d = ROWS::template key<METRIC>(s, side[u], inv_qn[i], qn[i]);
-                tk[i].push(make_key(d + 0.0f, a.row_base + r), offer);
+                lists.offer(i, make_key(d + 0.0f, a.row_base + r), offer);
             }
         }
     }
 
-    // per query: the waves' lists -> the workgroup's MIRROR_KP best -> partials[blockIdx.x]
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-        tk[i].finalize();
-        int* counts = reinterpret_cast<int*>(lds + i * MIRROR_PASS_LDS + SCAN_WAVES * MIRROR_CAP);
-        if (lane == 0) counts[wave] = tk[i].cnt;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-        int64_t* base = lds + i * MIRROR_PASS_LDS;
-        block_rank_merge<SCAN_WAVES>(base, MIRROR_CAP, reinterpret_cast<int*>(base + SCAN_WAVES * MIRROR_CAP), MIRROR_KP,
-                                     base + SCAN_WAVES * MIRROR_CAP + SCAN_WAVES);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-        const int64_t* fin = lds + i * MIRROR_PASS_LDS + SCAN_WAVES * MIRROR_CAP + SCAN_WAVES;
-        int64_t* mine = qs.partials(i) + (size_t)blockIdx.x * MIRROR_KP;
-        for (int t = (int)threadIdx.x; t < MIRROR_KP; t += SCAN_THREADS) mine[t] = fin[t];
-    }
+    lists.finish(qs);
 }
 
 // ---- the host side of a pass ----

@@ -94,6 +94,53 @@ __device__ __attribute__((noinline)) PruneOut wave_prune(lds_i64* buf, int cnt, 
     return r;
 }
 
+// wave_prune<CAP, true> with k = 64 for a list that an earlier prune left full: buf[0 .. 64) are the 64 smallest keys so far,
+// ascending, and buf[64 .. cnt) the m = cnt - 64 >= 1 keys pushed since. Lane l owns old key l and new key l. An old key's rank is
+// its index plus the new keys below it; a new key's rank is the old keys below it — a binary search in the sorted prefix, one step
+// per trip of the loop — plus the new keys below it. m broadcast keys and 2 m compares per lane where the general prune has
+// 64 + m and 2 (64 + m), and the result is the same: the 64 smallest in buf[0 .. 64) ascending, tau = buf[63].
+template <int CAP>
+__device__ __attribute__((noinline)) PruneOut wave_prune_sorted(lds_i64* buf, int cnt) {
+    constexpr int K = 64, STEPS = 7;                        // a search over 64 entries ends within 7 steps
+    static_assert(CAP - K <= 64 && (CAP - K) % 4 == 0, "one new key per lane, four per trip");
+    wave_lds_fence();
+    const int lane = lane_id();
+    const int m = __builtin_amdgcn_readfirstlane(cnt) - K;
+    const int64_t old = buf[lane];
+    const int64_t nw = (lane < m) ? buf[K + lane] : KEY_PAD;
+    int rank_old = lane, below = 0, lo = 0, hi = K;
+    auto search_step = [&]() {
+        const bool open = lo < hi;
+        const int mid = open ? (lo + hi) >> 1 : 0;
+        const bool before = buf[mid] < nw;
+        lo = (open && before) ? mid + 1 : lo;
+        hi = (open && !before) ? mid : hi;
+    };
+    int steps = 0;
+    for (int j = 0; j < m; j += 4) {
+        int64_t o[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) o[u] = buf[K + j + u];
+        if (steps < STEPS) { search_step(); ++steps; }      // (wave-uniform)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t key = (j + u < m) ? o[u] : KEY_PAD;     // a slot past the live ones holds an old key
+            rank_old += (key < old) ? 1 : 0;
+            below += (key < nw) ? 1 : 0;
+        }
+    }
+    for (; steps < STEPS; ++steps) search_step();
+    const int rank_new = lo + below;
+    wave_lds_fence();
+    if (rank_old < K) buf[rank_old] = old;
+    if (lane < m && rank_new < K) buf[rank_new] = nw;
+    wave_lds_fence();
+    PruneOut r;
+    r.cnt = K;
+    r.tau = buf[K - 1];
+    return r;
+}
+
 // Streaming k-smallest over int64 keys, private to one wave.
 //   CAP  : LDS slots (power of two, >= k + 64 so that one push of up to 64
 //          candidates always fits after a prune)

@@ -447,3 +447,22 @@ int wax_hip_mirror_select_probe(const int64_t* lists, uint32_t n_lists, int64_t*
     *out_gathered = gathered;
     return WAX_HIP_OK;
 }
+
+// Diagnostic for tests/test_pass_lists_gpu.py: the selection frame of a mirror pass on keys the caller makes up
+// (launch_mirror_lists_probe). No engine, no product path.
+int wax_hip_mirror_lists_probe(const int64_t* keys, uint32_t nq, uint64_t n_slots, uint32_t grid, int64_t* out_partials) {
+    if (!keys || !out_partials) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (nq < 1 || nq > (uint32_t)MIRROR_MAX_NQ) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror_lists_probe: 1 to 4 queries");
+    if (grid < 1 || grid > 8) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror_lists_probe: 1 to 8 workgroups");
+    if (n_slots < 1 || n_slots > (1ull << 24)) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror_lists_probe: 1 to 2^24 slots");
+    const size_t in_bytes = (size_t)nq * n_slots * sizeof(int64_t), out_bytes = (size_t)nq * grid * MIRROR_KP * sizeof(int64_t);
+    char* d = nullptr;
+    HIP_TRY(hipMalloc(&d, in_bytes + out_bytes), WAX_HIP_ERR_INTERNAL, "mirror_lists_probe allocation");
+    int64_t* d_out = reinterpret_cast<int64_t*>(d + in_bytes);
+    hipError_t err = hipMemcpy(d, keys, in_bytes, hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = launch_mirror_lists_probe(reinterpret_cast<const int64_t*>(d), (int)nq, (uint32_t)n_slots, (int)grid, d_out, nullptr);
+    if (err == hipSuccess) err = hipMemcpy(out_partials, d_out, out_bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    HIP_TRY(err, WAX_HIP_ERR_INTERNAL, "mirror_lists_probe");
+    return WAX_HIP_OK;
+}
