@@ -469,6 +469,33 @@ int wax_hip_search_batch_predicate(wax_hip_engine* e, const float* queries, uint
                                    const float* min_scores, const wax_hip_row_predicate* preds,
                                    uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts);
 
+/* ---- the timeline lane ------------------------------------------------------------------------------------------ *
+ * Wax.timeline(TimelineQuery) (TimelineQuery.swift:38-53) is the third ranked id list UnifiedSearch fuses (UnifiedSearch.swift:181-194,
+ * with limit = max(candidateLimit, timelineFallbackLimit): 30 to 1 000): the `limit` newest (or oldest) frames that pass after /
+ * before and the deleted / superseded exclusions. Here it is selected on the device from the attribute columns above: a row passes
+ * under wax_hip_row_predicate's rule (a store, or a row, without attributes is (0, 0)), and the answer is the first `limit` passing
+ * rows by (timestamp ascending, frame id ascending) for chronological order, (timestamp descending, frame id ascending) for
+ * newest_first != 0. Ties go by ascending FRAME ID, compared unsigned, not by row: toc.frames is indexed by frame id and Swift's sort
+ * is stable, so that is what the reference returns in both orders, and it makes the answer independent of the store's mutation
+ * history and of sharding. includeDeleted / includeSuperseded map to deny_flags as in wax_hip_search_predicate. The reference drops
+ * surrogates AFTER the prefix; WAX_HIP_FLAG_SURROGATE in deny_flags makes that a PRE-filter here: the limit newest of the frames that
+ * are not surrogates, never fewer because surrogates crowded the prefix. */
+#define WAX_HIP_TIMELINE_MAX_LIMIT 4096   /* = WAX_HIP_RRF_MAX_ENTRIES: a longer lane cannot be fused */
+/* Blocking. A reader: shared lock, rows staged by wax_hip_add are seen, re-entrant for a thread that holds tickets. Writes
+ * min(passing rows, limit, out_capacity) ids (and their timestamps: out_timestamps may be NULL) and that number to *out_count.
+ * limit <= 0: count 0, no device is touched (TimelineQuery.swift:51). pred NULL: every row passes. An empty engine gives count 0.
+ * A sharded handle runs every shard and merges on the host by the same pair order. Refused with WAX_HIP_ERR_INVALID_ARGUMENT, the
+ * outputs untouched: a NULL engine, a NULL out_count, NULL out_ids with out_capacity != 0, limit > WAX_HIP_TIMELINE_MAX_LIMIT. */
+int wax_hip_timeline(wax_hip_engine* e, int32_t limit, int newest_first, const wax_hip_row_predicate* pred,
+                     uint64_t* out_ids, int64_t* out_timestamps, uint32_t out_capacity, uint32_t* out_count);
+/* The same answer left in HBM: exactly `limit` ids to d_out_ids, entries past the answer padded with UINT64_MAX, and the real count
+ * to *d_out_count. Enqueued on `stream` and NOT synchronised, under the contract of wax_hip_search_shard_device — the result is a lane
+ * for wax_hip_rrf_fuse_batch_device with stride = limit, pitch = 1 on the same stream. The attribute columns are brought up to date
+ * as the blocking predicate search does it, on a stream of the engine's, and `stream` waits for that by an event. limit <= 0 writes
+ * count 0 only. A sharded handle is refused. */
+int wax_hip_timeline_device(wax_hip_engine* e, int32_t limit, int newest_first, const wax_hip_row_predicate* pred,
+                            uint64_t* d_out_ids, uint32_t* d_out_count, void* stream);
+
 /* ---- persistence: "MV2V" vec segment, encoding 2 ------------------------- */
 
 /* serialize() (MetalVectorEngine.swift:682-714): byte-identical layout
@@ -671,6 +698,15 @@ int wax_hip_mirror_select_probe(const int64_t* lists, uint32_t n_lists, int64_t*
  * keys there. out_partials[(q * grid + b) * 64 ..] = the 64 keys workgroup b keeps for query q: the smallest it was offered,
  * ascending, INT64_MAX behind them. Blocking. */
 int wax_hip_mirror_lists_probe(const int64_t* keys, uint32_t nq, uint64_t n_slots, uint32_t grid, int64_t* out_partials);
+/* Diagnostic of the timeline's two kernels on columns the caller makes up (tests make one workgroup walk many tiles and cut its buffer
+ * several times on a few thousand rows through it; no product path calls it, no tuning key exists for its grid). Host columns of
+ * n_rows (< 2^32) rows — timestamps NULL / flags NULL = zeros, frame_ids distinct — are uploaded to the current device, the selection
+ * runs with `grid` workgroups (0 = the product's own choice, at most 1 024) and the merge behind it, and out_ids[limit] (padded with
+ * UINT64_MAX), out_timestamps[limit] (may be NULL; padding 0) and *out_count come back. limit <= 0 gives count 0 and touches no
+ * device; limit > WAX_HIP_TIMELINE_MAX_LIMIT is refused. Blocking. */
+int wax_hip_timeline_probe(const int64_t* timestamps, const uint32_t* flags, const uint64_t* frame_ids, uint64_t n_rows,
+                           int32_t limit, int newest_first, const wax_hip_row_predicate* pred, uint32_t grid,
+                           uint64_t* out_ids, int64_t* out_timestamps, uint32_t* out_count);
 
 #ifdef __cplusplus
 }

@@ -241,6 +241,27 @@ public actor HIPVectorEngine {
         }
     }
 
+    /// `Wax.timeline(_:)` (Wax.swift:2108-2112; `TimelineQuery.filter`, TimelineQuery.swift:38-53) selected on the device from the
+    /// engine's attribute columns (`wax_hip_timeline`): the `limit` newest (`.reverseChronological`) or oldest frames that pass
+    /// `after` / `before` (before exclusive) and the deleted / superseded exclusions, equal timestamps in ascending frame id — the
+    /// order the stable sort over `toc.frames` gives. `limit` <= 0 returns nothing (:51); above 4 096 the library refuses.
+    public func timeline(_ query: TimelineQuery) async throws -> [(frameId: UInt64, timestamp: Int64)] {
+        let h = handle
+        let limit = max(0, min(query.limit, 4096))
+        let newest: Int32 = query.order == .reverseChronological ? 1 : 0
+        let deny: UInt32 = (query.includeDeleted ? 0 : 1) | (query.includeSuperseded ? 0 : 2)
+        let after = query.after, before = query.before, asked = query.limit
+        return try await io.run {
+            var ids = [UInt64](repeating: 0, count: limit)
+            var stamps = [Int64](repeating: 0, count: limit)
+            var n: UInt32 = 0
+            var pred: wax_hip_row_predicate = .init(has_after: after == nil ? 0 : 1, after: after ?? 0, has_before: before == nil ? 0 : 1,
+                                                    before: before ?? 0, deny_flags: deny)
+            try Self.check(wax_hip_timeline(h.raw, Int32(clamping: asked), newest, &pred, &ids, &stamps, UInt32(limit), &n))
+            return (0..<Int(n)).map { (frameId: ids[$0], timestamp: stamps[$0]) }
+        }
+    }
+
     /// Pending-embedding replay without the [[Float]] detour: WAL putEmbedding payloads (WALEntryCodec.encode,
     /// WALEntryCodec.swift:39-54) concatenated, validated and applied inside the library as one addBatch.
     /// UnifiedSearchEngineCache.applyPendingEmbeddingsIfNeeded (:252-283) can call this with the raw payloads.

@@ -169,6 +169,12 @@ SIGNATURES: Dict[str, tuple] = {
                                                    ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)]),
     "wax_hip_mirror_lists_probe": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
                                                   ctypes.POINTER(ctypes.c_int64)]),
+    "wax_hip_timeline": (ctypes.c_int, [_engine_p, ctypes.c_int32, ctypes.c_int, ctypes.POINTER(RowPredicate), _u64p,
+                                        ctypes.POINTER(ctypes.c_int64), ctypes.c_uint32, _u32p]),
+    "wax_hip_timeline_device": (ctypes.c_int, [_engine_p, ctypes.c_int32, ctypes.c_int, ctypes.POINTER(RowPredicate), ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p]),
+    "wax_hip_timeline_probe": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), _u32p, _u64p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int,
+                                              ctypes.POINTER(RowPredicate), ctypes.c_uint32, _u64p, ctypes.POINTER(ctypes.c_int64), _u32p]),
 }
 
 

@@ -12,6 +12,7 @@ int wax_hip_set_attributes(wax_hip_engine* e, const uint64_t* frame_ids, const i
     if (e->sh) return sh_set_attributes(e, frame_ids, timestamps, flags, n, out_applied);
     REFUSE_IF_HOLDING(e);
     WriteGuard w(e->lock);
+    sync_timeline_work(e);
     uint64_t applied = 0, lowest = UINT64_MAX;
     for (uint64_t i = 0; i < n; ++i) {
         const int64_t r = e->idmap.find(frame_ids[i]);

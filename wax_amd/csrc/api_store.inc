@@ -102,6 +102,11 @@ void wax_hip_engine_destroy(wax_hip_engine* e) {
         if (e->ring_ev1[i]) (void)hipEventDestroy(e->ring_ev1[i]);
         if (e->ring_done[i]) (void)hipEventDestroy(e->ring_done[i]);
     }
+    for (auto& t : e->tl_ring) {
+        (void)hipFree(t.d);
+        if (t.done) (void)hipEventDestroy(t.done);
+        if (t.cols) (void)hipEventDestroy(t.cols);
+    }
     {
         BatchMirror& b = e->batch;
         (void)hipFree(b.d_cb); (void)hipFree(b.d_vn2); (void)hipFree(b.d_maxnorm); (void)hipFree(b.d_dirty);

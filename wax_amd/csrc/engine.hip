@@ -46,6 +46,7 @@ using namespace wax;
 //   api_predicate.inc      C ABI: per-row attributes (set / get) and their device columns
 //   filter_host.inc        C ABI: the filtered searches — one query with an allow-list and / or a row predicate (one locked body), the batched allow-list form
 //   search_many.inc        C ABI: wax_hip_search_many[_predicate] — one query each against many stores of one device under one snapshot, the eligible pairs in one pooled launch, with a row predicate and a score cut per pair
+//   api_timeline.inc       C ABI: wax_hip_timeline[_device | _probe] — the newest / oldest passing rows by (timestamp, frame id), selected on the device from the attribute columns (TimelineQuery.swift:38-53)
 //   codec.inc              C ABI: MV2V encoding-2 serialize / deserialize (MetalVectorEngine.swift:682-815)
 //   tuning.inc             C ABI: stats, the tuning registry (set / get), the two timing microbenchmarks
 //   sharded.inc            the multi-GPU handle (one engine per device behind one handle): DESIGN 4.3
@@ -62,6 +63,7 @@ using namespace wax;
 #include "api_predicate.inc"
 #include "filter_host.inc"
 #include "search_many.inc"
+#include "api_timeline.inc"
 #include "codec.inc"
 #include "tuning.inc"
 }  // extern "C"

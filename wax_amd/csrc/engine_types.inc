@@ -496,6 +496,17 @@ struct wax_hip_engine {
     bool ring_busy[kShardRing] = {};
     std::mutex ring_mu[kShardRing];
     std::atomic<uint32_t> ring_next{0};
+    // wax_hip_timeline_device's scratch (api_timeline.inc): the partial lists of a launch on the CALLER's stream, in use until `done`
+    // (recorded behind the launch) has passed; `cols` orders the caller's stream behind the attribute upload. Entries are taken in
+    // turn, one user at a time, and waited for by every writer like the shard ring above.
+    struct TimelineRing {
+        std::mutex mu;
+        int64_t* d = nullptr;
+        uint64_t words = 0;
+        hipEvent_t done = nullptr, cols = nullptr;
+        bool busy = false;
+    } tl_ring[kShardRing];
+    std::atomic<uint32_t> tl_next{0};
 
     float* d_sink = nullptr;
     void* d_bounce = nullptr;
@@ -686,6 +697,18 @@ inline void cpu_relax() {   // a spin-wait hint, per architecture
 
 constexpr uint64_t kBounceBytes = 64ull << 20;
 
+// The same for wax_hip_timeline_device, which reads the id table and the attribute columns on its caller's stream: waited for by
+// every writer, wax_hip_set_attributes included (the next upload of the columns overwrites what such a launch reads).
+void sync_timeline_work(wax_hip_engine* e) {
+    for (auto& t : e->tl_ring) {
+        std::unique_lock<std::mutex> g(t.mu);
+        if (t.busy) {
+            (void)hipEventSynchronize(t.done);
+            t.busy = false;
+        }
+    }
+}
+
 // Wait until no shard-path work (wax_hip_search_shard_device: enqueued on caller streams, not synchronised by the
 // call) is in flight. Called by writers under the exclusive lock, so no new shard work can start meanwhile.
 void sync_shard_work(wax_hip_engine* e) {
@@ -696,6 +719,7 @@ void sync_shard_work(wax_hip_engine* e) {
             e->ring_busy[r] = false;
         }
     }
+    sync_timeline_work(e);
 }
 
 int holding(wax_hip_engine* e) {   // uncollected tickets submitted by the calling thread
@@ -755,6 +779,8 @@ int sh_get_attributes(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, 
 int sh_search_predicate(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, int has_allow, const uint64_t* allow,
                         uint64_t n_allow, int has_min, float min_score, const wax_hip_row_predicate* pred, uint64_t* out_ids,
                         float* out_scores, uint32_t capacity, uint32_t* out_count, bool caller_locked = false);
+int sh_timeline(wax_hip_engine* e, int32_t limit, int newest_first, const wax_hip_row_predicate* pred, uint64_t* out_ids, int64_t* out_ts,
+                uint32_t capacity, uint32_t* out_count);
 int sh_serialize(wax_hip_engine* e, uint8_t** out_bytes, size_t* out_len);
 int sh_deserialize(wax_hip_engine* e, const uint8_t* data, size_t len);
 void sh_destroy(wax_hip_engine* e);

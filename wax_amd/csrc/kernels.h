@@ -687,6 +687,33 @@ uint32_t scan_masked_chunk_rows(uint32_t dims);  // rows a wave consumes per ite
 // cap: 128 (k <= 64) or 256 (k <= 192). The per-workgroup lists go through launch_merge_keys / launch_select_short.
 hipError_t launch_scan_masked(const MaskedScanArgs& a, int metric, int cap, int grid_cap, hipStream_t st, int* out_grid);
 
+// ---- timeline.hip: the `limit` newest / oldest passing rows by (timestamp, frame id), from the attribute columns ----
+constexpr int TIMELINE_MAX_LIMIT = 4096;       // = WAX_HIP_TIMELINE_MAX_LIMIT = WAX_HIP_RRF_MAX_ENTRIES
+constexpr uint32_t TIMELINE_MAX_GRID = 1024;
+struct TimelineArgs {
+    const int64_t* ts;          // [n_rows] timestamps; null = every row 0
+    const uint32_t* flags;      // [n_rows] flag words; null = every row 0
+    const uint64_t* ids;        // [n_rows] frame ids by row; null = the row itself
+    uint64_t n_rows;            // may be 0: the answer is all padding
+    int32_t limit;              // 1 .. TIMELINE_MAX_LIMIT
+    int32_t newest;             // != 0: (timestamp descending, frame id ascending); 0: (timestamp ascending, frame id ascending)
+    int32_t has_after, has_before;
+    int64_t after, before;
+    uint32_t deny_flags;
+    uint64_t* out_ids;          // [limit], padded with ID_PAD
+    int64_t* out_ts;            // [limit] (padding 0); may be null
+    uint32_t* out_count;        // [1]
+    int64_t* part_t;            // set by launch_timeline from its scratch: [limit][grid] t' of each workgroup's list, position-major
+    uint64_t* part_id;          //                                          [limit][grid] their frame ids
+    uint32_t* part_cnt;         //                                          [grid] entries of each list
+    uint64_t tile_stride;       // set by launch_timeline: the walk's multiplier, coprime to the number of tiles
+};
+uint32_t timeline_grid(uint64_t n_rows, int32_t limit);           // the product's own number of scan workgroups
+uint64_t timeline_scratch_words(uint32_t grid, int32_t limit);    // int64 words of scratch a launch of `grid` workgroups needs
+// Two launches on `st`: timeline_select_kernel with `grid` workgroups (the event pair of launch_timing(), if armed, binds to it) and
+// timeline_merge_kernel with one. Nothing is synchronised; d_scratch is in use until both have run.
+hipError_t launch_timeline(const TimelineArgs& args, uint32_t grid, int64_t* d_scratch, hipStream_t st);
+
 // ---- rrf.hip: reciprocal-rank fusion of ranked id lists, one workgroup per query ----
 hipError_t launch_rrf_fuse(const wax_hip_rrf_lane* lanes, uint32_t n_lanes, uint32_t nq, int32_t k, uint64_t* out_ids,
                            float* out_scores, uint32_t* out_best_rank, uint32_t* out_sources, uint32_t out_stride,

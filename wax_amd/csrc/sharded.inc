@@ -1341,6 +1341,40 @@ int sh_get_attributes(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, 
     return WAX_HIP_OK;
 }
 
+// The timeline on a handle: every shard selects its own `limit` best rows (its columns follow its rows), side by side on the handle's
+// workers; the host merges them by the same pair order — (timestamp, frame id), the timestamp reversed for newest-first — so the
+// answer does not depend on which shard holds which frame.
+int sh_timeline(wax_hip_engine* e, int32_t limit, int newest_first, const wax_hip_row_predicate* pred, uint64_t* out_ids, int64_t* out_ts,
+                uint32_t capacity, uint32_t* out_count) {
+    ShardedState* s = e->sh;
+    *out_count = 0;
+    ReadGuard rd(e);
+    const size_t G = s->subs.size(), L = (size_t)limit;
+    std::vector<uint64_t> g_ids(G * L);
+    std::vector<int64_t> g_ts(G * L);
+    std::vector<uint32_t> g_m(G, 0);
+    std::vector<int> rcs(G, WAX_HIP_OK);
+    std::vector<std::string> errs(G);
+    auto one = [&](size_t g) {
+        rcs[g] = wax_hip_timeline(s->subs[g], limit, newest_first, pred, g_ids.data() + g * L, g_ts.data() + g * L, (uint32_t)limit, &g_m[g]);
+        if (rcs[g] != WAX_HIP_OK) errs[g] = g_last_error;   // thread-local: carry it to the caller
+    };
+    if (G == 1) one(0); else s->workers.run_all(one);
+    std::vector<std::pair<int64_t, uint64_t>> all;
+    for (size_t g = 0; g < G; ++g) {
+        if (rcs[g] != WAX_HIP_OK) return fail(rcs[g], errs[g]);
+        for (uint32_t i = 0; i < g_m[g]; ++i) all.emplace_back(newest_first != 0 ? ~g_ts[g * L + i] : g_ts[g * L + i], g_ids[g * L + i]);
+    }
+    std::sort(all.begin(), all.end());                       // lexicographic: signed t', then unsigned frame id
+    const size_t n = std::min(all.size(), std::min(L, (size_t)capacity));
+    for (size_t i = 0; i < n; ++i) {
+        out_ids[i] = all[i].second;
+        if (out_ts) out_ts[i] = newest_first != 0 ? ~all[i].first : all[i].first;
+    }
+    *out_count = (uint32_t)n;
+    return WAX_HIP_OK;
+}
+
 // Batched form: every shard answers the whole batch on its own rows (its own batched filtered call, on the handle's workers, in
 // parallel); then each query is merged exactly as sh_search_filtered merges one: stable by score, shard order on ties, then the cut.
 // preds (null: none) go to every shard as they are: a row's attributes live with the shard that owns the row.

@@ -19,6 +19,7 @@ from .vector_metric import VectorMetric
 
 MAX_EMBEDDING_DIMENSIONS = 1_000_000  # Constants.maxEmbeddingDimensions (WaxCore/Constants.swift:51)
 MAX_RESULTS = 10_000                  # MetalVectorEngine.maxResults (:18)
+TIMELINE_MAX_LIMIT = 4096             # WAX_HIP_TIMELINE_MAX_LIMIT (include/wax_hip.h): the longest lane the fusion takes
 
 
 def _as_f32(a) -> np.ndarray:
@@ -339,6 +340,38 @@ class HIPVectorEngine:
             raise_for_status(rc)
         return ts, fl, found.astype(bool)
 
+    def timeline(self, limit: int, newestFirst: bool = True, timeRange=None, denyFlags: int = 0) -> Tuple[np.ndarray, np.ndarray]:  # noqa: N803
+        """Wax.timeline(TimelineQuery) (TimelineQuery.swift:38-53) on the device: the `limit` newest (newestFirst) or oldest frames
+        that pass `timeRange` = (after | None, before | None) and `denyFlags` (searchFiltered's meaning), ordered by timestamp and,
+        among equal timestamps, by ascending frame id. Returns (frame ids uint64, timestamps int64). limit <= 0 returns nothing;
+        limit > TIMELINE_MAX_LIMIT is refused."""
+        limit = int(max(min(limit, 2**31 - 1), -2**31))
+        pred = ticket_predicate(timeRange, denyFlags, who="timeline")
+        cap = max(0, min(limit, TIMELINE_MAX_LIMIT))
+        ids = np.empty(cap, dtype=np.uint64)
+        ts = np.empty(cap, dtype=np.int64)
+        got = ctypes.c_uint32(0)
+        rc = self._lib.wax_hip_timeline(self._h, limit, 1 if newestFirst else 0, ctypes.byref(pred), _u64p(ids),
+                                        ts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), cap, ctypes.byref(got))
+        raise_for_status(rc)
+        return ids[:got.value].copy(), ts[:got.value].copy()
+
+    def timelineDevice(self, limit: int, out_ids, out_count, newestFirst: bool = True, timeRange=None, denyFlags: int = 0,  # noqa: N802,N803
+                       stream: int = 0) -> None:
+        """timeline() left in HBM (wax_hip_timeline_device): `out_ids` a torch uint64 / int64 tensor of at least `limit` elements and
+        `out_count` one of at least one 32-bit element, both on this engine's device. Exactly `limit` ids are written, padded
+        with UInt64.max, and the real count; the work is enqueued on `stream` (a raw hipStream_t, 0 = the null stream) and not
+        synchronised — the ids are a lane for wax_hip_rrf_fuse_batch_device (stride = limit, pitch = 1) on the same stream."""
+        limit = int(max(min(limit, 2**31 - 1), -2**31))
+        pred = ticket_predicate(timeRange, denyFlags, who="timelineDevice")
+        for t, width, need, what in ((out_ids, 8, max(limit, 0), "out_ids"), (out_count, 4, 1, "out_count")):
+            if not getattr(t, "is_cuda", False) or not t.is_contiguous() or t.element_size() != width or t.numel() < need:
+                raise EncodingError(f"timelineDevice: {what} must be a contiguous device tensor of {need} {width}-byte elements")
+        rc = self._lib.wax_hip_timeline_device(self._h, limit, 1 if newestFirst else 0, ctypes.byref(pred),
+                                               ctypes.c_void_p(out_ids.data_ptr()), ctypes.c_void_p(out_count.data_ptr()),
+                                               ctypes.c_void_p(stream))
+        raise_for_status(rc)
+
     def searchFilteredHits(self, vector, topK: int, allow) -> List[Tuple[int, float]]:  # noqa: N802,N803
         """searchFiltered as [(frameId, score)] (the shape the transcribed reference cases assert on)."""
         ids, scores = self.searchFiltered(vector, topK, frameIds=allow)
@@ -627,16 +660,41 @@ def searchMany(engines, queries, topK: int):  # noqa: N802,N803
     return ids, scores, counts
 
 
-def ticket_predicate(timeRange=None, denyFlags=0) -> "_abi.RowPredicate":  # noqa: N803
-    """submitFiltered's row predicate: `timeRange` None or (after | None, before | None), `denyFlags` a mask of 32 bits."""
+def timelineProbe(timestamps, flags, frameIds, limit: int, newestFirst: bool = True, timeRange=None, denyFlags: int = 0,  # noqa: N802,N803
+                  grid: int = 0):
+    """wax_hip_timeline_probe: the timeline's two kernels on host columns (`timestamps` / `flags` None = zeros), the selection run
+    with `grid` workgroups (0 = the product's choice). Returns (ids[limit] padded with UInt64.max, timestamps[limit], count)."""
+    ids = np.ascontiguousarray(frameIds, dtype=np.uint64).reshape(-1)
+    n = int(ids.size)
+    ts = None if timestamps is None else np.ascontiguousarray(timestamps, dtype=np.int64).reshape(-1)
+    fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint32).reshape(-1)
+    if (ts is not None and ts.size != n) or (fl is not None and fl.size != n):
+        raise EncodingError("timelineProbe: one timestamp / flag word per frame id")
+    limit = int(limit)
+    pred = ticket_predicate(timeRange, denyFlags, who="timelineProbe")
+    cap = max(0, min(limit, TIMELINE_MAX_LIMIT))
+    out_ids = np.zeros(cap, dtype=np.uint64)
+    out_ts = np.zeros(cap, dtype=np.int64)
+    got = ctypes.c_uint32(0)
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    rc = _abi.lib().wax_hip_timeline_probe(None if ts is None else ts.ctypes.data_as(i64p),
+                                           None if fl is None else fl.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                           _u64p(ids), n, limit, 1 if newestFirst else 0, ctypes.byref(pred), int(grid),
+                                           _u64p(out_ids), out_ts.ctypes.data_as(i64p), ctypes.byref(got))
+    raise_for_status(rc)
+    return out_ids, out_ts, int(got.value)
+
+
+def ticket_predicate(timeRange=None, denyFlags=0, who: str = "submitFiltered") -> "_abi.RowPredicate":  # noqa: N803
+    """submitFiltered's (and the timeline's) row predicate: `timeRange` None or (after | None, before | None), `denyFlags` a mask of 32 bits."""
     if timeRange is not None and (not isinstance(timeRange, (tuple, list)) or len(timeRange) != 2):
-        raise EncodingError("submitFiltered: timeRange must be None or (after | None, before | None)")
+        raise EncodingError(f"{who}: timeRange must be None or (after | None, before | None)")
     after, before = (None, None) if timeRange is None else timeRange
     for bound in (after, before):
         if bound is not None and not (isinstance(bound, (int, np.integer)) and -2**63 <= int(bound) < 2**63):
-            raise EncodingError("submitFiltered: a timeRange bound must be an int64 or None")
+            raise EncodingError(f"{who}: a timeRange bound must be an int64 or None")
     if not isinstance(denyFlags, (int, np.integer)) or not 0 <= int(denyFlags) <= 0xffffffff:
-        raise EncodingError("submitFiltered: denyFlags must be a mask of 32 bits")
+        raise EncodingError(f"{who}: denyFlags must be a mask of 32 bits")
     return _abi.RowPredicate(0 if after is None else 1, 0 if after is None else int(after),
                              0 if before is None else 1, 0 if before is None else int(before), int(denyFlags))
 
