@@ -496,6 +496,72 @@ int wax_hip_timeline(wax_hip_engine* e, int32_t limit, int newest_first, const w
 int wax_hip_timeline_device(wax_hip_engine* e, int32_t limit, int newest_first, const wax_hip_row_predicate* pred,
                             uint64_t* d_out_ids, uint32_t* d_out_count, void* stream);
 
+/* ---- grouped search: best parents by best member, members per parent ---------------------------------------------- *
+ * What PhotoRAGOrchestrator.recall (PhotoRAGOrchestrator.swift:264-317) and VideoRAGOrchestrator.recall
+ * (VideoRAGOrchestrator.swift:252, 273-417) do with the vector lane's answer: collapse the hits by `meta.parentId ?? meta.id`, score a
+ * root by its best member (`entry.score = max(entry.score, result.score)`), order roots by (score descending, rootId ascending), keep
+ * resultLimit roots (default 12) and, for video, segmentLimitPerVideo (default 3) best segments per root. The reference over-fetches
+ * rows (topK = max(400, resultLimit * segmentLimitPerVideo * 8); 200 for photos) and collapses on the host, which returns too few or
+ * the wrong roots when one root owns the over-fetched prefix. Here one pass over the store answers exactly.
+ *
+ * A third optional per-row column carries a uint64 parent id beside the two attribute columns above, under their lifecycle word for
+ * word: a store on which parents were never set allocates nothing and every row is its own root; an appended row gets
+ * WAX_HIP_NO_PARENT; an upsert keeps its row's parent; removals take the row's entry with them; reserve and growth keep the column; a
+ * move between shards carries it; wax_hip_deserialize drops it (MV2V has no field for it, and wax_hip_serialize is unchanged). The
+ * host copy is authoritative; the device copy is brought up to date by the first grouped search after a change. A row's ROOT is its
+ * parent, or its own frame id where the parent is WAX_HIP_NO_PARENT (`meta.parentId ?? meta.id`, PhotoRAGOrchestrator.swift:282,
+ * VideoRAGOrchestrator.swift:314). A root need not be a frame the engine holds: roots often have no embedding. */
+#define WAX_HIP_NO_PARENT UINT64_MAX
+/* FrameMeta.parentId of the listed frames (the value PhotoRAGOrchestrator.swift:282 / VideoRAGOrchestrator.swift:314 read). Writer and
+ * reader exactly as wax_hip_set_attributes / wax_hip_get_attributes are: ids the engine does not hold are skipped, an id listed twice
+ * takes its last entry, *out_applied (may be NULL) = entries that named a held frame, a thread that holds uncollected search tickets is
+ * refused, a sharded handle routes every id to the shard that owns it. out_found[i] = 1 and the row's parent, or 0 and
+ * WAX_HIP_NO_PARENT for an id the engine does not hold; either output array may be NULL. */
+int wax_hip_set_parents(wax_hip_engine* e, const uint64_t* frame_ids, const uint64_t* parent_ids, uint64_t n, uint64_t* out_applied);
+int wax_hip_get_parents(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, uint64_t* out_parents, uint8_t* out_found);
+#define WAX_HIP_GROUP_MAX_LIMIT   1024
+#define WAX_HIP_GROUP_MAX_MEMBERS 8
+/* The `limit` best roots and, per root, its `per_group` best rows (PhotoRAGOrchestrator.swift:264-317 with per_group 1;
+ * VideoRAGOrchestrator.swift:273-417 with per_group = segmentLimitPerVideo). Blocking; a reader: shared lock, rows staged by
+ * wax_hip_add are seen, re-entrant for a thread that holds tickets. The answer, exactly:
+ *  1. Only rows that pass pred take part (wax_hip_row_predicate's rule; NULL = every row). A row whose distance is not finite takes
+ *     no part, as in wax_hip_search.
+ *  2. A group is the set of participating rows with one root; its distance is the smallest distance among its rows — the bits
+ *     wax_hip_search gives those rows.
+ *  3. Groups are ordered by (distance ascending, root id ascending as unsigned): the tie goes by ROOT ID, not by row — what both
+ *     orchestrators sort by (PhotoRAGOrchestrator.swift:313, VideoRAGOrchestrator.swift:385-388), and what makes the answer
+ *     independent of the store's mutation history and of sharding.
+ *  4. The first `limit` groups are returned: out_root_ids[g], and out_root_scores[g] = VectorMetric.score(fromDistance:) of the
+ *     group's distance.
+ *  5. Within a returned group the per_group best rows by (distance ascending, row ascending), the tie rule of every search route:
+ *     out_member_ids[g * per_group + j], out_member_scores likewise. Member 0 is the row that gave the group its distance.
+ *  6. Unused member slots are padded with UINT64_MAX / 0.0f; out_member_counts[g] (may be NULL) = members written for group g.
+ *  7. With has_min_score, groups whose score is below min_score are dropped, as are members below it (on the host, as elsewhere).
+ * out_root_ids / out_root_scores: [limit]. out_member_ids / out_member_scores: [limit][per_group], both NULL = no members wanted.
+ * *out_count = groups written. limit <= 0: count 0, no device touched. per_group < 1 is read as 1. An empty engine gives count 0.
+ * Refused with the outputs untouched: limit > WAX_HIP_GROUP_MAX_LIMIT, per_group > WAX_HIP_GROUP_MAX_MEMBERS, a NULL engine, query,
+ * out_count or root array, one member array without the other, a dimension mismatch (the reference's message). On a store where no
+ * parent was ever set the same machinery runs with one group per row; there is no shortcut through wax_hip_search, whose tie rule is
+ * by row. All three metrics and every dimension are served: the dimensions of the lane-shape table by one fused pass that offers every
+ * row's key to its group's slot by a 64-bit atomic minimum, the others (and "force_general") by the distance column and the same
+ * offers. A sharded handle serves per_group == 1: every shard answers `limit` groups, the host keeps the smaller distance per root,
+ * sorts by (distance, root id) and takes `limit` — exact, because a root among the global first `limit` is, on the shard that holds
+ * its best row, beaten only by roots that beat it globally. per_group > 1 on a handle is refused: a shard that did not rank a root
+ * cannot say what its members there are. No allow-list, no ticket form, no batched form. */
+int wax_hip_search_grouped(wax_hip_engine* e, const float* query, uint32_t dims, int32_t limit, int32_t per_group,
+                           int has_min_score, float min_score, const wax_hip_row_predicate* pred,
+                           uint64_t* out_root_ids, float* out_root_scores,
+                           uint64_t* out_member_ids, float* out_member_scores,
+                           uint32_t* out_member_counts, uint32_t* out_count);
+/* What the grouped searches of this engine did, in the way of wax_hip_predicate_ticket_stats (a read-out, no tuning key): searches
+ * that reached the device, of which fused_scans took the one-pass scan and column_scans the distance column; member_rounds launched;
+ * group_slots of the latest search (rows, on a store without parents); parent_rows_uploaded = rows of the slot column sent to the
+ * device so far. A sharded handle reports the sums over its shards (group_slots: the sum of the shards' latest). */
+typedef struct wax_hip_group_stats_t {
+    uint64_t searches, fused_scans, column_scans, member_rounds, group_slots, parent_rows_uploaded;
+} wax_hip_group_stats_t;
+int wax_hip_group_stats(wax_hip_engine* e, wax_hip_group_stats_t* out);
+
 /* ---- persistence: "MV2V" vec segment, encoding 2 ------------------------- */
 
 /* serialize() (MetalVectorEngine.swift:682-714): byte-identical layout
@@ -707,6 +773,17 @@ int wax_hip_mirror_lists_probe(const int64_t* keys, uint32_t nq, uint64_t n_slot
 int wax_hip_timeline_probe(const int64_t* timestamps, const uint32_t* flags, const uint64_t* frame_ids, uint64_t n_rows,
                            int32_t limit, int newest_first, const wax_hip_row_predicate* pred, uint32_t grid,
                            uint64_t* out_ids, int64_t* out_timestamps, uint32_t* out_count);
+/* Diagnostic of the grouped search's selection on distances the caller makes up (tests set them bit for bit; no product path calls it).
+ * Host columns of n_rows (< 2^32) rows — distances, slots (NULL = every row its own slot, n_slots >= n_rows), slot_root[n_slots]
+ * (NULL = the slot's number), bitmap of ceil(n_rows / 32) words (NULL = every row takes part) — are uploaded to the current device;
+ * the column route's offer kernel and the member rounds run with `grid` workgroups (0 = the product's own choice, at most 1 024),
+ * the selection and the marking between them. Back come out_root_ids[limit] (padded with UINT64_MAX), out_root_keys[limit] (each
+ * group's best key, distance bits : row; padding INT64_MAX), out_member_keys[limit][per_group] (may be NULL; padding INT64_MAX) and
+ * *out_count. limit <= 0 gives count 0 and touches no device; limit > WAX_HIP_GROUP_MAX_LIMIT, per_group outside
+ * 1 .. WAX_HIP_GROUP_MAX_MEMBERS and a slot >= n_slots are refused. Blocking. */
+int wax_hip_group_probe(const float* distances, const uint32_t* slots, const uint64_t* slot_root, const uint32_t* bitmap,
+                        uint64_t n_rows, uint32_t n_slots, int32_t limit, int32_t per_group, uint32_t grid,
+                        uint64_t* out_root_ids, int64_t* out_root_keys, int64_t* out_member_keys, uint32_t* out_count);
 
 #ifdef __cplusplus
 }

@@ -117,6 +117,39 @@ class VectorEngine {
                                          frameIds.size(), &applied));
         return applied;
     }
+    /// FrameMeta.parentId of the listed frames for searchGrouped (wax_hip_set_parents): WAX_HIP_NO_PARENT = the frame is its own root.
+    uint64_t setParents(const std::vector<uint64_t>& frameIds, const std::vector<uint64_t>& parentIds) {
+        uint64_t applied = 0;
+        if (frameIds.size() != parentIds.size()) throw std::runtime_error("setParents: one parent id per frame id");
+        if (!frameIds.empty()) check(wax_hip_set_parents(h_, frameIds.data(), parentIds.data(), frameIds.size(), &applied));
+        return applied;
+    }
+    /// One root of a grouped answer: its id, its score (its best member's) and its best members, best first.
+    struct Group {
+        uint64_t rootId;
+        float score;
+        std::vector<std::pair<uint64_t, float>> members;
+    };
+    /// The `limit` best roots by their best member and the perGroup best rows of each (wax_hip_search_grouped): what
+    /// PhotoRAGOrchestrator.recall / VideoRAGOrchestrator.recall make of the vector lane, exactly. pred null = every row takes part.
+    std::vector<Group> searchGrouped(const std::vector<float>& q, int limit, int perGroup, const float* minScore,
+                                     const wax_hip_row_predicate* pred) {
+        const uint32_t cap = limit > 0 ? (uint32_t)(limit < WAX_HIP_GROUP_MAX_LIMIT ? limit : WAX_HIP_GROUP_MAX_LIMIT) : 0u;
+        const uint32_t width = perGroup < 1 ? 1u : (uint32_t)(perGroup < WAX_HIP_GROUP_MAX_MEMBERS ? perGroup : WAX_HIP_GROUP_MAX_MEMBERS);
+        std::vector<uint64_t> roots(cap ? cap : 1), mids((size_t)(cap ? cap : 1) * width);
+        std::vector<float> scores(cap ? cap : 1), mscores((size_t)(cap ? cap : 1) * width);
+        std::vector<uint32_t> counts(cap ? cap : 1);
+        uint32_t n = 0;
+        check(wax_hip_search_grouped(h_, q.data(), (uint32_t)q.size(), limit, perGroup, minScore ? 1 : 0, minScore ? *minScore : 0.0f, pred,
+                                     roots.data(), scores.data(), mids.data(), mscores.data(), counts.data(), &n));
+        std::vector<Group> out(n);
+        for (uint32_t g = 0; g < n; ++g) {
+            out[g].rootId = roots[g];
+            out[g].score = scores[g];
+            for (uint32_t j = 0; j < counts[g]; ++j) out[g].members.push_back({mids[(size_t)g * width + j], mscores[(size_t)g * width + j]});
+        }
+        return out;
+    }
     /// searchFiltered plus the row predicate (time range, denied flag bits): best topK among the frames that pass.
     std::vector<std::pair<uint64_t, float>> searchPredicate(const std::vector<float>& q, int topK, const std::vector<uint64_t>* allow,
                                                             const float* minScore, const wax_hip_row_predicate& pred) {

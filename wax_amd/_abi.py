@@ -74,6 +74,16 @@ class PredicateTicketStats(ctypes.Structure):
                                                      "host_decided", "bitmap_builds", "bitmap_hits")]
 
 
+class GroupStats(ctypes.Structure):
+    """wax_hip_group_stats_t (include/wax_hip.h)."""
+    _fields_ = [(name, ctypes.c_uint64) for name in ("searches", "fused_scans", "column_scans", "member_rounds", "group_slots",
+                                                     "parent_rows_uploaded")]
+
+
+NO_PARENT = (1 << 64) - 1       # WAX_HIP_NO_PARENT: the row is its own root
+GROUP_MAX_LIMIT = 1024          # WAX_HIP_GROUP_MAX_LIMIT
+GROUP_MAX_MEMBERS = 8           # WAX_HIP_GROUP_MAX_MEMBERS
+
 # wax_hip_set_attributes flag bits (WAX_HIP_FLAG_*); bits 8..31 are the caller's
 FLAG_DELETED = 0x1
 FLAG_SUPERSEDED = 0x2
@@ -175,6 +185,13 @@ SIGNATURES: Dict[str, tuple] = {
                                                ctypes.c_void_p, ctypes.c_void_p]),
     "wax_hip_timeline_probe": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), _u32p, _u64p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int,
                                               ctypes.POINTER(RowPredicate), ctypes.c_uint32, _u64p, ctypes.POINTER(ctypes.c_int64), _u32p]),
+    "wax_hip_set_parents": (ctypes.c_int, [_engine_p, _u64p, _u64p, ctypes.c_uint64, _u64p]),
+    "wax_hip_get_parents": (ctypes.c_int, [_engine_p, _u64p, ctypes.c_uint64, _u64p, _u8p]),
+    "wax_hip_search_grouped": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_float,
+                                              ctypes.POINTER(RowPredicate), _u64p, _f32p, _u64p, _f32p, _u32p, _u32p]),
+    "wax_hip_group_stats": (ctypes.c_int, [_engine_p, ctypes.POINTER(GroupStats)]),
+    "wax_hip_group_probe": (ctypes.c_int, [_f32p, _u32p, _u64p, _u32p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32,
+                                           ctypes.c_uint32, _u64p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _u32p]),
 }
 
 

@@ -117,6 +117,7 @@ void wax_hip_engine_destroy(wax_hip_engine* e) {
         for (FilterWork* f : e->filter_all) free_filter_work(f);
         (void)hipFree(e->idhash.d_table);
         (void)hipFree(e->d_attr_ts); (void)hipFree(e->d_attr_flags);
+        (void)hipFree(e->d_grp_slot); (void)hipFree(e->d_grp_root);
         for (PredEntry& p : e->pred_entries) {
             (void)hipFree(p.d_bitmap); (void)hipFree(p.d_counts); (void)hipHostFree(p.h_counts);
             if (p.built_ev) (void)hipEventDestroy(p.built_ev);
@@ -412,18 +413,24 @@ int wax_hip_remove_batch(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t 
             e->idmap.renumber_removed(rem, e->count);
             {
                 // the id vector and the two attribute columns (which may end below `count`: the rows behind them are (0, 0)) in one pass
-                const uint64_t na = e->attr_ts.size();
-                uint64_t wr = rem[0], wa = rem[0];
+                const uint64_t na = e->attr_ts.size(), np = e->attr_parent.size();
+                uint64_t wr = rem[0], wa = rem[0], wp = rem[0];
                 size_t p = 0;
                 for (uint64_t r = rem[0]; r < e->count; ++r) {
                     if (p < m && rem[p] == r) { ++p; continue; }
                     e->ids[wr++] = e->ids[r];
                     if (r < na) { e->attr_ts[wa] = e->attr_ts[r]; e->attr_flags[wa] = e->attr_flags[r]; ++wa; }
+                    if (r < np) e->attr_parent[wp++] = e->attr_parent[r];
                 }
                 e->ids.resize((size_t)wr);
                 if (rem[0] < na) {
                     e->attr_ts.resize((size_t)wa); e->attr_flags.resize((size_t)wa);
                     attr_note_moved(e, rem[0]);
+                }
+                if (np != 0) {                                 // the parent column likewise; rows behind it shift their slot entries all the same
+                    if (rem[0] < np) e->attr_parent.resize((size_t)wp);
+                    if (e->attr_parent.empty()) parent_note_replaced(e);
+                    else parent_note_moved(e, rem[0]);
                 }
             }
             e->count -= m;                                     // :441, m times

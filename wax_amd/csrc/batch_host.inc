@@ -39,7 +39,23 @@ static void mirror_note_replaced(wax_hip_engine* e) {       // deserialize: ever
 static void attr_note_moved(wax_hip_engine* e, uint64_t row) {
     if (row < e->attr_stale_from) e->attr_stale_from = row;
 }
+// The same hooks for the parent column (DESIGN 4.10). A store without parents has no slot column to keep: nothing is marked there.
+static void parent_note_moved(wax_hip_engine* e, uint64_t row) {
+    if (!e->attr_parent.empty() && row < e->grp_stale_from) e->grp_stale_from = row;
+}
+static void parent_note_replaced(wax_hip_engine* e) {             // every row is its own root again
+    e->attr_parent.clear();
+    e->grp_slot_of.clear(); e->grp_slot_root.clear(); e->grp_slot.clear();
+    e->grp_rows = 0; e->grp_stale_from = UINT64_MAX; e->grp_root_dev = 0;
+}
+static void parent_note_remove(wax_hip_engine* e, uint64_t idx) {
+    if (e->attr_parent.empty()) return;
+    if (idx < e->attr_parent.size()) e->attr_parent.erase(e->attr_parent.begin() + (ptrdiff_t)idx);
+    if (e->attr_parent.empty()) parent_note_replaced(e);          // every row left is its own root: a store without parents
+    else parent_note_moved(e, idx);                                // (a row behind the column shifts its slot entry all the same)
+}
 static void attr_note_remove(wax_hip_engine* e, uint64_t idx) {   // remove(frameId:): the entry leaves as the id does
+    parent_note_remove(e, idx);
     if (idx >= e->attr_ts.size()) return;                          // the row was (0, 0) like everything behind it
     e->attr_ts.erase(e->attr_ts.begin() + (ptrdiff_t)idx);
     e->attr_flags.erase(e->attr_flags.begin() + (ptrdiff_t)idx);
@@ -48,6 +64,7 @@ static void attr_note_remove(wax_hip_engine* e, uint64_t idx) {   // remove(fram
 static void attr_note_replaced(wax_hip_engine* e) {               // deserialize / a shard emptied: every row is (0, 0) again
     e->attr_ts.clear(); e->attr_flags.clear();
     e->attr_stale_from = 0; e->attr_dev_rows = 0;
+    parent_note_replaced(e);
 }
 // a mutation the mirror could not follow (a failed row shift): convert everything at the next use
 static void mirror_note_lost(wax_hip_engine* e) {

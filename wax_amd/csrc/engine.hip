@@ -21,6 +21,7 @@
 #include <string>
 #include <thread>
 #include <tuple>
+#include <unordered_map>
 #include <vector>
 
 #include "kernels.h"
@@ -47,6 +48,7 @@ using namespace wax;
 //   filter_host.inc        C ABI: the filtered searches — one query with an allow-list and / or a row predicate (one locked body), the batched allow-list form
 //   search_many.inc        C ABI: wax_hip_search_many[_predicate] — one query each against many stores of one device under one snapshot, the eligible pairs in one pooled launch, with a row predicate and a score cut per pair
 //   api_timeline.inc       C ABI: wax_hip_timeline[_device | _probe] — the newest / oldest passing rows by (timestamp, frame id), selected on the device from the attribute columns (TimelineQuery.swift:38-53)
+//   api_grouped.inc        C ABI: wax_hip_set_parents / get_parents, wax_hip_search_grouped, wax_hip_group_stats, wax_hip_group_probe — the parent column and the best roots by their best member, members per root (PhotoRAGOrchestrator.swift:264-317, VideoRAGOrchestrator.swift:273-417)
 //   codec.inc              C ABI: MV2V encoding-2 serialize / deserialize (MetalVectorEngine.swift:682-815)
 //   tuning.inc             C ABI: stats, the tuning registry (set / get), the two timing microbenchmarks
 //   sharded.inc            the multi-GPU handle (one engine per device behind one handle): DESIGN 4.3
@@ -64,6 +66,7 @@ using namespace wax;
 #include "filter_host.inc"
 #include "search_many.inc"
 #include "api_timeline.inc"
+#include "api_grouped.inc"
 #include "codec.inc"
 #include "tuning.inc"
 }  // extern "C"

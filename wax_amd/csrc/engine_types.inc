@@ -634,7 +634,26 @@ struct wax_hip_engine {
     uint64_t attr_cap = 0, attr_dev_rows = 0;
     uint64_t attr_stale_from = UINT64_MAX;        // lowest row whose device copy may differ from the host's
     std::atomic<uint64_t> st_attr_uploaded{0};
-    std::atomic<int64_t> predicate_route{0};      // 0 = auto, 1 = always gather the passing rows, 2 = the masked scan wherever it is eligible
+    // The parent column (wax_hip_set_parents; DESIGN 4.10): a third host column under the rules of the two above — authoritative, in row
+    // order, possibly SHORTER than the store (rows at or beyond its length are WAX_HIP_NO_PARENT, what every appended row is), empty on
+    // a store that never had parents. Writers change it under the exclusive engine lock.
+    std::vector<uint64_t> attr_parent;
+    // What the grouped search derives from it (ensure_groups, api_grouped.inc, under grp_mu and the shared engine lock): roots numbered
+    // densely — grp_slot_of maps a root id to its slot, grp_slot_root back, grp_slot is the slot of every row. Slots are stable under
+    // removal and renumbered from scratch once there are more than twice as many as rows. Rows [0, grp_rows) below grp_stale_from are
+    // current on the host and on the device; writers only lower grp_stale_from. Nothing of this exists while attr_parent is empty.
+    std::mutex grp_mu;
+    std::unordered_map<uint64_t, uint32_t> grp_slot_of;
+    std::vector<uint64_t> grp_slot_root;
+    std::vector<uint32_t> grp_slot;
+    uint64_t grp_rows = 0;
+    uint64_t grp_stale_from = UINT64_MAX;
+    uint32_t* d_grp_slot = nullptr;               // [grp_cap]
+    uint64_t* d_grp_root = nullptr;               // [grp_root_cap], the first grp_root_dev entries uploaded
+    uint64_t grp_cap = 0, grp_root_cap = 0, grp_root_dev = 0;
+    // wax_hip_group_stats (a read-out, no tuning key)
+    std::atomic<uint64_t> gs_searches{0}, gs_fused_scans{0}, gs_column_scans{0}, gs_member_rounds{0}, gs_group_slots{0}, gs_parent_rows_uploaded{0};
+    std::atomic<int64_t> predicate_route{0};     // 0 = auto, 1 = always gather the passing rows, 2 = the masked scan wherever it is eligible
     // auto rule: the masked scan when at least this many rows per thousand pass. 500 = the random mask's crossover of the FIRST build
     // (between 1/8 and 1/2 passing, profiles/r13/c_routes_first_build.json). At 10M rows the committed f32 scan crosses the gather
     // between 1/2 and 15/16, its mirror form between 1/8 and 1/2 (profiles/r20/predicate_mirror.json; DESIGN 4.5): not retuned.
@@ -781,6 +800,12 @@ int sh_search_predicate(wax_hip_engine* e, const float* query, uint32_t dims, in
                         float* out_scores, uint32_t capacity, uint32_t* out_count, bool caller_locked = false);
 int sh_timeline(wax_hip_engine* e, int32_t limit, int newest_first, const wax_hip_row_predicate* pred, uint64_t* out_ids, int64_t* out_ts,
                 uint32_t capacity, uint32_t* out_count);
+int sh_set_parents(wax_hip_engine* e, const uint64_t* frame_ids, const uint64_t* parent_ids, uint64_t n, uint64_t* out_applied);
+int sh_get_parents(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, uint64_t* out_parents, uint8_t* out_found);
+int sh_search_grouped(wax_hip_engine* e, const float* query, uint32_t dims, int32_t limit, int32_t per_group, int has_min_score, float min_score,
+                      const wax_hip_row_predicate* pred, uint64_t* out_root_ids, float* out_root_scores, uint64_t* out_member_ids,
+                      float* out_member_scores, uint32_t* out_member_counts, uint32_t* out_count);
+int sh_group_stats(wax_hip_engine* e, wax_hip_group_stats_t* out);
 int sh_serialize(wax_hip_engine* e, uint8_t** out_bytes, size_t* out_len);
 int sh_deserialize(wax_hip_engine* e, const uint8_t* data, size_t len);
 void sh_destroy(wax_hip_engine* e);

@@ -714,6 +714,56 @@ uint64_t timeline_scratch_words(uint32_t grid, int32_t limit);    // int64 words
 // timeline_merge_kernel with one. Nothing is synchronised; d_scratch is in use until both have run.
 hipError_t launch_timeline(const TimelineArgs& args, uint32_t grid, int64_t* d_scratch, hipStream_t st);
 
+// ---- grouped.hip: the `limit` best groups by their best row, and the best rows of each ----
+constexpr int GROUP_MAX_LIMIT = 1024;          // = WAX_HIP_GROUP_MAX_LIMIT
+constexpr int GROUP_MAX_MEMBERS = 8;           // = WAX_HIP_GROUP_MAX_MEMBERS
+// The fused scan: scan_body's streaming loop (kernels.hip) with the offer in the place of the LDS lists. The owner lane of a valid row
+// whose bitmap bit is set (or with no bitmap) and whose distance is finite writes dist_out[row] (if not null) and offers
+// make_key(distance, row) to best[slot of the row]. `best` holds KEY_PAD in every slot before the launch (launch_group_fill).
+struct GroupScanArgs {
+    const float* store;         // [n_rows][dims] f32
+    const float* query;         // [dims] f32 in HBM
+    const uint32_t* bitmap;     // [ceil(n_rows / 32)] rows that take part; null = every row
+    const uint32_t* slots;      // [n_rows] group slot of every row; null = slot = row
+    int64_t* best;              // [n_slots] smallest key offered to the slot
+    float* dist_out;            // [n_rows] distances of the rows that take part (the rounds read only those); null = not wanted
+    uint32_t n_rows, n_slots, dims;
+    float q_norm;
+};
+bool group_scan_dims(uint32_t dims);            // = the lane-shape table
+hipError_t launch_group_fill(int64_t* best, uint64_t n, hipStream_t st);   // best[0 .. n) = KEY_PAD
+hipError_t launch_group_scan(const GroupScanArgs& a, int metric, int grid_cap, hipStream_t st);
+// The column route's offer: the same offers from dist[n_rows] (every row's distance, as the scan's write-distance form leaves them)
+// with `grid` workgroups of 256 lanes, grid-strided (0 = one per 256 rows, at most 1024).
+hipError_t launch_group_offer(const float* dist, const uint32_t* slots, const uint32_t* bitmap, uint32_t n_rows, uint32_t n_slots,
+                              int64_t* best, uint32_t grid, hipStream_t st);
+// Everything behind the offers, enqueued on `st` without a synchronisation: best -> the distance column, launch_timeline over
+// (distance bits, root id) oldest-first under the exclusive bound INT64_MAX, the marking of the chosen slots, per_group - 1 member
+// rounds over (dist, slots, bitmap) and the gather of the members' frame ids.
+struct GroupSelectArgs {
+    const int64_t* best;        // [n_slots] as the offers left it
+    const uint64_t* slot_root;  // [n_slots] root id of every slot; null = the slot itself
+    const float* dist;          // [n_rows] distances of the rows that take part (members only)
+    const uint32_t* slots;      // [n_rows]; null = slot = row
+    const uint32_t* bitmap;     // null = every row
+    const uint64_t* row_ids;    // [n_rows] frame ids by row for the members' ids; null = no ids wanted
+    uint32_t n_rows, n_slots;
+    int32_t limit;              // 1 .. GROUP_MAX_LIMIT
+    int32_t per_group;          // 0 = no members wanted (no marking, no rounds); else 1 .. GROUP_MAX_MEMBERS
+    uint32_t grid;              // workgroups of a member round (0 = one per 256 rows, at most 1024)
+    // scratch
+    int64_t* dist_col;          // [n_slots]
+    int32_t* rank_of_slot;      // [n_slots] (members only)
+    int64_t* cur;               // [2 * limit]: the round's running minimum per rank, then each rank's previous pick (members only)
+    int64_t* tl_scratch;        // [timeline_scratch_words(timeline_grid(n_slots, limit), limit)]
+    // the answer: one block, so that one copy brings it to the host (group_out_words(limit, per_group) int64 words)
+    //   [limit] root ids (ID_PAD-padded) | [limit] group distance as the ordered bits, sign-extended | [1] count (u32) |
+    //   [limit * per_group] member keys (KEY_PAD-padded) | [limit * per_group] member frame ids (ID_PAD-padded; row_ids only)
+    int64_t* out;
+};
+inline uint64_t group_out_words(int32_t limit, int32_t per_group) { return 2ull * (uint64_t)limit + 1ull + 2ull * (uint64_t)limit * (uint64_t)per_group; }
+hipError_t launch_group_select(const GroupSelectArgs& a, hipStream_t st);
+
 // ---- rrf.hip: reciprocal-rank fusion of ranked id lists, one workgroup per query ----
 hipError_t launch_rrf_fuse(const wax_hip_rrf_lane* lanes, uint32_t n_lanes, uint32_t nq, int32_t k, uint64_t* out_ids,
                            float* out_scores, uint32_t* out_best_rank, uint32_t* out_sources, uint32_t out_stride,

@@ -419,6 +419,7 @@ int sh_move_all(ShardedState* s, size_t from, size_t to) {
         dst->ids.resize((size_t)dst_before);
         dst->count = dst_before;
         if (dst->attr_ts.size() > dst_before) { dst->attr_ts.resize((size_t)dst_before); dst->attr_flags.resize((size_t)dst_before); }
+        parent_note_moved(dst, dst_before);
         mirror_note_replaced(dst);     // (rows were appended and taken back: the mirror and the id table start over)
         return rc;
     }
@@ -428,6 +429,11 @@ int sh_move_all(ShardedState* s, size_t from, size_t to) {
         dst->attr_ts.insert(dst->attr_ts.end(), src->attr_ts.begin(), src->attr_ts.end());
         dst->attr_flags.insert(dst->attr_flags.end(), src->attr_flags.begin(), src->attr_flags.end());
         attr_note_moved(dst, dst_before);
+    }
+    if (!src->attr_parent.empty()) {                           // and their parents (DESIGN 4.10), by the same padding
+        dst->attr_parent.resize((size_t)dst_before, WAX_HIP_NO_PARENT);
+        dst->attr_parent.insert(dst->attr_parent.end(), src->attr_parent.begin(), src->attr_parent.end());
+        parent_note_moved(dst, dst_before);
     }
     attr_note_replaced(src);
     // empty the source (capacity stays)
@@ -1372,6 +1378,119 @@ int sh_timeline(wax_hip_engine* e, int32_t limit, int newest_first, const wax_hi
         if (out_ts) out_ts[i] = newest_first != 0 ? ~all[i].first : all[i].first;
     }
     *out_count = (uint32_t)n;
+    return WAX_HIP_OK;
+}
+
+// setParents / getParents on a handle: sh_set_attributes' routing — ids grouped by owning shard, call order kept inside a group.
+int sh_set_parents(wax_hip_engine* e, const uint64_t* frame_ids, const uint64_t* parent_ids, uint64_t n, uint64_t* out_applied) {
+    ShardedState* s = e->sh;
+    REFUSE_IF_HOLDING(e);
+    WriteGuard w(e->lock);
+    const size_t G = s->subs.size();
+    std::vector<std::vector<uint64_t>> ids(G), par(G);
+    for (uint64_t i = 0; i < n; ++i) {
+        int64_t local = -1;
+        const int g = sh_find(s, frame_ids[i], &local);
+        if (g < 0) continue;
+        ids[(size_t)g].push_back(frame_ids[i]);
+        par[(size_t)g].push_back(parent_ids[i]);
+    }
+    uint64_t total = 0;
+    for (size_t g = 0; g < G; ++g) {
+        if (ids[g].empty()) continue;
+        uint64_t got = 0;
+        const int rc = wax_hip_set_parents(s->subs[g], ids[g].data(), par[g].data(), ids[g].size(), &got);
+        if (rc != WAX_HIP_OK) return rc;
+        total += got;
+    }
+    if (out_applied) *out_applied = total;
+    return WAX_HIP_OK;
+}
+
+int sh_get_parents(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, uint64_t* out_parents, uint8_t* out_found) {
+    ShardedState* s = e->sh;
+    ReadGuard rd(e);
+    for (uint64_t i = 0; i < n; ++i) {
+        int64_t local = -1;
+        const int g = sh_find(s, frame_ids[i], &local);
+        if (out_parents) out_parents[i] = WAX_HIP_NO_PARENT;
+        if (out_found) out_found[i] = 0;
+        if (g < 0) continue;
+        const int rc = wax_hip_get_parents(s->subs[(size_t)g], frame_ids + i, 1, out_parents ? out_parents + i : nullptr, out_found ? out_found + i : nullptr);
+        if (rc != WAX_HIP_OK) return rc;
+    }
+    return WAX_HIP_OK;
+}
+
+// The grouped search on a handle, per_group == 1 (DESIGN 4.10): every shard answers `limit` groups on its own rows, side by side on the
+// handle's workers; the host keeps the smaller distance per root (the lower shard on equal bits: shards are in global row order, so
+// that is the lower row), sorts by (distance, root id) and takes `limit`. Exact: a root among the global first `limit` is, on the
+// shard that holds its best row, beaten only by roots that beat it globally, so that shard returns it.
+int sh_search_grouped(wax_hip_engine* e, const float* query, uint32_t dims, int32_t limit, int32_t per_group, int has_min_score, float min_score,
+                      const wax_hip_row_predicate* pred, uint64_t* out_root_ids, float* out_root_scores, uint64_t* out_member_ids,
+                      float* out_member_scores, uint32_t* out_member_counts, uint32_t* out_count) {
+    ShardedState* s = e->sh;
+    if (per_group > 1)
+        return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "searchGrouped: per_group > 1 is not served on a sharded engine (a shard that did not rank a root cannot say what its members there are)");
+    *out_count = 0;
+    if (limit <= 0) return WAX_HIP_OK;
+    ReadGuard rd(e);
+    const bool members = out_member_ids != nullptr;
+    const size_t G = s->subs.size();
+    const uint32_t L = (uint32_t)limit, P = members ? 1u : 0u;
+    std::vector<std::vector<int64_t>> raw(G);
+    std::vector<int> rcs(G, WAX_HIP_OK);
+    std::vector<std::string> errs(G);
+    auto one = [&](size_t g) {
+        rcs[g] = grouped_raw(s->subs[g], query, dims, limit, (int32_t)P, pred, raw[g]);
+        if (rcs[g] != WAX_HIP_OK) errs[g] = g_last_error;   // thread-local: carry it to the caller
+    };
+    if (G == 1) one(0); else s->workers.run_all(one);
+    struct Best { int64_t dist; int64_t key; uint64_t member; };
+    std::map<uint64_t, Best> by_root;
+    for (size_t g = 0; g < G; ++g) {
+        if (rcs[g] != WAX_HIP_OK) return fail(rcs[g], errs[g]);
+        const int64_t* r = raw[g].data();
+        const uint32_t n = *reinterpret_cast<const uint32_t*>(r + 2u * (size_t)L);
+        const int64_t* keys = r + 2u * (size_t)L + 1u;
+        for (uint32_t i = 0; i < n && i < L; ++i) {
+            const Best b{r[L + i], members ? keys[i] : KEY_PAD, members ? (uint64_t)keys[(size_t)L + i] : ID_PAD};
+            auto it = by_root.find((uint64_t)r[i]);
+            if (it == by_root.end()) by_root.emplace((uint64_t)r[i], b);
+            else if (b.dist < it->second.dist) it->second = b;
+        }
+    }
+    std::vector<std::pair<int64_t, uint64_t>> order;
+    order.reserve(by_root.size());
+    for (const auto& kv : by_root) order.emplace_back(kv.second.dist, kv.first);
+    std::sort(order.begin(), order.end());                   // lexicographic: signed distance bits, then unsigned root id
+    uint32_t kept = 0;
+    for (size_t i = 0; i < order.size() && i < (size_t)L; ++i) {
+        const float score = group_score(e->metric, unorder_bits((int32_t)order[i].first));
+        if (has_min_score && score < min_score) continue;
+        out_root_ids[kept] = order[i].second;
+        out_root_scores[kept] = score;
+        if (members) {
+            const Best& b = by_root[order[i].second];
+            out_member_ids[kept] = b.member;                 // (the group's own distance: it passed the cut with the group)
+            out_member_scores[kept] = group_score(e->metric, key_distance(b.key));
+        }
+        if (out_member_counts) out_member_counts[kept] = members ? 1u : 0u;
+        ++kept;
+    }
+    *out_count = kept;
+    return WAX_HIP_OK;
+}
+
+int sh_group_stats(wax_hip_engine* e, wax_hip_group_stats_t* out) {
+    *out = wax_hip_group_stats_t{};
+    for (wax_hip_engine* sub : e->sh->subs) {
+        wax_hip_group_stats_t one{};
+        const int rc = wax_hip_group_stats(sub, &one);
+        if (rc != WAX_HIP_OK) return rc;
+        out->searches += one.searches; out->fused_scans += one.fused_scans; out->column_scans += one.column_scans;
+        out->member_rounds += one.member_rounds; out->group_slots += one.group_slots; out->parent_rows_uploaded += one.parent_rows_uploaded;
+    }
     return WAX_HIP_OK;
 }
 

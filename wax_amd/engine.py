@@ -340,6 +340,65 @@ class HIPVectorEngine:
             raise_for_status(rc)
         return ts, fl, found.astype(bool)
 
+    def setParents(self, frameIds, parentIds) -> int:  # noqa: N802,N803
+        """FrameMeta.parentId of the listed frames for searchGrouped (wax_hip_set_parents): `parentIds` uint64, NO_PARENT (UInt64.max)
+        = the frame is its own root. Ids the engine does not hold are skipped; an id listed twice takes its last entry. Returns the
+        entries that named a held frame."""
+        ids = np.ascontiguousarray(frameIds, dtype=np.uint64).reshape(-1)
+        par = np.ascontiguousarray(parentIds, dtype=np.uint64).reshape(-1)
+        n = int(ids.size)
+        if par.size != n:
+            raise EncodingError("setParents: one parent id per frame id")
+        if n == 0:
+            return 0
+        applied = ctypes.c_uint64(0)
+        raise_for_status(self._lib.wax_hip_set_parents(self._h, _u64p(ids), _u64p(par), n, ctypes.byref(applied)))
+        return int(applied.value)
+
+    def getParents(self, frameIds) -> Tuple[np.ndarray, np.ndarray]:  # noqa: N802,N803
+        """(parent ids uint64, found bool) of the listed frames; (NO_PARENT, False) for an id the engine does not hold."""
+        ids = np.ascontiguousarray(frameIds, dtype=np.uint64).reshape(-1)
+        n = int(ids.size)
+        par = np.full(n, _abi.NO_PARENT, dtype=np.uint64)
+        found = np.zeros(n, dtype=np.uint8)
+        if n:
+            raise_for_status(self._lib.wax_hip_get_parents(self._h, _u64p(ids), n, _u64p(par),
+                                                           found.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+        return par, found.astype(bool)
+
+    def searchGrouped(self, vector, limit: int, perGroup: int = 1, timeRange=None, denyFlags: int = 0, minScore=None):  # noqa: N802,N803
+        """What PhotoRAGOrchestrator.recall / VideoRAGOrchestrator.recall make of the vector lane, exactly and on the device
+        (wax_hip_search_grouped): the `limit` best roots (a row's root is its parent, or its own frame id) by their best member,
+        ordered by (score descending, root id ascending), and the `perGroup` best rows of each. Only rows that pass `timeRange` /
+        `denyFlags` (searchFiltered's meaning) take part; `minScore` drops groups and members below it. Returns (rootIds [g],
+        rootScores [g], memberIds [g, perGroup] padded with UInt64.max, memberScores [g, perGroup] padded with 0, memberCounts [g])."""
+        q = _as_f32(vector).reshape(-1)
+        limit = int(max(min(limit, 2**31 - 1), -2**31))
+        per = int(max(min(perGroup, 2**31 - 1), -2**31))
+        pred = ticket_predicate(timeRange, denyFlags, who="searchGrouped")
+        cap = max(0, min(limit, _abi.GROUP_MAX_LIMIT))
+        width = max(1, min(per, _abi.GROUP_MAX_MEMBERS))
+        roots = np.empty(cap, dtype=np.uint64)
+        scores = np.empty(cap, dtype=np.float32)
+        mids = np.empty((cap, width), dtype=np.uint64)
+        mscores = np.empty((cap, width), dtype=np.float32)
+        mcounts = np.empty(cap, dtype=np.uint32)
+        got = ctypes.c_uint32(0)
+        rc = self._lib.wax_hip_search_grouped(self._h, _fp(q), q.size, limit, per, 0 if minScore is None else 1,
+                                              0.0 if minScore is None else float(minScore), ctypes.byref(pred), _u64p(roots), _fp(scores),
+                                              _u64p(mids), _fp(mscores), mcounts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                              ctypes.byref(got))
+        raise_for_status(rc)
+        g = int(got.value)
+        return roots[:g].copy(), scores[:g].copy(), mids[:g].copy(), mscores[:g].copy(), mcounts[:g].copy()
+
+    def groupStats(self) -> dict:  # noqa: N802
+        """What the grouped searches did (wax_hip_group_stats): searches, fused_scans, column_scans, member_rounds, group_slots,
+        parent_rows_uploaded."""
+        st = _abi.GroupStats()
+        raise_for_status(self._lib.wax_hip_group_stats(self._h, ctypes.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in _abi.GroupStats._fields_}
+
     def timeline(self, limit: int, newestFirst: bool = True, timeRange=None, denyFlags: int = 0) -> Tuple[np.ndarray, np.ndarray]:  # noqa: N803
         """Wax.timeline(TimelineQuery) (TimelineQuery.swift:38-53) on the device: the `limit` newest (newestFirst) or oldest frames
         that pass `timeRange` = (after | None, before | None) and `denyFlags` (searchFiltered's meaning), ordered by timestamp and,
@@ -683,6 +742,38 @@ def timelineProbe(timestamps, flags, frameIds, limit: int, newestFirst: bool = T
                                            _u64p(out_ids), out_ts.ctypes.data_as(i64p), ctypes.byref(got))
     raise_for_status(rc)
     return out_ids, out_ts, int(got.value)
+
+
+def groupProbe(distances, slots, slotRoot, limit: int, perGroup: int = 1, bitmap=None, nSlots=None, grid: int = 0):  # noqa: N802,N803
+    """wax_hip_group_probe: the grouped search's offers, selection, marking and member rounds on host columns. `distances` float32
+    per row (taken bit for bit), `slots` uint32 per row (None = every row its own slot), `slotRoot` uint64 per slot (None = the slot's
+    number), `bitmap` uint32 words (None = every row takes part). Returns (rootIds[limit] padded with UInt64.max, rootKeys[limit]
+    padded with Int64.max, memberKeys[limit, perGroup] likewise, count)."""
+    dist = np.ascontiguousarray(distances, dtype=np.float32).reshape(-1)
+    n = int(dist.size)
+    sl = None if slots is None else np.ascontiguousarray(slots, dtype=np.uint32).reshape(-1)
+    sr = None if slotRoot is None else np.ascontiguousarray(slotRoot, dtype=np.uint64).reshape(-1)
+    bm = None if bitmap is None else np.ascontiguousarray(bitmap, dtype=np.uint32).reshape(-1)
+    if sl is not None and sl.size != n:
+        raise EncodingError("groupProbe: one slot per row")
+    if bm is not None and bm.size != (n + 31) // 32:
+        raise EncodingError("groupProbe: the bitmap holds one bit per row")
+    n_slots = int(nSlots) if nSlots is not None else (int(sr.size) if sr is not None else (n if sl is None else int(sl.max()) + 1 if n else 0))
+    if sr is not None and sr.size != n_slots:
+        raise EncodingError("groupProbe: one root id per slot")
+    limit, per = int(limit), int(perGroup)
+    cap = max(0, min(limit, _abi.GROUP_MAX_LIMIT))
+    width = max(1, min(per, _abi.GROUP_MAX_MEMBERS))
+    roots = np.zeros(cap, dtype=np.uint64)
+    rkeys = np.zeros(cap, dtype=np.int64)
+    mkeys = np.zeros((cap, width), dtype=np.int64)
+    got = ctypes.c_uint32(0)
+    i64p, u32p = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint32)
+    rc = _abi.lib().wax_hip_group_probe(_fp(dist), None if sl is None else sl.ctypes.data_as(u32p), None if sr is None else _u64p(sr),
+                                        None if bm is None else bm.ctypes.data_as(u32p), n, n_slots, limit, per, int(grid),
+                                        _u64p(roots), rkeys.ctypes.data_as(i64p), mkeys.ctypes.data_as(i64p), ctypes.byref(got))
+    raise_for_status(rc)
+    return roots, rkeys, mkeys, int(got.value)
 
 
 def ticket_predicate(timeRange=None, denyFlags=0, who: str = "submitFiltered") -> "_abi.RowPredicate":  # noqa: N803
