@@ -562,6 +562,65 @@ typedef struct wax_hip_group_stats_t {
 } wax_hip_group_stats_t;
 int wax_hip_group_stats(wax_hip_engine* e, wax_hip_group_stats_t* out);
 
+/* ---- required-term search: MetadataFilter as a pre-filter ------------------------- */
+
+/* FrameFilter.metadataFilter (SearchRequest.swift:130-145; matches(metadataFilter:meta:), UnifiedSearch.swift:1215-1239) is the sixth
+ * test of passesFrameFilter (UnifiedSearch.swift:1241-1258): a conjunction — every requiredEntries[key] == value, every requiredTags
+ * pair and every requiredLabels string must be on the frame. The reference applies it to an over-fetched prefix (candidateLimit rows),
+ * so a session that owns a small share of a large store (WaxMCPTools.swift:582 scopes every recall by "session_id") gets too few hits
+ * or none. Here it is a pre-filter on the device.
+ *
+ * A TERM is an opaque uint32 the caller chooses: strings do not cross this ABI. The caller owns the dictionary that maps
+ * ("entry", key, value), ("tag", key, value) and ("label", s) to ids, so the filter is exact — no hash, no collision. A fourth
+ * optional per-row column carries a SET of 0 .. WAX_HIP_TERMS_MAX_PER_ROW distinct terms per row, under the lifecycle of the
+ * timestamp, flag and parent columns word for word: a store on which terms were never set allocates nothing and every row holds the
+ * empty set; an appended row gets the empty set; an upsert keeps its row's set; removals take the row's set with them; reserve and
+ * growth keep the column; a move between shards carries it; wax_hip_deserialize drops it (wax_hip_serialize is unchanged). The host
+ * copy is authoritative; the device copy (CSR: uint32 offsets of rows + 1 entries, uint32 values ascending within a row) is brought
+ * up to date by the first term search after a change, from the lowest changed row. A store holds fewer than 2^32 terms in all. */
+#define WAX_HIP_TERMS_MAX_PER_ROW  64
+#define WAX_HIP_TERMS_MAX_REQUIRED 16
+/* Replaces the WHOLE set of frame_ids[i] with terms[term_begin[i] .. term_begin[i] + term_len[i]) (the allow_begin / allow_len
+ * convention of wax_hip_search_batch_filtered); a length of 0 clears the set; duplicates inside one set collapse. Ids the engine does
+ * not hold are skipped, an id listed twice takes its last entry, *out_applied (may be NULL) = entries that named a held frame — as
+ * wax_hip_set_attributes. A writer: a thread that holds uncollected search tickets is refused. Refused with NOTHING applied: a set of
+ * more than WAX_HIP_TERMS_MAX_PER_ROW terms after de-duplication, a span that leaves [0, n_terms), NULL arrays (terms may be NULL
+ * when every length is 0), and (WAX_HIP_ERR_CAPACITY) a call after which the store would hold 2^32 terms or more. The spans and
+ * set sizes are checked before the engine is looked at; a sharded handle checks every shard's total before it changes any shard. */
+int wax_hip_set_terms(wax_hip_engine* e, const uint64_t* frame_ids, const uint64_t* term_begin, const uint32_t* term_len,
+                      const uint32_t* terms, uint64_t n_terms, uint64_t n, uint64_t* out_applied);
+/* The set of one frame, ascending: *out_count = its size (also when out_capacity is smaller; then only out_capacity terms are
+ * written), *out_found (may be NULL) = 1 for a frame the engine holds, else 0 and count 0. */
+int wax_hip_get_terms(wax_hip_engine* e, uint64_t frame_id, uint32_t* out_terms, uint32_t out_capacity, uint32_t* out_count, uint8_t* out_found);
+/* wax_hip_search_predicate restricted to the rows whose set contains EVERY one of required_terms[0 .. n_required) (duplicates among
+ * them collapse; more than WAX_HIP_TERMS_MAX_REQUIRED distinct ones are refused). The answer is bit for bit what
+ * wax_hip_search_predicate returns when its allow-list is the frame ids of exactly those rows, intersected with the caller's list if
+ * one is given: ids, scores, count, ties in ascending row order, the score cut on the host. With n_required == 0 the call IS
+ * wax_hip_search_predicate (one body, the same launches, the same counters). On a store where no terms were ever set, n_required > 0
+ * gives count 0 with no device work (`guard let entries = meta.metadata?.entries else { return false }`, UnifiedSearch.swift:1219).
+ * Otherwise term_mask_kernel turns the CSR column into the row bitmap every filter route works from — ANDed into the allow-list
+ * probe's where there is a long list — attr_mask_kernel applies the predicate (or passes everything) and counts, and the routes of
+ * wax_hip_search_predicate answer: the gather, the masked f32 scan, the masked bf16-mirror scan under its certificate. A list below
+ * "filter_device_min" is staged on the host, where the term test reads the host column. The counters and tuning keys are those of
+ * the predicate search — of one under a predicate that passes every row where the caller gave none, so a term search charges
+ * "predicate_searches" and its route's counter ("predicate_gather_searches", ...) although no attribute was tested;
+ * wax_hip_term_stats reads out the rest. Refusals: those of wax_hip_search_predicate in its order, then a NULL
+ * required_terms with n_required > 0, then too many distinct terms. Blocking; a reader. A sharded handle runs every shard on its
+ * workers and merges as it does for wax_hip_search_predicate. */
+int wax_hip_search_terms(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k,
+                         int has_allow, const uint64_t* allow_frame_ids, uint64_t n_allow,
+                         int has_min_score, float min_score, const wax_hip_row_predicate* pred,
+                         const uint32_t* required_terms, uint32_t n_required,
+                         uint64_t* out_ids, float* out_scores, uint32_t out_capacity, uint32_t* out_count);
+/* What the term searches (n_required > 0) of this engine did, a read-out in the way of wax_hip_group_stats (no tuning key): searches;
+ * device_masks = term_mask_kernel launches; host_staged = short lists tested on the host column; host_decided = answered empty
+ * because the store never had terms; term_rows_uploaded / term_values_uploaded = offsets' rows and values sent to the device so far.
+ * A sharded handle reports the sums over its shards. */
+typedef struct wax_hip_term_stats_t {
+    uint64_t searches, device_masks, host_staged, host_decided, term_rows_uploaded, term_values_uploaded;
+} wax_hip_term_stats_t;
+int wax_hip_term_stats(wax_hip_engine* e, wax_hip_term_stats_t* out);
+
 /* ---- persistence: "MV2V" vec segment, encoding 2 ------------------------- */
 
 /* serialize() (MetalVectorEngine.swift:682-714): byte-identical layout
@@ -784,6 +843,13 @@ int wax_hip_timeline_probe(const int64_t* timestamps, const uint32_t* flags, con
 int wax_hip_group_probe(const float* distances, const uint32_t* slots, const uint64_t* slot_root, const uint32_t* bitmap,
                         uint64_t n_rows, uint32_t n_slots, int32_t limit, int32_t per_group, uint32_t grid,
                         uint64_t* out_root_ids, int64_t* out_root_keys, int64_t* out_member_keys, uint32_t* out_count);
+/* Diagnostic of term_mask_kernel on a column the caller makes up (tests drive many grid-stride iterations and every span shape
+ * through it without a large store; no product path calls it). offsets[n_rows + 1] (non-decreasing, n_rows < 2^32) and
+ * values[offsets[n_rows]] are uploaded to the current device, ONE launch of exactly `grid` workgroups (1 .. 1 024) writes
+ * out_bitmap[ceil(n_rows / 32)]: bit r = "row r's values contain all of required[0 .. n_required)" (1 .. WAX_HIP_TERMS_MAX_REQUIRED
+ * terms, duplicates collapse), ANDed with bitmap_in where that is not NULL; bits at and beyond n_rows are clear. Blocking. */
+int wax_hip_term_mask_probe(const uint32_t* offsets, const uint32_t* values, uint64_t n_rows, const uint32_t* required, uint32_t n_required,
+                            const uint32_t* bitmap_in, uint32_t grid, uint32_t* out_bitmap);
 
 #ifdef __cplusplus
 }

@@ -80,6 +80,14 @@ class GroupStats(ctypes.Structure):
                                                      "parent_rows_uploaded")]
 
 
+class TermStats(ctypes.Structure):
+    """wax_hip_term_stats_t (include/wax_hip.h)."""
+    _fields_ = [(name, ctypes.c_uint64) for name in ("searches", "device_masks", "host_staged", "host_decided", "term_rows_uploaded",
+                                                     "term_values_uploaded")]
+
+
+TERMS_MAX_PER_ROW = 64          # WAX_HIP_TERMS_MAX_PER_ROW
+TERMS_MAX_REQUIRED = 16         # WAX_HIP_TERMS_MAX_REQUIRED
 NO_PARENT = (1 << 64) - 1       # WAX_HIP_NO_PARENT: the row is its own root
 GROUP_MAX_LIMIT = 1024          # WAX_HIP_GROUP_MAX_LIMIT
 GROUP_MAX_MEMBERS = 8           # WAX_HIP_GROUP_MAX_MEMBERS
@@ -190,6 +198,12 @@ SIGNATURES: Dict[str, tuple] = {
     "wax_hip_search_grouped": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_float,
                                               ctypes.POINTER(RowPredicate), _u64p, _f32p, _u64p, _f32p, _u32p, _u32p]),
     "wax_hip_group_stats": (ctypes.c_int, [_engine_p, ctypes.POINTER(GroupStats)]),
+    "wax_hip_set_terms": (ctypes.c_int, [_engine_p, _u64p, _u64p, _u32p, _u32p, ctypes.c_uint64, ctypes.c_uint64, _u64p]),
+    "wax_hip_get_terms": (ctypes.c_int, [_engine_p, ctypes.c_uint64, _u32p, ctypes.c_uint32, _u32p, _u8p]),
+    "wax_hip_search_terms": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int, _u64p, ctypes.c_uint64, ctypes.c_int,
+                                            ctypes.c_float, ctypes.POINTER(RowPredicate), _u32p, ctypes.c_uint32, _u64p, _f32p, ctypes.c_uint32, _u32p]),
+    "wax_hip_term_stats": (ctypes.c_int, [_engine_p, ctypes.POINTER(TermStats)]),
+    "wax_hip_term_mask_probe": (ctypes.c_int, [_u32p, _u32p, ctypes.c_uint64, _u32p, ctypes.c_uint32, _u32p, ctypes.c_uint32, _u32p]),
     "wax_hip_group_probe": (ctypes.c_int, [_f32p, _u32p, _u64p, _u32p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32,
                                            ctypes.c_uint32, _u64p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _u32p]),
 }

@@ -19,9 +19,10 @@ int wax_hip_search_submit(wax_hip_engine* e, const float* query, uint32_t dims, 
 // filter_host.inc
 static inline bool predicate_passes(const wax_hip_row_predicate& p, int64_t ts, uint32_t fl);
 static bool predicate_uses_mirror(wax_hip_engine* e, int kpad);
+struct TermReq;   // api_terms.inc: the distinct required terms of a term search (null: none)
 static int search_rows_locked(wax_hip_engine* e, const float* query, uint32_t dims, int kpad, int has_allow, const uint64_t* allow_frame_ids,
                               uint64_t n_allow, const wax_hip_row_predicate* pred, uint64_t* out_ids, float* out_scores,
-                              uint32_t out_capacity, uint32_t* out_n);
+                              uint32_t out_capacity, uint32_t* out_n, const TermReq* req = nullptr);
 static inline void apply_min_score(float cut, uint64_t* ids, float* scores, uint32_t* n);
 
 // what every ticket starts from

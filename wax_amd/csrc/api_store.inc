@@ -118,6 +118,7 @@ void wax_hip_engine_destroy(wax_hip_engine* e) {
         (void)hipFree(e->idhash.d_table);
         (void)hipFree(e->d_attr_ts); (void)hipFree(e->d_attr_flags);
         (void)hipFree(e->d_grp_slot); (void)hipFree(e->d_grp_root);
+        (void)hipFree(e->d_term_off); (void)hipFree(e->d_term_val);
         for (PredEntry& p : e->pred_entries) {
             (void)hipFree(p.d_bitmap); (void)hipFree(p.d_counts); (void)hipHostFree(p.h_counts);
             if (p.built_ev) (void)hipEventDestroy(p.built_ev);
@@ -432,6 +433,7 @@ int wax_hip_remove_batch(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t 
                     if (e->attr_parent.empty()) parent_note_replaced(e);
                     else parent_note_moved(e, rem[0]);
                 }
+                term_note_remove_rows(e, rem.data(), rem.size());   // and the term column (CSR: a pass of its own)
             }
             e->count -= m;                                     // :441, m times
             e->st_remove_batches += 1;

@@ -1,0 +1,316 @@
+// api_terms.inc — part of engine.hip's translation unit (included there; not compiled alone).
+// C ABI: the per-row term column (set / get), its device copy, the required-term search, its read-out and the kernel's probe
+// (DESIGN 4.11; FrameFilter.metadataFilter, SearchRequest.swift:130-145; matches(metadataFilter:meta:), UnifiedSearch.swift:1215-1239).
+// The search itself is search_rows_locked (filter_host.inc) with the term mask in front of the attribute mask.
+
+// filter_host.inc
+static inline bool predicate_is_empty(const wax_hip_row_predicate* p);
+static inline wax_hip_row_predicate normalised_predicate(const wax_hip_row_predicate* p);
+
+// The distinct required terms of one search, ascending.
+struct TermReq {
+    uint32_t n = 0;
+    uint32_t t[TERMS_MAX_REQUIRED] = {};
+};
+
+// required[0 .. n) -> TermReq (duplicates collapse); false: more than TERMS_MAX_REQUIRED distinct terms
+static bool make_term_req(const uint32_t* required, uint32_t n, TermReq* out) {
+    std::vector<uint32_t> v(required, required + n);
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    if (v.size() > (size_t)TERMS_MAX_REQUIRED) return false;
+    out->n = (uint32_t)v.size();
+    for (size_t i = 0; i < v.size(); ++i) out->t[i] = v[i];
+    return true;
+}
+
+// The kernel's argument block: unused slots repeat the first term, so that a row passes exactly when all sixteen bits are set.
+static void fill_term_mask_req(TermMaskArgs* a, const TermReq& req) {
+    for (int i = 0; i < TERMS_MAX_REQUIRED; ++i) a->req[i] = req.t[(uint32_t)i < req.n ? i : 0];
+}
+
+// Does row r of the HOST column hold every required term? (the short allow-list's test: stage_host_rows)
+static bool term_row_has_all(const wax_hip_engine* e, uint64_t r, const TermReq& req) {
+    if (r + 1 >= e->term_off.size()) return false;                 // behind the column: the empty set
+    const uint32_t* b = e->term_val.data() + e->term_off[(size_t)r];
+    const uint32_t* en = e->term_val.data() + e->term_off[(size_t)r + 1];
+    for (uint32_t i = 0; i < req.n; ++i)
+        if (!std::binary_search(b, en, req.t[i])) return false;
+    return true;
+}
+
+// ---- the column -------------------------------------------------------------------
+
+// (TermPlan, one validated set_terms call, is in engine_types.inc: the sharded handle takes it too)
+// One engine's share of a plan: (row, entry) by ascending row, one per row — in call order the last entry of a repeated id wins.
+typedef std::vector<std::pair<uint64_t, uint64_t>> TermRows;
+
+static int validate_term_sets(const uint64_t* term_begin, const uint32_t* term_len, const uint32_t* terms, uint64_t n_terms, uint64_t n, TermPlan* p) {
+    uint64_t sum = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t len = term_len[i];
+        if (term_begin[i] > n_terms || len > n_terms - term_begin[i])
+            return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "setTerms: term range of entry " + std::to_string(i) + " leaves the term array");
+        if (len != 0 && !terms) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "setTerms: term array is null");
+        sum += len;
+    }
+    p->flat.resize((size_t)sum);
+    p->e_off.assign((size_t)n + 1, 0);
+    uint64_t w = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t len = term_len[i];
+        uint32_t* b = p->flat.data() + w;
+        if (len != 0) std::memcpy(b, terms + term_begin[i], (size_t)len * sizeof(uint32_t));
+        std::sort(b, b + len);
+        const uint64_t kept = (uint64_t)(std::unique(b, b + len) - b);
+        if (kept > (uint64_t)TERMS_MAX_PER_ROW)
+            return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "setTerms: entry " + std::to_string(i) + " holds more than " + std::to_string(TERMS_MAX_PER_ROW) + " distinct terms");
+        w += kept;
+        p->e_off[(size_t)i + 1] = w;
+    }
+    p->flat.resize((size_t)w);
+    return WAX_HIP_OK;
+}
+
+// (row, entry) pairs in call order -> one per row, ascending, the last entry of a row kept
+static void finish_term_rows(TermRows* rows) {
+    std::stable_sort(rows->begin(), rows->end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    size_t w = 0;
+    for (size_t i = 0; i < rows->size(); ++i)
+        if (i + 1 == rows->size() || (*rows)[i + 1].first != (*rows)[i].first) (*rows)[w++] = (*rows)[i];
+    rows->resize(w);
+}
+
+// The terms the engine would hold once `rows` of the plan are applied (exclusive lock held).
+static uint64_t term_total_after(const wax_hip_engine* e, const TermPlan& p, const TermRows& rows) {
+    const uint64_t old_rows = e->term_off.empty() ? 0 : e->term_off.size() - 1;
+    uint64_t total = e->term_off.empty() ? 0 : e->term_off.back();
+    for (const auto& re : rows) {
+        if (re.first < old_rows) total -= e->term_off[(size_t)re.first + 1] - e->term_off[(size_t)re.first];
+        total += p.e_off[(size_t)re.second + 1] - p.e_off[(size_t)re.second];
+    }
+    return total;
+}
+
+// Apply (exclusive lock held; term_total_after(e, p, rows) < 2^32; rows not empty). Sets of the size they had are overwritten in place;
+// otherwise the CSR is rebuilt from the lowest row whose size changes, to the end of the column: the old one's, or the highest row
+// set if that lies behind it — the rows behind the column hold the empty set and need no entry.
+static void commit_term_rows(wax_hip_engine* e, const TermPlan& p, const TermRows& rows) {
+    const uint64_t old_rows = e->term_off.empty() ? 0 : e->term_off.size() - 1;
+    auto new_len = [&](const std::pair<uint64_t, uint64_t>& re) { return (uint32_t)(p.e_off[(size_t)re.second + 1] - p.e_off[(size_t)re.second]); };
+    auto old_len = [&](uint64_t r) -> uint32_t { return r < old_rows ? e->term_off[(size_t)r + 1] - e->term_off[(size_t)r] : 0u; };
+    size_t first_resized = rows.size();
+    for (size_t i = 0; i < rows.size(); ++i) {
+        if (rows[i].first < old_rows && new_len(rows[i]) == old_len(rows[i].first)) {
+            if (new_len(rows[i]) != 0)
+                std::memcpy(e->term_val.data() + e->term_off[(size_t)rows[i].first], p.flat.data() + p.e_off[(size_t)rows[i].second], (size_t)new_len(rows[i]) * sizeof(uint32_t));
+        } else if (first_resized == rows.size()) {
+            first_resized = i;
+        }
+    }
+    if (first_resized != rows.size()) {
+        const uint64_t lowest = rows[first_resized].first;
+        const uint64_t new_rows = std::max(old_rows, rows.back().first + 1);
+        if (e->term_off.empty()) e->term_off.push_back(0u);
+        const uint64_t keep_rows = std::min(lowest, old_rows);
+        const uint32_t keep = e->term_off[(size_t)keep_rows];
+        std::vector<uint32_t> tail_off, tail_val;
+        tail_off.reserve((size_t)(new_rows - lowest));
+        size_t i = first_resized;
+        for (uint64_t r = lowest; r < new_rows; ++r) {
+            if (i < rows.size() && rows[i].first == r) {
+                tail_val.insert(tail_val.end(), p.flat.begin() + (ptrdiff_t)p.e_off[(size_t)rows[i].second], p.flat.begin() + (ptrdiff_t)p.e_off[(size_t)rows[i].second + 1]);
+                ++i;
+            } else if (r < old_rows) {
+                tail_val.insert(tail_val.end(), e->term_val.begin() + e->term_off[(size_t)r], e->term_val.begin() + e->term_off[(size_t)r + 1]);
+            }
+            tail_off.push_back(keep + (uint32_t)tail_val.size());
+        }
+        e->term_off.resize((size_t)keep_rows + 1);
+        e->term_off.resize((size_t)lowest + 1, keep);          // rows between the old column's end and `lowest` held the empty set
+        e->term_off.insert(e->term_off.end(), tail_off.begin(), tail_off.end());
+        e->term_val.resize((size_t)keep);
+        e->term_val.insert(e->term_val.end(), tail_val.begin(), tail_val.end());
+    }
+    term_note_moved(e, rows.front().first);
+}
+
+int wax_hip_set_terms(wax_hip_engine* e, const uint64_t* frame_ids, const uint64_t* term_begin, const uint32_t* term_len, const uint32_t* terms,
+                      uint64_t n_terms, uint64_t n, uint64_t* out_applied) {
+    if (out_applied) *out_applied = 0;
+    // the arguments against themselves first (no engine is looked at): nothing is applied when any entry is refused
+    if (n != 0 && (!frame_ids || !term_begin || !term_len)) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "setTerms: null input");
+    TermPlan plan;
+    { const int vrc = validate_term_sets(term_begin, term_len, terms, n_terms, n, &plan); if (vrc != WAX_HIP_OK) return vrc; }
+    if (!e) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine is null");
+    if (n == 0) return WAX_HIP_OK;
+    if (e->sh) return sh_set_terms(e, frame_ids, n, plan, out_applied);
+    REFUSE_IF_HOLDING(e);
+    WriteGuard w(e->lock);
+    TermRows rows;
+    uint64_t applied = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const int64_t r = e->idmap.find(frame_ids[i]);
+        if (r < 0) continue;                                   // a frame without a vector has no row to describe
+        ++applied;
+        rows.emplace_back((uint64_t)r, i);
+    }
+    finish_term_rows(&rows);
+    if (!rows.empty()) {
+        if (term_total_after(e, plan, rows) >= 0x100000000ull) return fail(WAX_HIP_ERR_CAPACITY, "setTerms: the store would hold 2^32 terms or more");
+        commit_term_rows(e, plan, rows);
+    }
+    if (out_applied) *out_applied = applied;
+    return WAX_HIP_OK;
+}
+
+int wax_hip_get_terms(wax_hip_engine* e, uint64_t frame_id, uint32_t* out_terms, uint32_t out_capacity, uint32_t* out_count, uint8_t* out_found) {
+    if (out_count) *out_count = 0;
+    if (out_found) *out_found = 0;
+    if (!e) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine is null");
+    if (!out_count || (!out_terms && out_capacity)) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "getTerms: null argument");
+    if (e->sh) return sh_get_terms(e, frame_id, out_terms, out_capacity, out_count, out_found);
+    ReadGuard rd(e);
+    const int64_t r = e->idmap.find(frame_id);
+    if (r < 0) return WAX_HIP_OK;
+    if (out_found) *out_found = 1;
+    if ((uint64_t)r + 1 >= e->term_off.size()) return WAX_HIP_OK;
+    const uint32_t b = e->term_off[(size_t)r], len = e->term_off[(size_t)r + 1] - b;
+    for (uint32_t i = 0; i < len && i < out_capacity; ++i) out_terms[i] = e->term_val[(size_t)b + i];
+    *out_count = len;
+    return WAX_HIP_OK;
+}
+
+// The device CSR of the store as it is now (shared lock held; pending rows flushed; the host column is not empty): count + 1 offsets
+// and the values. Concurrent term searches serialise here; what is uploaded is the offsets of rows [lowest changed or first
+// appended, count] and the values from that row's offset on. Growth keeps what was current by a device copy.
+static int ensure_terms(wax_hip_engine* e, hipStream_t st, const uint32_t** d_off, const uint32_t** d_val) {
+    *d_off = nullptr; *d_val = nullptr;
+    std::unique_lock<std::mutex> g(e->term_mu);
+    const uint64_t count = e->count, host_rows = e->term_off.size() - 1, total = e->term_off.back();
+    auto host_off = [&](uint64_t r) -> uint32_t { return e->term_off[(size_t)std::min(r, host_rows)]; };
+    uint64_t from = std::min(std::min(e->term_dev_rows, e->term_stale_from), count);
+    bool current = from == count && e->term_dev_rows == count && e->term_stale_from == UINT64_MAX;
+    const uint64_t val_need = ((total + 3ull) & ~3ull) + 4ull;   // whole dwordx4 pieces (terms.hip), never an empty allocation
+    if (e->term_off_cap < count + 1 || e->term_val_cap < val_need) {
+        // the rows that were current are kept by a device copy, the rest is uploaded below
+        const uint64_t keep = e->term_off_cap == 0 ? 0 : std::min(from, e->term_off_cap - 1);
+        const uint64_t keep_val = std::min<uint64_t>(host_off(keep), e->term_val_cap);
+        uint64_t off_cap = e->term_off_cap, val_cap = e->term_val_cap;
+        if (off_cap < count + 1) off_cap = (e->capacity > count ? e->capacity : count) + 1;
+        if (val_cap < val_need) { val_cap = std::max<uint64_t>(val_cap * 2, 1024); while (val_cap < val_need) val_cap *= 2; }
+        uint32_t* no = nullptr;
+        uint32_t* nv = nullptr;
+        HIP_TRY(hipMalloc(&no, (size_t)off_cap * sizeof(uint32_t)), WAX_HIP_ERR_ALLOC, "Failed to allocate the term offsets");
+        hipError_t err = hipMalloc(&nv, (size_t)val_cap * sizeof(uint32_t));
+        if (err == hipSuccess && keep > 0) err = hipMemcpyAsync(no, e->d_term_off, (size_t)keep * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
+        if (err == hipSuccess && keep > 0 && keep_val > 0) err = hipMemcpyAsync(nv, e->d_term_val, (size_t)keep_val * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
+        if (err == hipSuccess) err = hipStreamSynchronize(st);
+        if (err != hipSuccess) { (void)hipFree(no); (void)hipFree(nv); return fail(WAX_HIP_ERR_ALLOC, std::string("Failed to allocate the term values: ") + hipGetErrorString(err)); }
+        (void)hipFree(e->d_term_off); (void)hipFree(e->d_term_val);
+        e->d_term_off = no; e->d_term_val = nv; e->term_off_cap = off_cap; e->term_val_cap = val_cap;
+        e->term_dev_rows = keep;
+        from = std::min(from, keep);
+        current = false;
+    }
+    if (!current) {
+        // offsets of rows [from, count]: the host's, and the column's end for the rows behind it
+        std::vector<uint32_t> offs((size_t)(count - from) + 1);
+        for (uint64_t r = from; r <= count; ++r) offs[(size_t)(r - from)] = host_off(r);
+        const uint32_t v0 = host_off(from);
+        // pageable sources: the runtime stages them before returning
+        HIP_TRY(hipMemcpyAsync(e->d_term_off + from, offs.data(), offs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st), WAX_HIP_ERR_INTERNAL, "term offset upload");
+        if (v0 < total)
+            HIP_TRY(hipMemcpyAsync(e->d_term_val + v0, e->term_val.data() + v0, (size_t)(total - v0) * sizeof(uint32_t), hipMemcpyHostToDevice, st),
+                    WAX_HIP_ERR_INTERNAL, "term value upload");
+        HIP_TRY(hipStreamSynchronize(st), WAX_HIP_ERR_INTERNAL, "term upload failed on device");   // other workspaces' streams read the column next
+        e->tm_rows_uploaded += count - from;
+        e->tm_values_uploaded += total - v0;
+    }
+    e->term_dev_rows = count;
+    e->term_stale_from = UINT64_MAX;
+    *d_off = e->d_term_off; *d_val = e->d_term_val;
+    return WAX_HIP_OK;
+}
+
+int wax_hip_term_stats(wax_hip_engine* e, wax_hip_term_stats_t* out) {
+    if (!e || !out) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine/out is null");
+    if (e->sh) return sh_term_stats(e, out);
+    out->searches = e->tm_searches.load(); out->device_masks = e->tm_device_masks.load(); out->host_staged = e->tm_host_staged.load();
+    out->host_decided = e->tm_host_decided.load(); out->term_rows_uploaded = e->tm_rows_uploaded.load();
+    out->term_values_uploaded = e->tm_values_uploaded.load();
+    return WAX_HIP_OK;
+}
+
+// ---- the search -------------------------------------------------------------------
+
+int wax_hip_search_terms(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, int has_allow, const uint64_t* allow_frame_ids,
+                         uint64_t n_allow, int has_min_score, float min_score, const wax_hip_row_predicate* pred, const uint32_t* required_terms,
+                         uint32_t n_required, uint64_t* out_ids, float* out_scores, uint32_t out_capacity, uint32_t* out_count) {
+    if (n_required == 0)   // no term to require: the predicate search as it is — one body, the same launches, the same counters
+        return wax_hip_search_predicate(e, query, dims, top_k, has_allow, allow_frame_ids, n_allow, has_min_score, min_score, pred, out_ids, out_scores,
+                                        out_capacity, out_count);
+    // search_filtered_entry's refusals in its order, the new ones behind them
+    if (out_count) *out_count = 0;
+    if (!e) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine is null");
+    if (!query || !out_count || ((!out_ids || !out_scores) && out_capacity)) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (has_allow && n_allow > 0 && !allow_frame_ids) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "allow-list is null");
+    if (!e->sh && dims != e->dims) return fail(WAX_HIP_ERR_DIM_MISMATCH, dim_mismatch_msg(e->dims, dims));
+    if (!required_terms) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "required terms are null");
+    TermReq req;
+    if (!make_term_req(required_terms, n_required, &req))
+        return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "searchTerms: more than " + std::to_string(TERMS_MAX_REQUIRED) + " distinct required terms");
+    if (e->sh)
+        return sh_search_terms(e, query, dims, top_k, has_allow, allow_frame_ids, n_allow, has_min_score, min_score, pred, req.t, req.n, out_ids,
+                               out_scores, out_capacity, out_count);
+    const wax_hip_row_predicate np = normalised_predicate(pred);
+    uint32_t n = 0;
+    {
+        DeviceGuard g(e->device);
+        ReadGuard rd(e);
+        { const int frc = flush_pending(e); if (frc != WAX_HIP_OK) return frc; }
+        e->tm_searches++;
+        const int rc = search_rows_locked(e, query, dims, clamp_topk(top_k), has_allow, allow_frame_ids, n_allow, predicate_is_empty(&np) ? nullptr : &np,
+                                          out_ids, out_scores, out_capacity, &n, &req);
+        if (rc != WAX_HIP_OK) return rc;
+    }
+    if (has_min_score) apply_min_score(min_score, out_ids, out_scores, &n);
+    *out_count = n;
+    return WAX_HIP_OK;
+}
+
+// ---- the kernel's probe -----------------------------------------------------------
+
+int wax_hip_term_mask_probe(const uint32_t* offsets, const uint32_t* values, uint64_t n_rows, const uint32_t* required, uint32_t n_required,
+                            const uint32_t* bitmap_in, uint32_t grid, uint32_t* out_bitmap) {
+    if (!offsets || !required || !out_bitmap) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_required == 0) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "term_mask_probe: at least one required term");
+    TermReq req;
+    if (!make_term_req(required, n_required, &req))
+        return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "term_mask_probe: more than " + std::to_string(TERMS_MAX_REQUIRED) + " distinct required terms");
+    if (grid == 0 || grid > TERM_MASK_MAX_GRID) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "term_mask_probe: 1 to 1024 workgroups");
+    if (n_rows == 0 || n_rows > 0xffffffffull) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "term_mask_probe: 1 to 2^32 - 1 rows");
+    for (uint64_t r = 0; r < n_rows; ++r)
+        if (offsets[r] > offsets[r + 1]) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "term_mask_probe: offsets must not decrease");
+    const uint64_t total = offsets[n_rows];
+    if (total >= 0x80000000ull) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "term_mask_probe: fewer than 2^31 values");
+    if (total != 0 && !values) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    const uint64_t n_words = (n_rows + 31) / 32;
+    const uint64_t val_words = ((total + 3ull) & ~3ull) + 4ull, off_words = (n_rows + 1 + 3ull) & ~3ull;   // every section starts 16-byte aligned
+    uint32_t* d = nullptr;
+    HIP_TRY(hipMalloc(&d, (size_t)(val_words + off_words + n_words) * sizeof(uint32_t)), WAX_HIP_ERR_INTERNAL, "term_mask_probe allocation");
+    uint32_t* d_val = d;
+    uint32_t* d_off = d + val_words;
+    uint32_t* d_bm = d_off + off_words;
+    TermMaskArgs a{};
+    a.off = d_off; a.val = d_val; a.bitmap = d_bm; a.n_rows = (uint32_t)n_rows; a.and_bitmap = bitmap_in ? 1 : 0;
+    fill_term_mask_req(&a, req);
+    hipError_t err = hipMemcpy(d_off, offsets, (size_t)(n_rows + 1) * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (err == hipSuccess && total != 0) err = hipMemcpy(d_val, values, (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (err == hipSuccess && bitmap_in) err = hipMemcpy(d_bm, bitmap_in, (size_t)n_words * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = launch_term_mask(a, grid, nullptr);
+    if (err == hipSuccess) err = hipMemcpy(out_bitmap, d_bm, (size_t)n_words * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    HIP_TRY(err, WAX_HIP_ERR_INTERNAL, "term_mask_probe");
+    return WAX_HIP_OK;
+}

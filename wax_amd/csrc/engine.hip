@@ -45,6 +45,7 @@ using namespace wax;
 //   api_shard.inc          C ABI: the one-rank-per-GPU entry points (set_row_base, search_shard_device, merge_hits_device, merge_batch_hits_device, hits_to_results)
 //   api_fusion_filter.inc  C ABI: reciprocal-rank fusion
 //   api_predicate.inc      C ABI: per-row attributes (set / get) and their device columns
+//   api_terms.inc          C ABI: wax_hip_set_terms / get_terms, wax_hip_search_terms, wax_hip_term_stats, wax_hip_term_mask_probe — the CSR term column and its device copy; the search itself is filter_host.inc's locked body with the term mask in front (UnifiedSearch.swift:1215-1239)
 //   filter_host.inc        C ABI: the filtered searches — one query with an allow-list and / or a row predicate (one locked body), the batched allow-list form
 //   search_many.inc        C ABI: wax_hip_search_many[_predicate] — one query each against many stores of one device under one snapshot, the eligible pairs in one pooled launch, with a row predicate and a score cut per pair
 //   api_timeline.inc       C ABI: wax_hip_timeline[_device | _probe] — the newest / oldest passing rows by (timestamp, frame id), selected on the device from the attribute columns (TimelineQuery.swift:38-53)
@@ -63,6 +64,7 @@ using namespace wax;
 #include "api_shard.inc"
 #include "api_fusion_filter.inc"
 #include "api_predicate.inc"
+#include "api_terms.inc"
 #include "filter_host.inc"
 #include "search_many.inc"
 #include "api_timeline.inc"

@@ -653,6 +653,22 @@ struct wax_hip_engine {
     uint64_t grp_cap = 0, grp_root_cap = 0, grp_root_dev = 0;
     // wax_hip_group_stats (a read-out, no tuning key)
     std::atomic<uint64_t> gs_searches{0}, gs_fused_scans{0}, gs_column_scans{0}, gs_member_rounds{0}, gs_group_slots{0}, gs_parent_rows_uploaded{0};
+    // The term column (wax_hip_set_terms; DESIGN 4.11): a fourth host column, every row a set of 0 .. WAX_HIP_TERMS_MAX_PER_ROW distinct
+    // uint32 terms, kept as CSR — term_off[r] .. term_off[r + 1] index row r's terms, ascending, in term_val. Under the rules of the
+    // columns above: authoritative, in row order, possibly SHORTER than the store (term_off holds one entry more than the rows it
+    // covers; rows behind it hold the empty set, what every appended row does), both vectors empty on a store that never had terms.
+    // Writers change it under the exclusive engine lock.
+    std::vector<uint32_t> term_off, term_val;
+    // Device mirror (ensure_terms, api_terms.inc, under term_mu and the shared engine lock): d_term_off[term_off_cap] holds count + 1
+    // offsets, d_term_val[term_val_cap] the values (the capacity a multiple of 4 words: term_mask_kernel reads whole dwordx4). Rows
+    // [0, term_dev_rows) below term_stale_from match the host; writers only lower term_stale_from.
+    std::mutex term_mu;
+    uint32_t* d_term_off = nullptr;
+    uint32_t* d_term_val = nullptr;
+    uint64_t term_off_cap = 0, term_val_cap = 0, term_dev_rows = 0;
+    uint64_t term_stale_from = UINT64_MAX;
+    // wax_hip_term_stats (a read-out, no tuning key)
+    std::atomic<uint64_t> tm_searches{0}, tm_device_masks{0}, tm_host_staged{0}, tm_host_decided{0}, tm_rows_uploaded{0}, tm_values_uploaded{0};
     std::atomic<int64_t> predicate_route{0};     // 0 = auto, 1 = always gather the passing rows, 2 = the masked scan wherever it is eligible
     // auto rule: the masked scan when at least this many rows per thousand pass. 500 = the random mask's crossover of the FIRST build
     // (between 1/8 and 1/2 passing, profiles/r13/c_routes_first_build.json). At 10M rows the committed f32 scan crosses the gather
@@ -806,6 +822,18 @@ int sh_search_grouped(wax_hip_engine* e, const float* query, uint32_t dims, int3
                       const wax_hip_row_predicate* pred, uint64_t* out_root_ids, float* out_root_scores, uint64_t* out_member_ids,
                       float* out_member_scores, uint32_t* out_member_counts, uint32_t* out_count);
 int sh_group_stats(wax_hip_engine* e, wax_hip_group_stats_t* out);
+// One set_terms call, checked against itself (api_terms.inc): entry i's distinct terms, ascending, are flat[e_off[i] .. e_off[i + 1]) —
+// one allocation for the whole call, sorted and de-duplicated in place.
+struct TermPlan {
+    std::vector<uint32_t> flat;
+    std::vector<uint64_t> e_off;
+};
+int sh_set_terms(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, const TermPlan& plan, uint64_t* out_applied);
+int sh_get_terms(wax_hip_engine* e, uint64_t frame_id, uint32_t* out_terms, uint32_t out_capacity, uint32_t* out_count, uint8_t* out_found);
+int sh_search_terms(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, int has_allow, const uint64_t* allow, uint64_t n_allow,
+                    int has_min, float min_score, const wax_hip_row_predicate* pred, const uint32_t* required, uint32_t n_required,
+                    uint64_t* out_ids, float* out_scores, uint32_t capacity, uint32_t* out_count);
+int sh_term_stats(wax_hip_engine* e, wax_hip_term_stats_t* out);
 int sh_serialize(wax_hip_engine* e, uint8_t** out_bytes, size_t* out_len);
 int sh_deserialize(wax_hip_engine* e, const uint8_t* data, size_t len);
 void sh_destroy(wax_hip_engine* e);

@@ -58,8 +58,9 @@ static int reserve_row_lists(FilterWork& f, uint64_t m) {
 
 // A short allow-list, resolved on the host: allowed frame ids -> local rows, ascending and unique (row order is the tie-break order of
 // every path), their ids beside them, both uploaded. With a predicate only the rows that pass it stay: the authoritative attribute
-// columns are on the host too. *m = rows staged; nothing is uploaded for 0.
-static int stage_host_rows(wax_hip_engine* e, FilterWork& f, const uint64_t* allow, uint64_t n_allow, const wax_hip_row_predicate* pred, uint64_t* m) {
+// columns are on the host too; with required terms (req) only the rows whose set holds them all. *m = rows staged; nothing is uploaded for 0.
+static int stage_host_rows(wax_hip_engine* e, FilterWork& f, const uint64_t* allow, uint64_t n_allow, const wax_hip_row_predicate* pred, uint64_t* m,
+                           const TermReq* req = nullptr) {
     const uint64_t na = e->attr_ts.size();
     std::vector<uint32_t> rows;
     rows.reserve((size_t)n_allow);
@@ -67,6 +68,7 @@ static int stage_host_rows(wax_hip_engine* e, FilterWork& f, const uint64_t* all
         const int64_t r = e->idmap.find(allow[i]);
         if (r < 0) continue;
         const bool set = (uint64_t)r < na;
+        if (req && !term_row_has_all(e, (uint64_t)r, *req)) continue;   // the term column is authoritative on the host as well (DESIGN 4.11)
         if (!pred || predicate_passes(*pred, set ? e->attr_ts[(size_t)r] : 0, set ? e->attr_flags[(size_t)r] : 0u)) rows.push_back((uint32_t)r);
     }
     std::sort(rows.begin(), rows.end());
@@ -212,9 +214,14 @@ static int masked_mirror_topk(wax_hip_engine* e, FilterWork& f, const float* que
 // mask), answered by gathering them or — predicate only — by the masked scan, over the f32 store or, on a large store, over the bf16
 // mirror under the certificate ("predicate_mirror").
 static int search_rows_locked(wax_hip_engine* e, const float* query, uint32_t dims, int kpad, int has_allow, const uint64_t* allow_frame_ids,
-                              uint64_t n_allow, const wax_hip_row_predicate* pred, uint64_t* out_ids, float* out_scores,
-                              uint32_t out_capacity, uint32_t* out_n) {
+                              uint64_t n_allow, const wax_hip_row_predicate* user_pred, uint64_t* out_ids, float* out_scores,
+                              uint32_t out_capacity, uint32_t* out_n, const TermReq* req) {
     *out_n = 0;
+    // Required terms (wax_hip_search_terms; DESIGN 4.11) put term_mask_kernel in front of the attribute mask, which then always runs
+    // — under a predicate that passes every row where the caller gave none — and stays the one place that counts.
+    static const wax_hip_row_predicate pass_all{};
+    const wax_hip_row_predicate* pred = user_pred ? user_pred : (req ? &pass_all : nullptr);
+    if (req && e->term_off.empty()) { e->tm_host_decided++; return WAX_HIP_OK; }   // no frame has metadata: none matches (UnifiedSearch.swift:1219)
     if (pred) e->st_predicate_searches++;
     if (e->count == 0 || (has_allow && n_allow == 0)) return WAX_HIP_OK;
     if (pred && e->row_base + e->count > 0x100000000ull) return fail(WAX_HIP_ERR_CAPACITY, "row_base + count exceeds UInt32 row indices");
@@ -227,7 +234,8 @@ static int search_rows_locked(wax_hip_engine* e, const float* query, uint32_t di
     const int64_t dev_min = e->filter_device_min.load();
     uint64_t m = 0;
     if (has_allow && !(dev_min >= 0 && n_allow >= (uint64_t)dev_min)) {
-        { const int src = stage_host_rows(e, f, allow_frame_ids, n_allow, pred, &m); if (src != WAX_HIP_OK) return src; }
+        { const int src = stage_host_rows(e, f, allow_frame_ids, n_allow, user_pred, &m, req); if (src != WAX_HIP_OK) return src; }
+        if (req) e->tm_host_staged++;
         if (m == 0) return WAX_HIP_OK;
     } else {
         // ---- the row bitmap: [allow-list probe,] [attributes] ----
@@ -236,7 +244,10 @@ static int search_rows_locked(wax_hip_engine* e, const float* query, uint32_t di
         // and unique
         const int64_t* d_ts = nullptr;
         const uint32_t* d_fl = nullptr;
-        if (pred) { const int arc = ensure_attrs(e, st, &d_ts, &d_fl); if (arc != WAX_HIP_OK) return arc; }
+        if (user_pred) { const int arc = ensure_attrs(e, st, &d_ts, &d_fl); if (arc != WAX_HIP_OK) return arc; }
+        const uint32_t* d_term_off = nullptr;
+        const uint32_t* d_term_val = nullptr;
+        if (req) { const int trc = ensure_terms(e, st, &d_term_off, &d_term_val); if (trc != WAX_HIP_OK) return trc; }
         const uint64_t n_words = ((uint64_t)count + 31) / 32, n_blocks = filter_bitmap_blocks(count);
         int grc = grow_dev(&f.d_bitmap, &f.bitmap_words, n_words, sizeof(uint32_t), "Failed to allocate row bitmap");
         if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_block_sum, &f.block_cap, n_blocks, sizeof(uint32_t), "Failed to allocate bitmap offsets");
@@ -256,6 +267,14 @@ static int search_rows_locked(wax_hip_engine* e, const float* query, uint32_t di
                                        pred ? nullptr : f.d_block_sum, pred ? nullptr : f.d_total, st), WAX_HIP_ERR_INTERNAL, "allow-list probe launch");
             if (pred) e->st_filter_device++;
         }
+        if (req) {
+            // bit r = "row r holds every required term", ANDed into the probe's bitmap where there is a list; the attribute mask ANDs into it
+            TermMaskArgs ta{};
+            ta.off = d_term_off; ta.val = d_term_val; ta.bitmap = f.d_bitmap; ta.n_rows = count; ta.and_bitmap = has_allow ? 1 : 0;
+            fill_term_mask_req(&ta, *req);
+            HIP_TRY(launch_term_mask(ta, 0u, st), WAX_HIP_ERR_INTERNAL, "term mask launch");
+            e->tm_device_masks++;
+        }
         if (!pred) {
             HIP_TRY(launch_allow_emit(f.d_bitmap, count, f.d_block_sum, e->d_ids, f.d_rows, f.d_ids, st), WAX_HIP_ERR_INTERNAL, "allow-list compaction launch");
             HIP_TRY(hipMemcpyAsync(f.h_total, f.d_total, sizeof(uint32_t), hipMemcpyDeviceToHost, st), WAX_HIP_ERR_INTERNAL, "row count download");
@@ -269,7 +288,7 @@ static int search_rows_locked(wax_hip_engine* e, const float* query, uint32_t di
             const uint32_t mirror_chunk_rows = scan_shape && predicate_uses_mirror(e, kpad) ? mirror_masked_chunk_rows(dims) : 0u;   // 0 = the mirror form is not taken
             AttrMaskArgs ma{};
             ma.ts = d_ts; ma.flags = d_fl; ma.bitmap = f.d_bitmap; ma.counts = f.d_pred_counts; ma.n_rows = count; ma.chunk_rows = chunk_rows; ma.chunk_rows2 = mirror_chunk_rows;
-            ma.and_bitmap = has_allow ? 1 : 0;
+            ma.and_bitmap = (has_allow || req) ? 1 : 0;
             ma.has_after = pred->has_after != 0; ma.has_before = pred->has_before != 0; ma.after = pred->after; ma.before = pred->before; ma.deny_flags = pred->deny_flags;
             HIP_TRY(hipMemsetAsync(f.d_pred_counts, 0, kPredCounts * sizeof(uint32_t), st), WAX_HIP_ERR_INTERNAL, "predicate counters");
             HIP_TRY(launch_attr_mask(ma, st), WAX_HIP_ERR_INTERNAL, "attribute mask launch");

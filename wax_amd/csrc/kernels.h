@@ -764,6 +764,25 @@ struct GroupSelectArgs {
 inline uint64_t group_out_words(int32_t limit, int32_t per_group) { return 2ull * (uint64_t)limit + 1ull + 2ull * (uint64_t)limit * (uint64_t)per_group; }
 hipError_t launch_group_select(const GroupSelectArgs& a, hipStream_t st);
 
+// ---- terms.hip: the CSR term column -> row bitmap ----
+constexpr int TERMS_MAX_PER_ROW = 64;           // = WAX_HIP_TERMS_MAX_PER_ROW
+constexpr int TERMS_MAX_REQUIRED = 16;          // = WAX_HIP_TERMS_MAX_REQUIRED
+constexpr uint32_t TERM_MASK_PIECE = 1024;      // term_mask_wave_kernel: values of a wave's span consumed per loop iteration, 4 dwordx4 loads per lane in flight
+constexpr uint32_t TERM_MASK_MAX_GRID = 1024;   // the probe's largest grid (workgroups of 256 lanes, 256 rows each, grid-strided); the product's own is terms.hip's
+// bit r of bitmap = "values[off[r] .. off[r + 1]) contain every one of req[0 .. 16)". The host fills req's unused slots with req[0], so
+// the test is the same sixteen compares whatever the number of required terms. Every word of the bitmap is written; bits of rows >=
+// n_rows are clear. `val` must be readable in whole 16-byte pieces up to the end of the piece that holds off[n_rows] - 1.
+struct TermMaskArgs {
+    const uint32_t* off;        // [n_rows + 1] non-decreasing; a row's set holds at most TERMS_MAX_PER_ROW values
+    const uint32_t* val;        // 16-byte aligned
+    uint32_t* bitmap;           // [ceil(n_rows / 32)]
+    uint32_t n_rows;
+    int32_t and_bitmap;         // != 0: the bitmap already holds the allow-list's rows (filter.hip's probe): AND into it
+    uint32_t req[TERMS_MAX_REQUIRED];
+};
+// grid 0 = the product's own: one workgroup per 256 rows, at most WAX_TERM_MASK_GRID_CAP (terms.hip)
+hipError_t launch_term_mask(const TermMaskArgs& a, uint32_t grid, hipStream_t st);
+
 // ---- rrf.hip: reciprocal-rank fusion of ranked id lists, one workgroup per query ----
 hipError_t launch_rrf_fuse(const wax_hip_rrf_lane* lanes, uint32_t n_lanes, uint32_t nq, int32_t k, uint64_t* out_ids,
                            float* out_scores, uint32_t* out_best_rank, uint32_t* out_sources, uint32_t out_stride,

@@ -393,6 +393,8 @@ int sh_move_all(ShardedState* s, size_t from, size_t to) {
     { const int frc = flush_pending(src); if (frc != WAX_HIP_OK) return frc; }
     const uint64_t n = src->count;
     if (n == 0) return WAX_HIP_OK;
+    if (!src->term_off.empty() && (uint64_t)src->term_off.back() + (dst->term_off.empty() ? 0u : dst->term_off.back()) >= 0x100000000ull)
+        return fail(WAX_HIP_ERR_CAPACITY, "rebalance: the target shard would hold 2^32 terms or more");   // (before any row moves)
     const uint32_t D = src->dims;
     const uint64_t chunk = std::max<uint64_t>(1, (64ull << 20) / ((uint64_t)D * 4));
     float* d_tmp = nullptr;
@@ -420,6 +422,7 @@ int sh_move_all(ShardedState* s, size_t from, size_t to) {
         dst->count = dst_before;
         if (dst->attr_ts.size() > dst_before) { dst->attr_ts.resize((size_t)dst_before); dst->attr_flags.resize((size_t)dst_before); }
         parent_note_moved(dst, dst_before);
+        term_note_moved(dst, dst_before);
         mirror_note_replaced(dst);     // (rows were appended and taken back: the mirror and the id table start over)
         return rc;
     }
@@ -434,6 +437,14 @@ int sh_move_all(ShardedState* s, size_t from, size_t to) {
         dst->attr_parent.resize((size_t)dst_before, WAX_HIP_NO_PARENT);
         dst->attr_parent.insert(dst->attr_parent.end(), src->attr_parent.begin(), src->attr_parent.end());
         parent_note_moved(dst, dst_before);
+    }
+    if (!src->term_off.empty()) {                              // and their term sets (DESIGN 4.11): dst's rows up to there hold what they held
+        if (dst->term_off.empty()) dst->term_off.push_back(0u);
+        dst->term_off.resize((size_t)dst_before + 1, dst->term_off.back());
+        const uint32_t base = dst->term_off.back(), src0 = src->term_off.front();
+        for (size_t r = 1; r < src->term_off.size(); ++r) dst->term_off.push_back(base + (src->term_off[r] - src0));
+        dst->term_val.insert(dst->term_val.end(), src->term_val.begin(), src->term_val.end());
+        term_note_moved(dst, dst_before);
     }
     attr_note_replaced(src);
     // empty the source (capacity stays)
@@ -1490,6 +1501,68 @@ int sh_group_stats(wax_hip_engine* e, wax_hip_group_stats_t* out) {
         if (rc != WAX_HIP_OK) return rc;
         out->searches += one.searches; out->fused_scans += one.fused_scans; out->column_scans += one.column_scans;
         out->member_rounds += one.member_rounds; out->group_slots += one.group_slots; out->parent_rows_uploaded += one.parent_rows_uploaded;
+    }
+    return WAX_HIP_OK;
+}
+
+// setTerms / getTerms on a handle: sh_set_parents' routing — the entries of the validated plan go to the shard that owns their frame.
+// Every shard's total is checked before any shard is changed: a refusal leaves the whole handle as it was.
+int sh_set_terms(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, const TermPlan& plan, uint64_t* out_applied) {
+    ShardedState* s = e->sh;
+    REFUSE_IF_HOLDING(e);
+    WriteGuard w(e->lock);
+    const size_t G = s->subs.size();
+    std::vector<TermRows> rows(G);
+    uint64_t applied = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        int64_t local = -1;
+        const int g = sh_find(s, frame_ids[i], &local);
+        if (g < 0) continue;
+        ++applied;
+        rows[(size_t)g].emplace_back((uint64_t)local, i);
+    }
+    std::vector<std::unique_ptr<WriteGuard>> sub_locks;        // (in shard order; searches of the shards' workers hold their shared locks)
+    for (size_t g = 0; g < G; ++g) {
+        if (rows[g].empty()) continue;
+        finish_term_rows(&rows[g]);
+        sub_locks.emplace_back(new WriteGuard(s->subs[g]->lock));
+        if (term_total_after(s->subs[g], plan, rows[g]) >= 0x100000000ull)
+            return fail(WAX_HIP_ERR_CAPACITY, "setTerms: a shard would hold 2^32 terms or more");
+    }
+    for (size_t g = 0; g < G; ++g)
+        if (!rows[g].empty()) commit_term_rows(s->subs[g], plan, rows[g]);
+    if (out_applied) *out_applied = applied;
+    return WAX_HIP_OK;
+}
+
+int sh_get_terms(wax_hip_engine* e, uint64_t frame_id, uint32_t* out_terms, uint32_t out_capacity, uint32_t* out_count, uint8_t* out_found) {
+    ShardedState* s = e->sh;
+    ReadGuard rd(e);
+    int64_t local = -1;
+    const int g = sh_find(s, frame_id, &local);
+    if (g < 0) return WAX_HIP_OK;
+    return wax_hip_get_terms(s->subs[(size_t)g], frame_id, out_terms, out_capacity, out_count, out_found);
+}
+
+// The term search on a handle: every shard masks and searches its own rows (its term column follows its rows).
+int sh_search_terms(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, int has_allow, const uint64_t* allow, uint64_t n_allow,
+                    int has_min, float min_score, const wax_hip_row_predicate* pred, const uint32_t* required, uint32_t n_required,
+                    uint64_t* out_ids, float* out_scores, uint32_t capacity, uint32_t* out_count) {
+    return sh_fanout_filtered(e, dims, top_k, out_ids, out_scores, capacity, out_count,
+                              [&](wax_hip_engine* sub, uint64_t* ids, float* scores, uint32_t cap, uint32_t* n) {
+                                  return wax_hip_search_terms(sub, query, dims, top_k, has_allow, allow, n_allow, has_min, min_score, pred, required,
+                                                              n_required, ids, scores, cap, n);
+                              });
+}
+
+int sh_term_stats(wax_hip_engine* e, wax_hip_term_stats_t* out) {
+    *out = wax_hip_term_stats_t{};
+    for (wax_hip_engine* sub : e->sh->subs) {
+        wax_hip_term_stats_t one{};
+        const int rc = wax_hip_term_stats(sub, &one);
+        if (rc != WAX_HIP_OK) return rc;
+        out->searches += one.searches; out->device_masks += one.device_masks; out->host_staged += one.host_staged;
+        out->host_decided += one.host_decided; out->term_rows_uploaded += one.term_rows_uploaded; out->term_values_uploaded += one.term_values_uploaded;
     }
     return WAX_HIP_OK;
 }

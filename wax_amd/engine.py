@@ -278,13 +278,19 @@ class HIPVectorEngine:
         return ids[:got.value].copy(), scores[:got.value].copy()
 
     def searchFiltered(self, vector, topK: int, frameIds=None, minScore=None, timeRange=None,  # noqa: N802,N803
-                       denyFlags: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+                       denyFlags: int = 0, requiredTerms=None) -> Tuple[np.ndarray, np.ndarray]:
         """The vector lane's candidate filters applied on the device (UnifiedSearch.swift:1241-1258): `frameIds` is
         FrameFilter.frameIds (allow-list; None = no list, empty = nothing allowed), `minScore` is SearchRequest.minScore,
         `timeRange` = (after | None, before | None) is SearchRequest.timeRange against the rows' timestamps (after inclusive,
         before exclusive: TimeRange.contains), `denyFlags` drops every row with one of these flag bits set (setAttributes).
         Returns the best topK among the frames that PASS (a pre-filter), best first, minus those scoring below minScore.
-        A call without timeRange / denyFlags takes wax_hip_search_filtered, as before those arguments existed."""
+        A call without timeRange / denyFlags takes wax_hip_search_filtered, as before those arguments existed.
+        `requiredTerms` is FrameFilter.metadataFilter through a TermDictionary (setTerms): only rows whose term set holds every one
+        of these ids pass (wax_hip_search_terms). None or an empty list takes the paths above exactly; TermDictionary.NO_MATCH (a
+        required string nobody ever interned) returns empty arrays without a call."""
+        if requiredTerms is TermDictionary.NO_MATCH:
+            return np.empty(0, dtype=np.uint64), np.empty(0, dtype=np.float32)
+        req = None if requiredTerms is None else np.ascontiguousarray(list(requiredTerms), dtype=np.uint32).reshape(-1)
         q = _as_f32(vector).reshape(-1)
         cap = self._result_capacity(topK)
         ids = np.empty(cap, dtype=np.uint64)
@@ -297,7 +303,10 @@ class HIPVectorEngine:
                 0 if allow is None else int(allow.size),
                 0 if minScore is None else 1, 0.0 if minScore is None else float(minScore))
         tail = (_u64p(ids), _fp(scores), cap, ctypes.byref(got))
-        if timeRange is None and not denyFlags:
+        if req is not None and req.size:
+            pred = ticket_predicate(timeRange, denyFlags, who="searchFiltered")
+            rc = self._lib.wax_hip_search_terms(*head, ctypes.byref(pred), req.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), int(req.size), *tail)
+        elif timeRange is None and not denyFlags:
             rc = self._lib.wax_hip_search_filtered(*head, *tail)
         else:
             after, before = (None, None) if timeRange is None else timeRange
@@ -365,6 +374,51 @@ class HIPVectorEngine:
             raise_for_status(self._lib.wax_hip_get_parents(self._h, _u64p(ids), n, _u64p(par),
                                                            found.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
         return par, found.astype(bool)
+
+    def setTerms(self, frameIds, terms) -> int:  # noqa: N802,N803
+        """The term SETS of the listed frames for searchFiltered(requiredTerms=...) (wax_hip_set_terms): `terms` is a sequence of
+        iterables of int (uint32 ids of a TermDictionary), one per frame id, or a 2-D array [n, width]; each replaces the frame's whole set, an empty one clears
+        it, duplicates collapse, at most TERMS_MAX_PER_ROW distinct terms. Ids the engine does not hold are skipped; an id listed
+        twice takes its last entry. Returns the entries that named a held frame."""
+        ids = np.ascontiguousarray(frameIds, dtype=np.uint64).reshape(-1)
+        n = int(ids.size)
+        if isinstance(terms, np.ndarray) and terms.ndim == 2:       # [n, width]: every set of the same size, without a Python loop
+            if terms.shape[0] != n:
+                raise EncodingError("setTerms: one term set per frame id")
+            flat = np.ascontiguousarray(terms, dtype=np.uint32).reshape(-1)
+            lens = np.full(n, terms.shape[1], dtype=np.uint32)
+            begin = np.arange(n, dtype=np.uint64) * np.uint64(terms.shape[1])
+        else:
+            sets = [np.asarray(list(t) if not isinstance(t, np.ndarray) else t, dtype=np.uint32).reshape(-1) for t in terms]
+            if len(sets) != n:
+                raise EncodingError("setTerms: one term set per frame id")
+            lens = np.array([t.size for t in sets], dtype=np.uint32)
+            begin = np.zeros(n, dtype=np.uint64)
+            np.cumsum(lens[:-1], out=begin[1:])
+            flat = np.ascontiguousarray(np.concatenate(sets) if n else np.empty(0), dtype=np.uint32)
+        if n == 0:
+            return 0
+        applied = ctypes.c_uint64(0)
+        u32 = ctypes.POINTER(ctypes.c_uint32)
+        raise_for_status(self._lib.wax_hip_set_terms(self._h, _u64p(ids), _u64p(begin), lens.ctypes.data_as(u32),
+                                                     flat.ctypes.data_as(u32) if flat.size else None, int(flat.size), n, ctypes.byref(applied)))
+        return int(applied.value)
+
+    def getTerms(self, frameId: int):  # noqa: N802,N803
+        """The frame's term set, ascending (uint32 array), or None for a frame the engine does not hold."""
+        out = np.empty(_abi.TERMS_MAX_PER_ROW, dtype=np.uint32)
+        got = ctypes.c_uint32(0)
+        found = ctypes.c_uint8(0)
+        raise_for_status(self._lib.wax_hip_get_terms(self._h, int(frameId), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), int(out.size),
+                                                     ctypes.byref(got), ctypes.byref(found)))
+        return out[:got.value].copy() if found.value else None
+
+    def termStats(self) -> dict:  # noqa: N802
+        """What the term searches did (wax_hip_term_stats): searches, device_masks, host_staged, host_decided, term_rows_uploaded,
+        term_values_uploaded."""
+        st = _abi.TermStats()
+        raise_for_status(self._lib.wax_hip_term_stats(self._h, ctypes.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in _abi.TermStats._fields_}
 
     def searchGrouped(self, vector, limit: int, perGroup: int = 1, timeRange=None, denyFlags: int = 0, minScore=None):  # noqa: N802,N803
         """What PhotoRAGOrchestrator.recall / VideoRAGOrchestrator.recall make of the vector lane, exactly and on the device
@@ -774,6 +828,92 @@ def groupProbe(distances, slots, slotRoot, limit: int, perGroup: int = 1, bitmap
                                         _u64p(roots), rkeys.ctypes.data_as(i64p), mkeys.ctypes.data_as(i64p), ctypes.byref(got))
     raise_for_status(rc)
     return roots, rkeys, mkeys, int(got.value)
+
+
+def termMaskProbe(offsets, values, required, bitmapIn=None, grid: int = 1) -> np.ndarray:  # noqa: N802,N803
+    """wax_hip_term_mask_probe: term_mask_kernel on a made-up CSR column — offsets [rows + 1], values [offsets[-1]], `required` 1 .. 16
+    terms, `bitmapIn` (uint32 words, None = none) ANDed in, exactly `grid` workgroups. Returns the row bitmap (uint32 words)."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+    val = np.ascontiguousarray(values, dtype=np.uint32).reshape(-1)
+    req = np.ascontiguousarray(required, dtype=np.uint32).reshape(-1)
+    rows = int(off.size) - 1
+    if rows < 0 or (rows >= 0 and val.size != int(off[-1])):
+        raise EncodingError("termMaskProbe: offsets of rows + 1 entries, values of offsets[-1] entries")
+    words = (max(rows, 0) + 31) // 32
+    bm = None if bitmapIn is None else np.ascontiguousarray(bitmapIn, dtype=np.uint32).reshape(-1)
+    if bm is not None and bm.size != words:
+        raise EncodingError("termMaskProbe: one bitmap word per 32 rows")
+    out = np.zeros(words, dtype=np.uint32)
+    u32 = ctypes.POINTER(ctypes.c_uint32)
+    raise_for_status(_abi.lib().wax_hip_term_mask_probe(off.ctypes.data_as(u32), val.ctypes.data_as(u32) if val.size else None, rows,
+                                                        req.ctypes.data_as(u32) if req.size else None, int(req.size),
+                                                        None if bm is None else bm.ctypes.data_as(u32), int(grid), out.ctypes.data_as(u32)))
+    return out
+
+
+class _NoMatch:
+    """TermDictionary.NO_MATCH: a filter that names a string no frame was ever given."""
+    def __repr__(self):
+        return "TermDictionary.NO_MATCH"
+
+
+class TermDictionary:
+    """The caller's side of the term column: interns ("entry", key, value), ("tag", key, value) and ("label", s) to uint32 ids, so
+    that FrameFilter.metadataFilter (SearchRequest.swift:130-145) becomes a list of required ids and a frame's
+    FrameMeta.metadata.entries / tags / labels become its term set — exactly (no hashing, no collisions). The engine never sees
+    a string."""
+    NO_MATCH = _NoMatch()
+
+    def __init__(self):
+        self._ids = {}
+        self._keys = []
+
+    def __len__(self):
+        return len(self._keys)
+
+    def _intern(self, key) -> int:
+        i = self._ids.get(key)
+        if i is None:
+            if len(self._keys) >= 0xffffffff:
+                raise EncodingError("TermDictionary: more than 2^32 - 1 terms")
+            i = len(self._keys)
+            self._ids[key] = i
+            self._keys.append(key)
+        return i
+
+    def entry(self, key: str, value: str) -> int:
+        return self._intern(("entry", str(key), str(value)))
+
+    def tag(self, key: str, value: str) -> int:
+        return self._intern(("tag", str(key), str(value)))
+
+    def label(self, s: str) -> int:
+        return self._intern(("label", str(s)))
+
+    def lookup(self, termId: int):  # noqa: N803
+        """The ("entry" | "tag", key, value) or ("label", s) tuple behind an id."""
+        return self._keys[int(termId)]
+
+    def forFrame(self, entries=None, tags=None, labels=None) -> List[int]:  # noqa: N802
+        """A frame's term set (interning what is new): `entries` a mapping, `tags` an iterable of (key, value), `labels` of strings."""
+        out = {self.entry(k, v) for k, v in dict(entries or {}).items()}
+        out |= {self.tag(k, v) for k, v in (tags or ())}
+        out |= {self.label(s) for s in (labels or ())}
+        return sorted(out)
+
+    def forFilter(self, requiredEntries=None, requiredTags=None, requiredLabels=None):  # noqa: N802,N803
+        """MetadataFilter -> the ids searchFiltered(requiredTerms=...) takes; NO_MATCH when a required string was never interned (no
+        frame can hold it). Nothing is interned. An empty filter gives []."""
+        keys = [("entry", str(k), str(v)) for k, v in dict(requiredEntries or {}).items()]
+        keys += [("tag", str(k), str(v)) for k, v in (requiredTags or ())]
+        keys += [("label", str(s)) for s in (requiredLabels or ())]
+        out = set()
+        for key in keys:
+            i = self._ids.get(key)
+            if i is None:
+                return TermDictionary.NO_MATCH
+            out.add(i)
+        return sorted(out)
 
 
 def ticket_predicate(timeRange=None, denyFlags=0, who: str = "submitFiltered") -> "_abi.RowPredicate":  # noqa: N803
