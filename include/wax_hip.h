@@ -620,6 +620,40 @@ typedef struct wax_hip_term_stats_t {
     uint64_t searches, device_masks, host_staged, host_decided, term_rows_uploaded, term_values_uploaded;
 } wax_hip_term_stats_t;
 int wax_hip_term_stats(wax_hip_engine* e, wax_hip_term_stats_t* out);
+/* wax_hip_search_batch_predicate with a required-term set PER QUERY: query q requires
+ * required_terms[term_begin[q] .. term_begin[q] + term_len[q]) (the allow_begin / allow_len convention; length 0 = no term filter for
+ * q). Both arrays NULL: no query has one, and the call IS wax_hip_search_batch_predicate — one body, the same launches, the same
+ * counters. Row q equals, bit for bit (ids, scores, count, ties in ascending row order),
+ * wax_hip_search_terms(e, query q, ..., list q, cut q, &preds[q], terms q, ...) with out_capacity = out_stride.
+ * Refusals: those of wax_hip_search_batch_predicate in its order; then one of term_begin / term_len given without the other; then a
+ * span that leaves [0, n_required_terms) (or a non-empty span with required_terms NULL); then a set of more than
+ * WAX_HIP_TERMS_MAX_REQUIRED distinct terms (duplicates collapse first). The outputs are untouched and the message names the query.
+ * Queries whose sets are equal AS SETS — whatever the order or the duplicates — share a set, and with the same list and predicate
+ * an entry of the pass. On a store that never had terms every query with a non-empty set gets count 0 without device work.
+ * Entries without an allow-list: term_mask_multi_kernel reads the CSR term column ONCE for up to 32 distinct sets (further launches
+ * beyond 32) and writes one row bitmap and one passing count per set; the counts are downloaded (one small copy, one synchronisation,
+ * only in calls that have such entries), an entry's upper bound is its set's count — not the store's — and a count of 0 ends it; the
+ * entries' row lists then come from the three launches of wax_hip_search_batch_predicate with the bitmap ANDed in. Sets are admitted in
+ * order of their first query while there are at most 256 of them and their bitmaps fit 256 MiB. Entries with a list of at most 16 384
+ * ids: the LDS sort drops a probed row that lacks a required term, beside the predicate test. Queries with a longer list and terms,
+ * and those of sets or entries that are not admitted, take wax_hip_search_terms' body under the lock held. A term query is charged as
+ * a predicate query is — one without a predicate as one whose predicate passes every row; "predicate_batch_rows" applies to the
+ * upper bounds above. A sharded handle runs every shard on its workers and merges as wax_hip_search_batch_predicate does. */
+int wax_hip_search_batch_terms(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
+                               const uint64_t* allow_frame_ids, uint64_t n_allow_ids,
+                               const uint64_t* allow_begin, const uint64_t* allow_len,
+                               const float* min_scores, const wax_hip_row_predicate* preds,
+                               const uint32_t* required_terms, uint64_t n_required_terms,
+                               const uint64_t* term_begin, const uint32_t* term_len,
+                               uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts);
+/* What the wax_hip_search_batch_terms calls with at least one term query did (no tuning key): calls; queries = term queries answered by
+ * the shared pass; sets = distinct term sets sent to the device by those passes; mask_launches = term_mask_multi_kernel launches;
+ * looped = term queries answered by the single-query body; host_decided = term queries answered empty because the store never had
+ * terms. A sharded handle reports the sums over its shards. */
+typedef struct wax_hip_term_batch_stats_t {
+    uint64_t calls, queries, sets, mask_launches, looped, host_decided;
+} wax_hip_term_batch_stats_t;
+int wax_hip_term_batch_stats(wax_hip_engine* e, wax_hip_term_batch_stats_t* out);
 
 /* ---- persistence: "MV2V" vec segment, encoding 2 ------------------------- */
 
@@ -850,6 +884,12 @@ int wax_hip_group_probe(const float* distances, const uint32_t* slots, const uin
  * terms, duplicates collapse), ANDed with bitmap_in where that is not NULL; bits at and beyond n_rows are clear. Blocking. */
 int wax_hip_term_mask_probe(const uint32_t* offsets, const uint32_t* values, uint64_t n_rows, const uint32_t* required, uint32_t n_required,
                             const uint32_t* bitmap_in, uint32_t grid, uint32_t* out_bitmap);
+/* The same for term_mask_multi_kernel: n_sets (1 .. 32) term sets, set s = required[set_begin[s] .. set_begin[s] + set_len[s]) (1 ..
+ * WAX_HIP_TERMS_MAX_REQUIRED distinct terms each, duplicates collapse; a row's values must be distinct), ONE launch of exactly `grid`
+ * workgroups (1 .. 1 024) writes out_bitmaps[n_sets][ceil(n_rows / 32)] and out_counts[n_sets] = the rows that pass each set. Blocking. */
+int wax_hip_term_mask_multi_probe(const uint32_t* offsets, const uint32_t* values, uint64_t n_rows, const uint32_t* required,
+                                  const uint64_t* set_begin, const uint32_t* set_len, uint32_t n_sets, uint32_t grid,
+                                  uint32_t* out_bitmaps, uint32_t* out_counts);
 
 #ifdef __cplusplus
 }

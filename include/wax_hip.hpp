@@ -164,6 +164,87 @@ class VectorEngine {
         for (uint32_t i = 0; i < n; ++i) out[i] = {ids[i], scores[i]};
         return out;
     }
+    /// The term SETS of the listed frames (wax_hip_set_terms): terms[i] replaces the whole set of frameIds[i]; an empty one clears it.
+    uint64_t setTerms(const std::vector<uint64_t>& frameIds, const std::vector<std::vector<uint32_t>>& terms) {
+        if (frameIds.size() != terms.size()) throw std::invalid_argument("setTerms: one term set per frame id");
+        std::vector<uint32_t> flat, len(terms.size());
+        std::vector<uint64_t> begin(terms.size());
+        for (size_t i = 0; i < terms.size(); ++i) {
+            begin[i] = flat.size();
+            len[i] = (uint32_t)terms[i].size();
+            flat.insert(flat.end(), terms[i].begin(), terms[i].end());
+        }
+        uint64_t applied = 0;
+        if (!frameIds.empty())
+            check(wax_hip_set_terms(h_, frameIds.data(), begin.data(), len.data(), flat.empty() ? nullptr : flat.data(), flat.size(), frameIds.size(),
+                                    &applied));
+        return applied;
+    }
+    /// The frame's term set, ascending; `found` (may be null) says whether the engine holds the frame.
+    std::vector<uint32_t> getTerms(uint64_t frameId, bool* found = nullptr) {
+        std::vector<uint32_t> out(WAX_HIP_TERMS_MAX_PER_ROW);
+        uint32_t n = 0;
+        uint8_t f = 0;
+        check(wax_hip_get_terms(h_, frameId, out.data(), (uint32_t)out.size(), &n, &f));
+        if (found) *found = f != 0;
+        out.resize(n);
+        return out;
+    }
+    /// searchPredicate among the frames whose term set holds every one of `required` (wax_hip_search_terms); pred null = no predicate.
+    std::vector<std::pair<uint64_t, float>> searchTerms(const std::vector<float>& q, int topK, const std::vector<uint64_t>* allow,
+                                                        const float* minScore, const wax_hip_row_predicate* pred,
+                                                        const std::vector<uint32_t>& required) {
+        const uint32_t cap = wax_hip_result_capacity(topK);
+        std::vector<uint64_t> ids(cap);
+        std::vector<float> scores(cap);
+        uint32_t n = 0;
+        check(wax_hip_search_terms(h_, q.data(), (uint32_t)q.size(), topK, allow ? 1 : 0,
+                                   allow && !allow->empty() ? allow->data() : nullptr, allow ? allow->size() : 0,
+                                   minScore ? 1 : 0, minScore ? *minScore : 0.0f, pred, required.empty() ? nullptr : required.data(),
+                                   (uint32_t)required.size(), ids.data(), scores.data(), cap, &n));
+        std::vector<std::pair<uint64_t, float>> out(n);
+        for (uint32_t i = 0; i < n; ++i) out[i] = {ids[i], scores[i]};
+        return out;
+    }
+    /// searchBatchPredicate plus a required-term set per query (wax_hip_search_batch_terms): `required` holds one entry per query (an
+    /// empty one: no term filter for that query) or is empty (no query has one). Query q is what searchTerms(query q, ...) returns.
+    std::vector<std::vector<std::pair<uint64_t, float>>> searchBatchTerms(const std::vector<float>& queries, uint32_t nq, int topK,
+                                                                          const std::vector<const std::vector<uint64_t>*>& allow,
+                                                                          const std::vector<float>* minScores,
+                                                                          const std::vector<wax_hip_row_predicate>& preds,
+                                                                          const std::vector<std::vector<uint32_t>>& required) {
+        if (!preds.empty() && preds.size() != nq) throw std::invalid_argument("searchBatchTerms: one predicate per query, or none");
+        if (!required.empty() && required.size() != nq) throw std::invalid_argument("searchBatchTerms: one term set per query, or none");
+        const uint32_t dims = nq ? (uint32_t)(queries.size() / nq) : 0;
+        const uint32_t stride = wax_hip_result_capacity(topK);
+        std::vector<uint64_t> flat, begin(nq), len(nq), tbegin(required.size());
+        std::vector<uint32_t> tflat, tlen(required.size());
+        for (uint32_t q = 0; q < nq; ++q) {
+            const std::vector<uint64_t>* a = q < allow.size() ? allow[q] : nullptr;
+            begin[q] = flat.size();
+            len[q] = a ? a->size() : WAX_HIP_NO_ALLOW_LIST;
+            if (a) flat.insert(flat.end(), a->begin(), a->end());
+        }
+        for (size_t q = 0; q < required.size(); ++q) {
+            tbegin[q] = tflat.size();
+            tlen[q] = (uint32_t)required[q].size();
+            tflat.insert(tflat.end(), required[q].begin(), required[q].end());
+        }
+        std::vector<uint64_t> ids((size_t)nq * stride);
+        std::vector<float> scores((size_t)nq * stride);
+        std::vector<uint32_t> counts(nq);
+        check(wax_hip_search_batch_terms(h_, queries.data(), nq, dims, topK, flat.data(), flat.size(), begin.data(), len.data(),
+                                         minScores ? minScores->data() : nullptr, preds.empty() ? nullptr : preds.data(),
+                                         tflat.empty() ? nullptr : tflat.data(), tflat.size(), required.empty() ? nullptr : tbegin.data(),
+                                         required.empty() ? nullptr : tlen.data(), ids.data(), scores.data(), stride, counts.data()));
+        std::vector<std::vector<std::pair<uint64_t, float>>> out(nq);
+        for (uint32_t q = 0; q < nq; ++q)
+            for (uint32_t i = 0; i < counts[q]; ++i) out[q].emplace_back(ids[(size_t)q * stride + i], scores[(size_t)q * stride + i]);
+        return out;
+    }
+    /// What the term searches / the batched term searches did (wax_hip_term_stats, wax_hip_term_batch_stats).
+    wax_hip_term_stats_t termStats() { wax_hip_term_stats_t st{}; check(wax_hip_term_stats(h_, &st)); return st; }
+    wax_hip_term_batch_stats_t termBatchStats() { wax_hip_term_batch_stats_t st{}; check(wax_hip_term_batch_stats(h_, &st)); return st; }
     /// Pending-embedding replay: WAL putEmbedding payloads back to back (UnifiedSearchEngineCache.swift:252-283).
     uint64_t applyPutEmbeddings(const uint8_t* payloads, uint64_t len) {
         uint64_t applied = 0;

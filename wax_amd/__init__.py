@@ -6,12 +6,12 @@ The product is `wax_amd/lib/libwaxhip.so` (hand-written HIP kernels behind the C
 """
 from .errors import CapacityExceeded, EncodingError, InvalidToc, WaxError
 from .vector_metric import VectorEnginePreference, VectorMetric
-from .engine import HIPVectorEngine, BufferPoolStats, clampTopK, searchMany, searchManyFiltered, timelineProbe, TIMELINE_MAX_LIMIT, groupProbe, termMaskProbe, TermDictionary
+from .engine import HIPVectorEngine, BufferPoolStats, clampTopK, searchMany, searchManyFiltered, timelineProbe, TIMELINE_MAX_LIMIT, groupProbe, termMaskProbe, termMaskMultiProbe, TermDictionary
 from . import vector_math as VectorMath
 from . import vector_serializer as VectorSerializer
 from . import hybrid_search as HybridSearch
 
 __all__ = [
-    "HIPVectorEngine", "BufferPoolStats", "clampTopK", "searchMany", "searchManyFiltered", "timelineProbe", "TIMELINE_MAX_LIMIT", "groupProbe", "termMaskProbe", "TermDictionary", "VectorMetric", "VectorEnginePreference", "VectorMath",
+    "HIPVectorEngine", "BufferPoolStats", "clampTopK", "searchMany", "searchManyFiltered", "timelineProbe", "TIMELINE_MAX_LIMIT", "groupProbe", "termMaskProbe", "termMaskMultiProbe", "TermDictionary", "VectorMetric", "VectorEnginePreference", "VectorMath",
     "VectorSerializer", "HybridSearch", "WaxError", "EncodingError", "CapacityExceeded", "InvalidToc",
 ]

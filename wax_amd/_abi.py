@@ -86,6 +86,11 @@ class TermStats(ctypes.Structure):
                                                      "term_values_uploaded")]
 
 
+class TermBatchStats(ctypes.Structure):
+    """wax_hip_term_batch_stats_t (include/wax_hip.h)."""
+    _fields_ = [(name, ctypes.c_uint64) for name in ("calls", "queries", "sets", "mask_launches", "looped", "host_decided")]
+
+
 TERMS_MAX_PER_ROW = 64          # WAX_HIP_TERMS_MAX_PER_ROW
 TERMS_MAX_REQUIRED = 16         # WAX_HIP_TERMS_MAX_REQUIRED
 NO_PARENT = (1 << 64) - 1       # WAX_HIP_NO_PARENT: the row is its own root
@@ -203,6 +208,12 @@ SIGNATURES: Dict[str, tuple] = {
     "wax_hip_search_terms": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int, _u64p, ctypes.c_uint64, ctypes.c_int,
                                             ctypes.c_float, ctypes.POINTER(RowPredicate), _u32p, ctypes.c_uint32, _u64p, _f32p, ctypes.c_uint32, _u32p]),
     "wax_hip_term_stats": (ctypes.c_int, [_engine_p, ctypes.POINTER(TermStats)]),
+    "wax_hip_search_batch_terms": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, _u64p,
+                                                  ctypes.c_uint64, _u64p, _u64p, _f32p, ctypes.POINTER(RowPredicate), _u32p, ctypes.c_uint64,
+                                                  _u64p, _u32p, _u64p, _f32p, ctypes.c_uint32, _u32p]),
+    "wax_hip_term_batch_stats": (ctypes.c_int, [_engine_p, ctypes.POINTER(TermBatchStats)]),
+    "wax_hip_term_mask_multi_probe": (ctypes.c_int, [_u32p, _u32p, ctypes.c_uint64, _u32p, _u64p, _u32p, ctypes.c_uint32, ctypes.c_uint32,
+                                                     _u32p, _u32p]),
     "wax_hip_term_mask_probe": (ctypes.c_int, [_u32p, _u32p, ctypes.c_uint64, _u32p, ctypes.c_uint32, _u32p, ctypes.c_uint32, _u32p]),
     "wax_hip_group_probe": (ctypes.c_int, [_f32p, _u32p, _u64p, _u32p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32,
                                            ctypes.c_uint32, _u64p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _u32p]),

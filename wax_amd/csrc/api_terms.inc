@@ -1,7 +1,9 @@
 // api_terms.inc — part of engine.hip's translation unit (included there; not compiled alone).
 // C ABI: the per-row term column (set / get), its device copy, the required-term search, its read-out and the kernel's probe
 // (DESIGN 4.11; FrameFilter.metadataFilter, SearchRequest.swift:130-145; matches(metadataFilter:meta:), UnifiedSearch.swift:1215-1239).
-// The search itself is search_rows_locked (filter_host.inc) with the term mask in front of the attribute mask.
+// The search itself is search_rows_locked (filter_host.inc) with the term mask in front of the attribute mask. The batched form
+// (wax_hip_search_batch_terms) is filter_host.inc's batched body with a term set per entry; its term sets, the tables of
+// term_mask_multi_kernel, its read-out and that kernel's probe are here.
 
 // filter_host.inc
 static inline bool predicate_is_empty(const wax_hip_row_predicate* p);
@@ -37,6 +39,64 @@ static bool term_row_has_all(const wax_hip_engine* e, uint64_t r, const TermReq&
     for (uint32_t i = 0; i < req.n; ++i)
         if (!std::binary_search(b, en, req.t[i])) return false;
     return true;
+}
+
+// The term sets of one wax_hip_search_batch_terms call: the distinct sets in order of their first query (sets equal as sets are one),
+// and each query's set (-1: no term filter).
+struct BatchTerms {
+    std::vector<TermReq> sets;
+    std::vector<int32_t> of;
+    const TermReq* req(uint32_t q) const { return of[q] >= 0 ? &sets[(size_t)of[q]] : nullptr; }
+};
+
+// The call's term arguments against themselves (no engine is looked at). *any = some query has a non-empty set.
+static int make_batch_terms(uint32_t nq, const uint32_t* required_terms, uint64_t n_required_terms, const uint64_t* term_begin,
+                            const uint32_t* term_len, BatchTerms* out, bool* any) {
+    *any = false;
+    if ((term_begin == nullptr) != (term_len == nullptr))
+        return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "term_begin and term_len must both be given or both be null");
+    if (!term_len) return WAX_HIP_OK;
+    for (uint32_t q = 0; q < nq; ++q) {
+        if (term_begin[q] > n_required_terms || term_len[q] > n_required_terms - term_begin[q])
+            return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "term range of query " + std::to_string(q) + " leaves the term array");
+        if (term_len[q] != 0 && !required_terms) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "required terms of query " + std::to_string(q) + " are null");
+    }
+    out->of.assign(nq, -1);
+    std::map<std::vector<uint32_t>, int32_t> index;
+    for (uint32_t q = 0; q < nq; ++q) {
+        if (term_len[q] == 0) continue;
+        TermReq r;
+        if (!make_term_req(required_terms + term_begin[q], term_len[q], &r))
+            return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "searchBatchTerms: query " + std::to_string(q) + " requires more than " +
+                                                          std::to_string(TERMS_MAX_REQUIRED) + " distinct terms");
+        auto it = index.emplace(std::vector<uint32_t>(r.t, r.t + r.n), (int32_t)out->sets.size());
+        if (it.second) out->sets.push_back(r);
+        out->of[q] = it.first->second;
+        *any = true;
+    }
+    return WAX_HIP_OK;
+}
+
+// The tables of one term_mask_multi_kernel launch over sets[0 .. n_sets) (1 .. TERM_MULTI_MAX_SETS): the union of their terms ascending,
+// padded with UINT32_MAX, then the membership words; the bit planes of the sets' sizes.
+struct TermMultiPlan {
+    uint32_t tables[2 * TERM_MULTI_MAX_UNION];
+    uint32_t n_union;
+    uint32_t nbits[5];
+};
+static void make_term_multi_plan(const TermReq* const* sets, uint32_t n_sets, TermMultiPlan* p) {
+    std::vector<uint32_t> u;
+    for (uint32_t s = 0; s < n_sets; ++s) u.insert(u.end(), sets[s]->t, sets[s]->t + sets[s]->n);
+    std::sort(u.begin(), u.end());
+    u.erase(std::unique(u.begin(), u.end()), u.end());
+    p->n_union = (uint32_t)u.size();
+    for (uint32_t i = 0; i < TERM_MULTI_MAX_UNION; ++i) { p->tables[i] = i < u.size() ? u[i] : UINT32_MAX; p->tables[TERM_MULTI_MAX_UNION + i] = 0u; }
+    for (uint32_t b = 0; b < 5; ++b) p->nbits[b] = 0u;
+    for (uint32_t s = 0; s < n_sets; ++s) {
+        for (uint32_t i = 0; i < sets[s]->n; ++i)
+            p->tables[TERM_MULTI_MAX_UNION + (size_t)(std::lower_bound(u.begin(), u.end(), sets[s]->t[i]) - u.begin())] |= 1u << s;
+        for (uint32_t b = 0; b < 5; ++b) p->nbits[b] |= ((sets[s]->n >> b) & 1u) << s;
+    }
 }
 
 // ---- the column -------------------------------------------------------------------
@@ -312,5 +372,64 @@ int wax_hip_term_mask_probe(const uint32_t* offsets, const uint32_t* values, uin
     if (err == hipSuccess) err = hipMemcpy(out_bitmap, d_bm, (size_t)n_words * sizeof(uint32_t), hipMemcpyDeviceToHost);
     (void)hipFree(d);
     HIP_TRY(err, WAX_HIP_ERR_INTERNAL, "term_mask_probe");
+    return WAX_HIP_OK;
+}
+
+int wax_hip_term_batch_stats(wax_hip_engine* e, wax_hip_term_batch_stats_t* out) {
+    if (!e || !out) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine/out is null");
+    if (e->sh) return sh_term_batch_stats(e, out);
+    out->calls = e->tb_calls.load(); out->queries = e->tb_queries.load(); out->sets = e->tb_sets.load();
+    out->mask_launches = e->tb_mask_launches.load(); out->looped = e->tb_looped.load(); out->host_decided = e->tb_host_decided.load();
+    return WAX_HIP_OK;
+}
+
+int wax_hip_term_mask_multi_probe(const uint32_t* offsets, const uint32_t* values, uint64_t n_rows, const uint32_t* required,
+                                  const uint64_t* set_begin, const uint32_t* set_len, uint32_t n_sets, uint32_t grid, uint32_t* out_bitmaps,
+                                  uint32_t* out_counts) {
+    if (!offsets || !required || !set_begin || !set_len || !out_bitmaps || !out_counts) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_sets == 0 || n_sets > TERM_MULTI_MAX_SETS) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "term_mask_multi_probe: 1 to 32 term sets");
+    std::vector<TermReq> sets(n_sets);
+    std::vector<const TermReq*> ptrs(n_sets);
+    for (uint32_t s = 0; s < n_sets; ++s) {
+        if (set_len[s] == 0) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "term_mask_multi_probe: set " + std::to_string(s) + " is empty");
+        if (!make_term_req(required + set_begin[s], set_len[s], &sets[s]))
+            return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "term_mask_multi_probe: set " + std::to_string(s) + " holds more than " +
+                                                          std::to_string(TERMS_MAX_REQUIRED) + " distinct terms");
+        ptrs[s] = &sets[s];
+    }
+    if (grid == 0 || grid > TERM_MASK_MAX_GRID) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "term_mask_multi_probe: 1 to 1024 workgroups");
+    if (n_rows == 0 || n_rows > 0xffffffffull) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "term_mask_multi_probe: 1 to 2^32 - 1 rows");
+    for (uint64_t r = 0; r < n_rows; ++r)
+        if (offsets[r] > offsets[r + 1]) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "term_mask_multi_probe: offsets must not decrease");
+    const uint64_t total = offsets[n_rows];
+    if (total >= 0x80000000ull) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "term_mask_multi_probe: fewer than 2^31 values");
+    if (total != 0 && !values) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "null argument");
+    TermMultiPlan plan;
+    make_term_multi_plan(ptrs.data(), n_sets, &plan);
+    const uint64_t n_words = (n_rows + 31) / 32, stride = term_multi_stride_words((uint32_t)n_rows);
+    const uint64_t val_words = ((total + 3ull) & ~3ull) + 4ull, off_words = (n_rows + 1 + 3ull) & ~3ull;   // every section starts 16-byte aligned
+    const uint64_t table_words = 2ull * TERM_MULTI_MAX_UNION, count_words = TERM_MULTI_MAX_SETS;
+    uint32_t* d = nullptr;
+    HIP_TRY(hipMalloc(&d, (size_t)(val_words + off_words + table_words + count_words + stride * n_sets) * sizeof(uint32_t)), WAX_HIP_ERR_INTERNAL,
+            "term_mask_multi_probe allocation");
+    uint32_t* d_val = d;
+    uint32_t* d_off = d_val + val_words;
+    uint32_t* d_tab = d_off + off_words;
+    uint32_t* d_cnt = d_tab + table_words;
+    uint32_t* d_bm = d_cnt + count_words;
+    TermMaskMultiArgs a{};
+    a.off = d_off; a.val = d_val; a.uni = d_tab; a.memb = d_tab + TERM_MULTI_MAX_UNION; a.bitmaps = d_bm; a.counts = d_cnt;
+    a.n_rows = (uint32_t)n_rows; a.n_union = plan.n_union; a.n_sets = n_sets; a.stride_words = (uint32_t)stride;
+    for (int b = 0; b < 5; ++b) a.nbits[b] = plan.nbits[b];
+    hipError_t err = hipMemcpy(d_off, offsets, (size_t)(n_rows + 1) * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (err == hipSuccess && total != 0) err = hipMemcpy(d_val, values, (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemcpy(d_tab, plan.tables, sizeof(plan.tables), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemset(d_cnt, 0, (size_t)count_words * sizeof(uint32_t));
+    if (err == hipSuccess) err = launch_term_mask_multi(a, grid, nullptr);
+    for (uint32_t s = 0; s < n_sets && err == hipSuccess; ++s)
+        err = hipMemcpy(out_bitmaps + (size_t)s * n_words, d_bm + (size_t)s * stride, (size_t)n_words * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (err == hipSuccess) err = hipMemcpy(out_counts, d_cnt, (size_t)n_sets * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    HIP_TRY(err, WAX_HIP_ERR_INTERNAL, "term_mask_multi_probe");
     return WAX_HIP_OK;
 }

@@ -463,7 +463,7 @@ void free_filter_work(FilterWork* f) {
     (void)hipFree(f->d_rows); (void)hipFree(f->d_ids); (void)hipFree(f->d_dist); (void)hipFree(f->d_allow); (void)hipFree(f->d_bitmap);
     (void)hipFree(f->d_block_sum); (void)hipFree(f->d_total); (void)hipFree(f->d_query); (void)hipFree(f->d_qnorm); (void)hipFree(f->d_hits);
     (void)hipFree(f->d_bq); (void)hipFree(f->d_meta); (void)hipFree(f->d_lrows); (void)hipFree(f->d_lcnt); (void)hipFree(f->d_lids);
-    (void)hipFree(f->d_part); (void)hipFree(f->d_bhits);
+    (void)hipFree(f->d_part); (void)hipFree(f->d_bhits); (void)hipFree(f->d_tplan); (void)hipFree(f->d_tbits);
     free_select_work(&f->sw);
     if (f->h_total) (void)hipHostFree(f->h_total);
     if (f->h_hits) (void)hipHostFree(f->h_hits);

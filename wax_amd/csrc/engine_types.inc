@@ -293,6 +293,11 @@ struct FilterWork {
     uint64_t part_cap = 0;
     wax_hip_hit* d_bhits = nullptr;  // [bhits_cap] merged hits, one row of k per fused query
     uint64_t bhits_cap = 0;
+    // wax_hip_search_batch_terms: the term pass in front of the entries' layout
+    uint32_t* d_tplan = nullptr;     // [tplan_cap] per launch: union terms | membership words (512 each), then one count per set
+    uint64_t tplan_cap = 0;
+    uint32_t* d_tbits = nullptr;     // [tbits_cap] one row bitmap per admitted term set
+    uint64_t tbits_cap = 0;
     // wax_hip_search_predicate (allocated by its first call on this workspace)
     uint32_t* d_pred_counts = nullptr;   // [kPredCounts] passing rows, scan chunks that hold one, mirror chunks that hold one (attr_mask_kernel)
     uint32_t* h_pred_counts = nullptr;   // pinned [kPredCounts]
@@ -669,6 +674,8 @@ struct wax_hip_engine {
     uint64_t term_stale_from = UINT64_MAX;
     // wax_hip_term_stats (a read-out, no tuning key)
     std::atomic<uint64_t> tm_searches{0}, tm_device_masks{0}, tm_host_staged{0}, tm_host_decided{0}, tm_rows_uploaded{0}, tm_values_uploaded{0};
+    // wax_hip_term_batch_stats (a read-out of its own)
+    std::atomic<uint64_t> tb_calls{0}, tb_queries{0}, tb_sets{0}, tb_mask_launches{0}, tb_looped{0}, tb_host_decided{0};
     std::atomic<int64_t> predicate_route{0};     // 0 = auto, 1 = always gather the passing rows, 2 = the masked scan wherever it is eligible
     // auto rule: the masked scan when at least this many rows per thousand pass. 500 = the random mask's crossover of the FIRST build
     // (between 1/8 and 1/2 passing, profiles/r13/c_routes_first_build.json). At 10M rows the committed f32 scan crosses the gather
@@ -804,7 +811,9 @@ int sh_batch_device(wax_hip_engine* e, const float* d_queries, uint32_t nq, uint
 int sh_batch_collect_device(wax_hip_engine* e, uint64_t ticket, uint32_t* out_fallbacks);
 int sh_search_batch_predicate(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k, const uint64_t* allow,
                               uint64_t n_allow_ids, const uint64_t* allow_begin, const uint64_t* allow_len, const float* min_scores,
-                              const wax_hip_row_predicate* preds, uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts);
+                              const wax_hip_row_predicate* preds, uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts,
+                              const uint32_t* required_terms = nullptr, uint64_t n_required_terms = 0, const uint64_t* term_begin = nullptr,
+                              const uint32_t* term_len = nullptr);
 int sh_search_filtered(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, int has_allow, const uint64_t* allow,
                        uint64_t n_allow, int has_min, float min_score, uint64_t* out_ids, float* out_scores, uint32_t capacity,
                        uint32_t* out_count);
@@ -834,6 +843,7 @@ int sh_search_terms(wax_hip_engine* e, const float* query, uint32_t dims, int32_
                     int has_min, float min_score, const wax_hip_row_predicate* pred, const uint32_t* required, uint32_t n_required,
                     uint64_t* out_ids, float* out_scores, uint32_t capacity, uint32_t* out_count);
 int sh_term_stats(wax_hip_engine* e, wax_hip_term_stats_t* out);
+int sh_term_batch_stats(wax_hip_engine* e, wax_hip_term_batch_stats_t* out);
 int sh_serialize(wax_hip_engine* e, uint8_t** out_bytes, size_t* out_len);
 int sh_deserialize(wax_hip_engine* e, const uint8_t* data, size_t len);
 void sh_destroy(wax_hip_engine* e);

@@ -63,6 +63,7 @@ __global__ __launch_bounds__(256) void idhash_probe_kernel(const uint64_t* __res
 // One workgroup per list: probe every id into LDS (kNoRow for an id the store lacks), bitonic sort of the next power of two,
 // then keep the first of every run of equal rows (duplicate ids) and drop kNoRow; a workgroup-wide scan places the survivors.
 // PRED (wax_hip_search_batch_predicate): list blockIdx.x carries the row predicate preds[blockIdx.x]; a probed row that fails it
+// — or, where the entry has required terms (n_terms != 0), lacks one of them in its row of the CSR term column —
 // becomes kNoRow before the sort. PRED = false never reads `preds` and is the kernel of the lists without a predicate.
 constexpr int kSortThreads = 1024;
 template <bool PRED>
@@ -84,6 +85,17 @@ __global__ __launch_bounds__(kSortThreads) void rowlist_sort_kernel(const uint64
                 const int64_t ts = p.ts != nullptr ? p.ts[row] : 0;
                 const uint32_t fl = p.flags != nullptr ? p.flags[row] : 0u;
                 if (!attr_row_passes(p.has_after, p.after, p.has_before, p.before, p.deny_flags, ts, fl)) row = kNoRow;
+            }
+            if (row != kNoRow && p.n_terms != 0u) {
+                // the required terms of the list's queries (wax_hip_search_batch_terms): term_mask_kernel's test on this one row
+                const uint32_t end = p.term_off[row + 1u];
+                uint32_t bits = 0u;
+                for (uint32_t v = p.term_off[row]; v < end; ++v) {
+                    const uint32_t x = p.term_val[v];
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) bits |= x == p.terms[j] ? (1u << j) : 0u;
+                }
+                if (bits != 0xffffu) row = kNoRow;
             }
             srt[i] = row;
         }

@@ -424,16 +424,22 @@ struct BatchFilters {
 // the attribute mask; an entry without a list comes straight from the attribute columns, predicate.hip), multiscan.hip's gather form
 // scores every row list against the queries that share it, the span merge attaches frame ids: one download, one synchronisation, no
 // host round trip for a count. What that pass does not serve takes search_rows_locked per query.
+// T (wax_hip_search_batch_terms; null: no query has a term set and nothing differs): a term set joins the entry's key. An entry
+// without a list gets its set's row bitmap and passing count from term_mask_multi_kernel AHEAD of the layout — the one extra
+// synchronisation — and its upper bound is that count; a short list's sort drops rows that lack a term; a long list with terms loops.
 static int batch_filtered_locked(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int kpad, const std::vector<uint32_t>& fq,
                                  const BatchFilters& F, uint64_t n_allow_ids, const float* min_scores, uint64_t* out_ids, float* out_scores,
-                                 uint32_t out_stride, uint32_t* out_counts) {
+                                 uint32_t out_stride, uint32_t* out_counts, const BatchTerms* T = nullptr) {
     const uint64_t count = e->count;
     const int k = kpad < (int)out_stride ? kpad : (int)out_stride;   // the best out_stride of kpad: the same rows hits_to_results keeps
     const uint32_t group = (k >= 1 && k <= FUSED_MAX_K) ? scan_multi_group(dims, k) : 0u;
+    auto term_req = [&](uint32_t q) -> const TermReq* { return T ? T->req(q) : nullptr; };   // (T: wax_hip_search_batch_terms, some query has a set)
     auto one = [&](uint32_t q) -> int {   // query q through the single-query body (which counts its own predicate search), then its cut
         uint32_t n = 0;
+        const TermReq* req = term_req(q);
+        if (req) { e->tm_searches++; e->tb_looped++; }   // wax_hip_search_terms' body: a looped term query counts itself as one of those
         const int rc = search_rows_locked(e, queries + (size_t)q * dims, dims, kpad, F.listed(q) ? 1 : 0, F.ids(q), F.length(q), F.pred(q),
-                                          out_ids + (size_t)q * out_stride, out_scores + (size_t)q * out_stride, out_stride, &n);
+                                          out_ids + (size_t)q * out_stride, out_scores + (size_t)q * out_stride, out_stride, &n, req);
         if (rc != WAX_HIP_OK) return rc;
         if (min_scores) apply_min_score(min_scores[q], out_ids + (size_t)q * out_stride, out_scores + (size_t)q * out_stride, &n);
         out_counts[q] = n;
@@ -445,37 +451,132 @@ static int batch_filtered_locked(wax_hip_engine* e, const float* queries, uint32
         return WAX_HIP_OK;
     }
     if (e->row_base + count > 0x100000000ull) return fail(WAX_HIP_ERR_CAPACITY, "row_base + count exceeds UInt32 row indices");
-    // distinct entries: queries with the same (begin, len | no list, predicate) share one
-    struct Entry { uint64_t begin, len, ub; uint32_t row_off; const wax_hip_row_predicate* pred; bool admitted; std::vector<uint32_t> qs; };
+    // distinct entries: queries with the same (begin, len | no list, predicate, term set) share one. A term query without a predicate is
+    // one whose predicate passes every row (DESIGN 4.11), so every term entry is an entry with a predicate below.
+    static const wax_hip_row_predicate pass_all{};
+    struct Entry {
+        uint64_t begin, len, ub; uint32_t row_off; const wax_hip_row_predicate* pred; bool admitted; std::vector<uint32_t> qs;
+        int32_t tset;    // its term set (T->sets), -1: none
+        int32_t tslot;   // the bitmap of that set in f.d_tbits (entries without a list), -1: none
+    };
     std::vector<Entry> lists;
+    std::vector<uint8_t> apart(T ? nq : 0, 0);                    // term queries this pass does not answer: decided here, or looped
+    uint64_t term_decided = 0;
     {
-        typedef std::tuple<uint64_t, uint64_t, int32_t, int64_t, int32_t, int64_t, uint32_t> EntryKey;
+        typedef std::tuple<uint64_t, uint64_t, int32_t, int64_t, int32_t, int64_t, uint32_t, int32_t> EntryKey;
         std::map<EntryKey, uint32_t> index;
         for (uint32_t q : fq) {
+            const int32_t ts = T ? T->of[q] : -1;
+            if (ts >= 0 && e->term_off.empty()) { apart[q] = 1; ++term_decided; continue; }   // no frame has metadata: none matches (UnifiedSearch.swift:1219)
             const bool listed = F.listed(q);
             const uint64_t len = count == 0 ? 0 : (listed ? F.length(q) : WAX_HIP_NO_ALLOW_LIST);
             if (len == 0) continue;                               // nothing allowed: count 0
             const wax_hip_row_predicate* p = F.pred(q);
+            if (ts >= 0 && !p) p = &pass_all;
             const uint64_t begin = listed ? F.begin[q] : 0;
-            const EntryKey key = p ? EntryKey(begin, len, p->has_after, p->after, p->has_before, p->before, p->deny_flags) : EntryKey(begin, len, 0, 0, 0, 0, 0u);
+            const EntryKey key = p ? EntryKey(begin, len, p->has_after, p->after, p->has_before, p->before, p->deny_flags, ts) : EntryKey(begin, len, 0, 0, 0, 0, 0u, ts);
             auto it = index.emplace(key, (uint32_t)lists.size());
-            if (it.second) lists.push_back(Entry{begin, len, listed && len < count ? len : count, 0, p, true, {}});
+            if (it.second) lists.push_back(Entry{begin, len, listed && len < count ? len : count, 0, p, true, {}, ts, -1});
             lists[it.first->second].qs.push_back(q);
         }
     }
-    // the row-slot budget of the entries with a predicate, in order of their first query (an entry without a list costs `count` slots
-    // whatever passes); what does not fit takes the single-query body below
+    e->tb_host_decided += term_decided;
     std::vector<uint32_t> looped;
-    uint64_t pred_entries = 0;
+    // Term entries (wax_hip_search_batch_terms). One with a list too long for the LDS sort takes the single-query body. One without a list
+    // gets its set's row bitmap from term_mask_multi_kernel: sets are admitted in order of their first query while there are at most
+    // kTermBatchMaxSets of them and their bitmaps fit kTermBatchMaxBytes (a memory cap); the entries of the rest are looped.
+    constexpr uint64_t kTermBatchMaxSets = 256, kTermBatchMaxBytes = 256ull << 20;
+    std::vector<int32_t> slot_set;                                // bitmap slot -> term set
+    const uint64_t tstride = term_multi_stride_words((uint32_t)count);
+    if (T) {
+        std::map<int32_t, int32_t> slot_of;
+        for (Entry& L : lists) {
+            if (L.tset < 0) continue;
+            bool admit = true;
+            if (L.len != WAX_HIP_NO_ALLOW_LIST) {
+                admit = L.len <= ROWLIST_SORT_MAX;
+            } else {
+                auto it = slot_of.find(L.tset);
+                if (it == slot_of.end()) {
+                    admit = slot_set.size() < kTermBatchMaxSets && (slot_set.size() + 1) * tstride * sizeof(uint32_t) <= kTermBatchMaxBytes;
+                    if (admit) { it = slot_of.emplace(L.tset, (int32_t)slot_set.size()).first; slot_set.push_back(L.tset); }
+                }
+                if (admit) L.tslot = it->second;
+            }
+            if (!admit) { L.admitted = false; looped.insert(looped.end(), L.qs.begin(), L.qs.end()); }
+        }
+    }
+    // The term pass: the CSR column once per 32 admitted sets -> one bitmap and one passing count per set; the counts come to the host
+    // (the one extra synchronisation, only in calls with such entries) and become the entries' upper bounds. A count of 0 ends an entry.
+    // The workspace stays with the call from here on, so what is looped waits until the pass has given it back (see below).
+    std::unique_ptr<FilterLease> lease;
+    const uint32_t* d_term_off = nullptr;
+    const uint32_t* d_term_val = nullptr;
+    if (!slot_set.empty()) {
+        lease.reset(new FilterLease(e));
+        if (lease->rc != WAX_HIP_OK) return lease->rc;
+        FilterWork& f = lease->work();
+        hipStream_t st = f.stream;
+        { const int trc = ensure_terms(e, st, &d_term_off, &d_term_val); if (trc != WAX_HIP_OK) return trc; }
+        const uint32_t S = (uint32_t)slot_set.size(), n_launch = (S + TERM_MULTI_MAX_SETS - 1) / TERM_MULTI_MAX_SETS;
+        const uint64_t table_words = 2ull * TERM_MULTI_MAX_UNION, cnt0 = (uint64_t)n_launch * table_words;
+        int grc = grow_dev(&f.d_tplan, &f.tplan_cap, cnt0 + S, sizeof(uint32_t), "Failed to allocate term-set tables");
+        if (grc == WAX_HIP_OK) grc = grow_dev(&f.d_tbits, &f.tbits_cap, (uint64_t)S * tstride, sizeof(uint32_t), "Failed to allocate term-set bitmaps");
+        if (grc != WAX_HIP_OK) return grc;
+        std::vector<uint32_t> tp((size_t)(cnt0 + S), 0u);         // per launch its tables, then the counts (zero)
+        std::vector<TermMaskMultiArgs> targs(n_launch);
+        for (uint32_t l = 0; l < n_launch; ++l) {
+            const uint32_t s0 = l * TERM_MULTI_MAX_SETS, sn = std::min<uint32_t>(TERM_MULTI_MAX_SETS, S - s0);
+            const TermReq* sets[TERM_MULTI_MAX_SETS];
+            for (uint32_t s = 0; s < sn; ++s) sets[s] = &T->sets[(size_t)slot_set[s0 + s]];
+            TermMultiPlan plan;
+            make_term_multi_plan(sets, sn, &plan);
+            std::memcpy(tp.data() + (size_t)l * table_words, plan.tables, sizeof(plan.tables));
+            TermMaskMultiArgs& a = targs[l];
+            a = TermMaskMultiArgs{};
+            a.off = d_term_off; a.val = d_term_val; a.uni = f.d_tplan + (size_t)l * table_words; a.memb = a.uni + TERM_MULTI_MAX_UNION;
+            a.bitmaps = f.d_tbits + (size_t)s0 * tstride; a.counts = f.d_tplan + cnt0 + s0;
+            a.n_rows = (uint32_t)count; a.n_union = plan.n_union; a.n_sets = sn; a.stride_words = (uint32_t)tstride;
+            for (int b = 0; b < 5; ++b) a.nbits[b] = plan.nbits[b];
+        }
+        HIP_TRY(hipMemcpyAsync(f.d_tplan, tp.data(), tp.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st), WAX_HIP_ERR_INTERNAL, "term-set table upload");
+        for (uint32_t l = 0; l < n_launch; ++l) HIP_TRY(launch_term_mask_multi(targs[l], 0u, st), WAX_HIP_ERR_INTERNAL, "term mask launch");
+        std::vector<uint32_t> tcnt(S);
+        HIP_TRY(hipMemcpyAsync(tcnt.data(), f.d_tplan + cnt0, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, st), WAX_HIP_ERR_INTERNAL, "term count download");
+        HIP_TRY(hipStreamSynchronize(st), WAX_HIP_ERR_INTERNAL, "term mask failed on device");
+        e->tb_mask_launches += n_launch;
+        for (Entry& L : lists)
+            if (L.tslot >= 0) { L.ub = tcnt[(size_t)L.tslot]; if (L.ub == 0) L.admitted = false; }
+    }
+    // the row-slot budget of the entries with a predicate, in order of their first query (an entry without a list costs `count` slots
+    // whatever passes — or, with a term set, the rows that hold the set); what does not fit takes the single-query body below
+    uint64_t pred_entries = 0, attr_entries = 0;
+    bool short_terms = false;
     {
         const uint64_t budget = (uint64_t)e->predicate_batch_rows.load();
         uint64_t used = 0;
         for (Entry& L : lists) {
-            if (!L.pred) continue;
-            if (L.ub <= budget - used) { used += L.ub; ++pred_entries; continue; }
+            if (!L.pred || !L.admitted) continue;
+            if (L.ub <= budget - used) {
+                used += L.ub; ++pred_entries;
+                attr_entries += predicate_is_empty(L.pred) ? 0u : 1u;
+                short_terms = short_terms || (L.tset >= 0 && L.tslot < 0);
+                continue;
+            }
             L.admitted = false;
             looped.insert(looped.end(), L.qs.begin(), L.qs.end());
         }
+    }
+    for (uint32_t q : looped) if (T) apart[q] = 1;
+    if (T) {
+        std::vector<uint8_t> sent(T->sets.size(), 0);
+        uint64_t n_sent = 0, n_answered = 0;
+        for (int32_t s : slot_set) if (!sent[(size_t)s]) { sent[(size_t)s] = 1; ++n_sent; }
+        for (const Entry& L : lists)
+            if (L.admitted && L.tset >= 0 && !sent[(size_t)L.tset]) { sent[(size_t)L.tset] = 1; ++n_sent; }
+        for (uint32_t q : fq) n_answered += (T->of[q] >= 0 && !apart[q]) ? 1u : 0u;
+        e->tb_sets += n_sent;
+        e->tb_queries += n_answered;
     }
     uint64_t rows_total = 0, long_max = 0, attr_items = 0;
     uint32_t short_max = 0, short_max_pred = 0;
@@ -499,6 +600,7 @@ static int batch_filtered_locked(wax_hip_engine* e, const float* queries, uint32
             r.n_rows = (uint32_t)count; r.row_off = L.row_off; r.count_slot = li;
             r.n_items = (uint32_t)((count + ATTR_ROWS_ITEM - 1) / ATTR_ROWS_ITEM); r.item0 = (uint32_t)attr_items; r.block0 = long_blocks + (uint32_t)attr_items;
             pred_fields(*L.pred, r);
+            if (L.tslot >= 0) r.bitmap = lease->work().d_tbits + (size_t)L.tslot * tstride;   // its set's rows: at most ub of them pass
             for (uint32_t i = 0; i < r.n_items; ++i) item_rec.push_back((uint32_t)records.size());
             attr_items += r.n_items;
             if (attr_items >= 0x80000000ull) return fail(WAX_HIP_ERR_CAPACITY, "too many work items in one batch");
@@ -511,6 +613,11 @@ static int batch_filtered_locked(wax_hip_engine* e, const float* queries, uint32
         } else if (L.pred) {
             RowListPred sp{};
             pred_fields(*L.pred, sp);
+            if (L.tset >= 0) {   // the sort drops a probed row that lacks a required term (the column's pointers follow below)
+                const TermReq& req = T->sets[(size_t)L.tset];
+                sp.n_terms = req.n;
+                for (int i = 0; i < TERMS_MAX_REQUIRED; ++i) sp.terms[i] = req.t[(uint32_t)i < req.n ? i : 0];
+            }
             sort_preds.push_back(sp);
             descs_pred.push_back(RowListDesc{L.begin, (uint32_t)L.len, L.row_off, li, 0u});
             if (L.len > short_max_pred) short_max_pred = (uint32_t)L.len;
@@ -549,39 +656,53 @@ static int batch_filtered_locked(wax_hip_engine* e, const float* queries, uint32
     }
     for (uint32_t q : fq) out_counts[q] = 0;
     const uint32_t P = (uint32_t)slot_q.size();
-    const uint64_t passed = fq.size() - looped.size();
+    const uint64_t passed = fq.size() - looped.size() - term_decided;
     e->st_filter_batch_queries += passed;
     e->st_searches += passed;
-    if (F.eff) {
-        // the predicates this pass answers (one without a row to offer included); a looped query is counted by the single-query body
+    if (F.eff || T) {
+        // the predicates this pass answers (one without a row to offer included; a term query counts as one, DESIGN 4.11); a looped query
+        // is counted by the single-query body
         std::vector<uint8_t> is_looped(nq, 0);
         for (uint32_t q : looped) is_looped[q] = 1;
         uint64_t n = 0;
-        for (uint32_t q : fq) n += (F.pred(q) != nullptr && !is_looped[q]) ? 1u : 0u;
+        for (uint32_t q : fq) n += ((F.pred(q) != nullptr || (term_req(q) != nullptr && !apart[q])) && !is_looped[q]) ? 1u : 0u;
         e->st_predicate_searches += n;
         e->st_predicate_batch_queries += n;
         e->st_predicate_batch_classes += pred_entries;
     }
-    // Ahead of the pass and of its workspace: the single-query body leases a workspace of its own, and a call that held one while it
-    // waited for another could wait for a call doing the same.
-    for (uint32_t q : looped) { const int rc = one(q); if (rc != WAX_HIP_OK) return rc; }
-    e->st_filter_batch_fallbacks += looped.size();
-    if (P == 0) return WAX_HIP_OK;
-
-    FilterLease lease(e);
-    if (lease.rc != WAX_HIP_OK) return lease.rc;
-    FilterWork& f = lease.work();
+    // The looped queries go ahead of the pass and of its workspace: the single-query body leases a workspace of its own, and a call that
+    // held one while it waited for another could wait for a call doing the same. A call whose term pass already holds the workspace
+    // loops them behind the pass instead, once the workspace is given back.
+    const bool loop_first = lease == nullptr;
+    auto run_looped = [&]() -> int {
+        for (uint32_t q : looped) { const int rc = one(q); if (rc != WAX_HIP_OK) return rc; }
+        e->st_filter_batch_fallbacks += looped.size();
+        return WAX_HIP_OK;
+    };
+    if (loop_first) { const int lrc = run_looped(); if (lrc != WAX_HIP_OK) return lrc; }
+    auto pass = [&]() -> int {
+    if (!lease) lease.reset(new FilterLease(e));
+    if (lease->rc != WAX_HIP_OK) return lease->rc;
+    FilterWork& f = lease->work();
     hipStream_t st = f.stream;
     if (any_listed) { const int hrc = ensure_idhash(e, st); if (hrc != WAX_HIP_OK) return hrc; }
     const int64_t* d_ts = nullptr;
     const uint32_t* d_fl = nullptr;
-    if (pred_entries != 0) {
-        // the attribute columns, once, on this stream under the lock held (null: a store without attributes reads (0, 0) in every row)
+    if (attr_entries != 0) {
+        // the attribute columns, once, on this stream under the lock held (null: a store without attributes reads (0, 0) in every row);
+        // an entry whose predicate passes every row (a term query without one) does not read them
         { const int arc = ensure_attrs(e, st, &d_ts, &d_fl); if (arc != WAX_HIP_OK) return arc; }
-        for (AttrRowsRecord& r : records) { r.ts = d_ts; r.flags = d_fl; }
-        for (RowListPred& sp : sort_preds) { sp.ts = d_ts; sp.flags = d_fl; }
+        for (AttrRowsRecord& r : records)
+            if (r.has_after != 0 || r.has_before != 0 || r.deny_flags != 0u) { r.ts = d_ts; r.flags = d_fl; }
+        for (RowListPred& sp : sort_preds)
+            if (sp.has_after != 0 || sp.has_before != 0 || sp.deny_flags != 0u) { sp.ts = d_ts; sp.flags = d_fl; }
         if (long_max > 0 && !f.d_pred_counts)
             HIP_TRY(hipMalloc(&f.d_pred_counts, kPredCounts * sizeof(uint32_t)), WAX_HIP_ERR_ALLOC, "Failed to allocate predicate counters");
+    }
+    if (short_terms) {
+        // the term column for the sorted lists' term test (ensure_terms is the only uploader; the term pass above has called it already)
+        if (!d_term_off) { const int trc = ensure_terms(e, st, &d_term_off, &d_term_val); if (trc != WAX_HIP_OK) return trc; }
+        for (RowListPred& sp : sort_preds) { sp.term_off = d_term_off; sp.term_val = d_term_val; }
     }
     // one blob: descs | descs with a predicate | their predicates | attribute records | their work table | groups | item_group | slot_q |
     // slot_norm | spans (16-byte aligned sections)
@@ -684,22 +805,38 @@ static int batch_filtered_locked(wax_hip_engine* e, const float* queries, uint32
     e->st_rows += rows_read;
     e->st_bytes += rows_read * (uint64_t)dims * 4ull;
     return WAX_HIP_OK;
+    };
+    const int prc = P == 0 ? WAX_HIP_OK : pass();
+    lease.reset();                                             // (waits for what is still on the workspace's stream)
+    if (prc != WAX_HIP_OK) return prc;
+    return loop_first ? WAX_HIP_OK : run_looped();
 }
 
-int wax_hip_search_batch_predicate(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
+// wax_hip_search_batch_predicate and wax_hip_search_batch_terms: one body. term_begin / term_len null: no query has a term set, and
+// nothing below differs from the call as it was before the term arguments existed.
+static int search_batch_rows_entry(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
                                    const uint64_t* allow_frame_ids, uint64_t n_allow_ids, const uint64_t* allow_begin,
                                    const uint64_t* allow_len, const float* min_scores, const wax_hip_row_predicate* preds,
-                                   uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts) {
+                                   const uint32_t* required_terms, uint64_t n_required_terms, const uint64_t* term_begin,
+                                   const uint32_t* term_len, uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts) {
     if (!e) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine is null");
     if (nq == 0) return WAX_HIP_OK;
     if (!queries || !out_counts) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "null input");
     if ((!out_ids || !out_scores) && out_stride) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "output arrays are null");
     { const int crc = check_batch_allow(nq, allow_frame_ids, n_allow_ids, allow_begin, allow_len); if (crc != WAX_HIP_OK) return crc; }
+    // every refusal precedes the first write to the outputs: the dimension check (the call's own, the handle's and the shards' alike) too
+    if ((term_begin || term_len) && dims != e->dims) return fail(WAX_HIP_ERR_DIM_MISMATCH, dim_mismatch_msg(e->dims, dims));
+    BatchTerms terms;
+    bool any_terms = false;
+    { const int trc = make_batch_terms(nq, required_terms, n_required_terms, term_begin, term_len, &terms, &any_terms); if (trc != WAX_HIP_OK) return trc; }
     for (uint32_t q = 0; q < nq; ++q) out_counts[q] = 0;
     if (e->sh) return sh_search_batch_predicate(e, queries, nq, dims, top_k, allow_frame_ids, n_allow_ids, allow_begin, allow_len, min_scores, preds,
-                                                out_ids, out_scores, out_stride, out_counts);
+                                                out_ids, out_scores, out_stride, out_counts, required_terms, n_required_terms,
+                                                any_terms ? term_begin : nullptr, any_terms ? term_len : nullptr);
     if (dims != e->dims) return fail(WAX_HIP_ERR_DIM_MISMATCH, dim_mismatch_msg(e->dims, dims));
     if (out_stride == 0) return WAX_HIP_OK;
+    const BatchTerms* T = any_terms ? &terms : nullptr;
+    if (T) e->tb_calls++;
     // The effective predicates: normalised, and — on a store that never had attributes, where every row reads (0, 0) — decided here,
     // once for all rows: the query loses its predicate, or its count stays 0 without device work (`dead`).
     std::vector<wax_hip_row_predicate> eff;
@@ -724,7 +861,7 @@ int wax_hip_search_batch_predicate(wax_hip_engine* e, const float* queries, uint
     std::vector<uint32_t> plain, fq;
     for (uint32_t q = 0; q < nq; ++q) {
         if (any_pred && dead[q]) continue;
-        (F.listed(q) || F.pred(q) ? fq : plain).push_back(q);
+        (F.listed(q) || F.pred(q) || (T && T->of[q] >= 0) ? fq : plain).push_back(q);
     }
     if (!plain.empty()) {
         // queries with neither list nor predicate: one sub-batch of the unfiltered batched search (its own lock acquisition), then the cut
@@ -753,7 +890,24 @@ int wax_hip_search_batch_predicate(wax_hip_engine* e, const float* queries, uint
     DeviceGuard g(e->device);
     ReadGuard rd(e);
     { const int frc = flush_pending(e); if (frc != WAX_HIP_OK) return frc; }
-    return batch_filtered_locked(e, queries, nq, dims, clamp_topk(top_k), fq, F, n_allow_ids, min_scores, out_ids, out_scores, out_stride, out_counts);
+    return batch_filtered_locked(e, queries, nq, dims, clamp_topk(top_k), fq, F, n_allow_ids, min_scores, out_ids, out_scores, out_stride, out_counts, T);
+}
+
+int wax_hip_search_batch_predicate(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
+                                   const uint64_t* allow_frame_ids, uint64_t n_allow_ids, const uint64_t* allow_begin,
+                                   const uint64_t* allow_len, const float* min_scores, const wax_hip_row_predicate* preds,
+                                   uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts) {
+    return search_batch_rows_entry(e, queries, nq, dims, top_k, allow_frame_ids, n_allow_ids, allow_begin, allow_len, min_scores, preds, nullptr, 0,
+                                   nullptr, nullptr, out_ids, out_scores, out_stride, out_counts);
+}
+
+int wax_hip_search_batch_terms(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
+                               const uint64_t* allow_frame_ids, uint64_t n_allow_ids, const uint64_t* allow_begin,
+                               const uint64_t* allow_len, const float* min_scores, const wax_hip_row_predicate* preds,
+                               const uint32_t* required_terms, uint64_t n_required_terms, const uint64_t* term_begin,
+                               const uint32_t* term_len, uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts) {
+    return search_batch_rows_entry(e, queries, nq, dims, top_k, allow_frame_ids, n_allow_ids, allow_begin, allow_len, min_scores, preds, required_terms,
+                                   n_required_terms, term_begin, term_len, out_ids, out_scores, out_stride, out_counts);
 }
 
 int wax_hip_search_batch_filtered(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,

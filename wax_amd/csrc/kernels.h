@@ -611,7 +611,10 @@ struct RowListPred {
     int32_t has_after, has_before;
     int64_t after, before;
     uint32_t deny_flags;
-    uint32_t pad;
+    uint32_t n_terms;           // wax_hip_search_batch_terms: 0 = no required terms (term_off / term_val / terms are not read)
+    const uint32_t* term_off;   // the store's CSR term column (count + 1 offsets, the values)
+    const uint32_t* term_val;
+    uint32_t terms[16];         // = TERMS_MAX_REQUIRED; unused slots repeat terms[0]: a row passes when all sixteen are found
 };
 // d_preds null: lists without a predicate (the kernel of wax_hip_search_batch_filtered as it was); otherwise one entry per list.
 hipError_t launch_rowlist_sort(const uint64_t* d_allow, const RowListDesc* d_desc, const RowListPred* d_preds, uint32_t n_lists, uint32_t max_len,
@@ -670,6 +673,7 @@ struct AttrRowsRecord {
     uint32_t item0, n_items;    // its work items: [item0, item0 + ceil(n_rows / ATTR_ROWS_ITEM))
     uint32_t block0;            // its first slot of block_sum ([n_items] of them)
     uint32_t pad;
+    const uint32_t* bitmap;     // null, or one bit per row ANDed into the votes (a term set's bitmap; then at most its count rows are written)
 };
 hipError_t launch_attr_rows(const AttrRowsRecord* d_records, uint32_t n_records, const uint32_t* d_item_rec, uint32_t n_items, uint32_t* block_sum,
                             uint32_t* rows_out, uint32_t* counts, hipStream_t st);
@@ -782,6 +786,26 @@ struct TermMaskArgs {
 };
 // grid 0 = the product's own: one workgroup per 256 rows, at most WAX_TERM_MASK_GRID_CAP (terms.hip)
 hipError_t launch_term_mask(const TermMaskArgs& a, uint32_t grid, hipStream_t st);
+// term_mask_multi_kernel (wax_hip_search_batch_terms): ONE pass over off / val decides up to TERM_MULTI_MAX_SETS required-term sets per
+// row. uni[0 .. TERM_MULTI_MAX_UNION) holds the n_union distinct terms of all the sets, ascending, the rest padded with UINT32_MAX;
+// memb[u] bit s = "set s requires uni[u]" (0 in the padding); nbits[p] bit s = bit p of |set s| (1 .. TERMS_MAX_REQUIRED). Set s's bitmap
+// is bitmaps + s * stride_words: its first ceil(n_rows / 32) words are all written, bits of rows >= n_rows clear. counts[s] (zero before
+// the launch) receives the rows that pass set s.
+constexpr uint32_t TERM_MULTI_MAX_SETS = 32;
+constexpr uint32_t TERM_MULTI_MAX_UNION = TERM_MULTI_MAX_SETS * (uint32_t)TERMS_MAX_REQUIRED;   // 512
+struct TermMaskMultiArgs {
+    const uint32_t* off;        // [n_rows + 1] non-decreasing; a row's values are distinct
+    const uint32_t* val;
+    const uint32_t* uni;        // [TERM_MULTI_MAX_UNION]
+    const uint32_t* memb;       // [TERM_MULTI_MAX_UNION]
+    uint32_t* bitmaps;          // [n_sets][stride_words]
+    uint32_t* counts;           // [n_sets]
+    uint32_t n_rows, n_union, n_sets, stride_words;
+    uint32_t nbits[5];
+};
+inline uint32_t term_multi_stride_words(uint32_t n_rows) { return (uint32_t)((((uint64_t)n_rows + 31u) / 32u + 3u) & ~3ull); }   // whole 16-byte pieces
+// grid 0 = the product's own: one workgroup per 256 rows, at most WAX_TERM_MULTI_GRID_CAP (terms.hip), grid-strided beyond
+hipError_t launch_term_mask_multi(const TermMaskMultiArgs& a, uint32_t grid, hipStream_t st);
 
 // ---- rrf.hip: reciprocal-rank fusion of ranked id lists, one workgroup per query ----
 hipError_t launch_rrf_fuse(const wax_hip_rrf_lane* lanes, uint32_t n_lanes, uint32_t nq, int32_t k, uint64_t* out_ids,

@@ -111,13 +111,15 @@ constexpr int kAttrTiles = (int)(ATTR_ROWS_ITEM / 256u);
 static_assert(kAttrTiles * 4 == 64, "the emit kernel scans one (tile, wave) count per lane");
 
 // The wave's votes on its 64 rows of each of the item's 16 tiles: tile t of item i is rows i * 4096 + t * 256 .. + 255 of the record,
-// one row per lane, both columns read coalesced. Rows at or beyond n_rows vote false.
+// one row per lane, both columns read coalesced. Rows at or beyond n_rows vote false, and so do rows whose bit in r.bitmap is clear
+// (null: no bitmap, the form as it was).
 __device__ inline void attr_rows_votes(const AttrRowsRecord& r, uint32_t item, unsigned long long (&b)[kAttrTiles]) {
     const uint64_t row0 = (uint64_t)item * ATTR_ROWS_ITEM + threadIdx.x;
 #pragma unroll
     for (int t = 0; t < kAttrTiles; ++t) {
         const uint64_t row = row0 + (uint64_t)t * 256u;
         bool pass = row < (uint64_t)r.n_rows;
+        if (pass && r.bitmap != nullptr) pass = ((r.bitmap[row >> 5] >> (row & 31u)) & 1u) != 0u;   // a term set's rows: the columns are read for these only
         if (pass) {
             const int64_t ts = r.ts != nullptr ? r.ts[row] : 0;
             const uint32_t fl = r.flags != nullptr ? r.flags[row] : 0u;

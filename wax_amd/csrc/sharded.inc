@@ -1567,12 +1567,25 @@ int sh_term_stats(wax_hip_engine* e, wax_hip_term_stats_t* out) {
     return WAX_HIP_OK;
 }
 
+int sh_term_batch_stats(wax_hip_engine* e, wax_hip_term_batch_stats_t* out) {
+    *out = wax_hip_term_batch_stats_t{};
+    for (wax_hip_engine* sub : e->sh->subs) {
+        wax_hip_term_batch_stats_t one{};
+        const int rc = wax_hip_term_batch_stats(sub, &one);
+        if (rc != WAX_HIP_OK) return rc;
+        out->calls += one.calls; out->queries += one.queries; out->sets += one.sets; out->mask_launches += one.mask_launches;
+        out->looped += one.looped; out->host_decided += one.host_decided;
+    }
+    return WAX_HIP_OK;
+}
+
 // Batched form: every shard answers the whole batch on its own rows (its own batched filtered call, on the handle's workers, in
 // parallel); then each query is merged exactly as sh_search_filtered merges one: stable by score, shard order on ties, then the cut.
 // preds (null: none) go to every shard as they are: a row's attributes live with the shard that owns the row.
 int sh_search_batch_predicate(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k, const uint64_t* allow,
                               uint64_t n_allow_ids, const uint64_t* allow_begin, const uint64_t* allow_len, const float* min_scores,
-                              const wax_hip_row_predicate* preds, uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts) {
+                              const wax_hip_row_predicate* preds, uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts,
+                              const uint32_t* required_terms, uint64_t n_required_terms, const uint64_t* term_begin, const uint32_t* term_len) {
     ShardedState* s = e->sh;
     if (dims != e->dims) return fail(WAX_HIP_ERR_DIM_MISMATCH, dim_mismatch_msg(e->dims, dims));
     if (out_stride == 0) return WAX_HIP_OK;
@@ -1585,8 +1598,10 @@ int sh_search_batch_predicate(wax_hip_engine* e, const float* queries, uint32_t 
     std::vector<int> rcs(G, WAX_HIP_OK);
     std::vector<std::string> errs(G);
     auto one = [&](size_t g) {
-        rcs[g] = wax_hip_search_batch_predicate(s->subs[g], queries, nq, dims, top_k, allow, n_allow_ids, allow_begin, allow_len, nullptr, preds,
-                                                g_ids[g].data(), g_scores[g].data(), limit, g_m[g].data());
+        // (term_begin / term_len null: wax_hip_search_batch_predicate itself; a row's terms live with the shard that owns the row)
+        rcs[g] = wax_hip_search_batch_terms(s->subs[g], queries, nq, dims, top_k, allow, n_allow_ids, allow_begin, allow_len, nullptr, preds,
+                                            required_terms, n_required_terms, term_begin, term_len, g_ids[g].data(), g_scores[g].data(), limit,
+                                            g_m[g].data());
         if (rcs[g] != WAX_HIP_OK) errs[g] = g_last_error;   // thread-local: carry it to the caller
     };
     if (G == 1) one(0); else s->workers.run_all(one);

@@ -553,7 +553,8 @@ class HIPVectorEngine:
         sequence (None entries: no cut). `timeRange` and `denyFlags` are each one value for all queries or a list of nq with None
         entries allowed, by searchManyFiltered's rules: one (after | None, before | None) tuple is one value, a LIST is per query.
         Returns (ids[nq, kcap], scores, counts) like searchBatch; row q equals searchFiltered for that query. A call without
-        timeRange / denyFlags takes wax_hip_search_batch_filtered, as before those arguments existed."""
+        timeRange / denyFlags takes wax_hip_search_batch_filtered, as before those arguments existed. searchBatchTerms adds a
+        required-term filter per query."""
         qs = _as_f32(vectors)
         if qs.ndim != 2:
             raise EncodingError("searchBatchFiltered: vectors must be [nq, dims]")
@@ -587,6 +588,76 @@ class HIPVectorEngine:
             rc = self._lib.wax_hip_search_batch_predicate(*head, preds, *tail)
         raise_for_status(rc)
         return ids, scores, counts
+
+    def searchBatchTerms(self, vectors, topK: int, requiredTerms, frameIds=None, minScore=None, timeRange=None, denyFlags=0):  # noqa: N802,N803
+        """searchBatchFiltered with searchFiltered's `requiredTerms` PER QUERY (wax_hip_search_batch_terms): None, ONE filter for all
+        queries (an iterable of term ids, or TermDictionary.NO_MATCH), or a list / tuple of nq entries, each None, an iterable of ids
+        or NO_MATCH. A sequence that holds only ints is one filter. Row q equals searchFiltered(vectors[q], ..., requiredTerms=filter
+        q). A NO_MATCH query gets count 0 and its vector is never sent; None or an empty filter is no term filter. With
+        requiredTerms=None the call is searchBatchFiltered. The other arguments are searchBatchFiltered's."""
+        if requiredTerms is None:
+            return self.searchBatchFiltered(vectors, topK, frameIds=frameIds, minScore=minScore, timeRange=timeRange, denyFlags=denyFlags)
+        qs = _as_f32(vectors)
+        if qs.ndim != 2:
+            raise EncodingError("searchBatchTerms: vectors must be [nq, dims]")
+        nq, width = qs.shape
+        terms = _per_query_terms(requiredTerms, nq)
+        kcap = max(1, min(clampTopK(topK), max(self.count, 1)))
+        ids = np.zeros((nq, kcap), dtype=np.uint64)
+        scores = np.zeros((nq, kcap), dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        live = [q for q in range(nq) if terms[q] is not TermDictionary.NO_MATCH]
+        if not live:
+            return ids, scores, counts
+        n = len(live)
+
+        def pick(value, what, tuple_is_value=False):
+            per = _per_pair(value, nq, what, tuple_is_value=tuple_is_value, who="searchBatchTerms", per="query")
+            return [per[q] for q in live]
+        if frameIds is not None and len(frameIds) != nq:
+            raise EncodingError("searchBatchTerms: frameIds must hold one entry per query")
+        flat, begin, length = pack_allow_lists(None if frameIds is None else [frameIds[q] for q in live], n)
+        cuts = None
+        if minScore is not None:
+            if np.ndim(minScore) == 0:
+                cuts = np.full(n, float(minScore), dtype=np.float32)
+            else:
+                if len(minScore) != nq:
+                    raise EncodingError("searchBatchTerms: minScore must hold one entry per query")
+                cuts = np.array([np.nan if minScore[q] is None else float(minScore[q]) for q in live], dtype=np.float32)
+        ranges = pick(timeRange, "timeRange", tuple_is_value=True)
+        denies = pick(denyFlags, "denyFlags")
+        preds = None
+        if any(r is not None for r in ranges) or any(d for d in denies):
+            preds = _row_predicates(ranges, denies)
+        sets = [np.empty(0, dtype=np.uint32) if terms[q] is None else terms[q] for q in live]
+        tlen = np.array([t.size for t in sets], dtype=np.uint32)
+        tbegin = np.zeros(n, dtype=np.uint64)
+        np.cumsum(tlen[:-1], out=tbegin[1:])
+        tflat = np.ascontiguousarray(np.concatenate(sets), dtype=np.uint32)
+        sub = qs if n == nq else np.ascontiguousarray(qs[live])
+        s_ids = ids if n == nq else np.zeros((n, kcap), dtype=np.uint64)
+        s_scores = scores if n == nq else np.zeros((n, kcap), dtype=np.float32)
+        s_counts = counts if n == nq else np.zeros(n, dtype=np.uint32)
+        u32 = ctypes.POINTER(ctypes.c_uint32)
+        rc = self._lib.wax_hip_search_batch_terms(
+            self._h, _fp(sub), n, width, int(max(min(topK, 2**31 - 1), -2**31)),
+            None if flat.size == 0 else _u64p(flat), int(flat.size),
+            None if begin is None else _u64p(begin), None if length is None else _u64p(length),
+            None if cuts is None else _fp(cuts), preds,
+            tflat.ctypes.data_as(u32) if tflat.size else None, int(tflat.size), _u64p(tbegin), tlen.ctypes.data_as(u32),
+            _u64p(s_ids), _fp(s_scores), kcap, s_counts.ctypes.data_as(u32))
+        raise_for_status(rc)
+        if n != nq:
+            ids[live], scores[live], counts[live] = s_ids, s_scores, s_counts
+        return ids, scores, counts
+
+    def termBatchStats(self) -> dict:  # noqa: N802
+        """What searchBatchTerms did (wax_hip_term_batch_stats): calls, queries, sets, mask_launches, looped,
+        host_decided."""
+        st = _abi.TermBatchStats()
+        raise_for_status(self._lib.wax_hip_term_batch_stats(self._h, ctypes.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in _abi.TermBatchStats._fields_}
 
     def searchBatchHits(self, vectors, topK: int):  # noqa: N802,N803
         """Raw ranked candidates: int64[nq, kcap, 2] of (key, frame_id bits), ascending key, KEY_PAD padded."""
@@ -849,6 +920,52 @@ def termMaskProbe(offsets, values, required, bitmapIn=None, grid: int = 1) -> np
                                                         req.ctypes.data_as(u32) if req.size else None, int(req.size),
                                                         None if bm is None else bm.ctypes.data_as(u32), int(grid), out.ctypes.data_as(u32)))
     return out
+
+
+def termMaskMultiProbe(offsets, values, sets, grid: int = 1):  # noqa: N802,N803
+    """wax_hip_term_mask_multi_probe: term_mask_multi_kernel on a made-up CSR column — offsets [rows + 1], values [offsets[-1]] (distinct
+    within a row), `sets` 1 .. 32 iterables of 1 .. 16 term ids, exactly `grid` workgroups. Returns (bitmaps uint32 [len(sets), words],
+    counts uint32 [len(sets)])."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+    val = np.ascontiguousarray(values, dtype=np.uint32).reshape(-1)
+    reqs = [np.asarray(list(t) if not isinstance(t, np.ndarray) else t, dtype=np.uint32).reshape(-1) for t in sets]
+    rows = int(off.size) - 1
+    if rows < 0 or val.size != int(off[-1]):
+        raise EncodingError("termMaskMultiProbe: offsets of rows + 1 entries, values of offsets[-1] entries")
+    n = len(reqs)
+    lens = np.array([t.size for t in reqs], dtype=np.uint32)
+    begin = np.zeros(max(n, 1), dtype=np.uint64)
+    if n:
+        np.cumsum(lens[:-1], out=begin[1:n])
+    flat = np.ascontiguousarray(np.concatenate(reqs) if n else np.empty(0), dtype=np.uint32)
+    words = (max(rows, 0) + 31) // 32
+    bitmaps = np.zeros((n, words), dtype=np.uint32)
+    counts = np.zeros(max(n, 1), dtype=np.uint32)
+    u32 = ctypes.POINTER(ctypes.c_uint32)
+    raise_for_status(_abi.lib().wax_hip_term_mask_multi_probe(
+        off.ctypes.data_as(u32), val.ctypes.data_as(u32) if val.size else None, rows, flat.ctypes.data_as(u32) if flat.size else None,
+        _u64p(begin), lens.ctypes.data_as(u32) if n else None, n, int(grid), bitmaps.ctypes.data_as(u32) if bitmaps.size else None,
+        counts.ctypes.data_as(u32)))
+    return bitmaps, counts[:n]
+
+
+def _per_query_terms(requiredTerms, nq: int) -> list:  # noqa: N803
+    """searchBatchTerms' requiredTerms -> nq entries, each None (no term filter), a uint32 array or TermDictionary.NO_MATCH."""
+    def one(t):
+        if t is None or t is TermDictionary.NO_MATCH:
+            return t
+        a = np.ascontiguousarray(list(t) if not isinstance(t, np.ndarray) else t, dtype=np.uint32).reshape(-1)
+        return a if a.size else None
+    if requiredTerms is TermDictionary.NO_MATCH:
+        return [requiredTerms] * nq
+    if isinstance(requiredTerms, np.ndarray) and requiredTerms.ndim == 1:
+        return [one(requiredTerms)] * nq
+    seq = list(requiredTerms)
+    if all(isinstance(t, (int, np.integer)) for t in seq):          # ids only (or nothing): one filter for all queries
+        return [one(seq)] * nq
+    if len(seq) != nq:
+        raise EncodingError("searchBatchTerms: requiredTerms must be one filter or hold one entry per query")
+    return [one(t) for t in seq]
 
 
 class _NoMatch:
