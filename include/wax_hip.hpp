@@ -117,6 +117,33 @@ class VectorEngine {
                                          frameIds.size(), &applied));
         return applied;
     }
+    /// One frame's attribute columns as getAttributes reads them back: (0, 0, false) for a frame the engine does not hold.
+    struct Attributes {
+        int64_t timestamp;
+        uint32_t flags;
+        bool found;
+    };
+    std::vector<Attributes> getAttributes(const std::vector<uint64_t>& frameIds) {
+        std::vector<int64_t> ts(frameIds.size());
+        std::vector<uint32_t> flags(frameIds.size());
+        std::vector<uint8_t> found(frameIds.size());
+        if (!frameIds.empty()) check(wax_hip_get_attributes(h_, frameIds.data(), frameIds.size(), ts.data(), flags.data(), found.data()));
+        std::vector<Attributes> out(frameIds.size());
+        for (size_t i = 0; i < out.size(); ++i) out[i] = {ts[i], flags[i], found[i] != 0};
+        return out;
+    }
+    /// The timeline lane (wax_hip_timeline): the `limit` newest (or oldest) frames that pass `pred` (null = every frame), as
+    /// (frameId, timestamp), ties by ascending frame id. limit <= 0 gives an empty answer.
+    std::vector<std::pair<uint64_t, int64_t>> timeline(int limit, bool newestFirst, const wax_hip_row_predicate* pred) {
+        const uint32_t cap = limit > 0 ? (uint32_t)(limit < WAX_HIP_TIMELINE_MAX_LIMIT ? limit : WAX_HIP_TIMELINE_MAX_LIMIT) : 0u;
+        std::vector<uint64_t> ids(cap ? cap : 1);
+        std::vector<int64_t> ts(cap ? cap : 1);
+        uint32_t n = 0;
+        check(wax_hip_timeline(h_, limit, newestFirst ? 1 : 0, pred, ids.data(), ts.data(), cap, &n));
+        std::vector<std::pair<uint64_t, int64_t>> out(n);
+        for (uint32_t i = 0; i < n; ++i) out[i] = {ids[i], ts[i]};
+        return out;
+    }
     /// FrameMeta.parentId of the listed frames for searchGrouped (wax_hip_set_parents): WAX_HIP_NO_PARENT = the frame is its own root.
     uint64_t setParents(const std::vector<uint64_t>& frameIds, const std::vector<uint64_t>& parentIds) {
         uint64_t applied = 0;
@@ -124,6 +151,17 @@ class VectorEngine {
         if (!frameIds.empty()) check(wax_hip_set_parents(h_, frameIds.data(), parentIds.data(), frameIds.size(), &applied));
         return applied;
     }
+    /// The parents read back (wax_hip_get_parents): (parent, found) per frame; (WAX_HIP_NO_PARENT, false) for a frame the engine does not hold.
+    std::vector<std::pair<uint64_t, bool>> getParents(const std::vector<uint64_t>& frameIds) {
+        std::vector<uint64_t> parents(frameIds.size());
+        std::vector<uint8_t> found(frameIds.size());
+        if (!frameIds.empty()) check(wax_hip_get_parents(h_, frameIds.data(), frameIds.size(), parents.data(), found.data()));
+        std::vector<std::pair<uint64_t, bool>> out(frameIds.size());
+        for (size_t i = 0; i < out.size(); ++i) out[i] = {parents[i], found[i] != 0};
+        return out;
+    }
+    /// What the grouped searches did (wax_hip_group_stats).
+    wax_hip_group_stats_t groupStats() { wax_hip_group_stats_t st{}; check(wax_hip_group_stats(h_, &st)); return st; }
     /// One root of a grouped answer: its id, its score (its best member's) and its best members, best first.
     struct Group {
         uint64_t rootId;
@@ -256,6 +294,8 @@ class VectorEngine {
         check(wax_hip_add_batch(h_, frameIds.data(), rowsRowMajor.data(), frameIds.size(),
                                 (uint32_t)(rowsRowMajor.size() / frameIds.size())));
     }
+    /// Capacity for at least `rows` rows (wax_hip_reserve); columns and rows are kept.
+    void reserve(uint64_t rows) { check(wax_hip_reserve(h_, rows)); }
     void remove(uint64_t frameId) { check(wax_hip_remove(h_, frameId)); }
     /// remove() for many ids in one compaction pass; returns the rows removed (absent ids are ignored, repeated ones count once).
     uint64_t removeBatch(const std::vector<uint64_t>& frameIds) {
