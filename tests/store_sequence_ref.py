@@ -9,8 +9,8 @@ GPU test replays a Sequence on an engine and, after every step, holds every rout
 
 Model      ordered frame ids, rows, ts, flags with the reference's semantics as helpers.OracleEngine has them: upsert by id (first
            row that holds the id), order-preserving remove of that first row, attributes (0, 0) for new rows and after deserialize.
-Protocol   the host-side state machines of batch_host.inc / api_store.inc / codec.inc, restated rule by rule (each method names the
-           engine function it restates), so the deltas of "mirror_rows_converted", "idhash_rows_inserted", "mirror8_conversions" and
+Protocol   the host-side state machines of batch_host.inc / api_store.inc / codec.inc and of row_columns.h, restated rule by rule (each
+           method names the engine function it restates), so the deltas of "mirror_rows_converted", "idhash_rows_inserted", "mirror8_conversions" and
            "mirror8_rows_converted" over one step (its mutations, then every reader) are predicted, and so the states a step enters are
            tagged with the coverage class they belong to.
 Sequence   about 40 steps. A step is one to three mutations with no reader between them (the states the issue lists — an upsert of
@@ -100,7 +100,7 @@ FOREIGN_ROOT0 = 1 << 40                      # roots the store does not hold
 BASE_STEPS = 40                              # the steps that predate the columns; the TAIL steps follow them
 OVERLAY = "overlay"                          # fifth element of a setAttributes op the overlay inserted (the only store-op kind it inserts)
 COLUMN_COUNTERS = ("parent_rows_uploaded", "group_slots", "term_rows_uploaded", "term_values_uploaded")
-NEVER = 1 << 62                              # UINT64_MAX of *_stale_from
+NEVER = 1 << 62                              # UploadMark::kNone (row_columns.h)
 
 # sha256 over (name, store ops, predicted STEP_COUNTERS) of the first BASE_STEPS steps, taken on the commit before the columns joined
 BASE_DIGESTS = {
@@ -213,7 +213,7 @@ class Model:
         return len(self.ids) - 1, True
 
     def remove(self, fid):
-        """wax_hip_remove / attr_note_remove (and, in one pass, wax_hip_remove_batch): the entries leave with the row."""
+        """wax_hip_remove / RowColumns::remove_row (and, in one pass, wax_hip_remove_batch): the entries leave with the row."""
         i = self.find(fid)
         if i >= 0:
             for col in (self.ids, self.rows, self.ts, self.fl, self.parent, self.terms):
@@ -258,7 +258,7 @@ class Model:
     def replace(self, ids, rows):
         self.ids, self.rows = [int(i) for i in ids], [int(r) for r in rows]
         self.ts, self.fl = [0] * len(self.ids), [0] * len(self.ids)
-        # attr_note_replaced: MV2V has no field for any column
+        # RowColumns::clear: MV2V has no field for any column
         self.parent, self.terms = [NO_PARENT] * len(self.ids), [()] * len(self.ids)
 
     def has_repeated_ids(self):
@@ -329,17 +329,17 @@ class Protocol:
         self.h_valid, self.h_stale, self.h_rows, self.h_slots = False, False, 0, 0
         # 8-bit code mirror
         self.c_exists, self.c_cap, self.c_stale, self.c_valid, self.c_rows = False, 0, False, False, 0
-        # attribute columns: the host columns' length (attr_ts.size()) only
+        # attribute columns: the host columns' length (RowColumns::attr_rows()) only
         self.a_len = 0
-        # parent column (attr_parent.size()) and what ensure_groups derives: grp_rows, grp_stale_from, grp_cap, grp_root_cap, grp_slot.size(),
-        # grp_slot_of (root -> slot; its size is grp_slot_root.size())
+        # parent column (RowColumns::parents().rows()) and what ensure_groups derives: the group mark's two numbers, grp_cap, grp_root_cap,
+        # GroupSlots::rows(), GroupSlots' root -> slot map (its size is n_slots())
         self.p_len, self.g_rows, self.g_stale, self.g_cap, self.g_root_cap, self.g_slot_len, self.g_slot_of = 0, 0, NEVER, 0, 0, 0, {}
-        # term column: the sets' sizes by row under the host CSR (None: term_off is empty), term_stale_from, term_dev_rows, both capacities
+        # term column: the sets' sizes by row under the host CSR (None: the TermColumn is empty), the term mark's two numbers, both capacities
         self.t_len, self.t_stale, self.t_dev, self.t_off_cap, self.t_val_cap = None, NEVER, 0, 0, 0
         self.tags = set()
         self.moved = set()                                # the lanes ("attrs", "parents", "terms") whose host column a mutation moved or marked
 
-    # -- batch_host.inc: parent_note_replaced, term_note_replaced, attr_note_replaced
+    # -- row_columns.h: RowColumns::clear, and what remove_rows does to a column it leaves empty
     def _parents_replaced(self):
         self.p_len, self.g_rows, self.g_stale, self.g_slot_len, self.g_slot_of = 0, 0, NEVER, 0, {}
 
@@ -359,7 +359,7 @@ class Protocol:
         self._parents_replaced()
         self._terms_replaced()
 
-    # -- batch_host.inc: attr_note_remove (parent_note_remove, term_note_remove_rows) for one row; the column pass of wax_hip_remove_batch
+    # -- row_columns.h: RowColumns::remove_row (wax_hip_remove) and remove_rows (wax_hip_remove_batch)
     def _columns_remove(self, rem):
         """rem: the rows that leave, ascending and distinct."""
         if self.p_len:
@@ -374,7 +374,7 @@ class Protocol:
                 self._parents_replaced()
                 self.tags.add("parents_emptied")
             else:
-                self.g_stale = min(self.g_stale, rem[0])          # parent_note_moved: a row behind the column shifts its slot entry all the same
+                self.g_stale = min(self.g_stale, rem[0])          # remove_rows: a row behind the column shifts its slot entry all the same
         if self.t_len is not None:
             nt = len(self.t_len)
             if rem[0] < nt:
@@ -390,13 +390,13 @@ class Protocol:
                 self._terms_replaced()
                 self.tags.add("terms_emptied")
             else:
-                self.t_stale = min(self.t_stale, rem[0])          # term_note_moved
+                self.t_stale = min(self.t_stale, rem[0])          # remove_rows marks while the column exists
         below = sum(1 for r in rem if r < self.a_len)
         if below:
             self.moved.add("attrs")
         self.a_len -= below
 
-    # -- api_grouped.inc: wax_hip_set_parents
+    # -- api_grouped.inc: wax_hip_set_parents (RowColumns::set_parent)
     def set_parents(self, rows):
         """rows: the store rows the entries named, in call order."""
         if self.pend:
@@ -407,10 +407,10 @@ class Protocol:
             if self.p_len <= r:
                 self.tags.add("parents_set_behind_column" if self.p_len else "parents_first_set")
                 self.p_len = self.count                           # everything up to it was its own root
-        self.g_stale = min(self.g_stale, min(rows))               # parent_note_moved(lowest)
+        self.g_stale = min(self.g_stale, min(rows))               # set_parent marks every row it sets
         self.moved.add("parents")
 
-    # -- api_terms.inc: wax_hip_set_terms (finish_term_rows, commit_term_rows)
+    # -- api_terms.inc: wax_hip_set_terms (row_columns.h: finish_term_rows, TermColumn::commit, RowColumns::commit_terms)
     def set_terms(self, sizes):
         """sizes: {store row: size of its new set} (one entry per row: the last of a repeated id has won)."""
         if self.pend:
@@ -432,7 +432,7 @@ class Protocol:
             self.tags.add("terms_resize_rebuild")
         else:
             self.tags.add("terms_same_size_overwrite")            # values change, offsets do not
-        self.t_stale = min(self.t_stale, rows[0])                 # term_note_moved(rows.front())
+        self.t_stale = min(self.t_stale, rows[0])                 # commit_terms marks rows.front()
         self.moved.add("terms")
 
     # -- store_internal.inc: reserve_rows / resize_store
@@ -573,7 +573,7 @@ class Protocol:
         if windows > 1:
             self.tags.add("compact_several_windows")
 
-    # -- api_predicate.inc: wax_hip_set_attributes
+    # -- api_predicate.inc: wax_hip_set_attributes (RowColumns::set_attributes)
     def set_attributes(self, rows=()):
         """rows: the store rows the entries named."""
         if self.pend:
@@ -596,7 +596,7 @@ class Protocol:
         self.m_stale, self.m_dirty, self.m_rows = True, [], 0
         self.h_valid, self.h_stale, self.h_rows = False, True, 0
         self._c8_stale()
-        self._columns_replaced()                          # attr_note_replaced
+        self._columns_replaced()                          # RowColumns::clear
         self.pend = 0
         if n > self.capacity:
             self.capacity = n
@@ -652,7 +652,7 @@ class Protocol:
             self.c_exists, self.c_cap, self.c_stale, self.c_valid, self.c_rows = True, self.capacity, False, True, self.count
         return out
 
-    # -- the column readers: ensure_groups (every grouped search) and ensure_terms (every term search on a device bitmap). Both run at
+    # -- the column readers: ensure_groups (with GroupSlots::number of row_columns.h; every grouped search) and ensure_terms (every term search on a device bitmap). Both run at
     # -- least once per step on the store the step left; every later call of the step finds the columns current and uploads nothing.
     def read_columns(self, model):
         """The deltas of groupStats()["parent_rows_uploaded"], termStats()["term_rows_uploaded"] and ["term_values_uploaded"] over the

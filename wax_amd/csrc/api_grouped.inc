@@ -13,16 +13,13 @@ int wax_hip_set_parents(wax_hip_engine* e, const uint64_t* frame_ids, const uint
     if (e->sh) return sh_set_parents(e, frame_ids, parent_ids, n, out_applied);
     REFUSE_IF_HOLDING(e);
     WriteGuard w(e->lock);
-    uint64_t applied = 0, lowest = UINT64_MAX;
+    uint64_t applied = 0;
     for (uint64_t i = 0; i < n; ++i) {
         const int64_t r = e->idmap.find(frame_ids[i]);
         if (r < 0) continue;                                   // a frame without a vector has no row to describe
         ++applied;
-        if (e->attr_parent.size() <= (uint64_t)r) e->attr_parent.resize((size_t)e->count, WAX_HIP_NO_PARENT);   // everything up to it was its own root
-        e->attr_parent[(size_t)r] = parent_ids[i];             // in call order: the last entry of a repeated id wins
-        if ((uint64_t)r < lowest) lowest = (uint64_t)r;
+        e->cols.set_parent((uint64_t)r, e->count, parent_ids[i]);
     }
-    if (lowest != UINT64_MAX) parent_note_moved(e, lowest);
     if (out_applied) *out_applied = applied;
     return WAX_HIP_OK;
 }
@@ -33,10 +30,9 @@ int wax_hip_get_parents(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n
     if (!frame_ids) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "getParents: null input");
     if (e->sh) return sh_get_parents(e, frame_ids, n, out_parents, out_found);
     ReadGuard rd(e);
-    const uint64_t np = e->attr_parent.size();
     for (uint64_t i = 0; i < n; ++i) {
         const int64_t r = e->idmap.find(frame_ids[i]);
-        if (out_parents) out_parents[i] = (r >= 0 && (uint64_t)r < np) ? e->attr_parent[(size_t)r] : WAX_HIP_NO_PARENT;
+        if (out_parents) out_parents[i] = r >= 0 ? e->cols.parents().at((uint64_t)r) : WAX_HIP_NO_PARENT;
         if (out_found) out_found[i] = r >= 0 ? 1 : 0;
     }
     return WAX_HIP_OK;
@@ -49,30 +45,16 @@ int wax_hip_get_parents(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n
 // not part of the contract; that every row of one root shares a slot and no two roots do is.
 static int ensure_groups(wax_hip_engine* e, hipStream_t st, const uint32_t** d_slots, const uint64_t** d_root, uint32_t* n_slots) {
     std::unique_lock<std::mutex> g(e->grp_mu);
-    const uint64_t count = e->count, np = e->attr_parent.size();
-    if (np == 0) { *d_slots = nullptr; *d_root = e->d_ids; *n_slots = (uint32_t)count; return WAX_HIP_OK; }
-    uint64_t from = std::min(std::min(e->grp_rows, e->grp_stale_from), count);
-    if (from < count || e->grp_slot.size() != count) {
-        auto number_from = [&](uint64_t r0) {
-            e->grp_slot.resize((size_t)count);
-            for (uint64_t r = r0; r < count; ++r) {
-                const uint64_t p = r < np ? e->attr_parent[(size_t)r] : WAX_HIP_NO_PARENT;
-                const uint64_t root = p != WAX_HIP_NO_PARENT ? p : e->ids[(size_t)r];
-                auto it = e->grp_slot_of.find(root);
-                if (it == e->grp_slot_of.end()) {
-                    it = e->grp_slot_of.emplace(root, (uint32_t)e->grp_slot_root.size()).first;
-                    e->grp_slot_root.push_back(root);
-                }
-                e->grp_slot[(size_t)r] = it->second;
-            }
-        };
-        number_from(from);
-        if (e->grp_slot_root.size() > 2ull * count + 16ull) {      // removals left most slots without a row: number from scratch
-            e->grp_slot_of.clear(); e->grp_slot_root.clear(); e->grp_root_dev = 0;
-            from = 0;
-            number_from(0);
+    RowColumns& c = e->cols;
+    const uint64_t count = e->count;
+    if (c.parents().empty()) { *d_slots = nullptr; *d_root = e->d_ids; *n_slots = (uint32_t)count; return WAX_HIP_OK; }
+    if (!c.groups_current(count)) {
+        uint64_t from = c.number_groups(count, e->ids.data());
+        if (e->grp_root_epoch != c.slots().epoch()) {              // numbering started over since the last upload: every root is sent again
+            e->grp_root_epoch = c.slots().epoch();
+            e->grp_root_dev = 0;
         }
-        const uint64_t n_roots = e->grp_slot_root.size();
+        const uint64_t n_roots = c.slots().n_slots();
         if (e->grp_cap < count) {                                  // growth: the column is sent again whole
             const uint64_t cap = e->capacity > count ? e->capacity : count;
             (void)hipFree(e->d_grp_slot);
@@ -91,19 +73,18 @@ static int ensure_groups(wax_hip_engine* e, hipStream_t st, const uint32_t** d_s
         }
         // pageable sources: the runtime stages them before returning
         if (from < count)
-            HIP_TRY(hipMemcpyAsync(e->d_grp_slot + from, e->grp_slot.data() + from, (size_t)(count - from) * sizeof(uint32_t), hipMemcpyHostToDevice, st),
+            HIP_TRY(hipMemcpyAsync(e->d_grp_slot + from, c.slots().slots() + from, (size_t)(count - from) * sizeof(uint32_t), hipMemcpyHostToDevice, st),
                     WAX_HIP_ERR_INTERNAL, "group slot upload");
         if (e->grp_root_dev < n_roots)
-            HIP_TRY(hipMemcpyAsync(e->d_grp_root + e->grp_root_dev, e->grp_slot_root.data() + e->grp_root_dev,
+            HIP_TRY(hipMemcpyAsync(e->d_grp_root + e->grp_root_dev, c.slots().roots() + e->grp_root_dev,
                                    (size_t)(n_roots - e->grp_root_dev) * sizeof(uint64_t), hipMemcpyHostToDevice, st),
                     WAX_HIP_ERR_INTERNAL, "group root upload");
         HIP_TRY(hipStreamSynchronize(st), WAX_HIP_ERR_INTERNAL, "group slot upload failed on device");   // other workspaces' streams read the columns next
         e->grp_root_dev = n_roots;
         e->gs_parent_rows_uploaded += count - from;
     }
-    e->grp_rows = count;
-    e->grp_stale_from = UINT64_MAX;
-    *d_slots = e->d_grp_slot; *d_root = e->d_grp_root; *n_slots = (uint32_t)e->grp_slot_root.size();
+    c.group_mark().settle(count);
+    *d_slots = e->d_grp_slot; *d_root = e->d_grp_root; *n_slots = (uint32_t)c.slots().n_slots();
     return WAX_HIP_OK;
 }
 
@@ -142,7 +123,7 @@ static int grouped_raw(wax_hip_engine* e, const float* query, uint32_t dims, int
     if (e->count > 0xffffffffull) return fail(WAX_HIP_ERR_CAPACITY, "count exceeds UInt32 row indices");
     const wax_hip_row_predicate np = normalised_predicate(pred);
     bool masked = !predicate_is_empty(&np);
-    if (masked && e->attr_ts.empty()) {                          // every row reads (0, 0): decided on the host
+    if (masked && !e->cols.has_attributes()) {                   // every row reads (0, 0): decided on the host
         if (!predicate_passes(np, 0, 0u)) return WAX_HIP_OK;
         masked = false;
     }

@@ -13,21 +13,14 @@ int wax_hip_set_attributes(wax_hip_engine* e, const uint64_t* frame_ids, const i
     REFUSE_IF_HOLDING(e);
     WriteGuard w(e->lock);
     sync_timeline_work(e);
-    uint64_t applied = 0, lowest = UINT64_MAX;
+    uint64_t applied = 0;
     for (uint64_t i = 0; i < n; ++i) {
         const int64_t r = e->idmap.find(frame_ids[i]);
         if (r < 0) continue;                                   // a frame without a vector has no row to describe
         ++applied;
         if (!timestamps && !flags) continue;
-        if (e->attr_ts.size() <= (uint64_t)r) {                // the columns end below this row: everything up to it was (0, 0)
-            e->attr_ts.resize((size_t)e->count, 0);
-            e->attr_flags.resize((size_t)e->count, 0u);
-        }
-        if (timestamps) e->attr_ts[(size_t)r] = timestamps[i];  // in call order: the last entry of a repeated id wins
-        if (flags) e->attr_flags[(size_t)r] = flags[i];
-        if ((uint64_t)r < lowest) lowest = (uint64_t)r;
+        e->cols.set_attributes((uint64_t)r, e->count, timestamps ? timestamps + i : nullptr, flags ? flags + i : nullptr);
     }
-    if (lowest != UINT64_MAX) attr_note_moved(e, lowest);
     if (out_applied) *out_applied = applied;
     return WAX_HIP_OK;
 }
@@ -39,12 +32,10 @@ int wax_hip_get_attributes(wax_hip_engine* e, const uint64_t* frame_ids, uint64_
     if (!frame_ids) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "getAttributes: null input");
     if (e->sh) return sh_get_attributes(e, frame_ids, n, out_timestamps, out_flags, out_found);
     ReadGuard rd(e);
-    const uint64_t na = e->attr_ts.size();
     for (uint64_t i = 0; i < n; ++i) {
         const int64_t r = e->idmap.find(frame_ids[i]);
-        const bool set = r >= 0 && (uint64_t)r < na;
-        if (out_timestamps) out_timestamps[i] = set ? e->attr_ts[(size_t)r] : 0;
-        if (out_flags) out_flags[i] = set ? e->attr_flags[(size_t)r] : 0u;
+        if (out_timestamps) out_timestamps[i] = r >= 0 ? e->cols.ts().at((uint64_t)r) : 0;
+        if (out_flags) out_flags[i] = r >= 0 ? e->cols.flags().at((uint64_t)r) : 0u;
         if (out_found) out_found[i] = r >= 0 ? 1 : 0;
     }
     return WAX_HIP_OK;
@@ -56,12 +47,13 @@ int wax_hip_get_attributes(wax_hip_engine* e, const uint64_t* frame_ids, uint64_
 static int ensure_attrs(wax_hip_engine* e, hipStream_t st, const int64_t** d_ts, const uint32_t** d_flags) {
     *d_ts = nullptr; *d_flags = nullptr;
     std::unique_lock<std::mutex> g(e->attr_mu);
-    const uint64_t na = e->attr_ts.size(), count = e->count;
+    UploadMark& mark = e->cols.attr_mark();
+    const uint64_t na = e->cols.attr_rows(), count = e->count;
     if (na == 0) return WAX_HIP_OK;
     if (e->attr_cap < count) {
         // growth: columns of the store's capacity; the rows that were up to date are kept (a device copy), the rest is uploaded below
         const uint64_t cap = e->capacity > count ? e->capacity : count;
-        const uint64_t keep = std::min(std::min(e->attr_dev_rows, e->attr_stale_from), e->attr_cap);
+        const uint64_t keep = mark.from(e->attr_cap);
         int64_t* nt = nullptr;
         uint32_t* nf = nullptr;
         HIP_TRY(hipMalloc(&nt, (size_t)cap * sizeof(int64_t)), WAX_HIP_ERR_ALLOC, "Failed to allocate the timestamp column");
@@ -71,16 +63,17 @@ static int ensure_attrs(wax_hip_engine* e, hipStream_t st, const int64_t** d_ts,
         if (err == hipSuccess) err = hipStreamSynchronize(st);
         if (err != hipSuccess) { (void)hipFree(nt); (void)hipFree(nf); return fail(WAX_HIP_ERR_ALLOC, std::string("Failed to allocate the flag column: ") + hipGetErrorString(err)); }
         (void)hipFree(e->d_attr_ts); (void)hipFree(e->d_attr_flags);
-        e->d_attr_ts = nt; e->d_attr_flags = nf; e->attr_cap = cap; e->attr_dev_rows = keep;
+        e->d_attr_ts = nt; e->d_attr_flags = nf; e->attr_cap = cap;
+        mark.note(keep);                                       // the new columns hold nothing from there on
     }
-    const uint64_t from = std::min(std::min(e->attr_dev_rows, e->attr_stale_from), count);
+    const uint64_t from = mark.from(count);
     if (from < count) {
         const uint64_t host_end = std::min(na, count);         // rows behind the host columns are (0, 0)
         if (from < host_end) {
             // pageable sources: the runtime stages them before returning
-            HIP_TRY(hipMemcpyAsync(e->d_attr_ts + from, e->attr_ts.data() + from, (size_t)(host_end - from) * sizeof(int64_t), hipMemcpyHostToDevice, st),
+            HIP_TRY(hipMemcpyAsync(e->d_attr_ts + from, e->cols.ts().data() + from, (size_t)(host_end - from) * sizeof(int64_t), hipMemcpyHostToDevice, st),
                     WAX_HIP_ERR_INTERNAL, "timestamp upload");
-            HIP_TRY(hipMemcpyAsync(e->d_attr_flags + from, e->attr_flags.data() + from, (size_t)(host_end - from) * sizeof(uint32_t), hipMemcpyHostToDevice, st),
+            HIP_TRY(hipMemcpyAsync(e->d_attr_flags + from, e->cols.flags().data() + from, (size_t)(host_end - from) * sizeof(uint32_t), hipMemcpyHostToDevice, st),
                     WAX_HIP_ERR_INTERNAL, "flag upload");
         }
         const uint64_t z0 = std::max(from, host_end);
@@ -91,8 +84,7 @@ static int ensure_attrs(wax_hip_engine* e, hipStream_t st, const int64_t** d_ts,
         HIP_TRY(hipStreamSynchronize(st), WAX_HIP_ERR_INTERNAL, "attribute upload failed on device");   // other workspaces' streams read the columns next
         e->st_attr_uploaded += count - from;
     }
-    e->attr_dev_rows = count;
-    e->attr_stale_from = UINT64_MAX;
+    mark.settle(count);
     *d_ts = e->d_attr_ts; *d_flags = e->d_attr_flags;
     return WAX_HIP_OK;
 }

@@ -85,7 +85,7 @@ static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int
         bool ride = false;
         if (x != nullptr && x->pred != nullptr) {
             e->pt_submitted++;
-            if (e->attr_ts.empty()) {
+            if (!e->cols.has_attributes()) {
                 // a store on which attributes were never set reads (0, 0) in every row: every row passes or none does
                 e->pt_host_decided++;
                 if (!predicate_passes(*x->pred, 0, 0u)) { s->k_eff = 0; s->timed = false; break; }   // count 0, no device work

@@ -347,7 +347,7 @@ int wax_hip_remove(wax_hip_engine* e, uint64_t frame_id) {
     if (mirror_note_remove(e, (uint64_t)idx) != WAX_HIP_OK) { (void)hipGetLastError(); mirror_note_lost(e); }
     const bool repeated_ids = e->idmap.size() != e->count;   // only deserialize can put a frame id into several rows
     e->ids.erase(e->ids.begin() + idx);                   // :440
-    attr_note_remove(e, (uint64_t)idx);                   // the row's attributes go with its id
+    e->cols.remove_row((uint64_t)idx);                    // the row's entries in the per-row columns go with its id
     e->idmap.erase_row(frame_id, (uint32_t)idx);
     if (repeated_ids) {
         // firstIndex(of:) semantics: the id now means the next row that holds it (the map held the first one, so any other lies behind it)
@@ -413,28 +413,15 @@ int wax_hip_remove_batch(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t 
             for (uint32_t r : rem) e->idmap.erase_only(e->ids[r]);
             e->idmap.renumber_removed(rem, e->count);
             {
-                // the id vector and the two attribute columns (which may end below `count`: the rows behind them are (0, 0)) in one pass
-                const uint64_t na = e->attr_ts.size(), np = e->attr_parent.size();
-                uint64_t wr = rem[0], wa = rem[0], wp = rem[0];
+                uint64_t wr = rem[0];
                 size_t p = 0;
                 for (uint64_t r = rem[0]; r < e->count; ++r) {
                     if (p < m && rem[p] == r) { ++p; continue; }
                     e->ids[wr++] = e->ids[r];
-                    if (r < na) { e->attr_ts[wa] = e->attr_ts[r]; e->attr_flags[wa] = e->attr_flags[r]; ++wa; }
-                    if (r < np) e->attr_parent[wp++] = e->attr_parent[r];
                 }
                 e->ids.resize((size_t)wr);
-                if (rem[0] < na) {
-                    e->attr_ts.resize((size_t)wa); e->attr_flags.resize((size_t)wa);
-                    attr_note_moved(e, rem[0]);
-                }
-                if (np != 0) {                                 // the parent column likewise; rows behind it shift their slot entries all the same
-                    if (rem[0] < np) e->attr_parent.resize((size_t)wp);
-                    if (e->attr_parent.empty()) parent_note_replaced(e);
-                    else parent_note_moved(e, rem[0]);
-                }
-                term_note_remove_rows(e, rem.data(), rem.size());   // and the term column (CSR: a pass of its own)
             }
+            e->cols.remove_rows(rem.data(), rem.size());        // the per-row columns: a pass each, over the rows they hold
             e->count -= m;                                     // :441, m times
             e->st_remove_batches += 1;
             e->st_remove_batch_rows += m;

@@ -33,11 +33,9 @@ static void fill_term_mask_req(TermMaskArgs* a, const TermReq& req) {
 
 // Does row r of the HOST column hold every required term? (the short allow-list's test: stage_host_rows)
 static bool term_row_has_all(const wax_hip_engine* e, uint64_t r, const TermReq& req) {
-    if (r + 1 >= e->term_off.size()) return false;                 // behind the column: the empty set
-    const uint32_t* b = e->term_val.data() + e->term_off[(size_t)r];
-    const uint32_t* en = e->term_val.data() + e->term_off[(size_t)r + 1];
+    const TermColumn::Span set = e->cols.terms().span(r);          // behind the column: the empty set
     for (uint32_t i = 0; i < req.n; ++i)
-        if (!std::binary_search(b, en, req.t[i])) return false;
+        if (!std::binary_search(set.begin, set.end, req.t[i])) return false;
     return true;
 }
 
@@ -101,9 +99,7 @@ static void make_term_multi_plan(const TermReq* const* sets, uint32_t n_sets, Te
 
 // ---- the column -------------------------------------------------------------------
 
-// (TermPlan, one validated set_terms call, is in engine_types.inc: the sharded handle takes it too)
-// One engine's share of a plan: (row, entry) by ascending row, one per row — in call order the last entry of a repeated id wins.
-typedef std::vector<std::pair<uint64_t, uint64_t>> TermRows;
+// (TermPlan, one validated set_terms call, and TermRows, one store's share of it, are in row_columns.h with the column they are applied to)
 
 static int validate_term_sets(const uint64_t* term_begin, const uint32_t* term_len, const uint32_t* terms, uint64_t n_terms, uint64_t n, TermPlan* p) {
     uint64_t sum = 0;
@@ -132,69 +128,6 @@ static int validate_term_sets(const uint64_t* term_begin, const uint32_t* term_l
     return WAX_HIP_OK;
 }
 
-// (row, entry) pairs in call order -> one per row, ascending, the last entry of a row kept
-static void finish_term_rows(TermRows* rows) {
-    std::stable_sort(rows->begin(), rows->end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-    size_t w = 0;
-    for (size_t i = 0; i < rows->size(); ++i)
-        if (i + 1 == rows->size() || (*rows)[i + 1].first != (*rows)[i].first) (*rows)[w++] = (*rows)[i];
-    rows->resize(w);
-}
-
-// The terms the engine would hold once `rows` of the plan are applied (exclusive lock held).
-static uint64_t term_total_after(const wax_hip_engine* e, const TermPlan& p, const TermRows& rows) {
-    const uint64_t old_rows = e->term_off.empty() ? 0 : e->term_off.size() - 1;
-    uint64_t total = e->term_off.empty() ? 0 : e->term_off.back();
-    for (const auto& re : rows) {
-        if (re.first < old_rows) total -= e->term_off[(size_t)re.first + 1] - e->term_off[(size_t)re.first];
-        total += p.e_off[(size_t)re.second + 1] - p.e_off[(size_t)re.second];
-    }
-    return total;
-}
-
-// Apply (exclusive lock held; term_total_after(e, p, rows) < 2^32; rows not empty). Sets of the size they had are overwritten in place;
-// otherwise the CSR is rebuilt from the lowest row whose size changes, to the end of the column: the old one's, or the highest row
-// set if that lies behind it — the rows behind the column hold the empty set and need no entry.
-static void commit_term_rows(wax_hip_engine* e, const TermPlan& p, const TermRows& rows) {
-    const uint64_t old_rows = e->term_off.empty() ? 0 : e->term_off.size() - 1;
-    auto new_len = [&](const std::pair<uint64_t, uint64_t>& re) { return (uint32_t)(p.e_off[(size_t)re.second + 1] - p.e_off[(size_t)re.second]); };
-    auto old_len = [&](uint64_t r) -> uint32_t { return r < old_rows ? e->term_off[(size_t)r + 1] - e->term_off[(size_t)r] : 0u; };
-    size_t first_resized = rows.size();
-    for (size_t i = 0; i < rows.size(); ++i) {
-        if (rows[i].first < old_rows && new_len(rows[i]) == old_len(rows[i].first)) {
-            if (new_len(rows[i]) != 0)
-                std::memcpy(e->term_val.data() + e->term_off[(size_t)rows[i].first], p.flat.data() + p.e_off[(size_t)rows[i].second], (size_t)new_len(rows[i]) * sizeof(uint32_t));
-        } else if (first_resized == rows.size()) {
-            first_resized = i;
-        }
-    }
-    if (first_resized != rows.size()) {
-        const uint64_t lowest = rows[first_resized].first;
-        const uint64_t new_rows = std::max(old_rows, rows.back().first + 1);
-        if (e->term_off.empty()) e->term_off.push_back(0u);
-        const uint64_t keep_rows = std::min(lowest, old_rows);
-        const uint32_t keep = e->term_off[(size_t)keep_rows];
-        std::vector<uint32_t> tail_off, tail_val;
-        tail_off.reserve((size_t)(new_rows - lowest));
-        size_t i = first_resized;
-        for (uint64_t r = lowest; r < new_rows; ++r) {
-            if (i < rows.size() && rows[i].first == r) {
-                tail_val.insert(tail_val.end(), p.flat.begin() + (ptrdiff_t)p.e_off[(size_t)rows[i].second], p.flat.begin() + (ptrdiff_t)p.e_off[(size_t)rows[i].second + 1]);
-                ++i;
-            } else if (r < old_rows) {
-                tail_val.insert(tail_val.end(), e->term_val.begin() + e->term_off[(size_t)r], e->term_val.begin() + e->term_off[(size_t)r + 1]);
-            }
-            tail_off.push_back(keep + (uint32_t)tail_val.size());
-        }
-        e->term_off.resize((size_t)keep_rows + 1);
-        e->term_off.resize((size_t)lowest + 1, keep);          // rows between the old column's end and `lowest` held the empty set
-        e->term_off.insert(e->term_off.end(), tail_off.begin(), tail_off.end());
-        e->term_val.resize((size_t)keep);
-        e->term_val.insert(e->term_val.end(), tail_val.begin(), tail_val.end());
-    }
-    term_note_moved(e, rows.front().first);
-}
-
 int wax_hip_set_terms(wax_hip_engine* e, const uint64_t* frame_ids, const uint64_t* term_begin, const uint32_t* term_len, const uint32_t* terms,
                       uint64_t n_terms, uint64_t n, uint64_t* out_applied) {
     if (out_applied) *out_applied = 0;
@@ -217,8 +150,8 @@ int wax_hip_set_terms(wax_hip_engine* e, const uint64_t* frame_ids, const uint64
     }
     finish_term_rows(&rows);
     if (!rows.empty()) {
-        if (term_total_after(e, plan, rows) >= 0x100000000ull) return fail(WAX_HIP_ERR_CAPACITY, "setTerms: the store would hold 2^32 terms or more");
-        commit_term_rows(e, plan, rows);
+        if (e->cols.terms().total_after(plan, rows) >= 0x100000000ull) return fail(WAX_HIP_ERR_CAPACITY, "setTerms: the store would hold 2^32 terms or more");
+        e->cols.commit_terms(plan, rows);
     }
     if (out_applied) *out_applied = applied;
     return WAX_HIP_OK;
@@ -234,10 +167,9 @@ int wax_hip_get_terms(wax_hip_engine* e, uint64_t frame_id, uint32_t* out_terms,
     const int64_t r = e->idmap.find(frame_id);
     if (r < 0) return WAX_HIP_OK;
     if (out_found) *out_found = 1;
-    if ((uint64_t)r + 1 >= e->term_off.size()) return WAX_HIP_OK;
-    const uint32_t b = e->term_off[(size_t)r], len = e->term_off[(size_t)r + 1] - b;
-    for (uint32_t i = 0; i < len && i < out_capacity; ++i) out_terms[i] = e->term_val[(size_t)b + i];
-    *out_count = len;
+    const TermColumn::Span set = e->cols.terms().span((uint64_t)r);
+    for (uint32_t i = 0; i < set.size() && i < out_capacity; ++i) out_terms[i] = set.begin[i];
+    *out_count = set.size();
     return WAX_HIP_OK;
 }
 
@@ -247,15 +179,16 @@ int wax_hip_get_terms(wax_hip_engine* e, uint64_t frame_id, uint32_t* out_terms,
 static int ensure_terms(wax_hip_engine* e, hipStream_t st, const uint32_t** d_off, const uint32_t** d_val) {
     *d_off = nullptr; *d_val = nullptr;
     std::unique_lock<std::mutex> g(e->term_mu);
-    const uint64_t count = e->count, host_rows = e->term_off.size() - 1, total = e->term_off.back();
-    auto host_off = [&](uint64_t r) -> uint32_t { return e->term_off[(size_t)std::min(r, host_rows)]; };
-    uint64_t from = std::min(std::min(e->term_dev_rows, e->term_stale_from), count);
-    bool current = from == count && e->term_dev_rows == count && e->term_stale_from == UINT64_MAX;
+    const TermColumn& terms = e->cols.terms();
+    UploadMark& mark = e->cols.term_mark();
+    const uint64_t count = e->count, total = terms.total();
+    uint64_t from = mark.from(count);
+    bool current = mark.current(count);
     const uint64_t val_need = ((total + 3ull) & ~3ull) + 4ull;   // whole dwordx4 pieces (terms.hip), never an empty allocation
     if (e->term_off_cap < count + 1 || e->term_val_cap < val_need) {
         // the rows that were current are kept by a device copy, the rest is uploaded below
         const uint64_t keep = e->term_off_cap == 0 ? 0 : std::min(from, e->term_off_cap - 1);
-        const uint64_t keep_val = std::min<uint64_t>(host_off(keep), e->term_val_cap);
+        const uint64_t keep_val = std::min<uint64_t>(terms.offset(keep), e->term_val_cap);
         uint64_t off_cap = e->term_off_cap, val_cap = e->term_val_cap;
         if (off_cap < count + 1) off_cap = (e->capacity > count ? e->capacity : count) + 1;
         if (val_cap < val_need) { val_cap = std::max<uint64_t>(val_cap * 2, 1024); while (val_cap < val_need) val_cap *= 2; }
@@ -269,26 +202,25 @@ static int ensure_terms(wax_hip_engine* e, hipStream_t st, const uint32_t** d_of
         if (err != hipSuccess) { (void)hipFree(no); (void)hipFree(nv); return fail(WAX_HIP_ERR_ALLOC, std::string("Failed to allocate the term values: ") + hipGetErrorString(err)); }
         (void)hipFree(e->d_term_off); (void)hipFree(e->d_term_val);
         e->d_term_off = no; e->d_term_val = nv; e->term_off_cap = off_cap; e->term_val_cap = val_cap;
-        e->term_dev_rows = keep;
-        from = std::min(from, keep);
+        mark.note(keep);                                       // the new arrays hold nothing from there on
+        from = mark.from(count);
         current = false;
     }
     if (!current) {
         // offsets of rows [from, count]: the host's, and the column's end for the rows behind it
         std::vector<uint32_t> offs((size_t)(count - from) + 1);
-        for (uint64_t r = from; r <= count; ++r) offs[(size_t)(r - from)] = host_off(r);
-        const uint32_t v0 = host_off(from);
+        for (uint64_t r = from; r <= count; ++r) offs[(size_t)(r - from)] = terms.offset(r);
+        const uint32_t v0 = terms.offset(from);
         // pageable sources: the runtime stages them before returning
         HIP_TRY(hipMemcpyAsync(e->d_term_off + from, offs.data(), offs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st), WAX_HIP_ERR_INTERNAL, "term offset upload");
         if (v0 < total)
-            HIP_TRY(hipMemcpyAsync(e->d_term_val + v0, e->term_val.data() + v0, (size_t)(total - v0) * sizeof(uint32_t), hipMemcpyHostToDevice, st),
+            HIP_TRY(hipMemcpyAsync(e->d_term_val + v0, terms.values() + v0, (size_t)(total - v0) * sizeof(uint32_t), hipMemcpyHostToDevice, st),
                     WAX_HIP_ERR_INTERNAL, "term value upload");
         HIP_TRY(hipStreamSynchronize(st), WAX_HIP_ERR_INTERNAL, "term upload failed on device");   // other workspaces' streams read the column next
         e->tm_rows_uploaded += count - from;
         e->tm_values_uploaded += total - v0;
     }
-    e->term_dev_rows = count;
-    e->term_stale_from = UINT64_MAX;
+    mark.settle(count);
     *d_off = e->d_term_off; *d_val = e->d_term_val;
     return WAX_HIP_OK;
 }

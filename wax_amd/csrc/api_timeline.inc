@@ -81,7 +81,7 @@ int wax_hip_timeline_device(wax_hip_engine* e, int32_t limit, int newest_first, 
     if (!t.cols) HIP_TRY(hipEventCreateWithFlags(&t.cols, hipEventDisableTiming), WAX_HIP_ERR_ALLOC, "Failed to allocate timeline events");
     TimelineArgs a;
     timeline_args(&a, pred, limit, newest_first);
-    if (e->count != 0 && !e->attr_ts.empty()) {
+    if (e->count != 0 && e->cols.has_attributes()) {
         // The columns are brought up to date on a workspace stream, as the blocking predicate search does it, and the caller's stream
         // waits for that by an event: an upload on the caller's stream would let a concurrent predicate search (which takes the
         // columns as current once ensure_attrs has returned) read rows another stream is still writing.

@@ -34,71 +34,6 @@ static void mirror_note_replaced(wax_hip_engine* e) {       // deserialize: ever
     e->idhash.valid = false; e->idhash.stale = true; e->idhash.rows = 0;
     c8_note_stale(e);
 }
-// Mutation hooks of the per-row attribute columns (exclusive engine lock held). The device mirror is only ever marked: the next
-// predicate search uploads from the lowest marked row (ensure_attrs, api_predicate.inc).
-static void attr_note_moved(wax_hip_engine* e, uint64_t row) {
-    if (row < e->attr_stale_from) e->attr_stale_from = row;
-}
-// The same hooks for the parent column (DESIGN 4.10). A store without parents has no slot column to keep: nothing is marked there.
-static void parent_note_moved(wax_hip_engine* e, uint64_t row) {
-    if (!e->attr_parent.empty() && row < e->grp_stale_from) e->grp_stale_from = row;
-}
-static void parent_note_replaced(wax_hip_engine* e) {             // every row is its own root again
-    e->attr_parent.clear();
-    e->grp_slot_of.clear(); e->grp_slot_root.clear(); e->grp_slot.clear();
-    e->grp_rows = 0; e->grp_stale_from = UINT64_MAX; e->grp_root_dev = 0;
-}
-static void parent_note_remove(wax_hip_engine* e, uint64_t idx) {
-    if (e->attr_parent.empty()) return;
-    if (idx < e->attr_parent.size()) e->attr_parent.erase(e->attr_parent.begin() + (ptrdiff_t)idx);
-    if (e->attr_parent.empty()) parent_note_replaced(e);          // every row left is its own root: a store without parents
-    else parent_note_moved(e, idx);                                // (a row behind the column shifts its slot entry all the same)
-}
-// And for the term column (DESIGN 4.11), CSR on the host: a store without terms has nothing to mark.
-static void term_note_moved(wax_hip_engine* e, uint64_t row) {
-    if (!e->term_off.empty() && row < e->term_stale_from) e->term_stale_from = row;
-}
-static void term_note_replaced(wax_hip_engine* e) {               // every row holds the empty set again
-    e->term_off.clear(); e->term_val.clear();
-    e->term_stale_from = UINT64_MAX; e->term_dev_rows = 0;
-}
-// rows rem[0 .. m) (ascending, unique) leave with their sets: one compaction pass from the lowest of them
-template <typename Row>
-static void term_note_remove_rows(wax_hip_engine* e, const Row* rem, size_t m) {
-    if (e->term_off.empty() || m == 0) return;
-    const uint64_t nt = e->term_off.size() - 1;
-    if (rem[0] < nt) {
-        uint64_t wr = rem[0];
-        uint32_t wv = e->term_off[(size_t)rem[0]], b = wv;
-        size_t p = 0;
-        for (uint64_t r = rem[0]; r < nt; ++r) {
-            const uint32_t en = e->term_off[(size_t)r + 1];
-            if (p < m && rem[p] == r) { ++p; b = en; continue; }
-            if (wv != b) std::memmove(e->term_val.data() + wv, e->term_val.data() + b, (size_t)(en - b) * sizeof(uint32_t));
-            wv += en - b;
-            b = en;
-            e->term_off[(size_t)++wr] = wv;                        // (wr <= r + 1: an entry already read, or the one just read with its own value)
-        }
-        e->term_off.resize((size_t)wr + 1);
-        e->term_val.resize((size_t)wv);
-    }
-    if (e->term_off.size() <= 1) term_note_replaced(e);            // no row left under the column: a store without terms
-    else term_note_moved(e, (uint64_t)rem[0]);
-}
-static void attr_note_remove(wax_hip_engine* e, uint64_t idx) {   // remove(frameId:): the entry leaves as the id does
-    parent_note_remove(e, idx);
-    term_note_remove_rows(e, &idx, 1);
-    if (idx >= e->attr_ts.size()) return;                          // the row was (0, 0) like everything behind it
-    e->attr_ts.erase(e->attr_ts.begin() + (ptrdiff_t)idx);
-    e->attr_flags.erase(e->attr_flags.begin() + (ptrdiff_t)idx);
-    attr_note_moved(e, idx);
-}
-static void attr_note_replaced(wax_hip_engine* e) {               // deserialize / a shard emptied: every row is (0, 0) again
-    e->attr_ts.clear(); e->attr_flags.clear();
-    e->attr_stale_from = 0; e->attr_dev_rows = 0;
-    parent_note_replaced(e);
-    term_note_replaced(e);
-}
 // a mutation the mirror could not follow (a failed row shift): convert everything at the next use
 static void mirror_note_lost(wax_hip_engine* e) {
     c8_note_stale(e);

@@ -26,6 +26,7 @@
 
 #include "kernels.h"
 #include "mirror8_layout.h"
+#include "row_columns.h"
 
 using namespace wax;
 
@@ -33,7 +34,8 @@ using namespace wax;
 // ---------------------------------------------------------------------------------------------------------------------------
 // ONE translation unit, cut into the files below (round 6: the 3 300-line engine.hip hid the contract). Each .inc is a stretch of
 // this file as it stood — included here, in this order, and never compiled on its own: the order is the declaration order, the
-// anonymous namespace and the extern "C" block open and close where they always did.
+// anonymous namespace and the extern "C" block open and close where they always did. row_columns.h, included above, is the one part
+// that stands alone: the per-row columns on the host, plain C++ without HIP, tested on the CPU (tests/row_columns/driver.cpp).
 //
 //   engine_types.inc       types of the host side: error state, device / lock guards, the id map, the reader/writer lock, scratch slots, workspaces, the bf16 mirror's bookkeeping, `struct wax_hip_engine`, ticket ownership
 //   store_internal.inc     the store behind the C ABI: clampTopK, the scratch-slot pool, the general-selection workspace, staged appends, growth (MetalVectorEngine.swift:84-117, 330-357, 842-890)

@@ -625,53 +625,31 @@ struct wax_hip_engine {
     std::vector<FilterWork*> filter_all, filter_free;
     int filter_max = 4;
     IdHash idhash;
-    // Per-row attributes (wax_hip_set_attributes; DESIGN 2). The host columns are authoritative, in row order beside `ids`; they may be
-    // SHORTER than the store: rows at or beyond their length are (0, 0) — what every appended row is — so the append paths do not touch
-    // them, and a store that never had attributes holds two empty vectors. Writers change them under the exclusive engine lock.
-    std::vector<int64_t> attr_ts;
-    std::vector<uint32_t> attr_flags;
-    // Device mirror, [attr_cap] of each, kept as the id -> row table is kept: rows [0, attr_dev_rows) below attr_stale_from match the
-    // host; the first predicate search after a change uploads [min of the two, count) on its workspace stream (ensure_attrs, under
-    // attr_mu and the shared engine lock). Writers (exclusive lock) only lower attr_stale_from.
+    // The per-row columns (DESIGN 2): timestamps and flags (wax_hip_set_attributes), parents (wax_hip_set_parents; DESIGN 4.10), term sets
+    // (wax_hip_set_terms; DESIGN 4.11), the group slots derived from the parents, and the marks of their device copies. Everything about
+    // them that lives in host memory is in row_columns.h; writers change it under the exclusive engine lock.
+    RowColumns cols;
+    // Device copy of the attributes, [attr_cap] of each: the first predicate search after a change uploads from cols.attr_mark() on its
+    // workspace stream (ensure_attrs, api_predicate.inc, under attr_mu and the shared engine lock).
     std::mutex attr_mu;
     int64_t* d_attr_ts = nullptr;
     uint32_t* d_attr_flags = nullptr;
-    uint64_t attr_cap = 0, attr_dev_rows = 0;
-    uint64_t attr_stale_from = UINT64_MAX;        // lowest row whose device copy may differ from the host's
+    uint64_t attr_cap = 0;
     std::atomic<uint64_t> st_attr_uploaded{0};
-    // The parent column (wax_hip_set_parents; DESIGN 4.10): a third host column under the rules of the two above — authoritative, in row
-    // order, possibly SHORTER than the store (rows at or beyond its length are WAX_HIP_NO_PARENT, what every appended row is), empty on
-    // a store that never had parents. Writers change it under the exclusive engine lock.
-    std::vector<uint64_t> attr_parent;
-    // What the grouped search derives from it (ensure_groups, api_grouped.inc, under grp_mu and the shared engine lock): roots numbered
-    // densely — grp_slot_of maps a root id to its slot, grp_slot_root back, grp_slot is the slot of every row. Slots are stable under
-    // removal and renumbered from scratch once there are more than twice as many as rows. Rows [0, grp_rows) below grp_stale_from are
-    // current on the host and on the device; writers only lower grp_stale_from. Nothing of this exists while attr_parent is empty.
+    // Device copy of the group slots (ensure_groups, api_grouped.inc, under grp_mu and the shared engine lock): the slot of every row and
+    // the root id of every slot. Neither exists while the store has no parents.
     std::mutex grp_mu;
-    std::unordered_map<uint64_t, uint32_t> grp_slot_of;
-    std::vector<uint64_t> grp_slot_root;
-    std::vector<uint32_t> grp_slot;
-    uint64_t grp_rows = 0;
-    uint64_t grp_stale_from = UINT64_MAX;
     uint32_t* d_grp_slot = nullptr;               // [grp_cap]
-    uint64_t* d_grp_root = nullptr;               // [grp_root_cap], the first grp_root_dev entries uploaded
-    uint64_t grp_cap = 0, grp_root_cap = 0, grp_root_dev = 0;
+    uint64_t* d_grp_root = nullptr;               // [grp_root_cap], the first grp_root_dev entries uploaded under numbering grp_root_epoch
+    uint64_t grp_cap = 0, grp_root_cap = 0, grp_root_dev = 0, grp_root_epoch = 0;
     // wax_hip_group_stats (a read-out, no tuning key)
     std::atomic<uint64_t> gs_searches{0}, gs_fused_scans{0}, gs_column_scans{0}, gs_member_rounds{0}, gs_group_slots{0}, gs_parent_rows_uploaded{0};
-    // The term column (wax_hip_set_terms; DESIGN 4.11): a fourth host column, every row a set of 0 .. WAX_HIP_TERMS_MAX_PER_ROW distinct
-    // uint32 terms, kept as CSR — term_off[r] .. term_off[r + 1] index row r's terms, ascending, in term_val. Under the rules of the
-    // columns above: authoritative, in row order, possibly SHORTER than the store (term_off holds one entry more than the rows it
-    // covers; rows behind it hold the empty set, what every appended row does), both vectors empty on a store that never had terms.
-    // Writers change it under the exclusive engine lock.
-    std::vector<uint32_t> term_off, term_val;
-    // Device mirror (ensure_terms, api_terms.inc, under term_mu and the shared engine lock): d_term_off[term_off_cap] holds count + 1
-    // offsets, d_term_val[term_val_cap] the values (the capacity a multiple of 4 words: term_mask_kernel reads whole dwordx4). Rows
-    // [0, term_dev_rows) below term_stale_from match the host; writers only lower term_stale_from.
+    // Device copy of the term CSR (ensure_terms, api_terms.inc, under term_mu and the shared engine lock): d_term_off[term_off_cap] holds
+    // count + 1 offsets, d_term_val[term_val_cap] the values (the capacity a multiple of 4 words: term_mask_kernel reads whole dwordx4).
     std::mutex term_mu;
     uint32_t* d_term_off = nullptr;
     uint32_t* d_term_val = nullptr;
-    uint64_t term_off_cap = 0, term_val_cap = 0, term_dev_rows = 0;
-    uint64_t term_stale_from = UINT64_MAX;
+    uint64_t term_off_cap = 0, term_val_cap = 0;
     // wax_hip_term_stats (a read-out, no tuning key)
     std::atomic<uint64_t> tm_searches{0}, tm_device_masks{0}, tm_host_staged{0}, tm_host_decided{0}, tm_rows_uploaded{0}, tm_values_uploaded{0};
     // wax_hip_term_batch_stats (a read-out of its own)
@@ -831,12 +809,6 @@ int sh_search_grouped(wax_hip_engine* e, const float* query, uint32_t dims, int3
                       const wax_hip_row_predicate* pred, uint64_t* out_root_ids, float* out_root_scores, uint64_t* out_member_ids,
                       float* out_member_scores, uint32_t* out_member_counts, uint32_t* out_count);
 int sh_group_stats(wax_hip_engine* e, wax_hip_group_stats_t* out);
-// One set_terms call, checked against itself (api_terms.inc): entry i's distinct terms, ascending, are flat[e_off[i] .. e_off[i + 1]) —
-// one allocation for the whole call, sorted and de-duplicated in place.
-struct TermPlan {
-    std::vector<uint32_t> flat;
-    std::vector<uint64_t> e_off;
-};
 int sh_set_terms(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, const TermPlan& plan, uint64_t* out_applied);
 int sh_get_terms(wax_hip_engine* e, uint64_t frame_id, uint32_t* out_terms, uint32_t out_capacity, uint32_t* out_count, uint8_t* out_found);
 int sh_search_terms(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_k, int has_allow, const uint64_t* allow, uint64_t n_allow,

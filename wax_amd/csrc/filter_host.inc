@@ -61,15 +61,13 @@ static int reserve_row_lists(FilterWork& f, uint64_t m) {
 // columns are on the host too; with required terms (req) only the rows whose set holds them all. *m = rows staged; nothing is uploaded for 0.
 static int stage_host_rows(wax_hip_engine* e, FilterWork& f, const uint64_t* allow, uint64_t n_allow, const wax_hip_row_predicate* pred, uint64_t* m,
                            const TermReq* req = nullptr) {
-    const uint64_t na = e->attr_ts.size();
     std::vector<uint32_t> rows;
     rows.reserve((size_t)n_allow);
     for (uint64_t i = 0; i < n_allow; ++i) {
         const int64_t r = e->idmap.find(allow[i]);
         if (r < 0) continue;
-        const bool set = (uint64_t)r < na;
         if (req && !term_row_has_all(e, (uint64_t)r, *req)) continue;   // the term column is authoritative on the host as well (DESIGN 4.11)
-        if (!pred || predicate_passes(*pred, set ? e->attr_ts[(size_t)r] : 0, set ? e->attr_flags[(size_t)r] : 0u)) rows.push_back((uint32_t)r);
+        if (!pred || predicate_passes(*pred, e->cols.ts().at((uint64_t)r), e->cols.flags().at((uint64_t)r))) rows.push_back((uint32_t)r);
     }
     std::sort(rows.begin(), rows.end());
     rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
@@ -221,7 +219,7 @@ static int search_rows_locked(wax_hip_engine* e, const float* query, uint32_t di
     // — under a predicate that passes every row where the caller gave none — and stays the one place that counts.
     static const wax_hip_row_predicate pass_all{};
     const wax_hip_row_predicate* pred = user_pred ? user_pred : (req ? &pass_all : nullptr);
-    if (req && e->term_off.empty()) { e->tm_host_decided++; return WAX_HIP_OK; }   // no frame has metadata: none matches (UnifiedSearch.swift:1219)
+    if (req && e->cols.terms().empty()) { e->tm_host_decided++; return WAX_HIP_OK; }   // no frame has metadata: none matches (UnifiedSearch.swift:1219)
     if (pred) e->st_predicate_searches++;
     if (e->count == 0 || (has_allow && n_allow == 0)) return WAX_HIP_OK;
     if (pred && e->row_base + e->count > 0x100000000ull) return fail(WAX_HIP_ERR_CAPACITY, "row_base + count exceeds UInt32 row indices");
@@ -467,7 +465,7 @@ static int batch_filtered_locked(wax_hip_engine* e, const float* queries, uint32
         std::map<EntryKey, uint32_t> index;
         for (uint32_t q : fq) {
             const int32_t ts = T ? T->of[q] : -1;
-            if (ts >= 0 && e->term_off.empty()) { apart[q] = 1; ++term_decided; continue; }   // no frame has metadata: none matches (UnifiedSearch.swift:1219)
+            if (ts >= 0 && e->cols.terms().empty()) { apart[q] = 1; ++term_decided; continue; }   // no frame has metadata: none matches (UnifiedSearch.swift:1219)
             const bool listed = F.listed(q);
             const uint64_t len = count == 0 ? 0 : (listed ? F.length(q) : WAX_HIP_NO_ALLOW_LIST);
             if (len == 0) continue;                               // nothing allowed: count 0
@@ -845,7 +843,7 @@ static int search_batch_rows_entry(wax_hip_engine* e, const float* queries, uint
     for (uint32_t q = 0; preds && q < nq && !any_pred; ++q) any_pred = !predicate_is_empty(&preds[q]);
     if (any_pred) {
         bool has_attrs;
-        { ReadGuard rd(e); has_attrs = !e->attr_ts.empty(); }
+        { ReadGuard rd(e); has_attrs = e->cols.has_attributes(); }
         eff.resize(nq);
         dead.assign(nq, 0);
         for (uint32_t q = 0; q < nq; ++q) {

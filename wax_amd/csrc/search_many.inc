@@ -209,7 +209,7 @@ static int search_many_impl(wax_hip_engine* const* engines, const float* queries
         e->st_searches += m.pairs.size();
         // The pairs by normalised predicate. A store that never had attributes has no columns to read (ensure_attrs: every row is
         // (0, 0)): its predicates are decided here, once for all rows — the pair is an unmasked pair, or its count stays 0.
-        const bool has_attrs = !e->attr_ts.empty();
+        const bool has_attrs = e->cols.has_attributes();
         typedef std::tuple<int32_t, int64_t, int32_t, int64_t, uint32_t> PredKey;
         std::map<PredKey, size_t> index;
         m.classes.emplace_back();                    // [0]: no predicate, no mask

@@ -393,7 +393,7 @@ int sh_move_all(ShardedState* s, size_t from, size_t to) {
     { const int frc = flush_pending(src); if (frc != WAX_HIP_OK) return frc; }
     const uint64_t n = src->count;
     if (n == 0) return WAX_HIP_OK;
-    if (!src->term_off.empty() && (uint64_t)src->term_off.back() + (dst->term_off.empty() ? 0u : dst->term_off.back()) >= 0x100000000ull)
+    if (!dst->cols.can_take(src->cols))
         return fail(WAX_HIP_ERR_CAPACITY, "rebalance: the target shard would hold 2^32 terms or more");   // (before any row moves)
     const uint32_t D = src->dims;
     const uint64_t chunk = std::max<uint64_t>(1, (64ull << 20) / ((uint64_t)D * 4));
@@ -420,33 +420,13 @@ int sh_move_all(ShardedState* s, size_t from, size_t to) {
         for (uint64_t r = dst_before; r < dst->count; ++r) dst->idmap.erase_only(dst->ids[(size_t)r]);
         dst->ids.resize((size_t)dst_before);
         dst->count = dst_before;
-        if (dst->attr_ts.size() > dst_before) { dst->attr_ts.resize((size_t)dst_before); dst->attr_flags.resize((size_t)dst_before); }
-        parent_note_moved(dst, dst_before);
-        term_note_moved(dst, dst_before);
-        mirror_note_replaced(dst);     // (rows were appended and taken back: the mirror and the id table start over)
+        dst->cols.truncate(dst_before);
+        mirror_note_replaced(dst);    // (rows were appended and taken back: the mirror and the id table start over)
         return rc;
     }
-    // the rows' attributes travel with them: dst's columns are padded to where the moved rows begin, then take src's
-    if (!src->attr_ts.empty()) {
-        dst->attr_ts.resize((size_t)dst_before, 0); dst->attr_flags.resize((size_t)dst_before, 0u);
-        dst->attr_ts.insert(dst->attr_ts.end(), src->attr_ts.begin(), src->attr_ts.end());
-        dst->attr_flags.insert(dst->attr_flags.end(), src->attr_flags.begin(), src->attr_flags.end());
-        attr_note_moved(dst, dst_before);
-    }
-    if (!src->attr_parent.empty()) {                           // and their parents (DESIGN 4.10), by the same padding
-        dst->attr_parent.resize((size_t)dst_before, WAX_HIP_NO_PARENT);
-        dst->attr_parent.insert(dst->attr_parent.end(), src->attr_parent.begin(), src->attr_parent.end());
-        parent_note_moved(dst, dst_before);
-    }
-    if (!src->term_off.empty()) {                              // and their term sets (DESIGN 4.11): dst's rows up to there hold what they held
-        if (dst->term_off.empty()) dst->term_off.push_back(0u);
-        dst->term_off.resize((size_t)dst_before + 1, dst->term_off.back());
-        const uint32_t base = dst->term_off.back(), src0 = src->term_off.front();
-        for (size_t r = 1; r < src->term_off.size(); ++r) dst->term_off.push_back(base + (src->term_off[r] - src0));
-        dst->term_val.insert(dst->term_val.end(), src->term_val.begin(), src->term_val.end());
-        term_note_moved(dst, dst_before);
-    }
-    attr_note_replaced(src);
+    // the rows' attributes, parents and term sets travel with them: dst's columns are padded to where the moved rows begin, then take
+    // src's, which is left without columns
+    dst->cols.take_all(src->cols, dst_before);
     // empty the source (capacity stays)
     src->count = 0;
     src->ids.clear();
@@ -1526,11 +1506,11 @@ int sh_set_terms(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, const
         if (rows[g].empty()) continue;
         finish_term_rows(&rows[g]);
         sub_locks.emplace_back(new WriteGuard(s->subs[g]->lock));
-        if (term_total_after(s->subs[g], plan, rows[g]) >= 0x100000000ull)
+        if (s->subs[g]->cols.terms().total_after(plan, rows[g]) >= 0x100000000ull)
             return fail(WAX_HIP_ERR_CAPACITY, "setTerms: a shard would hold 2^32 terms or more");
     }
     for (size_t g = 0; g < G; ++g)
-        if (!rows[g].empty()) commit_term_rows(s->subs[g], plan, rows[g]);
+        if (!rows[g].empty()) s->subs[g]->cols.commit_terms(plan, rows[g]);
     if (out_applied) *out_applied = applied;
     return WAX_HIP_OK;
 }
