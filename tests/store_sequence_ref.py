@@ -9,7 +9,7 @@ GPU test replays a Sequence on an engine and, after every step, holds every rout
 
 Model      ordered frame ids, rows, ts, flags with the reference's semantics as helpers.OracleEngine has them: upsert by id (first
            row that holds the id), order-preserving remove of that first row, attributes (0, 0) for new rows and after deserialize.
-Protocol   the host-side state machines of batch_host.inc / api_store.inc / codec.inc and of row_columns.h, restated rule by rule (each
+Protocol   the host-side state machines of derived_rows.h, batch_host.inc / api_store.inc / codec.inc and of row_columns.h, restated rule by rule (each
            method names the engine function it restates), so the deltas of "mirror_rows_converted", "idhash_rows_inserted", "mirror8_conversions" and
            "mirror8_rows_converted" over one step (its mutations, then every reader) are predicted, and so the states a step enters are
            tagged with the coverage class they belong to.
@@ -446,14 +446,14 @@ class Protocol:
         self.capacity = nxt
         self.tags.add("growth")
 
-    # -- batch_host.inc: c8_note_append / c8_note_stale
+    # -- derived_rows.h: what DerivedRows' operations do to the code mirror: RowFill::appended / RowFill::restart
     def _c8_append(self):
         self.c_valid = False
 
     def _c8_stale(self):
         self.c_valid, self.c_stale = False, True
 
-    # -- batch_host.inc: mirror_note_upsert
+    # -- derived_rows.h: DerivedRows::overwritten
     def _upsert(self, row):
         self._c8_stale()
         if self.m_stale or row >= self.m_rows:
@@ -475,7 +475,7 @@ class Protocol:
             return
         if self.pend:
             self.tags.add("staged_pending:" + ("add" if n == 1 else "addBatch"))
-        self.h_valid = False                              # mirror_note_append
+        self.h_valid = False                              # DerivedRows::appended
         self._c8_append()
         if n == 1:
             if rows_hit[0] >= 0:
@@ -495,7 +495,7 @@ class Protocol:
         if len(self.m_dirty) == K_MAX_DIRTY and not self.m_stale:
             self.tags.add("upserts_4096_listed")
 
-    # -- api_store.inc: wax_hip_remove + batch_host.inc: mirror_note_remove
+    # -- api_store.inc: wax_hip_remove + batch_host.inc: mirror_follow_remove + derived_rows.h: DerivedRows::removed(row, followed)
     def remove(self, idx, loop=False):
         if idx < 0:
             if self.pend:
@@ -521,7 +521,7 @@ class Protocol:
         self._columns_remove([idx])
         self.count -= 1
 
-    # -- api_store.inc: wax_hip_remove_batch + batch_host.inc: compact_removed_rows, mirror_note_remove_batch
+    # -- api_store.inc: wax_hip_remove_batch + batch_host.inc: compact_removed_rows + derived_rows.h: DerivedRows::removed(rem, m, followed)
     def remove_batch(self, rem):
         """rem: the store rows that leave, ascending and distinct (a store without repeated ids)."""
         if self.pend:
@@ -589,7 +589,7 @@ class Protocol:
             self.tags.add("staged_pending:reserve")
         self._reserve_rows(rows)
 
-    # -- codec.inc: wax_hip_deserialize (mirror_note_replaced; capacity only grows, to the segment's rows exactly)
+    # -- codec.inc: wax_hip_deserialize (DerivedRows::replaced; capacity only grows, to the segment's rows exactly)
     def deserialize(self, n, kind):
         if self.pend:
             self.tags.add("staged_pending:" + kind)

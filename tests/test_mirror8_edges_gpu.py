@@ -213,7 +213,7 @@ def test_mirror_follows_every_mutation(wax):
     """test_mutations_between_queries's sequence with a host model of the rows alongside: after the append the old rows are byte for
     byte what they were and the new ones satisfy (a); after every rebuild the whole mirror satisfies (a) against the model's rows in
     their new order and the max-norm word is tight again (the 1.5-norm upsert leaves with deserialize). Between a mutation — an append
-    included — and the query that converts, the engine REFUSES the snapshot (`c8_valid` is false from the mutation on), so it never
+    included — and the query that converts, the engine REFUSES the snapshot (the code mirror's fill is not current() from the mutation on), so it never
     hands out rows beyond, or other than, what was coded."""
     dims, k, n = 384, 10, 2005
     queries = R.queries_for(dims)

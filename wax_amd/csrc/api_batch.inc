@@ -30,7 +30,7 @@ static int search_batch_hits_impl(wax_hip_engine* e, const float* queries, uint3
         use_mfma = t_pass + t_rebuild < t_loop;
         // ... but a steady stream of small batches amortises it: the third one in a row that a valid mirror would have
         // made cheaper pays for the rebuild
-        if (!use_mfma && t_pass < t_loop && e->batch.mirror_wanted.fetch_add(1) >= 2) use_mfma = true;
+        if (!use_mfma && t_pass < t_loop && e->derived.bf16.wanted()) use_mfma = true;
     }
     if (use_mfma) {
         int brc = WAX_HIP_OK;
@@ -290,7 +290,7 @@ static int batch_device_impl(wax_hip_engine* e, const float* d_queries, uint32_t
         const double t_pass = 135e-6 + elems * 2.0 / 4.7e12;
         const double t_rebuild = mirror_rows_to_convert(e) * (double)dims * 6.0 / 5.0e12;
         use_mfma = t_pass + t_rebuild < t_loop;
-        if (!use_mfma && t_pass < t_loop && e->batch.mirror_wanted.fetch_add(1) >= 2) use_mfma = true;
+        if (!use_mfma && t_pass < t_loop && e->derived.bf16.wanted()) use_mfma = true;
     }
     if (use_mfma) {
         rc = ensure_mirror(e, st);

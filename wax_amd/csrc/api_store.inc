@@ -160,8 +160,7 @@ int wax_hip_add_batch(wax_hip_engine* e, const uint64_t* frame_ids, const float*
     DeviceGuard g(e->device);
     WriteGuard w(e->lock);
     sync_shard_work(e);
-    mirror_note_append(e);
-    e->batch.mirror_wanted = 0;
+    e->derived.appended();
     const size_t row_bytes = (size_t)e->dims * sizeof(float);
     if (n == 1) {
         // add(frameId:vector:) (:330-357): no device call at all on the common paths — the row goes to the staging
@@ -175,7 +174,7 @@ int wax_hip_add_batch(wax_hip_engine* e, const uint64_t* frame_ids, const float*
                 HIP_TRY(hipMemcpy(e->d_store + (uint64_t)existing * e->dims, rows, row_bytes, hipMemcpyHostToDevice),
                         WAX_HIP_ERR_INTERNAL, "vector upload");
             }
-            mirror_note_upsert(e, (uint64_t)existing);
+            e->derived.overwritten((uint64_t)existing);
             return WAX_HIP_OK;
         }
         int rc1 = reserve_rows(e, e->count + 1);             // :341 (flushes before it reallocates)
@@ -222,7 +221,7 @@ int wax_hip_add_batch(wax_hip_engine* e, const uint64_t* frame_ids, const float*
             if ((rc = flush()) != WAX_HIP_OK) return rc;
             HIP_TRY(hipMemcpy(e->d_store + (uint64_t)existing * e->dims, rows + i * e->dims, row_bytes,
                               hipMemcpyHostToDevice), WAX_HIP_ERR_INTERNAL, "vector upload");
-            mirror_note_upsert(e, (uint64_t)existing);
+            e->derived.overwritten((uint64_t)existing);
         } else {
             if (run_len == 0) run_start = i;
             e->idmap.put(frame_ids[i], (uint32_t)e->count);
@@ -248,8 +247,7 @@ int wax_hip_add_batch_device(wax_hip_engine* e, const uint64_t* frame_ids, const
     DeviceGuard g(e->device);
     WriteGuard w(e->lock);
     sync_shard_work(e);
-    mirror_note_append(e);
-    e->batch.mirror_wanted = 0;
+    e->derived.appended();
     { const int frc = flush_pending(e); if (frc != WAX_HIP_OK) return frc; }
     for (uint64_t i = 0; i < n; ++i)
         if (e->idmap.find(frame_ids[i]) >= 0)
@@ -329,7 +327,6 @@ int wax_hip_remove(wax_hip_engine* e, uint64_t frame_id) {
     if (e->count == 0) return WAX_HIP_OK;                 // :425
     const int64_t idx = e->idmap.find(frame_id);
     if (idx < 0) return WAX_HIP_OK;                       // :426
-    e->batch.mirror_wanted = 0;
     { const int frc = flush_pending(e); if (frc != WAX_HIP_OK) return frc; }   // the shift below works on device rows
     const uint64_t after = e->count - 1 - (uint64_t)idx;  // :431
     if (after > 0) {
@@ -344,7 +341,9 @@ int wax_hip_remove(wax_hip_engine* e, uint64_t frame_id) {
     }
     // the mirror's tail follows the store's; if it cannot, the store has moved all the same: the mirror is converted again at its next
     // use and the host bookkeeping below still runs (returning here would leave ids / count describing the store before the shift)
-    if (mirror_note_remove(e, (uint64_t)idx) != WAX_HIP_OK) { (void)hipGetLastError(); mirror_note_lost(e); }
+    const bool followed = mirror_follow_remove(e, (uint64_t)idx) == WAX_HIP_OK;
+    if (!followed) (void)hipGetLastError();
+    e->derived.removed((uint64_t)idx, followed);
     const bool repeated_ids = e->idmap.size() != e->count;   // only deserialize can put a frame id into several rows
     e->ids.erase(e->ids.begin() + idx);                   // :440
     e->cols.remove_row((uint64_t)idx);                    // the row's entries in the per-row columns go with its id
@@ -387,7 +386,6 @@ int wax_hip_remove_batch(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t 
             rem.erase(std::unique(rem.begin(), rem.end()), rem.end());   // an id listed twice counts once
             if (rem.empty()) return WAX_HIP_OK;
             const uint64_t m = rem.size();
-            e->batch.mirror_wanted = 0;
             BatchMirror& b = e->batch;
             const bool moves = rem[0] + m < e->count;          // false: the removed rows are the store's tail, nothing moves
             uint32_t* d_rem = nullptr;
@@ -399,17 +397,17 @@ int wax_hip_remove_batch(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t 
                 HIP_TRY(hipMalloc(&d_rem, (size_t)m * sizeof(uint32_t)), WAX_HIP_ERR_ALLOC, "Failed to allocate the removed-row list");
                 hipError_t err = hipMemcpy(d_rem, rem.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice);
                 if (err != hipSuccess) { (void)hipFree(d_rem); return fail(WAX_HIP_ERR_INTERNAL, std::string("removed-row list upload: ") + hipGetErrorString(err)); }
-                follow = !b.stale && b.d_cb != nullptr && rem[0] < b.rows;
+                follow = e->derived.bf16.holds(rem[0]);               // (a fill that holds a row has its buffer: mirror_follow_remove)
                 if (b.ev_pending) { (void)hipEventSynchronize(b.ev_ready); b.ev_pending = false; }   // a conversion in flight reads the store and writes the mirror
                 // ---- the device pass ----
-                const int rc = compact_removed_rows(e, rem, d_rem, follow ? b.rows.load() : 0, &written);
+                const int rc = compact_removed_rows(e, rem, d_rem, follow ? e->derived.bf16.rows() : 0, &written);
                 (void)hipFree(d_rem);
-                if (rc != WAX_HIP_OK) { (void)hipGetLastError(); mirror_note_lost(e); return rc; }   // (a failed launch or copy: as in remove, the rows behind rem[0] are lost with it)
+                if (rc != WAX_HIP_OK) { (void)hipGetLastError(); e->derived.lost(); return rc; }   // (a failed launch or copy: as in remove, the rows behind rem[0] are lost with it)
             } else {
                 follow = true;                                 // the mirror's tail is simply cut off with the store's
             }
             // ---- host bookkeeping, committed after the device pass has completed ----
-            mirror_note_remove_batch(e, rem, follow);
+            e->derived.removed(rem.data(), rem.size(), follow);
             for (uint32_t r : rem) e->idmap.erase_only(e->ids[r]);
             e->idmap.renumber_removed(rem, e->count);
             {

@@ -7,48 +7,20 @@
 // Rows the next ensure_mirror would convert (a planning figure: read without the mirror's mutex).
 static double mirror_rows_to_convert(wax_hip_engine* e) {
     const BatchMirror& b = e->batch;
-    if (b.mirror_valid.load(std::memory_order_acquire)) return 0.0;
-    if (b.stale.load() || b.d_cb == nullptr || b.mirror_cap < e->capacity) return (double)e->count;
-    const uint64_t cnt = e->count, rows = b.rows.load();
-    return (double)(cnt > rows ? cnt - rows : 0) + (double)b.n_dirty.load();
+    if (e->derived.bf16.current()) return 0.0;
+    if (b.d_cb == nullptr || b.mirror_cap < e->capacity) return (double)e->count;
+    return (double)e->derived.bf16.pending(e->count);
 }
 
-// The 8-bit code mirror's two hooks (exclusive engine lock held): an append leaves rows [rows8, count) to convert; everything else
-// starts it over. Either way the count of queries that wanted a rebuild starts again.
-static void c8_note_append(wax_hip_engine* e) { e->batch.c8_valid = false; e->batch.c8_wanted = 0; }
-static void c8_note_stale(wax_hip_engine* e) { e->batch.c8_valid = false; e->batch.c8_stale = true; e->batch.c8_wanted = 0; }
-
-// Mutation hooks of the bf16 mirror and the id -> row table (exclusive engine lock held).
-static void mirror_note_upsert(wax_hip_engine* e, uint64_t row) {
+// remove(frameId:) moved store rows (idx, count) down by one (MetalVectorEngine.swift:431-438): where the mirror holds row idx its tail
+// follows (half the bytes of the store's own move). Device work only, called BEFORE count is decremented; anything but WAX_HIP_OK = the
+// mirror could not follow. (A fill that holds a row has a buffer: the fill only leaves its restart in ensure_mirror, behind the
+// allocation for a capacity of at least count rows, and d_cb is only ever replaced by a larger buffer.)
+static int mirror_follow_remove(wax_hip_engine* e, uint64_t idx) {
     BatchMirror& b = e->batch;
-    c8_note_stale(e);
-    b.mirror_valid = false;
-    if (b.stale || row >= b.rows) return;                    // not mirrored yet: converted with the appended range
-    if (b.dirty.size() >= kMirrorMaxDirty) { b.stale = true; b.dirty.clear(); b.n_dirty = 0; return; }
-    b.dirty.push_back((uint32_t)row);
-    b.n_dirty = b.dirty.size();
-}
-static void mirror_note_append(wax_hip_engine* e) { e->batch.mirror_valid = false; e->idhash.valid = false; c8_note_append(e); }
-static void mirror_note_replaced(wax_hip_engine* e) {       // deserialize: every row is new
-    e->batch.mirror_valid = false; e->batch.stale = true; e->batch.dirty.clear(); e->batch.n_dirty = 0; e->batch.rows = 0;
-    e->idhash.valid = false; e->idhash.stale = true; e->idhash.rows = 0;
-    c8_note_stale(e);
-}
-// a mutation the mirror could not follow (a failed row shift): convert everything at the next use
-static void mirror_note_lost(wax_hip_engine* e) {
-    c8_note_stale(e);
-    e->batch.mirror_valid = false; e->batch.stale = true; e->batch.dirty.clear(); e->batch.n_dirty = 0;
-}
-// remove(frameId:) moved store rows (idx, count) down by one (MetalVectorEngine.swift:431-438): the mirror's tail follows (half the
-// bytes of the store's own move), and the listed dirty rows move with it. Called BEFORE count is decremented.
-static int mirror_note_remove(wax_hip_engine* e, uint64_t idx) {
-    BatchMirror& b = e->batch;
-    e->idhash.valid = false; e->idhash.stale = true; e->idhash.rows = 0;     // every later row changed its number
-    c8_note_stale(e);
-    b.mirror_valid = false;
-    if (b.stale || b.d_cb == nullptr || idx >= b.rows) return WAX_HIP_OK;
+    if (!e->derived.bf16.holds(idx)) return WAX_HIP_OK;
     if (b.ev_pending) { (void)hipEventSynchronize(b.ev_ready); b.ev_pending = false; }
-    const uint64_t after = b.rows - 1 - idx;
+    const uint64_t after = e->derived.bf16.rows() - 1 - idx;
     if (after > 0) {
         if (!e->d_bounce)
             HIP_TRY(hipMalloc(&e->d_bounce, kBounceBytes), WAX_HIP_ERR_ALLOC, "Failed to allocate bounce buffer");
@@ -57,15 +29,6 @@ static int mirror_note_remove(wax_hip_engine* e, uint64_t idx) {
         HIP_TRY(device_shift_down(b.d_vn2, idx * 4, (idx + 1) * 4, after * 4, e->d_bounce, kBounceBytes, nullptr), WAX_HIP_ERR_INTERNAL, "mirror norm shift");
         HIP_TRY(hipStreamSynchronize(nullptr), WAX_HIP_ERR_INTERNAL, "mirror shift sync");
     }
-    b.rows -= 1;
-    size_t w = 0;
-    for (size_t i = 0; i < b.dirty.size(); ++i) {
-        const uint32_t r = b.dirty[i];
-        if (r == idx) continue;
-        b.dirty[w++] = r > idx ? r - 1 : r;
-    }
-    b.dirty.resize(w);
-    b.n_dirty = w;
     return WAX_HIP_OK;
 }
 
@@ -147,33 +110,13 @@ static int compact_removed_rows(wax_hip_engine* e, const std::vector<uint32_t>& 
     return WAX_HIP_OK;
 }
 
-// ... and the mirror's / id table's bookkeeping for it, what mirror_note_remove does for one row (`followed`: the mirror's rows were
-// compacted with the store's)
-static void mirror_note_remove_batch(wax_hip_engine* e, const std::vector<uint32_t>& rem, bool followed) {
-    BatchMirror& b = e->batch;
-    e->idhash.valid = false; e->idhash.stale = true; e->idhash.rows = 0;
-    c8_note_stale(e);
-    b.mirror_valid = false;
-    if (b.stale || b.d_cb == nullptr || rem[0] >= b.rows) return;    // nothing mirrored moved
-    if (!followed) { mirror_note_lost(e); return; }
-    auto rank = [&](uint64_t r) { return (uint64_t)(std::lower_bound(rem.begin(), rem.end(), (uint32_t)std::min<uint64_t>(r, 0xffffffffull)) - rem.begin()); };
-    b.rows -= rank(b.rows);
-    size_t w = 0;
-    for (size_t i = 0; i < b.dirty.size(); ++i) {
-        const uint32_t r = b.dirty[i];
-        if (std::binary_search(rem.begin(), rem.end(), r)) continue;
-        b.dirty[w++] = r - (uint32_t)rank(r);
-    }
-    b.dirty.resize(w);
-    b.n_dirty = w;
-}
-
 // The bf16 mirror of the store (+ ||v||^2, max ||v||, max rounding error): allocated at the first batched search, then kept in step
 // with the store incrementally — see BatchMirror. Concurrent batches serialise on the conversion's ENQUEUE only: nothing here waits
 // for the device (the converting stream records an event that every other workspace's stream waits for).
 int ensure_mirror(wax_hip_engine* e, hipStream_t st) {
     BatchMirror& b = e->batch;
-    if (b.mirror_valid.load(std::memory_order_acquire) && b.mirror_cap >= e->capacity) {
+    DirtyRowFill& fill = e->derived.bf16;
+    if (fill.current() && b.mirror_cap >= e->capacity) {
         // converted, but perhaps still in flight on another workspace's stream
         std::unique_lock<std::mutex> g(b.mu);
         if (b.ev_pending) {
@@ -188,7 +131,6 @@ int ensure_mirror(wax_hip_engine* e, hipStream_t st) {
         HIP_TRY(hipMalloc(&b.d_maxnorm, 2 * sizeof(unsigned int)), WAX_HIP_ERR_ALLOC, "Failed to allocate batch scalars");
         HIP_TRY(hipMalloc(&b.d_dirty, kMirrorMaxDirty * sizeof(uint32_t)), WAX_HIP_ERR_ALLOC, "Failed to allocate batch scalars");
         HIP_TRY(hipEventCreateWithFlags(&b.ev_ready, hipEventDisableTiming), WAX_HIP_ERR_INTERNAL, "event create");
-        b.stale = true;
     }
     if (b.ev_pending) HIP_TRY(hipStreamWaitEvent(st, b.ev_ready, 0), WAX_HIP_ERR_INTERNAL, "mirror ready wait");   // order behind the previous conversion
     if (b.mirror_cap < e->capacity) {
@@ -201,50 +143,48 @@ int ensure_mirror(wax_hip_engine* e, hipStream_t st) {
         HIP_TRY(hipMalloc(&ncb, ((size_t)e->capacity + BATCH_MIRROR_SLACK_ROWS) * D * sizeof(unsigned short)), WAX_HIP_ERR_ALLOC, "Failed to allocate bf16 mirror");
         if (hipMalloc(&nvn, (size_t)e->capacity * sizeof(float)) != hipSuccess) { (void)hipFree(ncb); return fail(WAX_HIP_ERR_ALLOC, "Failed to allocate row norms"); }
         hipError_t err = hipMemsetAsync(ncb + (size_t)e->capacity * D, 0, (size_t)BATCH_MIRROR_SLACK_ROWS * D * sizeof(unsigned short), st);
-        if (err == hipSuccess && !b.stale && b.rows > 0 && b.d_cb) {
-            err = hipMemcpyAsync(ncb, b.d_cb, (size_t)b.rows * D * sizeof(unsigned short), hipMemcpyDeviceToDevice, st);
-            if (err == hipSuccess) err = hipMemcpyAsync(nvn, b.d_vn2, (size_t)b.rows * sizeof(float), hipMemcpyDeviceToDevice, st);
+        const uint64_t kept = fill.restarting() ? 0 : fill.rows();
+        if (err == hipSuccess && kept > 0 && b.d_cb) {
+            err = hipMemcpyAsync(ncb, b.d_cb, (size_t)kept * D * sizeof(unsigned short), hipMemcpyDeviceToDevice, st);
+            if (err == hipSuccess) err = hipMemcpyAsync(nvn, b.d_vn2, (size_t)kept * sizeof(float), hipMemcpyDeviceToDevice, st);
             if (err == hipSuccess) err = hipStreamSynchronize(st);                     // the old buffers are freed next
         } else {
-            b.stale = true;
+            fill.restart();
         }
         if (err != hipSuccess) { (void)hipFree(ncb); (void)hipFree(nvn); return fail(WAX_HIP_ERR_INTERNAL, std::string("mirror move: ") + hipGetErrorString(err)); }
         (void)hipFree(b.d_cb); (void)hipFree(b.d_vn2);
         b.d_cb = ncb; b.d_vn2 = nvn; b.mirror_cap = e->capacity;
     }
     const uint64_t count = e->count;
-    if (b.stale) {
-        b.rows = 0; b.dirty.clear(); b.n_dirty = 0; b.stale = false;
-        HIP_TRY(hipMemsetAsync(b.d_maxnorm, 0, 2 * sizeof(unsigned int), st), WAX_HIP_ERR_INTERNAL, "batch memset");
-    }
-    if (b.rows > count) b.rows = count;                       // (cannot happen: removals move `rows` with them)
+    const RowFill::Build build = fill.begin(count);
+    if (build.scratch) HIP_TRY(hipMemsetAsync(b.d_maxnorm, 0, 2 * sizeof(unsigned int), st), WAX_HIP_ERR_INTERNAL, "batch memset");
     const int normalize = e->metric == WAX_HIP_METRIC_COSINE ? 1 : 0;
     uint64_t converted = 0;
-    if (b.rows < count) {                                     // appended since: rows [rows, count)
-        const uint64_t n_new = count - b.rows;
-        HIP_TRY(launch_mirror(e->d_store + b.rows * D, (uint32_t)n_new, (uint32_t)n_new, D, normalize, b.d_cb + b.rows * D, b.d_vn2 + b.rows,
+    if (build.from < count) {                                 // appended since: rows [from, count)
+        const uint64_t n_new = count - build.from;
+        HIP_TRY(launch_mirror(e->d_store + build.from * D, (uint32_t)n_new, (uint32_t)n_new, D, normalize, b.d_cb + build.from * D, b.d_vn2 + build.from,
                               b.d_maxnorm, st), WAX_HIP_ERR_INTERNAL, "mirror kernel launch");
         converted += n_new;
-        b.rows = count;
     }
-    if (!b.dirty.empty()) {                                   // overwritten since: the listed rows
-        std::sort(b.dirty.begin(), b.dirty.end());
-        b.dirty.erase(std::unique(b.dirty.begin(), b.dirty.end()), b.dirty.end());
-        HIP_TRY(hipMemcpyAsync(b.d_dirty, b.dirty.data(), b.dirty.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st), WAX_HIP_ERR_INTERNAL, "dirty row list upload");
-        HIP_TRY(hipStreamSynchronize(st), WAX_HIP_ERR_INTERNAL, "dirty row list upload");   // (pageable source: the vector is cleared next; a rare path)
-        HIP_TRY(launch_mirror_rows(e->d_store, b.d_dirty, (uint32_t)b.dirty.size(), D, normalize, b.d_cb, b.d_vn2, b.d_maxnorm, st),
-                WAX_HIP_ERR_INTERNAL, "mirror kernel launch");
-        converted += b.dirty.size();
-        b.dirty.clear();
-        b.n_dirty = 0;
+    const std::vector<uint32_t> dirty = fill.take_dirty();    // overwritten since: the listed rows
+    hipError_t err = hipSuccess;
+    if (!dirty.empty()) {
+        err = hipMemcpyAsync(b.d_dirty, dirty.data(), dirty.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+        if (err == hipSuccess) err = hipStreamSynchronize(st);                         // (pageable source: the vector goes next; a rare path)
+        if (err == hipSuccess) err = launch_mirror_rows(e->d_store, b.d_dirty, (uint32_t)dirty.size(), D, normalize, b.d_cb, b.d_vn2, b.d_maxnorm, st);
+        converted += dirty.size();
+    }
+    if (err == hipSuccess && converted) err = hipEventRecord(b.ev_ready, st);
+    if (err != hipSuccess) {                                  // the list is taken: what it named is converted with everything else
+        fill.restart();
+        return fail(WAX_HIP_ERR_INTERNAL, std::string("mirror conversion: ") + hipGetErrorString(err));
     }
     if (converted) {
-        HIP_TRY(hipEventRecord(b.ev_ready, st), WAX_HIP_ERR_INTERNAL, "mirror ready record");
         b.ev_pending = true;
         b.rows_converted += converted;
         b.conversions += 1;
     }
-    b.mirror_valid.store(true, std::memory_order_release);
+    fill.settle(count);
     return WAX_HIP_OK;
 }
 
@@ -253,8 +193,9 @@ int ensure_mirror(wax_hip_engine* e, hipStream_t st) {
 // the device: the converting stream records ev8_ready, every other slot's stream waits for it.
 int ensure_mirror8(wax_hip_engine* e, hipStream_t st) {
     BatchMirror& b = e->batch;
+    RowFill& fill = e->derived.codes;
     std::unique_lock<std::mutex> g(b.mu8);
-    if (b.c8_valid.load(std::memory_order_acquire) && b.c8_cap >= e->capacity) {
+    if (fill.current() && b.c8_cap >= e->capacity) {
         if (b.ev8_pending) {
             if (hipEventQuery(b.ev8_ready) == hipSuccess) b.ev8_pending = false;
             else HIP_TRY(hipStreamWaitEvent(st, b.ev8_ready, 0), WAX_HIP_ERR_INTERNAL, "code mirror ready wait");
@@ -262,10 +203,7 @@ int ensure_mirror8(wax_hip_engine* e, hipStream_t st) {
         return WAX_HIP_OK;
     }
     const uint32_t D = e->dims;
-    if (!b.d_c8_max) {
-        HIP_TRY(hipMalloc(&b.d_c8_max, sizeof(unsigned int)), WAX_HIP_ERR_ALLOC, "Failed to allocate code mirror scalars");
-        b.c8_stale = true;
-    }
+    if (!b.d_c8_max) HIP_TRY(hipMalloc(&b.d_c8_max, sizeof(unsigned int)), WAX_HIP_ERR_ALLOC, "Failed to allocate code mirror scalars");
     if (!b.ev8_ready) HIP_TRY(hipEventCreateWithFlags(&b.ev8_ready, hipEventDisableTiming), WAX_HIP_ERR_INTERNAL, "event create");
     if (b.ev8_pending) HIP_TRY(hipStreamWaitEvent(st, b.ev8_ready, 0), WAX_HIP_ERR_INTERNAL, "code mirror ready wait");
     if (b.c8_cap < e->capacity || b.d_c8 == nullptr) {
@@ -273,31 +211,28 @@ int ensure_mirror8(wax_hip_engine* e, hipStream_t st) {
         // exclusive lock); the codes do not move over, they are converted again
         if (b.ev8_pending) { (void)hipEventSynchronize(b.ev8_ready); b.ev8_pending = false; }
         (void)hipFree(b.d_c8); (void)hipFree(b.d_c8_meta);
-        b.d_c8 = nullptr; b.d_c8_meta = nullptr; b.c8_cap = 0; b.c8_stale = true;
+        b.d_c8 = nullptr; b.d_c8_meta = nullptr; b.c8_cap = 0;
+        fill.restart();
         unsigned char* nc = nullptr; float* nm = nullptr;
         HIP_TRY(hipMalloc(&nc, mirror8_bytes(e->capacity, D)), WAX_HIP_ERR_ALLOC, "Failed to allocate code mirror");   // whole tiles
         if (hipMalloc(&nm, (size_t)e->capacity * 2 * sizeof(float)) != hipSuccess) { (void)hipFree(nc); return fail(WAX_HIP_ERR_ALLOC, "Failed to allocate code mirror row words"); }
         b.d_c8 = nc; b.d_c8_meta = nm; b.c8_cap = e->capacity;
     }
     const uint64_t count = e->count;
-    if (b.c8_stale) {
-        b.rows8 = 0; b.c8_stale = false;
-        HIP_TRY(hipMemsetAsync(b.d_c8_max, 0, sizeof(unsigned int), st), WAX_HIP_ERR_INTERNAL, "code mirror memset");
-    }
-    if (b.rows8 > count) b.rows8 = count;
-    if (b.rows8 < count) {
-        const uint64_t first = b.rows8, n_new = count - first;
+    const RowFill::Build build = fill.begin(count);
+    if (build.scratch) HIP_TRY(hipMemsetAsync(b.d_c8_max, 0, sizeof(unsigned int), st), WAX_HIP_ERR_INTERNAL, "code mirror memset");
+    if (build.from < count) {
+        const uint64_t n_new = count - build.from;
         // the bases and the first row: the range may begin inside a tile (mirror8_layout.h)
-        const hipError_t err = launch_mirror8_build(e->d_store, first, (uint32_t)n_new, D, e->metric == WAX_HIP_METRIC_COSINE ? 1 : 0,
+        const hipError_t err = launch_mirror8_build(e->d_store, build.from, (uint32_t)n_new, D, e->metric == WAX_HIP_METRIC_COSINE ? 1 : 0,
                                                     b.d_c8, b.d_c8_meta, b.d_c8_max, st);
-        if (err != hipSuccess) { b.c8_stale = true; return fail(WAX_HIP_ERR_INTERNAL, std::string("code mirror kernel launch: ") + hipGetErrorString(err)); }
+        if (err != hipSuccess) { fill.restart(); return fail(WAX_HIP_ERR_INTERNAL, std::string("code mirror kernel launch: ") + hipGetErrorString(err)); }
         HIP_TRY(hipEventRecord(b.ev8_ready, st), WAX_HIP_ERR_INTERNAL, "code mirror ready record");
         b.ev8_pending = true;
-        b.rows8 = count;
         b.rows8_converted += n_new;
         b.conversions8 += 1;
     }
-    b.c8_valid.store(true, std::memory_order_release);
+    fill.settle(count);
     return WAX_HIP_OK;
 }
 
@@ -453,27 +388,26 @@ static void release_filter_work(wax_hip_engine* e, FilterWork* f) {
 // serialise on the rebuild only.
 static int ensure_idhash(wax_hip_engine* e, hipStream_t st) {
     IdHash& h = e->idhash;
-    if (h.valid.load(std::memory_order_acquire)) return WAX_HIP_OK;
+    RowFill& fill = e->derived.idtable;
+    if (fill.current()) return WAX_HIP_OK;
     std::unique_lock<std::mutex> g(h.mu);
-    if (h.valid.load(std::memory_order_acquire)) return WAX_HIP_OK;
+    if (fill.current()) return WAX_HIP_OK;
     uint64_t want = 1024;
     while (want < 2 * e->count) want *= 2;   // load factor <= 0.5
     if (h.slots < want) {
         (void)hipFree(h.d_table);
         h.d_table = nullptr; h.slots = 0;
+        fill.restart();
         want *= 2;                                // room for the appends to come: a table that must grow is rebuilt from row 0
         HIP_TRY(hipMalloc(&h.d_table, (size_t)want * sizeof(uint32_t)), WAX_HIP_ERR_ALLOC, "Failed to allocate id table");
         h.slots = want;
-        h.stale = true;
     }
-    if (h.stale) { h.rows = 0; h.stale = false; }
-    if (h.rows > e->count) { h.rows = 0; }        // (cannot happen: removals start the table over)
-    // rows [h.rows, count): all of them after a removal / deserialize / growth (the table is cleared first), the appended ones otherwise
-    HIP_TRY(launch_idhash_build(e->d_ids, (uint32_t)h.rows, (uint32_t)e->count, h.d_table, h.slots, st), WAX_HIP_ERR_INTERNAL, "id table kernel launch");
+    // rows [from, count): all of them after a removal / deserialize / growth (row 0 has the kernel clear the table first), the appended ones otherwise
+    const uint64_t from = fill.begin(e->count).from;
+    HIP_TRY(launch_idhash_build(e->d_ids, (uint32_t)from, (uint32_t)e->count, h.d_table, h.slots, st), WAX_HIP_ERR_INTERNAL, "id table kernel launch");
     HIP_TRY(hipStreamSynchronize(st), WAX_HIP_ERR_INTERNAL, "id table build failed on device");
-    e->st_idhash_rows += e->count - h.rows;
-    h.rows = e->count;
-    h.valid.store(true, std::memory_order_release);
+    e->st_idhash_rows += e->count - from;
+    fill.settle(e->count);
     return WAX_HIP_OK;
 }
 

@@ -51,9 +51,8 @@ int wax_hip_deserialize(wax_hip_engine* e, const uint8_t* data, size_t len) {
     DeviceGuard g(e->device);
     WriteGuard w(e->lock);  // withWriteLock (:717)
     sync_shard_work(e);
-    mirror_note_replaced(e);
+    e->derived.replaced();
     e->cols.clear();          // MV2V has no field for any per-row column: every row of the loaded store holds the defaults
-    e->batch.mirror_wanted = 0;
     e->pend_rows.store(0, std::memory_order_release);   // the store is replaced wholesale: staged appends are dropped with it
     // :790-792 — capacity only grows
     int rc = resize_store(e, n > e->capacity ? n : e->capacity);

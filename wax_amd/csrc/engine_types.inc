@@ -310,17 +310,13 @@ struct FilterWork {
 
 void free_filter_work(FilterWork* f);
 
-// id -> row table in HBM (filter.hip): built at the first long allow-list, rebuilt lazily after a mutation.
+// id -> row table in HBM (filter.hip): built at the first long allow-list, brought up to date lazily after a mutation. How far it has
+// followed the store is DerivedRows::idtable (derived_rows.h): appends insert rows [rows, count), a removal or a deserialize starts it
+// over (like the reference's firstIndex(of:) scan they are O(N) anyway).
 struct IdHash {
     std::mutex mu;                   // serialises the (re)build only
     uint32_t* d_table = nullptr;
     uint64_t slots = 0;
-    std::atomic<bool> valid{false};  // the table holds exactly rows [0, count)
-    // Round 6: appends do not discard the table — rows [rows, count) are inserted by the next long allow-list (an upsert keeps id -> row;
-    // a removal shifts every later row and a deserialize replaces them all: those start over, like the reference's firstIndex(of:) scan
-    // they are O(N) anyway).
-    uint64_t rows = 0;               // rows [0, rows) are in the table (guarded by mu / the exclusive engine lock)
-    bool stale = true;               // the table must be rebuilt from row 0
 };
 
 // Batched (bf16 MFMA) path. The corpus mirror is shared by every batch (read-only during searches, rebuilt lazily by
@@ -332,44 +328,31 @@ struct BatchMirror {
     float* d_vn2 = nullptr;              // [mirror_cap] ||v||^2
     unsigned int* d_maxnorm = nullptr;
     uint64_t mirror_cap = 0;
-    std::atomic<bool> mirror_valid{false};   // fast path: nothing to convert (rows == count, no dirty row, not stale, large enough)
-    // Round 6: a mutation no longer throws the mirror away (rounds 1-5 re-converted the WHOLE store after any add / remove: 30.7 GB read
-    // + 15.4 GB written and a blocking sync at 10M x 768, per mutation, on an ingest-while-serving workload — the reference's add is one
-    // row copy, MetalVectorEngine.swift:330-357). Appends leave rows [rows, count) to convert; an upsert lists its row in `dirty`; a
-    // removal moves the mirror's tail down like the store's (:431-438); only reallocation and deserialize convert everything again.
+    // A mutation does not throw the mirror away (re-converting the WHOLE store after any add / remove is 30.7 GB read + 15.4 GB written
+    // and a blocking sync at 10M x 768, per mutation, on an ingest-while-serving workload — the reference's add is one row copy,
+    // MetalVectorEngine.swift:330-357): what each mutation leaves to convert is DerivedRows::bf16 (derived_rows.h); only reallocation
+    // without the old contents and deserialize convert everything again.
     // max ||v|| and max ||x - bf16(x)|| stay on the device (d_maxnorm, read there by the prep kernel) and only ever grow between full
     // conversions: a bound that is too large by a row that has since been overwritten or removed is still a bound.
-    // Writers hold the exclusive engine lock; ensure_mirror holds `mu` under the shared one.
-    // `rows`, `stale` and `n_dirty` are atomics: mirror_rows_to_convert reads them without `mu` (a planning figure, now read by
-    // every large single query as well as by batches)
-    std::atomic<uint64_t> rows{0};       // rows [0, rows) of the mirror match the store, except `dirty`
-    std::vector<uint32_t> dirty;         // rows < `rows` overwritten since (upserts); more than kMirrorMaxDirty of them = stale
-    std::atomic<uint64_t> n_dirty{0};    // dirty.size(), kept beside it
-    std::atomic<bool> stale{true};       // convert everything again
-    uint32_t* d_dirty = nullptr;         // device copy of `dirty` for the listed-rows conversion
+    uint32_t* d_dirty = nullptr;         // [kMirrorMaxDirty] the overwritten rows of a listed-rows conversion
     hipEvent_t ev_ready = nullptr;       // recorded behind the last conversion: other workspaces' streams wait for it
     bool ev_pending = false;
     std::atomic<uint64_t> rows_converted{0}, conversions{0};   // statistics ("mirror_rows_converted" / "mirror_conversions")
-    std::atomic<int> mirror_wanted{0};   // small batches since the last mutation that a VALID mirror would have made cheaper    // The 8-bit code mirror of the single-query scan (mirror8_scan.hip; DESIGN 4.1): codes + 128 and {scale, err} per row, built from
-    // the f32 store. Maintenance is deliberately simpler than the bf16 mirror's: appends convert rows [rows8, count); every other
-    // mutation (upsert, remove, removeBatch, deserialize, reallocation) marks it stale as a whole, and a stale or missing code mirror
-    // is rebuilt only when three eligible queries in a row since the last mutation wanted it (c8_wanted) — until then they take bf16.
+    // The 8-bit code mirror of the single-query scan (mirror8_scan.hip; DESIGN 4.1): codes + 128 and {scale, err} per row, built from
+    // the f32 store. Maintenance is deliberately simpler than the bf16 mirror's (DerivedRows::codes): appends convert rows [rows, count);
+    // every other mutation and a reallocation start it over, and a code mirror that has to start over is rebuilt only when three
+    // eligible queries in a row since the last mutation wanted it — until then they take bf16.
     std::mutex mu8;                      // serialises the (re)build only
     unsigned char* d_c8 = nullptr;       // biased codes in 16-row tiles, MFMA operand order (mirror8_layout.h): ceil16(c8_cap) * dims bytes
     float* d_c8_meta = nullptr;          // [c8_cap] float2 {scale, err}
     unsigned int* d_c8_max = nullptr;    // one word: max ||v|| over the coded rows (grows between full conversions, like d_maxnorm)
     uint64_t c8_cap = 0;
-    std::atomic<uint64_t> rows8{0};      // rows [0, rows8) are coded
-    std::atomic<bool> c8_valid{false};   // fast path: nothing to convert
-    std::atomic<bool> c8_stale{true};    // convert everything again
     hipEvent_t ev8_ready = nullptr;      // recorded behind the last conversion: other slots' streams wait for it
     bool ev8_pending = false;
-    std::atomic<int> c8_wanted{0};       // eligible queries since the last mutation that found the code mirror stale or missing
     std::atomic<uint64_t> rows8_converted{0}, conversions8{0};   // "mirror8_rows_converted" / "mirror8_conversions"
 };
 
 constexpr int kBreakerWindow = 32, kBreakerFails = 8, kBreakerHold = 1024;   // "mirror_bits" breaker (wax_hip_engine::breaker_*)
-constexpr size_t kMirrorMaxDirty = 4096; // upserted rows remembered one by one; beyond that the mirror is converted again as a whole
 constexpr uint32_t kBatchMaxQ = 1024;   // queries per GEMM pass
 constexpr uint32_t kBatchSegBase = FUSED_MAX_K;   // slab pipeline: a candidate row = [0, kBatchSegBase) best list, then the survivor area
 constexpr uint32_t kBatchSegArea = 4096;          // survivors per query between two tighten passes (slab pipeline) / of the one pass
@@ -629,6 +612,9 @@ struct wax_hip_engine {
     // (wax_hip_set_terms; DESIGN 4.11), the group slots derived from the parents, and the marks of their device copies. Everything about
     // them that lives in host memory is in row_columns.h; writers change it under the exclusive engine lock.
     RowColumns cols;
+    // How far the bf16 mirror, the code mirror and the id table (`batch`, `idhash`) have followed the store: derived_rows.h. One call per
+    // mutation, under the exclusive engine lock.
+    DerivedRows derived;
     // Device copy of the attributes, [attr_cap] of each: the first predicate search after a change uploads from cols.attr_mark() on its
     // workspace stream (ensure_attrs, api_predicate.inc, under attr_mu and the shared engine lock).
     std::mutex attr_mu;

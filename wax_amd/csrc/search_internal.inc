@@ -287,8 +287,8 @@ static bool mirror8_take(wax_hip_engine* e, int k_eff) {
         if (e->breaker_hold > 0) { --e->breaker_hold; return false; }
     }
     BatchMirror& b = e->batch;
-    if (b.c8_cap >= e->capacity && b.d_c8 != nullptr && (b.c8_valid.load(std::memory_order_acquire) || !b.c8_stale.load())) return true;
-    return b.c8_wanted.fetch_add(1) >= 2;
+    if (b.c8_cap >= e->capacity && b.d_c8 != nullptr && (e->derived.codes.current() || !e->derived.codes.restarting())) return true;
+    return e->derived.codes.wanted();
 }
 
 // The certificate of a collected 8-bit query feeds the breaker: kBreakerFails uncertified among the last kBreakerWindow send the next

@@ -421,7 +421,7 @@ int sh_move_all(ShardedState* s, size_t from, size_t to) {
         dst->ids.resize((size_t)dst_before);
         dst->count = dst_before;
         dst->cols.truncate(dst_before);
-        mirror_note_replaced(dst);    // (rows were appended and taken back: the mirror and the id table start over)
+        dst->derived.replaced();    // (rows were appended and taken back: the mirror and the id table start over)
         return rc;
     }
     // the rows' attributes, parents and term sets travel with them: dst's columns are padded to where the moved rows begin, then take
@@ -432,7 +432,7 @@ int sh_move_all(ShardedState* s, size_t from, size_t to) {
     src->ids.clear();
     src->idmap.clear();
     src->pend_rows.store(0);
-    mirror_note_replaced(src);
+    src->derived.replaced();
     return WAX_HIP_OK;
 }
 

@@ -361,9 +361,9 @@ int wax_hip_mirror8_snapshot(wax_hip_engine* e, uint64_t first_row, uint64_t n_r
     ReadGuard rg(e);
     BatchMirror& b = e->batch;
     std::unique_lock<std::mutex> mg(b.mu8);
-    if (!b.c8_valid.load(std::memory_order_acquire) || b.d_c8 == nullptr || b.d_c8_meta == nullptr || b.d_c8_max == nullptr || b.c8_cap < e->capacity)
+    if (!e->derived.codes.current() || b.d_c8 == nullptr || b.d_c8_meta == nullptr || b.d_c8_max == nullptr || b.c8_cap < e->capacity)
         return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror8_snapshot: the code mirror is absent or not valid");
-    const uint64_t rows = b.rows8.load();
+    const uint64_t rows = e->derived.codes.rows();
     if (first_row > rows || n_rows > rows - first_row)
         return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror8_snapshot: rows [" + std::to_string(first_row) + ", " + std::to_string(first_row) + " + " +
                                                   std::to_string(n_rows) + ") exceed the " + std::to_string(rows) + " coded rows");
@@ -401,9 +401,9 @@ int wax_hip_mirror8_keys(wax_hip_engine* e, const float* query, float* out_keys,
     ReadGuard rg(e);
     BatchMirror& b = e->batch;
     std::unique_lock<std::mutex> mg(b.mu8);
-    if (!b.c8_valid.load(std::memory_order_acquire) || b.d_c8 == nullptr || b.d_c8_meta == nullptr || b.d_c8_max == nullptr || b.c8_cap < e->capacity)
+    if (!e->derived.codes.current() || b.d_c8 == nullptr || b.d_c8_meta == nullptr || b.d_c8_max == nullptr || b.c8_cap < e->capacity)
         return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror8_keys: the code mirror is absent or not valid");
-    const uint64_t rows = b.rows8.load();
+    const uint64_t rows = e->derived.codes.rows();
     if (rows == 0 || rows > e->count || n_keys != rows)
         return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror8_keys: out_keys holds " + std::to_string(n_keys) + " keys, the code mirror " + std::to_string(rows) + " rows");
     if (!mirror_scan_supported(e->dims, e->metric)) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "mirror8_keys: no 8-bit pass at this dimension and metric");
