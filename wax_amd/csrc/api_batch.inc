@@ -48,7 +48,7 @@ static int search_batch_hits_impl(wax_hip_engine* e, const float* queries, uint3
             if (batch_mfma_applicable(e, dims, (int)k64, nq, &plan, &onepass)) {
                 const int k_eff = (int)k64;
                 BatchCtx* c = nullptr;
-                brc = acquire_bctx(e, &c);
+                brc = take_bctx(e, &c);
                 if (brc != WAX_HIP_OK) return brc;
                 brc = ensure_mirror(e, c->stream);
                 if (brc == WAX_HIP_OK) brc = bctx_reserve_host(e, c, nq, (uint64_t)nq * k_eff);
@@ -86,7 +86,7 @@ static int search_batch_hits_impl(wax_hip_engine* e, const float* queries, uint3
                 } else {
                     (void)hipStreamSynchronize(c->stream);
                 }
-                release_bctx(e, c);
+                e->bctxs.release(c);
             }
         }
         if (brc != WAX_HIP_OK) return brc;
@@ -110,7 +110,7 @@ static int search_batch_hits_impl(wax_hip_engine* e, const float* queries, uint3
             if (k64 > 0 && k64 <= (uint64_t)FUSED_MAX_K && scan_multi_group(dims, (int)k64) >= 2) {
                 const int k_eff = (int)k64;
                 BatchCtx* c = nullptr;
-                brc = acquire_bctx(e, &c);
+                brc = take_bctx(e, &c);
                 if (brc != WAX_HIP_OK) return brc;
                 brc = bctx_reserve_host(e, c, nq, (uint64_t)nq * k_eff);
                 if (brc == WAX_HIP_OK) {
@@ -142,7 +142,7 @@ static int search_batch_hits_impl(wax_hip_engine* e, const float* queries, uint3
                 } else {
                     (void)hipStreamSynchronize(c->stream);
                 }
-                release_bctx(e, c);
+                e->bctxs.release(c);
             }
         }
         if (brc != WAX_HIP_OK) return brc;
@@ -151,7 +151,7 @@ static int search_batch_hits_impl(wax_hip_engine* e, const float* queries, uint3
     // Loop path: pipelined single-query scans over the scratch-slot pool.
     std::vector<uint32_t> todo(nq);
     for (uint32_t q = 0; q < nq; ++q) todo[q] = q;
-    const uint32_t depth = (uint32_t)(e->max_slots > 1 ? e->max_slots : 1);
+    const uint32_t depth = (uint32_t)std::max(e->slots.cap(), 1);
     std::vector<uint64_t> tk(todo.size(), 0);
     size_t submitted = 0, collected = 0;
     int rc = WAX_HIP_OK;
@@ -247,10 +247,7 @@ static int batch_device_impl(wax_hip_engine* e, const float* d_queries, uint32_t
     bool keep_lock = false;   // a pending ticket keeps the shared lock until its collect
     struct Unlock { RWLock& l; bool& keep; ~Unlock() { if (!keep) l.unlock_shared(); } } unlock{e->lock, keep_lock};
     auto done_ticket = [&]() {   // answered (or nothing to do) at submit time: a ticket whose collect is a no-op
-        if (!ticket) return;
-        std::unique_lock<std::mutex> tg(e->bticket_mu);
-        *ticket = e->next_bticket++;
-        e->btickets[*ticket] = wax_hip_engine::BatchTicket{};
+        if (ticket) *ticket = e->btickets.put(wax_hip_engine::BatchTicket{});
     };
     if (nq == 0) { done_ticket(); return WAX_HIP_OK; }
     { const int frc = flush_pending(e); if (frc != WAX_HIP_OK) return frc; }
@@ -260,10 +257,10 @@ static int batch_device_impl(wax_hip_engine* e, const float* d_queries, uint32_t
     if (k64 > out_stride) k64 = out_stride;
     const int k_eff = (int)k64;
     BatchCtx* c = nullptr;
-    int rc = acquire_bctx(e, &c, /*try_only=*/ticket != nullptr && holder);
+    int rc = take_bctx(e, &c, /*try_only=*/ticket != nullptr && holder);
     if (rc != WAX_HIP_OK) return rc;
     bool keep_ctx = false;
-    struct Release { wax_hip_engine* e; BatchCtx* c; bool& keep; ~Release() { if (!keep) release_bctx(e, c); } } release{e, c, keep_ctx};
+    struct Release { wax_hip_engine* e; BatchCtx* c; bool& keep; ~Release() { if (!keep) e->bctxs.release(c); } } release{e, c, keep_ctx};
     hipStream_t st = c->stream;
     // inputs are produced on the caller's stream: the workspace's stream waits for what is pending there. A caller stream
     // that has already drained (the usual blocking caller) needs no marker packet on it and no barrier packet in front
@@ -300,12 +297,8 @@ static int batch_device_impl(wax_hip_engine* e, const float* d_queries, uint32_t
         if (rc != WAX_HIP_OK) return rc;
         wax_hip_engine::BatchTicket t;
         t.c = c; t.d_queries = d_queries; t.d_out = d_out_hits; t.nq = nq; t.out_stride = out_stride; t.k_eff = k_eff;
-        note_submit_id(e, &t.owner);
-        {
-            std::unique_lock<std::mutex> tg(e->bticket_mu);
-            *ticket = e->next_bticket++;
-            e->btickets[*ticket] = t;
-        }
+        e->holders.note_submit(&t.owner);
+        *ticket = e->btickets.put(t);
         keep_ctx = true;
         keep_lock = true;
         return WAX_HIP_OK;
@@ -344,19 +337,13 @@ int batch_collect_device_impl(wax_hip_engine* e, uint64_t ticket, uint32_t* out_
     if (!e) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine is null");
     if (e->sh) return sh_batch_collect_device(e, ticket, out_fallbacks);
     wax_hip_engine::BatchTicket t;
-    {
-        std::unique_lock<std::mutex> tg(e->bticket_mu);
-        auto it = e->btickets.find(ticket);
-        if (it == e->btickets.end()) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "unknown batch ticket " + std::to_string(ticket));
-        t = it->second;
-        e->btickets.erase(it);
-    }
+    if (!e->btickets.take(ticket, &t)) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "unknown batch ticket " + std::to_string(ticket));
     if (!t.c) return WAX_HIP_OK;   // answered at submit time
     DeviceGuard g(e->device);
     const int rc = batch_finish_device_locked(e, t.c, t.d_queries, t.nq, t.k_eff, t.d_out, t.out_stride, out_fallbacks, out_rewritten);
     if (rc != WAX_HIP_OK) (void)hipStreamSynchronize(t.c->stream);
-    release_bctx(e, t.c);
-    note_collect_id(e, t.owner);
+    e->bctxs.release(t.c);
+    e->holders.note_collect(t.owner);
     e->lock.unlock_shared();
     return rc;
 }

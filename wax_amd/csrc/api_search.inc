@@ -43,13 +43,12 @@ static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int
         e->lock.lock_shared(holding(e) > 0);             // withReadLock (:447)
         { const int frc = flush_pending(e); if (frc != WAX_HIP_OK) { e->lock.unlock_shared(); return frc; } }   // staged single-frame appends reach HBM here
     }
-    bool others_in_flight = false;                     // uncollected single-query tickets of this engine, whoever holds them
-    { std::unique_lock<std::mutex> tg(e->slot_mu); others_in_flight = !e->tickets.empty(); }
+    const bool others_in_flight = !e->tickets.empty();   // uncollected single-query tickets of this engine, whoever holds them
     Slot* s = nullptr;
     int rc = WAX_HIP_OK;
     do {
         if (e->count == 0) {                               // :448 — an empty ticket, no GPU work
-            rc = acquire_slot(e, &s, try_only, holding(e) > 0);
+            rc = take_slot(e, &s, try_only, holding(e) > 0);
             if (rc != WAX_HIP_OK) break;
             s->k_eff = 0; s->timed = false; s->shared = false; s->listed = false;
             reset_ticket_extras(s, x, top_k);
@@ -65,7 +64,7 @@ static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int
         }
         const int limit = clamp_topk(top_k);               // :450
         const int k_eff = (uint64_t)limit < e->count ? limit : (int)e->count;  // :451
-        rc = acquire_slot(e, &s, try_only, holding(e) > 0);
+        rc = take_slot(e, &s, try_only, holding(e) > 0);
         if (rc != WAX_HIP_OK) break;
         s->k_eff = k_eff;
         const int tk_mode = (int)e->time_kernels.load();   // read once per submit
@@ -181,17 +180,12 @@ static int submit_impl(wax_hip_engine* e, const float* query, uint32_t dims, int
         }
     } while (0);
     if (rc != WAX_HIP_OK) {
-        if (s) { (void)hipStreamSynchronize(s->stream); pred_entry_release(e, s->pred_entry); s->pred_entry = -1; release_slot(e, s); }
+        if (s) { (void)hipStreamSynchronize(s->stream); pred_entry_release(e, s->pred_entry); s->pred_entry = -1; e->slots.release(s); }
         if (!caller_locked) e->lock.unlock_shared();
         return rc;
     }
-    {
-        std::unique_lock<std::mutex> tg(e->slot_mu);
-        const uint64_t t = e->next_ticket++;
-        e->tickets[t] = s;
-        *out_ticket = t;
-    }
-    note_submit(e, s);
+    *out_ticket = e->tickets.put(s);
+    e->holders.note_submit(&s->owner);
     return WAX_HIP_OK;  // shared lock stays held until collect (caller_locked: until the caller's scope ends)
 }
 
@@ -211,13 +205,7 @@ static int collect_impl(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, f
     if (!e || !out_count) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine/out_count is null");
     DeviceGuard g(e->device);
     Slot* s = nullptr;
-    {
-        std::unique_lock<std::mutex> tg(e->slot_mu);
-        auto it = e->tickets.find(ticket);
-        if (it == e->tickets.end()) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "unknown ticket " + std::to_string(ticket));
-        s = it->second;
-        e->tickets.erase(it);
-    }
+    if (!e->tickets.take(ticket, &s)) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "unknown ticket " + std::to_string(ticket));
     int rc = WAX_HIP_OK;
     *out_count = 0;
     if (s->k_eff == 0 && out_hits)
@@ -349,8 +337,8 @@ static int collect_impl(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, f
     if (rc == WAX_HIP_OK && s->has_cut && !out_hits && out_ids && out_scores) apply_min_score(s->cut, out_ids, out_scores, out_count);
     pred_entry_release(e, s->pred_entry);
     s->pred_entry = -1;
-    note_collect(e, s);
-    release_slot(e, s);
+    e->holders.note_collect(s->owner);
+    e->slots.release(s);
     if (!caller_locked) e->lock.unlock_shared();   // (a ticket submitted with caller_locked never took it)
     return rc;
 }

@@ -71,8 +71,7 @@ int wax_hip_engine_create(uint8_t metric, uint32_t dims, int device_id, wax_hip_
         if (rc == WAX_HIP_OK) {
             s->index = 0;
             s->stream = e->streams[0];
-            e->all_slots.push_back(s);
-            e->free_slots.push_back(s);
+            e->slots.seed(s);
         }
     }
     if (rc != WAX_HIP_OK) {
@@ -88,7 +87,7 @@ void wax_hip_engine_destroy(wax_hip_engine* e) {
     if (e->sh) { sh_destroy(e); delete e; return; }
     DeviceGuard g(e->device);
     (void)hipDeviceSynchronize();
-    for (Slot* s : e->all_slots) free_slot(s);
+    e->slots.drain(free_slot);
     for (int i = 0; i < kMaxStreams; ++i)
         if (e->streams[i]) (void)hipStreamDestroy(e->streams[i]);
     if (e->scan_done) (void)hipEventDestroy(e->scan_done);
@@ -113,8 +112,8 @@ void wax_hip_engine_destroy(wax_hip_engine* e) {
         if (b.ev_ready) (void)hipEventDestroy(b.ev_ready);
         (void)hipFree(b.d_c8); (void)hipFree(b.d_c8_meta); (void)hipFree(b.d_c8_max);
         if (b.ev8_ready) (void)hipEventDestroy(b.ev8_ready);
-        for (BatchCtx* c : e->bctx_all) free_bctx(c);
-        for (FilterWork* f : e->filter_all) free_filter_work(f);
+        e->bctxs.drain(free_bctx);
+        e->filter_works.drain(free_filter_work);
         (void)hipFree(e->idhash.d_table);
         (void)hipFree(e->d_attr_ts); (void)hipFree(e->d_attr_flags);
         (void)hipFree(e->d_grp_slot); (void)hipFree(e->d_grp_root);

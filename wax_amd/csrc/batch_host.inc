@@ -284,32 +284,13 @@ int alloc_bctx(wax_hip_engine* e, BatchCtx** out) {
     return WAX_HIP_OK;
 }
 
-int acquire_bctx(wax_hip_engine* e, BatchCtx** out, bool try_only = false) {
-    std::unique_lock<std::mutex> g(e->bctx_mu);
-    for (;;) {
-        if (!e->bctx_free.empty()) {
-            *out = e->bctx_free.back();
-            e->bctx_free.pop_back();
-            return WAX_HIP_OK;
-        }
-        if ((int)e->bctx_all.size() < e->bctx_max) {
-            BatchCtx* c = nullptr;
-            int rc = alloc_bctx(e, &c);
-            if (rc != WAX_HIP_OK) return rc;
-            e->bctx_all.push_back(c);
-            *out = c;
-            return WAX_HIP_OK;
-        }
-        if (try_only)
-            return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "every batch workspace is in use: collect outstanding batch tickets first (or raise \"batch_workspaces\")");
-        e->bctx_cv.wait(g);
-    }
-}
+constexpr const char* kBatchWorkBusy = "every batch workspace is in use: collect outstanding batch tickets first (or raise \"batch_workspaces\")";
 
-void release_bctx(wax_hip_engine* e, BatchCtx* c) {
-    std::unique_lock<std::mutex> g(e->bctx_mu);
-    e->bctx_free.push_back(c);
-    e->bctx_cv.notify_one();
+// try_only: the caller holds batch tickets (= workspaces) and is refused where another would wait (work_pool.h). Returned by e->bctxs.release(c).
+int take_bctx(wax_hip_engine* e, BatchCtx** out, bool try_only = false) {
+    int rc = WAX_HIP_OK;
+    const PoolGot got = e->bctxs.acquire(try_only ? PoolMode::tries : PoolMode::wait, out, &rc, [e](int, BatchCtx** made) { return alloc_bctx(e, made); });
+    return got == PoolGot::busy ? fail(WAX_HIP_ERR_INVALID_ARGUMENT, kBatchWorkBusy) : rc;
 }
 
 // Grow-on-demand buffers of a workspace (idle on its stream when called: a call owns its workspace and starts here).
@@ -358,30 +339,10 @@ static int alloc_filter_work(wax_hip_engine* e, FilterWork** out) {
     return WAX_HIP_OK;
 }
 
-static int acquire_filter_work(wax_hip_engine* e, FilterWork** out) {
-    std::unique_lock<std::mutex> g(e->filter_mu);
-    for (;;) {
-        if (!e->filter_free.empty()) {
-            *out = e->filter_free.back();
-            e->filter_free.pop_back();
-            return WAX_HIP_OK;
-        }
-        if ((int)e->filter_all.size() < e->filter_max) {
-            FilterWork* f = nullptr;
-            int rc = alloc_filter_work(e, &f);
-            if (rc != WAX_HIP_OK) return rc;
-            e->filter_all.push_back(f);
-            *out = f;
-            return WAX_HIP_OK;
-        }
-        e->filter_cv.wait(g);
-    }
-}
-
-static void release_filter_work(wax_hip_engine* e, FilterWork* f) {
-    std::unique_lock<std::mutex> g(e->filter_mu);
-    e->filter_free.push_back(f);
-    e->filter_cv.notify_one();
+static int take_filter_work(wax_hip_engine* e, FilterWork** out) {   // waits for one; returned by e->filter_works.release(f)
+    int rc = WAX_HIP_OK;
+    (void)e->filter_works.acquire(PoolMode::wait, out, &rc, [e](int, FilterWork** made) { return alloc_filter_work(e, made); });
+    return rc;
 }
 
 // The id -> row table of the store as it is now (shared lock held; pending rows flushed). Concurrent filtered searches
@@ -816,7 +777,7 @@ int exact_scan_queries(wax_hip_engine* e, BatchCtx* c, const float* d_queries, c
     for (; done < nf; ++done) {
         const uint32_t q = fq[done];
         if (!s) {
-            rc = acquire_slot(e, &s, /*try_only=*/false, /*holding=*/true);
+            rc = take_slot(e, &s, /*try_only=*/false, /*holder=*/true);
             if (rc != WAX_HIP_OK) return rc;
         }
         rc = enqueue_scan(e, d_queries + (uint64_t)q * D, h_norm_by_query[q], k_eff, (int)out_stride, s->d_partials, s,
@@ -825,7 +786,7 @@ int exact_scan_queries(wax_hip_engine* e, BatchCtx* c, const float* d_queries, c
     }
     if (s) {
         (void)hipStreamSynchronize(st);
-        release_slot(e, s);
+        e->slots.release(s);
     }
     return rc;
 }

@@ -28,6 +28,10 @@
 #include "mirror8_layout.h"
 #include "row_columns.h"
 #include "derived_rows.h"
+#include "work_pool.h"
+#include "rw_lock.h"
+#include "shard_workers.h"
+#include "id_map.h"
 
 using namespace wax;
 
@@ -38,9 +42,11 @@ using namespace wax;
 // anonymous namespace and the extern "C" block open and close where they always did. row_columns.h, included above, is the one part
 // that stands alone: the per-row columns on the host, plain C++ without HIP, tested on the CPU (tests/row_columns/driver.cpp).
 // derived_rows.h stands alone in the same way: how far the bf16 mirror, the code mirror and the id table have followed the store
-// (tests/derived_rows/driver.cpp).
+// (tests/derived_rows/driver.cpp). So does the host-side concurrency, which may use threads and mutexes but no HIP: work_pool.h (the pools
+// of per-call workspaces and the ticket tables), rw_lock.h (the reader/writer lock, the tickets per submitting thread), shard_workers.h
+// (the hand-off to the per-shard threads) and id_map.h (frame id -> row), each with a driver under tests/<name>/driver.cpp.
 //
-//   engine_types.inc       types of the host side: error state, device / lock guards, the id map, the reader/writer lock, scratch slots, workspaces, the device side of the mirrors and the id table, `struct wax_hip_engine`, ticket ownership
+//   engine_types.inc       types of the host side: error state, the device guard, scratch slots, workspaces, the device side of the mirrors and the id table, `struct wax_hip_engine`, ticket ownership
 //   store_internal.inc     the store behind the C ABI: clampTopK, the scratch-slot pool, the general-selection workspace, staged appends, growth (MetalVectorEngine.swift:84-117, 330-357, 842-890)
 //   search_internal.inc    one query -> one scan: which launch form a scan takes and how it is enqueued (`enqueue_scan`), hits -> results (MetalVectorEngine.swift:446-627, VectorMetric.swift:32-43)
 //   batch_host.inc         batched queries, host side: the incremental bf16 mirror and id table, pooled batch workspaces, the one-pass planner, the launch chain (`batch_enqueue`) and the exactness ladder behind it

@@ -1,5 +1,5 @@
 // engine_types.inc — part of engine.hip's translation unit (included there; not compiled alone).
-// types of the host side: error state, device / lock guards, the id map, the reader/writer lock, scratch slots, workspaces, the bf16 mirror's bookkeeping, `struct wax_hip_engine`, ticket ownership
+// types of the host side: error state, the device guard, scratch slots, workspaces, the bf16 mirror's bookkeeping, `struct wax_hip_engine`, ticket ownership
 
 namespace {
 
@@ -32,153 +32,6 @@ struct DeviceGuard {
     }
 };
 
-// Writer-preferring reader/writer lock with thread-agnostic unlock (a ticket may be
-// collected on another thread). Same contract as AsyncReadWriteLock
-// (WaxCore/Concurrency/ReadWriteLock.swift:79-156).
-class RWLock {
-  public:
-    // reentrant = the caller already holds a shared lock (an uncollected search ticket): it must not queue
-    // behind a waiting writer, or the writer (waiting for readers == 0) and the reader (waiting for the
-    // writer) deadlock. With readers_ > 0 no writer can be active, so skipping the preference is safe.
-    void lock_shared(bool reentrant = false) {
-        std::unique_lock<std::mutex> g(m_);
-        cv_.wait(g, [&] { return !writer_ && (reentrant || writers_waiting_ == 0); });
-        ++readers_;
-    }
-    void unlock_shared() {
-        std::unique_lock<std::mutex> g(m_);
-        if (--readers_ == 0) cv_.notify_all();
-    }
-    void lock() {
-        std::unique_lock<std::mutex> g(m_);
-        ++writers_waiting_;
-        cv_.wait(g, [&] { return !writer_ && readers_ == 0; });
-        --writers_waiting_;
-        writer_ = true;
-        epoch_.fetch_add(1, std::memory_order_relaxed);   // every writer: what is cached per store state (the predicate tickets' bitmaps) is of an older epoch now
-    }
-    // the number of exclusive acquisitions so far: constant while a shared lock is held
-    uint64_t epoch() const { return epoch_.load(std::memory_order_relaxed); }
-    void unlock() {
-        std::unique_lock<std::mutex> g(m_);
-        writer_ = false;
-        cv_.notify_all();
-    }
-
-  private:
-    std::mutex m_;
-    std::condition_variable cv_;
-    int readers_ = 0;
-    int writers_waiting_ = 0;
-    bool writer_ = false;
-    std::atomic<uint64_t> epoch_{0};
-};
-
-struct WriteGuard {
-    RWLock& l;
-    explicit WriteGuard(RWLock& l_) : l(l_) { l.lock(); }
-    ~WriteGuard() { l.unlock(); }
-};
-
-// frameId -> row. Open addressing, linear probing, backward-shift deletion. Replaces the
-// reference's O(N) `frameIds.firstIndex(of:)` (MetalVectorEngine.swift:334, 385, 426).
-class IdMap {
-  public:
-    IdMap() { resize_table(1024); }
-    int64_t find(uint64_t id) const {
-        size_t i = hash(id) & mask_;
-        while (used_[i]) {
-            if (keys_[i] == id) return (int64_t)vals_[i];
-            i = (i + 1) & mask_;
-        }
-        return -1;
-    }
-    void put(uint64_t id, uint32_t row) {
-        if ((size_ + 1) * 10 > (mask_ + 1) * 6) grow();
-        size_t i = hash(id) & mask_;
-        while (used_[i]) {
-            if (keys_[i] == id) { vals_[i] = row; return; }
-            i = (i + 1) & mask_;
-        }
-        used_[i] = 1; keys_[i] = id; vals_[i] = row; ++size_;
-    }
-    // remove `id` (stored at row `row`) and renumber every row above it down by one
-    void erase_row(uint64_t id, uint32_t row) {
-        erase_only(id);
-        for (size_t s = 0; s <= mask_; ++s)
-            if (used_[s] && vals_[s] > row) --vals_[s];
-    }
-    // After erase_only of the ids of the rows `rem` (ascending, distinct): every remaining row drops by the number of removed rows
-    // below it, in ONE pass over the table (n calls of erase_row are n passes). rank(r) comes from a bitmap of the removed rows
-    // with a running count per 64-row word — 1 bit + half a byte per 64 rows behind rem[0], cache-resident at 10M rows.
-    void renumber_removed(const std::vector<uint32_t>& rem, uint64_t rows) {
-        if (rem.empty()) return;
-        const uint64_t first = rem[0] & ~63ull;                    // word-aligned start of the affected range
-        const size_t words = (size_t)((rows - first + 63) / 64);
-        std::vector<uint64_t> bits(words, 0);
-        std::vector<uint32_t> before(words, 0);                    // removed rows below the word
-        for (uint32_t r : rem) bits[(r - first) >> 6] |= 1ull << ((r - first) & 63);
-        uint32_t run = 0;
-        for (size_t w = 0; w < words; ++w) { before[w] = run; run += (uint32_t)__builtin_popcountll(bits[w]); }
-        for (size_t s = 0; s <= mask_; ++s) {
-            if (!used_[s] || vals_[s] <= rem[0]) continue;
-            const uint64_t o = vals_[s] - first;
-            vals_[s] -= before[o >> 6] + (uint32_t)__builtin_popcountll(bits[o >> 6] & ((1ull << (o & 63)) - 1ull));
-        }
-    }
-    void erase_only(uint64_t id) {
-        size_t i = hash(id) & mask_;
-        while (used_[i] && keys_[i] != id) i = (i + 1) & mask_;
-        if (used_[i]) {
-            size_t hole = i, j = i;
-            for (;;) {
-                j = (j + 1) & mask_;
-                if (!used_[j]) break;
-                const size_t home = hash(keys_[j]) & mask_;
-                // can entry j move into the hole? yes iff hole lies cyclically in [home, j)
-                const bool movable = (hole <= j) ? (home <= hole || home > j) : (home <= hole && home > j);
-                if (movable) {
-                    keys_[hole] = keys_[j]; vals_[hole] = vals_[j];
-                    hole = j;
-                }
-            }
-            used_[hole] = 0;
-            --size_;
-        }
-    }
-    void clear() { resize_table(1024); }
-    void reserve(size_t n) {
-        size_t want = 1024;
-        while (want * 6 < n * 10 + 10) want <<= 1;
-        if (want > mask_ + 1) rehash(want);
-    }
-    size_t size() const { return size_; }
-
-  private:
-    static uint64_t hash(uint64_t x) {
-        x += 0x9e3779b97f4a7c15ull;
-        x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
-        x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
-        return x ^ (x >> 31);
-    }
-    void resize_table(size_t cap) {
-        keys_.assign(cap, 0); vals_.assign(cap, 0); used_.assign(cap, 0);
-        mask_ = cap - 1; size_ = 0;
-    }
-    void rehash(size_t cap) {
-        std::vector<uint64_t> ok; std::vector<uint32_t> ov; std::vector<uint8_t> ou;
-        ok.swap(keys_); ov.swap(vals_); ou.swap(used_);
-        resize_table(cap);
-        for (size_t s = 0; s < ou.size(); ++s)
-            if (ou[s]) put(ok[s], ov[s]);
-    }
-    void grow() { rehash((mask_ + 1) * 2); }
-    std::vector<uint64_t> keys_;
-    std::vector<uint32_t> vals_;
-    std::vector<uint8_t> used_;
-    size_t mask_ = 0, size_ = 0;
-};
-
 constexpr int kShardRing = 8;
 
 // A scan's stage buffer: per-workgroup partial top-k lists, followed by one cache line holding the arrival ticket of the
@@ -191,6 +44,7 @@ inline uint32_t* partials_ticket(int64_t* d_partials) {
 }
 
 constexpr int kMaxStreams = 4;
+constexpr int kHardSlotCap = 256;        // scratch slots a thread that pipelines submits without collecting can bring the pool to (work_pool.h)
 constexpr size_t kPredCounts = 3;        // words of FilterWork::d_pred_counts and PredEntry::d_counts (AttrMaskArgs::counts)
 
 struct Slot {
@@ -257,7 +111,7 @@ struct PredEntry {
 };
 constexpr int kPredEntries = 4;
 
-// Workspace of one wax_hip_search_filtered call: pooled (filter_max per engine, allocated on demand) with its own stream,
+// Workspace of one wax_hip_search_filtered call: pooled (4 per engine, allocated on demand) with its own stream,
 // so filtered searches run concurrently with each other and with every other read entry point.
 struct FilterWork {
     hipStream_t stream = nullptr;
@@ -434,7 +288,7 @@ struct wax_hip_engine {
     RWLock lock;
 
     hipStream_t streams[kMaxStreams] = {};
-    int n_streams = 2;            // slots are spread round-robin over this many in-order streams
+    std::atomic<int> n_streams{2};   // slots are spread round-robin over this many in-order streams
     // Scan kernels are chained across streams through this event so that they never overlap each
     // other (each one owns the whole HBM pipe and its HIP-event duration stays meaningful) while
     // the merge kernel, the query upload and the result write of neighbouring queries do overlap.
@@ -457,18 +311,11 @@ struct wax_hip_engine {
     std::atomic<int64_t> scan_chain{-1};
     std::mutex chain_mu;
 
-    std::mutex slot_mu;
-    std::condition_variable slot_cv;
-    std::vector<Slot*> all_slots;
-    std::vector<Slot*> free_slots;
-    int max_slots = 4;
-    std::map<uint64_t, Slot*> tickets;
-    uint64_t next_ticket = 1;
-    // Uncollected search tickets per SUBMITTING thread (a ticket holds the shared lock until it is collected, possibly
-    // by another thread): lets a thread that already holds the lock re-enter past a queued writer, never wait for a
-    // scratch slot, and be refused by the mutating entry points instead of dead-locking on itself.
-    std::mutex out_mu;
-    std::map<std::thread::id, int> outstanding;
+    // The scratch slots, the batch workspaces and the filtered-search workspaces (work_pool.h: who waits, who is refused, who grows), the
+    // tickets in flight, and the uncollected tickets per submitting thread (rw_lock.h).
+    WorkPool<Slot> slots{4, kHardSlotCap};
+    TicketTable<Slot*> tickets;
+    TicketHolders holders;
 
     // shard-search scratch ring (caller-stream async work)
     float* ring_d_query[kShardRing] = {};
@@ -539,10 +386,7 @@ struct wax_hip_engine {
     std::atomic<int64_t> batch_rega{1};      // register-resident-queries GEMM where it applies: 1 (default) workgroup barrier per tile, 5 split tile barrier; 0 = the LDS-tiled kernel instead
     std::atomic<uint64_t> st_batch_queries{0}, st_batch_fallbacks{0}, st_idhash_rows{0};
     BatchMirror batch;
-    std::mutex bctx_mu;
-    std::condition_variable bctx_cv;
-    std::vector<BatchCtx*> bctx_all, bctx_free;
-    int bctx_max = 4;
+    WorkPool<BatchCtx> bctxs{4};
     std::atomic<int64_t> batch_onepass{1};        // 0 = always the slab pipeline
     std::atomic<int64_t> batch_onepass_tiles{64};     // smallest store (in units of 64 rows, 32 at D = 768) the one-pass pipeline takes (rounds 2-5: 1024; measured down to 64: profiles/r06/r_*)
     std::atomic<int64_t> batch_survivors{3};      // one-pass pipeline: expected survivors per query = this x k'
@@ -589,7 +433,7 @@ struct wax_hip_engine {
     std::mutex breaker_mu;
     uint32_t breaker_bits = 0;           // one bit per collected 8-bit query, newest in bit 0: 1 = uncertified
     int64_t breaker_hold = 0;            // eligible queries still to send to bf16
-    // wax_hip_search_batch_submit_device tickets (guarded by bticket_mu)
+    // wax_hip_search_batch_submit_device tickets
     struct BatchTicket {
         BatchCtx* c = nullptr;           // null: the batch was answered at submit time (empty engine / loop path)
         const float* d_queries = nullptr;
@@ -600,13 +444,8 @@ struct wax_hip_engine {
     };
     std::mutex gemm_chain_mu;                     // "time_kernels": filtering GEMMs of concurrent batches run one after another
     hipEvent_t gemm_chain_ev = nullptr;           // the last one's end-of-kernel event (owned by its workspace)
-    std::mutex bticket_mu;
-    std::map<uint64_t, BatchTicket> btickets;
-    uint64_t next_bticket = 1;
-    std::mutex filter_mu;                         // pool of filtered-search workspaces
-    std::condition_variable filter_cv;
-    std::vector<FilterWork*> filter_all, filter_free;
-    int filter_max = 4;
+    TicketTable<BatchTicket> btickets;
+    WorkPool<FilterWork> filter_works{4};         // pool of filtered-search workspaces
     IdHash idhash;
     // The per-row columns (DESIGN 2): timestamps and flags (wax_hip_set_attributes), parents (wax_hip_set_parents; DESIGN 4.10), term sets
     // (wax_hip_set_terms; DESIGN 4.11), the group slots derived from the parents, and the marks of their device copies. Everything about
@@ -691,16 +530,6 @@ struct wax_hip_engine {
 
 namespace {
 
-inline void cpu_relax() {   // a spin-wait hint, per architecture
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#elif defined(__aarch64__)
-    asm volatile("yield" ::: "memory");
-#else
-    std::this_thread::yield();
-#endif
-}
-
 constexpr uint64_t kBounceBytes = 64ull << 20;
 
 // The same for wax_hip_timeline_device, which reads the id table and the attribute columns on its caller's stream: waited for by
@@ -728,11 +557,7 @@ void sync_shard_work(wax_hip_engine* e) {
     sync_timeline_work(e);
 }
 
-int holding(wax_hip_engine* e) {   // uncollected tickets submitted by the calling thread
-    std::unique_lock<std::mutex> g(e->out_mu);
-    auto it = e->outstanding.find(std::this_thread::get_id());
-    return it == e->outstanding.end() ? 0 : it->second;
-}
+int holding(wax_hip_engine* e) { return e->holders.holding(); }   // uncollected tickets submitted by the calling thread
 // The read side of WriteGuard: the shared lock for the scope, re-entrant for a thread that holds uncollected tickets (RWLock::lock_shared).
 struct ReadGuard {
     RWLock& l;
@@ -740,18 +565,6 @@ struct ReadGuard {
     explicit ReadGuard(wax_hip_engine* e) : l(e->lock), holder(holding(e) > 0) { l.lock_shared(holder); }
     ~ReadGuard() { l.unlock_shared(); }
 };
-void note_submit_id(wax_hip_engine* e, std::thread::id* owner) {
-    *owner = std::this_thread::get_id();
-    std::unique_lock<std::mutex> g(e->out_mu);
-    e->outstanding[*owner] += 1;
-}
-void note_collect_id(wax_hip_engine* e, std::thread::id owner) {
-    std::unique_lock<std::mutex> g(e->out_mu);
-    auto it = e->outstanding.find(owner);
-    if (it != e->outstanding.end() && --it->second <= 0) e->outstanding.erase(it);
-}
-void note_submit(wax_hip_engine* e, Slot* s) { note_submit_id(e, &s->owner); }
-void note_collect(wax_hip_engine* e, Slot* s) { note_collect_id(e, s->owner); }
 
 // sharded.inc (included at the end of this file)
 int sh_add_batch(wax_hip_engine* e, const uint64_t* frame_ids, const float* rows, uint64_t n, uint32_t dims);

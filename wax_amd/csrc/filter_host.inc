@@ -37,10 +37,10 @@ struct FilterLease {
     wax_hip_engine* e;
     FilterWork* f = nullptr;
     const int rc;
-    explicit FilterLease(wax_hip_engine* e_) : e(e_), rc(acquire_filter_work(e_, &f)) {}
+    explicit FilterLease(wax_hip_engine* e_) : e(e_), rc(take_filter_work(e_, &f)) {}
     FilterLease(const FilterLease&) = delete;
     FilterWork& work() const { return *f; }
-    ~FilterLease() { if (rc == WAX_HIP_OK) { (void)hipStreamSynchronize(f->stream); release_filter_work(e, f); } }
+    ~FilterLease() { if (rc == WAX_HIP_OK) { (void)hipStreamSynchronize(f->stream); e->filter_works.release(f); } }
 };
 
 // room for m rows in the compact list (rows, their frame ids, their distances)

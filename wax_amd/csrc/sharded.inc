@@ -67,115 +67,6 @@ struct ShardSlot {
     std::vector<float> query;
 };
 
-// Persistent per-shard worker threads: per-shard host work (single-query submits — one kernel launch each —, filtered search,
-// the k > 192 batched path, mirror builds) runs on all shards at once without creating a thread per call. Worker g is bound
-// to device g for its whole life.
-// Hand-off (round 5): a job is published by bumping an atomic epoch; a worker that has just finished a job POLLS the epoch for
-// kSpinUs before it goes back to sleep on the condition variable, and the caller polls the completion count the same way. While
-// queries keep coming, a fan-out therefore costs an atomic store, the workers' own work side by side and an atomic load — not a
-// futex wake per shard (5 - 10 us each) and not G launches one after the other from one thread (12 - 15 us per shard measured in
-// round 4: 100 - 130 us per query at 8 shards). An idle handle burns no CPU: every worker is asleep kSpinUs after the last job.
-class ShardWorkers {
-  public:
-    static constexpr int kSpinUs = 200;
-    void start(const std::vector<int>& devices) {
-        n_ = devices.size();
-        for (size_t g = 0; g < n_; ++g)
-            threads_.emplace_back([this, g, dev = devices[g]]() {
-                (void)hipSetDevice(dev);
-                uint64_t seen = 0;
-                for (;;) {
-                    // poll, then sleep
-                    bool got = false;
-                    const auto t0 = std::chrono::steady_clock::now();
-                    for (uint32_t spins = 1;; ++spins) {
-                        if (epoch_.load(std::memory_order_acquire) != seen || stop_.load(std::memory_order_acquire)) { got = true; break; }
-                        cpu_relax();
-                        if ((spins & 0xffu) == 0u &&
-                            std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > kSpinUs)
-                            break;
-                    }
-                    if (!got) {
-                        std::unique_lock<std::mutex> lk(mu_);
-                        ++sleepers_;
-                        cv_.wait(lk, [&] { return stop_.load() || epoch_.load() != seen; });
-                        --sleepers_;
-                    }
-                    if (stop_.load()) return;
-                    seen = epoch_.load(std::memory_order_acquire);
-                    const std::function<void(size_t)>* job = job_.load(std::memory_order_acquire);
-                    (*job)(g);
-                    // The last worker ALWAYS takes the mutex and notifies (one uncontended lock per job). Round 5 skipped this unless a
-                    // `waiting_` flag was up — a store-then-load on both sides that release / acquire does not order: the caller could
-                    // raise the flag, read done_ == n - 1 and go to sleep while the last worker read the flag as still down and never
-                    // notified (advisor, round 5). Under the mutex the caller's predicate check and this notify cannot interleave that way.
-                    if (done_.fetch_add(1, std::memory_order_acq_rel) + 1 == n_) {
-                        std::unique_lock<std::mutex> lk(mu_);
-                        done_cv_.notify_all();
-                    }
-                }
-            });
-    }
-    // fn(g) on every worker, concurrently; returns when all are done. One job at a time per handle (callers queue here).
-    void run_all(const std::function<void(size_t)>& fn) {
-        std::unique_lock<std::mutex> one(job_mu_);
-        run_locked(fn);
-    }
-    // The same, unless another job holds the workers (a mirror build, a filtered search, a k > 192 batch: milliseconds): then false at
-    // once, and the caller does its short per-shard work itself instead of queueing behind the long job (advisor, round 5).
-    bool try_run_all(const std::function<void(size_t)>& fn) {
-        std::unique_lock<std::mutex> one(job_mu_, std::try_to_lock);
-        if (!one.owns_lock()) return false;
-        run_locked(fn);
-        return true;
-    }
-
-  private:
-    void run_locked(const std::function<void(size_t)>& fn) {
-        job_.store(&fn, std::memory_order_release);
-        done_.store(0, std::memory_order_release);
-        epoch_.fetch_add(1, std::memory_order_acq_rel);
-        {
-            std::unique_lock<std::mutex> lk(mu_);    // (a worker checks the epoch under this lock before it sleeps: no lost wake-up)
-            if (sleepers_ > 0) cv_.notify_all();
-        }
-        const auto t0 = std::chrono::steady_clock::now();
-        for (uint32_t spins = 1;; ++spins) {
-            if (done_.load(std::memory_order_acquire) == n_) break;
-            cpu_relax();
-            if ((spins & 0xffu) == 0u &&
-                std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > kSpinUs) {
-                std::unique_lock<std::mutex> lk(mu_);   // a long job (mirror build, filtered search): sleep until the last worker reports
-                done_cv_.wait(lk, [&] { return done_.load(std::memory_order_acquire) == n_; });
-                break;
-            }
-        }
-        job_.store(nullptr, std::memory_order_release);
-    }
-
-  public:
-    void stop() {
-        {
-            std::unique_lock<std::mutex> lk(mu_);
-            stop_.store(true);
-            cv_.notify_all();
-        }
-        for (auto& t : threads_) t.join();
-        threads_.clear();
-    }
-
-  private:
-    std::mutex mu_, job_mu_;
-    std::condition_variable cv_, done_cv_;
-    std::vector<std::thread> threads_;
-    std::atomic<const std::function<void(size_t)>*> job_{nullptr};
-    std::atomic<uint64_t> epoch_{0};
-    std::atomic<size_t> done_{0};
-    std::atomic<bool> stop_{false};
-    size_t n_ = 0;
-    int sleepers_ = 0;                               // guarded by mu_
-};
-
 // Workspace of one batched search on a sharded handle (pooled; nothing is allocated per call once warm).
 struct ShardBatchWork {
     std::vector<float*> d_q;                // per shard, on its device: the query block (unused where the shard shares the caller's device)
@@ -207,11 +98,8 @@ struct ShardedState {
     hipStream_t merge_stream = nullptr;     // device of shard 0
     uint64_t block_rows = 0;                // rows at which a shard is full (0 = not chosen yet)
     uint64_t reserve_hint = 0;
-    std::mutex slot_mu;
-    std::condition_variable slot_cv;
-    std::vector<ShardSlot*> slots_all, slots_free;
-    std::map<uint64_t, ShardSlot*> tickets;
-    uint64_t next_ticket = 1;
+    WorkPool<ShardSlot> slots{kShardSlots, kShardHardSlots};
+    TicketTable<ShardSlot*> tickets;
     std::atomic<int64_t> exchange{0};       // 0 = peer copies (default), 1 = RCCL all-gather
     RcclApi rccl;
     std::vector<void*> comms;
@@ -235,12 +123,8 @@ struct ShardedState {
     std::atomic<int64_t> shard_min_mb{64};
     std::atomic<uint64_t> rebalances{0};
     ShardWorkers workers;
-    std::mutex bw_mu;
-    std::condition_variable bw_cv;
-    std::vector<ShardBatchWork*> bw_all, bw_free;
-    int bw_max = 4;
-    std::map<uint64_t, ShardBatchWork*> btickets;   // guarded by bw_mu
-    uint64_t next_bticket = 1;
+    WorkPool<ShardBatchWork> bworks{4};
+    TicketTable<ShardBatchWork*> btickets;
     // batched collect: the shards' collects run one after the other on the calling thread (each is just a wait when every
     // query was certified on the device) — unless the previous batch had two or more shards settle queries on the host side
     // (full retries / exact passes: data with dense neighbourhoods, which tends to persist from batch to batch); then the
@@ -355,32 +239,13 @@ int sh_alloc_slot(ShardedState* s, ShardSlot** out) {
     return WAX_HIP_OK;
 }
 
-// `holding`: the calling thread already owns tickets of this handle (= slots, and the shared lock). Like the single-device
-// acquire_slot it must never WAIT for a slot — a thread that pipelines a 9th submit without collecting would wait for
-// itself while holding the shared lock (and block every writer with it) — so it gets a freshly allocated slot beyond the
-// soft cap, up to kShardHardSlots, and an error after that.
-int sh_acquire_slot(ShardedState* s, ShardSlot** out, bool holding) {
-    std::unique_lock<std::mutex> g(s->slot_mu);
-    for (;;) {
-        if (!s->slots_free.empty()) { *out = s->slots_free.back(); s->slots_free.pop_back(); return WAX_HIP_OK; }
-        if ((int)s->slots_all.size() < kShardSlots || holding) {
-            if ((int)s->slots_all.size() >= kShardHardSlots)
-                return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "too many outstanding search tickets (collect some first)");
-            ShardSlot* sl = nullptr;
-            int rc = sh_alloc_slot(s, &sl);
-            if (rc != WAX_HIP_OK) return rc;
-            s->slots_all.push_back(sl);
-            *out = sl;
-            return WAX_HIP_OK;
-        }
-        s->slot_cv.wait(g);
-    }
-}
-
-void sh_release_slot(ShardedState* s, ShardSlot* sl) {
-    std::unique_lock<std::mutex> g(s->slot_mu);
-    s->slots_free.push_back(sl);
-    s->slot_cv.notify_one();
+// `holder`: the calling thread already owns tickets of this handle (= slots, and the shared lock), so like take_slot's it never
+// WAITS for a slot (work_pool.h, PoolMode::grow): a freshly allocated one beyond kShardSlots, up to kShardHardSlots, and an error
+// after that. Returned by s->slots.release(sl).
+int sh_take_slot(ShardedState* s, ShardSlot** out, bool holder) {
+    int rc = WAX_HIP_OK;
+    const PoolGot got = s->slots.acquire(holder ? PoolMode::grow : PoolMode::wait, out, &rc, [s](int, ShardSlot** made) { return sh_alloc_slot(s, made); });
+    return got == PoolGot::exhausted ? fail(WAX_HIP_ERR_INVALID_ARGUMENT, "too many outstanding search tickets (collect some first)") : rc;
 }
 
 // ---- mutations (handle's exclusive lock held) ---------------------------------------------------------------------
@@ -660,7 +525,7 @@ int sh_submit(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_
     ShardSlot* sl = nullptr;
     do {
         const uint64_t total = sh_count(s);
-        rc = sh_acquire_slot(s, &sl, holding(e) > 0);
+        rc = sh_take_slot(s, &sl, holding(e) > 0);
         if (rc != WAX_HIP_OK) break;
         sl->kpad = 0; sl->host_path = false; sl->top_k = top_k; sl->sub_tickets.clear(); sl->only_shard = -1;
         sl->has_cut = x != nullptr && x->has_cut != 0; sl->cut = x != nullptr ? x->cut : 0.f; sl->pred_deferred = false;
@@ -770,18 +635,13 @@ int sh_submit(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_
                 if (sl->sub_tickets[g]) { uint32_t dummy = 0; std::vector<wax_hip_hit> tmp(1); (void)collect_impl(s->subs[g], sl->sub_tickets[g], nullptr, nullptr, 0, &dummy, tmp.data(), 0); }
             for (size_t g = 0; g < s->subs.size(); ++g) { DeviceGuard dg(s->devices[g]); (void)hipStreamSynchronize(s->streams[g]); }
             g_last_error = keep;
-            sh_release_slot(s, sl);
+            s->slots.release(sl);
         }
         e->lock.unlock_shared();
         return rc;
     }
-    {
-        std::unique_lock<std::mutex> tg(s->slot_mu);
-        const uint64_t t = s->next_ticket++;
-        s->tickets[t] = sl;
-        *out_ticket = t;
-    }
-    note_submit_id(e, &sl->owner);   // ticket ownership, as for one engine (the shared lock is held until collect)
+    *out_ticket = s->tickets.put(sl);
+    e->holders.note_submit(&sl->owner);   // ticket ownership, as for one engine (the shared lock is held until collect)
     return WAX_HIP_OK;
 }
 
@@ -789,13 +649,7 @@ int sh_collect(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, float* out
     ShardedState* s = e->sh;
     if (!out_count) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine/out_count is null");
     ShardSlot* sl = nullptr;
-    {
-        std::unique_lock<std::mutex> tg(s->slot_mu);
-        auto it = s->tickets.find(ticket);
-        if (it == s->tickets.end()) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "unknown ticket " + std::to_string(ticket));
-        sl = it->second;
-        s->tickets.erase(it);
-    }
+    if (!s->tickets.take(ticket, &sl)) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "unknown ticket " + std::to_string(ticket));
     int rc = WAX_HIP_OK;
     *out_count = 0;
     if ((!out_ids || !out_scores) && capacity > 0) rc = fail(WAX_HIP_ERR_INVALID_ARGUMENT, "output arrays are null");
@@ -838,8 +692,8 @@ int sh_collect(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, float* out
         (void)hipEventSynchronize(sl->done);
     }
     if (rc == WAX_HIP_OK && sl->has_cut && !sl->pred_deferred && out_ids && out_scores) apply_min_score(sl->cut, out_ids, out_scores, out_count);
-    note_collect_id(e, sl->owner);
-    sh_release_slot(s, sl);
+    e->holders.note_collect(sl->owner);
+    s->slots.release(sl);
     e->lock.unlock_shared();
     return rc;
 }
@@ -895,35 +749,17 @@ int sh_alloc_bwork(ShardedState* s, ShardBatchWork** out) {
     return WAX_HIP_OK;
 }
 
-int sh_acquire_bwork(ShardedState* s, ShardBatchWork** out, bool try_only) {
-    std::unique_lock<std::mutex> g(s->bw_mu);
-    for (;;) {
-        if (!s->bw_free.empty()) { *out = s->bw_free.back(); s->bw_free.pop_back(); return WAX_HIP_OK; }
-        if ((int)s->bw_all.size() < s->bw_max) {
-            ShardBatchWork* w = nullptr;
-            int rc = sh_alloc_bwork(s, &w);
-            if (rc != WAX_HIP_OK) return rc;
-            s->bw_all.push_back(w);
-            *out = w;
-            return WAX_HIP_OK;
-        }
-        if (try_only)
-            return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "every batch workspace is in use: collect outstanding batch tickets first (or raise \"batch_workspaces\")");
-        s->bw_cv.wait(g);
-    }
-}
-
-void sh_release_bwork(ShardedState* s, ShardBatchWork* w) {
-    std::unique_lock<std::mutex> g(s->bw_mu);
-    s->bw_free.push_back(w);
-    s->bw_cv.notify_one();
+int sh_take_bwork(ShardedState* s, ShardBatchWork** out, bool try_only) {   // as take_bctx; returned by s->bworks.release(w)
+    int rc = WAX_HIP_OK;
+    const PoolGot got = s->bworks.acquire(try_only ? PoolMode::tries : PoolMode::wait, out, &rc, [s](int, ShardBatchWork** made) { return sh_alloc_bwork(s, made); });
+    return got == PoolGot::busy ? fail(WAX_HIP_ERR_INVALID_ARGUMENT, kBatchWorkBusy) : rc;
 }
 
 // The stream a submitted single-device batch runs on (null: it was answered at submit time and is complete).
 hipStream_t sh_batch_stream(wax_hip_engine* sub, uint64_t ticket) {
-    std::unique_lock<std::mutex> tg(sub->bticket_mu);
-    auto it = sub->btickets.find(ticket);
-    return (it == sub->btickets.end() || !it->second.c) ? nullptr : it->second.c->stream;
+    hipStream_t st = nullptr;
+    (void)sub->btickets.peek(ticket, [&st](const wax_hip_engine::BatchTicket& t) { if (t.c) st = t.c->stream; });
+    return st;
 }
 
 int sh_copy_part(ShardedState* s, ShardBatchWork* w, size_t g, hipStream_t st) {
@@ -1102,10 +938,10 @@ int sh_batch_device(wax_hip_engine* e, const float* d_queries, uint32_t nq, uint
     ShardBatchWork* w = nullptr;
     // a thread that already holds batch tickets must never WAIT for a workspace — it would wait for itself while holding the
     // handle's shared lock (and block every writer) — whether this call is a submit or a blocking search
-    int rc = sh_acquire_bwork(s, &w, holder);
+    int rc = sh_take_bwork(s, &w, holder);
     if (rc != WAX_HIP_OK) return rc;
     bool keep_w = false;
-    struct Release { ShardedState* s; ShardBatchWork* w; bool& keep; ~Release() { if (!keep) sh_release_bwork(s, w); } } release{s, w, keep_w};
+    struct Release { ShardedState* s; ShardBatchWork* w; bool& keep; ~Release() { if (!keep) s->bworks.release(w); } } release{s, w, keep_w};
     std::fill(w->sub_valid.begin(), w->sub_valid.end(), 0);
     w->nq = 0;
     const uint64_t total = sh_count(s);
@@ -1122,12 +958,8 @@ int sh_batch_device(wax_hip_engine* e, const float* d_queries, uint32_t nq, uint
         if (!ticket) return sh_batch_collect(e, w, nullptr);
     }
     if (!ticket) return WAX_HIP_OK;
-    note_submit_id(e, &w->owner);
-    {
-        std::unique_lock<std::mutex> tg(s->bw_mu);
-        *ticket = s->next_bticket++;
-        s->btickets[*ticket] = w;
-    }
+    e->holders.note_submit(&w->owner);
+    *ticket = s->btickets.put(w);
     keep_w = true;
     keep_lock = true;
     return WAX_HIP_OK;
@@ -1137,20 +969,14 @@ int sh_batch_collect_device(wax_hip_engine* e, uint64_t ticket, uint32_t* out_fa
     ShardedState* s = e->sh;
     if (out_fallbacks) *out_fallbacks = 0;
     ShardBatchWork* w = nullptr;
-    {
-        std::unique_lock<std::mutex> tg(s->bw_mu);
-        auto it = s->btickets.find(ticket);
-        if (it == s->btickets.end()) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "unknown batch ticket " + std::to_string(ticket));
-        w = it->second;
-        s->btickets.erase(it);
-    }
+    if (!s->btickets.take(ticket, &w)) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "unknown batch ticket " + std::to_string(ticket));
     int rc = WAX_HIP_OK;
     if (w->nq > 0) {
         rc = sh_batch_collect(e, w, out_fallbacks);
         if (rc != WAX_HIP_OK) sh_batch_drain(s, w);
     }
-    note_collect_id(e, w->owner);
-    sh_release_bwork(s, w);
+    e->holders.note_collect(w->owner);
+    s->bworks.release(w);
     e->lock.unlock_shared();
     return rc;
 }
@@ -1171,9 +997,9 @@ int sh_search_batch_hits(wax_hip_engine* e, const float* queries, uint32_t nq, u
     if (k > stride) k = stride;
     if ((uint64_t)k > total) k = (uint32_t)total;
     ShardBatchWork* w = nullptr;
-    int rc = sh_acquire_bwork(s, &w, rd.holder);
+    int rc = sh_take_bwork(s, &w, rd.holder);
     if (rc != WAX_HIP_OK) return rc;
-    struct Release { ShardedState* s; ShardBatchWork* w; ~Release() { sh_release_bwork(s, w); } } release{s, w};
+    struct Release { ShardedState* s; ShardBatchWork* w; ~Release() { s->bworks.release(w); } } release{s, w};
     DeviceGuard dg(s->devices[0]);
     const uint64_t n_hits = (uint64_t)nq * k;
     rc = grow_dev(&w->d_q0, &w->q0_cap, (uint64_t)nq * dims, sizeof(float), "Failed to allocate batch queries");
@@ -1731,10 +1557,7 @@ int sh_set_tuning(wax_hip_engine* e, const std::string& k, int64_t value) {
         int rc = wax_hip_set_tuning(sub, k.c_str(), value);
         if (rc != WAX_HIP_OK) return rc;
     }
-    if (k == "batch_workspaces") {   // concurrent batched searches per shard (above) and per handle
-        std::unique_lock<std::mutex> g(s->bw_mu);
-        s->bw_max = (int)value;
-    }
+    if (k == "batch_workspaces") s->bworks.set_cap((int)value);   // concurrent batched searches per shard (above) and per handle
     return WAX_HIP_OK;
 }
 
@@ -1777,8 +1600,8 @@ void sh_destroy(wax_hip_engine* e) {
         (void)hipDeviceSynchronize();
     }
     s->workers.stop();
-    for (ShardSlot* sl : s->slots_all) sh_free_slot(s, sl);
-    for (ShardBatchWork* w : s->bw_all) sh_free_bwork(s, w);
+    s->slots.drain([s](ShardSlot* sl) { sh_free_slot(s, sl); });
+    s->bworks.drain([s](ShardBatchWork* w) { sh_free_bwork(s, w); });
     if (s->rccl.lib && s->rccl.CommDestroy)
         for (void* c : s->comms)
             if (c) (void)s->rccl.CommDestroy(c);
@@ -1882,7 +1705,7 @@ int wax_hip_engine_create_sharded(uint8_t metric, uint32_t dims, const int* devi
         const long mb = std::strtol(v, nullptr, 10);
         if (mb >= 0 && mb <= (1 << 20)) s->shard_min_mb = mb;
     }
-    s->workers.start(s->devices);
+    s->workers.start(s->devices.size(), [s](size_t g) { (void)hipSetDevice(s->devices[g]); });
     *out = e;
     return WAX_HIP_OK;
 }

@@ -71,56 +71,25 @@ void free_slot(Slot* s) {
 // acquireTransientBuffers (MetalVectorEngine.swift:84-113): reuse a pooled slot or create one.
 constexpr int kSlotBusy = 1;  // internal: try_only and every slot is in use
 
-// `holding`: the calling thread already owns tickets (= slots). It must never WAIT for a slot — two threads that each
-// hold half of the pool and want one more would wait for each other forever — so, like the reference's transient
-// buffer pool (MetalVectorEngine.swift:84-117: an empty pool allocates), it gets a freshly allocated slot beyond
-// `max_slots` (counted in transient_allocations; the slot stays pooled afterwards), up to kHardSlotCap.
-constexpr int kHardSlotCap = 256;
-
-int acquire_slot(wax_hip_engine* e, Slot** out, bool try_only = false, bool holding = false) {
-    std::unique_lock<std::mutex> g(e->slot_mu);
-    for (;;) {
-        if (!e->free_slots.empty()) {
-            Slot* s = e->free_slots.back();
-            e->free_slots.pop_back();
-            s->stream = e->streams[s->index % e->n_streams];  // idle slot: safe to re-home
-            e->st_reuse++;
-            *out = s;
-            return WAX_HIP_OK;
-        }
-        if ((int)e->all_slots.size() < e->max_slots) {
-            Slot* s = nullptr;
-            int rc = alloc_slot(e, &s);
-            if (rc != WAX_HIP_OK) return rc;
-            s->index = (int)e->all_slots.size();
-            s->stream = e->streams[s->index % e->n_streams];
-            e->all_slots.push_back(s);
-            e->st_alloc++;
-            *out = s;
-            return WAX_HIP_OK;
-        }
-        if (try_only) return kSlotBusy;
-        if (holding) {
-            if ((int)e->all_slots.size() >= kHardSlotCap)
-                return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "too many outstanding search tickets (collect some first)");
-            Slot* s = nullptr;
-            int rc = alloc_slot(e, &s);
-            if (rc != WAX_HIP_OK) return rc;
-            s->index = (int)e->all_slots.size();
-            s->stream = e->streams[s->index % e->n_streams];
-            e->all_slots.push_back(s);
-            e->st_alloc++;
-            *out = s;
-            return WAX_HIP_OK;
-        }
-        e->slot_cv.wait(g);
+// `holder`: the calling thread already owns tickets (= slots), so it never WAITS for one (work_pool.h, PoolMode::grow). Like the
+// reference's transient buffer pool (MetalVectorEngine.swift:84-117: an empty pool allocates) it gets a freshly allocated slot beyond
+// "slots" (counted in transient_allocations; the slot stays pooled afterwards), up to kHardSlotCap. Returned by e->slots.release(s)
+// (releaseTransientBuffers, :115-117).
+int take_slot(wax_hip_engine* e, Slot** out, bool try_only = false, bool holder = false) {
+    int rc = WAX_HIP_OK;
+    switch (e->slots.acquire(try_only ? PoolMode::tries : holder ? PoolMode::grow : PoolMode::wait, out, &rc, [e](int index, Slot** made) {
+        const int mrc = alloc_slot(e, made);
+        if (mrc == WAX_HIP_OK) (*made)->index = index;
+        return mrc;
+    })) {
+    case PoolGot::reused: e->st_reuse++; break;   // idle slot: safe to re-home
+    case PoolGot::fresh: e->st_alloc++; break;
+    case PoolGot::busy: return kSlotBusy;
+    case PoolGot::exhausted: return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "too many outstanding search tickets (collect some first)");
+    case PoolGot::failed: return rc;
     }
-}
-
-void release_slot(wax_hip_engine* e, Slot* s) {  // releaseTransientBuffers (:115-117)
-    std::unique_lock<std::mutex> g(e->slot_mu);
-    e->free_slots.push_back(s);
-    e->slot_cv.notify_one();
+    (*out)->stream = e->streams[(*out)->index % e->n_streams];
+    return WAX_HIP_OK;
 }
 
 int ensure_general(wax_hip_engine* e, Slot* s) {

@@ -67,9 +67,9 @@ constexpr TuningGet get_fn(int64_t (*fn)(wax_hip_engine*)) { return {nullptr, nu
 #define GET_EXPR(expr) get_fn([](wax_hip_engine* e) -> int64_t { return (int64_t)(expr); })
 
 // the FN setters (the row's range, where it has one, is checked before they are called)
-int set_batch_workspaces(wax_hip_engine* e, int64_t v) { std::unique_lock<std::mutex> g(e->bctx_mu); e->bctx_max = (int)v; return WAX_HIP_OK; }
-int set_streams(wax_hip_engine* e, int64_t v) { std::unique_lock<std::mutex> g(e->slot_mu); e->n_streams = (int)v; return WAX_HIP_OK; }
-int set_slots(wax_hip_engine* e, int64_t v) { std::unique_lock<std::mutex> g(e->slot_mu); e->max_slots = (int)v; return WAX_HIP_OK; }
+int set_batch_workspaces(wax_hip_engine* e, int64_t v) { e->bctxs.set_cap((int)v); return WAX_HIP_OK; }
+int set_streams(wax_hip_engine* e, int64_t v) { e->n_streams = (int)v; return WAX_HIP_OK; }
+int set_slots(wax_hip_engine* e, int64_t v) { e->slots.set_cap((int)v); return WAX_HIP_OK; }
 int set_retry_hint(wax_hip_engine* e, int64_t v) { e->retry_hint = (int)v; return WAX_HIP_OK; }   // > 0: the next `v` clean batches still carry the device-side retry kernel (set by collect; tests force it)
 int set_merge_overlap_mb(wax_hip_engine* e, int64_t v) { e->merge_overlap_mb = v < 0 ? 0 : v; return WAX_HIP_OK; }
 int set_batch_first(wax_hip_engine* e, int64_t v) {
@@ -93,12 +93,11 @@ int64_t get_short_select_failures(wax_hip_engine* e) {   // short selections who
     int64_t t = 0;
     DeviceGuard g(e->device);
     (void)hipDeviceSynchronize();
-    std::unique_lock<std::mutex> tg(e->slot_mu);
-    for (Slot* sl : e->all_slots) {
+    e->slots.for_each([&t](Slot* sl) {
         uint32_t f[4] = {0u, 0u, 0u, 0u};
         if (sl->sw_ready && sl->sw.flags && hipMemcpy(f, sl->sw.flags, sizeof(f), hipMemcpyDeviceToHost) == hipSuccess) t += f[1];
         if (sl->d_partials && hipMemcpy(f, partials_ticket(sl->d_partials) + 8, sizeof(f), hipMemcpyDeviceToHost) == hipSuccess) t += f[1];   // the fused path's short merge
-    }
+    });
     for (int r = 0; r < kShardRing; ++r) {
         uint32_t f[4] = {0u, 0u, 0u, 0u};
         if (e->ring_d_partials[r] && hipMemcpy(f, partials_ticket(e->ring_d_partials[r]) + 8, sizeof(f), hipMemcpyDeviceToHost) == hipSuccess) t += f[1];
@@ -143,7 +142,7 @@ constexpr TuningRow kTuning[] = {
     {"scan_chain", set_range(&wax_hip_engine::scan_chain, -1, 1, "scan_chain must be -1 (auto), 0 or 1"), get_knob(&wax_hip_engine::scan_chain), FIRST_SHARD},
     {"share_timing", set_flag(&wax_hip_engine::share_timing), get_knob(&wax_hip_engine::share_timing), FIRST_SHARD},   // 0: every chained scan records its own start event (one more packet between scans)
     {"streams", set_fn(set_streams, 1, kMaxStreams, "streams must be 1..4"), GET_EXPR(e->n_streams), FIRST_SHARD},
-    {"slots", set_fn(set_slots, 1, 64, "slots must be 1..64"), GET_EXPR(e->max_slots), FIRST_SHARD},
+    {"slots", set_fn(set_slots, 1, 64, "slots must be 1..64"), GET_EXPR(e->slots.cap()), FIRST_SHARD},
     {"store_ptr", not_set(), GET_EXPR((uintptr_t)e->d_store), FIRST_SHARD},   // diagnosis: where the slab sits (tools/bimodal_probe.py)
     {"reset_stats", set_fn(set_reset_stats, INT64_MIN, INT64_MAX, nullptr), not_get(), FIRST_SHARD},
     {"scan_mirror", set_range(&wax_hip_engine::scan_mirror, 0, 2, "scan_mirror must be 0, 1 or 2"), get_knob(&wax_hip_engine::scan_mirror), FIRST_SHARD},
@@ -177,7 +176,7 @@ constexpr TuningRow kTuning[] = {
     {"batch_in_wait", set_range(&wax_hip_engine::batch_in_wait, 0, 1, "batch_in_wait must be 0 or 1"), get_knob(&wax_hip_engine::batch_in_wait), FIRST_SHARD},
     {"batch_debug", set_mask(&wax_hip_engine::batch_debug, 4096 | 16384 | 65536, "batch_debug: bits 4096, 16384, 65536 only"), not_get(), FIRST_SHARD},
     {"batch_prof_ptr", set_any(&wax_hip_engine::batch_prof_ptr), not_get(), FIRST_SHARD},
-    {"batch_workspaces", set_fn(set_batch_workspaces, 1, 16, "batch_workspaces must be 1..16"), GET_EXPR(e->bctx_max), FIRST_SHARD},
+    {"batch_workspaces", set_fn(set_batch_workspaces, 1, 16, "batch_workspaces must be 1..16"), GET_EXPR(e->bctxs.cap()), FIRST_SHARD},
     {"batch_first", set_fn(set_batch_first, INT64_MIN, INT64_MAX, nullptr), get_knob(&wax_hip_engine::batch_first), FIRST_SHARD},
     {"batch_growth", set_range(&wax_hip_engine::batch_growth, 1, 64, "batch_growth must be 1..64"), get_knob(&wax_hip_engine::batch_growth), FIRST_SHARD},
     {"batch_slab_mb", set_range(&wax_hip_engine::batch_slab_mb, 1, 4096, "batch_slab_mb must be 1..4096"), get_knob(&wax_hip_engine::batch_slab_mb), FIRST_SHARD},
@@ -289,7 +288,7 @@ int wax_hip_time_scan_kernel(wax_hip_engine* e, const float* query, uint32_t dim
         const int limit = clamp_topk(top_k);
         const int k_eff = (uint64_t)limit < e->count ? limit : (int)e->count;
         if (k_eff > FUSED_MAX_K) { rc = fail(WAX_HIP_ERR_INVALID_ARGUMENT, "time_scan_kernel: top_k must be <= 192"); break; }
-        rc = acquire_slot(e, &s);
+        rc = take_slot(e, &s);
         if (rc != WAX_HIP_OK) break;
         std::memcpy(s->h_query, query, (size_t)dims * sizeof(float));
         ScanArgs a{};
@@ -311,7 +310,7 @@ int wax_hip_time_scan_kernel(wax_hip_engine* e, const float* query, uint32_t dim
         if (err != hipSuccess) { rc = fail(WAX_HIP_ERR_INTERNAL, std::string("time_scan_kernel: ") + hipGetErrorString(err)); break; }
         *out_avg_ms = (double)ms / (double)iters;
     } while (0);
-    if (s) release_slot(e, s);
+    if (s) e->slots.release(s);
     e->lock.unlock_shared();
     return rc;
 }
@@ -328,7 +327,7 @@ int wax_hip_time_stream_read(wax_hip_engine* e, uint32_t iters, double* out_avg_
     do {
         const uint64_t bytes = (e->count * (uint64_t)e->dims * 4ull) & ~15ull;
         if (bytes == 0) { rc = fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine is empty"); break; }
-        rc = acquire_slot(e, &s);
+        rc = take_slot(e, &s);
         if (rc != WAX_HIP_OK) break;
         int grid = (int)e->grid_blocks.load();
         if (grid <= 0) grid = 2048;
@@ -345,7 +344,7 @@ int wax_hip_time_stream_read(wax_hip_engine* e, uint32_t iters, double* out_avg_
         if (err != hipSuccess) { rc = fail(WAX_HIP_ERR_INTERNAL, std::string("time_stream_read: ") + hipGetErrorString(err)); break; }
         *out_avg_ms = (double)ms / (double)iters;
     } while (0);
-    if (s) release_slot(e, s);
+    if (s) e->slots.release(s);
     e->lock.unlock_shared();
     return rc;
 }
