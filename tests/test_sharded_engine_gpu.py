@@ -296,6 +296,28 @@ def test_sharded_batched_device_resident_entry_points(wax, shards):
     empty.close()
 
 
+def test_sharded_batch_with_k_above_the_device_merge_limit_merges_on_the_host(wax):
+    """A batched search with top_k above 192 on a handle: the per-query merge of the shards' parts runs on the host (by key, pads
+    skipped, cut at k). Every shard holds rows (3 000 rows in blocks of 1 024), and at k = 1 000 the last shard has fewer rows than k,
+    so its part ends in pads in the middle of the gathered runs. The keys are ONE engine's."""
+    n, dims, nq = 3_000, 64, 4
+    one, many = pair(wax, 0, dims, 3)
+    corpus = oracle.gaussian_unit_rows(9, n, dims)
+    ids = np.arange(n, dtype=np.uint64) * 5 + 2
+    for eng in (one, many):
+        eng.reserve(n)
+        eng.addBatch(ids, corpus)
+    assert all(many.shardInfo(g)[2] > 0 for g in range(3))
+    queries = oracle.gaussian_unit_queries(nq, dims, seed=31)
+    for k in (193, 1000):
+        a, ca = one.searchBatchHits(queries, k)
+        b, cb = many.searchBatchHits(queries, k)
+        assert a.shape == (nq, k, 2) and np.all(ca == k)
+        assert np.array_equal(a[:, :, 0], b[:, :, 0]), k
+        assert np.array_equal(a, b) and np.array_equal(ca, cb), k
+    one.close(), many.close()
+
+
 @pytest.mark.parametrize("shards", [2, 3])
 def test_sharded_batch_resends_parts_rewritten_at_collect(wax, shards):
     """A shard's [nq][k] part goes to the first device right behind that shard's finish kernel; queries the certificate cannot

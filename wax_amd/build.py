@@ -16,7 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libwaxhip.so")
 SOURCES = ["kernels.hip", "mirror_scan.hip", "mirror8_scan.hip", "multiscan.hip", "batch.hip", "filter.hip", "predicate.hip", "rrf.hip", "compact.hip", "timeline.hip", "grouped.hip", "terms.hip", "engine.hip"]
-HEADERS = ["common.h", "topk.h", "row_math.h", "kernels.h", "mirror_pass.h", "mirror_finish.h", "mirror8_layout.h", "row_columns.h", "derived_rows.h", "work_pool.h", "rw_lock.h", "shard_workers.h", "id_map.h", "multiscan_body.inc", "engine_types.inc", "store_internal.inc", "search_internal.inc", "batch_host.inc", "api_store.inc",
+HEADERS = ["common.h", "topk.h", "row_math.h", "kernels.h", "mirror_pass.h", "mirror_finish.h", "mirror8_layout.h", "row_columns.h", "derived_rows.h", "work_pool.h", "rw_lock.h", "shard_workers.h", "id_map.h", "shard_layout.h", "shard_merge.h", "multiscan_body.inc", "engine_types.inc", "store_internal.inc", "search_internal.inc", "batch_host.inc", "api_store.inc",
            "api_search.inc", "api_batch.inc", "api_shard.inc", "api_fusion_filter.inc", "api_predicate.inc", "filter_host.inc", "search_many.inc", "api_timeline.inc", "api_grouped.inc", "api_terms.inc", "codec.inc", "tuning.inc", "sharded.inc",
            os.path.join(ROOT, "include", "wax_hip.h")]
 ARCH = "gfx950"

@@ -32,6 +32,8 @@
 #include "rw_lock.h"
 #include "shard_workers.h"
 #include "id_map.h"
+#include "shard_layout.h"
+#include "shard_merge.h"
 
 using namespace wax;
 
@@ -44,7 +46,10 @@ using namespace wax;
 // derived_rows.h stands alone in the same way: how far the bf16 mirror, the code mirror and the id table have followed the store
 // (tests/derived_rows/driver.cpp). So does the host-side concurrency, which may use threads and mutexes but no HIP: work_pool.h (the pools
 // of per-call workspaces and the ticket tables), rw_lock.h (the reader/writer lock, the tickets per submitting thread), shard_workers.h
-// (the hand-off to the per-shard threads) and id_map.h (frame id -> row), each with a driver under tests/<name>/driver.cpp.
+// (the hand-off to the per-shard threads) and id_map.h (frame id -> row), each with a driver under tests/<name>/driver.cpp. And so do the
+// host rules of the sharded handle, which need neither a device nor an engine: shard_layout.h (the block size, the tail shard, the moves of
+// a doubling, what a reserve asks of each shard, the slices of a loaded segment, the bases — all from the shards' row counts) and
+// shard_merge.h (G shards' answers -> one: by key, by score, timeline pairs, grouped roots), with drivers of their own.
 //
 //   engine_types.inc       types of the host side: error state, the device guard, scratch slots, workspaces, the device side of the mirrors and the id table, `struct wax_hip_engine`, ticket ownership
 //   store_internal.inc     the store behind the C ABI: clampTopK, the scratch-slot pool, the general-selection workspace, staged appends, growth (MetalVectorEngine.swift:84-117, 330-357, 842-890)
@@ -63,7 +68,7 @@ using namespace wax;
 //   api_grouped.inc        C ABI: wax_hip_set_parents / get_parents, wax_hip_search_grouped, wax_hip_group_stats, wax_hip_group_probe — the parent column and the best roots by their best member, members per root (PhotoRAGOrchestrator.swift:264-317, VideoRAGOrchestrator.swift:273-417)
 //   codec.inc              C ABI: MV2V encoding-2 serialize / deserialize (MetalVectorEngine.swift:682-815)
 //   tuning.inc             C ABI: stats, the tuning registry (set / get), the two timing microbenchmarks
-//   sharded.inc            the multi-GPU handle (one engine per device behind one handle): DESIGN 4.3
+//   sharded.inc            the multi-GPU handle (one engine per device behind one handle): streams, peer copies, RCCL, events, workspaces, one fan-out over the shards and one id router; its layout decisions are shard_layout.h's, its host merges shard_merge.h's
 // ---------------------------------------------------------------------------------------------------------------------------
 #include "engine_types.inc"
 #include "store_internal.inc"

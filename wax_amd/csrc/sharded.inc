@@ -22,6 +22,8 @@
 //     from its own host thread; device 0 merges per query (merge_batch_hits).
 //   * mutations take the handle's exclusive lock; searches its shared lock — the reader/writer contract of
 //     AsyncReadWriteLock (ReadWriteLock.swift:79-156), as for one engine.
+//   * what needs no device lives in two host-only headers, tested on the CPU: the layout decisions in shard_layout.h, the host merges of
+//     the shards' answers in shard_merge.h. This file carries them out.
 #include <dlfcn.h>
 
 #include <functional>
@@ -96,8 +98,7 @@ struct ShardedState {
     std::vector<int> devices;
     std::vector<hipStream_t> streams;       // one per shard, on its device
     hipStream_t merge_stream = nullptr;     // device of shard 0
-    uint64_t block_rows = 0;                // rows at which a shard is full (0 = not chosen yet)
-    uint64_t reserve_hint = 0;
+    ShardLayout layout;                     // block_rows, reserve_hint and every decision that follows from the shards' counts (shard_layout.h)
     WorkPool<ShardSlot> slots{kShardSlots, kShardHardSlots};
     TicketTable<ShardSlot*> tickets;
     std::atomic<int64_t> exchange{0};       // 0 = peer copies (default), 1 = RCCL all-gather
@@ -140,12 +141,20 @@ uint64_t sh_count(const ShardedState* s) {
     return n;
 }
 
+// what the layout decides from
+std::vector<uint64_t> sh_counts(const ShardedState* s) {
+    std::vector<uint64_t> counts;
+    for (auto* e : s->subs) counts.push_back(e->count);
+    return counts;
+}
+
+ShardLayout::Shape sh_shape(const ShardedState* s, uint32_t dims) {
+    return ShardLayout::Shape{s->subs.size(), dims, s->shard_min_mb.load(), WAX_HIP_INITIAL_RESERVE};
+}
+
 void sh_update_bases(ShardedState* s) {
-    uint64_t base = 0;
-    for (auto* e : s->subs) {
-        e->row_base = base;       // under the handle's exclusive lock: no shard search is in flight
-        base += e->count;
-    }
+    const std::vector<uint64_t> bases = ShardLayout::bases(sh_counts(s).data(), s->subs.size());
+    for (size_t g = 0; g < bases.size(); ++g) s->subs[g]->row_base = bases[g];   // under the handle's exclusive lock: no shard search is in flight
 }
 
 // (shard, local row) of a frame id, or shard = -1
@@ -157,15 +166,30 @@ int sh_find(ShardedState* s, uint64_t id, int64_t* local) {
     return -1;
 }
 
-uint64_t round_up64(uint64_t x) { return (x + 63ull) & ~63ull; }
-
-// Rows per shard block for a store announced / started at `want` rows: an even spread, but never less than "shard_min_mb" of rows
-uint64_t sh_block_rows_for(const ShardedState* s, uint64_t want, uint32_t dims) {
-    const uint64_t G = s->subs.size();
-    uint64_t per = std::max<uint64_t>(WAX_HIP_INITIAL_RESERVE, round_up64((want + G - 1) / G));
-    const int64_t mb = s->shard_min_mb.load();
-    if (mb > 0 && G > 1) per = std::max<uint64_t>(per, round_up64((((uint64_t)mb << 20) + (uint64_t)dims * 4 - 1) / ((uint64_t)dims * 4)));
-    return per;
+// The ids of a call by owning shard: per shard the caller positions it owns and their local rows, call order kept inside a shard (so the
+// last entry of a repeated id still wins). Absent ids are in no shard's list. Callers gather their own payload columns through `at`.
+struct ShardRoute {
+    std::vector<uint64_t> at;       // positions in the caller's arrays
+    std::vector<uint64_t> ids;      // frame_ids[at[j]]
+    std::vector<uint64_t> rows;     // local row of ids[j]
+    template <typename T>
+    std::vector<T> gather(const T* column) const {       // (a null column: nothing)
+        std::vector<T> out;
+        for (size_t j = 0; column && j < at.size(); ++j) out.push_back(column[at[j]]);
+        return out;
+    }
+};
+std::vector<ShardRoute> sh_route(ShardedState* s, const uint64_t* frame_ids, uint64_t n) {
+    std::vector<ShardRoute> routes(s->subs.size());
+    for (uint64_t i = 0; i < n; ++i) {
+        int64_t local = -1;
+        const int g = sh_find(s, frame_ids[i], &local);
+        if (g < 0) continue;
+        routes[(size_t)g].at.push_back(i);
+        routes[(size_t)g].ids.push_back(frame_ids[i]);
+        routes[(size_t)g].rows.push_back((uint64_t)local);
+    }
+    return routes;
 }
 
 int sh_load_rccl(ShardedState* s) {
@@ -248,6 +272,37 @@ int sh_take_slot(ShardedState* s, ShardSlot** out, bool holder) {
     return got == PoolGot::exhausted ? fail(WAX_HIP_ERR_INVALID_ARGUMENT, "too many outstanding search tickets (collect some first)") : rc;
 }
 
+// per_shard(g) -> rc on every shard; the lowest failing shard's code and text (a worker's g_last_error is its own thread's) become the
+// caller's through fail().
+enum class FanOut {
+    workers,           // side by side on the persistent workers (each bound to its shard's device); one shard: the caller's thread
+    workers_if_free,   // the same unless another job holds the workers: then the caller's thread at once, and *ran_inline says so
+    serial_stop,       // the caller's thread, shard after shard, stopping at the first failure
+    serial_all,        // the caller's thread, every shard whatever the others returned
+};
+template <typename PerShard>
+int sh_fan_out(ShardedState* s, FanOut mode, PerShard per_shard, bool* ran_inline = nullptr) {
+    const size_t G = s->subs.size();
+    std::vector<int> rcs(G, WAX_HIP_OK);
+    std::vector<std::string> errs(G);
+    const std::function<void(size_t)> one = [&](size_t g) {
+        rcs[g] = per_shard(g);
+        if (rcs[g] != WAX_HIP_OK) errs[g] = g_last_error;
+    };
+    bool on_workers = false;
+    if (mode == FanOut::workers && G > 1) { s->workers.run_all(one); on_workers = true; }
+    else if (mode == FanOut::workers_if_free) on_workers = s->workers.try_run_all(one);
+    if (ran_inline) *ran_inline = !on_workers;
+    if (!on_workers)
+        for (size_t g = 0; g < G; ++g) {
+            one(g);
+            if (rcs[g] != WAX_HIP_OK && mode == FanOut::serial_stop) break;
+        }
+    for (size_t g = 0; g < G; ++g)
+        if (rcs[g] != WAX_HIP_OK) return fail(rcs[g], errs[g]);
+    return WAX_HIP_OK;
+}
+
 // ---- mutations (handle's exclusive lock held) ---------------------------------------------------------------------
 
 // Move every row of shard `from` to the end of shard `to` (same or another device), in chunks through a buffer on
@@ -301,47 +356,25 @@ int sh_move_all(ShardedState* s, size_t from, size_t to) {
     return WAX_HIP_OK;
 }
 
-// Every shard is full: double the block size. New shard h = old shards 2h, 2h+1 (concatenated in order), done in
-// place: shard h was emptied when it served as a source of an earlier target (2h' or 2h'+1 = h with h' < h), and
-// sources 2h, 2h+1 >= h are not yet overwritten.
-int sh_double_blocks(ShardedState* s) {
-    const size_t G = s->subs.size();
-    for (size_t h = 0; 2 * h < G; ++h) {
-        for (size_t src = 2 * h; src <= 2 * h + 1 && src < G; ++src) {
-            if (src == h) continue;                  // h = 0: shard 0 keeps its rows, shard 1 is appended
-            int rc = sh_move_all(s, src, h);
+// The shard that takes the next appended row (and how many it can take). When all are full the layout doubles its blocks
+// (ShardLayout::doubling_moves: in place, in an order that never overwrites a source) and the rows move here.
+int sh_next_tail(ShardedState* s, size_t* shard, uint64_t* room) {
+    while (!s->layout.tail(sh_counts(s).data(), s->subs.size(), shard, room)) {
+        for (const auto& move : ShardLayout::doubling_moves(s->subs.size())) {
+            const int rc = sh_move_all(s, move.first, move.second);
             if (rc != WAX_HIP_OK) {
-                // A failed move left both shards as they were, but earlier moves of this pass have already happened:
-                // the rows are all still there, in global order, yet no longer in blocks of `block_rows`. Bases follow
-                // the counts; appends keep working (sh_tail looks at counts only).
+                // A failed move left both shards as they were, but earlier moves of this pass have already happened: the rows are
+                // all still there, in global order, yet no longer in blocks of `block_rows`. Bases follow the counts; appends keep
+                // working (the tail is found from the counts only).
                 sh_update_bases(s);
                 return rc;
             }
         }
+        s->layout.doubled();
+        s->rebalances++;
+        sh_update_bases(s);
     }
-    s->block_rows *= 2;
-    s->rebalances++;
-    sh_update_bases(s);
     return WAX_HIP_OK;
-}
-
-// The shard that takes the next appended row (and how many it can take), growing the layout when all are full.
-int sh_tail(ShardedState* s, size_t* shard, uint64_t* room) {
-    const size_t G = s->subs.size();
-    for (;;) {
-        size_t tail = 0;
-        for (size_t g = 0; g < G; ++g)
-            if (s->subs[g]->count > 0) tail = g;
-        if (s->subs[tail]->count >= s->block_rows && tail + 1 < G) ++tail;
-        if (s->subs[tail]->count < s->block_rows) {
-            *shard = tail;
-            *room = s->block_rows - s->subs[tail]->count;
-            return WAX_HIP_OK;
-        }
-        if (G == 1) { s->block_rows *= 2; continue; }   // one shard: the block size is only a formality
-        int rc = sh_double_blocks(s);
-        if (rc != WAX_HIP_OK) return rc;
-    }
 }
 
 int sh_add_batch(wax_hip_engine* e, const uint64_t* frame_ids, const float* rows, uint64_t n, uint32_t dims) {
@@ -353,10 +386,7 @@ int sh_add_batch(wax_hip_engine* e, const uint64_t* frame_ids, const float* rows
     WriteGuard w(e->lock);
     if (sh_count(s) + n > 0xffffffffull)
         return fail(WAX_HIP_ERR_CAPACITY, "capacity exceeded: limit 4294967295, requested " + std::to_string(sh_count(s) + n));
-    if (s->block_rows == 0) {   // first rows: a bulk load spreads evenly, anything else starts from the reserve hint
-        const uint64_t want = std::max<uint64_t>(s->reserve_hint, n);
-        s->block_rows = sh_block_rows_for(s, want, e->dims);
-    }
+    s->layout.first_rows(sh_shape(s, e->dims), n);   // a bulk load spreads evenly, anything else starts from the reserve hint
     // Sequential upsert semantics of MetalVectorEngine.addBatch (:384-398): an id that already exists (anywhere, or
     // earlier in this batch) is overwritten in place; new ids are appended in order. Runs of consecutive new ids go to
     // the tail shard as one batch.
@@ -372,7 +402,7 @@ int sh_add_batch(wax_hip_engine* e, const uint64_t* frame_ids, const float* rows
         }
         size_t tail = 0;
         uint64_t room = 0;
-        rc = sh_tail(s, &tail, &room);
+        rc = sh_next_tail(s, &tail, &room);
         if (rc != WAX_HIP_OK) break;
         // extend the run while ids are new (not in any shard, not repeated inside the run) and the shard has room
         IdMap seen;
@@ -411,10 +441,7 @@ int sh_add_batch_device(wax_hip_engine* e, const uint64_t* frame_ids, const floa
             return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "add_batch_device: frame id " + std::to_string(frame_ids[i]) + " already present (append-only path)");
         seen.put(frame_ids[i], 0);
     }
-    if (s->block_rows == 0) {
-        const uint64_t want = std::max<uint64_t>(s->reserve_hint, n);
-        s->block_rows = sh_block_rows_for(s, want, e->dims);
-    }
+    s->layout.first_rows(sh_shape(s, e->dims), n);
     int rc = WAX_HIP_OK;
     uint64_t i = 0;
     float* d_tmp = nullptr;
@@ -423,7 +450,7 @@ int sh_add_batch_device(wax_hip_engine* e, const uint64_t* frame_ids, const floa
     while (i < n && rc == WAX_HIP_OK) {
         size_t tail = 0;
         uint64_t room = 0;
-        rc = sh_tail(s, &tail, &room);
+        rc = sh_next_tail(s, &tail, &room);
         if (rc != WAX_HIP_OK) break;
         const uint64_t m = std::min(room, n - i);
         const float* src = d_rows + i * (uint64_t)dims;
@@ -473,18 +500,13 @@ int sh_remove_batch(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, ui
     if (!frame_ids) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "removeBatch: null input");
     REFUSE_IF_HOLDING(e);
     WriteGuard w(e->lock);
-    std::vector<std::vector<uint64_t>> per(s->subs.size());
-    for (uint64_t i = 0; i < n; ++i) {
-        int64_t local = -1;
-        const int g = sh_find(s, frame_ids[i], &local);
-        if (g >= 0) per[(size_t)g].push_back(frame_ids[i]);              // :426 absent ids are ignored
-    }
+    const std::vector<ShardRoute> per = sh_route(s, frame_ids, n);        // :426 absent ids are ignored
     int rc = WAX_HIP_OK;
     uint64_t total = 0;
     for (size_t g = 0; g < per.size() && rc == WAX_HIP_OK; ++g) {
-        if (per[g].empty()) continue;
+        if (per[g].ids.empty()) continue;
         uint64_t got = 0;
-        rc = wax_hip_remove_batch(s->subs[g], per[g].data(), per[g].size(), &got);
+        rc = wax_hip_remove_batch(s->subs[g], per[g].ids.data(), per[g].ids.size(), &got);
         total += got;
     }
     sh_update_bases(s);
@@ -498,20 +520,11 @@ int sh_reserve(wax_hip_engine* e, uint64_t rows) {
     WriteGuard w(e->lock);
     if (rows > 0xffffffffull)
         return fail(WAX_HIP_ERR_CAPACITY, "capacity exceeded: limit 4294967295, requested " + std::to_string(rows));
-    s->reserve_hint = std::max(s->reserve_hint, rows);
-    const uint64_t per = sh_block_rows_for(s, rows, e->dims);
-    if (sh_count(s) == 0) s->block_rows = per;           // an empty engine adopts the layout the caller announced
-    // shards are filled in order: reserve what this many rows will occupy (a store below one block touches the first device only)
-    const uint64_t blk = std::max(per, s->block_rows);
+    // an empty engine adopts the layout the caller announced; shards are filled in order: reserve what this many rows will occupy
+    // (a store below one block touches the first device only)
+    const std::vector<uint64_t> ask = s->layout.reserve(sh_shape(s, e->dims), rows, sh_counts(s).data());
     int rc = WAX_HIP_OK;
-    uint64_t left = std::max(rows, sh_count(s));
-    for (auto* sub : s->subs) {
-        const uint64_t here = std::min(left, blk);
-        left -= here;
-        if (here == 0) break;
-        rc = wax_hip_reserve(sub, here);
-        if (rc != WAX_HIP_OK) break;
-    }
+    for (size_t g = 0; g < ask.size() && ask[g] > 0 && rc == WAX_HIP_OK; ++g) rc = wax_hip_reserve(s->subs[g], ask[g]);
     return rc;
 }
 
@@ -559,22 +572,15 @@ int sh_submit(wax_hip_engine* e, const float* query, uint32_t dims, int32_t top_
                 break;
             }
             // side by side on the persistent workers (each bound to its shard's device): a fan-out costs one launch time, not G
-            std::vector<int> rcs(G, WAX_HIP_OK);
-            std::vector<std::string> errs(G);
-            const std::function<void(size_t)> one_submit = [&](size_t g) {
-                wax_hip_engine* sub = s->subs[g];
-                if (sub->count == 0 && sub->pend_rows.load() == 0) return;
-                rcs[g] = submit_impl(sub, query, dims, top_k, &sl->sub_tickets[g], false);
-                if (rcs[g] != WAX_HIP_OK) errs[g] = g_last_error;       // thread-local (the worker's, or this thread's below)
-            };
             // (workers busy with a long job — mirror build, filtered search, k > 192 batch —: G launches from this thread, 3 - 4 us each,
             // instead of waiting milliseconds for the workers; submit_impl binds the shard's device itself)
-            if (!s->workers.try_run_all(one_submit)) {
-                for (size_t g = 0; g < G; ++g) one_submit(g);
-                s->inline_fanouts++;
-            }
-            for (size_t g = 0; g < G; ++g)
-                if (rcs[g] != WAX_HIP_OK && rc == WAX_HIP_OK) rc = fail(rcs[g], errs[g]);
+            bool ran_inline = false;
+            rc = sh_fan_out(s, FanOut::workers_if_free, [&](size_t g) {
+                wax_hip_engine* sub = s->subs[g];
+                if (sub->count == 0 && sub->pend_rows.load() == 0) return (int)WAX_HIP_OK;
+                return submit_impl(sub, query, dims, top_k, &sl->sub_tickets[g], false);
+            }, &ran_inline);
+            if (ran_inline) s->inline_fanouts++;
             s->ticket_searches++;
             break;
         }
@@ -673,13 +679,11 @@ int sh_collect(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, float* out
             uint32_t m = 0;
             const int crc = collect_impl(s->subs[g], sl->sub_tickets[g], nullptr, nullptr, 0, &m, part.data(), limit);
             if (crc != WAX_HIP_OK && rc == WAX_HIP_OK) rc = crc;
-            for (uint32_t i = 0; i < limit; ++i)
-                if (part[i].key != KEY_PAD) all.push_back(part[i]);
+            key_merge_add(all, part.data(), limit, KEY_PAD);
         }
         if (rc == WAX_HIP_OK) {
             // every part is sorted: the k best of G sorted runs (keys are unique: a total order, identical at any shard count)
-            std::sort(all.begin(), all.end(), [](const wax_hip_hit& a, const wax_hip_hit& b) { return a.key < b.key; });
-            if (all.size() > limit) all.resize(limit);
+            key_merge_cut(all, limit);
             rc = hits_to_results(e->metric, all.data(), (uint32_t)all.size(), out_ids, out_scores, capacity, out_count);
         }
     } else if (sl->kpad > 0 && rc == WAX_HIP_OK) {
@@ -841,19 +845,8 @@ int sh_batch_submit(wax_hip_engine* e, ShardBatchWork* w, const float* d_queries
     // still run side by side rather than one after the other (a G-fold slowdown otherwise).
     bool blocks = false;
     for (size_t g = 0; g < G && G > 1 && !blocks; ++g) blocks = batch_submit_blocks(s->subs[g], dims, (int32_t)k, nq, k);
-    if (blocks) {
-        std::vector<int> rcs(G, WAX_HIP_OK);
-        std::vector<std::string> errs(G);
-        s->workers.run_all([&](size_t g) {
-            rcs[g] = one(g);
-            if (rcs[g] != WAX_HIP_OK) errs[g] = g_last_error;      // thread-local: carry it to the caller
-        });
-        s->parallel_submits += 1;
-        for (size_t g = 0; g < G && rc == WAX_HIP_OK; ++g)
-            if (rcs[g] != WAX_HIP_OK) rc = fail(rcs[g], errs[g]);
-    } else {
-        for (size_t g = 0; g < G && rc == WAX_HIP_OK; ++g) rc = one(g);
-    }
+    rc = sh_fan_out(s, blocks ? FanOut::workers : FanOut::serial_stop, one);
+    if (blocks) s->parallel_submits += 1;
     if (rc != WAX_HIP_OK) sh_batch_drain(s, w);
     return rc;
 }
@@ -861,34 +854,28 @@ int sh_batch_submit(wax_hip_engine* e, ShardBatchWork* w, const float* d_queries
 int sh_batch_collect(wax_hip_engine* e, ShardBatchWork* w, uint32_t* out_fallbacks) {
     ShardedState* s = e->sh;
     const size_t G = s->subs.size();
-    int rc = WAX_HIP_OK;
     uint32_t fallbacks = 0;
-    std::vector<int> rcs(G, WAX_HIP_OK);
     std::vector<uint32_t> fbs(G, 0), rws(G, 0);
-    std::vector<std::string> errs(G);
-    auto one = [&](size_t g) {
-        if (!w->sub_valid[g]) return;
+    // (every sub-ticket has to be collected, whatever another shard's collect returned)
+    const bool parallel = G > 1 && s->collect_parallel.load() != 0;
+    const int rc = sh_fan_out(s, parallel ? FanOut::workers : FanOut::serial_all, [&](size_t g) {
+        if (!w->sub_valid[g]) return (int)WAX_HIP_OK;
+        int crc = WAX_HIP_OK;
         {
             DeviceGuard dg(s->devices[g]);
-            rcs[g] = batch_collect_device_impl(s->subs[g], w->sub_tickets[g], &fbs[g], &rws[g]);
+            crc = batch_collect_device_impl(s->subs[g], w->sub_tickets[g], &fbs[g], &rws[g]);
         }
         w->sub_valid[g] = 0;
         // the part went to the first device right behind the shard's finish kernel; a full retry or the exact path has since
         // rewritten rows of it (synchronously, inside the collect above): send it again
-        if (rcs[g] == WAX_HIP_OK && rws[g] > 0) rcs[g] = sh_copy_part(s, w, g, s->streams[g]);
-        if (rcs[g] != WAX_HIP_OK) errs[g] = g_last_error;   // thread-local: carry it to the caller
-    };
-    if (G > 1 && s->collect_parallel.load() != 0) {
-        s->workers.run_all(one);
-        s->parallel_collects += 1;
-    } else {
-        for (size_t g = 0; g < G; ++g) one(g);
-    }
+        if (crc == WAX_HIP_OK && rws[g] > 0) crc = sh_copy_part(s, w, g, s->streams[g]);
+        return crc;
+    });
+    if (parallel) s->parallel_collects += 1;
     int settled_on_host = 0;
     for (size_t g = 0; g < G; ++g) {
         fallbacks += fbs[g];
         settled_on_host += rws[g] > 0;
-        if (rcs[g] != WAX_HIP_OK && rc == WAX_HIP_OK) rc = fail(rcs[g], errs[g]);
     }
     s->collect_parallel = settled_on_host >= 2 ? 1 : 0;
     if (out_fallbacks) *out_fallbacks = fallbacks;
@@ -909,13 +896,9 @@ int sh_batch_collect(wax_hip_engine* e, ShardBatchWork* w, uint32_t* out_fallbac
             if (err == hipSuccess) err = hipMemcpy(all.data(), w->d_all, all.size() * sizeof(wax_hip_hit), hipMemcpyDeviceToHost);
             for (uint32_t q = 0; q < nq && err == hipSuccess; ++q) {
                 row.clear();
-                for (size_t g = 0; g < G; ++g)
-                    for (uint32_t i = 0; i < k; ++i) {
-                        const wax_hip_hit& h = all[(g * nq + q) * (size_t)k + i];
-                        if (h.key != KEY_PAD) row.push_back(h);
-                    }
-                std::sort(row.begin(), row.end(), [](const wax_hip_hit& a, const wax_hip_hit& b) { return a.key < b.key; });
-                for (uint32_t i = 0; i < k && i < row.size(); ++i) merged[(size_t)q * w->out_stride + i] = row[i];
+                for (size_t g = 0; g < G; ++g) key_merge_add(row, all.data() + (g * nq + q) * (size_t)k, k, KEY_PAD);
+                key_merge_cut(row, k);
+                std::copy(row.begin(), row.end(), merged.begin() + (size_t)q * w->out_stride);
             }
             if (err == hipSuccess) err = hipMemcpy(w->d_out, merged.data(), merged.size() * sizeof(wax_hip_hit), hipMemcpyHostToDevice);
         }
@@ -1029,26 +1012,11 @@ int sh_search_batch_hits(wax_hip_engine* e, const float* queries, uint32_t nq, u
 }
 
 // ---- filtered search: every shard pre-filters its own rows; the shards are in global row order, so a stable merge by
-// (score desc, shard asc) is the (distance asc, global row asc) order of one engine -------------------------------------
-struct ShardAnswer { const uint64_t* ids; const float* scores; uint32_t n; };
-
-// The shards' answers to one query, in shard order -> the handle's: stable by score descending, so (shard, position) order is kept on
-// ties, then the cut at `limit` and the caller's capacity. Returns the results written.
-struct ShardHit { float score; uint64_t id; };
-static uint32_t merge_shard_results(const std::vector<ShardAnswer>& parts, uint32_t limit, uint32_t capacity, uint64_t* out_ids, float* out_scores,
-                                    std::vector<ShardHit>& all) {   // `all`: scratch, reused by a caller that merges many queries
-    all.clear();
-    for (const ShardAnswer& p : parts)
-        for (uint32_t i = 0; i < p.n; ++i) all.push_back(ShardHit{p.scores[i], p.ids[i]});
-    std::stable_sort(all.begin(), all.end(), [](const ShardHit& a, const ShardHit& b) { return a.score > b.score; });
-    uint32_t m = 0;
-    for (; m < all.size() && m < limit && m < capacity; ++m) { out_ids[m] = all[m].id; out_scores[m] = all[m].score; }
-    return m;
-}
+// (score desc, shard asc) is the (distance asc, global row asc) order of one engine (shard_merge.h: merge_by_score) -----
 
 // One query on a handle: every shard answers on its own rows at the same time (persistent per-shard workers) through `per_shard`
 // (shard engine, ids, scores, capacity, count) — the filtered or the predicate search — and the host merges them
-// (merge_shard_results) under the cut at clamp(top_k) and the caller's capacity.
+// (merge_by_score) under the cut at clamp(top_k) and the caller's capacity.
 template <typename PerShard>
 static int sh_fanout_filtered(wax_hip_engine* e, uint32_t dims, int32_t top_k, uint64_t* out_ids, float* out_scores, uint32_t capacity,
                               uint32_t* out_count, PerShard per_shard, bool caller_locked = false) {
@@ -1062,20 +1030,12 @@ static int sh_fanout_filtered(wax_hip_engine* e, uint32_t dims, int32_t top_k, u
     std::vector<std::vector<uint64_t>> g_ids(G, std::vector<uint64_t>(limit));
     std::vector<std::vector<float>> g_scores(G, std::vector<float>(limit));
     std::vector<uint32_t> g_m(G, 0);
-    std::vector<int> rcs(G, WAX_HIP_OK);
-    std::vector<std::string> errs(G);
-    auto one = [&](size_t g) {
-        rcs[g] = per_shard(s->subs[g], g_ids[g].data(), g_scores[g].data(), limit, &g_m[g]);
-        if (rcs[g] != WAX_HIP_OK) errs[g] = g_last_error;   // thread-local: carry it to the caller
-    };
-    if (G == 1) one(0); else s->workers.run_all(one);
+    const int rc = sh_fan_out(s, FanOut::workers, [&](size_t g) { return per_shard(s->subs[g], g_ids[g].data(), g_scores[g].data(), limit, &g_m[g]); });
+    if (rc != WAX_HIP_OK) return rc;
     std::vector<ShardAnswer> parts(G);
-    for (size_t g = 0; g < G; ++g) {
-        if (rcs[g] != WAX_HIP_OK) return fail(rcs[g], errs[g]);
-        parts[g] = ShardAnswer{g_ids[g].data(), g_scores[g].data(), g_m[g]};
-    }
+    for (size_t g = 0; g < G; ++g) parts[g] = ShardAnswer{g_ids[g].data(), g_scores[g].data(), g_m[g]};
     std::vector<ShardHit> scratch;
-    *out_count = merge_shard_results(parts, limit, capacity, out_ids, out_scores, scratch);
+    *out_count = merge_by_score(parts, limit, capacity, out_ids, out_scores, scratch);
     return WAX_HIP_OK;
 }
 
@@ -1106,24 +1066,15 @@ int sh_set_attributes(wax_hip_engine* e, const uint64_t* frame_ids, const int64_
     ShardedState* s = e->sh;
     REFUSE_IF_HOLDING(e);
     WriteGuard w(e->lock);
-    const size_t G = s->subs.size();
-    std::vector<std::vector<uint64_t>> ids(G);
-    std::vector<std::vector<int64_t>> ts(G);
-    std::vector<std::vector<uint32_t>> fl(G);
-    for (uint64_t i = 0; i < n; ++i) {
-        int64_t local = -1;
-        const int g = sh_find(s, frame_ids[i], &local);
-        if (g < 0) continue;
-        ids[(size_t)g].push_back(frame_ids[i]);
-        if (timestamps) ts[(size_t)g].push_back(timestamps[i]);
-        if (flags) fl[(size_t)g].push_back(flags[i]);
-    }
+    const std::vector<ShardRoute> per = sh_route(s, frame_ids, n);
     uint64_t total = 0;
-    for (size_t g = 0; g < G; ++g) {
-        if (ids[g].empty()) continue;
+    for (size_t g = 0; g < per.size(); ++g) {
+        if (per[g].ids.empty()) continue;
         uint64_t got = 0;
-        const int rc = wax_hip_set_attributes(s->subs[g], ids[g].data(), timestamps ? ts[g].data() : nullptr, flags ? fl[g].data() : nullptr,
-                                              ids[g].size(), &got);
+        const std::vector<int64_t> ts = per[g].gather(timestamps);
+        const std::vector<uint32_t> fl = per[g].gather(flags);
+        const int rc = wax_hip_set_attributes(s->subs[g], per[g].ids.data(), timestamps ? ts.data() : nullptr, flags ? fl.data() : nullptr,
+                                              per[g].ids.size(), &got);
         if (rc != WAX_HIP_OK) return rc;
         total += got;
     }
@@ -1134,28 +1085,22 @@ int sh_set_attributes(wax_hip_engine* e, const uint64_t* frame_ids, const int64_
 int sh_get_attributes(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, int64_t* out_ts, uint32_t* out_flags, uint8_t* out_found) {
     ShardedState* s = e->sh;
     ReadGuard rd(e);
-    const size_t G = s->subs.size();
-    std::vector<std::vector<uint64_t>> ids(G), at(G);
     for (uint64_t i = 0; i < n; ++i) {
-        int64_t local = -1;
-        const int g = sh_find(s, frame_ids[i], &local);
         if (out_ts) out_ts[i] = 0;
         if (out_flags) out_flags[i] = 0u;
         if (out_found) out_found[i] = 0;
-        if (g < 0) continue;
-        ids[(size_t)g].push_back(frame_ids[i]);
-        at[(size_t)g].push_back(i);
     }
-    for (size_t g = 0; g < G; ++g) {
-        const size_t m = ids[g].size();
+    const std::vector<ShardRoute> per = sh_route(s, frame_ids, n);
+    for (size_t g = 0; g < per.size(); ++g) {
+        const size_t m = per[g].ids.size();
         if (m == 0) continue;
         std::vector<int64_t> ts(m);
         std::vector<uint32_t> fl(m);
         std::vector<uint8_t> found(m);
-        const int rc = wax_hip_get_attributes(s->subs[g], ids[g].data(), m, ts.data(), fl.data(), found.data());
+        const int rc = wax_hip_get_attributes(s->subs[g], per[g].ids.data(), m, ts.data(), fl.data(), found.data());
         if (rc != WAX_HIP_OK) return rc;
         for (size_t j = 0; j < m; ++j) {
-            const uint64_t i = at[g][j];
+            const uint64_t i = per[g].at[j];
             if (out_ts) out_ts[i] = ts[j];
             if (out_flags) out_flags[i] = fl[j];
             if (out_found) out_found[i] = found[j];
@@ -1176,25 +1121,11 @@ int sh_timeline(wax_hip_engine* e, int32_t limit, int newest_first, const wax_hi
     std::vector<uint64_t> g_ids(G * L);
     std::vector<int64_t> g_ts(G * L);
     std::vector<uint32_t> g_m(G, 0);
-    std::vector<int> rcs(G, WAX_HIP_OK);
-    std::vector<std::string> errs(G);
-    auto one = [&](size_t g) {
-        rcs[g] = wax_hip_timeline(s->subs[g], limit, newest_first, pred, g_ids.data() + g * L, g_ts.data() + g * L, (uint32_t)limit, &g_m[g]);
-        if (rcs[g] != WAX_HIP_OK) errs[g] = g_last_error;   // thread-local: carry it to the caller
-    };
-    if (G == 1) one(0); else s->workers.run_all(one);
-    std::vector<std::pair<int64_t, uint64_t>> all;
-    for (size_t g = 0; g < G; ++g) {
-        if (rcs[g] != WAX_HIP_OK) return fail(rcs[g], errs[g]);
-        for (uint32_t i = 0; i < g_m[g]; ++i) all.emplace_back(newest_first != 0 ? ~g_ts[g * L + i] : g_ts[g * L + i], g_ids[g * L + i]);
-    }
-    std::sort(all.begin(), all.end());                       // lexicographic: signed t', then unsigned frame id
-    const size_t n = std::min(all.size(), std::min(L, (size_t)capacity));
-    for (size_t i = 0; i < n; ++i) {
-        out_ids[i] = all[i].second;
-        if (out_ts) out_ts[i] = newest_first != 0 ? ~all[i].first : all[i].first;
-    }
-    *out_count = (uint32_t)n;
+    const int rc = sh_fan_out(s, FanOut::workers, [&](size_t g) {
+        return wax_hip_timeline(s->subs[g], limit, newest_first, pred, g_ids.data() + g * L, g_ts.data() + g * L, (uint32_t)limit, &g_m[g]);
+    });
+    if (rc != WAX_HIP_OK) return rc;
+    *out_count = merge_timeline(g_ids.data(), g_ts.data(), g_m.data(), G, L, newest_first != 0, L, capacity, out_ids, out_ts);
     return WAX_HIP_OK;
 }
 
@@ -1203,20 +1134,12 @@ int sh_set_parents(wax_hip_engine* e, const uint64_t* frame_ids, const uint64_t*
     ShardedState* s = e->sh;
     REFUSE_IF_HOLDING(e);
     WriteGuard w(e->lock);
-    const size_t G = s->subs.size();
-    std::vector<std::vector<uint64_t>> ids(G), par(G);
-    for (uint64_t i = 0; i < n; ++i) {
-        int64_t local = -1;
-        const int g = sh_find(s, frame_ids[i], &local);
-        if (g < 0) continue;
-        ids[(size_t)g].push_back(frame_ids[i]);
-        par[(size_t)g].push_back(parent_ids[i]);
-    }
+    const std::vector<ShardRoute> per = sh_route(s, frame_ids, n);
     uint64_t total = 0;
-    for (size_t g = 0; g < G; ++g) {
-        if (ids[g].empty()) continue;
+    for (size_t g = 0; g < per.size(); ++g) {
+        if (per[g].ids.empty()) continue;
         uint64_t got = 0;
-        const int rc = wax_hip_set_parents(s->subs[g], ids[g].data(), par[g].data(), ids[g].size(), &got);
+        const int rc = wax_hip_set_parents(s->subs[g], per[g].ids.data(), per[g].gather(parent_ids).data(), per[g].ids.size(), &got);
         if (rc != WAX_HIP_OK) return rc;
         total += got;
     }
@@ -1228,13 +1151,21 @@ int sh_get_parents(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, uin
     ShardedState* s = e->sh;
     ReadGuard rd(e);
     for (uint64_t i = 0; i < n; ++i) {
-        int64_t local = -1;
-        const int g = sh_find(s, frame_ids[i], &local);
         if (out_parents) out_parents[i] = WAX_HIP_NO_PARENT;
         if (out_found) out_found[i] = 0;
-        if (g < 0) continue;
-        const int rc = wax_hip_get_parents(s->subs[(size_t)g], frame_ids + i, 1, out_parents ? out_parents + i : nullptr, out_found ? out_found + i : nullptr);
+    }
+    const std::vector<ShardRoute> per = sh_route(s, frame_ids, n);
+    for (size_t g = 0; g < per.size(); ++g) {
+        const size_t m = per[g].ids.size();
+        if (m == 0) continue;
+        std::vector<uint64_t> parents(m);
+        std::vector<uint8_t> found(m);
+        const int rc = wax_hip_get_parents(s->subs[g], per[g].ids.data(), m, parents.data(), found.data());
         if (rc != WAX_HIP_OK) return rc;
+        for (size_t j = 0; j < m; ++j) {
+            if (out_parents) out_parents[per[g].at[j]] = parents[j];
+            if (out_found) out_found[per[g].at[j]] = found[j];
+        }
     }
     return WAX_HIP_OK;
 }
@@ -1256,39 +1187,25 @@ int sh_search_grouped(wax_hip_engine* e, const float* query, uint32_t dims, int3
     const size_t G = s->subs.size();
     const uint32_t L = (uint32_t)limit, P = members ? 1u : 0u;
     std::vector<std::vector<int64_t>> raw(G);
-    std::vector<int> rcs(G, WAX_HIP_OK);
-    std::vector<std::string> errs(G);
-    auto one = [&](size_t g) {
-        rcs[g] = grouped_raw(s->subs[g], query, dims, limit, (int32_t)P, pred, raw[g]);
-        if (rcs[g] != WAX_HIP_OK) errs[g] = g_last_error;   // thread-local: carry it to the caller
-    };
-    if (G == 1) one(0); else s->workers.run_all(one);
-    struct Best { int64_t dist; int64_t key; uint64_t member; };
-    std::map<uint64_t, Best> by_root;
+    const int rc = sh_fan_out(s, FanOut::workers, [&](size_t g) { return grouped_raw(s->subs[g], query, dims, limit, (int32_t)P, pred, raw[g]); });
+    if (rc != WAX_HIP_OK) return rc;
+    GroupMerge merge;
     for (size_t g = 0; g < G; ++g) {
-        if (rcs[g] != WAX_HIP_OK) return fail(rcs[g], errs[g]);
         const int64_t* r = raw[g].data();
         const uint32_t n = *reinterpret_cast<const uint32_t*>(r + 2u * (size_t)L);
         const int64_t* keys = r + 2u * (size_t)L + 1u;
-        for (uint32_t i = 0; i < n && i < L; ++i) {
-            const Best b{r[L + i], members ? keys[i] : KEY_PAD, members ? (uint64_t)keys[(size_t)L + i] : ID_PAD};
-            auto it = by_root.find((uint64_t)r[i]);
-            if (it == by_root.end()) by_root.emplace((uint64_t)r[i], b);
-            else if (b.dist < it->second.dist) it->second = b;
-        }
+        for (uint32_t i = 0; i < n && i < L; ++i)
+            merge.offer((uint64_t)r[i], GroupBest{r[L + i], members ? keys[i] : KEY_PAD, members ? (uint64_t)keys[(size_t)L + i] : ID_PAD});
     }
-    std::vector<std::pair<int64_t, uint64_t>> order;
-    order.reserve(by_root.size());
-    for (const auto& kv : by_root) order.emplace_back(kv.second.dist, kv.first);
-    std::sort(order.begin(), order.end());                   // lexicographic: signed distance bits, then unsigned root id
+    const std::vector<std::pair<int64_t, uint64_t>> order = merge.first(L);   // (signed distance bits, root id)
     uint32_t kept = 0;
-    for (size_t i = 0; i < order.size() && i < (size_t)L; ++i) {
+    for (size_t i = 0; i < order.size(); ++i) {
         const float score = group_score(e->metric, unorder_bits((int32_t)order[i].first));
         if (has_min_score && score < min_score) continue;
         out_root_ids[kept] = order[i].second;
         out_root_scores[kept] = score;
         if (members) {
-            const Best& b = by_root[order[i].second];
+            const GroupBest& b = merge.best(order[i].second);
             out_member_ids[kept] = b.member;                 // (the group's own distance: it passed the cut with the group)
             out_member_scores[kept] = group_score(e->metric, key_distance(b.key));
         }
@@ -1318,14 +1235,12 @@ int sh_set_terms(wax_hip_engine* e, const uint64_t* frame_ids, uint64_t n, const
     REFUSE_IF_HOLDING(e);
     WriteGuard w(e->lock);
     const size_t G = s->subs.size();
+    const std::vector<ShardRoute> per = sh_route(s, frame_ids, n);
     std::vector<TermRows> rows(G);
     uint64_t applied = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        int64_t local = -1;
-        const int g = sh_find(s, frame_ids[i], &local);
-        if (g < 0) continue;
-        ++applied;
-        rows[(size_t)g].emplace_back((uint64_t)local, i);
+    for (size_t g = 0; g < G; ++g) {
+        applied += per[g].at.size();
+        for (size_t j = 0; j < per[g].at.size(); ++j) rows[g].emplace_back(per[g].rows[j], per[g].at[j]);
     }
     std::vector<std::unique_ptr<WriteGuard>> sub_locks;        // (in shard order; searches of the shards' workers hold their shared locks)
     for (size_t g = 0; g < G; ++g) {
@@ -1401,25 +1316,20 @@ int sh_search_batch_predicate(wax_hip_engine* e, const float* queries, uint32_t 
     std::vector<std::vector<uint64_t>> g_ids(G, std::vector<uint64_t>((size_t)nq * limit));
     std::vector<std::vector<float>> g_scores(G, std::vector<float>((size_t)nq * limit));
     std::vector<std::vector<uint32_t>> g_m(G, std::vector<uint32_t>(nq, 0));
-    std::vector<int> rcs(G, WAX_HIP_OK);
-    std::vector<std::string> errs(G);
-    auto one = [&](size_t g) {
+    const int rc = sh_fan_out(s, FanOut::workers, [&](size_t g) {
         // (term_begin / term_len null: wax_hip_search_batch_predicate itself; a row's terms live with the shard that owns the row)
-        rcs[g] = wax_hip_search_batch_terms(s->subs[g], queries, nq, dims, top_k, allow, n_allow_ids, allow_begin, allow_len, nullptr, preds,
-                                            required_terms, n_required_terms, term_begin, term_len, g_ids[g].data(), g_scores[g].data(), limit,
-                                            g_m[g].data());
-        if (rcs[g] != WAX_HIP_OK) errs[g] = g_last_error;   // thread-local: carry it to the caller
-    };
-    if (G == 1) one(0); else s->workers.run_all(one);
-    for (size_t g = 0; g < G; ++g)
-        if (rcs[g] != WAX_HIP_OK) return fail(rcs[g], errs[g]);
+        return wax_hip_search_batch_terms(s->subs[g], queries, nq, dims, top_k, allow, n_allow_ids, allow_begin, allow_len, nullptr, preds,
+                                          required_terms, n_required_terms, term_begin, term_len, g_ids[g].data(), g_scores[g].data(), limit,
+                                          g_m[g].data());
+    });
+    if (rc != WAX_HIP_OK) return rc;
     std::vector<ShardAnswer> parts(G);
     std::vector<ShardHit> scratch;
     for (uint32_t q = 0; q < nq; ++q) {
         for (size_t g = 0; g < G; ++g) parts[g] = ShardAnswer{g_ids[g].data() + (size_t)q * limit, g_scores[g].data() + (size_t)q * limit, g_m[g][q]};
         uint64_t* ids = out_ids + (size_t)q * out_stride;
         float* scores = out_scores + (size_t)q * out_stride;
-        uint32_t m = merge_shard_results(parts, limit, out_stride, ids, scores, scratch);
+        uint32_t m = merge_by_score(parts, limit, out_stride, ids, scores, scratch);
         if (min_scores) apply_min_score(min_scores[q], ids, scores, &m);
         out_counts[q] = m;
     }
@@ -1473,12 +1383,13 @@ int sh_deserialize(wax_hip_engine* e, const uint8_t* data, size_t len) {
     REFUSE_IF_HOLDING(e);
     WriteGuard w(e->lock);
     const size_t G = s->subs.size();
-    s->block_rows = std::max(sh_block_rows_for(s, n, dims), s->block_rows);   // (a segment below "shard_min_mb" loads into the first shard alone)
+    s->layout.segment(sh_shape(s, dims), n);   // (a segment below "shard_min_mb" loads into the first shard alone)
     const uint8_t* vec = data + 36;
     const uint8_t* idp = data + 36 + vec_len + 8;
     int rc = WAX_HIP_OK;
     for (size_t g = 0; g < G && rc == WAX_HIP_OK; ++g) {
-        const uint64_t lo = std::min<uint64_t>(n, g * s->block_rows), hi = std::min<uint64_t>(n, (g + 1) * s->block_rows);
+        uint64_t lo = 0, hi = 0;
+        s->layout.slice(g, n, &lo, &hi);
         const uint64_t m = hi - lo;
         // the shard's slice as a segment of its own: the single-device deserialize keeps its exact semantics
         // (duplicate ids stay separate rows, first row wins the id map, :809-811)
@@ -1550,7 +1461,7 @@ int sh_set_tuning(wax_hip_engine* e, const std::string& k, int64_t value) {
         REFUSE_IF_HOLDING(e);
         WriteGuard w(e->lock);
         s->shard_min_mb = value;
-        if (sh_count(s) == 0) s->block_rows = 0;                  // an empty handle chooses again at its first rows / reserve
+        if (sh_count(s) == 0) s->layout.block_rows = 0;                  // an empty handle chooses again at its first rows / reserve
         return WAX_HIP_OK;
     }
     for (auto* sub : s->subs) {   // everything else is a per-shard setting, checked by its row (tuning.inc)
@@ -1574,7 +1485,7 @@ int64_t sh_get_tuning(wax_hip_engine* e, const std::string& k) {
         if (s->rccl.CommCount && s->rccl.CommCount(s->comms[0], &n) == 0) return n;
         return (int64_t)s->comms.size();
     }
-    if (k == "block_rows") return (int64_t)s->block_rows;
+    if (k == "block_rows") return (int64_t)s->layout.block_rows;
     if (k == "ticket_path") return s->ticket_path.load();
     if (k == "shard_min_mb") return s->shard_min_mb.load();
     if (k == "ticket_searches") return (int64_t)s->ticket_searches.load();
