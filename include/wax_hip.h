@@ -207,6 +207,23 @@ int wax_hip_search_submit(wax_hip_engine* e, const float* query, uint32_t dims, 
 int wax_hip_search_collect(wax_hip_engine* e, uint64_t ticket,
                            uint64_t* out_ids, float* out_scores, uint32_t out_capacity, uint32_t* out_count);
 
+/* One blocking query for the k the callers really send: UnifiedSearch asks the vector lane for candidateLimit = max(topK,
+ * min(3 topK, 1000)) rows (UnifiedSearch.swift:1195-1200), so recall's 10 arrives as 30, FastRAG's 24 as 72, PhotoRAG's 200 and
+ * VideoRAG's 400 as 600 and 1 000. For 32 < top_k <= 1024 the store's 8-bit code mirror (bits = 8) or bf16 mirror (bits = 16) is
+ * streamed once, up to 1 024 (top_k <= 256) or 4 096 candidates under a sound bound on every other row's key are re-scored in f32,
+ * and the answer is returned when its certificate holds; otherwise — and where no mirror can be prepared, or the store's shape has
+ * no mirror pass — the f32 scan of wax_hip_search answers on the spot. Either way hits_out[top_k] is wax_hip_search's answer for the
+ * same arguments as raw hits (ascending key, padded with key = INT64_MAX; wax_hip_hits_to_results gives ids and scores), *count_out
+ * the hits that are not padding. bits = 0: the code mirror unless the engine's "mirror_bits" is 16 or its breaker holds (a ticket's rules; only this mode feeds
+ * the breaker — an explicit 8 neither asks nor tells it).
+ * top_k: 1 to 1024 (WAX_HIP_ERR_INVALID_ARGUMENT otherwise); top_k <= 32 is forwarded to the existing search. stats_out (may be
+ * NULL) receives eight words: the mirror streamed (8, 16, 0 = none), certified (0 / 1), the candidates re-scored, what gave their
+ * bound (0 = every row was listed, 1 = the smallest last key of a full workgroup list, 2 = the listed key of rank C), the workgroup
+ * lists, C, 1 if the f32 scan re-ran the query, 0. The call neither parks nor shares a pass, takes no tuning key and adds no
+ * counter. A sharded handle answers with its search fan-out (mirror streamed = 0; the row word of a hit's key is its rank). */
+int wax_hip_search_wide(wax_hip_engine* e, const float* query, uint32_t dims, uint32_t top_k, uint32_t bits, wax_hip_hit* hits_out,
+                        uint32_t* count_out, uint64_t* stats_out);
+
 /* nq queries, row-major nq x dims. out_ids/out_scores are nq rows of out_stride entries (query q's
  * results start at q * out_stride; at most out_stride are written per query); out_counts[nq]. */
 int wax_hip_search_batch(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
@@ -849,6 +866,15 @@ int wax_hip_mirror8_keys(wax_hip_engine* e, const float* query, float* out_keys,
  * (the gathered prefixes where they fit its buffer, else the k-way merge), out_merged[64] = the k-way merge alone, *out_gathered =
  * 1 where the gather answered. Blocking. */
 int wax_hip_mirror_select_probe(const int64_t* lists, uint32_t n_lists, int64_t* out_selected, int64_t* out_merged, int32_t* out_gathered);
+/* Diagnostic of the first stage of wax_hip_search_wide (k lies in 33 to 1 024 because of candidateLimit, UnifiedSearch.swift:1195-1200;
+ * tests hold the stage to its definition through it, no product path calls it). lists_host = `lists` (1 to 512) lists of 64 keys,
+ * ascending, padded with INT64_MAX, no key twice; c = 1024 or 4096. A list is full if its last slot is no padding; T = the smallest
+ * last key of a full list (INT64_MAX without one); K_C = the key of 0-based rank c among all listed keys (INT64_MAX with no more
+ * than c of them); *bound_out = B = min(T, K_C); candidates_out[c] = the listed keys < B in any order, INT64_MAX behind them,
+ * *count_out their number; *source_out = 0 where B is INT64_MAX, 1 where B = T (also when K_C equals it), 2 where B = K_C < T.
+ * On the current device, blocking. */
+int wax_hip_mirror_wide_probe(const int64_t* lists_host, int32_t lists, uint32_t c, int64_t* candidates_out, uint32_t* count_out,
+                              int64_t* bound_out, uint32_t* source_out);
 /* Diagnostic of the selection frame of a mirror pass — the wave lists, their prunes and the workgroup merge — on keys the caller
  * makes up (tests hold it to a host model through it; no product path calls it). `keys` = nq (1 to 4) arrays of n_slots (1 to 2^24)
  * keys, one per row slot and query; INT64_MAX marks a slot that is not offered to that query (a tail row, a masked row), and no

@@ -190,6 +190,9 @@ SIGNATURES: Dict[str, tuple] = {
     "wax_hip_mirror8_keys": (ctypes.c_int, [_engine_p, _f32p, _f32p, ctypes.c_uint64]),
     "wax_hip_mirror_select_probe": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.c_uint32, ctypes.POINTER(ctypes.c_int64),
                                                    ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)]),
+    "wax_hip_search_wide": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _hitp, _u32p, _u64p]),
+    "wax_hip_mirror_wide_probe": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int64),
+                                                 _u32p, ctypes.POINTER(ctypes.c_int64), _u32p]),
     "wax_hip_mirror_lists_probe": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
                                                   ctypes.POINTER(ctypes.c_int64)]),
     "wax_hip_timeline": (ctypes.c_int, [_engine_p, ctypes.c_int32, ctypes.c_int, ctypes.POINTER(RowPredicate), _u64p,

@@ -200,6 +200,18 @@ int wax_hip_search_collect(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids
     return collect_impl(e, ticket, out_ids, out_scores, out_capacity, out_count, nullptr, 0);
 }
 
+// A scan that died part-way leaves its fused-merge ticket half counted; no later scan on this slot could ever be "last arriver"
+// again and callers would read stale hits with no error. Re-arm it (best effort: after a device fault the runtime usually refuses
+// this too, and every later call on the slot then fails loudly as well). The error already recorded stays the one reported.
+static void rearm_slot(Slot* s) {
+    std::string keep = g_last_error;
+    (void)hipStreamSynchronize(s->stream);
+    (void)hipMemsetAsync(partials_ticket(s->d_partials), 0, 128, s->stream);
+    (void)hipStreamSynchronize(s->stream);
+    (void)hipGetLastError();
+    g_last_error = keep;
+}
+
 static int collect_impl(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, float* out_scores, uint32_t capacity,
                         uint32_t* out_count, wax_hip_hit* out_hits, uint32_t hits_cap, bool caller_locked) {
     if (!e || !out_count) return fail(WAX_HIP_ERR_INVALID_ARGUMENT, "engine/out_count is null");
@@ -303,15 +315,7 @@ static int collect_impl(wax_hip_engine* e, uint64_t ticket, uint64_t* out_ids, f
         }
         if (err != hipSuccess) {
             rc = fail(WAX_HIP_ERR_INTERNAL, std::string("search failed on device: ") + hipGetErrorString(err));
-            // a scan that died part-way leaves its fused-merge ticket half counted; no later scan on this slot could ever be
-            // "last arriver" again and callers would read stale hits with no error. Re-arm it (best effort: after a device
-            // fault the runtime usually refuses this too, and every later call on the slot then fails loudly as well).
-            std::string keep = g_last_error;
-            (void)hipStreamSynchronize(s->stream);
-            (void)hipMemsetAsync(partials_ticket(s->d_partials), 0, 128, s->stream);
-            (void)hipStreamSynchronize(s->stream);
-            (void)hipGetLastError();
-            g_last_error = keep;
+            rearm_slot(s);
         } else if (!deferred) {
             if (s->timed) {
                 float ms = 0.f;

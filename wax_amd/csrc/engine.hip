@@ -57,6 +57,7 @@ using namespace wax;
 //   batch_host.inc         batched queries, host side: the incremental bf16 mirror and id table, pooled batch workspaces, the one-pass planner, the launch chain (`batch_enqueue`) and the exactness ladder behind it
 //   api_store.inc          C ABI: availability, create / destroy, accessors, reserve / add / add_batch / add_batch_device / apply_put_embeddings / remove / remove_batch
 //   api_search.inc         C ABI: search_submit / search_collect / search, result capacity; the routing of predicate tickets
+//   api_wide.inc           C ABI: wax_hip_search_wide — one blocking query for k up to 1 024 from a mirror pass and the wide finish (mirror_wide.hip) — and wax_hip_mirror_wide_probe
 //   api_batch.inc          C ABI: search_batch[_hits], the device-resident and ticketed batched entry points
 //   api_shard.inc          C ABI: the one-rank-per-GPU entry points (set_row_base, search_shard_device, merge_hits_device, merge_batch_hits_device, hits_to_results)
 //   api_fusion_filter.inc  C ABI: reciprocal-rank fusion
@@ -76,6 +77,7 @@ using namespace wax;
 #include "batch_host.inc"
 #include "api_store.inc"
 #include "api_search.inc"
+#include "api_wide.inc"
 #include "api_batch.inc"
 #include "api_shard.inc"
 #include "api_fusion_filter.inc"

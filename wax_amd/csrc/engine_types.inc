@@ -66,6 +66,9 @@ struct Slot {
     uint64_t dist_cap = 0;
     SelectWork sw{};
     bool sw_ready = false;
+    // the wide mirror finish (wax_hip_search_wide), allocated on first use: [MIRROR_WIDE_MAX_C] candidate keys, as many exact keys,
+    // MIRROR_WIDE_CTL control words
+    int64_t* d_wide = nullptr;
     // per-ticket state
     int k_eff = 0;
     bool timed = false;

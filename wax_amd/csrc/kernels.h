@@ -134,7 +134,9 @@ struct alignas(16) MirrorScanArgsQ {
 static_assert(sizeof(MirrorScanArgsQ<768>) <= 4096, "HIP kernel arguments are limited to 4 KB");
 bool mirror_scan_supported(uint32_t dims, int metric);
 // Two launches on `st`: mirror_scan_kernel (the event pair of launch_timing(), if armed, binds to it) and mirror_finish_kernel.
-hipError_t launch_mirror_scan(const MirrorScanArgs& args, const float* query, int metric, int grid_cap, hipStream_t st);
+// pass_alone != nullptr: the pass alone, for the wide finish behind it (mirror_wide.hip: args.k up to MIRROR_WIDE_MAX_K; the narrow
+// finish is not enqueued) — *pass_alone = the workgroups launched, which is the number of lists in args.partials.
+hipError_t launch_mirror_scan(const MirrorScanArgs& args, const float* query, int metric, int grid_cap, hipStream_t st, int* pass_alone = nullptr);
 // The same two launches under a row bitmap (predicate.hip's: every word written, bits of rows >= n_rows clear): mirror_scan_masked_kernel
 // loads only the chunks (mirror_masked_chunk_rows(dims) aligned rows: 16 at 384-d, 8 at 768-d) that hold a passing row and offers only
 // passing rows; the finish is unchanged. The caller sends only bitmaps with more than MIRROR_KP passing rows: fewer cannot certify.
@@ -199,7 +201,7 @@ struct Mirror8GroupArgs {
     const float* meta;
 };
 hipError_t launch_mirror8_scan(const MirrorScanArgs& args, const unsigned char* codes, const float* meta, const float* query, int metric,
-                               int grid_cap, hipStream_t st);
+                               int grid_cap, hipStream_t st, int* pass_alone = nullptr);   // (pass_alone: as launch_mirror_scan's)
 hipError_t launch_mirror8_group(const MirrorGroupArgs& args, const unsigned char* codes, const float* meta, int nq, int metric,
                                 int grid_cap, hipStream_t st);
 // The pass of 1 <= nq <= MIRROR_MAX_NQ members of which at least one has a MirrorMember::bitmap (every word written, bits of rows >=
@@ -216,6 +218,39 @@ hipError_t launch_mirror8_keys(const MirrorScanArgs& args, const unsigned char* 
 // where mirror8_layout.h puts them, and a range may begin or end inside a 16-row tile (its other rows are left as they are).
 hipError_t launch_mirror8_build(const float* src, uint64_t first_row, uint32_t n_rows, uint32_t dims, int normalize, unsigned char* codes,
                                 float* meta, unsigned int* max_bits, hipStream_t st);
+
+// ---- mirror_wide.hip: the finish of one query for 32 < k <= MIRROR_WIDE_MAX_K behind a pass over either mirror ("The wide
+// finish") ----
+// A pass leaves `lists` sorted lists of MIRROR_KP approximate keys whatever k is. Three launches turn them into the answer:
+//   select   one workgroup: B = min(T, K_C) — T the smallest last key of a full list, K_C the listed key of rank C — and the listed keys
+//            below B, at most C of them, compacted into cand[C] (KEY_PAD behind). Every row of the store that is not a candidate has
+//            a key >= B.
+//   rescore  C / rows-per-workgroup workgroups: row_distance at the f32 scan's shape for every candidate -> exact[C]
+//   finish   one workgroup: the exact keys sorted in LDS, kpad hits, the certificate (B == KEY_PAD, or dist(B) - eps > d_k)
+constexpr int MIRROR_WIDE_MAX_K = 1024;     // candidateLimit's cap is 1 000 (UnifiedSearch.swift:1195-1200)
+constexpr int MIRROR_WIDE_MAX_C = 4096;
+// candidates re-scored for top-k: 4 k at the top of each band
+inline int mirror_wide_candidates(int k) { return k <= 256 ? 1024 : MIRROR_WIDE_MAX_C; }
+enum { WIDE_BOUND_ALL = 0, WIDE_BOUND_TAIL = 1, WIDE_BOUND_RANK = 2 };   // what gave B: every row is listed, T, K_C
+constexpr int MIRROR_WIDE_CTL = 4;          // control words behind the selection: {m, source, B, 0}
+struct MirrorWideArgs {
+    MirrorScanArgs a;               // the pass's own, `lists` set: partials, store, ids, hits, certified, max_bits, k, kpad, q_norm
+    int64_t* cand;                  // [c] the candidates' approximate keys
+    int64_t* exact;                 // [c] their exact keys
+    uint64_t* ctl;                  // [MIRROR_WIDE_CTL] device words
+    uint64_t* report;               // [MIRROR_WIDE_CTL] the same words for the host (pinned host memory)
+    int32_t c;
+};
+template <int DIMS>
+struct alignas(16) MirrorWideArgsQ {
+    MirrorWideArgs w;
+    alignas(16) float q[DIMS];
+};
+static_assert(sizeof(MirrorWideArgsQ<768>) <= 4096, "HIP kernel arguments are limited to 4 KB");
+// the selection alone (also wax_hip_mirror_wide_probe's): d_lists [lists][MIRROR_KP], 1 <= lists <= SCAN_KWAY_MERGE_GRID, c 1024 or 4096
+hipError_t launch_mirror_wide_select(const int64_t* d_lists, int lists, int c, int64_t* d_cand, uint64_t* d_ctl, hipStream_t st);
+// the three launches on `st`; bits = 8 (Mirror8Slack) or 16 (Bf16Eps): the mirror the pass streamed
+hipError_t launch_mirror_wide(const MirrorWideArgs& w, const float* query, int metric, int bits, hipStream_t st);
 
 struct ScanVariantInfo {
     int unroll;          // row groups in flight per wave iteration

@@ -278,34 +278,6 @@ inline hipError_t with_code8_pass(uint32_t n_rows, uint32_t dims, int metric, in
     }, hipErrorInvalidValue);
 }
 
-// What the per-row err does not hold, as a bound on (lb as computed) - (the row's exact distance as row_distance computes it):
-//  (a) the query's digits and the combine. s is delta * scale * S~ with S~ the twice-rounded 16384 P_a + 128 P_b + P_c (the plane
-//      sums themselves are exact integers). With q^ = delta * m and x~ = scale * code:
-//        - the query's rounding: |q^.x~ - q.x~| <= ||q^ - q|| ||x~|| <= (delta sqrt(D) / 2) (||x^|| + err), and delta = max|q| / M
-//          <= ||q|| / 1 040 319, so at most 0.625 sqrt(D) / 1 040 319 ||q|| (||v|| + err) = 1.18e-5 ||q|| (||v|| + err) at 384-d
-//          (err <= ||v||: < 2.4e-5 ||q|| ||v|| even for a row coded as badly as can be);
-//        - the two fma roundings: each is relative 2^-24 of a partial sum, and by Cauchy-Schwarz delta scale |16384 P_a| (and the
-//          smaller partial sums) <= ~||q^|| ||x~|| <= 1.01 ||q|| ||v||: < 4 u ||q|| ||v||.
-//      Together < (1.25 sqrt(D) / 1 040 319 + 4 u) ||q|| ||v|| = 2.4e-5 (384-d), 3.4e-5 (768-d), below the
-//      8192 u sqrt(D) / 127 ||q|| max||v|| = 7.5e-5 (384-d), 1.07e-4 (768-d) that this term has always been (it was sized for the f32
-//      accumulation of the biased sum): both scale with sqrt(D), the factor of three between them holds at every D. The value stays;
-//  (b) 3 D u ||q|| max||v|| for the f32 sums and normalisations on either side, as in the bf16 certificate;
-//  (c) the roundings of delta * scale * S, / ||q||, the two subtractions, and the exact distance's own ~1e-6: 3e-6 (cosine),
-//      3e-6 (1 + ||q|| max||v||) (dot) — a row that matters has |lb| <= 2 (1 + ||q|| max||v||).
-// Cosine divides by ||q||, so both norms are 1 there.
-struct Mirror8Slack {
-    template <int DIMS, int METRIC>
-    static __device__ __forceinline__ float eps(const MirrorScanArgs& a) {
-        const double qn = METRIC == M_COS ? 1.0 + 1e-6 : (double)a.q_norm;
-        const double vn = METRIC == M_COS ? 1.0 + 1e-6 : (double)__uint_as_float(a.max_bits[0]);
-        const double u = 5.97e-8;
-        const double acc = 8192.0 * u * __builtin_sqrt((double)DIMS) / 127.0;
-        const double both = (acc + 3.0 * (double)DIMS * u) * qn * vn * 1.001;
-        const float s = METRIC == M_COS ? (float)(both + 3e-6) : (float)(both + 3e-6 * (1.0 + qn * vn));
-        return nextafterf(s, __builtin_inff());
-    }
-};
-
 }  // namespace
 
 template <int DIMS, int METRIC>
@@ -470,8 +442,9 @@ __global__ __launch_bounds__(256) void mirror8_kernel(const float* __restrict__ 
 }
 
 hipError_t launch_mirror8_scan(const MirrorScanArgs& args, const unsigned char* codes, const float* meta, const float* query, int metric,
-                               int grid_cap, hipStream_t st) {
-    if (!mirror_launch_ok(args, metric, MIRROR8_MAX_K) || codes == nullptr || meta == nullptr || args.max_bits == nullptr)
+                               int grid_cap, hipStream_t st, int* pass_alone) {
+    if (!mirror_launch_ok(args, metric, pass_alone != nullptr ? MIRROR_WIDE_MAX_K : MIRROR8_MAX_K) || codes == nullptr || meta == nullptr ||
+        args.max_bits == nullptr)
         return hipErrorInvalidValue;
     return with_code8_pass(args.n_rows, args.dims, metric, grid_cap, [&](auto s, auto m, int grid) {
         constexpr int D = decltype(s)::DIMS, M = decltype(m)::value;
@@ -482,6 +455,7 @@ hipError_t launch_mirror8_scan(const MirrorScanArgs& args, const unsigned char* 
         aq.meta = meta;
         std::memcpy(aq.q, query, sizeof(aq.q));
         launch_kernel((mirror8_scan_kernel<D, M>), dim3(grid), dim3(SCAN_THREADS), 0, st, aq);
+        if (pass_alone != nullptr) { *pass_alone = grid; return hipGetLastError(); }
         return launch_finish((mirror8_finish_kernel<D, M>), 1, st, aq);
     });
 }

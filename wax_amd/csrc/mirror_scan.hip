@@ -141,7 +141,8 @@ uint32_t mirror_masked_chunk_rows(uint32_t dims) {
 
 namespace {
 // the lone query's two launches, with or without a bitmap
-hipError_t launch_lone(const MirrorScanArgs& args, const uint32_t* bitmap, const float* query, int metric, int grid_cap, hipStream_t st) {
+hipError_t launch_lone(const MirrorScanArgs& args, const uint32_t* bitmap, const float* query, int metric, int grid_cap, hipStream_t st,
+                       int* pass_alone = nullptr) {
     return with_mirror_pass<Bf16Rows>(args.n_rows, args.dims, metric, grid_cap, [&](auto s, auto m, int grid) {
         constexpr int D = decltype(s)::DIMS, M = decltype(m)::value;
         MirrorScanArgsQ<D> aq;
@@ -150,14 +151,15 @@ hipError_t launch_lone(const MirrorScanArgs& args, const uint32_t* bitmap, const
         std::memcpy(aq.q, query, sizeof(aq.q));
         if (bitmap != nullptr) launch_kernel((mirror_scan_masked_kernel<D, M>), dim3(grid), dim3(SCAN_THREADS), 0, st, aq, bitmap);
         else launch_kernel((mirror_scan_kernel<D, M>), dim3(grid), dim3(SCAN_THREADS), 0, st, aq);
+        if (pass_alone != nullptr) { *pass_alone = grid; return hipGetLastError(); }
         return launch_finish((mirror_finish_kernel<D, M>), 1, st, aq);
     });
 }
 }  // namespace
 
-hipError_t launch_mirror_scan(const MirrorScanArgs& args, const float* query, int metric, int grid_cap, hipStream_t st) {
-    if (!mirror_launch_ok(args, metric, MIRROR_MAX_K)) return hipErrorInvalidValue;
-    return launch_lone(args, nullptr, query, metric, grid_cap, st);
+hipError_t launch_mirror_scan(const MirrorScanArgs& args, const float* query, int metric, int grid_cap, hipStream_t st, int* pass_alone) {
+    if (!mirror_launch_ok(args, metric, pass_alone != nullptr ? MIRROR_WIDE_MAX_K : MIRROR_MAX_K)) return hipErrorInvalidValue;
+    return launch_lone(args, nullptr, query, metric, grid_cap, st, pass_alone);
 }
 
 hipError_t launch_mirror_scan_masked(const MirrorScanArgs& args, const uint32_t* bitmap, const float* query, int metric, int grid_cap, hipStream_t st) {

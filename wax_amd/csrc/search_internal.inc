@@ -280,8 +280,10 @@ static bool mirror8_eligible(wax_hip_engine* e, int k_eff) {
 // The decision for one eligible query, made once at its submit (it counts): not while the breaker holds; at once on a code mirror that
 // is valid or only lacks appended rows; a stale or missing one is rebuilt by the third query in a row since the last mutation that
 // wanted it — the first two take bf16.
-static bool mirror8_take(wax_hip_engine* e, int k_eff) {
-    if (!mirror8_eligible(e, k_eff)) return false;
+static bool mirror8_take_now(wax_hip_engine* e);
+static bool mirror8_take(wax_hip_engine* e, int k_eff) { return mirror8_eligible(e, k_eff) && mirror8_take_now(e); }
+// ... the breaker and the state of the codes alone (wax_hip_search_wide in auto mode: its k is beyond MIRROR8_MAX_K by design)
+static bool mirror8_take_now(wax_hip_engine* e) {
     {
         std::unique_lock<std::mutex> bg(e->breaker_mu);
         if (e->breaker_hold > 0) { --e->breaker_hold; return false; }
@@ -319,7 +321,10 @@ static bool mirror8_ready(wax_hip_engine* e, hipStream_t st, uint64_t nq) {
 // memory). *took = false: the mirror could not be prepared (allocation, conversion launch) and nothing was enqueued — the caller takes
 // the f32 scan; a query never fails because of the mirror. Same chain and timing semantics as the fused f32 branch of enqueue_scan:
 // "time_kernels" 2 binds the event pair to the mirror_scan_kernel dispatch, 1 brackets the two launches.
-int enqueue_mirror_scan(wax_hip_engine* e, Slot* s, const float* query, float q_norm, int k_eff, int tk_mode, bool* took, bool want8 = false) {
+// wide != nullptr (wax_hip_search_wide; k_eff up to MIRROR_WIDE_MAX_K): the pass alone — the narrow finish is not enqueued, *wide = the
+// pass's arguments with its lists counted, for enqueue_mirror_wide behind it.
+int enqueue_mirror_scan(wax_hip_engine* e, Slot* s, const float* query, float q_norm, int k_eff, int tk_mode, bool* took, bool want8 = false,
+                        MirrorScanArgs* wide = nullptr) {
     *took = false;
     BatchMirror& b = e->batch;
     const bool use8 = want8 && mirror8_ready(e, s->stream, 1);
@@ -361,10 +366,13 @@ int enqueue_mirror_scan(wax_hip_engine* e, Slot* s, const float* query, float q_
     if (ev0 && !bound) HIP_TRY(hipEventRecord(ev0, s->stream), WAX_HIP_ERR_INTERNAL, "event record");
     if (bound) launch_timing() = LaunchTiming{ev0, ev1};
     if (use8) m.mirror = nullptr;
-    const hipError_t lerr = use8 ? launch_mirror8_scan(m, b.d_c8, b.d_c8_meta, query, e->metric, (int)e->grid_blocks.load(), s->stream)
-                                 : launch_mirror_scan(m, query, e->metric, (int)e->grid_blocks.load(), s->stream);
+    int lists = 0;
+    int* const alone = wide != nullptr ? &lists : nullptr;
+    const hipError_t lerr = use8 ? launch_mirror8_scan(m, b.d_c8, b.d_c8_meta, query, e->metric, (int)e->grid_blocks.load(), s->stream, alone)
+                                 : launch_mirror_scan(m, query, e->metric, (int)e->grid_blocks.load(), s->stream, alone);
     launch_timing() = LaunchTiming{};
     HIP_TRY(lerr, WAX_HIP_ERR_INTERNAL, "mirror scan launch");
+    if (wide != nullptr) { *wide = m; wide->lists = lists; }
     if (ev1 && !bound) HIP_TRY(hipEventRecord(ev1, s->stream), WAX_HIP_ERR_INTERNAL, "event record");
     if (chain_guard.owns_lock()) {
         HIP_TRY(hipEventRecord(e->scan_done, s->stream), WAX_HIP_ERR_INTERNAL, "scan chain record");
@@ -382,6 +390,27 @@ int enqueue_mirror_scan(wax_hip_engine* e, Slot* s, const float* query, float q_
     e->st_searches++;
     e->st_rows += e->count;
     e->st_bytes += e->count * (use8 ? (uint64_t)e->dims + 8ull : (uint64_t)e->dims * 2ull) + (uint64_t)MIRROR_KP * e->dims * 4ull;
+    return WAX_HIP_OK;
+}
+
+// The wide finish behind a pass that enqueue_mirror_scan launched alone (mirror_wide.hip: select, re-score, finish on the slot's
+// stream). The slot's candidate and exact buffers are allocated here, once; the hits land in the slot's pinned h_hits (it holds
+// WAX_HIP_MAX_RESULTS of them), the select's report — m, the source of B, B — behind the first MIRROR_WIDE_MAX_K of them.
+static uint64_t* slot_wide_report(Slot* s) { return reinterpret_cast<uint64_t*>(s->h_hits + MIRROR_WIDE_MAX_K); }
+int enqueue_mirror_wide(wax_hip_engine* e, Slot* s, const MirrorScanArgs& pass, int c) {
+    static_assert(WAX_HIP_MAX_RESULTS >= MIRROR_WIDE_MAX_K + MIRROR_WIDE_CTL, "the slot's pinned hits hold the wide answer and its report");
+    if (s->d_wide == nullptr)
+        HIP_TRY(hipMalloc(&s->d_wide, (2 * (size_t)MIRROR_WIDE_MAX_C + MIRROR_WIDE_CTL) * sizeof(int64_t)), WAX_HIP_ERR_ALLOC,
+                "Failed to allocate the wide finish's candidate buffers");
+    MirrorWideArgs w{};
+    w.a = pass;
+    w.cand = s->d_wide;
+    w.exact = s->d_wide + MIRROR_WIDE_MAX_C;
+    w.ctl = reinterpret_cast<uint64_t*>(s->d_wide + 2 * MIRROR_WIDE_MAX_C);
+    w.report = slot_wide_report(s);
+    w.c = c;
+    HIP_TRY(launch_mirror_wide(w, s->h_query, e->metric, s->mirror8 ? 8 : 16, s->stream), WAX_HIP_ERR_INTERNAL, "wide finish launch");
+    e->st_bytes += (uint64_t)c * e->dims * 4ull;
     return WAX_HIP_OK;
 }
 

@@ -63,6 +63,7 @@ void free_slot(Slot* s) {
     if (!s) return;
     (void)hipFree(s->d_query); (void)hipHostFree(s->h_query); (void)hipFree(s->d_partials);
     (void)hipFree(s->d_hits); (void)hipHostFree(s->h_hits); (void)hipHostFree(s->h_done); (void)hipFree(s->d_dist);
+    (void)hipFree(s->d_wide);
     if (s->sw_ready) free_select_work(&s->sw);
     (void)hipEventDestroy(s->ev0); (void)hipEventDestroy(s->ev1); (void)hipEventDestroy(s->ev_done);
     delete s;

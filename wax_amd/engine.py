@@ -819,6 +819,45 @@ class HIPVectorEngine:
         raise_for_status(self._lib.wax_hip_mirror8_keys(self._h, _fp(q), _fp(keys), rows))
         return keys
 
+    WIDE_STATS = ("mirror", "certified", "candidates", "bound_source", "lists", "c", "reran_f32")
+
+    def searchWide(self, vector, topK: int, bits: int = 0, stats: bool = False):  # noqa: N802,N803
+        """search(vector, topK) for the k UnifiedSearch really sends (candidateLimit: 33 to 1 000), answered from one pass over the
+        8-bit code mirror (bits=8), the bf16 mirror (bits=16) or the engine's choice (bits=0) and the wide finish
+        (wax_hip_search_wide): (ids, scores) exactly as searchArrays returns them — an answer without its certificate is re-run on
+        the f32 scan inside the call. topK is 1 to 1 024. stats=True adds a dict of WIDE_STATS: the mirror streamed (0 = none),
+        certified, the candidates re-scored, what gave their bound (0 every row listed, 1 a full list's last key, 2 the key of
+        rank C), the workgroup lists, C, and whether the f32 scan re-ran the query."""
+        q = _as_f32(vector).reshape(-1)
+        k = int(topK)
+        hits = np.empty((max(k, 1), 2), dtype=np.int64)
+        got = ctypes.c_uint32(0)
+        words = np.zeros(8, dtype=np.uint64)
+        hits_p = hits.ctypes.data_as(ctypes.POINTER(_abi.Hit))
+        raise_for_status(self._lib.wax_hip_search_wide(self._h, _fp(q), q.size, max(min(k, 2**32 - 1), 0), int(bits), hits_p,
+                                                       ctypes.byref(got), _u64p(words)))
+        ids = np.empty(max(k, 1), dtype=np.uint64)
+        scores = np.empty(max(k, 1), dtype=np.float32)
+        n = ctypes.c_uint32(0)
+        raise_for_status(self._lib.wax_hip_hits_to_results(int(self.metric.value), hits_p, got.value, _u64p(ids), _fp(scores), ctypes.byref(n)))
+        out = (ids[:n.value].copy(), scores[:n.value].copy())
+        return out + (dict(zip(self.WIDE_STATS, (int(w) for w in words))),) if stats else out
+
+    @staticmethod
+    def mirrorWideProbe(lists, c: int):  # noqa: N802
+        """The wide finish's selection alone on made-up lists (wax_hip_mirror_wide_probe), for tests: lists int64 [n, 64] ascending,
+        padded with KEY_PAD. Returns (candidates int64 [count] as the device left them, bound, source)."""
+        keys = np.ascontiguousarray(lists, dtype=np.int64)
+        if keys.ndim != 2 or keys.shape[1] != 64:
+            raise EncodingError("mirrorWideProbe: lists must be [n, 64]")
+        out = np.empty(int(c), dtype=np.int64)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        m, src, bound = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_int64(0)
+        raise_for_status(_abi.lib().wax_hip_mirror_wide_probe(keys.ctypes.data_as(i64p), keys.shape[0], int(c), out.ctypes.data_as(i64p),
+                                                              ctypes.byref(m), ctypes.byref(bound), ctypes.byref(src)))
+        assert (out[m.value:] == _abi.KEY_PAD).all(), "padding behind the candidates"
+        return out[:m.value].copy(), int(bound.value), int(src.value)
+
 
 def searchMany(engines, queries, topK: int):  # noqa: N802,N803
     """One query each against many stores of one device in one pass (wax_hip_search_many): pair i is (engines[i], queries[i]).
