@@ -236,6 +236,15 @@ int wax_hip_search_batch(wax_hip_engine* e, const float* queries, uint32_t nq, u
 int wax_hip_search_batch_hits(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
                               wax_hip_hit* out_hits, uint32_t out_stride, uint32_t* out_counts);
 
+/* The same search for a store small enough to sit in L2 / MALL (at most 4 096 rows): every (row, query) pair is scored exactly in f32
+ * and selected in ONE kernel launch per block of up to 1 024 queries — no mirror, no certificate, no launch chain. Arguments, refusals,
+ * padding and out_counts are wax_hip_search_batch_hits', and so is the answer, bit for bit. A sharded handle, a dimension outside
+ * 64 / 128 / 256 / 384 / 512 / 768 / 1024 / 1536, top_k > 192, a larger (or empty) store and "force_general" are forwarded to
+ * wax_hip_search_batch_hits unchanged. stats_out (may be NULL) receives eight words: route (1 = the resident kernel, 0 = forwarded),
+ * launches, query blocks per launch, row shares, tile rows, queries per block, 0, 0. The call takes no tuning key and adds no counter. */
+int wax_hip_search_batch_resident(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
+                                  wax_hip_hit* out_hits, uint32_t out_stride, uint32_t* out_counts, uint64_t* stats_out);
+
 /* Device-resident form of the same search: d_queries is nq x dims f32 in HBM on the engine's device (embeddings that
  * were produced on the GPU never bounce through the host), d_out_hits receives nq rows of out_stride hits in HBM
  * (ascending key, padded). Blocking. `stream` (a hipStream_t, NULL = the null stream) is the stream whose earlier

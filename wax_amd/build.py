@@ -15,11 +15,13 @@ ROOT = os.path.dirname(_HERE)
 CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libwaxhip.so")
-SOURCES = ["kernels.hip", "mirror_scan.hip", "mirror8_scan.hip", "mirror_wide.hip", "multiscan.hip", "batch.hip", "filter.hip", "predicate.hip", "rrf.hip", "compact.hip", "timeline.hip", "grouped.hip", "terms.hip", "engine.hip"]
-HEADERS = ["common.h", "topk.h", "row_math.h", "kernels.h", "mirror_pass.h", "mirror_finish.h", "mirror8_layout.h", "row_columns.h", "derived_rows.h", "work_pool.h", "rw_lock.h", "shard_workers.h", "id_map.h", "shard_layout.h", "shard_merge.h", "multiscan_body.inc", "engine_types.inc", "store_internal.inc", "search_internal.inc", "batch_host.inc", "api_store.inc",
-           "api_search.inc", "api_wide.inc", "api_batch.inc", "api_shard.inc", "api_fusion_filter.inc", "api_predicate.inc", "filter_host.inc", "search_many.inc", "api_timeline.inc", "api_grouped.inc", "api_terms.inc", "codec.inc", "tuning.inc", "sharded.inc",
+SOURCES = ["kernels.hip", "mirror_scan.hip", "mirror8_scan.hip", "mirror_wide.hip", "multiscan.hip", "batch_resident.hip", "batch.hip", "filter.hip", "predicate.hip", "rrf.hip", "compact.hip", "timeline.hip", "grouped.hip", "terms.hip", "engine.hip"]
+HEADERS = ["common.h", "topk.h", "row_math.h", "reduce_scatter.h", "kernels.h", "mirror_pass.h", "mirror_finish.h", "mirror8_layout.h", "row_columns.h", "derived_rows.h", "work_pool.h", "rw_lock.h", "shard_workers.h", "id_map.h", "shard_layout.h", "shard_merge.h", "multiscan_body.inc", "engine_types.inc", "store_internal.inc", "search_internal.inc", "batch_host.inc", "api_store.inc",
+           "api_search.inc", "api_wide.inc", "api_batch.inc", "api_batch_resident.inc", "api_shard.inc", "api_fusion_filter.inc", "api_predicate.inc", "filter_host.inc", "search_many.inc", "api_timeline.inc", "api_grouped.inc", "api_terms.inc", "codec.inc", "tuning.inc", "sharded.inc",
            os.path.join(ROOT, "include", "wax_hip.h")]
 ARCH = "gfx950"
+# per-unit flags: the resident batch's float4 fma chains are compiled to scalar v_fma_f32 (no packed-f32 instructions in this unit)
+UNIT_FLAGS = {"batch_resident.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc() -> str:
@@ -65,7 +67,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
             except OSError:
                 ver = ""
             import hashlib
-            stamp = hashlib.sha256((ver + "\n" + " ".join(flags)).encode()).hexdigest()
+            stamp = hashlib.sha256((ver + "\n" + " ".join(flags) + repr(sorted(UNIT_FLAGS.items()))).encode()).hexdigest()
             stamp_path = os.path.join(obj_dir, ".stamp")
             try:
                 stale = open(stamp_path).read().strip() != stamp
@@ -83,7 +85,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
                 path = os.path.join(CSRC, src)
                 if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(path), hdr_t):
                     return obj
-                cmd = [_hipcc()] + flags + ["-c", path, "-o", obj + ".tmp"]
+                cmd = [_hipcc()] + flags + UNIT_FLAGS.get(src, []) + ["-c", path, "-o", obj + ".tmp"]
                 if verbose:
                     print(" ".join(cmd), file=sys.stderr)
                 subprocess.run(cmd, check=True)

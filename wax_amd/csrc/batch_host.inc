@@ -244,6 +244,7 @@ void free_bctx(BatchCtx* c) {
     (void)hipFree(c->d_tile_max); (void)hipFree(c->d_hits);
     (void)hipHostFree(c->h_hits); (void)hipHostFree(c->h_cert); (void)hipFree(c->d_cert); (void)hipHostFree(c->h_qnorm); (void)hipHostFree(c->h_qlist);
     (void)hipFree(c->d_qlist); (void)hipHostFree(c->h_fnorm); (void)hipFree(c->d_fnorm); (void)hipFree(c->d_mpart); (void)hipFree(c->d_rescue); (void)hipFree(c->d_rescue_exact); (void)hipHostFree(c->h_live);
+    (void)hipFree(c->d_rpart); (void)hipFree(c->d_rarrive);
     if (c->ev_in) (void)hipEventDestroy(c->ev_in);
     if (c->ev_g0) (void)hipEventDestroy(c->ev_g0);
     if (c->ev_g1) (void)hipEventDestroy(c->ev_g1);

@@ -59,6 +59,7 @@ using namespace wax;
 //   api_search.inc         C ABI: search_submit / search_collect / search, result capacity; the routing of predicate tickets
 //   api_wide.inc           C ABI: wax_hip_search_wide — one blocking query for k up to 1 024 from a mirror pass and the wide finish (mirror_wide.hip) — and wax_hip_mirror_wide_probe
 //   api_batch.inc          C ABI: search_batch[_hits], the device-resident and ticketed batched entry points
+//   api_batch_resident.inc C ABI: wax_hip_search_batch_resident — search_batch_hits' answer for a store that sits in L2, one launch per 1 024 queries (batch_resident.hip; DESIGN 4.4, "The resident batch")
 //   api_shard.inc          C ABI: the one-rank-per-GPU entry points (set_row_base, search_shard_device, merge_hits_device, merge_batch_hits_device, hits_to_results)
 //   api_fusion_filter.inc  C ABI: reciprocal-rank fusion
 //   api_predicate.inc      C ABI: per-row attributes (set / get) and their device columns
@@ -79,6 +80,7 @@ using namespace wax;
 #include "api_search.inc"
 #include "api_wide.inc"
 #include "api_batch.inc"
+#include "api_batch_resident.inc"
 #include "api_shard.inc"
 #include "api_fusion_filter.inc"
 #include "api_predicate.inc"

@@ -270,6 +270,10 @@ struct BatchCtx {
     uint32_t* h_cert = nullptr;          // pinned [cert_cap]
     uint32_t* d_cert = nullptr;          // device [cert_cap]: the finish kernel's flags for the device-side retry kernel
     float* h_qnorm = nullptr;            // pinned [cert_cap]: exact norms (the exact-path fallback needs them on the host)
+    // resident batched search (batch_resident.hip): per-(query, share) partial lists; one arrival counter per query block, zero between launches
+    int64_t* d_rpart = nullptr;          // [query slots of a launch][shares][k]
+    uint64_t rpart_cap = 0;
+    uint32_t* d_rarrive = nullptr;       // [RESIDENT_MAX_Q / 16]
 };
 
 struct ShardedState;   // sharded.inc: the multi-GPU handle's state (null for a single-device engine)

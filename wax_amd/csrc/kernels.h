@@ -315,6 +315,25 @@ struct ScanPoolArgs {
     ScanMultiArgs a;       // queries, qlist, q_norm, partials, dims, k, item_group; store / n_rows / row_base / nq come from the group
     const PoolGroup* pool;
 };
+// Resident batched search (batch_resident.hip): one launch scores EVERY (row, query) pair of a store that sits in L2 exactly and
+// finishes in the kernel. Grid = shares (x) x blocks of 16 queries (y); the last workgroup of a query block to arrive
+// (arrive[block], left at zero) merges the block's lists and writes out_stride hits per query.
+constexpr uint32_t RESIDENT_MAX_Q = 1024;   // queries per launch
+struct ResidentArgs {
+    const float* store;      // [n_rows][dims]
+    const float* queries;    // [nq][dims]
+    const float* q_norm;     // [nq] (query_norm's)
+    const uint64_t* ids;     // frame ids by local row (may be null)
+    int64_t* partials;       // [blocks * 16][shares][k]
+    uint32_t* arrive;        // [blocks], zero on entry and on exit
+    wax_hip_hit* out;        // [nq][out_stride]
+    uint32_t n_rows, row_base, nq, k, out_stride;
+};
+bool batch_resident_dims(uint32_t dims);                                   // row_math.h's table
+uint32_t batch_resident_tile_rows(uint32_t dims);                          // T
+uint32_t batch_resident_shares(uint32_t blocks, int k, uint32_t cus);      // row shares of a launch of `blocks` query blocks
+hipError_t launch_batch_resident(const ResidentArgs& a, uint32_t dims, int metric, uint32_t shares, hipStream_t stream);
+
 bool scan_multi_dims(uint32_t dims);                    // dims the kernel is specialised for (= launch_scan's table)
 uint32_t scan_multi_group(uint32_t dims, int k);        // queries per launch (0: not served — k > 192, other dims, lists too large for LDS)
 int scan_multi_grid(uint32_t n_rows, uint32_t dims, int grid_cap);   // workgroups launch_scan_multi will use

@@ -547,6 +547,46 @@ class HIPVectorEngine:
         raise_for_status(rc)
         return ids, scores, counts
 
+    RESIDENT_STATS = ("route", "launches", "query_blocks", "row_shares", "tile_rows", "queries_per_block")
+
+    def searchBatchResident(self, vectors, topK: int, stats: bool = False):  # noqa: N802,N803
+        """searchBatch(vectors, topK) for a store that sits in L2 (wax_hip_search_batch_resident): every (row, query) pair scored
+        exactly in f32 and selected in one launch per 1 024 queries. Returns (ids, scores, counts) exactly as searchBatch does;
+        a sharded handle, a dimension outside the specialised table, topK > 192 and a store above the resident limit are
+        forwarded to searchBatch's path. stats=True adds a dict of RESIDENT_STATS: route (1 = the resident kernel, 0 =
+        forwarded), launches, query blocks per launch, row shares, tile rows, queries per block."""
+        qs = _as_f32(vectors)
+        if qs.ndim != 2:
+            raise EncodingError("searchBatchResident: vectors must be [nq, dims]")
+        nq, width = qs.shape
+        kcap = max(1, min(clampTopK(topK), max(self.count, 1)))
+        hits = np.empty((nq, kcap, 2), dtype=np.int64)
+        counts = np.zeros(nq, dtype=np.uint32)
+        words = np.zeros(8, dtype=np.uint64)
+        hit_p = ctypes.POINTER(_abi.Hit)
+        rc = self._lib.wax_hip_search_batch_resident(self._h, _fp(qs), nq, width, int(topK), hits.ctypes.data_as(hit_p), kcap,
+                                                     counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), _u64p(words))
+        raise_for_status(rc)
+        ids = np.zeros((nq, kcap), dtype=np.uint64)
+        scores = np.zeros((nq, kcap), dtype=np.float32)
+        metric, n = int(self.metric.value), ctypes.c_uint32(0)
+        # wax_hip_hits_to_results drops padding and non-finite distances and closes the gaps: one call converts the whole block when
+        # no row has any (every converted hit then sits where its row expects it), else row by row
+        if nq:
+            raise_for_status(self._lib.wax_hip_hits_to_results(metric, hits.ctypes.data_as(hit_p), nq * kcap, _u64p(ids), _fp(scores),
+                                                               ctypes.byref(n)))
+        if n.value == nq * kcap:
+            counts[:] = kcap
+        else:
+            ids[:], scores[:] = 0, 0
+            for q in range(nq):
+                raise_for_status(self._lib.wax_hip_hits_to_results(metric, hits[q].ctypes.data_as(hit_p), kcap, _u64p(ids[q]),
+                                                                   _fp(scores[q]), ctypes.byref(n)))
+                counts[q] = n.value
+                ids[q, n.value:], scores[q, n.value:] = 0, 0
+        out = (ids, scores, counts)
+        return out + (dict(zip(self.RESIDENT_STATS, (int(w) for w in words))),) if stats else out
+
     def searchBatchFiltered(self, vectors, topK: int, frameIds=None, minScore=None, timeRange=None, denyFlags=0):  # noqa: N802,N803
         """searchFiltered for a batch (wax_hip_search_batch_filtered / wax_hip_search_batch_predicate): `frameIds` is None or a
         length-nq sequence whose entries are None (no list) or an iterable of frame ids; `minScore` is None, one float, or a length-nq
