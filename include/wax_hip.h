@@ -495,6 +495,23 @@ int wax_hip_search_batch_predicate(wax_hip_engine* e, const float* queries, uint
                                    const float* min_scores, const wax_hip_row_predicate* preds,
                                    uint64_t* out_ids, float* out_scores, uint32_t out_stride, uint32_t* out_counts);
 
+/* A batch under ONE frame filter (FrameFilter's flag exclusions and SearchRequest.timeRange as wax_hip_row_predicate; the default
+ * filter of every Wax search is deny_flags = 0b111): row q of the answer is row q of wax_hip_search_batch_predicate with `pred` given
+ * for every query and no allow-list — ids, scores, counts and padding, bit for bit. The bf16 mirror is streamed ONCE per 256 queries
+ * under the predicate's row bitmap (v_mfma_f32_32x32x16_bf16; 32-row tiles without a passing row are neither loaded nor scored), the
+ * best 128 listed rows of each query are re-scored exactly in f32, and a query is released only under the certificate that no other
+ * passing row can reach its top k; a query that is not certified is re-run inside the call on the exact route of one filtered query.
+ * min_scores (may be NULL; NaN = no cut) holds one cut per query, applied to the exact scores. Forwarded to
+ * wax_hip_search_batch_predicate unchanged: a sharded handle, L2, dims other than 384 / 768, top_k > 32, an empty store, a store
+ * without attributes, an empty predicate (pred NULL included), and a call that finds all four bitmap entries held by tickets.
+ * stats_out (may be NULL) receives eight words: route (1 = the masked pass, 0 = forwarded), queries certified, queries re-run exactly,
+ * rows passing the predicate, workgroups of the pass, candidates re-scored per query, tiles skipped, 0. grid = 0 lets the call choose
+ * the row shares (compute units / query blocks); grid > 0 asks for that many (at most one per 32-row tile). The results come as ids
+ * and scores, not as wax_hip_hit rows: the forwarded call and the re-runs produce those. No tuning key and no counter is added. */
+int wax_hip_search_batch_masked(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
+                                const wax_hip_row_predicate* pred, const float* min_scores, uint64_t* out_ids, float* out_scores,
+                                uint32_t out_stride, uint32_t* out_counts, uint64_t* stats_out, int32_t grid);
+
 /* ---- the timeline lane ------------------------------------------------------------------------------------------ *
  * Wax.timeline(TimelineQuery) (TimelineQuery.swift:38-53) is the third ranked id list UnifiedSearch fuses (UnifiedSearch.swift:181-194,
  * with limit = max(candidateLimit, timelineFallbackLimit): 30 to 1 000): the `limit` newest (or oldest) frames that pass after /

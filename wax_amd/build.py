@@ -15,13 +15,14 @@ ROOT = os.path.dirname(_HERE)
 CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libwaxhip.so")
-SOURCES = ["kernels.hip", "mirror_scan.hip", "mirror8_scan.hip", "mirror_wide.hip", "multiscan.hip", "batch_resident.hip", "batch.hip", "filter.hip", "predicate.hip", "rrf.hip", "compact.hip", "timeline.hip", "grouped.hip", "terms.hip", "engine.hip"]
+SOURCES = ["kernels.hip", "mirror_scan.hip", "mirror8_scan.hip", "mirror_wide.hip", "multiscan.hip", "batch_resident.hip", "batch_masked.hip", "batch.hip", "filter.hip", "predicate.hip", "rrf.hip", "compact.hip", "timeline.hip", "grouped.hip", "terms.hip", "engine.hip"]
 HEADERS = ["common.h", "topk.h", "row_math.h", "reduce_scatter.h", "kernels.h", "mirror_pass.h", "mirror_finish.h", "mirror8_layout.h", "row_columns.h", "derived_rows.h", "work_pool.h", "rw_lock.h", "shard_workers.h", "id_map.h", "shard_layout.h", "shard_merge.h", "multiscan_body.inc", "engine_types.inc", "store_internal.inc", "search_internal.inc", "batch_host.inc", "api_store.inc",
-           "api_search.inc", "api_wide.inc", "api_batch.inc", "api_batch_resident.inc", "api_shard.inc", "api_fusion_filter.inc", "api_predicate.inc", "filter_host.inc", "search_many.inc", "api_timeline.inc", "api_grouped.inc", "api_terms.inc", "codec.inc", "tuning.inc", "sharded.inc",
+           "api_search.inc", "api_wide.inc", "api_batch.inc", "api_batch_resident.inc", "api_batch_masked.inc", "api_shard.inc", "api_fusion_filter.inc", "api_predicate.inc", "filter_host.inc", "search_many.inc", "api_timeline.inc", "api_grouped.inc", "api_terms.inc", "codec.inc", "tuning.inc", "sharded.inc",
            os.path.join(ROOT, "include", "wax_hip.h")]
 ARCH = "gfx950"
-# per-unit flags: the resident batch's float4 fma chains are compiled to scalar v_fma_f32 (no packed-f32 instructions in this unit)
-UNIT_FLAGS = {"batch_resident.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# per-unit flags: the resident batch's and the masked batch's float4 fma chains are compiled to scalar v_fma_f32 (no packed-f32 instructions in these units)
+_NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+UNIT_FLAGS = {"batch_resident.hip": _NO_PACKED_F32, "batch_masked.hip": _NO_PACKED_F32}
 
 
 def _hipcc() -> str:

@@ -334,6 +334,39 @@ uint32_t batch_resident_tile_rows(uint32_t dims);                          // T
 uint32_t batch_resident_shares(uint32_t blocks, int k, uint32_t cus);      // row shares of a launch of `blocks` query blocks
 hipError_t launch_batch_resident(const ResidentArgs& a, uint32_t dims, int metric, uint32_t shares, hipStream_t stream);
 
+// Masked batch pass (batch_masked.hip; DESIGN 4.5, "The masked batch pass"): a batch of queries under ONE row bitmap in one bf16 MFMA
+// pass over the mirror — grid = row shares (x) x blocks of BM_QUERIES queries (y), 8 waves of 32 register-resident queries — and one
+// finish workgroup per query (merge, exact re-score, certificate). Cosine / dot at 384-d and 768-d.
+constexpr uint32_t BM_QUERIES = 256;        // queries per workgroup of the pass: the mirror is read once per 256 queries
+constexpr int BM_LIST = 32;                 // keys published per (query, share): two half-wave lists of 16
+constexpr int BM_CAND = 128;                // candidates the finish re-scores per query
+constexpr int BM_MAX_K = 32;                // largest k the pass answers
+struct BatchMaskedArgs {
+    const unsigned short* mirror;   // [n_rows][dims] bf16 (BatchMirror::d_cb: whole 32-row tiles are readable behind the last row)
+    const unsigned short* qf;       // [nq_pad] queries in MFMA fragment order (GemmArgs::qf; rows [nq, nq_pad) zero)
+    const uint32_t* bitmap;         // [ceil(n_rows / 32)] one bit per row, bits of rows >= n_rows clear (attr_mask_kernel's)
+    int64_t* lists;                 // [nq_pad][shares][BM_LIST] approximate keys, KEY_PAD-padded, unsorted
+    int64_t* bounds;                // [nq_pad][shares][2] per half-wave list: every passing row it does not hold has a key above this (KEY_PAD: it holds them all)
+    uint32_t* skipped;              // [nq_pad / BM_QUERIES][shares] tiles the workgroup neither loaded nor scored
+    uint32_t n_rows, row_base, dims, nq_pad, shares;
+};
+struct BatchMaskedFinishArgs {
+    const int64_t* lists;           // the pass's
+    const int64_t* bounds;
+    const float* store;             // [n_rows][dims] f32
+    const float* queries;           // [nq][dims] f32
+    const float* q_norm;            // [nq] exact norms (batch_prep_kernel's)
+    const float* eps;               // [nq] |approximate - exact distance| bound from the mirror's measured error norms (batch_prep_kernel's)
+    const uint64_t* ids;            // frame ids by local row (may be null)
+    wax_hip_hit* hits;              // [nq][k]
+    uint32_t* certified;            // [nq] 1 = the hits are the exact route's, 0 = re-run the query there
+    uint32_t n_rows, row_base, dims, nq, shares;
+    int32_t k;
+};
+bool batch_masked_dims(uint32_t dims, int metric);
+hipError_t launch_batch_masked(const BatchMaskedArgs& a, int metric, hipStream_t stream);              // 1 <= shares <= ceil(n_rows / 32)
+hipError_t launch_batch_masked_finish(const BatchMaskedFinishArgs& a, int metric, hipStream_t stream);   // 1 <= k <= BM_MAX_K
+
 bool scan_multi_dims(uint32_t dims);                    // dims the kernel is specialised for (= launch_scan's table)
 uint32_t scan_multi_group(uint32_t dims, int k);        // queries per launch (0: not served — k > 192, other dims, lists too large for LDS)
 int scan_multi_grid(uint32_t n_rows, uint32_t dims, int grid_cap);   // workgroups launch_scan_multi will use

@@ -629,6 +629,43 @@ class HIPVectorEngine:
         raise_for_status(rc)
         return ids, scores, counts
 
+    MASKED_STATS = ("route", "certified", "rerun", "passing_rows", "workgroups", "candidates", "tiles_skipped")
+
+    def searchBatchMasked(self, vectors, topK: int, timeRange=None, denyFlags: int = 0, minScore=None, stats: bool = False,  # noqa: N802,N803
+                          grid: int = 0):
+        """searchBatchFiltered(vectors, topK, timeRange=..., denyFlags=..., minScore=...) for ONE row predicate shared by the whole
+        batch (wax_hip_search_batch_masked): the bf16 mirror is streamed once per 256 queries under the predicate's row bitmap, the
+        candidates are re-scored exactly, and a query that does not certify is re-run exactly inside the call — the answer is
+        searchBatchFiltered's, bit for bit, in the same (ids, scores, counts) arrays. `timeRange` is None or one (after | None,
+        before | None) tuple, `denyFlags` one mask; `minScore` is None, one float, or one per query (None entries: no cut). A sharded
+        handle, L2, dimensions other than 384 / 768, topK > 32, an empty store, a store without attributes and an empty predicate
+        are forwarded to searchBatchFiltered's call. stats=True adds a dict of MASKED_STATS (route 1 = the masked pass, 0 =
+        forwarded); grid > 0 asks for that many row shares instead of the default."""
+        qs = _as_f32(vectors)
+        if qs.ndim != 2:
+            raise EncodingError("searchBatchMasked: vectors must be [nq, dims]")
+        nq, width = qs.shape
+        kcap = max(1, min(clampTopK(topK), max(self.count, 1)))
+        ids = np.zeros((nq, kcap), dtype=np.uint64)
+        scores = np.zeros((nq, kcap), dtype=np.float32)
+        counts = np.zeros(nq, dtype=np.uint32)
+        cuts = None
+        if minScore is not None:
+            if np.ndim(minScore) == 0:
+                cuts = np.full(nq, float(minScore), dtype=np.float32)
+            else:
+                if len(minScore) != nq:
+                    raise EncodingError("searchBatchMasked: minScore must hold one entry per query")
+                cuts = np.array([np.nan if m is None else float(m) for m in minScore], dtype=np.float32)
+        pred = ticket_predicate(timeRange, denyFlags, who="searchBatchMasked")
+        words = np.zeros(8, dtype=np.uint64)
+        rc = self._lib.wax_hip_search_batch_masked(self._h, _fp(qs), nq, width, int(max(min(topK, 2**31 - 1), -2**31)), ctypes.byref(pred),
+                                                   None if cuts is None else _fp(cuts), _u64p(ids), _fp(scores), kcap,
+                                                   counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), _u64p(words), int(grid))
+        raise_for_status(rc)
+        out = (ids, scores, counts)
+        return out + (dict(zip(self.MASKED_STATS, (int(w) for w in words))),) if stats else out
+
     def searchBatchTerms(self, vectors, topK: int, requiredTerms, frameIds=None, minScore=None, timeRange=None, denyFlags=0):  # noqa: N802,N803
         """searchBatchFiltered with searchFiltered's `requiredTerms` PER QUERY (wax_hip_search_batch_terms): None, ONE filter for all
         queries (an iterable of term ids, or TermDictionary.NO_MATCH), or a list / tuple of nq entries, each None, an iterable of ids
