@@ -512,6 +512,27 @@ int wax_hip_search_batch_masked(wax_hip_engine* e, const float* queries, uint32_
                                 const wax_hip_row_predicate* pred, const float* min_scores, uint64_t* out_ids, float* out_scores,
                                 uint32_t out_stride, uint32_t* out_counts, uint64_t* stats_out, int32_t grid);
 
+/* nq queries (1 to 1 024) of an L2 store, optionally under ONE row predicate (predicate_or_null: NULL or a predicate without a bound
+ * and without a deny bit = none), answered from the bf16 mirror: row q of the answer is wax_hip_search's for query q — under a
+ * predicate wax_hip_search_predicate's without a list and without a cut — ids, scores and count, bit for bit. ids_out and scores_out
+ * hold nq rows of wax_hip_result_capacity(top_k) entries; a row's count goes to counts_out[q] and entries behind it are not written.
+ * Up to four queries share one pass over the mirror, ceil(nq / 4) passes on one stream, each followed by its finish launch, in
+ * front of one synchronisation. The key of a row is ||q||^2 + ||v||^2 - 2 q.v^ with v^ the mirror row and ||v||^2 the f32 row's; the
+ * 64 best rows by key are re-scored exactly in f32 (the f32 scan's bits) and a query is released only under the certificate
+ * a_64 - eps > d_k, eps = 2 ||q|| max ||v - v^|| (1.001) + 3 D 2^-24 (||q|| + max ||v||)^2 + 1e-6 (1 + (||q|| + max ||v||)^2). Under a
+ * predicate the pass runs under its row bitmap: chunks (16 rows at 384-d, 8 at 768-d) without a passing row are not loaded. A query
+ * that is not certified — ties, duplicate rows, a clustered store, a NaN query, 64 or fewer passing rows — is re-run inside the call
+ * on the f32 scan (under a predicate: on the exact route of one predicate query). Forwarded to wax_hip_search /
+ * wax_hip_search_predicate query by query: a sharded handle, another metric, dims other than 384 / 768, top_k > 32, an empty store,
+ * a predicate on a store without attributes, and a call that finds all four bitmap entries held by tickets.
+ * stats_out (may be NULL) receives eight words: route (1 = the mirror passes, 0 = forwarded), passes, queries certified, queries
+ * re-run, lists of 64 keys per pass and query (the pass's workgroups), chunks skipped by all passes (from the bitmap's 16-row tile
+ * counts: exact at 384-d, a lower bound at 768-d; the kernel counts nothing), 0, 0. No tuning key and no counter is added, and no
+ * existing call is routed here. */
+int wax_hip_search_mirror_l2(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, uint32_t top_k,
+                             const wax_hip_row_predicate* predicate_or_null, uint64_t* ids_out, float* scores_out,
+                             uint32_t* counts_out, uint64_t* stats_out);
+
 /* ---- the timeline lane ------------------------------------------------------------------------------------------ *
  * Wax.timeline(TimelineQuery) (TimelineQuery.swift:38-53) is the third ranked id list UnifiedSearch fuses (UnifiedSearch.swift:181-194,
  * with limit = max(candidateLimit, timelineFallbackLimit): 30 to 1 000): the `limit` newest (or oldest) frames that pass after /

@@ -171,6 +171,21 @@ struct MirrorQueryCopies {
     uint32_t dims;
 };
 hipError_t launch_mirror_group_queries(const MirrorQueryCopies& c, int nq, hipStream_t st);
+// ---- mirror_l2.hip: up to MIRROR_MAX_NQ L2 queries in one pass over the bf16 mirror, optionally under ONE row bitmap ("L2
+// on the bf16 mirror") ----
+// The key of a row is ||q||^2 + vn2[r] - 2 q.v^ (v^ the mirror row, vn2 the f32 row's ||v||^2); everything a query owns travels in
+// MirrorMember as in a shared cosine / dot pass (MirrorMember::bitmap is not read: the bitmap is the pass's).
+struct MirrorL2Args {
+    MirrorGroupArgs g;              // a: mirror (rows unscaled), store, ids, max_bits, n_rows, row_base, dims, use_measured; m[0 .. nq)
+    const float* vn2;               // [n_rows] ||v||^2 of the f32 rows (BatchMirror::d_vn2)
+    const uint32_t* bitmap;         // nullptr = every row; else predicate.hip's (every word written, bits of rows >= n_rows clear)
+};
+bool mirror_l2_dims(uint32_t dims);
+uint32_t mirror_l2_chunk_rows(uint32_t dims);                       // rows per wave iteration, the unit of the bitmap's skip test (0: no pass at this dimension)
+int mirror_l2_grid(uint32_t n_rows, uint32_t dims, int grid_cap);   // workgroups of a pass = lists of MIRROR_KP keys per member
+// Two launches on `st`: the pass of 1 <= nq <= MIRROR_MAX_NQ members (k <= MIRROR_MAX_K each) and a finish launch of nq workgroups.
+hipError_t launch_mirror_l2(const MirrorL2Args& args, int nq, int grid_cap, hipStream_t st);
+
 // A diagnostic (wax_hip_mirror_select_probe): step (1) of mirror_finish as the finish runs it (gather_select, kway_merge where it
 // overflows) into out[0 .. MIRROR_KP), kway_merge alone on the same lists into out[MIRROR_KP .. 2 MIRROR_KP), *gathered = 1 where
 // gather_select answered. d_lists: [lists][MIRROR_KP] sorted keys, KEY_PAD-padded, 1 <= lists <= SCAN_KWAY_MERGE_GRID. One workgroup.

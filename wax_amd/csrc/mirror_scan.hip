@@ -5,8 +5,8 @@
 // get faster by reading fewer bytes. The batched path already keeps a bf16 mirror of the store in step with it (batch_host.inc:
 // cosine rows pre-normalised, rows of norm <= 1e-6 zeroed) and a rigorous bound on what its rounding can move a distance by. Two
 // launches per pass:
-//   the scan    mirror_pass (mirror_pass.h) over Bf16Rows: it streams the mirror (half the f32 bytes); the queries stay f32, mirror
-//               values widen exactly (<< 16 / & 0xffff0000). Each workgroup keeps the MIRROR_KP best APPROXIMATE keys of each query.
+//   the scan    mirror_pass (mirror_pass.h) over Bf16Rows (mirror_bf16_rows.h): it streams the mirror (half the f32 bytes); the queries
+//               stay f32, mirror values widen exactly (<< 16 / & 0xffff0000). Each workgroup keeps the MIRROR_KP best APPROXIMATE keys of each query.
 //                 mirror_scan_kernel          one query, read from the kernel arguments
 //                 mirror_scan_masked_kernel   the same under a row bitmap (a predicate search, filter_host.inc): chunks without a
 //                                             passing row are not loaded, only passing rows are offered
@@ -22,38 +22,11 @@
 //               same holds over the passing rows: eps is bounded by maxima over the whole store, the passing rows among them.
 #include <cstring>
 
+#include "mirror_bf16_rows.h"
 #include "mirror_finish.h"
 #include "mirror_pass.h"
 
 namespace wax {
-
-namespace {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// The bf16 mirror as a row format of mirror_pass: three dwordx4 (24 bf16) per lane and row, 4 row groups in flight (3 x 4 dwordx4 loads
-// per lane, as scan_kernel's 384-d form), no side data, the key an approximate distance.
-struct Bf16Rows {
-    using Vec = u32x4;
-    struct Side {};
-    static constexpr int UNROLL = 4;
-    static __device__ __forceinline__ Side side(const Side*, uint32_t) { return {}; }
-    // two bf16 in dword c -> two f32, exactly (element 2i is the low half)
-    static __device__ __forceinline__ f32x2 part(const Vec& v, int c) {
-        f32x2 r;
-        r.x = __uint_as_float(v[c] << 16);
-        r.y = __uint_as_float(v[c] & 0xffff0000u);
-        return r;
-    }
-    static __device__ __forceinline__ float start(const f32x2 (&)[3][4]) { return 0.f; }
-    template <int METRIC>
-    static __device__ __forceinline__ float key(float s, Side, float inv_qn, float) {
-        const float d = METRIC == M_COS ? 1.0f - s * inv_qn : 1.0f - s;
-        return (d != d) ? __builtin_inff() : d;
-    }
-};
-
-}  // namespace
 
 template <int DIMS, int METRIC>
 __global__ __launch_bounds__(SCAN_THREADS) void mirror_scan_kernel(MirrorScanArgsQ<DIMS> aq) {
