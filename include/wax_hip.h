@@ -533,6 +533,27 @@ int wax_hip_search_mirror_l2(wax_hip_engine* e, const float* queries, uint32_t n
                              const wax_hip_row_predicate* predicate_or_null, uint64_t* ids_out, float* scores_out,
                              uint32_t* counts_out, uint64_t* stats_out);
 
+/* nq queries (1 to 1 024) of a cosine or dot store at 512, 1 024 or 1 536 dimensions, optionally under ONE row predicate
+ * (predicate_or_null: NULL or a predicate without a bound and without a deny bit = none), answered from the bf16 mirror: row q of the
+ * answer is wax_hip_search's for query q — under a predicate wax_hip_search_predicate's without a list and without a cut — ids,
+ * scores and count, bit for bit. ids_out and scores_out hold nq rows of wax_hip_result_capacity(top_k) entries; a row's count goes to
+ * counts_out[q] and entries behind it are not written. Up to four queries share one pass over the mirror, ceil(nq / 4) passes on one
+ * stream, each followed by its finish launch, in front of one synchronisation. A row is split among 32 lanes (512-d, two 16-byte
+ * loads per lane) or 64 lanes (1 024-d: two loads, 1 536-d: three); the 64 best rows by approximate distance are re-scored exactly in
+ * f32 (the f32 scan's bits) and a query is released only under the certificate of the 384-d / 768-d mirror scan, a_64 - eps > d_k.
+ * Under a predicate the pass runs under its row bitmap: chunks (8 rows at 512-d, 4 at 1 024-d and 1 536-d) without a passing row are
+ * not loaded. A query that is not certified — ties, duplicate rows, a clustered store, a NaN query, 64 or fewer passing rows — is
+ * re-run inside the call on the f32 scan (under a predicate: on the exact route of one predicate query). Forwarded to wax_hip_search
+ * / wax_hip_search_predicate query by query: a sharded handle, L2, every other dimension (384 and 768 included: wax_hip_search
+ * answers them from the mirror itself), top_k > 32, an empty store, a predicate on a store without attributes, and a call that finds
+ * all four bitmap entries held by tickets.
+ * stats_out (may be NULL) receives eight words: route (1 = the mirror passes, 0 = forwarded), passes, queries certified, queries
+ * re-run, lists of 64 keys per pass and query (the pass's workgroups), chunks skipped by all passes (a lower bound from the bitmap's
+ * 16-row tile counts; the kernel counts nothing), 0, 0. No tuning key and no counter is added, and no existing call is routed here. */
+int wax_hip_search_mirror(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, uint32_t top_k,
+                          const wax_hip_row_predicate* predicate_or_null, uint64_t* ids_out, float* scores_out,
+                          uint32_t* counts_out, uint64_t* stats_out);
+
 /* ---- the timeline lane ------------------------------------------------------------------------------------------ *
  * Wax.timeline(TimelineQuery) (TimelineQuery.swift:38-53) is the third ranked id list UnifiedSearch fuses (UnifiedSearch.swift:181-194,
  * with limit = max(candidateLimit, timelineFallbackLimit): 30 to 1 000): the `limit` newest (or oldest) frames that pass after /

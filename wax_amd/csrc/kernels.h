@@ -185,6 +185,16 @@ uint32_t mirror_l2_chunk_rows(uint32_t dims);                       // rows per 
 int mirror_l2_grid(uint32_t n_rows, uint32_t dims, int grid_cap);   // workgroups of a pass = lists of MIRROR_KP keys per member
 // Two launches on `st`: the pass of 1 <= nq <= MIRROR_MAX_NQ members (k <= MIRROR_MAX_K each) and a finish launch of nq workgroups.
 hipError_t launch_mirror_l2(const MirrorL2Args& args, int nq, int grid_cap, hipStream_t st);
+// ---- mirror_dims.hip: up to MIRROR_MAX_NQ cosine or dot queries in one pass over the bf16 mirror of a 512-, 1 024- or 1 536-d store,
+// optionally under ONE row bitmap ("The mirror pass at 512, 1 024 and 1 536 dimensions") ----
+// The row's split among the lanes is the unit's own table (two or three load vectors per lane and row); every query, a lone one
+// included, is read from device memory (MirrorMember::query; MirrorMember::bitmap is not read: the bitmap is the pass's).
+bool mirror_dims_supported(uint32_t dims, int metric);
+uint32_t mirror_dims_chunk_rows(uint32_t dims);                       // rows per wave iteration, the unit of the bitmap's skip test (0: no pass at this dimension)
+int mirror_dims_grid(uint32_t n_rows, uint32_t dims, int grid_cap);   // workgroups of a pass = lists of MIRROR_KP keys per member
+// Two launches on `st`: the pass of 1 <= nq <= MIRROR_MAX_NQ members (k <= MIRROR_MAX_K each), under `bitmap` unless it is nullptr
+// (predicate.hip's: every word written, bits of rows >= n_rows clear), and a finish launch of nq workgroups.
+hipError_t launch_mirror_dims(const MirrorGroupArgs& args, const uint32_t* bitmap, int nq, int metric, int grid_cap, hipStream_t st);
 
 // A diagnostic (wax_hip_mirror_select_probe): step (1) of mirror_finish as the finish runs it (gather_select, kway_merge where it
 // overflows) into out[0 .. MIRROR_KP), kway_merge alone on the same lists into out[MIRROR_KP .. 2 MIRROR_KP), *gathered = 1 where
