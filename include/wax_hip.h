@@ -245,6 +245,18 @@ int wax_hip_search_batch_hits(wax_hip_engine* e, const float* queries, uint32_t 
 int wax_hip_search_batch_resident(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
                                   wax_hip_hit* out_hits, uint32_t out_stride, uint32_t* out_counts, uint64_t* stats_out);
 
+/* The same search for cosine and dot stores at 1 024 and 1 536 dimensions, with the filtering launch of the one-pass pipeline on the
+ * K-split register-resident GEMM: two waves share 32 queries, each keeps half of K as v_mfma_f32_32x32x16_bf16 fragments in registers,
+ * the bf16 mirror streams through LDS in 32-row K-pieces, and the halves are added before the fused selection. Sampling, thresholds,
+ * the exact f32 re-score, the certificate and the exact ladder for uncertified queries are wax_hip_search_batch_hits' own, and so are
+ * arguments, refusals, padding, out_counts and the answer, bit for bit. Forwarded to wax_hip_search_batch_hits unchanged: a sharded
+ * handle, L2, any other dimension, a store the one-pass planner does not take (below its floor, top_k beyond its limit, "batch_mode" or
+ * "batch_onepass" 0) and "force_general". stats_out (may be NULL) receives eight words: route (1 = the K-split kernel filtered, 0 =
+ * forwarded), queries, queries answered by the exact ladder, workgroups of the filtering launch, rows per tile, queries per workgroup,
+ * 0, 0. The call takes no tuning key and adds no counter. */
+int wax_hip_search_batch_dims(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
+                              wax_hip_hit* out_hits, uint32_t out_stride, uint32_t* out_counts, uint64_t* stats_out);
+
 /* Device-resident form of the same search: d_queries is nq x dims f32 in HBM on the engine's device (embeddings that
  * were produced on the GPU never bounce through the host), d_out_hits receives nq rows of out_stride hits in HBM
  * (ascending key, padded). Blocking. `stream` (a hipStream_t, NULL = the null stream) is the stream whose earlier

@@ -2,6 +2,80 @@
 // C ABI: search_batch[_hits], the device-resident and ticketed batched entry points
 
 
+// The MFMA body of search_batch_hits: mirror, upload, the slab or one-pass pipeline, the exact ladder for uncertified queries, download.
+// *ran = false: the pipelines do not take this batch (nothing was written). `limit` is the clamped top_k.
+// ks != nullptr (wax_hip_search_batch_dims): the same body with the plan's filtering kernel set to the K-split GEMM (batch_ksplit.hip).
+struct KsplitReport { uint32_t fallbacks = 0, workgroups = 0, per_group = 0; };
+static int batch_hits_mfma(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, uint64_t limit, wax_hip_hit* out_hits,
+                           uint32_t stride, uint32_t* out_counts, KsplitReport* ks, bool* ran) {
+    int brc = WAX_HIP_OK;
+    *ran = false;
+    {
+        DeviceGuard g(e->device);
+        ReadGuard rd(e);
+        { const int frc = flush_pending(e); if (frc != WAX_HIP_OK) return frc; }
+        if (e->row_base + e->count > 0x100000000ull)
+            return fail(WAX_HIP_ERR_CAPACITY, "row_base + count exceeds UInt32 row indices");
+        uint64_t k64 = limit < e->count ? limit : e->count;   // the row count this batch is answered on
+        if (k64 > stride) k64 = stride;                       // a smaller result array: the best `stride` of them
+        OnepassPlan plan{};
+        bool onepass = false;
+        // (the K-split call takes this body only where its kernel filters: a one-pass plan at its dimensions)
+        if (batch_mfma_applicable(e, dims, (int)k64, nq, &plan, &onepass) &&
+            (ks == nullptr || (onepass && batch_ksplit_dims(dims, (int)e->metric)))) {
+            if (ks != nullptr) {
+                plan.ksplit = 1;
+                uint32_t groups = 0;
+                const uint32_t nq_blk = nq < kBatchMaxQ ? nq : kBatchMaxQ;
+                batch_ksplit_geometry((nq_blk + 255u) & ~255u, (uint32_t)e->count, &groups, &ks->per_group);
+                ks->workgroups = groups * ks->per_group;
+            }
+            const int k_eff = (int)k64;
+            BatchCtx* c = nullptr;
+            brc = take_bctx(e, &c);
+            if (brc != WAX_HIP_OK) return brc;
+            brc = ensure_mirror(e, c->stream);
+            if (brc == WAX_HIP_OK) brc = bctx_reserve_host(e, c, nq, (uint64_t)nq * k_eff);
+            if (brc == WAX_HIP_OK) {
+                hipError_t err = hipMemcpyAsync(c->d_q, queries, (size_t)nq * dims * sizeof(float), hipMemcpyHostToDevice, c->stream);
+                if (err != hipSuccess) brc = fail(WAX_HIP_ERR_INTERNAL, std::string("query upload: ") + hipGetErrorString(err));
+            }
+            // The download rides behind the batch's kernels, so the one synchronisation of the finish covers it; only a
+            // batch whose rows were rewritten after it (full retries, exact path) downloads again.
+            uint32_t rewritten = 0;
+            if (brc == WAX_HIP_OK)
+                brc = batch_submit_device_locked(e, c, c->d_q, nq, k_eff, onepass ? &plan : nullptr, c->d_hits, (uint32_t)k_eff);
+            if (brc == WAX_HIP_OK) {
+                hipError_t err = hipMemcpyAsync(c->h_hits, c->d_hits, (size_t)nq * k_eff * sizeof(wax_hip_hit), hipMemcpyDeviceToHost, c->stream);
+                if (err != hipSuccess) {
+                    (void)hipStreamSynchronize(c->stream);
+                    brc = fail(WAX_HIP_ERR_INTERNAL, std::string("hits download: ") + hipGetErrorString(err));
+                }
+            }
+            if (brc == WAX_HIP_OK)
+                brc = batch_finish_device_locked(e, c, c->d_q, nq, k_eff, c->d_hits, (uint32_t)k_eff, ks ? &ks->fallbacks : nullptr, &rewritten);
+            if (brc == WAX_HIP_OK && rewritten > 0) {
+                hipError_t err = hipMemcpyAsync(c->h_hits, c->d_hits, (size_t)nq * k_eff * sizeof(wax_hip_hit), hipMemcpyDeviceToHost, c->stream);
+                if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
+                if (err != hipSuccess) brc = fail(WAX_HIP_ERR_INTERNAL, std::string("hits download: ") + hipGetErrorString(err));
+            }
+            if (brc == WAX_HIP_OK) {
+                for (uint32_t q = 0; q < nq; ++q) {
+                    std::memcpy(out_hits + (size_t)q * stride, c->h_hits + (size_t)q * k_eff, (size_t)k_eff * sizeof(wax_hip_hit));
+                    uint32_t m = 0;
+                    for (int i = 0; i < k_eff; ++i) m += c->h_hits[(size_t)q * k_eff + i].key != KEY_PAD;
+                    out_counts[q] = m;
+                }
+                *ran = true;
+            } else {
+                (void)hipStreamSynchronize(c->stream);
+            }
+            e->bctxs.release(c);
+        }
+    }
+    return brc;
+}
+
 // nq queries -> nq rows of `stride` hits (ascending key, every row KEY_PAD padded to `stride`). Chooses the MFMA path
 // when the batch is a genuine GEMM, otherwise pipelines single-query scans over the scratch-slot pool. The row
 // count is read under the lock by whichever path runs; the output layout depends on `stride` alone, so a
@@ -33,62 +107,8 @@ static int search_batch_hits_impl(wax_hip_engine* e, const float* queries, uint3
         if (!use_mfma && t_pass < t_loop && e->derived.bf16.wanted()) use_mfma = true;
     }
     if (use_mfma) {
-        int brc = WAX_HIP_OK;
         bool ran = false;
-        {
-            DeviceGuard g(e->device);
-            ReadGuard rd(e);
-            { const int frc = flush_pending(e); if (frc != WAX_HIP_OK) return frc; }
-            if (e->row_base + e->count > 0x100000000ull)
-                return fail(WAX_HIP_ERR_CAPACITY, "row_base + count exceeds UInt32 row indices");
-            uint64_t k64 = limit < e->count ? limit : e->count;   // the row count this batch is answered on
-            if (k64 > stride) k64 = stride;                       // a smaller result array: the best `stride` of them
-            OnepassPlan plan{};
-            bool onepass = false;
-            if (batch_mfma_applicable(e, dims, (int)k64, nq, &plan, &onepass)) {
-                const int k_eff = (int)k64;
-                BatchCtx* c = nullptr;
-                brc = take_bctx(e, &c);
-                if (brc != WAX_HIP_OK) return brc;
-                brc = ensure_mirror(e, c->stream);
-                if (brc == WAX_HIP_OK) brc = bctx_reserve_host(e, c, nq, (uint64_t)nq * k_eff);
-                if (brc == WAX_HIP_OK) {
-                    hipError_t err = hipMemcpyAsync(c->d_q, queries, (size_t)nq * dims * sizeof(float), hipMemcpyHostToDevice, c->stream);
-                    if (err != hipSuccess) brc = fail(WAX_HIP_ERR_INTERNAL, std::string("query upload: ") + hipGetErrorString(err));
-                }
-                // The download rides behind the batch's kernels, so the one synchronisation of the finish covers it; only a
-                // batch whose rows were rewritten after it (full retries, exact path) downloads again.
-                uint32_t rewritten = 0;
-                if (brc == WAX_HIP_OK)
-                    brc = batch_submit_device_locked(e, c, c->d_q, nq, k_eff, onepass ? &plan : nullptr, c->d_hits, (uint32_t)k_eff);
-                if (brc == WAX_HIP_OK) {
-                    hipError_t err = hipMemcpyAsync(c->h_hits, c->d_hits, (size_t)nq * k_eff * sizeof(wax_hip_hit), hipMemcpyDeviceToHost, c->stream);
-                    if (err != hipSuccess) {
-                        (void)hipStreamSynchronize(c->stream);
-                        brc = fail(WAX_HIP_ERR_INTERNAL, std::string("hits download: ") + hipGetErrorString(err));
-                    }
-                }
-                if (brc == WAX_HIP_OK)
-                    brc = batch_finish_device_locked(e, c, c->d_q, nq, k_eff, c->d_hits, (uint32_t)k_eff, nullptr, &rewritten);
-                if (brc == WAX_HIP_OK && rewritten > 0) {
-                    hipError_t err = hipMemcpyAsync(c->h_hits, c->d_hits, (size_t)nq * k_eff * sizeof(wax_hip_hit), hipMemcpyDeviceToHost, c->stream);
-                    if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
-                    if (err != hipSuccess) brc = fail(WAX_HIP_ERR_INTERNAL, std::string("hits download: ") + hipGetErrorString(err));
-                }
-                if (brc == WAX_HIP_OK) {
-                    for (uint32_t q = 0; q < nq; ++q) {
-                        std::memcpy(out_hits + (size_t)q * stride, c->h_hits + (size_t)q * k_eff, (size_t)k_eff * sizeof(wax_hip_hit));
-                        uint32_t m = 0;
-                        for (int i = 0; i < k_eff; ++i) m += c->h_hits[(size_t)q * k_eff + i].key != KEY_PAD;
-                        out_counts[q] = m;
-                    }
-                    ran = true;
-                } else {
-                    (void)hipStreamSynchronize(c->stream);
-                }
-                e->bctxs.release(c);
-            }
-        }
+        const int brc = batch_hits_mfma(e, queries, nq, dims, limit, out_hits, stride, out_counts, nullptr, &ran);
         if (brc != WAX_HIP_OK) return brc;
         if (ran) return WAX_HIP_OK;
     }

@@ -1104,6 +1104,7 @@ static hipError_t launch_rq_filter(const GemmArgs& a, hipStream_t st) {
 }
 
 hipError_t launch_batch_gemm(const GemmArgs& a, int metric, hipStream_t st) {
+    if (a.ksplit != 0u && a.dense == nullptr) return launch_batch_gemm_ks(a, metric, st);   // batch_ksplit.hip
     // fast path: queries resident in registers (needs the query block padded to a multiple of 256 rows)
     if (rq_eligible(a, metric)) {
         switch (a.dims) {

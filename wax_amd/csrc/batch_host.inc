@@ -437,6 +437,7 @@ struct OnepassPlan {
     uint32_t tile_rows, ntiles, sample_tiles, rank, seg_area;
     int kp;
     double expect;       // expected survivors per query
+    uint32_t ksplit = 0; // filtering kernel: 0 = the one launch_batch_gemm picks, 1 = the K-split register-resident GEMM (GemmArgs::ksplit)
 };
 
 // tau_sim = the j-th largest of the S sampled tiles' best similarities (pick_tau_kernel). With well-mixed rows the
@@ -598,6 +599,7 @@ int batch_enqueue(wax_hip_engine* e, BatchCtx* c, const float* d_queries, uint32
         gs.tile_max = c->d_tile_max; gs.sample_tiles = plan->sample_tiles;
         g.progress = pa.progress;
         g.dyn = pa.dyn;
+        g.ksplit = plan->ksplit;
         HIP_TRY(launch_batch_gemm_sample(gs, e->metric, st), WAX_HIP_ERR_INTERNAL, "sampling gemm launch");
         const int tk_mode = (int)e->time_kernels.load();   // read once per batch
         const bool timed = tk_mode != 0;

@@ -551,6 +551,9 @@ struct GemmArgs {
     // Diagnosis ("batch_prof_ptr"): non-null = device buffer of [grid * 8 waves][RQ_PROF_WORDS] u32 that the PROF instantiation of the
     // filtering launch fills with per-wave phase cycle counts (indices RQP_*). Never set by the product path.
     uint32_t* prof;
+    // != 0 (one-pass filtering launch, OnepassPlan::ksplit): the K-split register-resident kernel filters (batch_ksplit.hip: cosine / dot
+    // at 1 024 and 1 536 dimensions), appending to the counted list exactly as the LDS-tiled kernel does.
+    uint32_t ksplit;
 };
 // Words per wave of GemmArgs::prof and what they hold (shader cycles unless said otherwise).
 enum : int {
@@ -621,6 +624,12 @@ hipError_t launch_mirror(const float* src, uint32_t n_rows, uint32_t n_rows_padd
 hipError_t launch_mirror_rows(const float* src, const uint32_t* d_rows, uint32_t n_listed, uint32_t dims, int normalize,
                               unsigned short* dst, float* norm2, unsigned int* max_norm_bits, hipStream_t stream);
 hipError_t launch_batch_gemm(const GemmArgs& a, int metric, hipStream_t stream);
+// The K-split register-resident filtering GEMM (batch_ksplit.hip; DESIGN 4.4, "The K-split filtering GEMM"): launch_batch_gemm's
+// filtering launch with GemmArgs::ksplit set. 32-row tiles, 128 queries per workgroup, nq_pad / 128 query groups of `per_group`
+// persistent workgroups. An argument block it does not serve is an error, never another kernel.
+bool batch_ksplit_dims(uint32_t dims, int metric);
+void batch_ksplit_geometry(uint32_t nq_pad, uint32_t n_rows, uint32_t* groups, uint32_t* per_group);
+hipError_t launch_batch_gemm_ks(const GemmArgs& a, int metric, hipStream_t stream);
 
 // ---- one-pass batched pipeline (large stores; cosine / dot at the register-resident GEMM dims) ----
 // prep -> sampling GEMM -> pick_tau -> ONE filtering GEMM over the whole store -> finish. No host round trip, no slabs.

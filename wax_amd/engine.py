@@ -558,14 +558,31 @@ class HIPVectorEngine:
         qs = _as_f32(vectors)
         if qs.ndim != 2:
             raise EncodingError("searchBatchResident: vectors must be [nq, dims]")
+        return self._batch_hits_call(self._lib.wax_hip_search_batch_resident, qs, topK, self.RESIDENT_STATS if stats else None)
+
+    DIMS_STATS = ("route", "queries", "exact_ladder", "workgroups", "tile_rows", "queries_per_workgroup")
+
+    def searchBatchDims(self, vectors, topK: int, stats: bool = False):  # noqa: N802,N803
+        """searchBatch(vectors, topK) for a cosine or dot store at 1 024 or 1 536 dimensions (wax_hip_search_batch_dims): the one-pass
+        pipeline with its filtering launch on the K-split register-resident GEMM. Returns (ids, scores, counts) exactly as searchBatch
+        does; a sharded handle, L2, any other dimension and a store the one-pass planner does not take are forwarded to searchBatch's
+        path. stats=True adds a dict of DIMS_STATS: route (1 = the K-split kernel filtered, 0 = forwarded), queries, queries answered
+        by the exact ladder, workgroups, rows per tile, queries per workgroup."""
+        qs = _as_f32(vectors)
+        if qs.ndim != 2:
+            raise EncodingError("searchBatchDims: vectors must be [nq, dims]")
+        return self._batch_hits_call(self._lib.wax_hip_search_batch_dims, qs, topK, self.DIMS_STATS if stats else None)
+
+    def _batch_hits_call(self, call, qs, topK, stat_names):  # noqa: N803
+        """A batched call that fills [nq][kcap] wax_hip_hit rows and eight stats words -> (ids, scores, counts[, stats dict])."""
         nq, width = qs.shape
         kcap = max(1, min(clampTopK(topK), max(self.count, 1)))
         hits = np.empty((nq, kcap, 2), dtype=np.int64)
         counts = np.zeros(nq, dtype=np.uint32)
         words = np.zeros(8, dtype=np.uint64)
         hit_p = ctypes.POINTER(_abi.Hit)
-        rc = self._lib.wax_hip_search_batch_resident(self._h, _fp(qs), nq, width, int(topK), hits.ctypes.data_as(hit_p), kcap,
-                                                     counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), _u64p(words))
+        rc = call(self._h, _fp(qs), nq, width, int(topK), hits.ctypes.data_as(hit_p), kcap,
+                  counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), _u64p(words))
         raise_for_status(rc)
         ids = np.zeros((nq, kcap), dtype=np.uint64)
         scores = np.zeros((nq, kcap), dtype=np.float32)
@@ -585,7 +602,7 @@ class HIPVectorEngine:
                 counts[q] = n.value
                 ids[q, n.value:], scores[q, n.value:] = 0, 0
         out = (ids, scores, counts)
-        return out + (dict(zip(self.RESIDENT_STATS, (int(w) for w in words))),) if stats else out
+        return out + (dict(zip(stat_names, (int(w) for w in words))),) if stat_names else out
 
     def searchBatchFiltered(self, vectors, topK: int, frameIds=None, minScore=None, timeRange=None, denyFlags=0):  # noqa: N802,N803
         """searchFiltered for a batch (wax_hip_search_batch_filtered / wax_hip_search_batch_predicate): `frameIds` is None or a
