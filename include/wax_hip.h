@@ -257,6 +257,18 @@ int wax_hip_search_batch_resident(wax_hip_engine* e, const float* queries, uint3
 int wax_hip_search_batch_dims(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
                               wax_hip_hit* out_hits, uint32_t out_stride, uint32_t* out_counts, uint64_t* stats_out);
 
+/* The same search for L2 stores at 384 and 768 dimensions, with the filtering launch of the one-pass pipeline on the register-resident
+ * L2 GEMM: each wave keeps 32 queries as v_mfma_f32_32x32x16_bf16 fragments in registers, the bf16 mirror streams through LDS in 64- or
+ * 32-row tiles, every tile's row norms travel beside it, and the fused selection tests ||q||^2 + ||v||^2 - 2 q.v against the query's
+ * threshold. Sampling, thresholds, the exact f32 re-score, the certificate and the exact ladder for uncertified queries are
+ * wax_hip_search_batch_hits' own, and so are arguments, refusals, padding, out_counts and the answer, bit for bit. Forwarded to
+ * wax_hip_search_batch_hits unchanged: a sharded handle, cosine and dot, any other dimension, a store the one-pass planner does not
+ * take (below its floor, top_k beyond its limit, "batch_mode" or "batch_onepass" 0) and "force_general". stats_out (may be NULL)
+ * receives eight words: route (1 = the L2 kernel filtered, 0 = forwarded), queries, queries answered by the exact ladder, workgroups
+ * of the filtering launch, rows per tile, queries per workgroup, 0, 0. The call takes no tuning key and adds no counter. */
+int wax_hip_search_batch_l2(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, int32_t top_k,
+                            wax_hip_hit* out_hits, uint32_t out_stride, uint32_t* out_counts, uint64_t* stats_out);
+
 /* Device-resident form of the same search: d_queries is nq x dims f32 in HBM on the engine's device (embeddings that
  * were produced on the GPU never bounce through the host), d_out_hits receives nq rows of out_stride hits in HBM
  * (ascending key, padded). Blocking. `stream` (a hipStream_t, NULL = the null stream) is the stream whose earlier

@@ -171,6 +171,7 @@ SIGNATURES: Dict[str, tuple] = {
     "wax_hip_search_batch_hits": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, _hitp, ctypes.c_uint32, _u32p]),
     "wax_hip_search_batch_resident": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, _hitp, ctypes.c_uint32, _u32p, _u64p]),
     "wax_hip_search_batch_dims": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, _hitp, ctypes.c_uint32, _u32p, _u64p]),
+    "wax_hip_search_batch_l2": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, _hitp, ctypes.c_uint32, _u32p, _u64p]),
     "wax_hip_search_batch_masked": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(RowPredicate),
                                                    _f32p, _u64p, _f32p, ctypes.c_uint32, _u32p, _u64p, ctypes.c_int32]),
     "wax_hip_search_mirror_l2": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(RowPredicate),

@@ -4,8 +4,9 @@
 
 // The MFMA body of search_batch_hits: mirror, upload, the slab or one-pass pipeline, the exact ladder for uncertified queries, download.
 // *ran = false: the pipelines do not take this batch (nothing was written). `limit` is the clamped top_k.
-// ks != nullptr (wax_hip_search_batch_dims): the same body with the plan's filtering kernel set to the K-split GEMM (batch_ksplit.hip).
-struct KsplitReport { uint32_t fallbacks = 0, workgroups = 0, per_group = 0; };
+// ks != nullptr (wax_hip_search_batch_dims, wax_hip_search_batch_l2): the same body with the plan's filtering kernel set to ks->kernel —
+// the K-split GEMM (batch_ksplit.hip) or the register-resident L2 GEMM (batch_rq_l2.hip).
+struct KsplitReport { uint32_t fallbacks = 0, workgroups = 0, per_group = 0, kernel = BATCH_FILTER_KSPLIT, tile_rows = 32; };
 static int batch_hits_mfma(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, uint64_t limit, wax_hip_hit* out_hits,
                            uint32_t stride, uint32_t* out_counts, KsplitReport* ks, bool* ran) {
     int brc = WAX_HIP_OK;
@@ -20,14 +21,16 @@ static int batch_hits_mfma(wax_hip_engine* e, const float* queries, uint32_t nq,
         if (k64 > stride) k64 = stride;                       // a smaller result array: the best `stride` of them
         OnepassPlan plan{};
         bool onepass = false;
-        // (the K-split call takes this body only where its kernel filters: a one-pass plan at its dimensions)
+        // (a call that names its kernel takes this body only where that kernel filters: a one-pass plan at its dimensions and metric)
+        const bool l2 = ks != nullptr && ks->kernel == BATCH_FILTER_RQ_L2;
         if (batch_mfma_applicable(e, dims, (int)k64, nq, &plan, &onepass) &&
-            (ks == nullptr || (onepass && batch_ksplit_dims(dims, (int)e->metric)))) {
+            (ks == nullptr || (onepass && (l2 ? batch_rq_l2_dims(dims, (int)e->metric) : batch_ksplit_dims(dims, (int)e->metric))))) {
             if (ks != nullptr) {
-                plan.ksplit = 1;
+                plan.ksplit = ks->kernel;
                 uint32_t groups = 0;
                 const uint32_t nq_blk = nq < kBatchMaxQ ? nq : kBatchMaxQ;
-                batch_ksplit_geometry((nq_blk + 255u) & ~255u, (uint32_t)e->count, &groups, &ks->per_group);
+                if (l2) batch_rq_l2_geometry(dims, (nq_blk + 255u) & ~255u, (uint32_t)e->count, &groups, &ks->per_group, &ks->tile_rows);
+                else batch_ksplit_geometry((nq_blk + 255u) & ~255u, (uint32_t)e->count, &groups, &ks->per_group);
                 ks->workgroups = groups * ks->per_group;
             }
             const int k_eff = (int)k64;

@@ -17,6 +17,8 @@
 //     batch_gemm_rq_kernel      D in {128, 256, 384, 512, 768}, cosine / dot: queries resident in VGPRs as A fragments,
 //                               corpus tiles by LDS-DMA, survivors into per-workgroup segments (no global atomics)
 //     batch_gemm_kernel         everything else (D % 64 == 0, L2, the dense first slab): LDS-tiled 128 x 128
+//                               (batch_ksplit.hip and batch_rq_l2.hip hold the register-resident kernels a call can name instead:
+//                               GemmArgs::ksplit; batch_rq.h is what they share with batch_gemm_rq_kernel)
 //   tighten_kernel       per query: best list + survivors -> best k' (sorted), tau_q tightened (between slabs)
 //   rescore_kernel       exact f32 distance of every candidate, SAME lane mapping / summation order
 //                        as scan_kernel => bit-identical to the single-query path
@@ -27,6 +29,7 @@
 //                        candidate list overflowed) the host re-runs that query on the exact single-query path.
 #include <type_traits>
 
+#include "batch_rq.h"
 #include "kernels.h"
 #include "row_math.h"
 #include "topk.h"
@@ -34,20 +37,7 @@
 
 namespace wax {
 
-// Compile-time loop: f(std::integral_constant<int, I>{}) for I in [I0, N) — the index is a constant expression inside
-// f (inline-asm immediates need one; an unrolled loop variable is not).
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ inline unsigned short f32_to_bf16_rne(float x) {
     unsigned int b = __float_as_uint(x);
@@ -440,16 +430,6 @@ __global__ __launch_bounds__(256) void batch_gemm_kernel(GemmArgs a) {
             }
 }
 
-typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
-typedef __attribute__((address_space(3))) unsigned int lds_u32;
-typedef __attribute__((address_space(3))) float lds_f32;
-typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void global_cvoid;
-
-template <int N>
-__device__ inline void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 // ---------------------------------------------------------------------------
 // Register-resident-queries GEMM ("rq"): cosine / dot at D in {128, 256, 384, 512, 768}; the filtering launch of the one-pass
 // pipeline, its sampling launch (SAMPLE), and every slab after the first of the slab pipeline.
@@ -513,26 +493,13 @@ __global__ __launch_bounds__(512, 2) void batch_gemm_rq_kernel(GemmArgs a, uint3
     unsigned long long rt0 = 0ull;
     if constexpr (PROF) rt0 = __builtin_amdgcn_s_memrealtime();
     const unsigned int k_entry = now();
-    constexpr int KS = D / 16;                       // MFMA k-steps
-    constexpr int RB = TROWS / 32;                   // 32-row blocks per tile = accumulators per wave
-    constexpr int NF = KS * RB;                      // B fragments (= MFMAs) per wave and tile; fragment f = (k-step f / RB, block f % RB)
-    constexpr int ROW_B = D * 2 + 16;                // LDS row stride (bytes); (ROW_B / 4) % 64 == 4
-    constexpr int SEG_PER_ROW = D * 2 / 16;          // 16-byte segments per row
-    constexpr int SLOTS_PER_ROW = ROW_B / 16;        // 16-byte slots per padded row
-    constexpr int IMG_B = TROWS * ROW_B;             // padded tile image
-    constexpr int PIECES = (IMG_B + 1023) / 1024;    // 1-KB DMA pieces per tile
-    constexpr int BUF_B = PIECES * 1024;             // buffer stride (the image + slack for the last piece)
-    constexpr int PPW = (PIECES + 7) / 8;            // pieces per wave
-    constexpr int FULL_WAVES = PIECES % 8 == 0 ? 8 : PIECES % 8;   // waves below this index carry PPW pieces, the others PPW - 1
+    using T = RqTile<D, TROWS>;                      // the padded tile image and its LDS-DMA map (batch_rq.h)
+    constexpr int KS = T::KS, RB = T::RB, ROW_B = T::ROW_B, SEG_PER_ROW = T::SEG_PER_ROW, SLOTS_PER_ROW = T::SLOTS_PER_ROW;
+    constexpr int PIECES = T::PIECES, BUF_B = T::BUF_B, PPW = T::PPW, FULL_WAVES = T::FULL_WAVES;
     constexpr int PRE = NBUF - 1;                    // tiles requested ahead of the one being read
-    constexpr int RING = AHEAD + 1;
     static_assert(!(SAMPLE && SPLIT), "the sampling launch keeps the workgroup barrier");
-    static_assert(TROWS % 32 == 0 && RB >= 1 && RB <= 4, "tile = 1..4 MFMA row blocks");
-    static_assert(TROWS + 2 <= (int)BATCH_MIRROR_SLACK_ROWS, "the un-clamped requests of the last tile stay inside the mirror's slack rows");
-    static_assert(D % 64 == 0 && (ROW_B / 4) % 64 == 4, "row stride must keep ds_read_b128 conflict-free");
     static_assert(NBUF >= 2, "one tile is read while the next lands");
     static_assert(NBUF * BUF_B + 2 * 8 * 32 * 4 + 64 <= 160 * 1024, "LDS budget of one CU");
-    static_assert((RB - 1) * 32 * ROW_B + (KS - 1) * 32 < 65536, "ds_read offset field");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned int* cnt_s = reinterpret_cast<unsigned int*>(smem + NBUF * BUF_B);    // [8][32] survivors per query (this workgroup; written once, at the end)
     float* sim_s = reinterpret_cast<float*>(cnt_s + 8 * 32);                       // [8][32] conservative similarity bounds
@@ -582,16 +549,13 @@ __global__ __launch_bounds__(512, 2) void batch_gemm_rq_kernel(GemmArgs a, uint3
 
     // LDS-DMA map: wave w moves pieces w, w + 8, ...; lane l of piece P fills slot P*64 + l of the padded image (point 2 above)
     const bool full_wave = wave < FULL_WAVES;
-    constexpr uint32_t DIV_SHIFT = 18, DIV_MAGIC = ((1u << DIV_SHIFT) + SLOTS_PER_ROW - 1) / SLOTS_PER_ROW;
-    static_assert((uint64_t)(PIECES * 64) * (DIV_MAGIC * (uint64_t)SLOTS_PER_ROW - (1u << DIV_SHIFT)) < (1u << DIV_SHIFT),
-                  "magic division must be exact for every slot of a tile");
     constexpr bool CACHE_OFF = !SAMPLE && D <= 512;  // per-piece offsets in VGPRs: a request is ONE instruction
     uint32_t doff[CACHE_OFF ? PPW : 1];
     if (CACHE_OFF) {
 #pragma unroll
         for (int i = 0; i < PPW; ++i) {
             const uint32_t slot = ((uint32_t)wave + 8u * (uint32_t)i) * 64u + (uint32_t)lane;
-            doff[i] = (slot - ((slot * DIV_MAGIC) >> DIV_SHIFT)) * 16u;
+            doff[i] = T::slot_offset(slot);
         }
     }
     auto dma_tile = [&](uint32_t tile, uint32_t buf_off) {
@@ -623,7 +587,7 @@ __global__ __launch_bounds__(512, 2) void batch_gemm_rq_kernel(GemmArgs a, uint3
                         uint32_t lane_o = (uint32_t)lane;
                         asm volatile("" : "+v"(lane_o));
                         const uint32_t slot = P * 64u + lane_o;
-                        off = (slot - ((slot * DIV_MAGIC) >> DIV_SHIFT)) * 16u;
+                        off = T::slot_offset(slot);
                     }
                     // NT (one query group: every tile is read exactly once): non-temporal requests
                     __builtin_amdgcn_global_load_lds((global_cvoid*)(tbase + off), (lds_void*)(smem + buf_off + P * 1024u), 16, 0, NT ? 2 : 0);
@@ -641,36 +605,7 @@ __global__ __launch_bounds__(512, 2) void batch_gemm_rq_kernel(GemmArgs a, uint3
     f32x16 acc[RB];
     const uint32_t smem_lds = (uint32_t)(size_t)(lds_void*)smem;
     const uint32_t lane_boff = (uint32_t)(lane & 31) * (uint32_t)ROW_B + (uint32_t)(lane >> 5) * 16u;
-    // K loop. Fragment f + AHEAD is requested before MFMA f; the wait in front of MFMA f leaves at most min(AHEAD, NF - 1 - f)
-    // younger reads outstanding. Every step is pinned (sched_barrier) — hipcc otherwise hoists an MFMA over the asm wait it depends
-    // on. s_setprio 1 lets the multiplying wave win issue arbitration against its selecting partner.
-    auto mfma_tile = [&](uint32_t baddr) {
-        const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        u32x4 fb[RING];
-        static_for<0, (AHEAD < NF ? AHEAD : NF)>([&](auto F) {
-            constexpr int f = decltype(F)::value;
-            u32x4(&fbr)[RING] = fb;                  // (asm operands alone do not make a generic lambda capture)
-            const uint32_t ba = baddr;
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fbr[f % RING]) : "v"(ba), "n"((f % RB) * 32 * ROW_B + (f / RB) * 32));
-        });
-        __builtin_amdgcn_s_setprio(1);
-        __builtin_amdgcn_sched_barrier(0);
-        static_for<0, NF>([&](auto F) {
-            constexpr int f = decltype(F)::value;
-            constexpr int g = f + AHEAD;
-            u32x4(&fbr)[RING] = fb;
-            const uint32_t ba = baddr;
-            if constexpr (g < NF)
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fbr[g % RING]) : "v"(ba), "n"((g % RB) * 32 * ROW_B + (g / RB) * 32));
-            constexpr int younger = (NF - 1 - f) < AHEAD ? (NF - 1 - f) : AHEAD;
-            asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(younger) : "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            constexpr int ks = f / RB, rb = f % RB;
-            acc[rb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ks], __builtin_bit_cast(bf16x8, fbr[f % RING]), ks == 0 ? zero16 : acc[rb], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        });
-        __builtin_amdgcn_s_setprio(0);
-    };
+    auto mfma_tile = [&](uint32_t baddr) { rq_mfma_tile<KS, RB, ROW_B, AHEAD>(fa, acc, baddr); };   // the K loop (batch_rq.h)
     // Fused selection on one tile. C/D layout of the 32x32 MFMA: column = lane & 31 (corpus row of the block), row =
     // (r & 3) + 8 (r >> 2) + 4 (lane >> 5) (query of the wave). A wave's 32 queries are ITS OWN: no other wave of the workgroup selects
     // for them. Hot path: per accumulator a subtraction and a funnel shift into a per-lane pass mask, one ballot per tile; nothing set
@@ -1021,21 +956,6 @@ __global__ __launch_bounds__(512, 2) void batch_gemm_rq_kernel(GemmArgs a, uint3
     }
 }
 
-// Per-dimension geometry of the rq kernel: rows per tile (what the one-pass planner calls a tile), LDS tile buffers, read-ahead.
-// D * TROWS is 16 - 32 K elements (32 - 64 MFMAs per wave and tile); three buffers where they fit beside the neighbouring batch's
-// small kernels (a workgroup of ~100 KB leaves them a third of the CU's LDS; 150 KB does not: measured in round 3 and again in
-// round 5 at D = 384, where two buffers lose nothing), except at D = 768 where a 32-row tile is already 48.5 KB and the third
-// buffer is what lets a request stay in flight across a tile.
-// (Round 6, D = 384: 96-row tiles — 2 x 75 KB — cut 7.6 % of the cycles per row and 4 % of the Q = 1 024 kernel, but a workgroup
-// that fills the CU's LDS keeps the neighbouring batches' small kernels off it: pipelined 256-query batches +2 %, dense
-// neighbourhoods +6 %. 64 rows stay: profiles/r06/g_*.)
-// (Round 6, D = 384 with three buffers + the early waves requesting behind their K loop: +5 % cycles per tile, pipelined batches +4 ... 7 %.)
-template <int D> struct RqGeom;
-template <> struct RqGeom<128> { static constexpr int TROWS = 128, NBUF = 3, AHEAD = 3; };
-template <> struct RqGeom<256> { static constexpr int TROWS = 64, NBUF = 3, AHEAD = 3; };
-template <> struct RqGeom<384> { static constexpr int TROWS = 64, NBUF = 2, AHEAD = 3; };
-template <> struct RqGeom<512> { static constexpr int TROWS = 64, NBUF = 2, AHEAD = 3; };
-template <> struct RqGeom<768> { static constexpr int TROWS = 32, NBUF = 3, AHEAD = 3; };
 static bool rq_dims(uint32_t dims) { return dims == 128 || dims == 256 || dims == 384 || dims == 512 || dims == 768; }
 static uint32_t rq_tile_rows(uint32_t dims) { return dims == 128 ? 128u : dims == 768 ? 32u : 64u; }
 template <int D>
@@ -1104,6 +1024,7 @@ static hipError_t launch_rq_filter(const GemmArgs& a, hipStream_t st) {
 }
 
 hipError_t launch_batch_gemm(const GemmArgs& a, int metric, hipStream_t st) {
+    if (a.ksplit == BATCH_FILTER_RQ_L2 && a.dense == nullptr) return launch_batch_gemm_rq_l2(a, metric, st);   // batch_rq_l2.hip
     if (a.ksplit != 0u && a.dense == nullptr) return launch_batch_gemm_ks(a, metric, st);   // batch_ksplit.hip
     // fast path: queries resident in registers (needs the query block padded to a multiple of 256 rows)
     if (rq_eligible(a, metric)) {

@@ -437,7 +437,7 @@ struct OnepassPlan {
     uint32_t tile_rows, ntiles, sample_tiles, rank, seg_area;
     int kp;
     double expect;       // expected survivors per query
-    uint32_t ksplit = 0; // filtering kernel: 0 = the one launch_batch_gemm picks, 1 = the K-split register-resident GEMM (GemmArgs::ksplit)
+    uint32_t ksplit = 0; // filtering kernel (GemmArgs::ksplit): 0 = the one launch_batch_gemm picks, BATCH_FILTER_KSPLIT, BATCH_FILTER_RQ_L2
 };
 
 // tau_sim = the j-th largest of the S sampled tiles' best similarities (pick_tau_kernel). With well-mixed rows the

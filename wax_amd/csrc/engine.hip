@@ -61,6 +61,7 @@ using namespace wax;
 //   api_batch.inc          C ABI: search_batch[_hits], the device-resident and ticketed batched entry points
 //   api_batch_resident.inc C ABI: wax_hip_search_batch_resident — search_batch_hits' answer for a store that sits in L2, one launch per 1 024 queries (batch_resident.hip; DESIGN 4.4, "The resident batch")
 //   api_batch_dims.inc     C ABI: wax_hip_search_batch_dims — search_batch_hits' answer for cosine / dot stores at 1 024 and 1 536 dimensions with the one-pass filtering launch on the K-split register-resident GEMM (batch_ksplit.hip; DESIGN 4.4, "The K-split filtering GEMM")
+//   api_batch_l2.inc       C ABI: wax_hip_search_batch_l2 — search_batch_hits' answer for L2 stores at 384 and 768 dimensions with the one-pass filtering launch on the register-resident L2 GEMM (batch_rq_l2.hip; DESIGN 4.4, "The register-resident L2 filter")
 //   api_shard.inc          C ABI: the one-rank-per-GPU entry points (set_row_base, search_shard_device, merge_hits_device, merge_batch_hits_device, hits_to_results)
 //   api_fusion_filter.inc  C ABI: reciprocal-rank fusion
 //   api_predicate.inc      C ABI: per-row attributes (set / get) and their device columns
@@ -86,6 +87,7 @@ using namespace wax;
 #include "api_batch.inc"
 #include "api_batch_resident.inc"
 #include "api_batch_dims.inc"
+#include "api_batch_l2.inc"
 #include "api_shard.inc"
 #include "api_fusion_filter.inc"
 #include "api_predicate.inc"

@@ -551,10 +551,12 @@ struct GemmArgs {
     // Diagnosis ("batch_prof_ptr"): non-null = device buffer of [grid * 8 waves][RQ_PROF_WORDS] u32 that the PROF instantiation of the
     // filtering launch fills with per-wave phase cycle counts (indices RQP_*). Never set by the product path.
     uint32_t* prof;
-    // != 0 (one-pass filtering launch, OnepassPlan::ksplit): the K-split register-resident kernel filters (batch_ksplit.hip: cosine / dot
-    // at 1 024 and 1 536 dimensions), appending to the counted list exactly as the LDS-tiled kernel does.
+    // != 0 (one-pass filtering launch, OnepassPlan::ksplit): which register-resident kernel filters instead of the one launch_batch_gemm
+    // would pick, appending to the counted list exactly as the LDS-tiled kernel does. BATCH_FILTER_KSPLIT: the K-split kernel
+    // (batch_ksplit.hip: cosine / dot at 1 024 and 1 536 dimensions); BATCH_FILTER_RQ_L2: the L2 kernel (batch_rq_l2.hip: 384 / 768).
     uint32_t ksplit;
 };
+enum : uint32_t { BATCH_FILTER_DEFAULT = 0, BATCH_FILTER_KSPLIT = 1, BATCH_FILTER_RQ_L2 = 2 };   // GemmArgs::ksplit
 // Words per wave of GemmArgs::prof and what they hold (shader cycles unless said otherwise).
 enum : int {
     RQP_PROLOGUE = 0,       // kernel entry -> first tile hand-over (A fragments, bounds, first DMA requests landed)
@@ -630,6 +632,13 @@ hipError_t launch_batch_gemm(const GemmArgs& a, int metric, hipStream_t stream);
 bool batch_ksplit_dims(uint32_t dims, int metric);
 void batch_ksplit_geometry(uint32_t nq_pad, uint32_t n_rows, uint32_t* groups, uint32_t* per_group);
 hipError_t launch_batch_gemm_ks(const GemmArgs& a, int metric, hipStream_t stream);
+// The register-resident L2 filtering GEMM (batch_rq_l2.hip; DESIGN 4.4, "The register-resident L2 filter"): launch_batch_gemm's
+// filtering launch with GemmArgs::ksplit == BATCH_FILTER_RQ_L2. L2 at 384 (64-row tiles) and 768 dimensions (32-row tiles), 256 queries
+// per workgroup, nq_pad / 256 query groups of `per_group` persistent workgroups; needs q_n2 and v_n2. An argument block it does not
+// serve is an error, never another kernel.
+bool batch_rq_l2_dims(uint32_t dims, int metric);
+void batch_rq_l2_geometry(uint32_t dims, uint32_t nq_pad, uint32_t n_rows, uint32_t* groups, uint32_t* per_group, uint32_t* tile_rows);
+hipError_t launch_batch_gemm_rq_l2(const GemmArgs& a, int metric, hipStream_t stream);
 
 // ---- one-pass batched pipeline (large stores; cosine / dot at the register-resident GEMM dims) ----
 // prep -> sampling GEMM -> pick_tau -> ONE filtering GEMM over the whole store -> finish. No host round trip, no slabs.

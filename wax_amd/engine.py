@@ -573,6 +573,17 @@ class HIPVectorEngine:
             raise EncodingError("searchBatchDims: vectors must be [nq, dims]")
         return self._batch_hits_call(self._lib.wax_hip_search_batch_dims, qs, topK, self.DIMS_STATS if stats else None)
 
+    def searchBatchL2(self, vectors, topK: int, stats: bool = False):  # noqa: N802,N803
+        """searchBatch(vectors, topK) for an L2 store at 384 or 768 dimensions (wax_hip_search_batch_l2): the one-pass pipeline with its
+        filtering launch on the register-resident L2 GEMM. Returns (ids, scores, counts) exactly as searchBatch does; a sharded handle,
+        cosine and dot, any other dimension and a store the one-pass planner does not take are forwarded to searchBatch's path.
+        stats=True adds a dict of DIMS_STATS: route (1 = the L2 kernel filtered, 0 = forwarded), queries, queries answered by the
+        exact ladder, workgroups, rows per tile, queries per workgroup."""
+        qs = _as_f32(vectors)
+        if qs.ndim != 2:
+            raise EncodingError("searchBatchL2: vectors must be [nq, dims]")
+        return self._batch_hits_call(self._lib.wax_hip_search_batch_l2, qs, topK, self.DIMS_STATS if stats else None)
+
     def _batch_hits_call(self, call, qs, topK, stat_names):  # noqa: N803
         """A batched call that fills [nq][kcap] wax_hip_hit rows and eight stats words -> (ids, scores, counts[, stats dict])."""
         nq, width = qs.shape
