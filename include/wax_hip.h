@@ -578,6 +578,24 @@ int wax_hip_search_mirror(wax_hip_engine* e, const float* queries, uint32_t nq, 
                           const wax_hip_row_predicate* predicate_or_null, uint64_t* ids_out, float* scores_out,
                           uint32_t* counts_out, uint64_t* stats_out);
 
+/* wax_hip_search_mirror's call — same arguments, same answer bit for bit — answered from the 8-bit code mirror on the int8 matrix
+ * pipe (v_mfma_i32_16x16x64_i8): D + 8 bytes per row and pass instead of 2 D. Up to four queries share one pass, ceil(nq / 4) passes
+ * on one stream in front of one synchronisation. The codes, their 16-row tiles, the query's three digit planes and the key (a lower
+ * bound of the row's distance from the row's own err) are those of the 384-d / 768-d code mirror; the query's digits are prepared once
+ * per workgroup into LDS and a tile's codes stream through registers eight k-steps at a time. Lower bounds lie closer together at
+ * these dimensions than 64 candidates can certify: 128 candidates per query are selected under B = min(smallest last key of a full
+ * list, the listed key of rank 128), re-scored exactly in f32 (the f32 scan's bits), and a query is released only if every row was
+ * re-scored or dist(B) - slack > d_k, strict. Under a predicate the pass runs under its row bitmap: 16-row tiles without a passing row
+ * are not loaded. A query that is not certified is re-run inside the call as wax_hip_search_mirror re-runs it. Forwarded query by
+ * query: a sharded handle, L2, every other dimension (384 and 768 included), top_k > 16, an empty store, a predicate on a store
+ * without attributes, and a call that finds all four bitmap entries held by tickets. The first call builds the store's code mirror.
+ * stats_out (may be NULL) receives eight words: route (1 = the code-mirror passes, 0 = forwarded), passes, queries certified, queries
+ * re-run, lists of 64 keys per pass and query, 16-row tiles skipped by all passes (from the bitmap's tile counts), candidates per
+ * query, 0. No tuning key and no counter is added, and no existing call is routed here. */
+int wax_hip_search_mirror_codes(wax_hip_engine* e, const float* queries, uint32_t nq, uint32_t dims, uint32_t top_k,
+                                const wax_hip_row_predicate* predicate_or_null, uint64_t* ids_out, float* scores_out,
+                                uint32_t* counts_out, uint64_t* stats_out);
+
 /* ---- the timeline lane ------------------------------------------------------------------------------------------ *
  * Wax.timeline(TimelineQuery) (TimelineQuery.swift:38-53) is the third ranked id list UnifiedSearch fuses (UnifiedSearch.swift:181-194,
  * with limit = max(candidateLimit, timelineFallbackLimit): 30 to 1 000): the `limit` newest (or oldest) frames that pass after /

@@ -2,13 +2,13 @@
 """searchMirror against the loop of search calls it replaces (searchArrays; searchFiltered under a mask) on cosine stores at 512, 1 024
 and 1 536 dimensions whose f32 image is about 15 GB each, with the byte floor of the passes beside every figure.
 
-Legs: loop, mirror — alternated call by call in one process on one engine, blocking wall time per call (every call ends in a device
-synchronise), median and interquartile range of --reps per leg; np.array_equal of the two answers is asserted before any timing.
+Legs: loop, mirror, codes (searchMirror(bits=8): the 8-bit code mirror on the int8 matrix pipe) — alternated call by call in one process on one engine, blocking wall time per call (every call ends in a device
+synchronise), median and interquartile range of --reps per leg; np.array_equal of the answers is asserted before any timing.
 Masks: none, a random 15/16 of the rows, a contiguous 1/16 (flag bits). floor_us: the bf16 bytes the passes read (rows outside the
 chunks the call reports as skipped, 2 B per element, once per pass) over the stream-read rate wax_hip_time_stream_read gives in the
-same run on the same store. stats: the call's own words — how many queries certified, how many were re-run. One JSON record.
+same run on the same store; floor8_us: the same for the codes leg, D + 8 bytes per row of the 16-row tiles it reads. stats, stats8: the call's own words — how many queries certified, how many were re-run. One JSON record.
 
-    python tools/mirror_dims_bench.py --out profiles/r39/mirror_dims.json
+    python tools/mirror_dims_bench.py --out profiles/r42/mirror8_dims.json
 """
 from __future__ import annotations
 
@@ -52,6 +52,7 @@ def main():
     ap.add_argument("--nq", type=int, nargs="+", default=[1, 4, 64])
     ap.add_argument("--topk", type=int, default=10)
     ap.add_argument("--reps", type=int, default=15)
+    ap.add_argument("--masks", nargs="+", default=list(MASKS), choices=list(MASKS))
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -77,16 +78,21 @@ def main():
         gbps = rows * dims * 4 / (eng.timeStreamRead(10) * 1e-3) / 1e9      # the f32 store over its read-only pass
         for nq in args.nq:
             q = np.ascontiguousarray(queries[:nq])
-            for name, deny in MASKS.items():
+            for name, deny in ((m, MASKS[m]) for m in args.masks):
                 one = (lambda v: eng.searchFiltered(v, args.topk, denyFlags=deny)) if deny else (lambda v: eng.searchArrays(v, args.topk))
-                legs = {"loop": lambda: [one(v) for v in q], "mirror": lambda: eng.searchMirror(q, args.topk, denyFlags=deny)}
+                legs = {"loop": lambda: [one(v) for v in q], "mirror": lambda: eng.searchMirror(q, args.topk, denyFlags=deny),
+                        "codes": lambda: eng.searchMirror(q, args.topk, denyFlags=deny, bits=8)}
                 for _ in range(2):                                   # every leg warm: buffers allocated, mirror and bitmap built
-                    want, got = legs["loop"](), legs["mirror"]()
-                assert all(np.array_equal(got[0][i, :got[2][i]], w[0]) and np.array_equal(got[1][i, :got[2][i]], w[1]) for i, w in enumerate(want)), (dims, nq, name)
+                    want, got, got8 = legs["loop"](), legs["mirror"](), legs["codes"]()
+                for g in (got, got8):
+                    assert all(np.array_equal(g[0][i, :g[2][i]], w[0]) and np.array_equal(g[1][i, :g[2][i]], w[1]) for i, w in enumerate(want)), (dims, nq, name)
                 stats = eng.searchMirror(q, args.topk, denyFlags=deny, returnStats=True)[3]
+                stats8 = eng.searchMirror(q, args.topk, denyFlags=deny, returnStats=True, bits=8)[3]
                 read = stats["passes"] * rows - stats["chunks_skipped"] * CHUNK_ROWS[dims]
-                case = {"rows": rows, "dims": dims, "nq": nq, "top_k": args.topk, "mask": name, "stats": stats, "stream_read_gbps": gbps,
-                        "floor_us": read * dims * 2 / (gbps * 1e9) * 1e6, **timed(legs, args.reps, sync)}
+                read8 = stats8["passes"] * rows - stats8["tiles_skipped"] * 16
+                case = {"rows": rows, "dims": dims, "nq": nq, "top_k": args.topk, "mask": name, "stats": stats, "stats8": stats8, "stream_read_gbps": gbps,
+                        "floor_us": read * dims * 2 / (gbps * 1e9) * 1e6, "floor8_us": read8 * (dims + 8) / (gbps * 1e9) * 1e6,
+                        **timed(legs, args.reps, sync)}
                 record["cases"].append(case)
                 print(json.dumps(case), flush=True)
         eng.close()

@@ -178,6 +178,8 @@ SIGNATURES: Dict[str, tuple] = {
                                                 _u64p, _f32p, _u32p, _u64p]),
     "wax_hip_search_mirror": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(RowPredicate),
                                              _u64p, _f32p, _u32p, _u64p]),
+    "wax_hip_search_mirror_codes": (ctypes.c_int, [_engine_p, _f32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(RowPredicate),
+                                                   _u64p, _f32p, _u32p, _u64p]),
     "wax_hip_search_batch_hits_device": (ctypes.c_int, [_engine_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32,
                                                         ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "wax_hip_search_batch_submit_device": (ctypes.c_int, [_engine_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32,

@@ -70,6 +70,7 @@ using namespace wax;
 //   api_batch_masked.inc   C ABI: wax_hip_search_batch_masked — a batch under ONE row predicate: one bf16 MFMA pass over the mirror under the predicate's bitmap, a finish workgroup per query, uncertified queries re-run by filter_host.inc's single-query body (batch_masked.hip; DESIGN 4.5, "The masked batch pass")
 //   api_mirror_l2.inc      C ABI: wax_hip_search_mirror_l2 — up to 1 024 queries of an L2 store, optionally under ONE row predicate, from the bf16 mirror: passes of up to four queries under the L2 key, a finish workgroup per query, uncertified queries re-run on the f32 scan or by filter_host.inc's single-query body (mirror_l2.hip; DESIGN 4.1, "L2 on the bf16 mirror")
 //   api_mirror_dims.inc    C ABI: wax_hip_search_mirror — up to 1 024 queries of a cosine or dot store at 512, 1 024 or 1 536 dimensions, optionally under ONE row predicate, from the bf16 mirror: passes of up to four queries at the split of a row each dimension has, a finish workgroup per query, uncertified queries re-run on the f32 scan or by filter_host.inc's single-query body (mirror_dims.hip; DESIGN 4.1, "The mirror pass at 512, 1 024 and 1 536 dimensions")
+//   api_mirror8_dims.inc   C ABI: wax_hip_search_mirror_codes — the same call answered from the 8-bit code mirror on the int8 matrix pipe: passes of up to four queries with the digits in LDS and the codes streamed in pieces, 128 candidates per query selected, re-scored and certified under Mirror8Slack, uncertified queries re-run as above (mirror8_dims.hip; DESIGN 4.1, "The code mirror at 512, 1 024 and 1 536 dimensions")
 //   search_many.inc        C ABI: wax_hip_search_many[_predicate] — one query each against many stores of one device under one snapshot, the eligible pairs in one pooled launch, with a row predicate and a score cut per pair
 //   api_timeline.inc       C ABI: wax_hip_timeline[_device | _probe] — the newest / oldest passing rows by (timestamp, frame id), selected on the device from the attribute columns (TimelineQuery.swift:38-53)
 //   api_grouped.inc        C ABI: wax_hip_set_parents / get_parents, wax_hip_search_grouped, wax_hip_group_stats, wax_hip_group_probe — the parent column and the best roots by their best member, members per root (PhotoRAGOrchestrator.swift:264-317, VideoRAGOrchestrator.swift:273-417)
@@ -96,6 +97,7 @@ using namespace wax;
 #include "api_batch_masked.inc"
 #include "api_mirror_l2.inc"
 #include "api_mirror_dims.inc"
+#include "api_mirror8_dims.inc"
 #include "search_many.inc"
 #include "api_timeline.inc"
 #include "api_grouped.inc"

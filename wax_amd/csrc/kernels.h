@@ -273,9 +273,31 @@ struct alignas(16) MirrorWideArgsQ {
 };
 static_assert(sizeof(MirrorWideArgsQ<768>) <= 4096, "HIP kernel arguments are limited to 4 KB");
 // the selection alone (also wax_hip_mirror_wide_probe's): d_lists [lists][MIRROR_KP], 1 <= lists <= SCAN_KWAY_MERGE_GRID, c 1024 or 4096
-hipError_t launch_mirror_wide_select(const int64_t* d_lists, int lists, int c, int64_t* d_cand, uint64_t* d_ctl, hipStream_t st);
+// (the wide finish's counts) or MIRROR8_DIMS_C (mirror8_dims.hip's: the rank select and the compaction are generic in c).
+constexpr int MIRROR8_DIMS_C = 128;         // candidates per query behind a code-mirror pass at 512 / 1 024 / 1 536 dimensions
+// members > 1 (mirror8_dims.hip): one workgroup per member of a pass, d_lists [members][lists][MIRROR_KP], d_cand [members][c],
+// d_ctl [members][MIRROR_WIDE_CTL].
+hipError_t launch_mirror_wide_select(const int64_t* d_lists, int lists, int c, int64_t* d_cand, uint64_t* d_ctl, hipStream_t st, int members = 1);
 // the three launches on `st`; bits = 8 (Mirror8Slack) or 16 (Bf16Eps): the mirror the pass streamed
 hipError_t launch_mirror_wide(const MirrorWideArgs& w, const float* query, int metric, int bits, hipStream_t st);
+
+// ---- mirror8_dims.hip: up to MIRROR_MAX_NQ cosine or dot queries in one pass over the 8-bit code mirror of a 512-, 1 024- or 1 536-d
+// store ("The code mirror at 512, 1 024 and 1 536 dimensions") ----
+// The codes, the tiles, the digits and the key are mirror8_scan.hip's; the digits live in LDS and the codes stream through registers
+// in pieces of eight k-steps. Every query is read from device memory; a member with a MirrorMember::bitmap is offered only its
+// passing rows. 64 candidates do not certify at these dimensions: the pass is followed by mirror_wide.hip's selection of
+// MIRROR8_DIMS_C candidates per member (one workgroup each), their exact re-score and a finish under Mirror8Slack.
+struct Mirror8DimsArgs {
+    Mirror8GroupArgs ga;            // g.a: store, ids, max_bits, n_rows, row_base, dims; g.m[0 .. nq): k <= MIRROR8_MAX_K, partials back to back
+                                    // ([nq][mirror8_dims_grid()][MIRROR_KP]), hits and certified in device or pinned memory
+    int64_t* cand;                  // [nq][MIRROR8_DIMS_C] the candidates' keys
+    int64_t* exact;                 // [nq][MIRROR8_DIMS_C] their exact keys
+    uint64_t* ctl;                  // [nq][MIRROR_WIDE_CTL] the selection's control words
+};
+bool mirror8_dims_supported(uint32_t dims, int metric);
+int mirror8_dims_grid(uint32_t n_rows, uint32_t dims, int grid_cap);   // workgroups of a pass = lists of MIRROR_KP keys per member
+// Four launches on `st`: the pass of 1 <= nq <= MIRROR_MAX_NQ members, the selection, the re-score, the finish.
+hipError_t launch_mirror8_dims(const Mirror8DimsArgs& args, int nq, int metric, int grid_cap, hipStream_t st);
 
 struct ScanVariantInfo {
     int unroll;          // row groups in flight per wave iteration

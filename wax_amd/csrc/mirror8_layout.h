@@ -62,6 +62,8 @@ constexpr bool tile_is_bijection(uint32_t dims) {
 
 static_assert(lanes_hold_operand_a(384) && lanes_hold_operand_a(768), "a lane's load must hold the elements operand B holds");
 static_assert(tile_is_bijection(384) && tile_is_bijection(768), "a tile's rows and elements fill [0, 16 D) exactly once");
+static_assert(lanes_hold_operand_a(512) && lanes_hold_operand_a(1024) && lanes_hold_operand_a(1536), "the same at the wide dimensions (mirror8_dims.hip)");
+static_assert(tile_is_bijection(512) && tile_is_bijection(1024) && tile_is_bijection(1536), "the same at the wide dimensions");
 static_assert(mirror8_offset(16, 0, 384) == 16 * 384 && mirror8_offset(33, 0, 768) == 2 * 16 * 768 + 16, "tiles are 16 D bytes apart");
 static_assert(mirror8_bytes(0, 384) == 0 && mirror8_bytes(1, 384) == 16 * 384 && mirror8_bytes(17, 384) == 32 * 384, "whole tiles");
 

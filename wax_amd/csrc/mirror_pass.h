@@ -29,6 +29,9 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // The dimensions with a mirror pass: the BASELINE pair (three load vectors per lane and row divide them; kernel arguments hold the
 // query). The exact re-score takes its lanes per row from ScanShape<DIMS> (row_math.h), like every exact path.
 using MirrorDims = DimList<384, 768>;
+// The dimensions at which the 8-bit code mirror has a pass of its own besides (mirror8_dims.hip; wax_hip_search_mirror_codes only):
+// mirror8_kernel writes the codes of either list, no other caller of MirrorDims learns of these.
+using Mirror8WideDims = DimList<512, 1024, 1536>;
 
 constexpr int MIRROR_CAP = 128;                                                    // WaveTopK capacity
 constexpr int MIRROR_PASS_LDS = SCAN_WAVES * MIRROR_CAP + SCAN_WAVES + MIRROR_KP;   // int64 words per query: lists, counts, merged

@@ -66,6 +66,10 @@ __global__ __launch_bounds__(WIDE_THREADS) void mirror_wide_select_kernel(const 
     __shared__ uint32_t fill;
     const int t = (int)threadIdx.x, lane = lane_id(), wave = t >> 6;
     const int n = lists * MIRROR_KP;
+    // one workgroup per member: member b's lists, candidates and control words lie b whole sets behind the first member's
+    lists_keys += (size_t)blockIdx.x * n;
+    cand += (size_t)blockIdx.x * c;
+    ctl += (size_t)blockIdx.x * MIRROR_WIDE_CTL;
 
     // (1) the listed keys, once: key i = j * WIDE_THREADS + t, so slot 63 of every list is in a lane 63
     uint64_t u[WIDE_KEYS];
@@ -264,11 +268,11 @@ __global__ __launch_bounds__(WIDE_THREADS) void mirror_wide_finish_kernel(Mirror
     }
 }
 
-hipError_t launch_mirror_wide_select(const int64_t* d_lists, int lists, int c, int64_t* d_cand, uint64_t* d_ctl, hipStream_t st) {
+hipError_t launch_mirror_wide_select(const int64_t* d_lists, int lists, int c, int64_t* d_cand, uint64_t* d_ctl, hipStream_t st, int members) {
     if (d_lists == nullptr || d_cand == nullptr || d_ctl == nullptr || lists < 1 || lists > SCAN_KWAY_MERGE_GRID ||
-        (c != 1024 && c != MIRROR_WIDE_MAX_C))
+        (c != MIRROR8_DIMS_C && c != 1024 && c != MIRROR_WIDE_MAX_C) || members < 1 || members > MIRROR_MAX_NQ)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(mirror_wide_select_kernel, dim3(1), dim3(WIDE_THREADS), 0, st, d_lists, lists, c, d_cand, d_ctl);
+    hipLaunchKernelGGL(mirror_wide_select_kernel, dim3(members), dim3(WIDE_THREADS), 0, st, d_lists, lists, c, d_cand, d_ctl);
     return hipGetLastError();
 }
 

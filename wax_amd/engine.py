@@ -721,7 +721,9 @@ class HIPVectorEngine:
         out = (np.ascontiguousarray(ids[:, :kcap]), np.ascontiguousarray(scores[:, :kcap]), counts)
         return out + (dict(zip(self.MIRROR_L2_STATS, (int(w) for w in words))),) if stats else out
 
-    def searchMirror(self, vectors, topK: int, timeRange=None, denyFlags: int = 0, returnStats: bool = False):  # noqa: N802,N803
+    MIRROR_CODES_STATS = ("route", "passes", "certified", "rerun", "lists", "tiles_skipped", "candidates")
+
+    def searchMirror(self, vectors, topK: int, timeRange=None, denyFlags: int = 0, returnStats: bool = False, bits: int = 16):  # noqa: N802,N803
         """searchArrays(vectors[q], topK) for up to 1 024 queries of a cosine or dot store at 512, 1 024 or 1 536 dimensions — with
         `timeRange` (None or one (after | None, before | None) tuple) or `denyFlags` (one mask): searchFiltered(vectors[q], topK,
         timeRange=..., denyFlags=...) — answered from the bf16 mirror (wax_hip_search_mirror): up to four queries share a pass, under
@@ -729,7 +731,11 @@ class HIPVectorEngine:
         exactly inside the call, so row q is that search's answer bit for bit. Returns (ids[nq, kcap], scores, counts) like
         searchBatch. A sharded handle, L2, every other dimension (384 and 768 included), topK > 32, an empty store and a predicate on
         a store without attributes are forwarded to that search, query by query. returnStats=True adds a dict of MIRROR_L2_STATS
-        (route 1 = the mirror passes, 0 = forwarded)."""
+        (route 1 = the mirror passes, 0 = forwarded).
+        bits=8: the same answer from the 8-bit code mirror on the int8 matrix pipe (wax_hip_search_mirror_codes): half the bytes per
+        pass, 128 exactly re-scored candidates per query, topK <= 16 (above: forwarded); the stats are MIRROR_CODES_STATS."""
+        if bits not in (8, 16):
+            raise EncodingError("searchMirror: bits is 8 or 16")
         qs = _as_f32(vectors)
         if qs.ndim != 2:
             raise EncodingError("searchMirror: vectors must be [nq, dims]")
@@ -741,11 +747,13 @@ class HIPVectorEngine:
         counts = np.zeros(nq, dtype=np.uint32)
         pred = ticket_predicate(timeRange, denyFlags, who="searchMirror")
         words = np.zeros(8, dtype=np.uint64)
-        rc = self._lib.wax_hip_search_mirror(self._h, _fp(qs), nq, width, int(max(min(topK, 2**32 - 1), 0)), ctypes.byref(pred),
-                                             _u64p(ids), _fp(scores), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), _u64p(words))
+        call = self._lib.wax_hip_search_mirror_codes if bits == 8 else self._lib.wax_hip_search_mirror
+        rc = call(self._h, _fp(qs), nq, width, int(max(min(topK, 2**32 - 1), 0)), ctypes.byref(pred),
+                  _u64p(ids), _fp(scores), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), _u64p(words))
         raise_for_status(rc)
         out = (np.ascontiguousarray(ids[:, :kcap]), np.ascontiguousarray(scores[:, :kcap]), counts)
-        return out + (dict(zip(self.MIRROR_L2_STATS, (int(w) for w in words))),) if returnStats else out
+        names = self.MIRROR_CODES_STATS if bits == 8 else self.MIRROR_L2_STATS
+        return out + (dict(zip(names, (int(w) for w in words))),) if returnStats else out
 
     def searchBatchTerms(self, vectors, topK: int, requiredTerms, frameIds=None, minScore=None, timeRange=None, denyFlags=0):  # noqa: N802,N803
         """searchBatchFiltered with searchFiltered's `requiredTerms` PER QUERY (wax_hip_search_batch_terms): None, ONE filter for all
